@@ -13,9 +13,17 @@ token-id level (no tokenizer offline).
 
 Data-parallel replicas: every rank decodes its own batch, no collective in the data path
 (SURVEY.md §8e); value = utterances of all ranks / max-over-ranks time.  Rank 0 prints ONE JSON
-line with the `roofline` of the dominant kernel class (prefill MFMA GEMMs, timed live with HIP
-events on the launch stream) and, at N=1, the `cpu_baseline` (the oracle = CPU restatement of
-the reference, timed on this host's cores on 8 utterances of the same workload after one warm-up).
+line.  A plain run sets up, warms up, times exactly --steps steps once and prints the headline
+figure.  With --full the line also carries the `roofline` of the dominant kernel class (prefill
+MFMA GEMMs, timed live with HIP events on the launch stream), the decode-phase figures, three
+timed regions when --steps <= 20, the one-batch and overlap probes and, at N=1, the `cpu_baseline`
+(the oracle = CPU restatement of the reference, timed on this host's cores on 8 utterances of the
+same workload after one warm-up) with `parity` of the timed run's ids against it.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+
+writes what the last timed step returned as DIR/<name>.npy (rank 0's; inputs are seeded, so two
+builds can be compared output for output).
 """
 from __future__ import annotations
 
@@ -171,6 +179,25 @@ def emit(result: dict) -> None:
         os.write(_RESULT_FD, line)
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32 (float64 stays float64).  An array larger than its
+    share of DUMP_BYTES is replaced by a fixed sample of its flattened elements (seed 0, ascending indices), so the same
+    arguments always write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        x = t.detach().cpu()
+        x = (x if x.dtype == torch.float64 else x.float()).numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x)
+
+
 def launch_cmd(n: int, argv: list) -> list:
     """The command the driver itself uses for N > 1: torch.distributed.run, one rank per GPU, rendezvous on 127.0.0.1."""
     with socket.socket() as sk:
@@ -220,10 +247,15 @@ def main() -> None:
                     help="--config finetune-tinyllama: micro-batches of the accumulation window per packed forward/backward launch")
     ap.add_argument("--repeats", type=int, default=0,
                     help="timed regions of --steps steps each, run back to back; the line is the MEDIAN one (its own barriers, wall time and "
-                         "HIP-event timings), the others are listed in `repeats`.  Default: 3 when --steps <= 20 (a 0.9-s region moves by +-1.5 %% "
-                         "from run to run and box to box), else 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-overlap-probe", action="store_true")
+                         "HIP-event timings), the others are listed in `repeats`.  Default: 1; with --full 3 when --steps <= 20 (a 0.9-s region "
+                         "moves by +-1.5 %% from run to run and box to box), else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP-event roofline and phase timings inside the timed region, the repeats "
+                         "above, the one-batch and overlap probes, the CPU baseline and parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32, at most 64 MB in all; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity")
+    ap.add_argument("--no-overlap-probe", action="store_true", help="--full without the one-batch and overlap probes")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="dh_set_tuning(key, value) before the run (kernel-selection experiments; recorded in config.tuning)")
     ap.add_argument("--selftest-launch", action="store_true",
@@ -313,7 +345,7 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    phase = {}     # HIP-event time of the prefill and decode phases of the merged schedule (timed region only)
+    phase = {} if a.full else None     # HIP-event time of the prefill and decode phases of the merged schedule (timed region only)
 
     def run_merged(bs):
         """a "step" is ONE batch of B utterances; up to G consecutive steps share a decode loop"""
@@ -342,13 +374,14 @@ def main() -> None:
         pipe.warm(flat([batches[0]] * min(G, a.steps)), NEW_TOKENS, prefill_batch=B, **gen_kw)
         engs = [m.engine() for m in pipe.models]
     timed_prompts = [p for b in batches[n_warm:] for p in b]
-    n_rep = a.repeats if a.repeats > 0 else (3 if a.steps <= 20 else 1)
+    n_rep = a.repeats if a.repeats > 0 else (3 if a.full and a.steps <= 20 else 1)
     runs = []
     for _rep in range(n_rep):
         # one timed region: EXACTLY --steps steps between barrier + synchronize on both sides, MAX over ranks
-        for e in engs:
-            e.set_timing(True)          # (re)starts the HIP-event record of the kernel classes
-        phase.clear()
+        if a.full:
+            for e in engs:
+                e.set_timing(True)          # (re)starts the HIP-event record of the kernel classes
+            phase.clear()
         barrier()
         t0 = time.perf_counter()
         if a.schedule == "merged":
@@ -360,32 +393,38 @@ def main() -> None:
         barrier()
         dt = time.perf_counter() - t0
         gemm_ms = gemm_n = attn_ms = 0
-        for e in engs:
-            ms, n = e.get_timing(0)
-            gemm_ms, gemm_n = gemm_ms + ms, gemm_n + n
-            attn_ms += e.get_timing(2)[0]
-            e.set_timing(False)
+        if a.full:
+            for e in engs:
+                ms, n = e.get_timing(0)
+                gemm_ms, gemm_n = gemm_ms + ms, gemm_n + n
+                attn_ms += e.get_timing(2)[0]
+                e.set_timing(False)
         assert all(o.numel() == p.numel() + NEW_TOKENS for o, p in zip([o for out in outs for o in out], timed_prompts))
         if use_pg:
             tt = torch.tensor([dt], device="cpu" if rehearsal else dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        runs.append(dict(dt=dt, gemm_ms=gemm_ms, gemm_n=gemm_n, attn_ms=attn_ms, phase=dict(phase), outs=outs))
+        runs.append(dict(dt=dt, gemm_ms=gemm_ms, gemm_n=gemm_n, attn_ms=attn_ms, phase=dict(phase or {}), outs=outs))
     # the line describes the MEDIAN region (by wall time, the same one on every rank: dt is already the max over ranks)
     order = sorted(range(n_rep), key=lambda i: runs[i]["dt"])
     med = runs[order[(n_rep - 1) // 2]]
     dt, gemm_ms, gemm_n, attn_ms, outs = med["dt"], med["gemm_ms"], med["gemm_n"], med["attn_ms"], med["outs"]
-    phase.clear()
-    phase.update(med["phase"])
+    if a.full:
+        phase.clear()
+        phase.update(med["phase"])
+    if rank == 0 and a.dump_outputs:
+        # what a caller of generate_batch received for the last timed step: prompt + generated ids of its B utterances
+        # (ragged prompts right-padded with -1)
+        last = outs[-1]
+        ids = torch.full((len(last), max(o.numel() for o in last)), -1, dtype=torch.float32)
+        for i, o in enumerate(last):
+            ids[i, :o.numel()] = o.cpu().float()
+        dump_outputs(a.dump_outputs, {"token_ids": ids})
 
     result = None
     if rank == 0:
         utt = B * a.steps * world
         pruned = not any(kv.split("=")[0] == "23" and kv.split("=")[1] == "0" for kv in a.tune)
-        flops = gemm_flops_per_prefill(cfg, sum(p.numel() for p in timed_prompts), B * a.steps, merged_lora=wl["fp8"],
-                                       last_rows_only=pruned)
-        achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        traffic, traffic_source = pmc_traffic(a.config)   # HBM-side bytes per launch from the committed PMC passes
         result = {
             "metric": wl["metric"],
             "value": utt / dt, "unit": "utterances/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -405,14 +444,19 @@ def main() -> None:
                                           "K / V of every token are computed; results bit-equal to the all-rows form, which `--tune 23=0` runs: "
                                           "759 vs 772 utt/s on one box, DESIGN.md §5)" if pruned else "all",
                        **({"tuning": a.tune} if a.tune else {})},
-            "roofline": {"bound": "mfma", "kernel": wl["kernel"],
-                         "achieved": achieved, "peak": wl["peak"], "unit": "TFLOP/s",
-                         "frac": achieved / wl["peak"], "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "launches": gemm_n, "avg_launch_ms": gemm_ms / max(gemm_n, 1),
-                         "prefill_attention_ms_per_step": attn_ms / max(a.steps, 1)},
         }
-    if rank == 0 and phase.get("decode_steps"):
+    if rank == 0 and a.full:
+        flops = gemm_flops_per_prefill(cfg, sum(p.numel() for p in timed_prompts), B * a.steps, merged_lora=wl["fp8"],
+                                       last_rows_only=pruned)
+        achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        traffic, traffic_source = pmc_traffic(a.config)   # HBM-side bytes per launch from the committed PMC passes
+        result["roofline"] = {"bound": "mfma", "kernel": wl["kernel"],
+                              "achieved": achieved, "peak": wl["peak"], "unit": "TFLOP/s",
+                              "frac": achieved / wl["peak"], "traffic": traffic,
+                              "traffic_source": traffic_source,
+                              "launches": gemm_n, "avg_launch_ms": gemm_ms / max(gemm_n, 1),
+                              "prefill_attention_ms_per_step": attn_ms / max(a.steps, 1)}
+    if rank == 0 and a.full and phase.get("decode_steps"):
         # second bound of the path: the decode step streams every weight once for all rows of the
         # launch plus each sequence's KV prefix; algorithmic bytes per step = 2.078 GB + rows x 22,528 B x S (S ~ 544)
         rows = phase["decode_row_steps"] / phase["decode_steps"]
@@ -426,7 +470,7 @@ def main() -> None:
                                      "bytes_per_decode_step": step_bytes,
                                      "kernel": "decode step (fp8 weight-streaming GEMMs + split-KV attention)" if wl["fp8"]
                                      else "decode step (157 launches: streaming GEMMs + fused attention)"}
-    if a.config != "tinyllama-bf16":
+    if a.config != "tinyllama-bf16" or not a.full:
         a.no_overlap_probe = True
     if rank == 0 and world == 1 and a.schedule == "merged" and not a.no_overlap_probe and G > 1:
         # informational: the same engine with ONE batch in flight (prefill, decode 32 rows, next batch)
@@ -455,7 +499,7 @@ def main() -> None:
         result["overlap_probe"] = {"schedule": "threads, 2 engines x %d batches each" % G, "steps": len(reps),
                                    "value": B * len(reps) / (time.perf_counter() - t1), "unit": "utterances/s"}
         pipe.close()
-    if rank == 0 and a.config != "tinyllama-bf16":
+    if rank == 0 and a.full and a.config != "tinyllama-bf16":
         # the CPU restatement of an 8B decoder on a 1536-token prompt takes minutes per utterance: outside the
         # "bounded sample" contract of the default run; parity of this path is asserted in tests/test_hip_fp8.py
         result["cpu_baseline"] = None
@@ -472,7 +516,7 @@ def main() -> None:
                             "logits, top-8 and greedy ids at T = 1536 + 16 decode steps, two layers of this shape — and the hs-128 attention kernels against the "
                             "oracle's SDPA up to 1700 keys (test_hip_ops.py, \"long\" cases); in the run: timed rows against the same prompts decoded alone",
                             "timed_rows_equal_alone_runs": same, "pass": all(same)}
-    elif rank == 0 and world == 1 and not a.no_cpu_baseline:
+    elif rank == 0 and a.full and world == 1 and not a.no_cpu_baseline:
         # the oracle decodes the first utterances of the timed region; its ids and logits are the checker for what the
         # timed run produced for those prompts (parity), its wall time is the CPU baseline
         result["cpu_baseline"], refs = cpu_baseline(cfg, timed_prompts[:9], NEW_TOKENS)
@@ -547,6 +591,10 @@ def bench_finetune(a, wl, cfg, model, dev, rank: int, world: int, rehearsal: boo
         ml = mean_loss.cpu() if rehearsal else mean_loss     # the global batch's mean loss: the same 32 utterances whatever the world size
         dist.all_reduce(ml, op=dist.ReduceOp.SUM)
         mean_loss = ml / world
+    if rank == 0 and a.dump_outputs:
+        # what the last optimizer step left its caller: this rank's per-utterance losses and the updated fp32 LoRA masters
+        dump_outputs(a.dump_outputs, {"losses": last.detach().cpu(),
+                                      "lora_masters": torch.cat([p.detach().reshape(-1) for p in params]).cpu()})
     if rank == 0:
         # fwd 2NT + dX 2NT over the frozen base (no dW), LoRA 6 x 4.5M x T, attention fwd+bwd
         d, I = cfg.n_embd, cfg.intermediate_size

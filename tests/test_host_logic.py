@@ -251,6 +251,26 @@ def test_bench_flop_accounting_counts_executed_launches_only():
     assert merged == (L - 1) * n_tok * 2 * d * (qkv + d + 3 * I) + n_tok * 2 * d * qkv
 
 
+def test_bench_dump_outputs_float_and_bounded(tmp_path):
+    """bench.py --dump-outputs: arrays land as <name>.npy in float32 (float64 kept); one larger than its share of the 64 MB
+    is a fixed sample of its own elements, the same from call to call."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(bench.DUMP_BYTES // 8 + 1000, dtype=torch.float64)             # > 64 MB
+    ids = torch.tensor([[1, 5, 31999], [1, 7, 3]], dtype=torch.int64)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"ids": ids, "big": big, "f32": torch.ones(3, dtype=torch.bfloat16)})
+    a_ids, a_big = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_ids.dtype == np.float32 and np.array_equal(a_ids, ids.numpy().astype(np.float32))
+    assert np.load(tmp_path / "a" / "f32.npy").dtype == np.float32
+    assert a_big.dtype == np.float64 and a_big.nbytes <= bench.DUMP_BYTES // 3 and np.all(np.diff(a_big) > 0)
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES
+
+
 # ---- data-parallel fit(): sharded validation, one best_model.pth, barriers (VERDICT r03 #9) ------------------------------------
 class _StubLM(torch.nn.Module):
     """CPU stand-in with the surface fit() / validate() use (the HIP decoder cannot run here): `transformer.h[l].attn.{attn,proj}`
