@@ -7,6 +7,9 @@
 * `best_model.pth` / `lit_model_lora_finetuned.pth` — what `fabric.save(path, {"model": model})`
   writes (`finetune/ger.py:356-358`) and `inference/ger.py:32-35` reads back as
   `checkpoint["model"]`: the WHOLE state dict (base + LoRA) under the key "model".
+* Hugging Face Phi-3 checkpoints (fused `qkv_proj` / `gate_up_proj`) -> lit layout as the reference's
+  `copy_weights_phi` does it (`scripts/convert_hf_checkpoint.py:204-291`), pinned by
+  `tests/golden/convert_hf_phi3.safetensors`.
 * Hugging Face Llama checkpoints -> lit layout (`scripts/convert_hf_checkpoint.py:117-202,313-373`):
   key renames, and q/k/v projections interleaved PER QUERY GROUP into one fused matrix
   `[q_0 .. q_{q_per_kv-1} k v]_g` — the layout `dh_qkv_rope_cache_bf16` and the LoRA-QKV zero-pad
@@ -118,6 +121,69 @@ class HFLlamaConverter:
         return self.state
 
 
+# Phi-3 names (scripts/convert_hf_checkpoint.py:217-248, the Phi-3 update of the map); q/k/v arrive fused (qkv_proj), gate and up
+# fused (gate_up_proj)
+_PHI3_LAYER_MAP = {
+    "input_layernorm.weight": "norm_1.weight",
+    "post_attention_layernorm.weight": "norm_2.weight",
+    "self_attn.qkv_proj.weight": "attn.attn.weight",
+    "self_attn.o_proj.weight": "attn.proj.weight",
+    "mlp.down_proj.weight": "mlp.proj.weight",
+}
+_PHI3_TOP_MAP = {
+    "model.embed_tokens.weight": "transformer.wte.weight",
+    "model.norm.weight": "transformer.ln_f.weight",
+    "lm_head.weight": "lm_head.weight",
+}
+
+
+class HFPhi3Converter:
+    """HF Phi-3 / Phi-3.5 shards in any order (`add`), then `finish()`: what the reference's copy_weights_phi produces
+    (scripts/convert_hf_checkpoint.py:204-291).  Every tensor is self-contained, so no state waits across shards.
+
+    Quirk (reproduced): `qkv_proj.weight` is copied as it stands, i.e. [all Q; all K; all V], into
+    `attn.attn.weight`, which the model reads as per-group interleaved [q_0 .. k v]_g (ger/model.py:217-219).  At
+    Phi-3.5's multi-head shape that re-pairs the heads' rows; the reference serves and fine-tunes such a model as is."""
+
+    def __init__(self, config: Config, dtype: Optional[torch.dtype] = None) -> None:
+        if config._mlp_class != "LLaMAMLP":
+            raise NotImplementedError(f"HF conversion is implemented for LLaMAMLP models, not {config._mlp_class}")
+        self.config, self.dtype = config, dtype
+        self.state: Dict[str, torch.Tensor] = {}
+
+    def _cast(self, t: torch.Tensor) -> torch.Tensor:
+        return t if self.dtype is None or t.dtype == self.dtype else t.to(self.dtype)
+
+    def add(self, hf_weights: Mapping[str, torch.Tensor]) -> None:
+        if any(n.startswith(("layers.", "transformer.")) for n in hf_weights):
+            raise ValueError("You are using an outdated Phi checkpoint (keys 'layers.' / 'transformer.'); "
+                             "download it again from the Hugging Face hub")
+        for name, param in hf_weights.items():
+            m = _LAYER.match(name)
+            if m:
+                l, rest = int(m.group(1)), m.group(2)
+                if rest == "mlp.gate_up_proj.weight":
+                    fc_1, fc_2 = self._cast(param).chunk(2, dim=0)
+                    self.state[f"transformer.h.{l}.mlp.fc_1.weight"] = fc_1
+                    self.state[f"transformer.h.{l}.mlp.fc_2.weight"] = fc_2
+                    continue
+                if rest not in _PHI3_LAYER_MAP:
+                    raise KeyError(f"unexpected HF Phi-3 tensor {name!r}")
+                self.state[f"transformer.h.{l}.{_PHI3_LAYER_MAP[rest]}"] = self._cast(param)
+            else:
+                if name not in _PHI3_TOP_MAP:
+                    raise KeyError(f"unexpected HF Phi-3 tensor {name!r}")
+                self.state[_PHI3_TOP_MAP[name]] = self._cast(param)
+
+    def finish(self) -> Dict[str, torch.Tensor]:
+        return self.state
+
+
+def hf_converter(config: Config, dtype: Optional[torch.dtype] = None):
+    """The converter of the reference's dispatch (scripts/convert_hf_checkpoint.py:332-335): Phi-3 names take copy_weights_phi."""
+    return HFPhi3Converter(config, dtype) if config.name.startswith("Phi-3") else HFLlamaConverter(config, dtype)
+
+
 def convert_hf_llama(hf_weights: Union[Mapping[str, torch.Tensor], Iterable[Mapping[str, torch.Tensor]]], config: Config,
                      dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
     conv = HFLlamaConverter(config, dtype)
@@ -150,7 +216,7 @@ def convert_hf_checkpoint(checkpoint_dir: Union[str, Path], model_name: Optional
         files = {f for f in d.glob("*.bin") if f.name != "training_args.bin"} or set(d.glob("*.safetensors"))
     if not files:
         raise ValueError(f"Expected {str(d)!r} to contain .bin or .safetensors files")
-    conv = HFLlamaConverter(config, dtype)
+    conv = hf_converter(config, dtype)
     for f in sorted(files):
         conv.add(_read_shard(f))
     out = d / "lit_model.pth"

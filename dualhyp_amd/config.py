@@ -5,7 +5,9 @@ LoRA fields of `ger.lora.Config` (ger/lora.py:446-472): same field names, same d
 values (`head_size`, `padded_vocab_size`, `n_query_groups`, `rope_n_elem`), same
 `from_name(name, **kwargs)` lookup by table name or HF name.  Only the two model families
 the hot path is quoted on are tabulated (TinyLlama-1.1B ger/config.py:1542-1567 and
-Llama-3-8B ger/config.py:801-818) plus small shapes used by the parity tests.
+Llama-3-8B ger/config.py:801-818), the reference's second LLM family (Phi-3.5-mini-instruct,
+ger/config.py:1453-1468: head size 96, multi-head attention) plus small shapes used by the
+parity tests.
 """
 from __future__ import annotations
 
@@ -101,8 +103,8 @@ class Config:
             problems.append("bias unsupported")
         if self.rotary_percentage != 1.0:
             problems.append("rotary_percentage must be 1.0")
-        if self.head_size not in (64, 128):
-            problems.append("head_size must be 64 or 128")
+        if self.head_size not in (64, 96, 128):
+            problems.append("head_size must be 64, 96 or 128")
         if self.n_embd % 64 or self.intermediate_size % 64 or self.padded_vocab_size % 64:
             problems.append("n_embd/intermediate_size/padded_vocab_size must be multiples of 64")
         if self.to_mlp or self.to_head:
@@ -187,6 +189,14 @@ for _kind in ("", "-Instruct"):
         block_size=8192, vocab_size=128000, padded_vocab_size=128256, n_layer=32, n_head=32,
         n_query_groups=8, n_embd=4096, intermediate_size=14336, rope_base=500000))
 
+# Phi-3.5-mini-instruct (ger/config.py:1453-1468): 32 heads of 96, full multi-head attention (n_query_groups defaults
+# to n_head), untied head.  Its HF longrope scaling is ignored, as in the reference (rope_base stays the default 10000).
+configs.append(_llama(
+    name="Phi-3.5-mini-instruct",
+    hf_config=dict(org="microsoft", name="Phi-3.5-mini-instruct"),
+    vocab_size=32000, padded_vocab_size=32064, block_size=4096, n_embd=3072, n_layer=32,
+    intermediate_size=8192))
+
 # Small shapes for parity tests (not in the reference's table).
 configs.append(_llama(name="parity-tiny", hf_config=dict(org="dualhyp_amd", name="parity-tiny"),
                       block_size=128, vocab_size=256, padding_multiple=64, n_layer=2, n_head=4,
@@ -197,6 +207,13 @@ configs.append(_llama(name="parity-block", hf_config=dict(org="dualhyp_amd", nam
 configs.append(_llama(name="parity-hs128", hf_config=dict(org="dualhyp_amd", name="parity-hs128"),
                       block_size=256, vocab_size=512, padding_multiple=64, n_layer=2, n_head=4,
                       n_embd=512, intermediate_size=768, n_query_groups=2))
+# head size 96, multi-head (Phi-3.5's attention shape) and grouped; room for a byte-tokenised DualHyp prompt (CLI tests)
+configs.append(_llama(name="parity-hs96", hf_config=dict(org="dualhyp_amd", name="parity-hs96"),
+                      block_size=1024, vocab_size=512, padding_multiple=64, n_layer=2, n_head=4,
+                      n_embd=384, intermediate_size=768, n_query_groups=4))
+configs.append(_llama(name="parity-hs96-gqa", hf_config=dict(org="dualhyp_amd", name="parity-hs96-gqa"),
+                      block_size=256, vocab_size=512, padding_multiple=64, n_layer=2, n_head=4,
+                      n_embd=384, intermediate_size=768, n_query_groups=2))
 
 # room for a byte-tokenised DualHyp prompt (~700 tokens) + 150 generated: harness tests (tests/test_harness.py)
 configs.append(_llama(name="parity-harness", hf_config=dict(org="dualhyp_amd", name="parity-harness"),

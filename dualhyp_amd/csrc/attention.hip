@@ -25,7 +25,8 @@ namespace {
 
 // ------------------------------------------------------------------------------------ prefill
 // grid (q tiles of 32, n_groups, n_seq); block = 64 * q_per_kv threads: one wave per query head
-// of the group, all waves share the K / V^T tiles of 64 keys staged in LDS.
+// of the group, all waves share the K / V^T tiles of 64 keys staged in LDS.  Head size 96 (Phi-3.5, multi-head: q_per_kv 1)
+// runs one wave per block: 48 KiB of stages, three blocks per CU by LDS.
 // PS: scale is a power of two (head size 64: 1/8), so it is applied to the Q fragments once — exact in bf16 and in the
 // fp32 products and sums (barring underflow) — instead of to every score: the loop is bound by its softmax VALU work.
 template <int HS, bool PS = false>
@@ -348,7 +349,7 @@ extern "C" int dh_attn_prefill_bf16(const dh_bf16* q, const dh_bf16* k_cache, co
                                     const int32_t* kv_pos0, dh_bf16* y, float* lse, int n_seq, int max_q_len,
                                     int n_head, int n_groups, int hs, int s_max, void* stream) {
     DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= 16, "dh_attn_prefill_bf16: bad head counts");
-    DH_CHECK(hs == 64 || hs == 128, "dh_attn_prefill_bf16: head_size %d unsupported", hs);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_prefill_bf16: head_size %d unsupported", hs);
     DH_CHECK(s_max % 64 == 0, "dh_attn_prefill_bf16: s_max must be a multiple of 64");
     DH_CHECK(64 * (n_head / n_groups) <= (hs == 64 ? 1024 : 512), "dh_attn_prefill_bf16: too many query heads per group");
     if (n_seq <= 0 || max_q_len <= 0) return 0;
@@ -357,6 +358,9 @@ extern "C" int dh_attn_prefill_bf16(const dh_bf16* q, const dh_bf16* k_cache, co
     hipStream_t s = (hipStream_t)stream;
     if (hs == 64)
         hipLaunchKernelGGL((attn_prefill_kernel<64, true>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len,   // scale = 1/8
+                           kv_pos0, y, lse, n_head, n_groups, s_max, scale);
+    else if (hs == 96)   // 1/sqrt(96) is not a power of two: scaled per score, as at 128
+        hipLaunchKernelGGL((attn_prefill_kernel<96>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len,
                            kv_pos0, y, lse, n_head, n_groups, s_max, scale);
     else
         hipLaunchKernelGGL((attn_prefill_kernel<128>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len,
@@ -375,7 +379,7 @@ extern "C" int dh_attn_decode_bf16(const dh_bf16* q, const dh_bf16* k_cache, con
                                    const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* y, void* work, int n_seq,
                                    int n_head, int n_groups, int hs, int s_max, void* stream) {
     DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DEC_COLS, "dh_attn_decode_bf16: bad head counts");
-    DH_CHECK(hs == 64 || hs == 128, "dh_attn_decode_bf16: head_size %d unsupported", hs);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_bf16: head_size %d unsupported", hs);
     DH_CHECK(s_max % 64 == 0, "dh_attn_decode_bf16: s_max must be a multiple of 64");
     DH_CHECK(work != nullptr, "dh_attn_decode_bf16: null workspace");
     if (n_seq <= 0) return 0;
@@ -387,6 +391,11 @@ extern "C" int dh_attn_decode_bf16(const dh_bf16* q, const dh_bf16* k_cache, con
         hipLaunchKernelGGL((attn_decode_kernel<64>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, kv_len,
                            (float*)work, n_head, n_groups, s_max, scale);
         hipLaunchKernelGGL((attn_decode_combine_kernel<64>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head,
+                           n_groups, DEC_NSPLIT * 4);
+    } else if (hs == 96) {
+        hipLaunchKernelGGL((attn_decode_kernel<96>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, kv_len,
+                           (float*)work, n_head, n_groups, s_max, scale);
+        hipLaunchKernelGGL((attn_decode_combine_kernel<96>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head,
                            n_groups, DEC_NSPLIT * 4);
     } else {
         hipLaunchKernelGGL((attn_decode_kernel<128>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, kv_len,

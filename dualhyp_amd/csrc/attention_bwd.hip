@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void transpose_pad_kernel(const bf16_t* __rest
         if (t < n_tok) {
             const int s = tok_seq[t];
             const int pp = pad_start[s] + (t - q_start[s]);
-            dst[hs == 64 ? tfrag_off<64>(h, n_pad, pp, e) : tfrag_off<128>(h, n_pad, pp, e)] = tile[tl][e];
+            dst[hs == 64 ? tfrag_off<64>(h, n_pad, pp, e) : hs == 96 ? tfrag_off<96>(h, n_pad, pp, e) : tfrag_off<128>(h, n_pad, pp, e)] = tile[tl][e];
         }
     }
 }
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
     // needed one whole phase of MFMAs and exps has passed.  lse / D travel as ONE value per lane (row q0 + lane % 32) and
     // reach the accumulator layout's rows through ds_bpermute instead of 16 loads per lane each.
     static_assert(!IMG || HS == 64, "the LDS image form is sized for hs 64 (16 KiB per wave)");
-    constexpr bool PIPE = HS == 64 && !IMG;       // hs 128 doubles every fragment set: the second set of row operands would spill
+    constexpr bool PIPE = HS == 64 && !IMG;       // hs 96 / 128 grow every fragment set: the second set of row operands would spill
     struct RowOps { bf16x8 qf[KS], dof[KS]; float l, d; };
     char* img = reinterpret_cast<char*>(red) + (IMG ? __builtin_amdgcn_readfirstlane(wave) * 16384 : 0);   // IMG: [2][q 4 KiB | dO 4 KiB] of this wave
     auto load_ld = [&](RowOps& R, int qt) __attribute__((always_inline)) {
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_group_kernel(
 
 extern "C" int dh_transpose_pad_bf16(const dh_bf16* src, dh_bf16* dst, const int32_t* tok_seq, const int32_t* q_start,
                                      const int32_t* pad_start, int n_tok, int heads, int hs, int n_pad, void* stream) {
-    DH_CHECK(src && dst && tok_seq && q_start && pad_start && hs <= 128 && n_pad % 32 == 0, "dh_transpose_pad_bf16: bad argument");
+    DH_CHECK(src && dst && tok_seq && q_start && pad_start && (hs == 64 || hs == 96 || hs == 128) && n_pad % 32 == 0, "dh_transpose_pad_bf16: bad argument");
     if (n_tok <= 0) return 0;
     hipLaunchKernelGGL(transpose_pad_kernel, dim3(cdiv(n_tok, 32), heads), dim3(256), 0, (hipStream_t)stream, src, dst, tok_seq,
                        q_start, pad_start, n_tok, heads, hs, n_pad);
@@ -584,10 +584,11 @@ extern "C" int dh_transpose_pad_bf16(const dh_bf16* src, dh_bf16* dst, const int
 
 extern "C" int dh_transpose_frag_bf16(const dh_bf16* src, dh_bf16* dst, const int32_t* pad_tok, int heads, int hs, int n_pad,
                                       void* stream) {
-    DH_CHECK(src && dst && pad_tok && (hs == 64 || hs == 128) && heads > 0 && n_pad >= 0 && n_pad % 32 == 0, "dh_transpose_frag_bf16: bad argument");
+    DH_CHECK(src && dst && pad_tok && (hs == 64 || hs == 96 || hs == 128) && heads > 0 && n_pad >= 0 && n_pad % 32 == 0, "dh_transpose_frag_bf16: bad argument");
     DH_CHECK(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0, "dh_transpose_frag_bf16: src / dst must be 16-byte aligned");
     if (n_pad == 0) return 0;
     if (hs == 64) hipLaunchKernelGGL((transpose_frag_kernel<64>), dim3(n_pad / 32, heads), dim3(256), 0, (hipStream_t)stream, src, dst, pad_tok, heads, n_pad);
+    else if (hs == 96) hipLaunchKernelGGL((transpose_frag_kernel<96>), dim3(n_pad / 32, heads), dim3(256), 0, (hipStream_t)stream, src, dst, pad_tok, heads, n_pad);
     else hipLaunchKernelGGL((transpose_frag_kernel<128>), dim3(n_pad / 32, heads), dim3(256), 0, (hipStream_t)stream, src, dst, pad_tok, heads, n_pad);
     DH_LAUNCH_CHECK();
     return 0;
@@ -607,7 +608,7 @@ extern "C" int dh_attn_bwd_bf16(const dh_bf16* q, const dh_bf16* k, const dh_bf1
                                 int hs, int n_pad, void* stream) {
     DH_CHECK(q && k && v && dout && kT && lse && dsum && dq && dk && dv, "dh_attn_bwd_bf16: null argument");
     DH_CHECK((qT && doT) || !(dh_attn_bwd_transposes(n_head, n_groups, hs, n_pad) & 1), "dh_attn_bwd_bf16: this shape reads qT / doT (dh_attn_bwd_transposes)");
-    DH_CHECK(hs == 64 || hs == 128, "dh_attn_bwd_bf16: head_size %d unsupported", hs);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_bwd_bf16: head_size %d unsupported", hs);
     DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= 8, "dh_attn_bwd_bf16: at most 8 query heads per group");
     DH_CHECK(n_pad % 32 == 0, "dh_attn_bwd_bf16: n_pad must be a multiple of 32");
     if (n_seq <= 0 || max_q_len <= 0) return 0;
@@ -635,6 +636,18 @@ extern "C" int dh_attn_bwd_bf16(const dh_bf16* q, const dh_bf16* k, const dh_bf1
                                q_start, q_len, pad_start, dq, n_head, n_groups, n_pad, scale, nt, n_seq);
         else
             hipLaunchKernelGGL((attn_bwd_dq_kernel<64>), dim3(grid_q), dim3(64), 0, s, q, k, v, dout, kT, lse, dsum,
+                               q_start, q_len, pad_start, dq, n_head, n_groups, n_pad, scale, nt, n_seq);
+    } else if (hs == 96) {   // the hs-128 form: register operands, one transposed fragment pair at a time
+#define DKDV(QT) do { DH_MAX_LDS_ONCE((attn_bwd_dkdv_kernel<96, QT>), 160 * 1024);                                        \
+        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<96, QT>), dim3(grid_kv), dim3(64 * qpk), lds, s, q, k, v, dout, qT, doT, lse, dsum,   \
+                           q_start, q_len, pad_start, dk, dv, n_head, n_groups, n_pad, scale, nt, n_seq); } while (0)
+        if (qpk == 8) DKDV(8); else if (qpk >= 4) DKDV(4); else DKDV(1);
+#undef DKDV
+        if (dq_group)
+            hipLaunchKernelGGL((attn_bwd_dq_group_kernel<96>), dim3(grid_qg), dim3(64 * qpk), 2 * (2 * 6 + 2 * 3) * 1024, s, q, k, v, dout, kT, lse, dsum,
+                               q_start, q_len, pad_start, dq, n_head, n_groups, n_pad, scale, nt, n_seq);
+        else
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<96>), dim3(grid_q), dim3(64), 0, s, q, k, v, dout, kT, lse, dsum,
                                q_start, q_len, pad_start, dq, n_head, n_groups, n_pad, scale, nt, n_seq);
     } else {
 #define DKDV(QT) do { DH_MAX_LDS_ONCE((attn_bwd_dkdv_kernel<128, QT>), 160 * 1024);                                       \

@@ -15,7 +15,7 @@ constexpr int DCOLS = 16;   // padded head columns of the attention partials
 constexpr int MAXP = 16;    // most K-slices a partial-sum GEMM emits
 
 // --------------------------------------------------------------------------- attention (decode)
-// grid (n_seq * n_groups), NW waves (hs 64: 16, hs 128: 8).  qkv32: [n_part][n_seq][ldq] fp32, ldq = qkv_dim + n_ext;
+// grid (n_seq * n_groups), NW waves (hs 64: 16, hs 96 and 128: 8; hs 96 needs 53 KiB of LDS, two blocks per CU).  qkv32: [n_part][n_seq][ldq] fp32, ldq = qkv_dim + n_ext;
 // columns [qkv_dim, qkv_dim+48) hold x·A^T of the q/k/v LoRA (when lora_b != null).
 // NW waves share the key tiles of one (sequence, group).  Round 3: SIXTEEN waves at hs 64 — at the benchmark's ~544 cached keys
 // (17 tiles) every tile is then requested before the LoRA / rope prologue and no wave walks a second or third tile behind an
@@ -401,7 +401,7 @@ extern "C" int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pai
                                          int n_head, int n_groups, int hs, int s_max, void* stream) {
     DH_CHECK(qkv32 && cos && sin && seq_slot && kv_len && k_cache && vT_cache && y, "dh_attn_decode_fused_bf16: null argument");
     DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DCOLS, "dh_attn_decode_fused_bf16: bad head counts");
-    DH_CHECK(hs == 64 || hs == 128, "dh_attn_decode_fused_bf16: head_size %d unsupported", hs);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_fused_bf16: head_size %d unsupported", hs);
     DH_CHECK(s_max % 64 == 0 && n_part >= 1 && n_part <= MAXP, "dh_attn_decode_fused_bf16: bad s_max / n_part");
     DH_CHECK(qkv_dim == (n_head + 2 * n_groups) * hs, "dh_attn_decode_fused_bf16: qkv_dim mismatch");
     DH_CHECK(lora_b == nullptr || n_ext >= 48, "dh_attn_decode_fused_bf16: LoRA needs the 48 x·A^T columns");
@@ -420,6 +420,13 @@ extern "C" int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pai
         if (n_part <= 2) ATT_LAUNCH(64, 2);
         else if (n_part <= 8) ATT_LAUNCH(64, 8);
         else ATT_LAUNCH(64, 16);
+    } else if (hs == 96) {
+        DH_MAX_LDS_ONCE((attn_decode_fused_kernel<96, 2, 8>), attn_fused_lds<96>());
+        DH_MAX_LDS_ONCE((attn_decode_fused_kernel<96, 8, 8>), attn_fused_lds<96>());
+        DH_MAX_LDS_ONCE((attn_decode_fused_kernel<96, 16, 8>), attn_fused_lds<96>());
+        if (n_part <= 2) ATT_LAUNCH(96, 2);
+        else if (n_part <= 8) ATT_LAUNCH(96, 8);
+        else ATT_LAUNCH(96, 16);
     } else {
         DH_MAX_LDS_ONCE((attn_decode_fused_kernel<128, 2, 8>), attn_fused_lds<128>());
         DH_MAX_LDS_ONCE((attn_decode_fused_kernel<128, 8, 8>), attn_fused_lds<128>());

@@ -199,12 +199,15 @@ extern "C" int dh_qkv_rope_cache_bf16(const dh_bf16* qkv, const dh_bf16* cos, co
                                       dh_bf16* k_cache, dh_bf16* vT_cache, dh_bf16* k_out, dh_bf16* v_out, int n_tok,
                                       int n_head, int n_groups, int hs, int s_max, void* stream) {
     DH_CHECK(n_tok >= 0 && n_groups > 0 && n_head % n_groups == 0, "dh_qkv_rope_cache_bf16: bad head counts");
-    DH_CHECK(hs == 64 || hs == 128, "dh_qkv_rope_cache_bf16: head_size %d unsupported (64 or 128)", hs);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_qkv_rope_cache_bf16: head_size %d unsupported (64, 96 or 128)", hs);
     if (n_tok == 0) return 0;
     dim3 grid(cdiv(n_tok, 64), n_groups), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (hs == 64)
         hipLaunchKernelGGL((qkv_rope_cache_kernel<64>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,
+                           k_cache, vT_cache, k_out, v_out, n_tok, n_head, n_groups, s_max);
+    else if (hs == 96)   // rope pairs (i, i + 48): six 16-B chunk pairs per head
+        hipLaunchKernelGGL((qkv_rope_cache_kernel<96>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,
                            k_cache, vT_cache, k_out, v_out, n_tok, n_head, n_groups, s_max);
     else
         hipLaunchKernelGGL((qkv_rope_cache_kernel<128>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,

@@ -162,7 +162,8 @@ int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q
         bf16_t* vtc = e->vtc + (size_t)l * e->cache_layer_elems;
         if ((rc = dh_rmsnorm_bf16(e->x, nullptr, W.norm_1, e->xn, nullptr, n_tok, d, D.norm_eps, rt, s))) return rc;
         // large packed prefills: rope + KV append ride in the QKV GEMM's epilogue (same bits, no pass over the qkv tensor)
-        const bool fuse_qkv = !decode && g_fuse_qkv_rope && dh_linear_is_big(n_tok, e->qkv_dim, DH_EPI_LORA);
+        // (not at head size 96: a 96-wide head straddles the 256-column tiles of that epilogue, gemm.hip)
+        const bool fuse_qkv = !decode && g_fuse_qkv_rope && hs != 96 && dh_linear_is_big(n_tok, e->qkv_dim, DH_EPI_LORA);
         // x.A^T: inside the QKV GEMM's K loop on the fused large-prefill path (dh_linear_qkv_lora_rope_cache_bf16 decides), else a launch
         if (W.attn_lora_a && !fuse_qkv)
             if ((rc = linear(e, e->xn, W.attn_lora_a, e->xa, n_tok, 48, d, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, 0, 0,
@@ -438,7 +439,7 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
 
 extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, dh_engine** out) {
     DH_CHECK(desc && out, "dh_engine_create: null argument");
-    DH_CHECK(desc->head_size == 64 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
+    DH_CHECK(desc->head_size == 64 || desc->head_size == 96 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
     DH_CHECK(desc->n_head % desc->n_groups == 0, "dh_engine_create: n_head %% n_groups != 0");
     DH_CHECK(desc->n_embd == desc->n_head * desc->head_size, "dh_engine_create: n_embd != n_head*head_size");
     DH_CHECK(desc->n_embd % 64 == 0 && desc->intermediate % 64 == 0 && desc->vocab % 8 == 0, "dh_engine_create: dims must be multiples of 64");
@@ -471,6 +472,17 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
         DH_CHECK(d % 128 == 0 && desc->intermediate % 128 == 0, "dh_engine_create: fp8 mode needs n_embd and intermediate %% 128 == 0");
     }
     e->cache_layer_elems = (size_t)max_batch * G * s_max * hs;
+    {
+        // a multi-head model's KV cache (Phi-3.5: 12 KiB per position and layer) outgrows the device at batch sizes tuned on
+        // TinyLlama: refuse before allocating anything, naming the knob
+        size_t free_b = 0, total_b = 0;
+        DH_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t kv_bytes = 2 * e->cache_layer_elems * desc->n_layer * sizeof(bf16_t);
+        DH_CHECK(kv_bytes <= free_b,
+                 "dh_engine_create: the KV cache of %d sequences x %d positions x %d layers needs %.1f GiB and %.1f GiB are free: "
+                 "lower the decode batch (--decode_batch)", max_batch, s_max, desc->n_layer, kv_bytes / 1073741824.0,
+                 free_b / 1073741824.0);
+    }
     const size_t T = max_tokens;
     int rc = 0;
     rc |= dmalloc(e, &e->kc, e->cache_layer_elems * desc->n_layer);

@@ -268,7 +268,9 @@ static int qkv_rope_cache_impl(const dh_bf16* x, const dh_bf16* w, int M, int K,
                                const int32_t* tok_slot, const int32_t* tok_pos, dh_bf16* q_out, dh_bf16* k_cache,
                                dh_bf16* vT_cache, int n_head, int n_groups, int hs, int s_max, void* stream) {
     DH_CHECK(x && w && cos && sin && tok_slot && tok_pos && q_out && k_cache && vT_cache, "dh_linear_qkv_rope_cache_bf16: null argument");
-    DH_CHECK(hs == 64 || hs == 128, "dh_linear_qkv_rope_cache_bf16: head_size %d unsupported", hs);
+    // the epilogue's head walk is built for 64 and 128 only (gemm256.hip): a 96-wide head straddles the 256-column tiles, so
+    // head size 96 takes dh_linear_bf16 + dh_qkv_rope_cache_bf16
+    DH_CHECK(hs == 64 || hs == 128, "dh_linear_qkv_rope_cache_bf16: head_size %d unsupported (64 or 128; use dh_linear_bf16 + dh_qkv_rope_cache_bf16)", hs);
     DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && K % BK == 0, "dh_linear_qkv_rope_cache_bf16: bad shape");
     const int N = (n_head + 2 * n_groups) * hs, d = n_head * hs, kv = n_groups * hs;
     DH_CHECK(dh_linear_is_big(M, N, DH_EPI_LORA), "dh_linear_qkv_rope_cache_bf16: M=%d is below the 256-tile kernel's range; use dh_linear_bf16 + dh_qkv_rope_cache_bf16", M);

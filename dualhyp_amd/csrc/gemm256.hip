@@ -250,6 +250,7 @@ __device__ __forceinline__ void g256_epilogue(const GemmArgs& a, f32x4 (&acc)[8]
                     r[4 * t + 3] = *reinterpret_cast<const uint2*>(sp + HALF + 16 * t);
                 }
             };
+            // hs is 64 or 128 in every epilogue of this kernel: dh_linear_256 (host) refuses any other head size
             if (a.hs == 64) rows(std::integral_constant<int, 64>{});
             else rows(std::integral_constant<int, 128>{});
         }
@@ -1433,6 +1434,8 @@ bool dh_linear_256_xa_ok(const GemmArgs& a, int epilogue) {
 }
 
 int dh_linear_256(GemmArgs a, int epilogue, hipStream_t s) {
+    // the fused-QKV epilogues branch "64, else 128" on the device: no other head size may reach them
+    DH_CHECK(epilogue != DH_EPI_QKV || a.hs == 64 || a.hs == 128, "dh_linear_256: fused-QKV epilogue with head_size %d (64 or 128 only)", a.hs);
     a.gm = g_gemm_gm > 0 ? g_gemm_gm : 4;
     a.fast_epi = g_w4_fast_epi;
     a.nb_m = cdiv(a.M, BT2);

@@ -498,11 +498,13 @@ extern "C" int dh_qkv_rope_bwd_bf16(const dh_bf16* dq, const dh_bf16* dk, const 
                                     const dh_bf16* sin, const int32_t* tok_pos, dh_bf16* dqkv, int n_tok, int n_head,
                                     int n_groups, int hs, void* stream) {
     DH_CHECK(dq && dk && dv && cos && sin && tok_pos && dqkv, "dh_qkv_rope_bwd_bf16: null argument");
-    DH_CHECK(hs == 64 || hs == 128, "dh_qkv_rope_bwd_bf16: head_size %d unsupported", hs);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_qkv_rope_bwd_bf16: head_size %d unsupported", hs);
     if (n_tok <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (hs == 64)
         hipLaunchKernelGGL((qkv_rope_bwd_kernel<64>), dim3(1024), dim3(256), 0, s, dq, dk, dv, cos, sin, tok_pos, dqkv, n_tok, n_head, n_groups);
+    else if (hs == 96)
+        hipLaunchKernelGGL((qkv_rope_bwd_kernel<96>), dim3(1024), dim3(256), 0, s, dq, dk, dv, cos, sin, tok_pos, dqkv, n_tok, n_head, n_groups);
     else
         hipLaunchKernelGGL((qkv_rope_bwd_kernel<128>), dim3(1024), dim3(256), 0, s, dq, dk, dv, cos, sin, tok_pos, dqkv, n_tok, n_head, n_groups);
     DH_LAUNCH_CHECK();

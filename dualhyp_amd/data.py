@@ -116,13 +116,33 @@ def relprompt_prompt(sample_asr: Dict[str, Any], sample_vsr: Dict[str, Any], aud
     return s + p["prompt_3"]
 
 
-def encode_example(tokenizer, prompt_no_response: str, caption: str, max_input_length: int = 0) -> Dict[str, Any]:
+CHAT_SYSTEM = "You are a helpful AI assistant."      # data/av_dataset.py:228, 401
+
+
+def prompt_ids(tokenizer, prompt_no_response: str, apply_chat_template: bool = False) -> List[int]:
+    """Ids of a prompt as the harness feeds it to the decoder: plain `encode`, or the chat template's (system message, user
+    prompt, generation prompt) when `apply_chat_template` (data/av_dataset.py:225-235)."""
+    if apply_chat_template:
+        return tokenizer.chat_prompt_ids(prompt_no_response, CHAT_SYSTEM)
+    return tokenizer.encode(prompt_no_response)
+
+
+def encode_example(tokenizer, prompt_no_response: str, caption: str, max_input_length: int = 0,
+                   apply_chat_template: bool = False) -> Dict[str, Any]:
     """Token ids + labels (-1 over the prompt) — data/av_dataset.py:246-256, 360-362.
-    `tokenizer` needs `.encode(str) -> List[int]` and `.eos_token`."""
+    `tokenizer` needs `.encode(str) -> List[int]` and `.eos_token`.  With `apply_chat_template` (Phi-3.5,
+    data/av_dataset.py:225-239, 398-411): the chat template's prompt ids, then the caption's ids without special tokens and
+    `eos_token_id`; labels -1 over the prompt."""
     full = prompt_no_response + caption + tokenizer.eos_token
-    ids_np = tokenizer.encode(prompt_no_response)
-    ids = tokenizer.encode(full)
-    labels = [-1] * len(ids_np) + ids[len(ids_np):]
+    if apply_chat_template:
+        ids_np = prompt_ids(tokenizer, prompt_no_response, True)
+        answer = tokenizer.encode_plain(caption) + [tokenizer.eos_token_id]
+        ids = ids_np + answer
+        labels = [-1] * len(ids_np) + answer
+    else:
+        ids_np = tokenizer.encode(prompt_no_response)
+        ids = tokenizer.encode(full)
+        labels = [-1] * len(ids_np) + ids[len(ids_np):]
     ids_t, lab_t = torch.tensor(ids, dtype=torch.int64), torch.tensor(labels, dtype=torch.int64)
     if max_input_length > 0:
         ids_t, lab_t = ids_t[:max_input_length], lab_t[:max_input_length]
@@ -169,7 +189,7 @@ class HypothesesDataset:
     def __init__(self, json_path_or_items, tokenizer, prompts_format: str = "DualHyp", nhyps_key: str = "nhyps_asr",
                  max_nhyps: Optional[int] = None, max_input_length: int = 0, language: Optional[str] = None,
                  mask_threshold: Optional[float] = None, time_window: float = 0.4, seed: Optional[int] = None,
-                 enc_features=None, leave_masks: bool = False) -> None:
+                 enc_features=None, leave_masks: bool = False, apply_chat_template: bool = False) -> None:
         items = json_path_or_items
         if isinstance(items, (str, bytes)) or hasattr(items, "__fspath__"):
             with open(items, encoding="utf-8") as f:
@@ -184,6 +204,7 @@ class HypothesesDataset:
         # RelPrompt inference (inference/relprompt.py:113-153): the prompt keeps its <<<ASR_MASKS>>> / <<<VSR_MASKS>>> placeholders;
         # the harness fills them with the classifiers' predictions and re-encodes
         self.leave_masks = leave_masks
+        self.apply_chat_template = apply_chat_template
         self.tokenizer, self.fmt, self.nhyps_key = tokenizer, prompts_format, nhyps_key
         self.max_nhyps, self.max_input_length, self.language = max_nhyps, max_input_length, language
         self.mask_threshold = mask_threshold
@@ -206,7 +227,7 @@ class HypothesesDataset:
                 _, al = chunk_reliability(noise_mask(s1, "audio", self.mask_threshold), self.audio_chunk)
                 _, vl = chunk_reliability(noise_mask(s2, "video", self.mask_threshold), self.video_chunk)
                 prompt = relprompt_prompt(s1, s2, al, vl, self.max_nhyps, leave_masks=self.leave_masks)
-        ex = encode_example(self.tokenizer, prompt, s1["Caption"], self.max_input_length)
+        ex = encode_example(self.tokenizer, prompt, s1["Caption"], self.max_input_length, self.apply_chat_template)
         ex["uid"], ex["ground_truth"] = s1.get("Uid", ""), s1.get("Caption", "")
         if self.fmt == "RelPrompt":
             # ground-truth reliability classes of the chunks (finetune/relprompt.py:73-79,364-365: <<C>> 0, <<M>> 1, else 2)

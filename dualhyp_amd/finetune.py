@@ -333,7 +333,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, float]:
     p.add_argument("--audio_corruption_disabled", action="store_true", help="accepted for compatibility")
     p.add_argument("--visual_corruption_disabled", action="store_true", help="accepted for compatibility")
     p.add_argument("--prompts_format", type=str, default="GER")
-    p.add_argument("--apply_chat_template", action="store_true")
+    p.add_argument("--apply_chat_template", action="store_true", help="pack prompts through the tokenizer's chat template (phi-3.5)")
     p.add_argument("--language", type=str, default=None)
     add_lora_arguments(p)
     # additions of this build
@@ -356,8 +356,6 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, float]:
                    help="addition of this build: <dir>/<Uid>.pt = {'audio': [T, whisper_dim], 'visual': [T, raven_dim]} encoder features "
                         "(the Whisper / BRAVEn encoders of finetune/relprompt.py:346-352 are upstream of this path)")
     args = p.parse_args(argv)
-    if args.apply_chat_template:
-        raise NotImplementedError("--apply_chat_template is outside the hot path")
     rank, world, dev = init_distributed(args.d)
     out_dir = Path(args.out_dir or f"./runs/{args.exp_name}")
     if rank == 0:
@@ -370,9 +368,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, float]:
     from .checkpoint import load_checkpoint
     from .data import HypothesesDataset, collate
     from .gpt import GPT
-    from .tokenizer import load_tokenizer
+    from .tokenizer import load_tokenizer, apply_eos_override
     cfg = config_from_args(args)
     tokenizer = load_tokenizer(args.llm_checkpoint, args.tokenizer)
+    apply_eos_override(tokenizer, cfg.name)                # finetune/ger.py:119-120 (phi-): targets end at <|endoftext|>
     max_input_length = 1024                                # finetune/ger.py:417-421
     tc_path = Path(args.llm_checkpoint) / "tokenizer_config.json"
     if tc_path.is_file():
@@ -416,7 +415,8 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, float]:
             _variants.setdefault(it["Uid"], []).append(it)
         return HypothesesDataset(items, tokenizer, prompts_format=fmt, nhyps_key=args.nhyps_key, max_nhyps=args.max_nhyps,
                                  max_input_length=max_input_length, language=args.language, seed=seed,
-                                 mask_threshold=args.mask_threshold, time_window=args.time_window, enc_features=enc_features)
+                                 mask_threshold=args.mask_threshold, time_window=args.time_window, enc_features=enc_features,
+                                 apply_chat_template=args.apply_chat_template)
     train_ds = dataset(args.train_path, args.seed + rank)
     train = [train_ds[i] for i in range(len(train_ds))]
     val_batches = None

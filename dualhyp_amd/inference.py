@@ -141,7 +141,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     import os
     from pathlib import Path
     from .checkpoint import load_checkpoint
-    from .data import HypothesesDataset
+    from .data import HypothesesDataset, prompt_ids
     from .generate import generate_batch
     if adapter_path:
         sd = load_checkpoint(adapter_path)
@@ -169,7 +169,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     ds = HypothesesDataset(args.test_path, tokenizer, prompts_format=fmt if (args.dual_hypotheses or fmt == "RelPrompt") else "GER",
                            nhyps_key=args.nhyps_key, max_nhyps=args.max_nhyps, language=args.language, seed=args.seed,
                            mask_threshold=getattr(args, "mask_threshold", None), time_window=getattr(args, "time_window", 0.4),
-                           enc_features=enc_features, leave_masks=bool(feats_dir))
+                           enc_features=enc_features, leave_masks=bool(feats_dir), apply_chat_template=args.apply_chat_template)
     _variants.update(ds.uid2sample)
     examples = [ds[i] for i in range(len(ds))]
     mask_stats = None
@@ -179,7 +179,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         for ex in examples:
             prompt, a, v = predicted_mask_prompt(model, ex["input_no_response"], ex["audio_enc_features"], ex["visual_enc_features"])
             ex["input_no_response"] = prompt
-            ex["input_ids_no_response"] = torch.tensor(tokenizer.encode(prompt), dtype=torch.int64)    # re-encoded with the predicted masks
+            ex["input_ids_no_response"] = torch.tensor(prompt_ids(tokenizer, prompt, args.apply_chat_template),   # re-encoded with the
+                                                       dtype=torch.int64)                                        # predicted masks
             for name, pred, tgt in (("audio", a, ex["audio_mask_targets"]), ("visual", v, ex["visual_mask_targets"])):
                 n = min(pred.numel(), tgt.numel())                                                   # trimmed to the shorter, as the reference
                 hit[name][0] += int((pred[:n] == tgt[:n]).sum())
@@ -250,7 +251,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
     p.add_argument("--visual_corruption_disabled", action="store_true", help="accepted for compatibility")
     p.add_argument("--seed", type=int, default=1337)
     p.add_argument("--prompts_format", type=str, default="GER")
-    p.add_argument("--apply_chat_template", action="store_true", help="unsupported here (phi-3.5 only in the reference)")
+    p.add_argument("--apply_chat_template", action="store_true", help="prompts through the tokenizer's chat template (phi-3.5)")
     p.add_argument("--language", type=str, default=None)
     add_lora_arguments(p)
     # additions of this build
@@ -270,16 +271,15 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
     p.add_argument("--pool_size", type=int, default=10)
     p.add_argument("--enc_features_dir", type=str, default=None)
     args = p.parse_args(argv)
-    if args.apply_chat_template:
-        raise NotImplementedError("--apply_chat_template is outside the hot path")
     rank, world, dev = init_distributed(args.d)
     random.seed(args.seed)
     torch.manual_seed(args.seed)
     from .gpt import GPT
     from .relprompt import GPT as RelGPT
-    from .tokenizer import load_tokenizer
+    from .tokenizer import load_tokenizer, apply_eos_override
     cfg = config_from_args(args)
     tokenizer = load_tokenizer(args.llm_checkpoint, args.tokenizer)
+    apply_eos_override(tokenizer, cfg.name)        # inference/ger.py:196-198 (phi-): decoding stops at <|endoftext|>
     rel = args.prompts_format == "RelPrompt"
     if rel:
         cfg.pool_size = args.pool_size

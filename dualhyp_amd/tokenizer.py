@@ -40,6 +40,10 @@ class ByteTokenizer:
             rest = rest[cut + len(tok):]
         return ids
 
+    def chat_prompt_ids(self, user_text: str, system_text: str) -> List[int]:
+        raise ValueError("--apply_chat_template needs the checkpoint's Hugging Face tokenizer and its chat template; "
+                         "the byte-level stand-in tokenizer has none")
+
     def decode(self, ids: Iterable[int]) -> str:
         """Special tokens are skipped, like `decode(..., skip_special_tokens=True)`; the reference's
         `output[len(tokenizer.decode(encoded)):]` slicing then works on plain text."""
@@ -61,11 +65,46 @@ class _HFTokenizer:
         if got != [first_id, first_id + 1, first_id + 2]:
             raise ValueError(f"reliability tokens got ids {got}, the decoder's added wte rows are {first_id}..{first_id + 2}")
 
+    def set_eos_token(self, token: str) -> None:
+        """The reference's Phi override (inference/ger.py:196-198, finetune/ger.py:119-120): `eos_token` / `eos_token_id` follow."""
+        self.tok.eos_token = token
+        self.eos_token, self.eos_token_id = self.tok.eos_token, self.tok.eos_token_id
+
     def encode(self, text: str) -> List[int]:
         return list(self.tok.encode(text))
 
+    def encode_plain(self, text: str) -> List[int]:
+        """`tokenizer(text, add_special_tokens=False)["input_ids"]` (data/av_dataset.py:236)."""
+        return list(self.tok(text, add_special_tokens=False)["input_ids"])
+
+    def chat_prompt_ids(self, user_text: str, system_text: str) -> List[int]:
+        """`apply_chat_template([system, user], tokenize=True, add_generation_prompt=True)` (data/av_dataset.py:226-235) as a list of
+        ids: transformers 4.x returns the list itself, 5.x a BatchEncoding (its "input_ids"), either possibly batched."""
+        if not getattr(self.tok, "chat_template", None):
+            raise ValueError("--apply_chat_template: the checkpoint's tokenizer has no chat template")
+        r = self.tok.apply_chat_template([{"role": "system", "content": system_text}, {"role": "user", "content": user_text}],
+                                         tokenize=True, add_generation_prompt=True)
+        if hasattr(r, "keys"):
+            r = r["input_ids"]
+        if hasattr(r, "tolist"):
+            r = r.tolist()
+        if len(r) and isinstance(r[0], (list, tuple)):
+            assert len(r) == 1, "one conversation"
+            r = r[0]
+        return [int(i) for i in r]
+
     def decode(self, ids) -> str:
         return self.tok.decode([int(i) for i in ids])
+
+
+PHI_EOS = "<|endoftext|>"
+
+
+def apply_eos_override(tokenizer, config_name: str) -> None:
+    """Both reference harnesses end Phi's targets and decoding at "<|endoftext|>" (`'phi-' in config.name.lower()`,
+    inference/ger.py:196-198, finetune/ger.py:119-120).  The byte-level stand-in has no such token and keeps its EOS."""
+    if "phi-" in config_name.lower() and hasattr(tokenizer, "set_eos_token"):
+        tokenizer.set_eos_token(PHI_EOS)
 
 
 def load_tokenizer(checkpoint_dir: Union[str, Path], kind: str = "auto"):

@@ -398,7 +398,9 @@ typedef struct dh_model_desc {
 typedef struct dh_engine dh_engine;
 
 /* Allocates KV cache [n_layer][max_batch, g, s_max, hs] x2, activations for up to
- * max_tokens packed tokens and the decode-graph state. */
+ * max_tokens packed tokens and the decode-graph state.  head_size 64, 96 or 128 (every attention
+ * entry point takes the same three; dh_linear_qkv_*rope_cache_bf16 only 64 and 128).  Fails before
+ * allocating when the KV cache alone exceeds the device's free memory. */
 int dh_engine_create(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens,
                      dh_engine** h_out);
 void dh_engine_destroy(dh_engine* e);
