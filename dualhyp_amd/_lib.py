@@ -70,6 +70,7 @@ SIGNATURES = {
     "dh_attn_decode_work_bytes": (I64, [I, I, I, I]),
     "dh_attn_decode_bf16": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "dh_sample_bf16": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P]),
+    "dh_sample_rows_bf16": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P]),
     "dh_quant_rows_fp8": (I, [P, P, P, I, I, P]),
     "dh_rmsnorm_quant_fp8": (I, [P, P, P, P, P, I, I, F, P, P]),
     "dh_linear_fp8": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
@@ -86,8 +87,10 @@ SIGNATURES = {
     "dh_cross_entropy_bwd": (I, [P, I, P, P, P, P, I, I, P]),
     "dh_engine_forward": (I, [P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, P, P, P]),
     "dh_engine_forward_at": (I, [P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, I, P, P, P]),
+    "dh_engine_forward_slots": (I, [P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, I, P, P, P]),
     "dh_engine_set_cpu_rsqrt_emulation": (I, [P, I, I]),
     "dh_engine_decode": (I, [P, P, I, P, P, I, I, F, I, I64, U64, I, P]),
+    "dh_engine_decode_rows": (I, [P, P, I, P, P, P, I, I, P, P, I, I, F, I, I64, U64, P]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),
     "dh_engine_get_timing": (I, [P, I, C.POINTER(C.c_double), C.POINTER(I64)]),

@@ -10,6 +10,9 @@
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
                    const int32_t* step_dev, void* stream);
+int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                        const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
+                        int top_k, int64_t eos_id, uint64_t seed, void* stream);
 
 namespace {
 
@@ -46,6 +49,7 @@ struct dh_engine {
            *act = nullptr, *xlast = nullptr, *logits = nullptr;
     int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B]
     int32_t *last_row = nullptr, *step_dev = nullptr;
+    int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* last_meta = nullptr;                       // [ones | position of the last token] x [B]: the pruned last layer's attention call
     bf16_t *att_last = nullptr, *xn_last = nullptr, *act_last = nullptr;   // its n_seq-row operands
     uint8_t *row_tail = nullptr, *last_tail = nullptr, *ones = nullptr;   // Q11 rsqrt emulation flags
@@ -63,12 +67,23 @@ struct dh_engine {
     hipStream_t gstream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_stage = nullptr;
     // captured decode steps, keyed by everything baked into the graph (a few batch sizes alternate in practice)
-    struct GKey { int64_t* tokens; int tok_ld; int32_t *length, *done; int n_seq, top_k; float temp; int64_t eos; uint64_t seed; int rsqrt_vec, tiled_rows; };
+    // (limit, row_seq, row_slot, n_all, max_new: the row-list step of dh_engine_decode_rows; null / 0 in dh_engine_decode's keys)
+    struct GKey {
+        int64_t* tokens; int tok_ld; int32_t *length, *done; int n_seq, top_k; float temp; int64_t eos; uint64_t seed; int rsqrt_vec, tiled_rows;
+        const int32_t *limit, *row_seq, *row_slot; int n_all, max_new;
+        bool operator==(const GKey& k) const {
+            return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
+                   top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
+                   tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
+                   n_all == k.n_all && max_new == k.max_new;
+        }
+    };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
     std::vector<GEntry> graphs;
     uint64_t graph_clock = 0;
     int last_ntok = 0;
     int slot_base = 0;         // first KV-cache slot of the sequences of the current forward call
+    const int32_t* seq_slot = nullptr;   // device array: KV slot of sequence / row i of the current call (set by every entry point)
     bool capturing = false;   // no event records inside a stream capture
     bool phase_decode = false; // single-token-per-sequence call: weight-streaming GEMMs + split-KV attention
     bool decode_tiled = false; // ... except that this step's row count put it in the tiled class (g_decode_tiled_rows)
@@ -99,6 +114,28 @@ __global__ void decode_prep_kernel(const int64_t* __restrict__ tokens, int tok_l
         kv_len[i] = n;
     }
     if (i == 0) *step_dev += 1;
+}
+
+// decode_prep_kernel over a row list: row r works on sequence u = row_seq[r] (its token buffer row, its length) in KV slot
+// row_slot[r].  A row list entry outside [0, n_all) x [0, max_batch) never comes from the entry point's callers; it is mapped
+// to sequence 0 / slot 0 positions that exist rather than trusted.
+__global__ void decode_prep_rows_kernel(const int64_t* __restrict__ tokens, int tok_ld, const int32_t* __restrict__ length,
+                                        const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_slot,
+                                        int64_t* __restrict__ ids, int32_t* __restrict__ tok_slot, int32_t* __restrict__ tok_pos,
+                                        int32_t* __restrict__ kv_len, int n_rows, int n_all, int max_batch, int s_max) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_rows) {
+        int u = row_seq[r], slot = row_slot[r];
+        u = u < 0 || u >= n_all ? 0 : u;
+        slot = slot < 0 || slot >= max_batch ? 0 : slot;
+        int n = length[u];
+        const int cap = s_max < tok_ld ? s_max : tok_ld;
+        n = n < 1 ? 1 : (n > cap ? cap : n);         // never index outside the cache or the token buffer
+        ids[r] = tokens[(size_t)u * tok_ld + n - 1];
+        tok_slot[r] = slot;
+        tok_pos[r] = n - 1;
+        kv_len[r] = n;
+    }
 }
 
 __global__ void set_i32_kernel(int32_t* p, int32_t v) { *p = v; }
@@ -150,7 +187,7 @@ int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q
     e->phase_decode = decode;
     const dh_model_desc& D = e->d;
     const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
-    int32_t* seq_slot = e->seq_meta + e->slot_base;      // identity: sequence i of the call lives in slot base+i
+    const int32_t* seq_slot = e->seq_slot;               // forward_at / decode: the identity at seq_meta + base (sequence i in slot base+i)
     int32_t* q_start = e->seq_meta + e->max_batch;
     int32_t* q_len = e->seq_meta + 2 * e->max_batch;
     int32_t* kv_pos0 = e->seq_meta + 3 * e->max_batch;   // decode: kv_len
@@ -259,7 +296,7 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
     e->phase_decode = decode;
     const dh_model_desc& D = e->d;
     const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
-    int32_t* seq_slot = e->seq_meta + e->slot_base;
+    const int32_t* seq_slot = e->seq_slot;
     int32_t* q_start = e->seq_meta + e->max_batch;
     int32_t* q_len = e->seq_meta + 2 * e->max_batch;
     int32_t* kv_pos0 = e->seq_meta + 3 * e->max_batch;   // decode: kv_len
@@ -372,12 +409,12 @@ int pick_ksplit(int tiles, int nks) {
 }
 
 // Single-token step for n_seq <= MAX_DECODE_ROWS sequences: 7 launches per layer (decode_fused.hip).  Leaves
-// ln_f(x) in e->xn.  kv_len lives in seq_meta[3B..], seq_slot in seq_meta[0..].
+// ln_f(x) in e->xn.  kv_len lives in seq_meta[3B..], seq_slot in e->seq_slot.
 int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t* tail_flags, hipStream_t s) {
     const dh_model_desc& D = e->d;
     const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
     const uint8_t* rt = e->rsqrt_vec > 0 ? tail_flags : nullptr;
-    const int32_t* seq_slot = e->seq_meta + e->slot_base;
+    const int32_t* seq_slot = e->seq_slot;
     const int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
     e->phase_decode = true;
     int rc;
@@ -505,6 +542,7 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     rc |= dmalloc(e, &e->xn_last, (size_t)max_batch * d);
     rc |= dmalloc(e, &e->act_last, (size_t)max_batch * desc->intermediate);
     rc |= dmalloc(e, &e->step_dev, 1);
+    rc |= dmalloc(e, &e->slot_list, (size_t)max_batch);
     rc |= dmalloc(e, &e->dec_ids, (size_t)max_batch);
     rc |= dmalloc(e, &e->part32, (size_t)16 * (max_batch < 32 ? 32 : (max_batch < MAX_DECODE_ROWS ? max_batch : MAX_DECODE_ROWS)) * (e->qkv_dim + 48));
     if (e->fp8) {
@@ -538,7 +576,7 @@ extern "C" void dh_engine_destroy(dh_engine* e) {
     if (!e) return;
     for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
     void* ptrs[] = {e->kc, e->vtc, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
-                    e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->dec_ids, e->dec_work,
+                    e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->dec_ids, e->dec_work,
                     e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale};
     for (void* p : ptrs)
         if (p) hipFree(p);
@@ -578,12 +616,43 @@ extern "C" int dh_engine_forward(dh_engine* e, const int64_t* ids, const int32_t
     return dh_engine_forward_at(e, ids, h_seq_len, h_pos0, n_seq, 0, logits_all, logits_last, stream);
 }
 
+namespace {
+int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0, const int32_t* h_slots,
+                 int n_seq, int slot_base, bool prompt_phase, dh_bf16* logits_all, dh_bf16* logits_last, void* stream);
+}
+
 extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0,
                                     int n_seq, int slot_base, dh_bf16* logits_all, dh_bf16* logits_last, void* stream) {
     DH_CHECK(e && ids && h_seq_len && h_pos0, "dh_engine_forward: null argument");
     DH_CHECK(n_seq > 0 && slot_base >= 0 && slot_base + n_seq <= e->max_batch,
              "dh_engine_forward: sequences [%d, %d) exceed max_batch=%d", slot_base, slot_base + n_seq, e->max_batch);
+    return forward_impl(e, ids, h_seq_len, h_pos0, nullptr, n_seq, slot_base, false, logits_all, logits_last, stream);
+}
+
+extern "C" int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0,
+                                       const int32_t* h_slot, int n_seq, int prompt_phase, dh_bf16* logits_all, dh_bf16* logits_last,
+                                       void* stream) {
+    DH_CHECK(e && ids && h_seq_len && h_pos0 && h_slot, "dh_engine_forward_slots: null argument");
+    DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_forward_slots: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
+    std::vector<char> taken(e->max_batch, 0);
+    for (int i = 0; i < n_seq; ++i) {
+        DH_CHECK(h_slot[i] >= 0 && h_slot[i] < e->max_batch, "dh_engine_forward_slots: sequence %d names slot %d of %d", i, h_slot[i], e->max_batch);
+        DH_CHECK(!taken[h_slot[i]], "dh_engine_forward_slots: slot %d is named twice", h_slot[i]);
+        taken[h_slot[i]] = 1;
+    }
+    return forward_impl(e, ids, h_seq_len, h_pos0, h_slot, n_seq, 0, prompt_phase != 0, logits_all, logits_last, stream);
+}
+
+namespace {
+
+// h_slots == nullptr: sequence i lives in slot slot_base + i (the identity array written at engine creation);
+// else in h_slots[i] (distinct, checked by the caller), uploaded to a device array of this call's own.
+// A call of one token per sequence is a decode step and takes the decode kernels — unless prompt_phase says that these
+// are prompts: then the kernels are the prefill's, as they are for a one-token prompt packed with longer ones.
+int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0, const int32_t* h_slots,
+                 int n_seq, int slot_base, bool prompt_phase, dh_bf16* logits_all, dh_bf16* logits_last, void* stream) {
     e->slot_base = slot_base;
+    e->seq_slot = h_slots ? e->slot_list : e->seq_meta + slot_base;
     hipStream_t s = (hipStream_t)stream;
     int n_tok = 0, max_q = 0;
     for (int i = 0; i < n_seq; ++i) {
@@ -593,6 +662,7 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
         n_tok += h_seq_len[i];
         max_q = h_seq_len[i] > max_q ? h_seq_len[i] : max_q;
     }
+    const bool step = max_q == 1 && !prompt_phase;    // one token per sequence == a decode step
     DH_CHECK(n_tok <= e->max_tokens, "dh_engine_forward: %d tokens exceed the workspace capacity %d", n_tok, e->max_tokens);
     // metadata: [tok_slot | tok_pos | seq_slot | q_start | q_len | kv_pos0 | last_row]
     const int B = e->max_batch;
@@ -601,11 +671,12 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
     int32_t *h_slot = hs_, *h_pos = hs_ + e->max_tokens, *h_meta = hs_ + 2 * (size_t)e->max_tokens;
     int t = 0;
     for (int i = 0; i < n_seq; ++i) {
-        h_meta[i] = i;
+        const int slot = h_slots ? h_slots[i] : slot_base + i;
+        h_meta[i] = slot;
         h_meta[B + i] = t;
         h_meta[2 * B + i] = h_seq_len[i];
-        h_meta[3 * B + i] = max_q == 1 ? h_pos0[i] + 1 : h_pos0[i];   // single-token call: kv_len
-        for (int j = 0; j < h_seq_len[i]; ++j, ++t) { h_slot[t] = slot_base + i; h_pos[t] = h_pos0[i] + j; }
+        h_meta[3 * B + i] = step ? h_pos0[i] + 1 : h_pos0[i];   // single-token call: kv_len
+        for (int j = 0; j < h_seq_len[i]; ++j, ++t) { h_slot[t] = slot; h_pos[t] = h_pos0[i] + j; }
         h_meta[4 * B + i] = t - 1;
     }
     // Q11: rows torch's CPU bf16 rsqrt would process in its scalar tail loop
@@ -625,6 +696,7 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
     DH_HIP(hipMemcpyAsync(e->tok_slot, h_slot, n_tok * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DH_HIP(hipMemcpyAsync(e->tok_pos, h_pos, n_tok * sizeof(int32_t), hipMemcpyHostToDevice, s));
     // seq_meta[0..B) (slot of sequence i = i) is written once at engine creation and left alone
+    if (h_slots) DH_HIP(hipMemcpyAsync(e->slot_list, h_meta, n_seq * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DH_HIP(hipMemcpyAsync(e->seq_meta + B, h_meta + B, 3 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DH_HIP(hipMemcpyAsync(e->last_row, h_meta + 4 * B, B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     // last-position logits of a multi-token forward only: the last block runs on the sequences' last rows (g_prune_last_layer)
@@ -637,9 +709,9 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
     DH_HIP(hipEventRecord(e->ev_stage, s));
     int rc;
     // one token per sequence == a decode step (what generate()'s loop issues): same kernels as dh_engine_decode
-    e->decode_tiled = max_q == 1 && g_decode_tiled_rows > 0 && n_seq >= g_decode_tiled_rows;
+    e->decode_tiled = step && g_decode_tiled_rows > 0 && n_seq >= g_decode_tiled_rows;
     if (e->fp8) {
-        if ((rc = run_layers_fp8(e, ids, n_tok, n_seq, max_q, max_q == 1, e->row_tail, s, prune_last))) return rc;
+        if ((rc = run_layers_fp8(e, ids, n_tok, n_seq, max_q, step, e->row_tail, s, prune_last))) return rc;
         e->last_ntok = n_tok;
         if (prune_last) return head_fp8(e, e->xlast, n_seq, logits_last, e->last_tail, s);
         if (logits_all && (rc = head_fp8(e, e->x, n_tok, logits_all, e->row_tail, s))) return rc;
@@ -651,7 +723,7 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
         }
         return 0;
     }
-    const bool fast = max_q == 1 && n_seq <= MAX_DECODE_ROWS && e->d.n_embd % 16 == 0 && !e->decode_tiled;
+    const bool fast = step && n_seq <= MAX_DECODE_ROWS && e->d.n_embd % 16 == 0 && !e->decode_tiled;
     if (fast) {
         if ((rc = run_layers_decode(e, ids, n_seq, e->row_tail, s))) return rc;
         e->last_ntok = n_tok;
@@ -659,7 +731,7 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
         if (logits_last && (rc = head_normed(e, n_seq, logits_last, s))) return rc;
         return 0;
     }
-    if ((rc = run_layers(e, ids, n_tok, n_seq, max_q, max_q == 1, e->row_tail, s, prune_last))) return rc;
+    if ((rc = run_layers(e, ids, n_tok, n_seq, max_q, step, e->row_tail, s, prune_last))) return rc;
     e->last_ntok = n_tok;
     if (prune_last) return head(e, e->xlast, n_seq, logits_last, e->last_tail, s);   // e->xlast: the last rows' final hidden state
     if (logits_all) {
@@ -679,14 +751,9 @@ extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int3
     return 0;
 }
 
-namespace {
-
-int decode_step(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq, float temperature,
-                int top_k, int64_t eos_id, uint64_t seed, hipStream_t s) {
-    int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
-    hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, s, tokens, tok_ld, length, e->dec_ids,
-                       e->tok_slot, e->tok_pos, kv_len, e->step_dev, n_seq, e->s_max);
-    DH_LAUNCH_CHECK();
+// One single-token step of the layer stack + lm_head over n_seq rows whose ids / tok_slot / tok_pos / kv_len a prep kernel
+// has just written and whose KV slots e->seq_slot names: logits in e->logits.  The kernel family is the row count's.
+int decode_forward(dh_engine* e, int n_seq, hipStream_t s) {
     int rc;
     e->decode_tiled = g_decode_tiled_rows > 0 && n_seq >= g_decode_tiled_rows;
     if (e->fp8) {
@@ -699,34 +766,41 @@ int decode_step(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int3
         if ((rc = run_layers(e, e->dec_ids, n_seq, n_seq, 1, true, e->ones, s))) return rc;
         if ((rc = head(e, e->x, n_seq, e->logits, e->ones, s))) return rc;
     }
+    return 0;
+}
+
+int decode_step(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq, float temperature,
+                int top_k, int64_t eos_id, uint64_t seed, hipStream_t s) {
+    int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
+    hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, s, tokens, tok_ld, length, e->dec_ids,
+                       e->tok_slot, e->tok_pos, kv_len, e->step_dev, n_seq, e->s_max);
+    DH_LAUNCH_CHECK();
+    int rc;
+    if ((rc = decode_forward(e, n_seq, s))) return rc;
     // the per-step RNG counter lives in step_dev (incremented by decode_prep_kernel)
     return dh_sample_impl(e->logits, e->d.vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id,
                           seed, 0, e->step_dev, s);
 }
 
-}  // namespace
-
-extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
-                                int n_steps, float temperature, int top_k, int64_t eos_id, uint64_t seed,
-                                int first_step, void* stream) {
-    DH_CHECK(e && tokens && length && done, "dh_engine_decode: null argument");
-    DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
-    DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
-    if (n_steps <= 0) return 0;
-    e->slot_base = 0;
-    hipStream_t s = (hipStream_t)stream;
-    // seq_slot (seq_meta[0..B)) is the identity from engine creation on; nothing here touches the host
-    // staging buffer, so the call never waits for the stream (several engines can be driven back to back)
-    hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
+// decode_step over a row list (dh_engine_decode_rows): the prep and the sampling kernel index the per-sequence arrays through
+// row_seq, the layers run on the n_rows rows as they do in decode_step
+int decode_rows_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
+    int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
+    hipLaunchKernelGGL(decode_prep_rows_kernel, dim3(cdiv(k.n_seq, 64)), dim3(64), 0, s, k.tokens, k.tok_ld, k.length, k.row_seq,
+                       k.row_slot, e->dec_ids, e->tok_slot, e->tok_pos, kv_len, k.n_seq, k.n_all, e->max_batch, e->s_max);
     DH_LAUNCH_CHECK();
-    // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
-    const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows};
+    int rc;
+    if ((rc = decode_forward(e, k.n_seq, s))) return rc;
+    return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
+                               k.max_new, k.temp, k.top_k, k.eos, k.seed, s);
+}
+
+// n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
+int launch_steps(dh_engine* e, const dh_engine::GKey& key, int n_steps, hipStream_t s) {
+    const bool rows = key.row_seq != nullptr;
     hipGraphExec_t gexec = nullptr;
     for (auto& g : e->graphs) {
-        const dh_engine::GKey& k = g.key;
-        if (k.tokens == key.tokens && k.tok_ld == key.tok_ld && k.length == key.length && k.done == key.done &&
-            k.n_seq == key.n_seq && k.top_k == key.top_k && k.temp == key.temp && k.eos == key.eos && k.seed == key.seed &&
-            k.rsqrt_vec == key.rsqrt_vec && k.tiled_rows == key.tiled_rows) {
+        if (g.key == key) {
             gexec = g.exec;
             g.used = ++e->graph_clock;
             break;
@@ -739,7 +813,8 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
         hipGraph_t graph = nullptr;
         DH_HIP(hipStreamBeginCapture(e->gstream, hipStreamCaptureModeThreadLocal));
         e->capturing = true;
-        int rc = decode_step(e, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, e->gstream);
+        int rc = rows ? decode_rows_step(e, key, e->gstream)
+                      : decode_step(e, key.tokens, key.tok_ld, key.length, key.done, key.n_seq, key.temp, key.top_k, key.eos, key.seed, e->gstream);
         e->capturing = false;
         hipError_t ce = hipStreamEndCapture(e->gstream, &graph);
         if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
@@ -761,6 +836,44 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_HIP(hipEventRecord(e->ev_out, e->gstream));
     DH_HIP(hipStreamWaitEvent(s, e->ev_out, 0));
     return 0;
+}
+
+}  // namespace
+
+extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
+                                int n_steps, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                int first_step, void* stream) {
+    DH_CHECK(e && tokens && length && done, "dh_engine_decode: null argument");
+    DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
+    DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
+    if (n_steps <= 0) return 0;
+    e->slot_base = 0;
+    e->seq_slot = e->seq_meta;
+    hipStream_t s = (hipStream_t)stream;
+    // seq_slot (seq_meta[0..B)) is the identity from engine creation on; nothing here touches the host
+    // staging buffer, so the call never waits for the stream (several engines can be driven back to back)
+    hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
+    DH_LAUNCH_CHECK();
+    // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
+    const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
+                              nullptr, nullptr, nullptr, 0, 0};
+    return launch_steps(e, key, n_steps, s);
+}
+
+extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, const int32_t* limit,
+                                     int n_seq, int max_new_tokens, const int32_t* row_seq, const int32_t* row_slot, int n_rows,
+                                     int n_steps, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
+    DH_CHECK(e && tokens && length && done && limit && row_seq && row_slot, "dh_engine_decode_rows: null argument");
+    DH_CHECK(n_rows > 0 && n_rows <= e->max_batch, "dh_engine_decode_rows: n_rows=%d exceeds max_batch=%d", n_rows, e->max_batch);
+    DH_CHECK(n_seq > 0 && tok_ld > 0 && max_new_tokens > 0, "dh_engine_decode_rows: bad shape");
+    DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
+    if (n_steps <= 0) return 0;
+    e->slot_base = 0;
+    e->seq_slot = row_slot;
+    // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
+    const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
+                              limit, row_seq, row_slot, n_seq, max_new_tokens};
+    return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
 extern "C" int dh_engine_set_cpu_rsqrt_emulation(dh_engine* e, int vec_width, int whole_call) {

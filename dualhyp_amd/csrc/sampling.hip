@@ -19,15 +19,11 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 
 constexpr int NT = 1024;
 
-__global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
-                                                    int64_t* __restrict__ tokens, int tok_ld,
-                                                    int32_t* __restrict__ length, int32_t* __restrict__ done,
-                                                    float temperature, int top_k, int64_t eos_id, uint64_t seed,
-                                                    int step_arg, const int32_t* __restrict__ step_dev) {
-    const int seq = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (done[seq]) return;
-    const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
-    const bf16_t* lg = logits + (size_t)seq * vocab;
+// The pick of one sequence's next token from its logits row `lg`, by the whole 1024-thread block; every thread
+// returns it.  The draw is keyed by (seed, step, seq).
+__device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k,
+                                          uint64_t seed, int step, int seq) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float s_f[NT / 64];
     __shared__ int s_i[NT / 64];
     __shared__ unsigned s_hist[256];
@@ -175,6 +171,18 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
         __syncthreads();
         choice = s_i[0];
     }
+    return choice;
+}
+
+__global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
+                                                    int64_t* __restrict__ tokens, int tok_ld,
+                                                    int32_t* __restrict__ length, int32_t* __restrict__ done,
+                                                    float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                                    int step_arg, const int32_t* __restrict__ step_dev) {
+    const int seq = blockIdx.x, tid = threadIdx.x;
+    if (done[seq]) return;
+    const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
+    const int choice = pick_token(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq);
     if (tid == 0) {
         const int n = length[seq];
         if (n < tok_ld) {
@@ -183,6 +191,32 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
         }
         if (eos_id >= 0 && choice == eos_id) done[seq] = 1;
         else if (n + 1 >= tok_ld) done[seq] = 2;   // buffer full
+    }
+}
+
+// sample_kernel over a row list (continuous batching): logits row r belongs to sequence u = row_seq[r] of a token buffer that
+// holds every sequence of the call.  The draw is keyed by (seed, tokens generated so far for u, u) — what sample_kernel's
+// (seed, step, row) is when all sequences start together — so a sequence's ids do not depend on when or where it was scheduled.
+// limit[u] = prompt length + max_new is the sequence's own budget (done = 2 when reached).  Several padding rows may name one
+// finished sequence: they return at once.
+__global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restrict__ logits, int vocab,
+                                                         int64_t* __restrict__ tokens, int tok_ld,
+                                                         int32_t* __restrict__ length, int32_t* __restrict__ done,
+                                                         const int32_t* __restrict__ limit,
+                                                         const int32_t* __restrict__ row_seq, int n_seq, int max_new,
+                                                         float temperature, int top_k, int64_t eos_id, uint64_t seed) {
+    const int u = row_seq[blockIdx.x], tid = threadIdx.x;
+    if (u < 0 || u >= n_seq || done[u]) return;
+    const int n = length[u], lim = min(limit[u], tok_ld);
+    const int step = n - (limit[u] - max_new);          // tokens generated so far
+    const int choice = pick_token(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u);
+    if (tid == 0) {
+        if (n < lim) {
+            tokens[(size_t)u * tok_ld + n] = choice;
+            length[u] = n + 1;
+        }
+        if (eos_id >= 0 && choice == eos_id) done[u] = 1;
+        else if (n + 1 >= lim) done[u] = 2;        // budget spent
     }
 }
 
@@ -206,4 +240,25 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
                               int step, void* stream) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
                           nullptr, stream);
+}
+
+int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                        const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
+                        int top_k, int64_t eos_id, uint64_t seed, void* stream) {
+    DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
+    DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
+    DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
+    DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, tokens, tok_ld,
+                       length, done, limit, row_seq, n_seq, max_new, temperature, top_k, eos_id, seed);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                   int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                   int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
+                               temperature, top_k, eos_id, seed, stream);
 }

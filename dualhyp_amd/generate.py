@@ -99,6 +99,106 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     return out
 
 
+class _StreamBackend:
+    """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
+
+    def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing) -> None:
+        N, dev = len(prompts), eng.device
+        self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
+        tok_ld = max(lens) + max_new_tokens
+        # row N is the dummy sequence of the padding rows: one token, finished, owner of the spare slot
+        self.tokens = torch.nn.functional.pad(torch.nn.utils.rnn.pad_sequence([p.to(dev) for p in prompts], batch_first=True),
+                                              (0, 0, 0, 1))
+        self.tokens = torch.nn.functional.pad(self.tokens, (0, tok_ld - self.tokens.size(1))).contiguous()
+        self.length = torch.tensor(lens + [1], dtype=torch.int32, device=dev)
+        self.limit = torch.tensor([n + max_new_tokens for n in lens] + [1], dtype=torch.int32, device=dev)
+        self.done = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+        self.done[N] = 2
+        self.row_seq, self.row_slot = eng.row_arrays()
+        self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
+
+    def _timed(self, key):
+        if self.events is None:
+            return None
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self.events[key].append(ev)
+        ev[0].record()
+        return ev[1]
+
+    def prefill(self, seqs, slots) -> None:
+        end = self._timed("prefill_ms")
+        dev = self.eng.device
+        packed = torch.cat([self.prompts[u].to(dev).reshape(-1) for u in seqs])
+        # a chunk of one-token prompts only is still a prompt forward (the engine would take it for a decode step) — unless the whole
+        # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
+        last = self.eng.forward_slots(packed, [self.lens[u] for u in seqs], list(slots), prompt_phase=max(self.lens) > 1)
+        ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
+                        self.max_new, **self.kw)
+        if end:
+            end.record()
+
+    def decode(self, row_seq, row_slot, n_steps) -> None:
+        n = len(row_seq)
+        rows = torch.tensor([row_seq, row_slot], dtype=torch.int32).to(self.eng.device)   # one upload per chunk
+        end = self._timed("decode_ms")
+        self.row_seq[:n].copy_(rows[0])
+        self.row_slot[:n].copy_(rows[1])
+        self.eng.decode_rows(self.tokens, self.length, self.done, self.limit, self.max_new, n, n_steps, self.kw["temperature"],
+                             self.kw["top_k"], self.kw["eos_id"], self.kw["seed"])
+        if end:
+            end.record()
+
+    def finished(self, seqs):
+        flags = self.done.tolist()          # the one small read-back per chunk (it synchronises the stream)
+        return [u for u in seqs if flags[u]]
+
+
+@torch.inference_mode()
+def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
+                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
+                    prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None):
+    """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
+    `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
+    budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
+    launched over the live rows only (rounded up to one of at most 8 row counts).  generate_batch steps all of its rows until
+    the last one has finished and starts nothing meanwhile.
+
+    A sequence's ids do not depend on the schedule: no kernel's per-row arithmetic depends on the row count or the packing
+    (an fp8 engine's two row classes are never mixed within a call), and the multinomial draw is keyed by
+    (seed, sequence index, tokens generated so far)."""
+    from .schedule import StreamScheduler
+    N = len(prompts)
+    assert N > 0 and max_new_tokens > 0
+    lens = [int(p.numel()) for p in prompts]
+    need_pos = max(lens) + max_new_tokens - 1
+    if model.max_seq_length < need_pos:
+        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
+    # slots 0..max_rows-1 and the spare one; a prefill packs at most the prefill_batch longest prompts
+    eng = model.engine(sched.max_rows + 1, need_pos, sum(sorted(lens)[-prefill_batch:]), exact=True)
+    eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
+    be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
+                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing)
+    sched.run(be)
+    model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
+    length_h = be.length.tolist()
+    done_h = be.done.tolist()
+    assert all(done_h[:N]), "generate_stream ended with an unfinished sequence"
+    if timing is not None:   # the read-back above has synchronised the stream
+        for key, evs in be.events.items():
+            timing[key] = timing.get(key, 0.0) + sum(a.elapsed_time(b) for a, b in evs)
+        timing["decode_steps"] = timing.get("decode_steps", 0) + sched.decode_steps
+        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + sched.decode_row_steps
+        timing["launch_rows"] = set(timing.get("launch_rows", ())) | sched.launch_rows
+    out: List[torch.Tensor] = []
+    for i in range(N):
+        n = min(length_h[i], lens[i] + max_new_tokens)
+        if done_h[i] == 1:
+            n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
+        out.append(be.tokens[i, :n])
+    return out
+
+
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None) -> torch.Tensor:

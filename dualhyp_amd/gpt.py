@@ -386,6 +386,40 @@ class _Engine:
                 -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(first_step),
                 torch.cuda.current_stream().cuda_stream))
 
+    def forward_slots(self, ids: torch.Tensor, seq_len: List[int], slots: List[int], prompt_phase: bool = False) -> torch.Tensor:
+        """Prompt forward (positions from 0) of sequence i into KV slot slots[i]: the last positions' logits
+        (dh_engine_forward_slots).  prompt_phase: prefill kernels even when every sequence has one token."""
+        n = len(seq_len)
+        ids = ids.reshape(-1)
+        assert len(slots) == n and ids.numel() == int(sum(seq_len)) and ids.dtype == torch.int64 and ids.is_cuda
+        ids = ids.contiguous()
+        ll = torch.empty((n, self.vocab), dtype=torch.bfloat16, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_forward_slots(self.handle, ids.data_ptr(), (C.c_int32 * n)(*seq_len), (C.c_int32 * n)(*([0] * n)),
+                                                        (C.c_int32 * n)(*slots), n, int(prompt_phase), None, ll.data_ptr(),
+                                                        torch.cuda.current_stream().cuda_stream))
+        return ll
+
+    def row_arrays(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The (row_seq, row_slot) device arrays of decode_rows: allocated once per engine, so their addresses stay
+        what the captured steps were keyed by."""
+        if getattr(self, "_rows", None) is None:
+            self._rows = (torch.zeros(self.max_batch, dtype=torch.int32, device=self.device),
+                          torch.zeros(self.max_batch, dtype=torch.int32, device=self.device))
+        return self._rows
+
+    def decode_rows(self, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor, max_new_tokens: int,
+                    n_rows: int, n_steps: int, temperature: float, top_k: Optional[int], eos_id: Optional[int], seed: int) -> None:
+        """n_steps decode steps over the first n_rows entries of row_arrays() (dh_engine_decode_rows)."""
+        row_seq, row_slot = self.row_arrays()
+        assert 0 < n_rows <= self.max_batch and length.numel() == done.numel() == limit.numel() == tokens.size(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_decode_rows(
+                self.handle, tokens.data_ptr(), tokens.size(1), length.data_ptr(), done.data_ptr(), limit.data_ptr(), tokens.size(0),
+                int(max_new_tokens), row_seq.data_ptr(), row_slot.data_ptr(), int(n_rows), int(n_steps), float(temperature),
+                0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1),
+                torch.cuda.current_stream().cuda_stream))
+
     def set_rsqrt_emulation(self, vec_width: int, whole_call: bool) -> None:
         _lib.check(self.lib.dh_engine_set_cpu_rsqrt_emulation(self.handle, int(vec_width), int(whole_call)))
 

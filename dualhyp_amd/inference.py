@@ -142,7 +142,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     from pathlib import Path
     from .checkpoint import load_checkpoint
     from .data import HypothesesDataset, prompt_ids
-    from .generate import generate_batch
+    from .generate import generate_batch, generate_stream
     if adapter_path:
         sd = load_checkpoint(adapter_path)
         missing, unexpected = model.load_state_dict(sd, strict=False)
@@ -189,14 +189,16 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     eos = tokenizer.eos_token_id
 
     # --decode_batch is a throughput knob tuned on TinyLlama (2 x 22.5 KB of KV per position); the KV cache is allocated for
-    # decode_batch x (longest prompt + max_new_tokens) positions, so bound it by what the device has free (Llama-3-8B: 131 KB per
-    # position — 640 x 1700 positions would be 140 GB)
+    # decode_batch x (longest prompt + max_new_tokens) positions (--schedule continuous: its decode rows, plus one spare slot), so
+    # bound it by what the device has free (Llama-3-8B: 131 KB per position — 640 x 1700 positions would be 140 GB)
     if torch.cuda.is_available() and model.transformer.wte.weight.is_cuda:
         c_ = model.config
         kv_per_pos = c_.n_layer * 2 * c_.n_query_groups * c_.head_size * 2
         longest = max((int(e["input_ids_no_response"].numel()) for e in examples), default=1) + args.max_new_tokens
         free, _total = torch.cuda.mem_get_info(model.transformer.wte.weight.device)
         fit = int(0.8 * free // max(kv_per_pos * longest, 1))
+        if getattr(args, "schedule", "batch") == "continuous" and fit > 1:
+            fit -= 1                                   # the spare slot of the padding rows
         if fit < 1:
             raise RuntimeError(f"not enough device memory for one sequence of {longest} positions ({kv_per_pos * longest / 2**30:.1f} GiB of KV cache)")
         if fit < args.decode_batch:
@@ -204,13 +206,19 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
                   f"{free / 2**30:.0f} GiB free")
             args.decode_batch = fit
 
+    continuous = getattr(args, "schedule", "batch") == "continuous"
+
     def gen(prompts):
         dev = model.transformer.wte.weight.device
+        if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
+            outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
+                                   max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)))
+            return [o.cpu() for o in outs]
         outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                               prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)))
         return [o.cpu() for o in outs]
 
-    out = run_inference(gen, examples, tokenizer.decode, batch_size=args.decode_batch, rank=rank, world=world,
+    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
     if mask_stats:
@@ -261,6 +269,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
     p.add_argument("--decode_batch", type=int, default=640,
                    help="utterances decoded jointly (one weight stream per step for all of them; bench.py: 260 utt/s at 32, 770 at 640); "
                         "a sequence's tokens do not depend on it")
+    p.add_argument("--schedule", choices=("batch", "continuous"), default="batch",
+                   help="batch: --decode_batch utterances at a time, each batch stepped until its last sequence has finished; continuous: "
+                        "--decode_batch decode rows over the whole shard, finished rows are retired and refilled (generate_stream); "
+                        "the predictions do not depend on it")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)

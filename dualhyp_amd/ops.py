@@ -212,6 +212,22 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
                                      int(seed) & ((1 << 64) - 1), int(step), _stream()))
 
 
+def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor,
+                row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
+                eos_id: Optional[int] = None, seed: int = 0) -> None:
+    """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16."""
+    k = _Keep()
+    logits = _dev(logits, name="logits")
+    n_rows, vocab = logits.shape
+    n_seq = tokens.size(0)
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and row_seq.numel() == n_rows
+    assert length.numel() == done.numel() == limit.numel() == n_seq
+    check(_lib.load().dh_sample_rows_bf16(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
+                                          k(done, torch.int32), k(limit, torch.int32), k(row_seq, torch.int32), n_rows, n_seq,
+                                          int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
+                                          -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream()))
+
+
 def quant_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(uint8 e4m3 [rows, K], fp32 scale [rows]) of bf16 rows; dh_quant_rows_fp8."""
     x = _dev(x, name="x")

@@ -320,6 +320,18 @@ int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
                    int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
                    uint64_t seed, int step, void* stream);
 
+/* dh_sample_bf16 over a row list (continuous batching, dualhyp_amd/generate.py: generate_stream): logits row r
+ * belongs to sequence u = row_seq[r] (device int32 [n_rows]) of per-sequence arrays that hold all n_seq sequences
+ * of a call: tokens [n_seq, tok_ld], length / done / limit [n_seq].  limit[u] = prompt length + max_new_tokens is
+ * the sequence's own budget: done[u] = 1 on eos_id, 2 once length[u] reaches limit[u]; rows whose sequence has
+ * done != 0 return at once (several padding rows may name one finished sequence).  The top_k != 1 draw is keyed
+ * by (seed, tokens generated so far = length[u] - (limit[u] - max_new_tokens), u): for the sequences of one call
+ * that is dh_sample_bf16's (seed, step, row) when all of them start together, so ids do not depend on the schedule. */
+int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                        int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                        int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                        void* stream);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -424,6 +436,17 @@ int dh_engine_forward(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len
 int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len,
                          const int32_t* h_pos0, int n_seq, int slot_base, dh_bf16* logits_all,
                          dh_bf16* logits_last, void* stream);
+/* Same, with sequence i of the call living in KV-cache slot h_slot[i] (host array): distinct slots in
+ * [0, max_batch), in any order — a prefill into whichever slots finished sequences have freed while the other
+ * slots hold live ones.  The slot list goes to a device array of the call's own; h_slot[i] = base + i gives the
+ * bits of dh_engine_forward_at(base), logits and caches.
+ * prompt_phase: dh_engine_forward(_at) takes a call of one token per sequence for a decode step and runs the decode
+ * kernels, so a one-token PROMPT forwarded alone and the same prompt packed with longer ones go through different
+ * kernel families (different fp32 summation orders).  prompt_phase = 1 says the call is a prompt forward whatever
+ * its lengths: prefill kernels, the bits the sequences have in any pack with a longer prompt.  0 = as forward_at. */
+int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len,
+                            const int32_t* h_pos0, const int32_t* h_slot, int n_seq, int prompt_phase,
+                            dh_bf16* logits_all, dh_bf16* logits_last, void* stream);
 
 /* Reproduce the rsqrt rounding of the reference's CPU path (see dh_rmsnorm_bf16 row_tail):
  * vec_width = lanes of torch's bf16 vector loop on the reference host (32 on AVX-512, 16 on
@@ -442,6 +465,19 @@ int dh_engine_set_cpu_rsqrt_emulation(dh_engine* e, int vec_width, int whole_cal
 int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                      int n_seq, int n_steps, float temperature, int top_k, int64_t eos_id,
                      uint64_t seed, int first_step, void* stream);
+
+/* dh_engine_decode over a ROW LIST: n_steps x { forward of n_rows rows ; dh_sample_rows_bf16 }.  Row r works on
+ * sequence row_seq[r] (its row of tokens, its length / done / limit entry: arrays over all n_seq sequences of the
+ * call, as in dh_sample_rows_bf16) in KV slot row_slot[r].  row_seq and row_slot are device int32 arrays that the
+ * captured step reads when it runs: the caller rewrites their contents between calls (sequences retire, others
+ * take their slots) and keeps their addresses, which are part of the graph key together with n_rows.  Layers,
+ * kernel family and rounding are those of dh_engine_decode at n_rows rows.  A padding row names a sequence with
+ * done != 0 and the slot that sequence owns (it recomputes that sequence's last position in place, as finished
+ * rows of dh_engine_decode do); live rows name distinct slots. */
+int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                          const int32_t* limit, int n_seq, int max_new_tokens, const int32_t* row_seq,
+                          const int32_t* row_slot, int n_rows, int n_steps, float temperature, int top_k,
+                          int64_t eos_id, uint64_t seed, void* stream);
 
 /* Test hook: copy engine state to `dst` (device memory, n_bytes) on `stream`.
  *   what 0: ln_f(x) of the last dh_engine_forward called with logits_all only, [n_tok, d]
