@@ -16,6 +16,7 @@
 //       S^T[key][q] = K.Q^T ; dP^T = V.dO^T ; dS^T = P^T*(dP^T - D[q])
 //       dQ^T[d][q] += K^T[d][key] . dS^T[key][q]    (A = kT fragment,  B = dS^T accumulator)
 #include "common.h"
+#include "tuning.h"
 
 int g_attn_bwd_dkdv_img = 1;    // dh_set_tuning(29, 0): the dkdv kernel with every operand fetched from global memory per wave (A/B)
 int g_attn_bwd_dq_group = 1;    // dh_set_tuning(27, 0): the single-wave dq kernel of rounds 2-3 (A/B)

@@ -1,5 +1,6 @@
-// Error plumbing + device info for the C ABI.
+// Error plumbing, device info and the tuning switchboard of the C ABI.
 #include "common.h"
+#include "tuning.h"
 #include <stdarg.h>
 
 static thread_local char g_err[512] = "";
@@ -29,4 +30,62 @@ extern "C" int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t
     if (h_num_cu) *h_num_cu = p.multiProcessorCount;
     if (h_hbm_bytes) *h_hbm_bytes = (int64_t)p.totalGlobalMem;
     return 0;
+}
+
+// ---- dh_set_tuning: one row per key ------------------------------------------------------------------------------------------
+// A/B switches and forced kernel choices for tools, tests and bench.py --tune, addressed by number.  A value outside a row's
+// filter leaves the knob alone and is refused like an unknown key.
+namespace {
+
+enum Accept { ANY, BOOL /* stored as value != 0 */, RANGE /* a <= value <= b */, ONE_OF /* value is a, b or c */ };
+struct TuningRow { int key; int* knob; Accept accept; int a, b, c; };
+constexpr int NO_MAX = 0x7fffffff;
+
+const TuningRow TUNING[] = {
+    {0, &g_skinny_variant, ANY, 0, 0, 0},
+    {1, &g_gemm_variant, ANY, 0, 0, 0},
+    {2, &g_swiglu2, ANY, 0, 0, 0},
+    {3, &g_mid, ANY, 0, 0, 0},
+    {4, &g_linear_phase, ANY, 0, 0, 0},
+    {5, &g_gemm_gm, RANGE, 0, NO_MAX, 0},
+    {6, &g_dt_min_rows, RANGE, 1, NO_MAX, 0},
+    {7, &g_chain_min_rows, RANGE, 1, NO_MAX, 0},
+    {8, &g_dt_stages, ANY, 0, 0, 0},
+    {9, &g_gemm128_stages, ANY, 0, 0, 0},
+    {10, &g_decode_tiled_rows, RANGE, 0, NO_MAX, 0},
+    {11, &g_rows_ct, RANGE, 0, NO_MAX, 0},
+    {12, &g_fuse_qkv_rope, ANY, 0, 0, 0},
+    {13, &g_mid_wlds, ANY, 0, 0, 0},
+    {14, &g_rows_ng, ONE_OF, 0, 8, 10},
+    {15, &g_dt_wide, ANY, 0, 0, 0},
+    {16, &g_short_kps, ONE_OF, 8, 16, 16},
+    {17, &g_pairs_wn, ONE_OF, 0, 2, 4},
+    {18, &g_pairs_min_rows, RANGE, 1, NO_MAX, 0},
+    {19, &g_fp8_tile, ONE_OF, 0, 128, 256},
+    {20, &g_fp8_gm, RANGE, 0, 64, 0},
+    {21, &g_pairs_wt, BOOL, 0, 0, 0},
+    {22, &g_w4_persist, RANGE, 0, 2, 0},
+    {23, &g_prune_last_layer, BOOL, 0, 0, 0},
+    {24, &g_w4_fast_epi, ANY, 0, 0, 0},   // only bit 2 selects anything today (gemm256.hip)
+    {25, &g_w4_persist_qkv, BOOL, 0, 0, 0},
+    {26, &g_tn_mfma, BOOL, 0, 0, 0},
+    {27, &g_attn_bwd_dq_group, BOOL, 0, 0, 0},
+    {28, &g_tail_split, BOOL, 0, 0, 0},
+    {29, &g_attn_bwd_dkdv_img, BOOL, 0, 0, 0},
+    {30, &g_w4_persist_lora, BOOL, 0, 0, 0},
+    {31, &g_skinny_n, BOOL, 0, 0, 0},
+};
+
+}  // namespace
+
+extern "C" int dh_set_tuning(int key, int value) {
+    for (const TuningRow& r : TUNING) {
+        if (r.key != key) continue;
+        if (r.accept == RANGE && (value < r.a || value > r.b)) break;
+        if (r.accept == ONE_OF && value != r.a && value != r.b && value != r.c) break;
+        *r.knob = r.accept == BOOL ? value != 0 : value;
+        return 0;
+    }
+    dh_set_error("dh_set_tuning: unknown key %d", key);
+    return 1;
 }

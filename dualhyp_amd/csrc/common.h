@@ -181,6 +181,14 @@ void dh_set_error(const char* fmt, ...);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
+// dh_sample_rows_bf16
+int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
+                   float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, void* stream);
+int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                        const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
+                        int top_k, int64_t eos_id, uint64_t seed, void* stream);
+
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads
 // racing on the first launch both set it, which is harmless.  `kernel` must be parenthesised if it contains commas.

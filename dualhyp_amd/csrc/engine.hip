@@ -7,23 +7,6 @@
 #include "common.h"
 #include "gemm.h"
 
-int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
-                   int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
-                   const int32_t* step_dev, void* stream);
-int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
-                        const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
-                        int top_k, int64_t eos_id, uint64_t seed, void* stream);
-
-namespace {
-
-struct Timing {
-    bool on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[4];
-    std::vector<hipEvent_t> pool;
-};
-
-}  // namespace
-
 constexpr int MAX_DECODE_ROWS = 2048;  // single-token calls up to here take the 7-launch streaming path
 // Single-token steps over at least this many rows run the layer on the TILED MFMA GEMMs of the prefill (natural
 // k order) instead of the K-sliced streaming kernels: from a few hundred rows on the step is no longer weight-
@@ -47,7 +30,7 @@ struct dh_engine {
     bf16_t *kc = nullptr, *vtc = nullptr;             // [L][B][G][S][HS], [L][B][G][HS][S]
     bf16_t *x = nullptr, *xn = nullptr, *qkv = nullptr, *qrot = nullptr, *att = nullptr, *xa = nullptr,
            *act = nullptr, *xlast = nullptr, *logits = nullptr;
-    int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B]
+    int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B], read through seq_meta() below
     int32_t *last_row = nullptr, *step_dev = nullptr;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* last_meta = nullptr;                       // [ones | position of the last token] x [B]: the pruned last layer's attention call
@@ -60,7 +43,7 @@ struct dh_engine {
     bool fp8 = false;                                   // e4m3 weights + channel scales (csrc/fp8.hip)
     uint8_t* xq = nullptr;                              // fp8 mode: quantised activations [max_tokens, max(d, I)]
     float* xscale = nullptr;                            // fp8 mode: their per-token scales [max_tokens]
-    int32_t* h_stage = nullptr;                         // pinned staging for the metadata
+    int32_t* h_stage = nullptr;                         // pinned staging for the metadata, carved by stage() below
     size_t cache_layer_elems = 0;
     int64_t dev_bytes = 0;
     // decode graph
@@ -81,13 +64,14 @@ struct dh_engine {
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
     std::vector<GEntry> graphs;
     uint64_t graph_clock = 0;
-    int last_ntok = 0;
-    int slot_base = 0;         // first KV-cache slot of the sequences of the current forward call
     const int32_t* seq_slot = nullptr;   // device array: KV slot of sequence / row i of the current call (set by every entry point)
     bool capturing = false;   // no event records inside a stream capture
     bool phase_decode = false; // single-token-per-sequence call: weight-streaming GEMMs + split-KV attention
     bool decode_tiled = false; // ... except that this step's row count put it in the tiled class (g_decode_tiled_rows)
-    Timing tm;
+    struct Timing {
+        bool on = false;
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[4];
+    } tm;
 };
 
 namespace {
@@ -99,35 +83,72 @@ int dmalloc(dh_engine* e, T** p, size_t n) {
     return 0;
 }
 
-// ids of the step, positions and lengths derived on device from (tokens, length)
-__global__ void decode_prep_kernel(const int64_t* __restrict__ tokens, int tok_ld, const int32_t* __restrict__ length,
-                                   int64_t* __restrict__ ids, int32_t* __restrict__ tok_slot,
-                                   int32_t* __restrict__ tok_pos, int32_t* __restrict__ kv_len, int32_t* step_dev,
-                                   int n_seq, int s_max) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_seq) {
-        int n = length[i];
-        n = n < 1 ? 1 : (n > s_max ? s_max : n);     // never index outside the cache
-        ids[i] = tokens[(size_t)i * tok_ld + n - 1];
-        tok_slot[i] = i;
-        tok_pos[i] = n - 1;
-        kv_len[i] = n;
-    }
-    if (i == 0) *step_dev += 1;
+// ---- metadata ----------------------------------------------------------------------------------------------------------------
+// Per-sequence arrays of the current call on the device.  seq_slot is the entry point's choice (e->seq_slot); the other three are
+// rows 1..3 of e->seq_meta (4 x [max_batch], contiguous: forward_impl uploads them with one copy).  Row 0 is the identity, written
+// once at engine creation: sequence i in slot i.
+struct SeqMeta {
+    const int32_t* seq_slot;
+    int32_t *q_start, *q_len;
+    int32_t* kv;   // prefill: kv_pos0, the position of a sequence's first query; single-token step: kv_len
+};
+SeqMeta seq_meta(const dh_engine* e) {
+    const int B = e->max_batch;
+    return {e->seq_slot, e->seq_meta + B, e->seq_meta + 2 * B, e->seq_meta + 3 * B};
 }
 
-// decode_prep_kernel over a row list: row r works on sequence u = row_seq[r] (its token buffer row, its length) in KV slot
-// row_slot[r].  A row list entry outside [0, n_all) x [0, max_batch) never comes from the entry point's callers; it is mapped
-// to sequence 0 / slot 0 positions that exist rather than trusted.
-__global__ void decode_prep_rows_kernel(const int64_t* __restrict__ tokens, int tok_ld, const int32_t* __restrict__ length,
-                                        const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_slot,
-                                        int64_t* __restrict__ ids, int32_t* __restrict__ tok_slot, int32_t* __restrict__ tok_pos,
-                                        int32_t* __restrict__ kv_len, int n_rows, int n_all, int max_batch, int s_max) {
+// The pinned staging buffer, offsets in int32 for T = max_tokens and B = max_batch:
+//   [tok_slot T | tok_pos T | seq_slot, q_start, q_len, kv, last_row: 5 x B | tail flags | last_meta: ones B, last position B]
+// The tail flags are bytes (T per-row flags, then B last-row flags) in a region of T + B int32.
+struct StageLayout { size_t tok_slot, tok_pos, meta, tail, last_meta, total; };
+constexpr StageLayout stage_layout(size_t T, size_t B) {
+    StageLayout L{};
+    L.tok_slot = 0;
+    L.tok_pos = L.tok_slot + T;
+    L.meta = L.tok_pos + T;
+    L.tail = L.meta + 5 * B;
+    L.last_meta = L.tail + T + B;
+    L.total = L.last_meta + 2 * B;
+    return L;
+}
+static_assert(stage_layout(4096, 48).total == 3 * 4096 + 8 * 48 && stage_layout(4096, 48).last_meta == 3 * 4096 + 6 * 48,
+              "the staging layout is part of nothing public, but its size is what the engine has always pinned");
+
+struct Stage {
+    int32_t *tok_slot, *tok_pos;
+    int32_t *seq_slot, *q_start, *q_len, *kv, *last_row;   // contiguous rows of B, as in SeqMeta
+    uint8_t *row_tail, *last_tail;
+    int32_t* last_meta;                                    // [ones | last position] x B
+};
+Stage stage(const dh_engine* e) {
+    const size_t T = e->max_tokens, B = e->max_batch;
+    const StageLayout L = stage_layout(T, B);
+    int32_t* h = e->h_stage;
+    int32_t* m = h + L.meta;
+    uint8_t* tail = reinterpret_cast<uint8_t*>(h + L.tail);
+    return {h + L.tok_slot, h + L.tok_pos, m, m + B, m + 2 * B, m + 3 * B, m + 4 * B, tail, tail + T, h + L.last_meta};
+}
+
+// ---- glue kernels ------------------------------------------------------------------------------------------------------------
+// ids of a decode step, positions and lengths derived on device from (tokens, length).  Row r works on sequence u = row_seq[r] (its
+// token buffer row, its length) in KV slot row_slot[r]; null lists mean u = slot = r.  A row list entry outside [0, n_all) x
+// [0, max_batch) never comes from the entry point's callers; it is mapped to sequence 0 / slot 0, positions that exist, rather than
+// trusted.  The length is clamped to the cache AND the token buffer: neither sampling kernel lets `length` pass tok_ld, so the second
+// bound only matters for a caller who hands in a length that its own buffer cannot hold.
+// step_dev (null: no counter) is the per-step RNG counter of dh_engine_decode's sampling kernel.
+__global__ void decode_prep_kernel(const int64_t* __restrict__ tokens, int tok_ld, const int32_t* __restrict__ length,
+                                   const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_slot,
+                                   int64_t* __restrict__ ids, int32_t* __restrict__ tok_slot, int32_t* __restrict__ tok_pos,
+                                   int32_t* __restrict__ kv_len, int32_t* step_dev, int n_rows, int n_all, int max_batch, int s_max) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r == 0 && step_dev) *step_dev += 1;
     if (r < n_rows) {
-        int u = row_seq[r], slot = row_slot[r];
-        u = u < 0 || u >= n_all ? 0 : u;
-        slot = slot < 0 || slot >= max_batch ? 0 : slot;
+        int u = r, slot = r;
+        if (row_seq) {   // the two lists come together
+            u = row_seq[r], slot = row_slot[r];
+            u = u < 0 || u >= n_all ? 0 : u;
+            slot = slot < 0 || slot >= max_batch ? 0 : slot;
+        }
         int n = length[u];
         const int cap = s_max < tok_ld ? s_max : tok_ld;
         n = n < 1 ? 1 : (n > cap ? cap : n);         // never index outside the cache or the token buffer
@@ -152,11 +173,20 @@ __global__ void gather_rows_kernel(const bf16_t* __restrict__ src, const int32_t
     uint4* t = reinterpret_cast<uint4*>(dst + (size_t)wave * d);
     for (int c = lane; c < d / 8; c += 64) t[c] = s[c];
 }
+// dst[i, :] = src[last_row[i], :] for the n_seq sequences of the call
+int gather_last_rows(dh_engine* e, const bf16_t* src, bf16_t* dst, int n_seq, hipStream_t s) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, src, e->last_row, dst, n_seq, e->d.n_embd);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
 
+// ---- timing + the dense products ---------------------------------------------------------------------------------------------
+// Event pair around what is launched while the object lives (class `which`: 0 prefill GEMMs, 1 decode GEMMs, 2 prefill attention,
+// 3 decode attention); nothing when `on` is false, when timing is off or inside a stream capture.
 struct TimeScope {
     dh_engine* e; int which; hipStream_t s; hipEvent_t a = nullptr, b = nullptr;
-    TimeScope(dh_engine* e_, int w, hipStream_t s_) : e(e_), which(w), s(s_) {
-        if (!e->tm.on || e->capturing) return;
+    TimeScope(dh_engine* e_, int w, hipStream_t s_, bool on = true) : e(e_), which(w), s(s_) {
+        if (!on || !e->tm.on || e->capturing) return;
         hipEventCreate(&a); hipEventCreate(&b);
         hipEventRecord(a, s);
     }
@@ -167,30 +197,138 @@ struct TimeScope {
     }
 };
 
-int linear(dh_engine* e, const bf16_t* x, const bf16_t* w, bf16_t* y, int M, int N, int K, int epi,
-           const bf16_t* w2, const bf16_t* xa, int xa_ld, const bf16_t* lb, int s0, int s1, const bf16_t* va,
-           const bf16_t* vb, const bf16_t* resid, hipStream_t s, bool timed) {
-    // kernel choice is a property of the phase, never of the packing (batch invariance)
-    const int kernel = e->phase_decode && !e->decode_tiled ? 2 : 1;
-    if (timed) {
-        TimeScope t(e, e->phase_decode ? 1 : 0, s);
-        return dh_linear_impl(x, w, y, M, N, K, epi, w2, xa, xa_ld, lb, e->d.lora_scale, s0, s1, va, vb, resid, kernel, s);
-    }
-    return dh_linear_impl(x, w, y, M, N, K, epi, w2, xa, xa_ld, lb, e->d.lora_scale, s0, s1, va, vb, resid, kernel, s);
+// kernel choice is a property of the phase, never of the packing (batch invariance)
+int phase_kernel(const dh_engine* e) { return e->phase_decode && !e->decode_tiled ? 2 : 1; }
+int gemm_class(const dh_engine* e) { return e->phase_decode ? 1 : 0; }
+
+// The bf16 products by epilogue, each ONE launch on the phase's kernel, in the phase's GEMM timing class when `timed`.
+// y = x . w^T [+ resid]
+int plain(dh_engine* e, const bf16_t* x, const bf16_t* w, bf16_t* y, int M, int N, int K, const bf16_t* resid, hipStream_t s,
+          bool timed) {
+    TimeScope t(e, gemm_class(e), s, timed);
+    return dh_linear_impl(x, w, y, M, N, K, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, e->d.lora_scale, 0, 0, nullptr, nullptr, resid,
+                          phase_kernel(e), s);
+}
+// y = silu(x . w_gate^T) * (x . w_up^T)
+int swiglu(dh_engine* e, const bf16_t* x, const bf16_t* w_gate, const bf16_t* w_up, bf16_t* y, int M, int N, int K, hipStream_t s,
+           bool timed) {
+    TimeScope t(e, gemm_class(e), s, timed);
+    return dh_linear_impl(x, w_gate, y, M, N, K, DH_EPI_SWIGLU, w_up, nullptr, 0, nullptr, e->d.lora_scale, 0, 0, nullptr, nullptr,
+                          nullptr, phase_kernel(e), s);
+}
+// y = x . w^T + scale * xa . lora_b^T per column segment [0, split0) / [split0, split1) / [split1, N), xa = x . A^T already computed
+int lora(dh_engine* e, const bf16_t* x, const bf16_t* w, bf16_t* y, int M, int N, int K, const bf16_t* xa, int xa_ld,
+         const bf16_t* lora_b, int split0, int split1, hipStream_t s, bool timed) {
+    TimeScope t(e, gemm_class(e), s, timed);
+    return dh_linear_impl(x, w, y, M, N, K, DH_EPI_LORA, nullptr, xa, xa_ld, lora_b, e->d.lora_scale, split0, split1, nullptr, nullptr,
+                          nullptr, phase_kernel(e), s);
+}
+// the same for one segment, + resid, with x . A^T left to the library: in the GEMM's K loop where the launch runs on the 4-wave
+// 256-tile kernel, else a launch of its own into e->xa (same bits)
+int lora_resid(dh_engine* e, const bf16_t* x, const bf16_t* w, bf16_t* y, int M, int N, int K, const bf16_t* lora_a,
+               const bf16_t* lora_b, const bf16_t* resid, hipStream_t s, bool timed) {
+    TimeScope t(e, gemm_class(e), s, timed);
+    return dh_linear_lora_impl(x, w, y, M, N, K, lora_a, lora_b, e->d.lora_scale, N, N, resid, e->xa, phase_kernel(e), s);
+}
+// y = (x . w^T) * vec_a + vec_b (the lm_head with the logit adapter)
+int adapter(dh_engine* e, const bf16_t* x, const bf16_t* w, bf16_t* y, int M, int N, int K, const bf16_t* vec_a, const bf16_t* vec_b,
+            hipStream_t s, bool timed) {
+    TimeScope t(e, gemm_class(e), s, timed);
+    return dh_linear_impl(x, w, y, M, N, K, DH_EPI_ADAPTER, nullptr, nullptr, 0, nullptr, e->d.lora_scale, 0, 0, vec_a, vec_b, nullptr,
+                          phase_kernel(e), s);
 }
 
+// fp8 GEMM kernel by PHASE, never by packing (the two kernels sum K in different fp32 orders): a prefill is tiled even
+// when a short prompt runs alone; a single-token step streams the weights up to 128 rows (the bench's four batches per
+// decode loop) and is tiled above that — the one documented class boundary of the fp8 decode phase (DESIGN.md §7).
+inline int fp8_kernel(bool decode, int rows) { return decode && rows <= 128 ? 2 : 1; }
+
+// fp8 product of the M quantised rows in e->xq / e->xscale; the weight pointers of dh_layer_weights address e4m3 bytes in this mode
+int linear_fp8(dh_engine* e, const bf16_t* w, const float* ws, bf16_t* y, int M, int N, int K, int epi, const bf16_t* w2,
+               const float* w2s, const bf16_t* resid, hipStream_t s, bool timed) {
+    TimeScope t(e, gemm_class(e), s, timed);
+    return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), ws, y, M, N, K, epi,
+                            reinterpret_cast<const uint8_t*>(w2), w2s, nullptr, nullptr, resid, fp8_kernel(e->phase_decode, M), s);
+}
+
+// ---- the pieces of a layer ---------------------------------------------------------------------------------------------------
+// rope + KV-cache append of the n_tok rows of e->qkv; the rotated queries land in e->qrot
+int rope_append(dh_engine* e, bf16_t* kc, bf16_t* vtc, int n_tok, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    return dh_qkv_rope_cache_bf16(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, kc, vtc, nullptr, nullptr, n_tok,
+                                  D.n_head, D.n_groups, D.head_size, e->s_max, s);
+}
+
+// Attention of e->qrot over one layer's cache into e->att: the split-KV kernel of a single-token step or the prefill kernel.
+// last_rows (last block of a call that wants the last position's logits only, g_prune_last_layer): attention of each sequence's LAST
+// query alone (a one-row tile at position pos0 + len - 1 over the same 64-key steps as in the full call); its n_seq output rows are
+// then gathered into e->att_last and the block's input rows into e->xlast, where the block's n_seq-row second half continues.
+int attention(dh_engine* e, bf16_t* kc, bf16_t* vtc, int n_seq, int max_q_len, bool last_rows, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    const int hs = D.head_size, H = D.n_head, G = D.n_groups;
+    const SeqMeta m = seq_meta(e);
+    int rc;
+    if (last_rows) {
+        {
+            TimeScope t(e, 2, s);
+            if ((rc = dh_attn_prefill_bf16(e->qrot, kc, vtc, m.seq_slot, e->last_row, e->last_meta, e->last_meta + e->max_batch, e->att,
+                                           nullptr, n_seq, 1, H, G, hs, e->s_max, s))) return rc;
+        }
+        if ((rc = gather_last_rows(e, e->att, e->att_last, n_seq, s))) return rc;
+        return gather_last_rows(e, e->x, e->xlast, n_seq, s);
+    }
+    if (e->phase_decode) {
+        TimeScope t(e, 3, s);
+        return dh_attn_decode_bf16(e->qrot, kc, vtc, m.seq_slot, m.kv, e->att, e->dec_work, n_seq, H, G, hs, e->s_max, s);
+    }
+    TimeScope t(e, 2, s);
+    return dh_attn_prefill_bf16(e->qrot, kc, vtc, m.seq_slot, m.q_start, m.q_len, m.kv, e->att, nullptr, n_seq, max_q_len, H, G, hs,
+                                e->s_max, s);
+}
+
+// The half of a block behind the attention, in place on `rows` rows: x += proj(att), x += mlp_proj(swiglu(norm_2(x))).  Called on
+// every row of the call with timed = true, or on the last rows of the last block (attention() above) with timed = false: those
+// n_seq-row launches stream the weights, they are not in the timed class of the large prefill GEMMs, and bench.py does not count their
+// FLOPs either.  A last-rows call is a prefill (its longest sequence has more than one token), so both run the tiled kernel.
+int post_attention(dh_engine* e, const dh_layer_weights& W, int rows, const bf16_t* att, bf16_t* x, bf16_t* xn, bf16_t* act,
+                   const uint8_t* rt, bool timed, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    const int d = D.n_embd, I = D.intermediate;
+    int rc;
+    if ((rc = W.proj_lora_a ? lora_resid(e, att, W.proj_w, x, rows, d, d, W.proj_lora_a, W.proj_lora_b, x, s, timed)
+                            : plain(e, att, W.proj_w, x, rows, d, d, x, s, timed))) return rc;
+    if ((rc = dh_rmsnorm_bf16(x, nullptr, W.norm_2, xn, nullptr, rows, d, D.norm_eps, rt, s))) return rc;
+    if ((rc = swiglu(e, xn, W.fc_1, W.fc_2, act, rows, I, d, s, timed))) return rc;
+    return plain(e, act, W.mlp_proj, x, rows, d, I, x, s, timed);
+}
+
+// The same in fp8 mode: the activations are quantised per row into e->xq / e->xscale in front of every product (by the norm kernel,
+// or by a pass over the attention / SwiGLU output), so a row keeps its bits whichever rows run with it.
+int post_attention_fp8(dh_engine* e, const dh_layer_weights& W, int rows, const bf16_t* att, bf16_t* x, bf16_t* act, const uint8_t* rt,
+                       bool timed, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    const int d = D.n_embd, I = D.intermediate;
+    int rc;
+    if ((rc = dh_quant_rows_fp8(att, e->xq, e->xscale, rows, d, s))) return rc;
+    if ((rc = linear_fp8(e, W.proj_w, W.proj_ws, x, rows, d, d, DH_EPI_PLAIN, nullptr, nullptr, x, s, timed))) return rc;
+    if ((rc = dh_rmsnorm_quant_fp8(x, W.norm_2, nullptr, e->xq, e->xscale, rows, d, D.norm_eps, rt, s))) return rc;
+    if ((rc = linear_fp8(e, W.fc_1, W.fc_1_ws, act, rows, I, d, DH_EPI_SWIGLU, W.fc_2, W.fc_2_ws, nullptr, s, timed))) return rc;
+    if ((rc = dh_quant_rows_fp8(act, e->xq, e->xscale, rows, I, s))) return rc;
+    return linear_fp8(e, W.mlp_proj, W.mlp_proj_ws, x, rows, d, I, DH_EPI_PLAIN, nullptr, nullptr, x, s, timed);
+}
+
+// ---- the layer stacks --------------------------------------------------------------------------------------------------------
 // The layer stack on n_tok packed tokens whose metadata is already on the device.
 // prefill: attention over (seq_slot, q_start, q_len, kv_pos0); decode: one token per sequence.
-int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q_len, bool decode,
-               const uint8_t* tail_flags, hipStream_t s, bool prune_last = false) {
+// prune_last: the last block finishes on the n_seq last rows; their final hidden rows land in e->xlast (where the caller would have
+// gathered them) and e->x keeps that block's input.
+int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q_len, bool decode, const uint8_t* tail_flags,
+               bool prune_last, hipStream_t s) {
     const uint8_t* rt = e->rsqrt_vec > 0 ? tail_flags : nullptr;
+    const uint8_t* rtl = e->rsqrt_vec > 0 ? e->last_tail : nullptr;
     e->phase_decode = decode;
     const dh_model_desc& D = e->d;
-    const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
-    const int32_t* seq_slot = e->seq_slot;               // forward_at / decode: the identity at seq_meta + base (sequence i in slot base+i)
-    int32_t* q_start = e->seq_meta + e->max_batch;
-    int32_t* q_len = e->seq_meta + 2 * e->max_batch;
-    int32_t* kv_pos0 = e->seq_meta + 3 * e->max_batch;   // decode: kv_len
+    const int d = D.n_embd, hs = D.head_size, H = D.n_head, G = D.n_groups;
     int rc;
     if ((rc = dh_embed_bf16(ids, D.wte, e->x, n_tok, d, D.wte_rows, s))) return rc;
     for (int l = 0; l < D.n_layer; ++l) {
@@ -201,11 +339,8 @@ int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q
         // large packed prefills: rope + KV append ride in the QKV GEMM's epilogue (same bits, no pass over the qkv tensor)
         // (not at head size 96: a 96-wide head straddles the 256-column tiles of that epilogue, gemm.hip)
         const bool fuse_qkv = !decode && g_fuse_qkv_rope && hs != 96 && dh_linear_is_big(n_tok, e->qkv_dim, DH_EPI_LORA);
-        // x.A^T: inside the QKV GEMM's K loop on the fused large-prefill path (dh_linear_qkv_lora_rope_cache_bf16 decides), else a launch
-        if (W.attn_lora_a && !fuse_qkv)
-            if ((rc = linear(e, e->xn, W.attn_lora_a, e->xa, n_tok, 48, d, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, 0, 0,
-                             nullptr, nullptr, nullptr, s, false))) return rc;
         if (fuse_qkv) {
+            // x.A^T: inside the QKV GEMM's K loop (dh_linear_qkv_lora_rope_cache_bf16 decides)
             TimeScope t(e, 0, s);
             if (W.attn_lora_a) {
                 if ((rc = dh_linear_qkv_lora_rope_cache_bf16(e->xn, W.attn_w, n_tok, d, W.attn_lora_a, W.attn_lora_b, D.lora_scale,
@@ -215,98 +350,33 @@ int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q
                                                            D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, kc, vtc, H, G, hs,
                                                            e->s_max, s))) return rc;
         } else {
-        if (W.attn_lora_a) {
-            if ((rc = linear(e, e->xn, W.attn_w, e->qkv, n_tok, e->qkv_dim, d, DH_EPI_LORA, nullptr, e->xa, 48,
-                             W.attn_lora_b, d, d + e->kv_dim, nullptr, nullptr, nullptr, s, true))) return rc;
-        } else {
-            if ((rc = linear(e, e->xn, W.attn_w, e->qkv, n_tok, e->qkv_dim, d, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr,
-                             0, 0, nullptr, nullptr, nullptr, s, true))) return rc;
+            if (W.attn_lora_a) {   // x.A^T is a launch of its own here, outside the timed class
+                if ((rc = plain(e, e->xn, W.attn_lora_a, e->xa, n_tok, 48, d, nullptr, s, false))) return rc;
+                if ((rc = lora(e, e->xn, W.attn_w, e->qkv, n_tok, e->qkv_dim, d, e->xa, 48, W.attn_lora_b, d, d + e->kv_dim, s, true)))
+                    return rc;
+            } else if ((rc = plain(e, e->xn, W.attn_w, e->qkv, n_tok, e->qkv_dim, d, nullptr, s, true))) return rc;
+            if ((rc = rope_append(e, kc, vtc, n_tok, s))) return rc;
         }
-        if ((rc = dh_qkv_rope_cache_bf16(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, kc, vtc, nullptr,
-                                         nullptr, n_tok, H, G, hs, e->s_max, s))) return rc;
-        }
-        if (prune_last && l == D.n_layer - 1) {
-            // last block, last-position logits only: attention of each sequence's LAST query (a one-row tile at position
-            // pos0 + len - 1 over the same 64-key steps as in the full call), then projection, norm and MLP on n_seq rows.  The
-            // final hidden rows land in e->xlast (where the caller would have gathered them); e->x keeps this block's input.
-            const uint8_t* rtl = e->rsqrt_vec > 0 ? e->last_tail : nullptr;
-            {
-                TimeScope t(e, 2, s);
-                if ((rc = dh_attn_prefill_bf16(e->qrot, kc, vtc, seq_slot, e->last_row, e->last_meta, e->last_meta + e->max_batch,
-                                               e->att, nullptr, n_seq, 1, H, G, hs, e->s_max, s))) return rc;
-            }
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, e->att, e->last_row, e->att_last, n_seq, d);
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, e->x, e->last_row, e->xlast, n_seq, d);
-            DH_LAUNCH_CHECK();
-            // (these n_seq-row launches stream the weights; they are not in the timed class of the large prefill GEMMs, and
-            // bench.py does not count their FLOPs either)
-            if (W.proj_lora_a) {
-                if ((rc = dh_linear_lora_impl(e->att_last, W.proj_w, e->xlast, n_seq, d, d, W.proj_lora_a, W.proj_lora_b, D.lora_scale, d, d,
-                                              e->xlast, e->xa, 1, s))) return rc;
-            } else {
-                if ((rc = linear(e, e->att_last, W.proj_w, e->xlast, n_seq, d, d, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, 0, 0,
-                                 nullptr, nullptr, e->xlast, s, false))) return rc;
-            }
-            if ((rc = dh_rmsnorm_bf16(e->xlast, nullptr, W.norm_2, e->xn_last, nullptr, n_seq, d, D.norm_eps, rtl, s))) return rc;
-            if ((rc = linear(e, e->xn_last, W.fc_1, e->act_last, n_seq, I, d, DH_EPI_SWIGLU, W.fc_2, nullptr, 0, nullptr, 0, 0, nullptr,
-                             nullptr, nullptr, s, false))) return rc;
-            if ((rc = linear(e, e->act_last, W.mlp_proj, e->xlast, n_seq, d, I, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, 0, 0, nullptr,
-                             nullptr, e->xlast, s, false))) return rc;
-            break;
-        }
-        if (decode) {
-            TimeScope t(e, 3, s);
-            if ((rc = dh_attn_decode_bf16(e->qrot, kc, vtc, seq_slot, kv_pos0, e->att, e->dec_work, n_seq, H, G, hs,
-                                          e->s_max, s))) return rc;
-        } else {
-            TimeScope t(e, 2, s);
-            if ((rc = dh_attn_prefill_bf16(e->qrot, kc, vtc, seq_slot, q_start, q_len, kv_pos0, e->att, nullptr, n_seq,
-                                           max_q_len, H, G, hs, e->s_max, s))) return rc;
-        }
-        if (W.proj_lora_a) {
-            // down-projection in the GEMM's K loop where the launch runs on the 4-wave 256-tile kernel, else its own launch (same bits)
-            TimeScope t(e, e->phase_decode ? 1 : 0, s);
-            if ((rc = dh_linear_lora_impl(e->att, W.proj_w, e->x, n_tok, d, d, W.proj_lora_a, W.proj_lora_b, D.lora_scale, d, d, e->x,
-                                          e->xa, e->phase_decode && !e->decode_tiled ? 2 : 1, s))) return rc;
-        } else {
-            if ((rc = linear(e, e->att, W.proj_w, e->x, n_tok, d, d, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, 0, 0,
-                             nullptr, nullptr, e->x, s, true))) return rc;
-        }
-        if ((rc = dh_rmsnorm_bf16(e->x, nullptr, W.norm_2, e->xn, nullptr, n_tok, d, D.norm_eps, rt, s))) return rc;
-        if ((rc = linear(e, e->xn, W.fc_1, e->act, n_tok, I, d, DH_EPI_SWIGLU, W.fc_2, nullptr, 0, nullptr, 0, 0, nullptr,
-                         nullptr, nullptr, s, true))) return rc;
-        if ((rc = linear(e, e->act, W.mlp_proj, e->x, n_tok, d, I, DH_EPI_PLAIN, nullptr, nullptr, 0, nullptr, 0, 0, nullptr,
-                         nullptr, e->x, s, true))) return rc;
+        const bool last_rows = prune_last && l == D.n_layer - 1;
+        if ((rc = attention(e, kc, vtc, n_seq, max_q_len, last_rows, s))) return rc;
+        if (last_rows) return post_attention(e, W, n_seq, e->att_last, e->xlast, e->xn_last, e->act_last, rtl, false, s);
+        if ((rc = post_attention(e, W, n_tok, e->att, e->x, e->xn, e->act, rt, true, s))) return rc;
     }
     return 0;
 }
-
-// fp8 GEMM kernel by PHASE, never by packing (the two kernels sum K in different fp32 orders): a prefill is tiled even
-// when a short prompt runs alone; a single-token step streams the weights up to 128 rows (the bench's four batches per
-// decode loop) and is tiled above that — the one documented class boundary of the fp8 decode phase (DESIGN.md §7).
-inline int fp8_kernel(bool decode, int rows) { return decode && rows <= 128 ? 2 : 1; }
 
 // fp8 serving: the same layer sequence with every dense product on the fp8 MFMA (csrc/fp8.hip).  Activations are
 // quantised per token right where they are produced (the norm kernels) or by a pass over the attention / SwiGLU
 // output; LoRA is merged into the weights before quantisation, so there is no rank-16 side product.  Prefill and
 // decode run the same sequence; the GEMM kernel is pinned by phase (fp8_kernel above).
-int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q_len, bool decode,
-                   const uint8_t* tail_flags, hipStream_t s, bool prune_last = false) {
+int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q_len, bool decode, const uint8_t* tail_flags,
+                   bool prune_last, hipStream_t s) {
     const uint8_t* rt = e->rsqrt_vec > 0 ? tail_flags : nullptr;
+    const uint8_t* rtl = e->rsqrt_vec > 0 ? e->last_tail : nullptr;
     e->phase_decode = decode;
     const dh_model_desc& D = e->d;
-    const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
-    const int32_t* seq_slot = e->seq_slot;
-    int32_t* q_start = e->seq_meta + e->max_batch;
-    int32_t* q_len = e->seq_meta + 2 * e->max_batch;
-    int32_t* kv_pos0 = e->seq_meta + 3 * e->max_batch;   // decode: kv_len
+    const int d = D.n_embd, hs = D.head_size, H = D.n_head, G = D.n_groups;
     int rc;
-    // the weight pointers of dh_layer_weights address e4m3 bytes in this mode
-    auto lin = [&](const bf16_t* w, const float* ws, bf16_t* y, int N, int K, int epi, const bf16_t* w2, const float* w2s,
-                   const bf16_t* res) {
-        return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), ws, y, n_tok, N, K, epi,
-                                reinterpret_cast<const uint8_t*>(w2), w2s, nullptr, nullptr, res, fp8_kernel(decode, n_tok), s);
-    };
     if ((rc = dh_embed_bf16(ids, D.wte, e->x, n_tok, d, D.wte_rows, s))) return rc;
     for (int l = 0; l < D.n_layer; ++l) {
         const dh_layer_weights& W = e->layers[l];
@@ -316,6 +386,7 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
         if (decode && n_tok <= 128) {     // every streaming-class step (fp8_kernel above): one family, no 32-row boundary
             // one launch for rope + cache append + split-KV attention + combine (decode_fused.hip): the QKV product
             // is handed over as its single fp32 "partial" (values already rounded to bf16), no LoRA (merged)
+            const SeqMeta m = seq_meta(e);
             {
                 TimeScope t(e, 1, s);
                 if ((rc = dh_linear_fp8_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w), W.attn_ws, e->part32,
@@ -323,84 +394,24 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
             }
             TimeScope t(e, 3, s);
             if ((rc = dh_attn_decode_fused_bf16(e->part32, 1, 0, n_seq, e->qkv_dim, 0, nullptr, 0.f, e->qkv_dim, e->qkv_dim,
-                                                D.rope_cos, D.rope_sin, seq_slot, kv_pos0, kc, vtc, e->att, H, G, hs,
+                                                D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
                                                 e->s_max, s))) return rc;
         } else {
-        {
-            TimeScope t(e, decode ? 1 : 0, s);
-            if ((rc = lin(W.attn_w, W.attn_ws, e->qkv, e->qkv_dim, d, DH_EPI_PLAIN, nullptr, nullptr, nullptr))) return rc;
+            if ((rc = linear_fp8(e, W.attn_w, W.attn_ws, e->qkv, n_tok, e->qkv_dim, d, DH_EPI_PLAIN, nullptr, nullptr, nullptr, s, true)))
+                return rc;
+            if ((rc = rope_append(e, kc, vtc, n_tok, s))) return rc;
+            // the last block of a prompt forward that wants the last position's logits only stays on the phase's (tiled) kernel
+            const bool last_rows = prune_last && l == D.n_layer - 1;
+            if ((rc = attention(e, kc, vtc, n_seq, max_q_len, last_rows, s))) return rc;
+            if (last_rows) return post_attention_fp8(e, W, n_seq, e->att_last, e->xlast, e->act_last, rtl, false, s);
         }
-        if ((rc = dh_qkv_rope_cache_bf16(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, kc, vtc, nullptr,
-                                         nullptr, n_tok, H, G, hs, e->s_max, s))) return rc;
-        if (prune_last && l == D.n_layer - 1) {
-            // last block of a prompt forward that wants the last position's logits only: see run_layers.  The products stay on the
-            // phase's (tiled) kernel and the activations are quantised per row, so the n_seq rows keep their bits.
-            const uint8_t* rtl = e->rsqrt_vec > 0 ? e->last_tail : nullptr;
-            auto lin_last = [&](const bf16_t* w, const float* ws, bf16_t* y, int N, int K, int epi, const bf16_t* w2, const float* w2s,
-                                const bf16_t* res) {
-                return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), ws, y, n_seq, N, K, epi,
-                                        reinterpret_cast<const uint8_t*>(w2), w2s, nullptr, nullptr, res, fp8_kernel(false, n_seq), s);
-            };
-            {
-                TimeScope t(e, 2, s);
-                if ((rc = dh_attn_prefill_bf16(e->qrot, kc, vtc, seq_slot, e->last_row, e->last_meta, e->last_meta + e->max_batch,
-                                               e->att, nullptr, n_seq, 1, H, G, hs, e->s_max, s))) return rc;
-            }
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, e->att, e->last_row, e->att_last, n_seq, d);
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, e->x, e->last_row, e->xlast, n_seq, d);
-            DH_LAUNCH_CHECK();
-            if ((rc = dh_quant_rows_fp8(e->att_last, e->xq, e->xscale, n_seq, d, s))) return rc;
-            if ((rc = lin_last(W.proj_w, W.proj_ws, e->xlast, d, d, DH_EPI_PLAIN, nullptr, nullptr, e->xlast))) return rc;
-            if ((rc = dh_rmsnorm_quant_fp8(e->xlast, W.norm_2, nullptr, e->xq, e->xscale, n_seq, d, D.norm_eps, rtl, s))) return rc;
-            if ((rc = lin_last(W.fc_1, W.fc_1_ws, e->act_last, I, d, DH_EPI_SWIGLU, W.fc_2, W.fc_2_ws, nullptr))) return rc;
-            if ((rc = dh_quant_rows_fp8(e->act_last, e->xq, e->xscale, n_seq, I, s))) return rc;
-            if ((rc = lin_last(W.mlp_proj, W.mlp_proj_ws, e->xlast, d, I, DH_EPI_PLAIN, nullptr, nullptr, e->xlast))) return rc;
-            break;
-        }
-        if (decode) {
-            TimeScope t(e, 3, s);
-            if ((rc = dh_attn_decode_bf16(e->qrot, kc, vtc, seq_slot, kv_pos0, e->att, e->dec_work, n_seq, H, G, hs,
-                                          e->s_max, s))) return rc;
-        } else {
-            TimeScope t(e, 2, s);
-            if ((rc = dh_attn_prefill_bf16(e->qrot, kc, vtc, seq_slot, q_start, q_len, kv_pos0, e->att, nullptr, n_seq,
-                                           max_q_len, H, G, hs, e->s_max, s))) return rc;
-        }
-        }
-        if ((rc = dh_quant_rows_fp8(e->att, e->xq, e->xscale, n_tok, d, s))) return rc;
-        {
-            TimeScope t(e, decode ? 1 : 0, s);
-            if ((rc = lin(W.proj_w, W.proj_ws, e->x, d, d, DH_EPI_PLAIN, nullptr, nullptr, e->x))) return rc;
-        }
-        if ((rc = dh_rmsnorm_quant_fp8(e->x, W.norm_2, nullptr, e->xq, e->xscale, n_tok, d, D.norm_eps, rt, s))) return rc;
-        {
-            TimeScope t(e, decode ? 1 : 0, s);
-            if ((rc = lin(W.fc_1, W.fc_1_ws, e->act, I, d, DH_EPI_SWIGLU, W.fc_2, W.fc_2_ws, nullptr))) return rc;
-        }
-        if ((rc = dh_quant_rows_fp8(e->act, e->xq, e->xscale, n_tok, I, s))) return rc;
-        {
-            TimeScope t(e, decode ? 1 : 0, s);
-            if ((rc = lin(W.mlp_proj, W.mlp_proj_ws, e->x, d, I, DH_EPI_PLAIN, nullptr, nullptr, e->x))) return rc;
-        }
+        if ((rc = post_attention_fp8(e, W, n_tok, e->att, e->x, e->act, rt, true, s))) return rc;
     }
     return 0;
 }
 
-// ln_f + lm_head of `rows` rows of `xrows` in fp8 mode; the bf16 ln_f output lands in e->xn as in the bf16 path
-int head_fp8(dh_engine* e, const bf16_t* xrows, int rows, bf16_t* logits, const uint8_t* rt, hipStream_t s) {
-    const dh_model_desc& D = e->d;
-    int rc;
-    if ((rc = dh_rmsnorm_quant_fp8(xrows, D.ln_f, e->xn, e->xq, e->xscale, rows, D.n_embd, D.norm_eps,
-                                   e->rsqrt_vec > 0 ? rt : nullptr, s))) return rc;
-    TimeScope t(e, e->phase_decode ? 1 : 0, s);
-    return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(D.lm_head), D.lm_head_ws, logits, rows, D.vocab,
-                            D.n_embd, DH_EPI_ADAPTER, nullptr, nullptr, D.adapter_scale, D.adapter_bias, nullptr,
-                            fp8_kernel(e->phase_decode, rows), s);
-}
-
 // K-slices of 8 (or 16 for long K) k-steps: the row-parallel streaming kernel (gemm_skinny.hip)
-int pick_ksplit(int tiles, int nks) {
-    (void)tiles;
+int pick_ksplit(int nks) {
     if (nks <= 128) return g_short_kps == 16 && nks % 16 == 0 ? nks / 16 : (nks + 7) / 8;
     if (nks <= 256) return (nks + 15) / 16;
     int ks = 1;
@@ -409,13 +420,12 @@ int pick_ksplit(int tiles, int nks) {
 }
 
 // Single-token step for n_seq <= MAX_DECODE_ROWS sequences: 7 launches per layer (decode_fused.hip).  Leaves
-// ln_f(x) in e->xn.  kv_len lives in seq_meta[3B..], seq_slot in e->seq_slot.
+// ln_f(x) in e->xn.
 int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t* tail_flags, hipStream_t s) {
     const dh_model_desc& D = e->d;
     const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
     const uint8_t* rt = e->rsqrt_vec > 0 ? tail_flags : nullptr;
-    const int32_t* seq_slot = e->seq_slot;
-    const int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
+    const SeqMeta m = seq_meta(e);
     e->phase_decode = true;
     int rc;
     if ((rc = dh_embed_bf16(ids, D.wte, e->x, n_seq, d, D.wte_rows, s))) return rc;
@@ -434,17 +444,16 @@ int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t
         };
         int np, pairs;
         const int ext1 = W.attn_lora_a ? 48 : 0;
-        if ((rc = partial(e->xn, W.attn_w, W.attn_lora_a, e->qkv_dim, ext1, d, pick_ksplit((e->qkv_dim + ext1) / 16, d / 32), np, pairs))) return rc;
+        if ((rc = partial(e->xn, W.attn_w, W.attn_lora_a, e->qkv_dim, ext1, d, pick_ksplit(d / 32), np, pairs))) return rc;
         if ((rc = dh_attn_decode_fused_bf16(e->part32, np, pairs, n_seq, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale, d,
-                                            d + e->kv_dim, D.rope_cos, D.rope_sin, seq_slot, kv_len, kc, vtc, e->att, H, G,
+                                            d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G,
                                             hs, e->s_max, s))) return rc;
         const int ext2 = W.proj_lora_a ? 16 : 0;
-        if ((rc = partial(e->att, W.proj_w, W.proj_lora_a, d, ext2, d, pick_ksplit((d + ext2) / 16, d / 32), np, pairs))) return rc;
+        if ((rc = partial(e->att, W.proj_w, W.proj_lora_a, d, ext2, d, pick_ksplit(d / 32), np, pairs))) return rc;
         if ((rc = dh_finish_norm_bf16(e->part32, np, pairs, n_seq, d, ext2, W.proj_lora_b, D.lora_scale, e->x, W.norm_2, e->x,
                                       e->xn, D.norm_eps, rt, s))) return rc;
-        if ((rc = linear(e, e->xn, W.fc_1, e->act, n_seq, I, d, DH_EPI_SWIGLU, W.fc_2, nullptr, 0, nullptr, 0, 0, nullptr,
-                         nullptr, nullptr, s, false))) return rc;
-        if ((rc = partial(e->act, W.mlp_proj, nullptr, d, 0, I, pick_ksplit(d / 16, I / 32), np, pairs))) return rc;
+        if ((rc = swiglu(e, e->xn, W.fc_1, W.fc_2, e->act, n_seq, I, d, s, false))) return rc;
+        if ((rc = partial(e->act, W.mlp_proj, nullptr, d, 0, I, pick_ksplit(I / 32), np, pairs))) return rc;
         const bf16_t* next_norm = l + 1 < D.n_layer ? e->layers[l + 1].norm_1 : D.ln_f;
         if ((rc = dh_finish_norm_bf16(e->part32, np, pairs, n_seq, d, 0, nullptr, 0.f, e->x, next_norm, e->x, e->xn,
                                       D.norm_eps, rt, s))) return rc;
@@ -452,45 +461,50 @@ int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t
     return 0;
 }
 
-// lm_head on rows that are already ln_f-normalised (e->xn)
-int head_normed(dh_engine* e, int rows, bf16_t* logits, hipStream_t s) {
+// ---- layers + logits ---------------------------------------------------------------------------------------------------------
+// ln_f + lm_head of `rows` rows of `xrows`; the bf16 ln_f output lands in e->xn (test hook dh_engine_read(0)) in either precision.
+// xrows == nullptr: the rows are in e->xn, normalised already (run_layers_decode).
+int head(dh_engine* e, const bf16_t* xrows, int rows, bf16_t* logits, const uint8_t* tail_flags, hipStream_t s) {
     const dh_model_desc& D = e->d;
-    return linear(e, e->xn, D.lm_head, logits, rows, D.vocab, D.n_embd, DH_EPI_ADAPTER, nullptr, nullptr, 0, nullptr, 0, 0,
-                  D.adapter_scale, D.adapter_bias, nullptr, s, true);
-}
-
-int head(dh_engine* e, const bf16_t* xrows, int rows, bf16_t* logits, const uint8_t* rt, hipStream_t s) {
-    const dh_model_desc& D = e->d;
+    const uint8_t* rt = e->rsqrt_vec > 0 ? tail_flags : nullptr;
     int rc;
-    if ((rc = dh_rmsnorm_bf16(xrows, nullptr, D.ln_f, e->xn, nullptr, rows, D.n_embd, D.norm_eps,
-                              e->rsqrt_vec > 0 ? rt : nullptr, s))) return rc;
-    return linear(e, e->xn, D.lm_head, logits, rows, D.vocab, D.n_embd, DH_EPI_ADAPTER, nullptr, nullptr, 0, nullptr, 0, 0,
-                  D.adapter_scale, D.adapter_bias, nullptr, s, true);
+    if (e->fp8) {
+        if ((rc = dh_rmsnorm_quant_fp8(xrows, D.ln_f, e->xn, e->xq, e->xscale, rows, D.n_embd, D.norm_eps, rt, s))) return rc;
+        TimeScope t(e, gemm_class(e), s);
+        return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(D.lm_head), D.lm_head_ws, logits, rows, D.vocab,
+                                D.n_embd, DH_EPI_ADAPTER, nullptr, nullptr, D.adapter_scale, D.adapter_bias, nullptr,
+                                fp8_kernel(e->phase_decode, rows), s);
+    }
+    if (xrows && (rc = dh_rmsnorm_bf16(xrows, nullptr, D.ln_f, e->xn, nullptr, rows, D.n_embd, D.norm_eps, rt, s))) return rc;
+    return adapter(e, e->xn, D.lm_head, logits, rows, D.vocab, D.n_embd, D.adapter_scale, D.adapter_bias, s, true);
 }
 
-int decode_step(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq, float temperature,
-                int top_k, int64_t eos_id, uint64_t seed, hipStream_t s);
-int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens);
-
-}  // namespace
-
-extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, dh_engine** out) {
-    DH_CHECK(desc && out, "dh_engine_create: null argument");
-    DH_CHECK(desc->head_size == 64 || desc->head_size == 96 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
-    DH_CHECK(desc->n_head % desc->n_groups == 0, "dh_engine_create: n_head %% n_groups != 0");
-    DH_CHECK(desc->n_embd == desc->n_head * desc->head_size, "dh_engine_create: n_embd != n_head*head_size");
-    DH_CHECK(desc->n_embd % 64 == 0 && desc->intermediate % 64 == 0 && desc->vocab % 8 == 0, "dh_engine_create: dims must be multiples of 64");
-    DH_CHECK(s_max > 0 && s_max % 64 == 0 && s_max <= (desc->block_size + 63) / 64 * 64, "dh_engine_create: s_max=%d must be a multiple of 64 and <= block_size rounded up", s_max);
-    DH_CHECK(max_batch > 0 && max_tokens >= max_batch, "dh_engine_create: bad batch/token capacity");
-    DH_CHECK(desc->rope_cos && desc->rope_sin && desc->wte && desc->ln_f && desc->lm_head && desc->h_layers, "dh_engine_create: null weight pointer");
-    dh_engine* e = new dh_engine();
-    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens);
-    if (rc) { dh_engine_destroy(e); return rc; }   // one cleanup path: nothing allocated so far leaks
-    *out = e;
+// The model on n_tok packed tokens of n_seq sequences whose ids and metadata are on the device: the layers on the path the call's
+// class selects (fp8 / the streaming single-token step / tiled), then ln_f + lm_head on every row (logits_all), on each sequence's
+// last row (logits_last), or both.  step: one token per sequence run as a decode step.  prune_last: logits_last alone is wanted and
+// the last block ran on the last rows only.  row_flags / last_flags: the rsqrt tail flags of all rows / of the last rows.
+int run_model(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q, bool step, const uint8_t* row_flags,
+              const uint8_t* last_flags, bool prune_last, bf16_t* logits_all, bf16_t* logits_last, hipStream_t s) {
+    e->decode_tiled = step && g_decode_tiled_rows > 0 && n_seq >= g_decode_tiled_rows;
+    const bool streaming = !e->fp8 && step && n_seq <= MAX_DECODE_ROWS && !e->decode_tiled;
+    int rc;
+    if (e->fp8) rc = run_layers_fp8(e, ids, n_tok, n_seq, max_q, step, row_flags, prune_last, s);
+    else if (streaming) rc = run_layers_decode(e, ids, n_seq, row_flags, s);
+    else rc = run_layers(e, ids, n_tok, n_seq, max_q, step, row_flags, prune_last, s);
+    if (rc) return rc;
+    if (prune_last) return head(e, e->xlast, n_seq, logits_last, last_flags, s);   // e->xlast: the last rows' final hidden state
+    if (streaming) {   // every row is its sequence's last row, and e->xn holds ln_f of them
+        if (logits_all && (rc = head(e, nullptr, n_seq, logits_all, nullptr, s))) return rc;
+        return logits_last ? head(e, nullptr, n_seq, logits_last, nullptr, s) : 0;
+    }
+    if (logits_all && (rc = head(e, e->x, n_tok, logits_all, row_flags, s))) return rc;
+    if (logits_last) {
+        // head() overwrites xn[0 : n_seq], which is fine after logits_all
+        if ((rc = gather_last_rows(e, e->x, e->xlast, n_seq, s))) return rc;
+        return head(e, e->xlast, n_seq, logits_last, last_flags, s);
+    }
     return 0;
 }
-
-namespace {
 
 int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens) {
     e->d = *desc;
@@ -560,7 +574,7 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     DH_HIP(hipMemset(e->vtc, 0, e->cache_layer_elems * desc->n_layer * sizeof(bf16_t)));
     DH_HIP(hipMemset(e->step_dev, 0, sizeof(int32_t)));
     DH_HIP(hipMemset(e->ones, 1, (size_t)max_batch));
-    DH_HIP(hipHostMalloc((void**)&e->h_stage, (3 * T + 8 * (size_t)max_batch) * sizeof(int32_t)));
+    DH_HIP(hipHostMalloc((void**)&e->h_stage, stage_layout(T, max_batch).total * sizeof(int32_t)));
     DH_HIP(hipStreamCreateWithFlags(&e->gstream, hipStreamNonBlocking));
     DH_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
     DH_HIP(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
@@ -570,7 +584,144 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     return 0;
 }
 
+// h_slots == nullptr: sequence i lives in slot slot_base + i (the identity array written at engine creation);
+// else in h_slots[i] (distinct, checked by the caller), uploaded to a device array of this call's own.
+// A call of one token per sequence is a decode step and takes the decode kernels — unless prompt_phase says that these
+// are prompts: then the kernels are the prefill's, as they are for a one-token prompt packed with longer ones.
+int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0, const int32_t* h_slots,
+                 int n_seq, int slot_base, bool prompt_phase, dh_bf16* logits_all, dh_bf16* logits_last, void* stream) {
+    e->seq_slot = h_slots ? e->slot_list : e->seq_meta + slot_base;
+    hipStream_t s = (hipStream_t)stream;
+    int n_tok = 0, max_q = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        DH_CHECK(h_seq_len[i] > 0 && h_pos0[i] >= 0, "dh_engine_forward: sequence %d has length %d at position %d", i, h_seq_len[i], h_pos0[i]);
+        DH_CHECK(h_pos0[i] + h_seq_len[i] <= e->s_max, "Cannot forward sequence %d: %d tokens at position %d exceed the KV cache length %d",
+                 i, h_seq_len[i], h_pos0[i], e->s_max);
+        n_tok += h_seq_len[i];
+        max_q = h_seq_len[i] > max_q ? h_seq_len[i] : max_q;
+    }
+    const bool step = max_q == 1 && !prompt_phase;    // one token per sequence == a decode step
+    DH_CHECK(n_tok <= e->max_tokens, "dh_engine_forward: %d tokens exceed the workspace capacity %d", n_tok, e->max_tokens);
+    const int B = e->max_batch;
+    const Stage h = stage(e);
+    const SeqMeta m = seq_meta(e);
+    DH_HIP(hipEventSynchronize(e->ev_stage));   // this engine's previous metadata upload must have left the pinned buffer
+    int t = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        const int slot = h_slots ? h_slots[i] : slot_base + i;
+        h.seq_slot[i] = slot;
+        h.q_start[i] = t;
+        h.q_len[i] = h_seq_len[i];
+        h.kv[i] = step ? h_pos0[i] + 1 : h_pos0[i];   // single-token call: kv_len
+        for (int j = 0; j < h_seq_len[i]; ++j, ++t) { h.tok_slot[t] = slot; h.tok_pos[t] = h_pos0[i] + j; }
+        h.last_row[i] = t - 1;
+    }
+    // Q11: rows torch's CPU bf16 rsqrt would process in its scalar tail loop
+    if (e->rsqrt_vec > 0) {
+        const int V = e->rsqrt_vec;
+        int r = 0;
+        for (int i = 0; i < n_seq; ++i) {
+            for (int j = 0; j < h_seq_len[i]; ++j, ++r)
+                h.row_tail[r] = e->rsqrt_whole ? (r >= n_tok / V * V) : (j >= h_seq_len[i] / V * V);
+            h.last_tail[i] = h.row_tail[r - 1];   // ln_f runs on all rows in the reference: the last row keeps its flag
+        }
+        DH_HIP(hipMemcpyAsync(e->row_tail, h.row_tail, n_tok, hipMemcpyHostToDevice, s));
+        DH_HIP(hipMemcpyAsync(e->last_tail, h.last_tail, n_seq, hipMemcpyHostToDevice, s));
+    }
+    DH_HIP(hipMemcpyAsync(e->tok_slot, h.tok_slot, n_tok * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    DH_HIP(hipMemcpyAsync(e->tok_pos, h.tok_pos, n_tok * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    // seq_meta[0..B) (slot of sequence i = i) is written once at engine creation and left alone
+    if (h_slots) DH_HIP(hipMemcpyAsync(e->slot_list, h.seq_slot, n_seq * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    DH_HIP(hipMemcpyAsync(m.q_start, h.q_start, 3 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));   // q_start | q_len | kv
+    DH_HIP(hipMemcpyAsync(e->last_row, h.last_row, B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    // last-position logits of a multi-token forward only: the last block runs on the sequences' last rows (g_prune_last_layer)
+    const bool prune_last = g_prune_last_layer && max_q > 1 && logits_all == nullptr && logits_last != nullptr;
+    if (prune_last) {
+        for (int i = 0; i < n_seq; ++i) { h.last_meta[i] = 1; h.last_meta[B + i] = h_pos0[i] + h_seq_len[i] - 1; }
+        DH_HIP(hipMemcpyAsync(e->last_meta, h.last_meta, 2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    DH_HIP(hipEventRecord(e->ev_stage, s));
+    // one token per sequence == a decode step (what generate()'s loop issues): same kernels as dh_engine_decode
+    return run_model(e, ids, n_tok, n_seq, max_q, step, e->row_tail, e->last_tail, prune_last, logits_all, logits_last, s);
+}
+
+// One decode step of the rows `k` names: ids / tok_slot / tok_pos / kv_len from a prep kernel, the model over the k.n_seq rows (the
+// kernel family is the row count's) with logits in e->logits, one sampled token per live sequence.  k.row_seq == nullptr
+// (dh_engine_decode): row r is sequence r in slot r, the draw is keyed by the step counter in step_dev, which the prep kernel
+// increments.  Else (dh_engine_decode_rows) the prep and the sampling kernel index the per-sequence arrays through the row list.
+int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
+    const bool rows = k.row_seq != nullptr;
+    hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(k.n_seq, 64)), dim3(64), 0, s, k.tokens, k.tok_ld, k.length, k.row_seq, k.row_slot,
+                       e->dec_ids, e->tok_slot, e->tok_pos, seq_meta(e).kv, rows ? nullptr : e->step_dev, k.n_seq, k.n_all,
+                       e->max_batch, e->s_max);
+    DH_LAUNCH_CHECK();
+    int rc;
+    if ((rc = run_model(e, e->dec_ids, k.n_seq, k.n_seq, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
+    if (rows)
+        return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
+                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, s);
+    return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
+                          e->step_dev, s);
+}
+
+// n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
+int launch_steps(dh_engine* e, const dh_engine::GKey& key, int n_steps, hipStream_t s) {
+    hipGraphExec_t gexec = nullptr;
+    for (auto& g : e->graphs) {
+        if (g.key == key) {
+            gexec = g.exec;
+            g.used = ++e->graph_clock;
+            break;
+        }
+    }
+    // hand over from the caller's stream to the engine's capture-capable stream
+    DH_HIP(hipEventRecord(e->ev_in, s));
+    DH_HIP(hipStreamWaitEvent(e->gstream, e->ev_in, 0));
+    if (!gexec) {
+        hipGraph_t graph = nullptr;
+        DH_HIP(hipStreamBeginCapture(e->gstream, hipStreamCaptureModeThreadLocal));
+        e->capturing = true;
+        int rc = decode_step(e, key, e->gstream);
+        e->capturing = false;
+        hipError_t ce = hipStreamEndCapture(e->gstream, &graph);
+        if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+        DH_CHECK(ce == hipSuccess && graph, "dh_engine_decode: graph capture failed: %s", hipGetErrorString(ce));
+        hipError_t ie = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        DH_CHECK(ie == hipSuccess, "dh_engine_decode: hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+        if (e->graphs.size() >= 8) {   // evict the least recently used (its launches are stream-ordered before the destroy)
+            size_t lru = 0;
+            for (size_t i = 1; i < e->graphs.size(); ++i)
+                if (e->graphs[i].used < e->graphs[lru].used) lru = i;
+            DH_HIP(hipStreamSynchronize(e->gstream));
+            hipGraphExecDestroy(e->graphs[lru].exec);
+            e->graphs.erase(e->graphs.begin() + lru);
+        }
+        e->graphs.push_back({key, gexec, ++e->graph_clock});
+    }
+    for (int i = 0; i < n_steps; ++i) DH_HIP(hipGraphLaunch(gexec, e->gstream));
+    DH_HIP(hipEventRecord(e->ev_out, e->gstream));
+    DH_HIP(hipStreamWaitEvent(s, e->ev_out, 0));
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, dh_engine** out) {
+    DH_CHECK(desc && out, "dh_engine_create: null argument");
+    DH_CHECK(desc->head_size == 64 || desc->head_size == 96 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
+    DH_CHECK(desc->n_head % desc->n_groups == 0, "dh_engine_create: n_head %% n_groups != 0");
+    DH_CHECK(desc->n_embd == desc->n_head * desc->head_size, "dh_engine_create: n_embd != n_head*head_size");
+    DH_CHECK(desc->n_embd % 64 == 0 && desc->intermediate % 64 == 0 && desc->vocab % 8 == 0, "dh_engine_create: dims must be multiples of 64");
+    DH_CHECK(s_max > 0 && s_max % 64 == 0 && s_max <= (desc->block_size + 63) / 64 * 64, "dh_engine_create: s_max=%d must be a multiple of 64 and <= block_size rounded up", s_max);
+    DH_CHECK(max_batch > 0 && max_tokens >= max_batch, "dh_engine_create: bad batch/token capacity");
+    DH_CHECK(desc->rope_cos && desc->rope_sin && desc->wte && desc->ln_f && desc->lm_head && desc->h_layers, "dh_engine_create: null weight pointer");
+    dh_engine* e = new dh_engine();
+    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens);
+    if (rc) { dh_engine_destroy(e); return rc; }   // one cleanup path: nothing allocated so far leaks
+    *out = e;
+    return 0;
+}
 
 extern "C" void dh_engine_destroy(dh_engine* e) {
     if (!e) return;
@@ -616,11 +767,6 @@ extern "C" int dh_engine_forward(dh_engine* e, const int64_t* ids, const int32_t
     return dh_engine_forward_at(e, ids, h_seq_len, h_pos0, n_seq, 0, logits_all, logits_last, stream);
 }
 
-namespace {
-int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0, const int32_t* h_slots,
-                 int n_seq, int slot_base, bool prompt_phase, dh_bf16* logits_all, dh_bf16* logits_last, void* stream);
-}
-
 extern "C" int dh_engine_forward_at(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0,
                                     int n_seq, int slot_base, dh_bf16* logits_all, dh_bf16* logits_last, void* stream) {
     DH_CHECK(e && ids && h_seq_len && h_pos0, "dh_engine_forward: null argument");
@@ -643,203 +789,6 @@ extern "C" int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const i
     return forward_impl(e, ids, h_seq_len, h_pos0, h_slot, n_seq, 0, prompt_phase != 0, logits_all, logits_last, stream);
 }
 
-namespace {
-
-// h_slots == nullptr: sequence i lives in slot slot_base + i (the identity array written at engine creation);
-// else in h_slots[i] (distinct, checked by the caller), uploaded to a device array of this call's own.
-// A call of one token per sequence is a decode step and takes the decode kernels — unless prompt_phase says that these
-// are prompts: then the kernels are the prefill's, as they are for a one-token prompt packed with longer ones.
-int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, const int32_t* h_pos0, const int32_t* h_slots,
-                 int n_seq, int slot_base, bool prompt_phase, dh_bf16* logits_all, dh_bf16* logits_last, void* stream) {
-    e->slot_base = slot_base;
-    e->seq_slot = h_slots ? e->slot_list : e->seq_meta + slot_base;
-    hipStream_t s = (hipStream_t)stream;
-    int n_tok = 0, max_q = 0;
-    for (int i = 0; i < n_seq; ++i) {
-        DH_CHECK(h_seq_len[i] > 0 && h_pos0[i] >= 0, "dh_engine_forward: sequence %d has length %d at position %d", i, h_seq_len[i], h_pos0[i]);
-        DH_CHECK(h_pos0[i] + h_seq_len[i] <= e->s_max, "Cannot forward sequence %d: %d tokens at position %d exceed the KV cache length %d",
-                 i, h_seq_len[i], h_pos0[i], e->s_max);
-        n_tok += h_seq_len[i];
-        max_q = h_seq_len[i] > max_q ? h_seq_len[i] : max_q;
-    }
-    const bool step = max_q == 1 && !prompt_phase;    // one token per sequence == a decode step
-    DH_CHECK(n_tok <= e->max_tokens, "dh_engine_forward: %d tokens exceed the workspace capacity %d", n_tok, e->max_tokens);
-    // metadata: [tok_slot | tok_pos | seq_slot | q_start | q_len | kv_pos0 | last_row]
-    const int B = e->max_batch;
-    int32_t* hs_ = e->h_stage;
-    DH_HIP(hipEventSynchronize(e->ev_stage));   // this engine's previous metadata upload must have left the pinned buffer
-    int32_t *h_slot = hs_, *h_pos = hs_ + e->max_tokens, *h_meta = hs_ + 2 * (size_t)e->max_tokens;
-    int t = 0;
-    for (int i = 0; i < n_seq; ++i) {
-        const int slot = h_slots ? h_slots[i] : slot_base + i;
-        h_meta[i] = slot;
-        h_meta[B + i] = t;
-        h_meta[2 * B + i] = h_seq_len[i];
-        h_meta[3 * B + i] = step ? h_pos0[i] + 1 : h_pos0[i];   // single-token call: kv_len
-        for (int j = 0; j < h_seq_len[i]; ++j, ++t) { h_slot[t] = slot; h_pos[t] = h_pos0[i] + j; }
-        h_meta[4 * B + i] = t - 1;
-    }
-    // Q11: rows torch's CPU bf16 rsqrt would process in its scalar tail loop
-    uint8_t* h_tail = reinterpret_cast<uint8_t*>(hs_ + 2 * (size_t)e->max_tokens + 5 * (size_t)B);
-    uint8_t* h_last_tail = h_tail + e->max_tokens;
-    if (e->rsqrt_vec > 0) {
-        const int V = e->rsqrt_vec;
-        int r = 0;
-        for (int i = 0; i < n_seq; ++i) {
-            for (int j = 0; j < h_seq_len[i]; ++j, ++r)
-                h_tail[r] = e->rsqrt_whole ? (r >= n_tok / V * V) : (j >= h_seq_len[i] / V * V);
-            h_last_tail[i] = h_tail[r - 1];   // ln_f runs on all rows in the reference: the last row keeps its flag
-        }
-        DH_HIP(hipMemcpyAsync(e->row_tail, h_tail, n_tok, hipMemcpyHostToDevice, s));
-        DH_HIP(hipMemcpyAsync(e->last_tail, h_last_tail, n_seq, hipMemcpyHostToDevice, s));
-    }
-    DH_HIP(hipMemcpyAsync(e->tok_slot, h_slot, n_tok * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    DH_HIP(hipMemcpyAsync(e->tok_pos, h_pos, n_tok * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    // seq_meta[0..B) (slot of sequence i = i) is written once at engine creation and left alone
-    if (h_slots) DH_HIP(hipMemcpyAsync(e->slot_list, h_meta, n_seq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    DH_HIP(hipMemcpyAsync(e->seq_meta + B, h_meta + B, 3 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    DH_HIP(hipMemcpyAsync(e->last_row, h_meta + 4 * B, B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    // last-position logits of a multi-token forward only: the last block runs on the sequences' last rows (g_prune_last_layer)
-    const bool prune_last = g_prune_last_layer && max_q > 1 && logits_all == nullptr && logits_last != nullptr;
-    if (prune_last) {
-        int32_t* h_lm = hs_ + 3 * (size_t)e->max_tokens + 6 * (size_t)B;   // behind the tail flags
-        for (int i = 0; i < n_seq; ++i) { h_lm[i] = 1; h_lm[B + i] = h_pos0[i] + h_seq_len[i] - 1; }
-        DH_HIP(hipMemcpyAsync(e->last_meta, h_lm, 2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
-    DH_HIP(hipEventRecord(e->ev_stage, s));
-    int rc;
-    // one token per sequence == a decode step (what generate()'s loop issues): same kernels as dh_engine_decode
-    e->decode_tiled = step && g_decode_tiled_rows > 0 && n_seq >= g_decode_tiled_rows;
-    if (e->fp8) {
-        if ((rc = run_layers_fp8(e, ids, n_tok, n_seq, max_q, step, e->row_tail, s, prune_last))) return rc;
-        e->last_ntok = n_tok;
-        if (prune_last) return head_fp8(e, e->xlast, n_seq, logits_last, e->last_tail, s);
-        if (logits_all && (rc = head_fp8(e, e->x, n_tok, logits_all, e->row_tail, s))) return rc;
-        if (logits_last) {
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, e->x, e->last_row, e->xlast, n_seq,
-                               e->d.n_embd);
-            DH_LAUNCH_CHECK();
-            if ((rc = head_fp8(e, e->xlast, n_seq, logits_last, e->last_tail, s))) return rc;
-        }
-        return 0;
-    }
-    const bool fast = step && n_seq <= MAX_DECODE_ROWS && e->d.n_embd % 16 == 0 && !e->decode_tiled;
-    if (fast) {
-        if ((rc = run_layers_decode(e, ids, n_seq, e->row_tail, s))) return rc;
-        e->last_ntok = n_tok;
-        if (logits_all && (rc = head_normed(e, n_seq, logits_all, s))) return rc;
-        if (logits_last && (rc = head_normed(e, n_seq, logits_last, s))) return rc;
-        return 0;
-    }
-    if ((rc = run_layers(e, ids, n_tok, n_seq, max_q, step, e->row_tail, s, prune_last))) return rc;
-    e->last_ntok = n_tok;
-    if (prune_last) return head(e, e->xlast, n_seq, logits_last, e->last_tail, s);   // e->xlast: the last rows' final hidden state
-    if (logits_all) {
-        // ln_f output lands in e->xn (test hook dh_engine_hidden)
-        if ((rc = head(e, e->x, n_tok, logits_all, e->row_tail, s))) return rc;
-    }
-    if (logits_last) {
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, e->x, e->last_row, e->xlast, n_seq,
-                           e->d.n_embd);
-        DH_LAUNCH_CHECK();
-        if (logits_all) {
-            // xn currently holds ln_f(x) of all rows; recompute for the gathered rows into a scratch
-            // region past them is unnecessary: head() overwrites xn[0:n_seq], which is fine after logits_all.
-        }
-        if ((rc = head(e, e->xlast, n_seq, logits_last, e->last_tail, s))) return rc;
-    }
-    return 0;
-}
-
-// One single-token step of the layer stack + lm_head over n_seq rows whose ids / tok_slot / tok_pos / kv_len a prep kernel
-// has just written and whose KV slots e->seq_slot names: logits in e->logits.  The kernel family is the row count's.
-int decode_forward(dh_engine* e, int n_seq, hipStream_t s) {
-    int rc;
-    e->decode_tiled = g_decode_tiled_rows > 0 && n_seq >= g_decode_tiled_rows;
-    if (e->fp8) {
-        if ((rc = run_layers_fp8(e, e->dec_ids, n_seq, n_seq, 1, true, e->ones, s))) return rc;
-        if ((rc = head_fp8(e, e->x, n_seq, e->logits, e->ones, s))) return rc;
-    } else if (n_seq <= MAX_DECODE_ROWS && !e->decode_tiled) {
-        if ((rc = run_layers_decode(e, e->dec_ids, n_seq, e->ones, s))) return rc;
-        if ((rc = head_normed(e, n_seq, e->logits, s))) return rc;
-    } else {
-        if ((rc = run_layers(e, e->dec_ids, n_seq, n_seq, 1, true, e->ones, s))) return rc;
-        if ((rc = head(e, e->x, n_seq, e->logits, e->ones, s))) return rc;
-    }
-    return 0;
-}
-
-int decode_step(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq, float temperature,
-                int top_k, int64_t eos_id, uint64_t seed, hipStream_t s) {
-    int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
-    hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, s, tokens, tok_ld, length, e->dec_ids,
-                       e->tok_slot, e->tok_pos, kv_len, e->step_dev, n_seq, e->s_max);
-    DH_LAUNCH_CHECK();
-    int rc;
-    if ((rc = decode_forward(e, n_seq, s))) return rc;
-    // the per-step RNG counter lives in step_dev (incremented by decode_prep_kernel)
-    return dh_sample_impl(e->logits, e->d.vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id,
-                          seed, 0, e->step_dev, s);
-}
-
-// decode_step over a row list (dh_engine_decode_rows): the prep and the sampling kernel index the per-sequence arrays through
-// row_seq, the layers run on the n_rows rows as they do in decode_step
-int decode_rows_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
-    int32_t* kv_len = e->seq_meta + 3 * e->max_batch;
-    hipLaunchKernelGGL(decode_prep_rows_kernel, dim3(cdiv(k.n_seq, 64)), dim3(64), 0, s, k.tokens, k.tok_ld, k.length, k.row_seq,
-                       k.row_slot, e->dec_ids, e->tok_slot, e->tok_pos, kv_len, k.n_seq, k.n_all, e->max_batch, e->s_max);
-    DH_LAUNCH_CHECK();
-    int rc;
-    if ((rc = decode_forward(e, k.n_seq, s))) return rc;
-    return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
-                               k.max_new, k.temp, k.top_k, k.eos, k.seed, s);
-}
-
-// n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
-int launch_steps(dh_engine* e, const dh_engine::GKey& key, int n_steps, hipStream_t s) {
-    const bool rows = key.row_seq != nullptr;
-    hipGraphExec_t gexec = nullptr;
-    for (auto& g : e->graphs) {
-        if (g.key == key) {
-            gexec = g.exec;
-            g.used = ++e->graph_clock;
-            break;
-        }
-    }
-    // hand over from the caller's stream to the engine's capture-capable stream
-    DH_HIP(hipEventRecord(e->ev_in, s));
-    DH_HIP(hipStreamWaitEvent(e->gstream, e->ev_in, 0));
-    if (!gexec) {
-        hipGraph_t graph = nullptr;
-        DH_HIP(hipStreamBeginCapture(e->gstream, hipStreamCaptureModeThreadLocal));
-        e->capturing = true;
-        int rc = rows ? decode_rows_step(e, key, e->gstream)
-                      : decode_step(e, key.tokens, key.tok_ld, key.length, key.done, key.n_seq, key.temp, key.top_k, key.eos, key.seed, e->gstream);
-        e->capturing = false;
-        hipError_t ce = hipStreamEndCapture(e->gstream, &graph);
-        if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-        DH_CHECK(ce == hipSuccess && graph, "dh_engine_decode: graph capture failed: %s", hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        DH_CHECK(ie == hipSuccess, "dh_engine_decode: hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-        if (e->graphs.size() >= 8) {   // evict the least recently used (its launches are stream-ordered before the destroy)
-            size_t lru = 0;
-            for (size_t i = 1; i < e->graphs.size(); ++i)
-                if (e->graphs[i].used < e->graphs[lru].used) lru = i;
-            DH_HIP(hipStreamSynchronize(e->gstream));
-            hipGraphExecDestroy(e->graphs[lru].exec);
-            e->graphs.erase(e->graphs.begin() + lru);
-        }
-        e->graphs.push_back({key, gexec, ++e->graph_clock});
-    }
-    for (int i = 0; i < n_steps; ++i) DH_HIP(hipGraphLaunch(gexec, e->gstream));
-    DH_HIP(hipEventRecord(e->ev_out, e->gstream));
-    DH_HIP(hipStreamWaitEvent(s, e->ev_out, 0));
-    return 0;
-}
-
-}  // namespace
-
 extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
                                 int n_steps, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                 int first_step, void* stream) {
@@ -847,7 +796,6 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
     if (n_steps <= 0) return 0;
-    e->slot_base = 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
     // seq_slot (seq_meta[0..B)) is the identity from engine creation on; nothing here touches the host
@@ -868,7 +816,6 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(n_seq > 0 && tok_ld > 0 && max_new_tokens > 0, "dh_engine_decode_rows: bad shape");
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
     if (n_steps <= 0) return 0;
-    e->slot_base = 0;
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,

@@ -18,6 +18,7 @@
 // MFMA operand map (checked with integer data, tests/test_hip_fp8.py): lane l holds the 32 consecutive k
 // [32 (l >> 4), 32 (l >> 4) + 32) of row (A) / column (B) l & 15 — one MX block per lane, hence one scale per lane.
 #include "common.h"
+#include "tuning.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;

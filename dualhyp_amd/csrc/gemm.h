@@ -1,6 +1,7 @@
 // Argument block shared by the tiled (gemm.hip) and weight-streaming (gemm_skinny.hip) kernels.
 #pragma once
 #include "common.h"
+#include "tuning.h"
 
 struct GemmArgs {
     const bf16_t* x;
@@ -18,7 +19,7 @@ struct GemmArgs {
     float lora_scale;
     int nb_n, nb_m;
     int gm;            // m-tiles per band of the 256-tile kernel's block order
-    int fast_epi;      // 4-wave kernel: bit 0 the v_dot2_f32_bf16 fused-QKV epilogue, bit 1 the v_dot2 LoRA / residual epilogues (dh_set_tuning(24, bits))
+    int fast_epi;      // 4-wave kernel: g_w4_fast_epi (dh_set_tuning(24, bits)); only bit 2 selects anything, see its definition in gemm256.hip
     int resid_mul;     // 256-tile kernels, PLAIN + resid: the `resid` operand is an elementwise MULTIPLIER, y = bf16(bf16(acc) * resid) (dh_linear_mul_bf16)
     // DH_EPI_QKV (256-tile kernel only): the fused-QKV projection whose epilogue also rotates q / k, writes q and
     // appends k / v to the KV cache (what dh_qkv_rope_cache_bf16 does in a separate pass over the qkv tensor)
@@ -34,8 +35,6 @@ struct GemmArgs {
 
 constexpr int DH_EPI_QKV = 4;   // internal: LoRA (optional) + rope + cache append, see dh_linear_qkv_rope_cache_bf16
 
-
-
 // M <= 32: one pass over W straight from HBM to registers (gemm_skinny.hip)
 int dh_linear_skinny(const GemmArgs& a, int epilogue, hipStream_t s);
 // y[M, N] = bf16(x . W^T), N = 16 .. 64, thousands of rows (gemm_skinny.hip: gemm_skinny_n_kernel); the bits of the tiled kernels
@@ -50,7 +49,7 @@ bool dh_linear_256_xa_ok(const GemmArgs& a, int epilogue);
 // decode phase, M <= 256 rows from several batches in one launch (gemm_mid.hip)
 bool dh_linear_mid_ok(const GemmArgs& a, int epilogue);
 int dh_linear_mid(const GemmArgs& a, int epilogue, hipStream_t s);
-extern int g_mid;            // 1: the decode phase uses the LDS-staged-x streaming kernel for PLAIN/SWIGLU/ADAPTER
+// g_mid = 1: the decode phase uses the LDS-staged-x streaming kernel for PLAIN/SWIGLU/ADAPTER
 
 // decode phase, > 64 rows: tiled kernel with the streaming kernels' summation order (gemm_dt.hip)
 bool dh_linear_dt_ok(const GemmArgs& a, int epilogue, int seg);
@@ -63,16 +62,13 @@ int dh_pairs_tiled(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float*
                    int kps, hipStream_t s);
 int dh_chain_tiled(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float* y32, int M, int n_main, int n_ext, int K,
                    int kps, hipStream_t s);
-extern int g_dt_min_rows, g_chain_min_rows;
 
 // true when dh_linear_impl would send this shape to the 256-tile kernel (gemm256.hip)
 bool dh_linear_is_big(int M, int N, int epilogue);
 
 // M >= 256: 256 x 256 x 64 tiles, one block per CU (gemm256.hip)
 int dh_linear_256(GemmArgs a, int epilogue, hipStream_t s);
-extern int g_linear_phase;
-extern int g_gemm_gm;
-extern int g_gemm_variant;   // 0: always the 128-tile kernel; 1 / 2 / 3: 256-tile kernel, loop variants of gemm256.hip; 4: 1 with persistent blocks for the PLAIN / SwiGLU epilogues; 5 (default): the 4-wave full-line kernel
+// g_gemm_variant = 0: always the 128-tile kernel; 1 / 2 / 3: 256-tile kernel, loop variants of gemm256.hip; 4: 1 with persistent blocks for the PLAIN / SwiGLU epilogues; 5 (default): the 4-wave full-line kernel
 
 // dh_linear_bf16 with an explicit kernel choice.  kernel: 0 = by shape (M <= 32 -> streaming),
 // 1 = tiled MFMA kernel whatever M, 2 = decode phase (streaming kernels up to 256 rows).  The engine pins the choice per PHASE (prefill = tiled,

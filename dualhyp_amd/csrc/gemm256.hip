@@ -28,7 +28,7 @@
 #include "common.h"
 #include "gemm.h"
 
-int g_w4_fast_epi = 7;  // dh_set_tuning(24, bits): bit 0 the fused-QKV epilogue of full tiles in its v_dot2_f32_bf16 form (g256_epilogue_qkv_fast), bit 1 the same arithmetic in the LoRA / residual epilogues; bit 2: a persistent block's tile start leaves the previous FULL tile's last stores in flight (counted wait); 0 = the round-3 forms (A/B)
+int g_w4_fast_epi = 7;  // dh_set_tuning(24, bits), handed to the 4-wave kernel as GemmArgs::fast_epi.  Only bit 2 selects anything: set, a persistent block's tile start leaves the previous FULL tile's last stores in flight (counted wait); clear, it waits for everything (A/B).  Bits 0 and 1 chose between two forms of the epilogues' arithmetic; one form is left and the bits are ignored
 int g_w4_persist_lora = 1;  // dh_set_tuning(30, 0 | 1): persistent blocks for the LoRA GEMM with the in-GEMM down-projection (attn proj of the prefill) and for plain + residual (mlp proj): the last two iterations of a tile request the next tile's first stages (CONT)
 int g_w4_persist_qkv = 1;   // dh_set_tuning(25, 0 | 1): persistent blocks for the fused-QKV GEMM with the in-GEMM LoRA, the stage stream continuing across
                             // tiles (CONT).  With the next tile's stages requested from inside the epilogue (asm requests: 184 bytes of spills, every

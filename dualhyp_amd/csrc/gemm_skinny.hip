@@ -14,6 +14,12 @@
 #include "common.h"
 #include "gemm.h"
 
+// dh_set_tuning keys 0, 2, 14, 11 (tuning.h)
+int g_skinny_variant = 1;   // 0: K split over the waves of a block, 1: row-parallel with LDS-staged x
+int g_swiglu2 = 1;           // SwiGLU of at most 32 rows: 1 = swiglu_skinny2_kernel where N % 32 == 0, 0 = the generic streaming kernel
+int g_rows_ng = 0;   // 0: by grid size; 8 or 10 row groups per block above 128 rows (dh_set_tuning key 14)
+int g_rows_ct = 0;   // 0: by row count; else forced column tiles per wave (dh_set_tuning key 11: 1, 2 or 4)
+
 namespace {
 
 constexpr int ROWS = 16;     // W rows per block
@@ -203,8 +209,6 @@ __global__ __launch_bounds__(512, 1) void swiglu_skinny2_kernel(GemmArgs a) {
         a.y[(size_t)tm * a.N + nn] = f2bf(rbf(silu_fast(g)) * u);
     }
 }
-
-int g_swiglu2 = 1;
 
 // fp32 partial sums for consumers that finish the epilogue themselves (decode_fused.hip):
 //   part[by][m][n] = sum over the k-steps of K-slice `by` of x[m,:] . W'[n,:],  W' = [w ; w_ext]
@@ -418,9 +422,6 @@ __global__ __launch_bounds__(512, NG == 1 ? 2 : 1) void gemm_skinny_rows_kernel(
     ROWS_STAMP(6);
 }
 
-int g_rows_ng = 0;   // 0: by grid size; 8 or 10 row groups per block above 128 rows (dh_set_tuning key 14)
-int g_rows_ct = 0;   // 0: by row count; else forced column tiles per wave (dh_set_tuning key 11: 1, 2 or 4)
-
 template <int KPS, int NG, int CT>
 int launch_rows(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float* y32, int M, int n_main, int N, int K,
                 int ksplit, hipStream_t s) {
@@ -460,8 +461,6 @@ int launch_rows_ng(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float*
     }
     return launch_rows<KPS, 8, 1>(x, w, w_ext, y32, M, n_main, N, K, ksplit, s);
 }
-
-int g_skinny_variant = 1;   // 0: K split over the waves of a block, 1: row-parallel with LDS-staged x
 
 template <int EPI>
 int launch(const GemmArgs& a, hipStream_t s) {
@@ -714,43 +713,6 @@ int dh_linear_k64(const dh_bf16* x, const dh_bf16* w, const dh_bf16* mul, dh_bf1
     else hipLaunchKernelGGL((gemm_k64_kernel<false>), grid, block, 0, s, x, w, mul, y, M, N);
     DH_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int dh_set_tuning(int key, int value) {
-    if (key == 0) { g_skinny_variant = value; return 0; }
-    if (key == 1) { g_gemm_variant = value; return 0; }
-    if (key == 2) { g_swiglu2 = value; return 0; }
-    if (key == 3) { g_mid = value; return 0; }
-    if (key == 4) { g_linear_phase = value; return 0; }
-    if (key == 5 && value >= 0) { g_gemm_gm = value; return 0; }
-    if (key == 6 && value >= 1) { g_dt_min_rows = value; return 0; }
-    if (key == 7 && value >= 1) { g_chain_min_rows = value; return 0; }
-    if (key == 8) { extern int g_dt_stages; g_dt_stages = value; return 0; }
-    if (key == 9) { extern int g_gemm128_stages; g_gemm128_stages = value; return 0; }
-    if (key == 10 && value >= 0) { extern int g_decode_tiled_rows; g_decode_tiled_rows = value; return 0; }
-    if (key == 11 && value >= 0) { g_rows_ct = value; return 0; }
-    if (key == 12) { extern int g_fuse_qkv_rope; g_fuse_qkv_rope = value; return 0; }
-    if (key == 14 && (value == 0 || value == 8 || value == 10)) { g_rows_ng = value; return 0; }
-    if (key == 16 && (value == 8 || value == 16)) { extern int g_short_kps; g_short_kps = value; return 0; }
-    if (key == 15) { extern int g_dt_wide; g_dt_wide = value; return 0; }
-    if (key == 13) { extern int g_mid_wlds; g_mid_wlds = value; return 0; }
-    if (key == 17 && (value == 0 || value == 2 || value == 4)) { extern int g_pairs_wn; g_pairs_wn = value; return 0; }
-    if (key == 18 && value >= 1) { g_pairs_min_rows = value; return 0; }
-    if (key == 21) { extern int g_pairs_wt; g_pairs_wt = value != 0; return 0; }
-    if (key == 19 && (value == 0 || value == 128 || value == 256)) { extern int g_fp8_tile; g_fp8_tile = value; return 0; }
-    if (key == 20 && value >= 0 && value <= 64) { extern int g_fp8_gm; g_fp8_gm = value; return 0; }
-    if (key == 22 && value >= 0 && value <= 2) { extern int g_w4_persist; g_w4_persist = value; return 0; }
-    if (key == 23) { extern int g_prune_last_layer; g_prune_last_layer = value != 0; return 0; }
-    if (key == 24) { extern int g_w4_fast_epi; g_w4_fast_epi = value; return 0; }
-    if (key == 25) { extern int g_w4_persist_qkv; g_w4_persist_qkv = value != 0; return 0; }
-    if (key == 26) { extern int g_tn_mfma; g_tn_mfma = value != 0; return 0; }
-    if (key == 31) { g_skinny_n = value != 0; return 0; }
-    if (key == 30) { extern int g_w4_persist_lora; g_w4_persist_lora = value != 0; return 0; }
-    if (key == 29) { extern int g_attn_bwd_dkdv_img; g_attn_bwd_dkdv_img = value != 0; return 0; }
-    if (key == 28) { extern int g_tail_split; g_tail_split = value != 0; return 0; }
-    if (key == 27) { extern int g_attn_bwd_dq_group; g_attn_bwd_dq_group = value != 0; return 0; }
-    dh_set_error("dh_set_tuning: unknown key %d", key);
-    return 1;
 }
 
 int dh_linear_skinny(const GemmArgs& a, int epilogue, hipStream_t s) {

@@ -3,6 +3,7 @@
 // attention backward (attention_bwd.hip).  Activations and activation-gradients are bf16, sums are
 // fp32, LoRA gradients are accumulated in fp32 buffers.
 #include "common.h"
+#include "tuning.h"
 #include <climits>
 
 int g_tn_mfma = 1;    // dh_set_tuning(26, 0): the LoRA-gradient contraction on the VALU kernel of rounds 2-3 (A/B)

@@ -95,3 +95,39 @@ def test_gemm256_has_no_asm_mfma_hazards(tmp_path):
         s = next(tmp_path.glob("*gfx950.s"))
     out = subprocess.run([sys.executable, str(REPO / "tools" / "check_asm_mfma.py"), str(s)], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-3000:]
+
+
+# dh_set_tuning as it stood before the switchboard became a table (read off that function, key by key):
+# key -> (default, a value the filter refuses or None when every value is taken)
+_TUNING = {
+    0: (1, None), 1: (5, None), 2: (1, None), 3: (1, None), 4: (0, None), 5: (0, -1), 6: (129, 0), 7: (1 << 30, 0), 8: (0, None),
+    9: (0, None), 10: (0, -1), 11: (0, -1), 12: (1, None), 13: (1, None), 14: (0, 9), 15: (0, None), 16: (8, 12), 17: (0, 3),
+    18: (288, 0), 19: (0, 64), 20: (0, 65), 21: (0, None), 22: (1, 3), 23: (1, None), 24: (7, None), 25: (1, None), 26: (1, None),
+    27: (1, None), 28: (1, None), 29: (1, None), 30: (1, None), 31: (1, None),
+}
+
+
+def test_set_tuning_keys_and_value_filters():
+    """Every key 0..31 takes its default value; a value outside a key's filter and a key outside the table are refused with a
+    message.  Host code only: no GPU.  The defaults are set again at the end (refused values change nothing)."""
+    import __graft_entry__ as ge
+    ge.build()
+    from dualhyp_amd import _lib
+    lib = _lib.load()
+    assert sorted(_TUNING) == list(range(32))
+    try:
+        for key, (default, refused) in _TUNING.items():
+            assert lib.dh_set_tuning(key, default) == 0, f"key {key} refuses its default {default}"
+            if refused is not None:
+                assert lib.dh_set_tuning(key, refused) != 0, f"key {key} takes {refused}"
+        for key, lo, hi in ((20, 0, 64), (22, 0, 2)):      # the two closed ranges: both ends in, one past the upper end out (above)
+            assert lib.dh_set_tuning(key, lo) == 0 and lib.dh_set_tuning(key, hi) == 0
+        for key, values in ((14, (0, 8, 10)), (16, (8, 16)), (17, (0, 2, 4)), (19, (0, 128, 256))):
+            assert all(lib.dh_set_tuning(key, v) == 0 for v in values), key
+        assert lib.dh_set_tuning(20, -1) != 0 and lib.dh_set_tuning(22, -1) != 0 and lib.dh_set_tuning(16, 0) != 0
+        assert lib.dh_set_tuning(-1, 0) != 0
+        assert lib.dh_set_tuning(32, 0) != 0
+        assert b"32" in lib.dh_last_error()
+    finally:
+        for key, (default, _) in _TUNING.items():
+            lib.dh_set_tuning(key, default)
