@@ -2,6 +2,8 @@
 // ger/lora.py:504-549 (GPT.forward) + generate/base.py:57-80 (the decode loop) for a packed,
 // ragged batch.  Host side is plain C++; the decode step is captured once into a hipGraph and
 // replayed, so a generated token costs one graph launch and no host synchronisation.
+#include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "common.h"
@@ -33,6 +35,8 @@ struct dh_engine {
     int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B], read through seq_meta() below
     int32_t *last_row = nullptr, *step_dev = nullptr;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
+    int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
+    bf16_t** cache_tab = nullptr;                       // [2 L] device table, written once: K cache of layer l at 2l, V^T cache at 2l + 1
     int32_t* last_meta = nullptr;                       // [ones | position of the last token] x [B]: the pruned last layer's attention call
     bf16_t *att_last = nullptr, *xn_last = nullptr, *act_last = nullptr;   // its n_seq-row operands
     uint8_t *row_tail = nullptr, *last_tail = nullptr, *ones = nullptr;   // Q11 rsqrt emulation flags
@@ -75,6 +79,15 @@ struct dh_engine {
 };
 
 namespace {
+
+// the engines dh_engine_create has handed out and dh_engine_destroy has not taken back: dh_engine_copy_prefix looks a handle up
+// here before it reads anything through it
+std::mutex g_engines_mu;
+std::vector<const dh_engine*> g_engines;
+bool engine_is_live(const dh_engine* e) {
+    std::lock_guard<std::mutex> lock(g_engines_mu);
+    return e && std::find(g_engines.begin(), g_engines.end(), e) != g_engines.end();
+}
 
 template <typename T>
 int dmalloc(dh_engine* e, T** p, size_t n) {
@@ -173,6 +186,27 @@ __global__ void gather_rows_kernel(const bf16_t* __restrict__ src, const int32_t
     uint4* t = reinterpret_cast<uint4*>(dst + (size_t)wave * d);
     for (int c = lane; c < d / 8; c += 64) t[c] = s[c];
 }
+// Fork of a KV prefix (dh_engine_copy_prefix): the first n_pos / 32 tiles of src_slot's (layer, cache, group) blocks, one contiguous
+// run of run16 16-byte units from the start of each block (common.h: 32-key tiles back to back), to the same place of every slot in
+// dst_slots.  grid (pieces of 256 units, 2 L tables x groups, shares of the destination list); a thread loads its unit once and
+// stores it to each destination of the block's share — all of them, unless the host split the list to fill the chip.
+// block_elems = s_max * hs; the host has checked the slots against max_batch and run16 * 8 <= block_elems.
+__global__ __launch_bounds__(256) void kv_copy_prefix_kernel(bf16_t* const* __restrict__ cache_tab, const int32_t* __restrict__ dst_slots,
+                                                             int n_dst, int dst_per_block, int src_slot, int n_groups,
+                                                             size_t block_elems, int run16) {
+    const int unit = blockIdx.x * 256 + threadIdx.x;
+    if (unit >= run16) return;
+    const int tab = blockIdx.y / n_groups, g = blockIdx.y % n_groups;
+    // a pointer read from memory has no known address space: said to be global, the accesses are global_load / global_store_dwordx4
+    typedef __attribute__((address_space(1))) bf16_t gbf16_t;
+    typedef __attribute__((address_space(1))) i32x4 gi32x4;
+    gbf16_t* base = (gbf16_t*)cache_tab[tab] + (size_t)g * block_elems + (size_t)unit * 8;
+    const size_t slot_elems = (size_t)n_groups * block_elems;
+    const i32x4 v = *(const gi32x4*)(base + (size_t)src_slot * slot_elems);
+    const int d0 = blockIdx.z * dst_per_block, d1 = min(d0 + dst_per_block, n_dst);
+    for (int i = d0; i < d1; ++i) *(gi32x4*)(base + (size_t)dst_slots[i] * slot_elems) = v;
+}
+
 // dst[i, :] = src[last_row[i], :] for the n_seq sequences of the call
 int gather_last_rows(dh_engine* e, const bf16_t* src, bf16_t* dst, int n_seq, hipStream_t s) {
     hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, s, src, e->last_row, dst, n_seq, e->d.n_embd);
@@ -557,6 +591,8 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     rc |= dmalloc(e, &e->act_last, (size_t)max_batch * desc->intermediate);
     rc |= dmalloc(e, &e->step_dev, 1);
     rc |= dmalloc(e, &e->slot_list, (size_t)max_batch);
+    rc |= dmalloc(e, &e->copy_dst, (size_t)max_batch);
+    rc |= dmalloc(e, &e->cache_tab, (size_t)2 * desc->n_layer);
     rc |= dmalloc(e, &e->dec_ids, (size_t)max_batch);
     rc |= dmalloc(e, &e->part32, (size_t)16 * (max_batch < 32 ? 32 : (max_batch < MAX_DECODE_ROWS ? max_batch : MAX_DECODE_ROWS)) * (e->qkv_dim + 48));
     if (e->fp8) {
@@ -574,6 +610,14 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     DH_HIP(hipMemset(e->vtc, 0, e->cache_layer_elems * desc->n_layer * sizeof(bf16_t)));
     DH_HIP(hipMemset(e->step_dev, 0, sizeof(int32_t)));
     DH_HIP(hipMemset(e->ones, 1, (size_t)max_batch));
+    {
+        std::vector<bf16_t*> tab(2 * (size_t)desc->n_layer);
+        for (int l = 0; l < desc->n_layer; ++l) {
+            tab[2 * l] = e->kc + (size_t)l * e->cache_layer_elems;
+            tab[2 * l + 1] = e->vtc + (size_t)l * e->cache_layer_elems;
+        }
+        DH_HIP(hipMemcpy(e->cache_tab, tab.data(), tab.size() * sizeof(bf16_t*), hipMemcpyHostToDevice));
+    }
     DH_HIP(hipHostMalloc((void**)&e->h_stage, stage_layout(T, max_batch).total * sizeof(int32_t)));
     DH_HIP(hipStreamCreateWithFlags(&e->gstream, hipStreamNonBlocking));
     DH_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
@@ -719,15 +763,23 @@ extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_
     dh_engine* e = new dh_engine();
     const int rc = engine_init(e, desc, max_batch, s_max, max_tokens);
     if (rc) { dh_engine_destroy(e); return rc; }   // one cleanup path: nothing allocated so far leaks
+    {
+        std::lock_guard<std::mutex> lock(g_engines_mu);
+        g_engines.push_back(e);
+    }
     *out = e;
     return 0;
 }
 
 extern "C" void dh_engine_destroy(dh_engine* e) {
     if (!e) return;
+    {
+        std::lock_guard<std::mutex> lock(g_engines_mu);
+        g_engines.erase(std::remove(g_engines.begin(), g_engines.end(), e), g_engines.end());
+    }
     for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
     void* ptrs[] = {e->kc, e->vtc, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
-                    e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->dec_ids, e->dec_work,
+                    e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->copy_dst, e->cache_tab, e->dec_ids, e->dec_work,
                     e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale};
     for (void* p : ptrs)
         if (p) hipFree(p);
@@ -787,6 +839,41 @@ extern "C" int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const i
         taken[h_slot[i]] = 1;
     }
     return forward_impl(e, ids, h_seq_len, h_pos0, h_slot, n_seq, 0, prompt_phase != 0, logits_all, logits_last, stream);
+}
+
+extern "C" int dh_engine_copy_prefix(dh_engine* e, int src_slot, const int32_t* h_dst_slots, int n_dst, int n_pos, void* stream) {
+    DH_CHECK(e, "dh_engine_copy_prefix: null engine");
+    DH_CHECK(engine_is_live(e), "dh_engine_copy_prefix: %p is not an engine of dh_engine_create (or was destroyed)", (void*)e);
+    DH_CHECK(n_pos > 0 && n_pos % 32 == 0 && n_pos <= e->s_max,
+             "dh_engine_copy_prefix: n_pos=%d must be a positive multiple of 32 (the cache tile) and <= s_max=%d", n_pos, e->s_max);
+    DH_CHECK(src_slot >= 0 && src_slot < e->max_batch, "dh_engine_copy_prefix: source slot %d of %d", src_slot, e->max_batch);
+    DH_CHECK(n_dst >= 0 && n_dst < e->max_batch && (h_dst_slots || n_dst == 0),
+             "dh_engine_copy_prefix: %d destinations (null list: %d) in an engine of %d slots", n_dst, h_dst_slots == nullptr, e->max_batch);
+    std::vector<char> taken(e->max_batch, 0);
+    for (int i = 0; i < n_dst; ++i) {
+        const int d = h_dst_slots[i];
+        DH_CHECK(d >= 0 && d < e->max_batch, "dh_engine_copy_prefix: destination %d names slot %d of %d", i, d, e->max_batch);
+        DH_CHECK(d != src_slot, "dh_engine_copy_prefix: the source slot %d is in the destination list", src_slot);
+        DH_CHECK(!taken[d], "dh_engine_copy_prefix: slot %d is named twice", d);
+        taken[d] = 1;
+    }
+    if (n_dst == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const Stage h = stage(e);
+    DH_HIP(hipEventSynchronize(e->ev_stage));   // the previous metadata upload must have left the pinned buffer
+    for (int i = 0; i < n_dst; ++i) h.seq_slot[i] = h_dst_slots[i];
+    DH_HIP(hipMemcpyAsync(e->copy_dst, h.seq_slot, n_dst * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    DH_HIP(hipEventRecord(e->ev_stage, s));
+    const int hs = e->d.head_size, G = e->d.n_groups;
+    const int run16 = n_pos * hs / 8;            // 16-byte units per (layer, cache, group) block: n_pos / 32 tiles of hs * 32 elements
+    const dim3 grid(cdiv(run16, 256), 2 * e->d.n_layer * G, 1);
+    // a short prefix in a shallow model makes few pieces: split the destination list until some 2048 blocks are in flight
+    const int shares = std::min<int64_t>(n_dst, std::max<int64_t>(1, 2048 / ((int64_t)grid.x * grid.y)));
+    const int dst_per_block = cdiv(n_dst, shares);
+    hipLaunchKernelGGL(kv_copy_prefix_kernel, dim3(grid.x, grid.y, cdiv(n_dst, dst_per_block)), dim3(256), 0, s, e->cache_tab, e->copy_dst,
+                       n_dst, dst_per_block, src_slot, G, (size_t)e->s_max * hs, run16);
+    DH_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,

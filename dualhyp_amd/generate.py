@@ -8,21 +8,53 @@ device state back once at the end instead of once per token (generate/base.py:79
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import torch
 
 from . import ops
 from .gpt import GPT
+from .schedule import shared_prefix_len
 
 
 EOS_CHECK_EVERY = 16     # decode steps between two "has every sequence finished" read-backs (generate_batch with an eos_id)
 
 
+def _shared_prefix(model: GPT, prompts: Sequence[torch.Tensor], share_prefix: Union[bool, str], dev) -> int:
+    """P of a call: the leading tokens forwarded once for all of its prompts (schedule.shared_prefix_len), 0 = each prompt whole.
+    share_prefix False: 0.  True: P, or an error where sharing would change bits.  "auto": P, or 0 there."""
+    if share_prefix is False:
+        return 0
+    if share_prefix is not True and share_prefix != "auto":
+        raise ValueError(f"share_prefix is False, True or 'auto', not {share_prefix!r}")
+    from .relprompt import GPT as RelGPT
+    why = None
+    if model.cpu_rsqrt_vec_width != 0:
+        # dh_engine_set_cpu_rsqrt_emulation(whole_call=0): the rsqrt tail rows are the last len % width rows of a sequence within
+        # its own forward, so a prompt forwarded in two pieces has other tail rows than the prompt forwarded whole
+        why = "cpu_rsqrt_vec_width != 0 flags rows by their index within a call; a prompt split at the prefix would move them"
+    elif isinstance(model, RelGPT):
+        why = "the RelPrompt decoder's prompts carry spliced reliability embeddings"
+    if why is not None:
+        if share_prefix is True:
+            raise ValueError(f"share_prefix=True: {why} (share_prefix='auto' runs such a call unshared)")
+        return 0
+    return shared_prefix_len([p.to(dev).reshape(-1) for p in prompts])
+
+
+def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: Sequence[int]) -> None:
+    """The call's first P tokens through the layers once, into KV slot `slot` (a prompt-phase forward, no logits), and their K / V
+    of every layer from there into other_slots."""
+    eng.forward(prompt[:P].to(eng.device), [P], [0], want_all=False, want_last=False, slot_base=slot)
+    if other_slots:
+        eng.copy_prefix(slot, list(other_slots), P)
+
+
 @torch.inference_mode()
 def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
-                   return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None):
+                   return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
+                   share_prefix: Union[bool, str] = False):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -31,7 +63,11 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     decoded TOGETHER: a decode step streams the weights once for all rows (up to 256 rows take the
     streaming kernels), which is where the time of a small-batch decode goes.  A sequence's tokens do
     not depend on how many others ride along (every kernel's per-row summation order is fixed by the
-    phase, not by the packing); only the multinomial draw is keyed by the row index in the call."""
+    phase, not by the packing); only the multinomial draw is keyed by the row index in the call.
+
+    share_prefix (True, or "auto": only where it changes no bit): the P leading tokens every prompt of the call opens with
+    (whole 32-token tiles, each prompt keeping a token of its own) go through the layers once, their K / V are copied into
+    every slot (dh_engine_copy_prefix), and the prefill forwards each prompt's tokens [P:] at position P.  Same ids."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     lens = [int(p.numel()) for p in prompts]
@@ -41,7 +77,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     dev = model.transformer.wte.weight.device
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
-    eng = model.engine(B, need_pos, max(sum(lens[a:b]) for a, b in chunks), exact=B > prefill_batch)
+    P = _shared_prefix(model, prompts, share_prefix, dev)
+    eng = model.engine(B, need_pos, max(P, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)), exact=B > prefill_batch)
     tok_ld = T_max + max_new_tokens
     if min(lens) == T_max:             # equal lengths: one copy
         tokens = torch.nn.functional.pad(torch.stack([p.to(dev) for p in prompts]), (0, tok_ld - T_max))
@@ -56,9 +93,14 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     if ev:
         ev[0].record()
     last = torch.empty((B, eng.vocab), dtype=torch.bfloat16, device=dev)
+    if P:
+        _forward_prefix(eng, prompts[0], P, 0, range(1, B))
     for a, b in chunks:
-        packed = torch.cat([p.to(dev).reshape(-1) for p in prompts[a:b]])
-        _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
+        packed = torch.cat([p.to(dev).reshape(-1)[P:] for p in prompts[a:b]])
+        if P:   # prompt_phase: a chunk of one-token remainders is still a piece of a prompt forward, not a decode step
+            last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], list(range(a, b)), prompt_phase=True, pos0=P)
+        else:
+            _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0)
     if ev:
         ev[1].record()
@@ -88,6 +130,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
         timing["decode_steps"] = timing.get("decode_steps", 0) + steps_run
         timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + B * steps_run
+        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens) - (B - 1) * P
+        timing["shared_prefix"] = P
     out: List[torch.Tensor] = []
     for i in range(B):
         n = min(length_h[i], lens[i] + max_new_tokens)
@@ -102,9 +146,11 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
 class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
-    def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing) -> None:
+    def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
+        self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
+        self.prefill_tokens = 0
         tok_ld = max(lens) + max_new_tokens
         # row N is the dummy sequence of the padding rows: one token, finished, owner of the spare slot
         self.tokens = torch.nn.functional.pad(torch.nn.utils.rnn.pad_sequence([p.to(dev) for p in prompts], batch_first=True),
@@ -128,10 +174,12 @@ class _StreamBackend:
     def prefill(self, seqs, slots) -> None:
         end = self._timed("prefill_ms")
         dev = self.eng.device
-        packed = torch.cat([self.prompts[u].to(dev).reshape(-1) for u in seqs])
+        P = self.prefix
+        packed = torch.cat([self.prompts[u].to(dev).reshape(-1)[P:] for u in seqs])
+        self.prefill_tokens += packed.numel()
         # a chunk of one-token prompts only is still a prompt forward (the engine would take it for a decode step) — unless the whole
         # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
-        last = self.eng.forward_slots(packed, [self.lens[u] for u in seqs], list(slots), prompt_phase=max(self.lens) > 1)
+        last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
                         self.max_new, **self.kw)
         if end:
@@ -156,7 +204,8 @@ class _StreamBackend:
 @torch.inference_mode()
 def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
-                    prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None):
+                    prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
+                    share_prefix: Union[bool, str] = False):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -165,7 +214,11 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 
     A sequence's ids do not depend on the schedule: no kernel's per-row arithmetic depends on the row count or the packing
     (an fp8 engine's two row classes are never mixed within a call), and the multinomial draw is keyed by
-    (seed, sequence index, tokens generated so far)."""
+    (seed, sequence index, tokens generated so far).
+
+    share_prefix: as in generate_batch.  The shared positions are forwarded once and copied into every slot the scheduler
+    hands out before the first prefill; no sequence of the call writes below position P, so they outlive every refill, and a
+    refill is a prefill of the tokens [P:] at position P.  The scheduler's decisions are those of the unshared call."""
     from .schedule import StreamScheduler
     N = len(prompts)
     assert N > 0 and max_new_tokens > 0
@@ -174,11 +227,18 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     if model.max_seq_length < need_pos:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
-    # slots 0..max_rows-1 and the spare one; a prefill packs at most the prefill_batch longest prompts
-    eng = model.engine(sched.max_rows + 1, need_pos, sum(sorted(lens)[-prefill_batch:]), exact=True)
+    dev = model.transformer.wte.weight.device
+    P = _shared_prefix(model, prompts, share_prefix, dev)
+    # slots 0..max_rows-1 and the spare one; a prefill packs at most the prefill_batch longest prompts (their tokens behind the prefix)
+    eng = model.engine(sched.max_rows + 1, need_pos, max(P, sum(sorted(n - P for n in lens)[-prefill_batch:])), exact=True)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
-                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing)
+                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P)
+    if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
+        end = be._timed("prefill_ms")
+        _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
+        if end:
+            end.record()
     sched.run(be)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
@@ -190,6 +250,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         timing["decode_steps"] = timing.get("decode_steps", 0) + sched.decode_steps
         timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + sched.decode_row_steps
         timing["launch_rows"] = set(timing.get("launch_rows", ())) | sched.launch_rows
+        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + P + be.prefill_tokens
+        timing["shared_prefix"] = P
     out: List[torch.Tensor] = []
     for i in range(N):
         n = min(length_h[i], lens[i] + max_new_tokens)

@@ -386,19 +386,28 @@ class _Engine:
                 -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(first_step),
                 torch.cuda.current_stream().cuda_stream))
 
-    def forward_slots(self, ids: torch.Tensor, seq_len: List[int], slots: List[int], prompt_phase: bool = False) -> torch.Tensor:
-        """Prompt forward (positions from 0) of sequence i into KV slot slots[i]: the last positions' logits
-        (dh_engine_forward_slots).  prompt_phase: prefill kernels even when every sequence has one token."""
+    def forward_slots(self, ids: torch.Tensor, seq_len: List[int], slots: List[int], prompt_phase: bool = False,
+                      pos0: int = 0) -> torch.Tensor:
+        """Prompt forward of sequence i into KV slot slots[i], its tokens at positions pos0.. (0: whole prompts; P: what follows
+        a shared prefix that copy_prefix has put into the slots): the last positions' logits (dh_engine_forward_slots).
+        prompt_phase: prefill kernels even when every sequence has one token."""
         n = len(seq_len)
         ids = ids.reshape(-1)
         assert len(slots) == n and ids.numel() == int(sum(seq_len)) and ids.dtype == torch.int64 and ids.is_cuda
         ids = ids.contiguous()
         ll = torch.empty((n, self.vocab), dtype=torch.bfloat16, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.dh_engine_forward_slots(self.handle, ids.data_ptr(), (C.c_int32 * n)(*seq_len), (C.c_int32 * n)(*([0] * n)),
+            _lib.check(self.lib.dh_engine_forward_slots(self.handle, ids.data_ptr(), (C.c_int32 * n)(*seq_len), (C.c_int32 * n)(*([int(pos0)] * n)),
                                                         (C.c_int32 * n)(*slots), n, int(prompt_phase), None, ll.data_ptr(),
                                                         torch.cuda.current_stream().cuda_stream))
         return ll
+
+    def copy_prefix(self, src_slot: int, dst_slots: List[int], n_pos: int) -> None:
+        """Cache positions [0, n_pos) of KV slot src_slot, every layer, into each slot of dst_slots (dh_engine_copy_prefix)."""
+        n = len(dst_slots)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_copy_prefix(self.handle, int(src_slot), (C.c_int32 * n)(*dst_slots), n, int(n_pos),
+                                                      torch.cuda.current_stream().cuda_stream))
 
     def row_arrays(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """The (row_seq, row_slot) device arrays of decode_rows: allocated once per engine, so their addresses stay

@@ -207,15 +207,17 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             args.decode_batch = fit
 
     continuous = getattr(args, "schedule", "batch") == "continuous"
+    share = "auto" if getattr(args, "share_prefix", "off") == "auto" else False
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
-                                   max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)))
+                                   max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
+                                   share_prefix=share)
             return [o.cpu() for o in outs]
         outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
-                              prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)))
+                              prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share)
         return [o.cpu() for o in outs]
 
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world,
@@ -273,6 +275,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
                    help="batch: --decode_batch utterances at a time, each batch stepped until its last sequence has finished; continuous: "
                         "--decode_batch decode rows over the whole shard, finished rows are retired and refilled (generate_stream); "
                         "the predictions do not depend on it")
+    p.add_argument("--share_prefix", choices=("off", "auto"), default="off",
+                   help="auto: the tokens every prompt of a call opens with (the template's instruction and header, the chat preamble; "
+                        "whole 32-token tiles) are prefilled once and their KV cache is copied to the other utterances, which forward "
+                        "the rest of their prompts only; the predictions do not depend on it")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)

@@ -1,7 +1,7 @@
 """Host side of continuous batching (generate.generate_stream): which prompts go in next, which KV slot each
 sequence owns, the row list of a decode chunk, its row count and when the call ends.
 
-Nothing here touches the GPU (no torch): `StreamScheduler.run(backend)` drives any object with the three methods
+Nothing here touches the GPU (torch only where shared_prefix_len is handed tensors): `StreamScheduler.run(backend)` drives any object with the three methods
 of `ScriptedBackend`, which is also how the decisions are tested on the CPU and how the number of row-steps of a
 run is predicted from the sequences' lengths."""
 from __future__ import annotations
@@ -11,6 +11,28 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 MAX_ROW_COUNTS = 8          # the engine keeps 8 captured decode graphs (csrc/engine.hip: launch_steps)
 FP8_STREAM_ROWS = 128       # fp8 decode steps stream the weights up to here and are tiled above (engine.hip: fp8_kernel)
 BF16_STREAM_ROWS = 2048     # bf16 single-token steps take the streaming path up to here (engine.hip: MAX_DECODE_ROWS)
+PREFIX_TILE = 32            # a shared prefix is whole KV-cache tiles (common.h: kfrag_off / vfrag_off) = whole q-tiles of the prefill attention
+
+
+def shared_prefix_len(prompts: Sequence) -> int:
+    """P, the number of leading tokens a call forwards once for all of its prompts (generate_batch / generate_stream,
+    share_prefix): the longest common token prefix, cut so that every prompt keeps a token of its own (its last position
+    must produce logits), rounded down to whole tiles of 32.  0: nothing is shared.
+    prompts: 1-D integer tensors (compared on their device, one read-back) or plain sequences of ids."""
+    cap = min(len(p) for p in prompts) - 1
+    if cap < PREFIX_TILE:
+        return 0
+    first = prompts[0]
+    if hasattr(first, "new_ones"):
+        import torch
+        m = torch.stack([p[:cap] for p in prompts])
+        differs = (m != m[0]).any(dim=0)
+        L = int(torch.cat([differs, differs.new_ones(1)]).int().argmax())     # the first column that differs, or cap
+    else:
+        L = cap
+        for p in prompts[1:]:
+            L = next((i for i in range(L) if p[i] != first[i]), L)
+    return L // PREFIX_TILE * PREFIX_TILE
 
 
 def row_buckets(max_rows: int, floor: int = 1) -> List[int]:

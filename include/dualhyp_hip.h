@@ -448,6 +448,22 @@ int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const int32_t* h_s
                             const int32_t* h_pos0, const int32_t* h_slot, int n_seq, int prompt_phase,
                             dh_bf16* logits_all, dh_bf16* logits_last, void* stream);
 
+/* Fork a KV prefix: cache positions [0, n_pos) of slot src_slot, K and V^T of every layer and group, are copied
+ * into each of the n_dst slots of h_dst_slots (host array) by one launch on `stream`.  Replaces the per-utterance
+ * recomputation of inference/ger.py:60-83, where every prompt's instruction sentences and "### ... Best-hypothesis:"
+ * header go through all layers again: K and V at a position depend on the tokens at or before it alone, and a
+ * prefill row's bits do not depend on what it is packed with, so sequences that open with the same n_pos tokens
+ * hold the same bits there.  Forward the shared tokens once into src_slot, fork them, then forward each
+ * sequence's remaining tokens with h_pos0 = n_pos (dh_engine_forward_slots, prompt_phase = 1): caches and logits
+ * equal those of the whole prompts' forward.
+ * n_pos is a multiple of 32, the cache tile (the caches store 32-key tiles back to back from the start of a
+ * (slot, group) block, so the copy is one contiguous run of n_pos * head_size elements per block at every head
+ * size), 0 < n_pos <= s_max.  Slots are in [0, max_batch); the destinations are distinct and exclude src_slot.
+ * Positions >= n_pos of the destinations and every other slot keep their contents.  The cache is bf16 in bf16
+ * and fp8 engines alike.  n_dst = 0 is a no-op. */
+int dh_engine_copy_prefix(dh_engine* e, int src_slot, const int32_t* h_dst_slots, int n_dst, int n_pos,
+                          void* stream);
+
 /* Reproduce the rsqrt rounding of the reference's CPU path (see dh_rmsnorm_bf16 row_tail):
  * vec_width = lanes of torch's bf16 vector loop on the reference host (32 on AVX-512, 16 on
  * AVX2), 0 = off (every row uses bf16(1/sqrt(t)), as a GPU run of the reference would).
