@@ -6,7 +6,9 @@
 namespace {
 
 __device__ __forceinline__ uint32_t bf16_key(bf16_t v) {
-    // monotone map bf16 bits -> uint16 key (larger value = larger key)
+    // monotone map bf16 bits -> uint16 key (larger value = larger key).  -0 takes +0's key: the reference crops with
+    // `l < kth`, for which the two zeros are equal, so a zero of either sign at the threshold keeps both
+    if ((v & 0x7FFFu) == 0) return 0x8000u;
     return (v & 0x8000u) ? (uint32_t)(~v & 0xFFFFu) : (uint32_t)(v | 0x8000u);
 }
 

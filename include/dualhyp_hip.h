@@ -307,8 +307,16 @@ int dh_col2im3_bf16(const dh_bf16* dcol, const dh_bf16* pre, const dh_bf16* mask
 /* One decode-loop tail per sequence — generate/base.py:62-80:
  *   l = logits/temperature (bf16) ; keep l >= k-th largest ; softmax ; multinomial.
  * top_k == 1 is resolved as arg-max with the LOWEST index among equal maxima (the reference
- * breaks bf16 ties with the torch RNG, quirk Q6).  top_k == 0 means no cropping.  For
- * top_k != 1 a counter hash of (seed, step, seq) drives the inverse-CDF draw.
+ * breaks bf16 ties with the torch RNG, quirk Q6).  top_k == 0 means no cropping; entries equal
+ * to the k-th largest are all kept, and -0 == +0 there as in the reference's `l < kth`.
+ * For top_k != 1 the draw is the inverse CDF, in ascending token order, of the fp32 softmax over
+ * the kept entries at the uniform
+ *   u = (mix64(seed ^ mix64(((uint64_t)step << 32) | (uint32_t)seq)) >> 40) / 2^24      in [0, 1)
+ *   mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)   (splitmix64, mod 2^64;
+ *             mix64(0) == 0xE220A8397B1DCDAF)
+ * with seq the row of `logits`.  The stream is part of the contract: seeded ids stay the same
+ * across versions (tests/sampling_reference.py is the host model).  NaN logits are not supported.
  *   tokens [n_seq, tok_ld] int64 : token buffer per sequence (prompt + generated)
  *   length [n_seq] int32         : tokens currently valid; the new id goes to
  *                                  tokens[i, length[i]] and length[i] is incremented
