@@ -92,6 +92,9 @@ SIGNATURES = {
     "dh_engine_set_cpu_rsqrt_emulation": (I, [P, I, I]),
     "dh_engine_decode": (I, [P, P, I, P, P, I, I, F, I, I64, U64, I, P]),
     "dh_engine_decode_rows": (I, [P, P, I, P, P, P, I, I, P, P, I, I, F, I, I64, U64, P]),
+    "dh_engine_decode_spec": (I, [P, P, I, P, P, P, I, I, I, P, P, I, F, I64, I, P]),
+    "dh_engine_reserve_rows": (I, [P, I]),
+    "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),
     "dh_engine_get_timing": (I, [P, I, C.POINTER(C.c_double), C.POINTER(I64)]),

@@ -189,6 +189,16 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, void* stream);
 
+// the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
+// acceptance kernel (sampling.hip)
+int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_seq, int S, int qkv_dim, int n_ext,
+                              const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
+                              const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
+                              dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream);
+int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
+                        int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
+                        const int32_t* step_dev, int32_t* counters, void* stream);
+
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads
 // racing on the first launch both set it, which is harmless.  `kernel` must be parenthesised if it contains commas.

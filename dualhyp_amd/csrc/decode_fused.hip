@@ -272,6 +272,252 @@ constexpr size_t attn_fused_lds() {
     return 16 * HS * 2 + (HS + HS + 48 + 16 + NW * DCOLS + NW * DCOLS + NW * HS * DCOLS) * sizeof(float);
 }
 
+// --------------------------------------------------------------------------- attention (verify)
+// attn_decode_fused_kernel for S = D + 1 consecutive positions of a sequence at once (speculative greedy decoding: the last token
+// and D drafted ones).  grid (n_seq * n_groups), NW waves; qkv32 rows seq * S + j, j = 0 .. S-1, row j at position pos + j.  The
+// S * q_per_kv <= 32 query columns ride in the 32 columns of the MFMA the single-token kernel pays for with q_per_kv <= 16 live.
+// Row j produces the bits attn_decode_fused_kernel produces at kv_len = len + j:
+//   - same NW, same tile -> wave deal (t % NW), same per-tile update and same combine order; a column's arithmetic never reads
+//     another column;
+//   - column of row j sees the keys [0, pos + j) as cached keys of their 32-key tiles (mask per column) and merges its own key
+//     at the combine from LDS.  Keys [pos, pos + j) are those rows 0 .. j-1 of this block have just appended: the tiles that
+//     hold positions >= pos are loaded behind the fence + barrier that follows the append, the tiles wholly below pos keep the
+//     early prefetch;
+//   - a tile in which a column sees no key (the single-token kernel at that kv_len never walks it) leaves the column's running
+//     maximum, sum and accumulator as they are: m_run - m_new would be -inf - -inf there.
+// Rows at positions >= p_max (the cache's or the rope table's end; a draft behind the last position that can be generated is
+// never accepted) append nothing; their output rows are finite and unused.
+template <int HS, int PMAX, int NW>
+__global__ __launch_bounds__(NW * 64, 1) void attn_verify_fused_kernel(
+    const float* __restrict__ qkv32, int n_part, int pairs, int n_rows, int ldq, int qkv_dim,
+    const bf16_t* __restrict__ lora_b, float lora_scale, int split0, int split1,
+    const bf16_t* __restrict__ cos, const bf16_t* __restrict__ sin, const int32_t* __restrict__ seq_slot,
+    const int32_t* __restrict__ kv_len, bf16_t* __restrict__ k_cache, bf16_t* __restrict__ vT_cache,
+    bf16_t* __restrict__ y, int n_head, int n_groups, int s_max, int p_max, int S, float scale) {
+    constexpr int KS = HS / 16, DT = HS / 32, HALF = HS / 2, VC = 32;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int pair = blockIdx.x, seq = pair / n_groups, g = pair % n_groups;
+    const int q_per_kv = n_head / n_groups, ncol = S * q_per_kv;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int slot = seq_slot[seq];
+    const int len = kv_len[seq], pos = len - 1;          // row 0 (the last token) sits at position len-1
+    const int n_live = min(S, p_max - pos);              // rows whose position exists (>= 1: the caller clamps len to p_max)
+    // LDS carve (all offsets multiples of 16 B)
+    bf16_t* sQ = reinterpret_cast<bf16_t*>(smem);                       // [32][HS] rotated queries, column = j * q_per_kv + head
+    float* sKn = reinterpret_cast<float*>(smem + VC * HS * 2);          // [S][HS] new keys (bf16 values)
+    float* sVn = sKn + S * HS;                                          // [S][HS] new values
+    float* sXa = sVn + S * HS;                                          // [S][48] bf16(x·A^T)
+    float* sSn = sXa + S * 48;                                          // [32] score of a column's own key
+    float* sPm = sSn + VC;                                              // [NW][32] running max
+    float* sPl = sPm + NW * VC;                                         // [NW][32] running sum
+    float* sPo = sPl + NW * VC;                                         // [NW][HS][ncol] partial O^T
+    constexpr int NT_ = NW * 64;
+
+    struct VF { bf16x8 v; };
+    struct Tile { bf16x8 kf[KS]; VF vf[DT][2]; };
+    Tile tl;
+    const bf16_t* kbase = k_cache + ((size_t)slot * n_groups + g) * s_max * HS;
+    const bf16_t* vbase = vT_cache + ((size_t)slot * n_groups + g) * HS * s_max;
+    const int n_tiles = (pos + n_live - 1 + 31) / 32;    // tiles with a key some live row sees: keys [0, pos + n_live - 1)
+    const int t_safe = pos >> 5;                         // tiles below hold positions < pos only: nobody writes them in this launch
+    auto load_tile = [&](Tile& T, int t, bool early) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const bf16x8* p = reinterpret_cast<const bf16x8*>(kbase + kfrag_blk<HS>(t, ks) + lane * 8);
+            T.kf[ks] = early ? __builtin_nontemporal_load(p) : *p;
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const bf16x8* p = reinterpret_cast<const bf16x8*>(vbase + vfrag_blk<HS>(t, dt, s2) + lane * 8);
+                T.vf[dt][s2].v = early ? __builtin_nontemporal_load(p) : *p;
+            }
+    };
+    if (wave < t_safe) load_tile(tl, wave, true);
+
+    const size_t pstride = (size_t)n_rows * ldq;
+    auto psum = [&](int j, int c) {
+        const float* row0 = qkv32 + ((size_t)seq * S + j) * ldq;
+        float v[PMAX];
+#pragma unroll
+        for (int p = 0; p < PMAX; ++p) v[p] = p < n_part ? row0[p * pstride + c] : 0.f;
+        float s = 0.f;
+        if (pairs) {
+#pragma unroll
+            for (int p = 0; p < PMAX; p += 2) s += v[p] + v[p + 1];
+        } else {
+#pragma unroll
+            for (int p = 0; p < PMAX; ++p) s += v[p];
+        }
+        return s;
+    };
+    if (lora_b != nullptr)
+        for (int i = tid; i < 48 * S; i += NT_) sXa[i] = rbf(psum(i / 48, qkv_dim + i % 48));
+    for (int i = tid; i < VC * HS; i += NT_) sQ[i] = 0;               // padding columns and rows without a position
+    for (int i = tid; i < 2 * S * HS; i += NT_) sKn[i] = 0.f;         // sKn and sVn are adjacent
+    __syncthreads();
+
+    auto finish = [&](int j, int c) -> float {
+        float o = rbf(psum(j, c));
+        if (lora_b != nullptr) {
+            const int seg = (c >= split0) + (c >= split1);
+            const uint4* b4 = reinterpret_cast<const uint4*>(lora_b + (size_t)c * 16);
+            float l = 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint4 bv = b4[h];
+                const bf16_t* bp = reinterpret_cast<const bf16_t*>(&bv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) l = fmaf(sXa[j * 48 + seg * 16 + h * 8 + e], bf2f(bp[e]), l);
+            }
+            o = rbf(o + rbf(rbf(l) * lora_scale));
+        }
+        return o;
+    };
+    const int gbase = g * (q_per_kv + 2) * HS;
+    bf16_t* kdst = k_cache + ((size_t)slot * n_groups + g) * s_max * HS;
+    bf16_t* vdst = vT_cache + ((size_t)slot * n_groups + g) * HS * s_max;
+    const int n_rope = (q_per_kv + 1) * HALF, per_row = n_rope + HS;
+    for (int it0 = tid; it0 < n_live * per_row; it0 += NT_) {
+        const int jr = it0 / per_row, it = it0 % per_row, pj = pos + jr;     // pj < p_max <= s_max
+        if (it < n_rope) {
+            const int j = it / HALF, i = it % HALF;
+            const float x1 = finish(jr, gbase + j * HS + i), x2 = finish(jr, gbase + j * HS + HALF + i);
+            const bf16_t* cp = cos + (size_t)pj * HS;
+            const bf16_t* sp = sin + (size_t)pj * HS;
+            const bf16_t o1 = f2bf(rbf(x1 * bf2f(cp[i])) + rbf(-x2 * bf2f(sp[i])));
+            const bf16_t o2 = f2bf(rbf(x2 * bf2f(cp[HALF + i])) + rbf(x1 * bf2f(sp[HALF + i])));
+            if (j < q_per_kv) {
+                sQ[(jr * q_per_kv + j) * HS + i] = o1;
+                sQ[(jr * q_per_kv + j) * HS + HALF + i] = o2;
+            } else {
+                sKn[jr * HS + i] = bf2f(o1);
+                sKn[jr * HS + HALF + i] = bf2f(o2);
+                kdst[kfrag_off<HS>(pj, i)] = o1;
+                kdst[kfrag_off<HS>(pj, HALF + i)] = o2;
+            }
+        } else {
+            const int e = it - n_rope;
+            const bf16_t v = f2bf(finish(jr, gbase + (q_per_kv + 1) * HS + e));
+            sVn[jr * HS + e] = bf2f(v);
+            vdst[vfrag_off<HS>(pj, e)] = v;
+        }
+    }
+    __threadfence_block();      // the appended K / V are visible to the block's later loads of the tiles >= t_safe
+    __syncthreads();
+    if (wave >= t_safe && wave < n_tiles) load_tile(tl, wave, false);
+
+    // score of each column's own key (merged at the combine, as in the single-token kernel)
+    for (int c = wave; c < ncol; c += NW) {
+        const float* kn = sKn + (c / q_per_kv) * HS;
+        float p = 0.f;
+        for (int e = lane; e < HS; e += 64) p += bf2f(sQ[c * HS + e]) * kn[e];
+        p = wave_sum(p);
+        if (lane == 0) sSn[c] = p * scale;
+    }
+
+    bf16x8 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(sQ + lr * HS + ks * 16 + lh * 8);
+    // the keys this lane's column sees in the cache: [0, p_col)
+    const int j_col = lr < ncol ? lr / q_per_kv : 0;
+    const int p_col = pos + (j_col < n_live ? j_col : 0);
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+    auto compute_tile = [&](const Tile& T, int t) {
+        const int key0 = t * 32;
+        f32x16 st;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.kf[ks], qf[ks], st, 0, 0, 0);
+        float m_t = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key_abs = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            float sc = st[r] * scale;
+            sc = key_abs < p_col ? sc : -INFINITY;
+            st[r] = sc;
+            m_t = fmaxf(m_t, sc);
+        }
+        m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
+        const float m_new = fmaxf(m_run, m_t);
+        const bool none = m_new == -INFINITY;               // no key of this column so far: nothing changes
+        const float alpha = none ? 1.f : __expf(m_run - m_new);
+        m_run = m_new;
+        float psm = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = none ? 0.f : __expf(st[r] - m_new);
+            st[r] = p;
+            psm += p;
+        }
+        l_run = l_run * alpha + psm;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            union { bf16x8 v; uint32_t u[4]; } pf;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pf.u[j] = pack2bf(st[8 * s2 + 2 * j], st[8 * s2 + 2 * j + 1]);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                if (s2 == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+                }
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.vf[dt][s2].v, pf.v, o[dt], 0, 0, 0);
+            }
+        }
+    };
+    for (int base = wave; base < n_tiles; base += NW) {
+        compute_tile(tl, base);
+        if (base + NW < n_tiles) load_tile(tl, base + NW, false);       // behind the barrier: any tile may be read
+    }
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (lr < ncol) {
+        if (lh == 0) {
+            sPm[wave * VC + lr] = m_run;
+            sPl[wave * VC + lr] = l_tot;
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                sPo[(wave * HS + d) * ncol + lr] = o[dt][r];
+            }
+    }
+    __syncthreads();
+    // ---- combine the NW wave partials and each column's own key
+    for (int it = tid; it < ncol * HS; it += NT_) {
+        const int c = it / HS, d = it % HS, jr = c / q_per_kv, h = c % q_per_kv;
+        const float sn = sSn[c];
+        float M = sn;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, sPm[w * VC + c]);
+        const float pn = __expf(sn - M);
+        float L = pn, O = rbf(pn) * sVn[jr * HS + d];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = sPm[w * VC + c];
+            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            L += sPl[w * VC + c] * f;
+            O += sPo[(w * HS + d) * ncol + c] * f;
+        }
+        y[((size_t)seq * S + jr) * n_head * HS + (g * q_per_kv + h) * HS + d] = f2bf(O / L);
+    }
+}
+template <int HS>
+size_t attn_verify_lds(int S, int ncol) {
+    constexpr int NW = attn_fused_waves<HS>();
+    return 32 * HS * 2 + (size_t)(2 * S * HS + 48 * S + 32 + 2 * NW * 32 + NW * HS * ncol) * sizeof(float);
+}
+
 // --------------------------------------------------------------------------- finish + norm
 // grid (rows), 256 threads.  h32: [n_part][rows][ldh] fp32 partials of x·[W;A]^T (columns
 // [d, d+16) = x·A^T when lora_b != null).  Per row:
@@ -436,6 +682,46 @@ extern "C" int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pai
         else ATT_LAUNCH(128, 16);
     }
 #undef ATT_LAUNCH
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+// the verify step's attention (engine.hip, dh_engine_decode_spec): dh_attn_decode_fused_bf16 for S rows per sequence
+int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_seq, int S, int qkv_dim, int n_ext,
+                              const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
+                              const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
+                              dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream) {
+    DH_CHECK(qkv32 && cos && sin && seq_slot && kv_len && k_cache && vT_cache && y, "attn_verify_fused: null argument");
+    DH_CHECK(n_groups > 0 && n_head % n_groups == 0, "attn_verify_fused: bad head counts");
+    DH_CHECK(S >= 2 && S <= 8 && S * (n_head / n_groups) <= 32, "attn_verify_fused: %d positions x %d heads per group exceed 32 query columns",
+             S, n_head / n_groups);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "attn_verify_fused: head_size %d unsupported", hs);
+    DH_CHECK(s_max % 64 == 0 && p_max > 0 && p_max <= s_max && n_part >= 1 && n_part <= MAXP, "attn_verify_fused: bad s_max / p_max / n_part");
+    DH_CHECK(qkv_dim == (n_head + 2 * n_groups) * hs, "attn_verify_fused: qkv_dim mismatch");
+    DH_CHECK(lora_b == nullptr || n_ext >= 48, "attn_verify_fused: LoRA needs the 48 x·A^T columns");
+    if (n_seq <= 0) return 0;
+    const float scale = 1.0f / sqrtf((float)hs);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(n_seq * n_groups);
+    const int ncol = S * (n_head / n_groups);
+#define VER_LAUNCH(HSV, PM)                                                                                           \
+    hipLaunchKernelGGL((attn_verify_fused_kernel<HSV, PM, attn_fused_waves<HSV>()>), grid, dim3(64 * attn_fused_waves<HSV>()), attn_verify_lds<HSV>(S, ncol), s, qkv32, n_part, pairs, \
+                       n_seq * S, qkv_dim + n_ext, qkv_dim, lora_b, lora_scale, split0, split1, cos, sin, seq_slot, kv_len, k_cache,  \
+                       vT_cache, y, n_head, n_groups, s_max, p_max, S, scale)
+#define VER_HS(HSV)                                                                                                   \
+    do {                                                                                                              \
+        DH_MAX_LDS_ONCE((attn_verify_fused_kernel<HSV, 2, attn_fused_waves<HSV>()>), attn_verify_lds<HSV>(8, 32));    \
+        DH_MAX_LDS_ONCE((attn_verify_fused_kernel<HSV, 8, attn_fused_waves<HSV>()>), attn_verify_lds<HSV>(8, 32));    \
+        DH_MAX_LDS_ONCE((attn_verify_fused_kernel<HSV, 16, attn_fused_waves<HSV>()>), attn_verify_lds<HSV>(8, 32));   \
+        if (n_part <= 2) VER_LAUNCH(HSV, 2);                                                                          \
+        else if (n_part <= 8) VER_LAUNCH(HSV, 8);                                                                     \
+        else VER_LAUNCH(HSV, 16);                                                                                     \
+    } while (0)
+    if (hs == 64) VER_HS(64);
+    else if (hs == 96) VER_HS(96);
+    else VER_HS(128);
+#undef VER_HS
+#undef VER_LAUNCH
     DH_LAUNCH_CHECK();
     return 0;
 }

@@ -27,6 +27,7 @@ struct dh_engine {
     dh_model_desc d;
     std::vector<dh_layer_weights> layers;
     int max_batch = 0, s_max = 0, max_tokens = 0;
+    int row_cap = 0;                                  // rows the single-token-step workspaces hold (logits, part32, dec_ids, ones): max_batch, or what dh_engine_reserve_rows asked for
     int qkv_dim = 0, kv_dim = 0;
     // device memory
     bf16_t *kc = nullptr, *vtc = nullptr;             // [L][B][G][S][HS], [L][B][G][HS][S]
@@ -50,6 +51,7 @@ struct dh_engine {
     int32_t* h_stage = nullptr;                         // pinned staging for the metadata, carved by stage() below
     size_t cache_layer_elems = 0;
     int64_t dev_bytes = 0;
+    int64_t row_ws_bytes = 0;                         // the part of dev_bytes that alloc_row_ws holds
     // decode graph
     hipStream_t gstream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_stage = nullptr;
@@ -58,11 +60,12 @@ struct dh_engine {
     struct GKey {
         int64_t* tokens; int tok_ld; int32_t *length, *done; int n_seq, top_k; float temp; int64_t eos; uint64_t seed; int rsqrt_vec, tiled_rows;
         const int32_t *limit, *row_seq, *row_slot; int n_all, max_new;
+        int spec; const int64_t* drafts; int32_t* counters;   // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
         bool operator==(const GKey& k) const {
             return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
-                   n_all == k.n_all && max_new == k.max_new;
+                   n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters;
         }
     };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
@@ -169,6 +172,64 @@ __global__ void decode_prep_kernel(const int64_t* __restrict__ tokens, int tok_l
         tok_slot[r] = slot;
         tok_pos[r] = n - 1;
         kv_len[r] = n;
+    }
+}
+
+// The same for a verify step of D = S - 1 drafts (dh_engine_decode_spec), one block per sequence: row u * S + j gets the sequence's
+// last token (j = 0) or its j-th draft, position len - 1 + j and slot u; kv_len[u] = len.  The length is clamped as above and to the
+// rope table; a position behind the cache's end is clamped too (the attention kernel appends nothing for such a row).
+// drafts != null: the scripted proposer, drafts[u, i] stands for the i-th generated token of sequence u (limit[u] - max_new = its
+// prompt length).  drafts == null: prompt lookup, dualhyp_amd/speculate.py:propose on tokens[u, :len] — for n = ngram_max .. 1 the
+// latest earlier occurrence of the last n tokens that a token follows; the drafts are the up to D tokens behind it, padded with the
+// last of them (which is then tokens[len - 1]); no occurrence: tokens[len - 1], D times.  An id outside the embedding table is
+// replaced by the last token.
+__global__ __launch_bounds__(256) void spec_prep_kernel(const int64_t* __restrict__ tokens, int tok_ld, const int32_t* __restrict__ length,
+                                                        const int32_t* __restrict__ limit, int max_new, const int64_t* __restrict__ drafts,
+                                                        int S, int ngram_max, int64_t* __restrict__ ids, int32_t* __restrict__ tok_slot,
+                                                        int32_t* __restrict__ tok_pos, int32_t* __restrict__ kv_len, int32_t* step_dev,
+                                                        int cap, int n_vocab) {
+    __shared__ int s_best;
+    const int u = blockIdx.x, tid = threadIdx.x;
+    if (u == 0 && tid == 0) *step_dev += 1;
+    int n = length[u];
+    n = n < 1 ? 1 : (n > cap ? cap : n);
+    const int64_t* row = tokens + (size_t)u * tok_ld;
+    int start = -1;                                   // index of the first token to draft
+    if (drafts == nullptr) {
+        for (int ng = ngram_max < n - 1 ? ngram_max : n - 1; ng >= 1; --ng) {
+            if (tid == 0) s_best = -1;
+            __syncthreads();
+            int best = -1;
+            for (int i = tid; i + ng < n; i += 256) {       // an occurrence at i is followed by tokens[i + ng]
+                bool ok = true;
+                for (int k = 0; k < ng; ++k) ok = ok && row[i + k] == row[n - ng + k];
+                if (ok) best = i;
+            }
+            if (best >= 0) atomicMax(&s_best, best);
+            __syncthreads();
+            const int b = s_best;
+            __syncthreads();
+            if (b >= 0) { start = b + ng; break; }
+        }
+    }
+    if (tid < S) {
+        const int j = tid;
+        int64_t id = row[n - 1];
+        if (j > 0) {
+            if (drafts != nullptr) {
+                const int i = n - 1 + j - (limit[u] - max_new);
+                if (i >= 0 && i < max_new) id = drafts[(size_t)u * max_new + i];
+            } else if (start >= 0) {
+                const int i = start + j - 1;
+                id = row[i < n - 1 ? i : n - 1];
+            }
+            if (id < 0 || id >= n_vocab) id = row[n - 1];
+        }
+        const int r = u * S + j, pj = n - 1 + j;
+        ids[r] = id;
+        tok_slot[r] = u;
+        tok_pos[r] = pj < cap ? pj : cap - 1;
+        if (j == 0) kv_len[u] = n;
     }
 }
 
@@ -455,7 +516,9 @@ int pick_ksplit(int nks) {
 
 // Single-token step for n_seq <= MAX_DECODE_ROWS sequences: 7 launches per layer (decode_fused.hip).  Leaves
 // ln_f(x) in e->xn.
-int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t* tail_flags, hipStream_t s) {
+// spec_S > 1 (a verify step, dh_engine_decode_spec): the n_seq rows are spec_S consecutive positions of n_seq / spec_S sequences; the
+// linears are the same launches over the same rows, the attention is attn_verify_fused_kernel over the sequences.
+int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t* tail_flags, hipStream_t s, int spec_S = 1) {
     const dh_model_desc& D = e->d;
     const int d = D.n_embd, I = D.intermediate, hs = D.head_size, H = D.n_head, G = D.n_groups;
     const uint8_t* rt = e->rsqrt_vec > 0 ? tail_flags : nullptr;
@@ -479,6 +542,12 @@ int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t
         int np, pairs;
         const int ext1 = W.attn_lora_a ? 48 : 0;
         if ((rc = partial(e->xn, W.attn_w, W.attn_lora_a, e->qkv_dim, ext1, d, pick_ksplit(d / 32), np, pairs))) return rc;
+        if (spec_S > 1) {
+            const int p_max = e->s_max < D.block_size ? e->s_max : D.block_size;
+            if ((rc = dh_attn_verify_fused_impl(e->part32, np, pairs, n_seq / spec_S, spec_S, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale,
+                                                d, d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
+                                                e->s_max, p_max, s))) return rc;
+        } else
         if ((rc = dh_attn_decode_fused_bf16(e->part32, np, pairs, n_seq, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale, d,
                                             d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G,
                                             hs, e->s_max, s))) return rc;
@@ -540,6 +609,40 @@ int run_model(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q,
     return 0;
 }
 
+// fp32 partial sums of a single-token step over `rows` rows: up to 16 K-slices of the widest product (the fused QKV + x·A^T)
+size_t part32_elems(const dh_engine* e, int rows) {
+    return (size_t)16 * (rows < 32 ? 32 : (rows < MAX_DECODE_ROWS ? rows : MAX_DECODE_ROWS)) * (e->qkv_dim + 48);
+}
+
+// The workspaces a single-token step sizes by its row count (logits, dec_ids, ones, part32).  engine_init and dh_engine_reserve_rows
+// both allocate them here, so their sizes are written once.  The engine's pointers change only after all four allocations have
+// succeeded: a failure leaves the engine, row_cap and dev_bytes as they were.  The caller has made sure nothing reads the old ones.
+int alloc_row_ws(dh_engine* e, int rows) {
+    decltype(e->logits) logits = nullptr;
+    decltype(e->dec_ids) dec_ids = nullptr;
+    decltype(e->ones) ones = nullptr;
+    decltype(e->part32) part32 = nullptr;
+    const int64_t before = e->dev_bytes;
+    int rc = 0;
+    rc |= dmalloc(e, &logits, (size_t)rows * e->d.vocab);
+    rc |= dmalloc(e, &dec_ids, (size_t)rows);
+    rc |= dmalloc(e, &ones, (size_t)rows);
+    rc |= dmalloc(e, &part32, part32_elems(e, rows));
+    if (!rc && hipMemset(ones, 1, (size_t)rows) != hipSuccess) rc = 2;
+    if (rc) {
+        hipFree(logits); hipFree(dec_ids); hipFree(ones); hipFree(part32);
+        e->dev_bytes = before;
+        return 2;
+    }
+    hipFree(e->logits); hipFree(e->dec_ids); hipFree(e->ones); hipFree(e->part32);
+    e->logits = logits; e->dec_ids = dec_ids; e->ones = ones; e->part32 = part32;
+    const int64_t bytes = e->dev_bytes - before;
+    e->dev_bytes -= e->row_ws_bytes;
+    e->row_ws_bytes = bytes;
+    e->row_cap = rows;
+    return 0;
+}
+
 int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens) {
     e->d = *desc;
     e->layers.assign(desc->h_layers, desc->h_layers + desc->n_layer);
@@ -580,7 +683,6 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     rc |= dmalloc(e, &e->xa, T * 48);
     rc |= dmalloc(e, &e->act, T * desc->intermediate);
     rc |= dmalloc(e, &e->xlast, (size_t)max_batch * d);
-    rc |= dmalloc(e, &e->logits, (size_t)max_batch * desc->vocab);
     rc |= dmalloc(e, &e->tok_slot, T);
     rc |= dmalloc(e, &e->tok_pos, T);
     rc |= dmalloc(e, &e->seq_meta, (size_t)4 * max_batch);
@@ -593,15 +695,13 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     rc |= dmalloc(e, &e->slot_list, (size_t)max_batch);
     rc |= dmalloc(e, &e->copy_dst, (size_t)max_batch);
     rc |= dmalloc(e, &e->cache_tab, (size_t)2 * desc->n_layer);
-    rc |= dmalloc(e, &e->dec_ids, (size_t)max_batch);
-    rc |= dmalloc(e, &e->part32, (size_t)16 * (max_batch < 32 ? 32 : (max_batch < MAX_DECODE_ROWS ? max_batch : MAX_DECODE_ROWS)) * (e->qkv_dim + 48));
+    rc |= alloc_row_ws(e, max_batch);
     if (e->fp8) {
         rc |= dmalloc(e, &e->xq, T * (size_t)(desc->intermediate > d ? desc->intermediate : d));
         rc |= dmalloc(e, &e->xscale, T);
     }
     rc |= dmalloc(e, &e->row_tail, T);
     rc |= dmalloc(e, &e->last_tail, (size_t)max_batch);
-    rc |= dmalloc(e, &e->ones, (size_t)max_batch);
     const int64_t wb = dh_attn_decode_work_bytes(max_batch, H, hs, s_max);
     if (!rc) { hipError_t he = hipMalloc(&e->dec_work, wb); if (he != hipSuccess) rc = 2; e->dev_bytes += wb; }
     if (rc) { dh_set_error("dh_engine_create: device allocation failed (%s)", dh_last_error()); return 2; }
@@ -609,7 +709,6 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     DH_HIP(hipMemset(e->kc, 0, e->cache_layer_elems * desc->n_layer * sizeof(bf16_t)));
     DH_HIP(hipMemset(e->vtc, 0, e->cache_layer_elems * desc->n_layer * sizeof(bf16_t)));
     DH_HIP(hipMemset(e->step_dev, 0, sizeof(int32_t)));
-    DH_HIP(hipMemset(e->ones, 1, (size_t)max_batch));
     {
         std::vector<bf16_t*> tab(2 * (size_t)desc->n_layer);
         for (int l = 0; l < desc->n_layer; ++l) {
@@ -693,7 +792,27 @@ int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, con
 // kernel family is the row count's) with logits in e->logits, one sampled token per live sequence.  k.row_seq == nullptr
 // (dh_engine_decode): row r is sequence r in slot r, the draw is keyed by the step counter in step_dev, which the prep kernel
 // increments.  Else (dh_engine_decode_rows) the prep and the sampling kernel index the per-sequence arrays through the row list.
+// One verify step of k.spec drafts per sequence (dh_engine_decode_spec): the prep kernel proposes and lays out the k.n_seq * S rows,
+// the streaming single-token family runs over them with the verify attention, the head gives every row's logits, the acceptance
+// kernel appends what the drafts got right plus one.
+int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
+    const int S = k.spec + 1, rows = k.n_seq * S;
+    const dh_model_desc& D = e->d;
+    int cap = e->s_max < k.tok_ld ? e->s_max : k.tok_ld;
+    cap = cap < D.block_size ? cap : D.block_size;
+    hipLaunchKernelGGL(spec_prep_kernel, dim3(k.n_seq), dim3(256), 0, s, k.tokens, k.tok_ld, k.length, k.limit, k.max_new, k.drafts, S, 3,
+                       e->dec_ids, e->tok_slot, e->tok_pos, seq_meta(e).kv, e->step_dev, cap, D.wte_rows);
+    DH_LAUNCH_CHECK();
+    e->decode_tiled = false;
+    int rc;
+    if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
+    if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
+    return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
+                               e->step_dev, k.counters, s);
+}
+
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
+    if (k.spec) return verify_step(e, k, s);
     const bool rows = k.row_seq != nullptr;
     hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(k.n_seq, 64)), dim3(64), 0, s, k.tokens, k.tok_ld, k.length, k.row_seq, k.row_slot,
                        e->dec_ids, e->tok_slot, e->tok_pos, seq_meta(e).kv, rows ? nullptr : e->step_dev, k.n_seq, k.n_all,
@@ -807,6 +926,8 @@ extern "C" int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int6
             src = (what == 1 ? e->kc : e->vtc) + (size_t)layer * e->cache_layer_elems;
             avail = cache_bytes;
             break;
+        case 4: src = e->dec_ids; avail = (int64_t)e->row_cap * sizeof(int64_t); break;
+        case 5: src = seq_meta(e).kv; avail = (int64_t)e->max_batch * sizeof(int32_t); break;
         default: DH_CHECK(false, "dh_engine_read: unknown selector %d", what);
     }
     DH_CHECK(n_bytes <= avail, "dh_engine_read: %lld bytes requested, %lld available", (long long)n_bytes, (long long)avail);
@@ -908,6 +1029,53 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               limit, row_seq, row_slot, n_seq, max_new_tokens};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
+}
+
+extern "C" int dh_engine_reserve_rows(dh_engine* e, int rows) {
+    DH_CHECK(e, "dh_engine_reserve_rows: null engine");
+    DH_CHECK(rows > 0 && rows <= MAX_DECODE_ROWS && rows <= e->max_tokens,
+             "dh_engine_reserve_rows: %d rows (at most %d, and the engine's max_tokens = %d)", rows, MAX_DECODE_ROWS, e->max_tokens);
+    if (rows <= e->row_cap) return 0;
+    // the captured steps hold the old addresses
+    DH_HIP(hipDeviceSynchronize());
+    for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
+    e->graphs.clear();
+    // on failure the engine keeps its workspaces and row_cap; its steps are captured again when they are next asked for
+    if (alloc_row_ws(e, rows)) { dh_set_error("dh_engine_reserve_rows: device allocation failed (%s)", dh_last_error()); return 2; }
+    return 0;
+}
+
+extern "C" int dh_engine_graph_count(const dh_engine* e, int n_draft) {
+    if (!e) return -1;
+    int n = 0;
+    for (const auto& g : e->graphs) n += n_draft < 0 || g.key.spec == n_draft;
+    return n;
+}
+
+extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, const int32_t* limit,
+                                     int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts, int32_t* counters, int n_steps,
+                                     float temperature, int64_t eos_id, int first_step, void* stream) {
+    DH_CHECK(e && tokens && length && done && limit && counters, "dh_engine_decode_spec: null argument");
+    DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode_spec: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
+    DH_CHECK(tok_ld > 0 && max_new_tokens > 0 && temperature > 0.f, "dh_engine_decode_spec: bad shape or temperature");
+    DH_CHECK(n_draft >= 1 && n_draft <= 7, "dh_engine_decode_spec: n_draft=%d is not in 1..7", n_draft);
+    const int S = n_draft + 1, q_per_kv = e->d.n_head / e->d.n_groups;
+    DH_CHECK(S * q_per_kv <= 32, "dh_engine_decode_spec: %d positions x %d heads per KV group exceed the 32 query columns of the verify attention",
+             S, q_per_kv);
+    DH_CHECK(n_seq * S <= MAX_DECODE_ROWS, "dh_engine_decode_spec: %d x %d rows exceed the streaming step's %d", n_seq, S, MAX_DECODE_ROWS);
+    DH_CHECK(n_seq * S <= e->row_cap && n_seq * S <= e->max_tokens,
+             "dh_engine_decode_spec: %d rows, the workspaces hold %d (dh_engine_reserve_rows) of max_tokens = %d", n_seq * S, e->row_cap, e->max_tokens);
+    DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
+    DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
+    DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
+    if (n_steps <= 0) return 0;
+    e->seq_slot = e->seq_meta;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
+    DH_LAUNCH_CHECK();
+    const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
+                              limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters};
+    return launch_steps(e, key, n_steps, s);
 }
 
 extern "C" int dh_engine_set_cpu_rsqrt_emulation(dh_engine* e, int vec_width, int whole_call) {

@@ -222,6 +222,46 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
     }
 }
 
+// The tail of a verify step (dh_engine_decode_spec): logits rows u * S + j, j = 0 .. S-1, are those of sequence u's last token and of
+// the D = S - 1 drafted tokens behind it (row_ids[u * S + j], j >= 1).  pick_j is the arg-max of row j by pick_token's lowest-index
+// rule; it is the sequence's next token as long as every draft before it was right, i.e. row_ids[u * S + i] == pick_{i-1} for
+// i = 1 .. j.  The picks are appended one by one exactly as sample_kernel appends its one: nothing behind an EOS (done = 1) or
+// behind the sequence's budget limit[u] = prompt length + max_new (done = 2), and a finished sequence is left alone.
+// counters: [0] the last step (1-based, *step_dev) at which a sequence was live, [1] drafts verified, [2] drafts appended.
+__global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
+                                                         int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
+                                                         int32_t* __restrict__ done, const int32_t* __restrict__ limit,
+                                                         float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
+                                                         int32_t* __restrict__ counters) {
+    const int u = blockIdx.x, tid = threadIdx.x;
+    if (done[u]) return;
+    int n = length[u];
+    const int lim = min(limit[u], tok_ld);
+    int appended = 0, state = 0, prev = 0;
+    for (int j = 0; j < S; ++j) {
+        if (j > 0) {
+            if (row_ids[(size_t)u * S + j] != (int64_t)prev) break;      // the same for every thread
+            __syncthreads();                                             // pick_token's shared scratch is free again
+        }
+        const int choice = pick_token(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u);
+        prev = choice;
+        if (n < lim) {
+            if (tid == 0) tokens[(size_t)u * tok_ld + n] = choice;
+            ++n;
+            ++appended;
+        }
+        if (eos_id >= 0 && choice == eos_id) { state = 1; break; }
+        if (n >= lim) { state = 2; break; }                               // budget spent
+    }
+    if (tid == 0) {
+        length[u] = n;
+        if (state) done[u] = state;
+        atomicMax(&counters[0], *step_dev);
+        atomicAdd(&counters[1], S - 1);
+        atomicAdd(&counters[2], appended > 1 ? appended - 1 : 0);
+    }
+}
+
 }  // namespace
 
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
@@ -263,4 +303,17 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
                                    int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
                                temperature, top_k, eos_id, seed, stream);
+}
+
+int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
+                        int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
+                        const int32_t* step_dev, int32_t* counters, void* stream) {
+    DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
+    DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
+    DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
+    if (n_seq == 0) return 0;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(n_seq), dim3(NT), 0, (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld,
+                       length, done, limit, temperature, eos_id, step_dev, counters);
+    DH_LAUNCH_CHECK();
+    return 0;
 }

@@ -15,6 +15,7 @@ import torch
 from . import ops
 from .gpt import GPT
 from .schedule import shared_prefix_len
+from .speculate import check_arguments as _check_speculate
 
 
 EOS_CHECK_EVERY = 16     # decode steps between two "has every sequence finished" read-backs (generate_batch with an eos_id)
@@ -54,7 +55,7 @@ def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: S
 def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
-                   share_prefix: Union[bool, str] = False):
+                   share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -67,9 +68,18 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
 
     share_prefix (True, or "auto": only where it changes no bit): the P leading tokens every prompt of the call opens with
     (whole 32-token tiles, each prompt keeping a token of its own) go through the layers once, their K / V are copied into
-    every slot (dh_engine_copy_prefix), and the prefill forwards each prompt's tokens [P:] at position P.  Same ids."""
+    every slot (dh_engine_copy_prefix), and the prefill forwards each prompt's tokens [P:] at position P.  Same ids.
+
+    speculate=D (1..7, top_k=1 only): a decode step verifies D drafted tokens per sequence next to its last one and appends those
+    the arg-max confirms plus one (dh_engine_decode_spec) — the same ids as speculate=0, bit for bit, in fewer steps where the
+    drafts are right.  drafts None: drafted by prompt lookup (speculate.propose); a [B, max_new_tokens] int64 tensor: drafts[u, i]
+    is proposed as the i-th generated token of sequence u (a scripted proposer for tests and tools/bench_speculate.py).
+    timing gains spec_steps (verify steps until the last sequence finished), spec_drafted and spec_accepted."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
+    D = _check_speculate(model, speculate, top_k, B)
+    if drafts is not None and (D == 0 or drafts.dtype != torch.int64 or tuple(drafts.shape) != (B, max_new_tokens)):
+        raise ValueError(f"drafts goes with speculate > 0 and is a [{B}, {max_new_tokens}] int64 tensor")
     lens = [int(p.numel()) for p in prompts]
     T_max = max(lens)
     need_pos = T_max + max_new_tokens - 1
@@ -78,7 +88,13 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     dev = model.transformer.wte.weight.device
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
     P = _shared_prefix(model, prompts, share_prefix, dev)
-    eng = model.engine(B, need_pos, max(P, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)), exact=B > prefill_batch)
+    # a verify step writes K / V up to D positions behind the last token (as far as the model has positions) and runs D + 1 rows per
+    # sequence through the row workspaces; the cache keeps B slots
+    spec_pos = min(need_pos + D, -(-model.config.block_size // 64) * 64)
+    eng = model.engine(B, spec_pos, max(P, B * (D + 1) if D else 0, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)),
+                       exact=B > prefill_batch)
+    if D:
+        eng.reserve_rows(B * (D + 1))
     tok_ld = T_max + max_new_tokens
     if min(lens) == T_max:             # equal lengths: one copy
         tokens = torch.nn.functional.pad(torch.stack([p.to(dev) for p in prompts]), (0, tok_ld - T_max))
@@ -86,8 +102,14 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         tokens = torch.nn.utils.rnn.pad_sequence([p.to(dev) for p in prompts], batch_first=True)
         tokens = torch.nn.functional.pad(tokens, (0, tok_ld - tokens.size(1)))
     tokens = tokens.contiguous()
-    length = torch.tensor(lens, dtype=torch.int32, device=dev)
-    done = torch.zeros(B, dtype=torch.int32, device=dev)
+    if D:   # lengths, flags and the three counters side by side: one read-back
+        state = torch.cat([torch.tensor(lens, dtype=torch.int32), torch.zeros(B + 3, dtype=torch.int32)]).to(dev)
+        length, done, counters = state[:B], state[B:2 * B], state[2 * B:]
+        limit = torch.tensor([n + max_new_tokens for n in lens], dtype=torch.int32, device=dev)
+        drafts = None if drafts is None else drafts.to(dev).contiguous()
+    else:
+        length = torch.tensor(lens, dtype=torch.int32, device=dev)
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -107,7 +129,17 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     steps_run = 0
     if max_new_tokens > 1:
         n = max_new_tokens - 1
-        if eos_id is None:
+        if D:
+            # a step yields 1 .. D + 1 tokens per live sequence, so at most n steps are needed; EOS_CHECK_EVERY at a time, until
+            # every sequence has met its EOS or its budget (done != 0)
+            while steps_run < n:
+                c = min(EOS_CHECK_EVERY, n - steps_run)
+                eng.decode_spec(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature, eos_id,
+                                first_step=steps_run)
+                steps_run += c
+                if steps_run < n and bool((done != 0).all()):
+                    break
+        elif eos_id is None:
             eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
             steps_run = n
         else:
@@ -123,8 +155,12 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
-    length_h = length.tolist()          # the one host read-back
-    done_h = done.tolist()
+    if D:
+        state_h = state.tolist()        # the one host read-back
+        length_h, done_h, counters_h = state_h[:B], state_h[B:2 * B], state_h[2 * B:]
+    else:
+        length_h = length.tolist()          # the one host read-back
+        done_h = done.tolist()
     if ev:   # the read-back above has synchronised the stream
         timing["prefill_ms"] = timing.get("prefill_ms", 0.0) + ev[0].elapsed_time(ev[1])
         timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
@@ -132,6 +168,9 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + B * steps_run
         timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens) - (B - 1) * P
         timing["shared_prefix"] = P
+    if D and timing is not None:
+        for key, v in zip(("spec_steps", "spec_drafted", "spec_accepted"), counters_h):
+            timing[key] = timing.get(key, 0) + v
     out: List[torch.Tensor] = []
     for i in range(B):
         n = min(length_h[i], lens[i] + max_new_tokens)
@@ -139,7 +178,10 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
         out.append(tokens[i, :n])       # a view of this call's own buffer (640 clone launches per 20-batch group otherwise)
     if return_state:
-        return out, dict(tokens=tokens, length=length, done=done)
+        st = dict(tokens=tokens, length=length, done=done)
+        if D and steps_run:             # the last verify step's drafts and the lengths they were proposed from
+            st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
+        return out, st
     return out
 
 
@@ -205,7 +247,7 @@ class _StreamBackend:
 def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
-                    share_prefix: Union[bool, str] = False):
+                    share_prefix: Union[bool, str] = False, speculate: int = 0):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -220,6 +262,9 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     hands out before the first prefill; no sequence of the call writes below position P, so they outlive every refill, and a
     refill is a prefill of the tokens [P:] at position P.  The scheduler's decisions are those of the unshared call."""
     from .schedule import StreamScheduler
+    if speculate:
+        raise ValueError(f"speculate={speculate}: continuous batching steps a row list one token at a time; speculative decoding runs "
+                         "under generate_batch (--schedule batch) only")
     N = len(prompts)
     assert N > 0 and max_new_tokens > 0
     lens = [int(p.numel()) for p in prompts]
@@ -263,10 +308,11 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
-             top_k: Optional[int] = None, eos_id: Optional[int] = None) -> torch.Tensor:
-    """Drop-in for generate/base.py:generate (one prompt of shape (T,))."""
+             top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0) -> torch.Tensor:
+    """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch."""
     T = idx.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
-    return generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id)[0]
+    return generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
+                          speculate=speculate)[0]

@@ -429,6 +429,39 @@ class _Engine:
                 0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1),
                 torch.cuda.current_stream().cuda_stream))
 
+    def reserve_rows(self, rows: int) -> None:
+        """Size the single-token-step workspaces for `rows` rows (dh_engine_reserve_rows): a verify step has (D + 1) rows per sequence."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_reserve_rows(self.handle, int(rows)))
+
+    def decode_spec(self, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor, max_new_tokens: int,
+                    n_draft: int, drafts: Optional[torch.Tensor], counters: torch.Tensor, n_steps: int, temperature: float,
+                    eos_id: Optional[int], first_step: int = 0) -> None:
+        """n_steps verify steps of n_draft drafts per sequence (dh_engine_decode_spec); drafts None: the prompt-lookup proposer."""
+        B = tokens.size(0)
+        assert length.numel() == done.numel() == limit.numel() == B and counters.numel() >= 3 and counters.dtype == torch.int32
+        assert drafts is None or (drafts.dtype == torch.int64 and drafts.is_contiguous() and tuple(drafts.shape) == (B, int(max_new_tokens)))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_decode_spec(
+                self.handle, tokens.data_ptr(), tokens.size(1), length.data_ptr(), done.data_ptr(), limit.data_ptr(), B,
+                int(max_new_tokens), int(n_draft), None if drafts is None else drafts.data_ptr(), counters.data_ptr(), int(n_steps),
+                float(temperature), -1 if eos_id is None else int(eos_id), int(first_step), torch.cuda.current_stream().cuda_stream))
+
+    def graph_count(self, n_draft: int = -1) -> int:
+        """Captured decode steps kept for n_draft drafts (0: the plain steps, -1: all)."""
+        return int(self.lib.dh_engine_graph_count(self.handle, int(n_draft)))
+
+    def read_spec(self, n_seq: int, n_draft: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(drafts [n_seq, n_draft], length [n_seq]) of the last verify step: what its proposer drafted and from how many tokens."""
+        S = n_draft + 1
+        ids = torch.empty((n_seq, S), dtype=torch.int64, device=self.device)
+        kv = torch.empty(n_seq, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(self.lib.dh_engine_read(self.handle, 4, 0, ids.data_ptr(), ids.numel() * 8, st))
+            _lib.check(self.lib.dh_engine_read(self.handle, 5, 0, kv.data_ptr(), kv.numel() * 4, st))
+        return ids[:, 1:].contiguous(), kv
+
     def set_rsqrt_emulation(self, vec_width: int, whole_call: bool) -> None:
         _lib.check(self.lib.dh_engine_set_cpu_rsqrt_emulation(self.handle, int(vec_width), int(whole_call)))
 

@@ -208,16 +208,17 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
 
     continuous = getattr(args, "schedule", "batch") == "continuous"
     share = "auto" if getattr(args, "share_prefix", "off") == "auto" else False
+    spec = int(getattr(args, "speculate", 0) or 0)
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
-                                   share_prefix=share)
+                                   share_prefix=share, speculate=spec)
             return [o.cpu() for o in outs]
         outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
-                              prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share)
+                              prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec)
         return [o.cpu() for o in outs]
 
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world,
@@ -279,6 +280,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
                    help="auto: the tokens every prompt of a call opens with (the template's instruction and header, the chat preamble; "
                         "whole 32-token tiles) are prefilled once and their KV cache is copied to the other utterances, which forward "
                         "the rest of their prompts only; the predictions do not depend on it")
+    p.add_argument("--speculate", type=int, default=0, metavar="D",
+                   help="D in 1..7: a decode step verifies D tokens drafted by prompt lookup (the correction mostly copies spans of its "
+                        "prompt) next to each sequence's last one and keeps those the greedy arg-max confirms; --schedule batch only; "
+                        "the predictions do not depend on it.  Default 0: off (acceptance on real corpora is unmeasured)")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)
@@ -289,6 +294,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
     p.add_argument("--pool_size", type=int, default=10)
     p.add_argument("--enc_features_dir", type=str, default=None)
     args = p.parse_args(argv)
+    if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet
+        p.error(f"--speculate {args.speculate} goes with --schedule batch: continuous batching steps a row list one token at a time")
+    if not 0 <= args.speculate <= 7:
+        p.error(f"--speculate {args.speculate}: D is 0 (off) or 1..7")
     rank, world, dev = init_distributed(args.d)
     random.seed(args.seed)
     torch.manual_seed(args.seed)

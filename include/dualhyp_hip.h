@@ -503,11 +503,43 @@ int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* le
                           const int32_t* row_slot, int n_rows, int n_steps, float temperature, int top_k,
                           int64_t eos_id, uint64_t seed, void* stream);
 
+/* Speculative greedy decoding: the loop of generate/base.py:57-80 with top_k = 1, n_draft + 1 positions of every
+ * sequence per step.  A step feeds each sequence's last token and n_draft drafted tokens behind it (S = n_draft + 1
+ * rows per sequence through the single-token-step kernels, one attention launch per layer over the S positions),
+ * takes the arg-max of every row and appends pick_0 .. pick_a, a = the number of leading drafts j with
+ * draft_j == pick_{j-1}: the ids are those of dh_engine_decode with top_k = 1, bit for bit, whatever the drafts
+ * (a row's bits do not depend on the rows beside it, rejected positions of the cache are overwritten before
+ * causality lets anything read them).
+ * tokens / length / done as in dh_engine_decode; limit[i] = prompt length + max_new_tokens is sequence i's budget
+ * (done = 2 when reached, as in dh_sample_rows_bf16; nothing is written at or behind it).
+ * drafts (device, [n_seq, max_new_tokens], may be null): drafts[i, k] is proposed as the k-th generated token of
+ * sequence i.  Null: prompt lookup on tokens[i, :length[i]] — the tokens behind the latest earlier occurrence of
+ * the last 3, 2 or 1 tokens (dualhyp_amd/speculate.py:propose is the specification).
+ * counters (device int32[3], zeroed by the caller): [0] steps until the last sequence finished (counted from
+ * first_step), [1] drafts verified, [2] drafts appended.
+ * Needs n_draft in 1..7, (n_draft + 1) * n_head / n_groups <= 32, n_seq * (n_draft + 1) <= 2048 rows reserved with
+ * dh_engine_reserve_rows, a bf16 engine without the CPU rsqrt emulation, and positions up to length + n_draft - 1
+ * in the cache (rows behind its end are computed and dropped). */
+int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                          const int32_t* limit, int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts,
+                          int32_t* counters, int n_steps, float temperature, int64_t eos_id, int first_step,
+                          void* stream);
+/* Size the per-row workspaces of the single-token steps (logits, fp32 partial sums, ids) for `rows` rows
+ * (<= 2048 and <= max_tokens) where dh_engine_create sized them for max_batch: a verify step has
+ * n_seq * (n_draft + 1) rows and the KV cache stays at max_batch slots.  Growing drops the captured steps.
+ * If the larger workspaces cannot be allocated the call fails and the engine keeps the ones it had. */
+int dh_engine_reserve_rows(dh_engine* e, int rows);
+/* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
+ * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
+int dh_engine_graph_count(const dh_engine* e, int n_draft);
+
 /* Test hook: copy engine state to `dst` (device memory, n_bytes) on `stream`.
  *   what 0: ln_f(x) of the last dh_engine_forward called with logits_all only, [n_tok, d]
  *   what 1: K   cache of `layer`  [max_batch, g, s_max, hs]
  *   what 2: V^T cache of `layer`  [max_batch, g, hs, s_max]
- *   what 3: residual stream x after the last layer of the last forward, [n_tok, d] */
+ *   what 3: residual stream x after the last layer of the last forward, [n_tok, d]
+ *   what 4: int64 ids of the last step's rows (a verify step: row i * S + j = last token, then the drafts)
+ *   what 5: int32 kv_len of the last step's sequences (a verify step: the lengths its drafts were proposed from) */
 int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int64_t n_bytes, void* stream);
 /* HIP-event timing of the dominant kernels inside the last forward/decode call (bench.py
  * roofline): returns accumulated milliseconds and launch count for kernel class `which`
