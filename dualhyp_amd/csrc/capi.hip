@@ -74,6 +74,9 @@ const TuningRow TUNING[] = {
     {29, &g_attn_bwd_dkdv_img, BOOL, 0, 0, 0},
     {30, &g_w4_persist_lora, BOOL, 0, 0, 0},
     {31, &g_skinny_n, BOOL, 0, 0, 0},
+    // 32 stays unassigned: it is the key tests/test_capi.py uses as the unknown one
+    {40, &g_attn_chain, BOOL, 0, 0, 0},
+    {41, &g_finish_hoist_rows, RANGE, -1, NO_MAX, 0},   // -1: the built-in crossover
 };
 
 }  // namespace

@@ -8,6 +8,26 @@
 // latency from the chain, lets small matrices be split over K across blocks, and folds
 // rope + KV-cache append + split-KV attention + combine into one kernel.
 #include "common.h"
+#include "tuning.h"
+
+// dh_set_tuning 40: the single-token attention kernel.  1 (default): attn_decode_chain_kernel where it applies (hs 64 and one
+// finish item per thread); 0: attn_decode_fused_kernel everywhere (the A/B arm; both give the same bits).
+int g_attn_chain = 1;
+// dh_set_tuning 41: finish_norm requests its independent loads ahead of the hand-over barrier from this many rows on
+// (0: never).  Chosen by the row count only.  Default and the sweep behind it: FINISH_HOIST_ROWS below.
+int g_finish_hoist_rows = -1;
+
+#ifdef DH_ATTN_STAMPS   // diagnostic build only (tools/probe_attn_chain.py): 100 MHz timestamps of thread 0 of each block
+__device__ unsigned long long g_attn_stamps[4096 * 8];
+#define ATTN_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_attn_stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define ATTN_DRAIN() __builtin_amdgcn_s_waitcnt(0)      // every store of this wave acknowledged
+extern "C" int dh_debug_attn_stamps(unsigned long long* out) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_stamps), sizeof(g_attn_stamps)) == hipSuccess ? 0 : 1;
+}
+#else
+#define ATTN_STAMP(i)
+#define ATTN_DRAIN()
+#endif
 
 namespace {
 
@@ -15,13 +35,14 @@ constexpr int DCOLS = 16;   // padded head columns of the attention partials
 constexpr int MAXP = 16;    // most K-slices a partial-sum GEMM emits
 
 // --------------------------------------------------------------------------- attention (decode)
-// grid (n_seq * n_groups), NW waves (hs 64: 16, hs 96 and 128: 8; hs 96 needs 53 KiB of LDS, two blocks per CU).  qkv32: [n_part][n_seq][ldq] fp32, ldq = qkv_dim + n_ext;
-// columns [qkv_dim, qkv_dim+48) hold x·A^T of the q/k/v LoRA (when lora_b != null).
-// NW waves share the key tiles of one (sequence, group).  Round 3: SIXTEEN waves at hs 64 — at the benchmark's ~544 cached keys
-// (17 tiles) every tile is then requested before the LoRA / rope prologue and no wave walks a second or third tile behind an
-// exposed HBM round trip (with 8 waves the loop issued a tile's loads only after computing the previous one; the 640-row step
-// spent 85 us per layer here, 4.5 TB/s).  The tile -> wave deal and the combine order are a property of the head size, never
-// of the row count, so batch invariance is untouched; hs 128 keeps 8 waves (its tile and accumulators need 256 VGPRs).
+// grid (n_seq * n_groups), NW waves (8 at every head size: DH_ATTN_WAVES64 below; hs 96 needs 53 KiB of LDS, two blocks per CU).
+// qkv32: [n_part][n_seq][ldq] fp32, ldq = qkv_dim + n_ext; columns [qkv_dim, qkv_dim+48) hold x·A^T of the q/k/v LoRA (when
+// lora_b != null).  NW waves share the key tiles of one (sequence, group): at the benchmark's ~544 cached keys (17 tiles) a
+// wave walks two tiles and wave 0 three, each after the first behind an exposed HBM round trip.  Sixteen waves at hs 64 (every
+// tile requested before the LoRA / rope prologue, one block per CU) and six with two tiles in flight were built in round 3,
+// measured slower per 640-row step and are A/B builds only (-DDH_ATTN_WAVES64=16 | 6).  The tile -> wave deal and the combine
+// order are a property of the head size, never of the row count, so batch invariance is untouched.  At hs 64 this kernel is the
+// A/B arm of attn_decode_chain_kernel below (dh_set_tuning 40) and serves the shapes that kernel does not take.
 template <int HS, int PMAX, int NW>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 4 : 2))) void attn_decode_fused_kernel(
     const float* __restrict__ qkv32, int n_part, int pairs, int n_seq, int ldq, int qkv_dim,
@@ -47,6 +68,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 
     float* sPl = sPm + NW * DCOLS;                                      // [NW][DCOLS] running sum
     float* sPo = sPl + NW * DCOLS;                                      // [NW][HS][DCOLS] partial O^T
     constexpr int NT_ = NW * 64;                                        // threads
+    ATTN_STAMP(0);
 
     // ---- request the K / V^T operands of this wave's first PF tiles before anything else: they do
     // not depend on the new token, and their HBM latency hides under the LoRA/rope phase
@@ -98,6 +120,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 
     if (lora_b != nullptr && tid < 48) sXa[tid] = rbf(psum(qkv_dim + tid));
     for (int i = tid; i < 16 * HS; i += NT_) sQ[i] = 0;               // zero padding rows of Q
     __syncthreads();
+    ATTN_STAMP(1);
 
     // bf16 value of fused-qkv column c: bf16(bf16(x·W^T) + bf16(bf16(xa·B^T)*s))
     auto finish = [&](int c) -> float {
@@ -146,6 +169,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 
         }
     }
     __syncthreads();
+    ATTN_STAMP(2);
 
     // score of the new key against each head (it is merged at the combine, so nobody has to
     // read this block's own cache write back)
@@ -221,7 +245,14 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 
             if (base + NW * p < n_tiles) compute_tile(tl[p], base + NW * p);
             if (base + NW * (PF + p) < n_tiles) load_tile(tl[p], base + NW * (PF + p));    // its set is free again
         }
+#ifdef DH_ATTN_STAMPS
+        if (base == wave) { asm volatile("" :: "v"(o[0][0])); ATTN_STAMP(3); }
+#endif
     }
+#ifdef DH_ATTN_STAMPS
+    asm volatile("" :: "v"(o[0][0]));
+#endif
+    ATTN_STAMP(4);
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (lr < q_per_kv) {
         if (lh == 0) {
@@ -237,6 +268,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 
             }
     }
     __syncthreads();
+    ATTN_STAMP(5);
     // ---- combine the NW wave partials and the new key
     for (int it = tid; it < q_per_kv * HS; it += NT_) {
         const int h = it / HS, d = it % HS;
@@ -255,6 +287,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 1 : (NW == 6 ? 3 : (HS == 64 ? 
         }
         y[(size_t)seq * n_head * HS + (g * q_per_kv + h) * HS + d] = f2bf(O / L);
     }
+    ATTN_STAMP(6);
+    ATTN_DRAIN();
+    ATTN_STAMP(7);
 }
 
 // Round 3, one more shape measured and not kept (bit-identical, 82 tests green): every tile after a wave's first streamed through an 8-KiB LDS slot
@@ -270,6 +305,281 @@ template <int HS>
 constexpr size_t attn_fused_lds() {
     constexpr int NW = attn_fused_waves<HS>();
     return 16 * HS * 2 + (HS + HS + 48 + 16 + NW * DCOLS + NW * DCOLS + NW * HS * DCOLS) * sizeof(float);
+}
+
+constexpr int CHAIN_NW = 8;      // attn_decode_chain_kernel's waves (an A/B build of the parent with 6 or 16 keeps the parent)
+template <int HS>
+constexpr size_t attn_chain_lds() {
+    return 16 * HS * 2 + (HS + HS + 48 + 16 + CHAIN_NW * DCOLS + CHAIN_NW * DCOLS + CHAIN_NW * DCOLS * (HS + 8)) * sizeof(float);
+}
+
+// --------------------------------------------------------------------------- attention (decode), short chain
+// attn_decode_fused_kernel with the head of each block's dependent chain shortened; the arithmetic, the tile -> wave deal, the
+// per-tile update and the combine are that kernel's, statement for statement, so both give the same bits.  What differs is
+// when things are asked for:
+//   - a thread owns ONE item of the LoRA finish / rope / append phase (the host checks n_rope + HS <= threads), and every load
+//     the item needs -- its fp32 partials, its rows of B, its cos / sin, and for 48 threads the x·A^T partials -- is requested
+//     before the first barrier.  The old order summed x·A^T, crossed a barrier and only then requested the items' partials:
+//     two memory round trips in sequence;
+//   - those loads are requested BEFORE the K / V^T tile.  The memory counter retires in order: behind the tile's HBM loads
+//     the first barrier also waited for the tile, and the finish phase started after it instead of under it;
+//   - Q's padding rows are zeroed in the MFMA operand registers, not in LDS.
+template <int HS, int PMAX, int NW>
+__global__ __launch_bounds__(NW * 64, HS == 64 ? 4 : 2) void attn_decode_chain_kernel(
+    const float* __restrict__ qkv32, int n_part, int pairs, int n_seq, int ldq, int qkv_dim,
+    const bf16_t* __restrict__ lora_b, float lora_scale, int split0, int split1,
+    const bf16_t* __restrict__ cos, const bf16_t* __restrict__ sin, const int32_t* __restrict__ seq_slot,
+    const int32_t* __restrict__ kv_len, bf16_t* __restrict__ k_cache, bf16_t* __restrict__ vT_cache,
+    bf16_t* __restrict__ y, int n_head, int n_groups, int s_max, float scale) {
+    static_assert(NW == CHAIN_NW, "one tile in flight per wave and the occupancy asked for above are those of the 8-wave form");
+    constexpr int KS = HS / 16, DT = HS / 32, HALF = HS / 2;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int pair = blockIdx.x, seq = pair / n_groups, g = pair % n_groups;
+    const int q_per_kv = n_head / n_groups;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 31, lh = lane >> 5;
+    // LDS carve: attn_decode_fused_kernel's
+    bf16_t* sQ = reinterpret_cast<bf16_t*>(smem);                       // [16][HS] rotated queries (rows >= q_per_kv unused)
+    float* sKn = reinterpret_cast<float*>(smem + 16 * HS * 2);          // [HS] new key (bf16 values)
+    float* sVn = sKn + HS;                                              // [HS] new value
+    float* sXa = sVn + HS;                                              // [48] bf16(x·A^T)
+    float* sSn = sXa + 48;                                              // [16] score of the new key
+    float* sPm = sSn + 16;                                              // [NW][DCOLS] running max
+    float* sPl = sPm + NW * DCOLS;                                      // [NW][DCOLS] running sum
+    float* sPo = sPl + NW * DCOLS;                                      // [NW][DCOLS][PST] partial O, head-major (see the combine)
+    constexpr int PST = HS + 8;                                         // row stride: 8 lr x 2 lh writers of one d land in 16 banks
+    constexpr int NT_ = NW * 64;
+    ATTN_STAMP(0);
+
+    const int slot = seq_slot[seq];
+    const int len = kv_len[seq], pos = len - 1;          // the new token sits at position len-1
+
+    // ---- this thread's finish item and every load it needs.  No load sits under a per-lane condition (a thread without an
+    // item asks for a column that exists and drops it): a conditional load is waited for where the branches join.
+    const float* row0 = qkv32 + (size_t)seq * ldq;
+    const size_t pstride = (size_t)n_seq * ldq;
+    auto pload = [&](int c, float (&v)[PMAX]) {
+#pragma unroll
+        for (int p = 0; p < PMAX; ++p) v[p] = p < n_part ? row0[p * pstride + c] : 0.f;
+    };
+    // the decode family's summation order (common.h, "K-slice combine"), as in attn_decode_fused_kernel
+    auto padd = [&](const float (&v)[PMAX]) {
+        float s = 0.f;
+        if (pairs) {
+#pragma unroll
+            for (int p = 0; p < PMAX; p += 2) s += v[p] + v[p + 1];
+        } else {
+#pragma unroll
+            for (int p = 0; p < PMAX; ++p) s += v[p];
+        }
+        return s;
+    };
+    const int gbase = g * (q_per_kv + 2) * HS;
+    const int n_rope = (q_per_kv + 1) * HALF;
+    const bool is_rope = tid < n_rope, is_val = !is_rope && tid < n_rope + HS;
+    const int rj = tid / HALF, ri = tid % HALF, ve = tid - n_rope;
+    const int c1 = is_rope ? gbase + rj * HS + ri : (is_val ? gbase + (q_per_kv + 1) * HS + ve : gbase);
+    const int c2 = is_rope ? c1 + HALF : gbase;
+    const bool has_xa = lora_b != nullptr && tid < 48;
+    float vx[PMAX], v1[PMAX], v2[PMAX];
+    uint4 b1[2], b2[2];
+    pload(has_xa ? qkv_dim + tid : 0, vx);
+    pload(c1, v1);
+    pload(c2, v2);
+    if (lora_b != nullptr) {
+        const uint4* b4 = reinterpret_cast<const uint4*>(lora_b + (size_t)c1 * 16);
+        b1[0] = b4[0]; b1[1] = b4[1];
+        b4 = reinterpret_cast<const uint4*>(lora_b + (size_t)c2 * 16);
+        b2[0] = b4[0]; b2[1] = b4[1];
+    } else {
+        b1[0] = b1[1] = b2[0] = b2[1] = uint4{0, 0, 0, 0};
+    }
+    const bf16_t* cp = cos + (size_t)pos * HS;
+    const bf16_t* sp = sin + (size_t)pos * HS;
+    const bf16_t cs[4] = {cp[ri], sp[ri], cp[HALF + ri], sp[HALF + ri]};
+
+    // ---- then the K / V^T operands of this wave's first tile (HBM; they land under the finish phase)
+    struct VF { bf16x8 v; };
+    struct Tile { bf16x8 kf[KS]; VF vf[DT][2]; };
+    Tile tl;
+    const bf16_t* kbase = k_cache + ((size_t)slot * n_groups + g) * s_max * HS;
+    const bf16_t* vbase = vT_cache + ((size_t)slot * n_groups + g) * HS * s_max;
+    const int n_tiles = (pos + 31) / 32;
+    auto load_tile = [&](Tile& T, int t) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            T.kf[ks] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kbase + kfrag_blk<HS>(t, ks) + lane * 8));
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+                T.vf[dt][s2].v = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vbase + vfrag_blk<HS>(t, dt, s2) + lane * 8));
+    };
+    // unconditional, like the loads above: a wave without a tile asks for the last one there is (tile 0 of the slot's cache
+    // when there is none: allocated, finite or not, never used)
+    load_tile(tl, wave < n_tiles ? wave : (n_tiles > 0 ? n_tiles - 1 : 0));
+
+    if (has_xa) sXa[tid] = rbf(padd(vx));
+    __syncthreads();
+    ATTN_STAMP(1);
+
+    // bf16 value of a fused-qkv column c from its summed partials and its rows of B:
+    // bf16(bf16(x·W^T) + bf16(bf16(xa·B^T)*s))
+    auto finish = [&](const float (&v)[PMAX], int c, const uint4 (&b)[2]) -> float {
+        float o = rbf(padd(v));
+        if (lora_b != nullptr) {
+            const int seg = (c >= split0) + (c >= split1);
+            float l = 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint4 bv = b[h];
+                const bf16_t* bp = reinterpret_cast<const bf16_t*>(&bv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) l = fmaf(sXa[seg * 16 + h * 8 + e], bf2f(bp[e]), l);
+            }
+            o = rbf(o + rbf(rbf(l) * lora_scale));
+        }
+        return o;
+    };
+    bf16_t* kdst = k_cache + ((size_t)slot * n_groups + g) * s_max * HS;
+    bf16_t* vdst = vT_cache + ((size_t)slot * n_groups + g) * HS * s_max;
+    if (is_rope) {
+        const int j = rj, i = ri;
+        const float x1 = finish(v1, c1, b1), x2 = finish(v2, c2, b2);
+        const bf16_t o1 = f2bf(rbf(x1 * bf2f(cs[0])) + rbf(-x2 * bf2f(cs[1])));
+        const bf16_t o2 = f2bf(rbf(x2 * bf2f(cs[2])) + rbf(x1 * bf2f(cs[3])));
+        if (j < q_per_kv) {
+            sQ[j * HS + i] = o1;
+            sQ[j * HS + HALF + i] = o2;
+        } else {
+            sKn[i] = bf2f(o1);
+            sKn[HALF + i] = bf2f(o2);
+            kdst[kfrag_off<HS>(pos, i)] = o1;
+            kdst[kfrag_off<HS>(pos, HALF + i)] = o2;
+        }
+    } else if (is_val) {
+        const bf16_t v = f2bf(finish(v1, c1, b1));
+        sVn[ve] = bf2f(v);
+        vdst[vfrag_off<HS>(pos, ve)] = v;
+    }
+    __syncthreads();
+    ATTN_STAMP(2);
+
+    // score of the new key against each head (merged at the combine)
+    for (int h = wave; h < q_per_kv; h += NW) {
+        float p = 0.f;
+        for (int e = lane; e < HS; e += 64) p += bf2f(sQ[h * HS + e]) * sKn[e];
+        p = wave_sum(p);
+        if (lane == 0) sSn[h] = p * scale;
+    }
+
+    // ---- keys 0 .. pos-1 straight from the cache, 32-key tiles dealt over the NW waves
+    bf16x8 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(sQ + (lr & 15) * HS + ks * 16 + lh * 8);
+    if (lr >= q_per_kv) {                                               // padding columns: sQ's rows there were never written
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+    auto compute_tile = [&](const Tile& T, int t) {
+        const int key0 = t * 32;
+        f32x16 st;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.kf[ks], qf[ks], st, 0, 0, 0);
+        float m_t = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key_abs = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            float sc = st[r] * scale;
+            sc = key_abs < pos ? sc : -INFINITY;
+            st[r] = sc;
+            m_t = fmaxf(m_t, sc);
+        }
+        m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
+        const float m_new = fmaxf(m_run, m_t);
+        const float alpha = __expf(m_run - m_new);
+        m_run = m_new;
+        float psm = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = __expf(st[r] - m_new);
+            st[r] = p;
+            psm += p;
+        }
+        l_run = l_run * alpha + psm;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            union { bf16x8 v; uint32_t u[4]; } pf;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pf.u[j] = pack2bf(st[8 * s2 + 2 * j], st[8 * s2 + 2 * j + 1]);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                if (s2 == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+                }
+                // keys >= pos carry p == 0 and the cache beyond the written prefix is finite
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.vf[dt][s2].v, pf.v, o[dt], 0, 0, 0);
+            }
+        }
+    };
+    for (int base = wave; base < n_tiles; base += NW) {
+        compute_tile(tl, base);
+        if (base + NW < n_tiles) load_tile(tl, base + NW);
+#ifdef DH_ATTN_STAMPS
+        if (base == wave) { asm volatile("" :: "v"(o[0][0])); ATTN_STAMP(3); }
+#endif
+    }
+#ifdef DH_ATTN_STAMPS
+    asm volatile("" :: "v"(o[0][0]));
+#endif
+    ATTN_STAMP(4);
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (lr < q_per_kv) {
+        if (lh == 0) {
+            sPm[wave * DCOLS + lr] = m_run;
+            sPl[wave * DCOLS + lr] = l_tot;
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                sPo[(wave * DCOLS + lr) * PST + d] = o[dt][r];
+            }
+    }
+    __syncthreads();
+    ATTN_STAMP(5);
+    // ---- combine the NW wave partials and the new key.  A wave's lanes walk d of one head: with O head-major they read 64
+    // consecutive floats (the d-major layout of attn_decode_fused_kernel puts them 16 floats apart, 4 banks for 64 lanes)
+    for (int it = tid; it < q_per_kv * HS; it += NT_) {
+        const int h = it / HS, d = it % HS;
+        const float sn = sSn[h];
+        float M = sn;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, sPm[w * DCOLS + h]);
+        const float pn = __expf(sn - M);
+        float L = pn, O = rbf(pn) * sVn[d];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = sPm[w * DCOLS + h];
+            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            L += sPl[w * DCOLS + h] * f;
+            O += sPo[(w * DCOLS + h) * PST + d] * f;
+        }
+        y[(size_t)seq * n_head * HS + (g * q_per_kv + h) * HS + d] = f2bf(O / L);
+    }
+    ATTN_STAMP(6);
+    ATTN_DRAIN();
+    ATTN_STAMP(7);
 }
 
 // --------------------------------------------------------------------------- attention (verify)
@@ -524,7 +834,10 @@ size_t attn_verify_lds(int S, int ncol) {
 //   h  = bf16( bf16(sum_p h32) + bf16( bf16(xa·B^T) * s ) )      (LoRA finish, ger/lora.py:159-166)
 //   x' = bf16( x + h )                                           (residual, ger/model.py:185-186)
 //   xn = RMSNorm(x') with weight w_norm                          (ger/rmsnorm.py:17-21, Q11 flag)
-template <int MAXC>
+// HOIST: a thread's first column chunk requests the first four partials, the residual and the norm weight ahead of the
+// barrier that hands x·A^T over.  Its 8 x 32 B of B stay behind the barrier: hoisted too they cost 64 more VGPRs (214), two
+// blocks per CU instead of eight, and 640 rows no longer fit in one round (measured slower at every row count).  Same arithmetic in the same order; chosen by the row count (FINISH_HOIST_ROWS).
+template <int MAXC, bool HOIST>
 __global__ __launch_bounds__(256) void finish_norm_kernel(const float* __restrict__ h32, int n_part, int pairs, int rows, int ldh,
                                                           const bf16_t* __restrict__ lora_b, float lora_scale,
                                                           const bf16_t* __restrict__ x_resid,
@@ -550,6 +863,19 @@ __global__ __launch_bounds__(256) void finish_norm_kernel(const float* __restric
         }
         sXa[tid] = rbf(s);
     }
+    float4 ha0[4] = {}, ha1[4] = {};
+    uint4 hxr = {}, hwu = {};
+    if (HOIST && tid * 8 < d) {
+        const int c0 = tid * 8;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int p = q < n_part ? q : 0;
+            ha0[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0);
+            ha1[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0 + 4);
+        }
+        hxr = *reinterpret_cast<const uint4*>(x_resid + (size_t)row * d + c0);
+        hwu = *reinterpret_cast<const uint4*>(w_norm + c0);
+    }
     __syncthreads();
     float v[MAXC][8];
     float ss = 0.f;
@@ -565,6 +891,10 @@ __global__ __launch_bounds__(256) void finish_norm_kernel(const float* __restric
                 float4 a0[4], a1[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
+                    if (HOIST && i == 0 && p0 == 0) {
+                        a0[q] = ha0[q]; a1[q] = ha1[q];
+                        continue;
+                    }
                     const int p = p0 + q < n_part ? p0 + q : p0;
                     a0[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0);
                     a1[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0 + 4);
@@ -589,7 +919,7 @@ __global__ __launch_bounds__(256) void finish_norm_kernel(const float* __restric
                 }
                 }
             }
-            const uint4 xr = *reinterpret_cast<const uint4*>(x_resid + (size_t)row * d + c0);
+            const uint4 xr = HOIST && i == 0 ? hxr : *reinterpret_cast<const uint4*>(x_resid + (size_t)row * d + c0);
             const bf16_t* xp = reinterpret_cast<const bf16_t*>(&xr);
             uint4 xo;
             bf16_t* xop = reinterpret_cast<bf16_t*>(&xo);
@@ -627,7 +957,7 @@ __global__ __launch_bounds__(256) void finish_norm_kernel(const float* __restric
     for (int i = 0; i < MAXC; ++i) {
         const int c0 = (tid + i * 256) * 8;
         if (c0 < d) {
-            const uint4 wu = *reinterpret_cast<const uint4*>(w_norm + c0);
+            const uint4 wu = HOIST && i == 0 ? hwu : *reinterpret_cast<const uint4*>(w_norm + c0);
             const bf16_t* wp = reinterpret_cast<const bf16_t*>(&wu);
             uint4 o;
             bf16_t* op = reinterpret_cast<bf16_t*>(&o);
@@ -659,11 +989,24 @@ extern "C" int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pai
     hipLaunchKernelGGL((attn_decode_fused_kernel<HSV, PM, attn_fused_waves<HSV>()>), grid, dim3(64 * attn_fused_waves<HSV>()), attn_fused_lds<HSV>(), s, qkv32, n_part, pairs, n_seq,  \
                        qkv_dim + n_ext, qkv_dim, lora_b, lora_scale, split0, split1, cos, sin, seq_slot, kv_len, k_cache,  \
                        vT_cache, y, n_head, n_groups, s_max, scale)
+#define CHAIN_LAUNCH(PM)                                                                                              \
+    hipLaunchKernelGGL((attn_decode_chain_kernel<64, PM, CHAIN_NW>), grid, dim3(64 * CHAIN_NW), attn_chain_lds<64>(), s, qkv32, n_part, pairs, n_seq,  \
+                       qkv_dim + n_ext, qkv_dim, lora_b, lora_scale, split0, split1, cos, sin, seq_slot, kv_len, k_cache,  \
+                       vT_cache, y, n_head, n_groups, s_max, scale)
     if (hs == 64) {
         DH_MAX_LDS_ONCE((attn_decode_fused_kernel<64, 2, attn_fused_waves<64>()>), attn_fused_lds<64>());
         DH_MAX_LDS_ONCE((attn_decode_fused_kernel<64, 8, attn_fused_waves<64>()>), attn_fused_lds<64>());
         DH_MAX_LDS_ONCE((attn_decode_fused_kernel<64, 16, attn_fused_waves<64>()>), attn_fused_lds<64>());
-        if (n_part <= 2) ATT_LAUNCH(64, 2);
+        // the short-chain kernel gives a thread one finish item: (q_per_kv + 1) * 32 + 64 of them
+        const bool chain = g_attn_chain != 0 && attn_fused_waves<64>() == CHAIN_NW && (n_head / n_groups + 1) * 32 + 64 <= 64 * CHAIN_NW;
+        if (chain) {
+            DH_MAX_LDS_ONCE((attn_decode_chain_kernel<64, 2, CHAIN_NW>), attn_chain_lds<64>());
+            DH_MAX_LDS_ONCE((attn_decode_chain_kernel<64, 8, CHAIN_NW>), attn_chain_lds<64>());
+            DH_MAX_LDS_ONCE((attn_decode_chain_kernel<64, 16, CHAIN_NW>), attn_chain_lds<64>());
+            if (n_part <= 2) CHAIN_LAUNCH(2);
+            else if (n_part <= 8) CHAIN_LAUNCH(8);
+            else CHAIN_LAUNCH(16);
+        } else if (n_part <= 2) ATT_LAUNCH(64, 2);
         else if (n_part <= 8) ATT_LAUNCH(64, 8);
         else ATT_LAUNCH(64, 16);
     } else if (hs == 96) {
@@ -682,6 +1025,7 @@ extern "C" int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pai
         else ATT_LAUNCH(128, 16);
     }
 #undef ATT_LAUNCH
+#undef CHAIN_LAUNCH
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -726,6 +1070,14 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
     return 0;
 }
 
+// finish_norm_kernel<, true> from this many rows on.  tools/sweep_finish.py, d 2048, us per launch, loads behind | ahead of the
+// barrier (8 partials + LoRA / 4 pair sums + LoRA / 11 partials, three alternating repeats, spread <= 0.1 us):
+//    32 rows   5.6 |  5.6    4.9 |  4.8    3.8 |  3.8        64 rows   5.9 |  5.8    5.0 |  4.9    3.9 | 3.9
+//   128 rows   7.0 |  6.7    5.2 |  5.1    5.3 |  4.9       256 rows   8.5 |  8.1    6.3 |  6.0    6.7 | 6.5
+//   640 rows  16.0 | 15.8   12.3 | 11.8   12.0 | 11.8
+// No difference beyond the spread at 32 and 64 rows; ahead in all three shapes from 128 rows on.
+constexpr int FINISH_HOIST_ROWS = 128;
+
 extern "C" int dh_finish_norm_bf16(const float* h32, int n_part, int pairs, int rows, int d, int n_ext, const dh_bf16* lora_b,
                                    float lora_scale, const dh_bf16* x_resid, const dh_bf16* w_norm, dh_bf16* x_out,
                                    dh_bf16* xn_out, float eps, const uint8_t* row_tail, void* stream) {
@@ -737,8 +1089,14 @@ extern "C" int dh_finish_norm_bf16(const float* h32, int n_part, int pairs, int 
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(rows), block(256);
     const int ldh = d + n_ext;
-#define LAUNCH(MAXC) hipLaunchKernelGGL((finish_norm_kernel<MAXC>), grid, block, 0, s, h32, n_part, pairs, rows, ldh, lora_b, \
-                                        lora_scale, x_resid, w_norm, x_out, xn_out, d, eps, row_tail)
+#define LAUNCH(MAXC) do {                                                                                             \
+        if (hoist) hipLaunchKernelGGL((finish_norm_kernel<MAXC, true>), grid, block, 0, s, h32, n_part, pairs, rows, ldh, lora_b,  \
+                                      lora_scale, x_resid, w_norm, x_out, xn_out, d, eps, row_tail);                  \
+        else hipLaunchKernelGGL((finish_norm_kernel<MAXC, false>), grid, block, 0, s, h32, n_part, pairs, rows, ldh, lora_b,       \
+                                lora_scale, x_resid, w_norm, x_out, xn_out, d, eps, row_tail);                        \
+    } while (0)
+    const int hoist_rows = g_finish_hoist_rows >= 0 ? g_finish_hoist_rows : FINISH_HOIST_ROWS;
+    const bool hoist = hoist_rows > 0 && rows >= hoist_rows;     // by the row count only, never by how the rows are packed
     if (d <= 2048) { LAUNCH(1); }
     else if (d <= 4096) { LAUNCH(2); }
     else { LAUNCH(4); }

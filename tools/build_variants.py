@@ -12,7 +12,7 @@ src = G.CSRC / sys.argv[1]
 out = ROOT / "tools" / "bin"
 out.mkdir(exist_ok=True)
 (ROOT / "build" / "variants").mkdir(parents=True, exist_ok=True)
-others = [str(o) for o in sorted((ROOT / "build" / "obj").glob("*.o")) if o.stem != src.stem]
+others = [str(o) for o in sorted((ROOT / "build" / "obj").glob("*.o")) if o.stem != src.stem and "-hip-" not in o.stem]      # not the -save-temps device object of gemm256
 def one(spec):
     name, _, flags = spec.partition(":")
     obj = ROOT / "build" / "variants" / f"{src.stem}_{name}.o"
