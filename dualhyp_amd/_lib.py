@@ -51,6 +51,7 @@ SIGNATURES = {
     "dh_linear_partial_pairs_bf16": (I, [P, P, P, P, I, I, I, I, I, P]),
     "dh_finish_norm_bf16": (I, [P, I, I, I, I, I, P, F, P, P, P, P, F, P, P]),
     "dh_attn_decode_fused_bf16": (I, [P, I, I, I, I, I, P, F, I, I, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "dh_attn_verify_fused_bf16": (I, [P, I, I, I, I, I, I, P, F, I, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "dh_attn_prefill_bf16": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "dh_dropout_bf16": (I, [P, P, P, I64, F, C.c_uint64, C.c_uint32, P, P]),
     "dh_swiglu_fwd_bf16": (I, [P, P, P, I64, P]),

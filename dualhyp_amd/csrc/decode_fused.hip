@@ -1037,7 +1037,8 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
                               dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream) {
     DH_CHECK(qkv32 && cos && sin && seq_slot && kv_len && k_cache && vT_cache && y, "attn_verify_fused: null argument");
     DH_CHECK(n_groups > 0 && n_head % n_groups == 0, "attn_verify_fused: bad head counts");
-    DH_CHECK(S >= 2 && S <= 8 && S * (n_head / n_groups) <= 32, "attn_verify_fused: %d positions x %d heads per group exceed 32 query columns",
+    DH_CHECK(S >= 2 && S <= 8, "attn_verify_fused: S = %d positions per sequence, 2 .. 8 are served", S);
+    DH_CHECK(S * (n_head / n_groups) <= 32, "attn_verify_fused: %d positions x %d heads per group exceed 32 query columns",
              S, n_head / n_groups);
     DH_CHECK(hs == 64 || hs == 96 || hs == 128, "attn_verify_fused: head_size %d unsupported", hs);
     DH_CHECK(s_max % 64 == 0 && p_max > 0 && p_max <= s_max && n_part >= 1 && n_part <= MAXP, "attn_verify_fused: bad s_max / p_max / n_part");
@@ -1068,6 +1069,16 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
 #undef VER_LAUNCH
     DH_LAUNCH_CHECK();
     return 0;
+}
+
+// the op on its own (include/dualhyp_hip.h): what the engine launches, for the op-level tests and other callers
+extern "C" int dh_attn_verify_fused_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int S, int qkv_dim, int n_ext,
+                                         const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
+                                         const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
+                                         dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max,
+                                         void* stream) {
+    return dh_attn_verify_fused_impl(qkv32, n_part, pairs, n_seq, S, qkv_dim, n_ext, lora_b, lora_scale, split0, split1, cos, sin,
+                                     seq_slot, kv_len, k_cache, vT_cache, y, n_head, n_groups, hs, s_max, p_max, stream);
 }
 
 // finish_norm_kernel<, true> from this many rows on.  tools/sweep_finish.py, d 2048, us per launch, loads behind | ahead of the

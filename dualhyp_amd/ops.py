@@ -418,6 +418,27 @@ def attn_decode_fused(qkv32: torch.Tensor, qkv_dim: int, lora_b: Optional[torch.
     return y
 
 
+def attn_verify_fused(qkv32: torch.Tensor, qkv_dim: int, lora_b: Optional[torch.Tensor], lora_scale: float,
+                      splits: Tuple[int, int], cos: torch.Tensor, sin: torch.Tensor, seq_slot: torch.Tensor,
+                      kv_len: torch.Tensor, k_cache: torch.Tensor, vT_cache: torch.Tensor, n_head: int, S: int,
+                      p_max: Optional[int] = None, pairs: bool = True) -> torch.Tensor:
+    """`attn_decode_fused` for S consecutive positions per sequence in one launch (the verify step of speculative decoding):
+    qkv32 [n_part, n_seq * S, ld], row seq * S + j at position kv_len[seq] - 1 + j; -> [n_seq * S, n_head * hs].  Rows at
+    positions >= p_max (default s_max) append nothing; dh_attn_verify_fused_bf16."""
+    k = _Keep()
+    n_part, n_rows, ld = qkv32.shape
+    if S <= 0 or n_rows % S:
+        raise ValueError(f"attn_verify_fused: {n_rows} rows are not S = {S} per sequence")
+    n_groups, s_max, hs = k_cache.size(1), k_cache.size(2), k_cache.size(3)
+    y = torch.empty((n_rows, n_head * hs), dtype=torch.bfloat16, device=qkv32.device)
+    i32 = torch.int32
+    check(_lib.load().dh_attn_verify_fused_bf16(_p(qkv32), n_part, int(pairs), n_rows // S, S, qkv_dim, ld - qkv_dim, _p(lora_b),
+                                                float(lora_scale), splits[0], splits[1], k(cos), k(sin),
+                                                k(seq_slot, i32), k(kv_len, i32), _p(k_cache), _p(vT_cache),
+                                                _p(y), n_head, n_groups, hs, s_max, s_max if p_max is None else int(p_max), _stream()))
+    return y
+
+
 def kcache_to_plain(kc: torch.Tensor) -> torch.Tensor:
     """K cache [slot, group, s_max, hs] as stored (MFMA-fragment order, csrc/common.h kfrag_off)
     -> plain [slot, group, key, channel].  Test/debug helper."""

@@ -201,6 +201,19 @@ int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pairs, int n_s
                               dh_bf16* y, int n_head, int n_groups, int hs, int s_max,
                               void* stream);
 
+/* dh_attn_decode_fused_bf16 for S = 2 .. 8 consecutive positions of every sequence in one launch (the verify step of speculative
+ * greedy decoding; S * n_head / n_groups <= 32).  qkv32 [n_part][n_seq * S][qkv_dim + n_ext] and y [n_seq * S, n_head*hs]: row
+ * seq * S + j is position kv_len[seq] - 1 + j of the sequence, so kv_len[seq] counts row 0's token and nothing of rows 1 .. S-1.
+ * Row j gives the bits of a single-token launch at kv_len[seq] + j that follows those of rows 0 .. j-1, and the caches end as
+ * after those launches.  Rows at positions >= p_max (0 < p_max <= s_max: the last position the cache and the cos / sin tables
+ * serve) append nothing; their rows of y are finite and mean nothing.  The caller keeps kv_len[seq] <= p_max.  Added under ABI 6. */
+int dh_attn_verify_fused_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int S, int qkv_dim, int n_ext,
+                              const dh_bf16* lora_b, float lora_scale, int split0, int split1,
+                              const dh_bf16* cos, const dh_bf16* sin, const int32_t* seq_slot,
+                              const int32_t* kv_len, dh_bf16* k_cache, dh_bf16* vT_cache,
+                              dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max,
+                              void* stream);
+
 /* ------------------------------------------------------------------ LoRA fine-tune backward
  * finetune/ger.py:278-285 `fabric.backward(loss / accum)` for the frozen-base / LoRA-only case: the dX
  * GEMMs reuse dh_linear_bf16 on transposed copies of the frozen weights; these are the rest. */

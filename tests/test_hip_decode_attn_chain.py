@@ -144,7 +144,8 @@ def test_other_head_sizes(hs):
 
 def test_verify_step_equals_plain_steps():
     """speculate=3 against the plain run at hs 64: attn_verify_fused_kernel still gives, position by position, the bits of the
-    single-token kernel that now is attn_decode_chain_kernel (the smallest case of tests/test_hip_speculate.py)."""
+    single-token kernel that now is attn_decode_chain_kernel (the smallest case of tests/test_hip_speculate.py).
+    The op itself, row by row against plain launches of the single-token op: tests/test_hip_verify_attn.py."""
     from dualhyp_amd import GPT, Config, generate_batch
     from dualhyp_amd.synth import synth_state_dict, synth_prompts
     new, kw = 24, dict(temperature=0.2, top_k=1)
