@@ -318,6 +318,131 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     }
 }
 
+// attn_decode_kernel over the fp8 KV cache (common.h k8_off / v8_off; written by kv8.hip): same grid, same tile-to-wave deal, same
+// per-tile update, same partials.  A tile is HS/32 + HS/32 coalesced 1-KiB loads of 16 B per lane, each holding two k-step
+// fragments, plus 32 + 32 exponent bytes.  A fragment becomes bf16 in registers, e4m3 -> fp32 (v_cvt_pk_f32_fp8), times the
+// power-of-two scale of its key, truncated to bf16 — all exact, and applied to the OPERAND: the MFMAs see the values the bf16
+// kernel reads from the expanded cache (dh_kv8_expand), so the two kernels agree bit for bit.
+template <int HS>
+__global__ __launch_bounds__(256) void attn_decode_kv8_kernel(
+    const bf16_t* __restrict__ q, const uint8_t* __restrict__ k8, const uint8_t* __restrict__ v8, const int8_t* __restrict__ k_exp,
+    const int8_t* __restrict__ v_exp, const int32_t* __restrict__ seq_slot, const int32_t* __restrict__ kv_len,
+    float* __restrict__ work, int n_head, int n_groups, int s_max, float scale) {
+    constexpr int KS = HS / 16, DT = HS / 32;
+    const int pair = blockIdx.x, seq = pair / n_groups, g = pair % n_groups;
+    const int nw = gridDim.y * 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wg = blockIdx.y * 4 + wave;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int q_per_kv = n_head / n_groups;
+    const int slot = seq_slot[seq], len = kv_len[seq];
+    const int n_tiles = (len + 31) / 32;
+
+    bf16x8 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (lr < q_per_kv)
+            z = *reinterpret_cast<const bf16x8*>(q + ((size_t)seq * n_head + g * q_per_kv + lr) * HS + ks * 16 + lh * 8);
+        qf[ks] = z;
+    }
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+    const size_t blk = (size_t)slot * n_groups + g;
+    const uint8_t *kbase = k8 + blk * s_max * HS, *vbase = v8 + blk * s_max * HS;
+    const int8_t *kebase = k_exp + blk * s_max, *vebase = v_exp + blk * s_max;
+
+    for (int t = wg; t < n_tiles; t += nw) {
+        const int key0 = t * 32;
+        // all loads of the tile first (keys >= len are masked below; their bytes and exponents are finite values)
+        i32x4 kb[DT], vb[DT];
+#pragma unroll
+        for (int b = 0; b < DT; ++b) {
+            kb[b] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(kbase + kv8_blk<HS>(t, b) + lane * 16));
+            vb[b] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(vbase + kv8_blk<HS>(t, b) + lane * 16));
+        }
+        const float ksc = kv8_pow2(kebase[key0 + lr]);      // the A row of this lane is key lr
+        uint32_t vew[2][2];                                  // exponents of the lane's 8 keys of k-step s: keys 16s + 4lh + 0..3, + 8
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            vew[s][0] = *reinterpret_cast<const uint32_t*>(vebase + key0 + 16 * s + 4 * lh);
+            vew[s][1] = *reinterpret_cast<const uint32_t*>(vebase + key0 + 16 * s + 4 * lh + 8);
+        }
+        f32x16 st;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            union { bf16x8 v; uint32_t u[4]; } kf;
+            const int w = (ks & 1) * 2;
+            kv8_cvt4((uint32_t)kb[ks >> 1][w], ksc, ksc, ksc, ksc, kf.u[0], kf.u[1]);
+            kv8_cvt4((uint32_t)kb[ks >> 1][w + 1], ksc, ksc, ksc, ksc, kf.u[2], kf.u[3]);
+            st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.v, qf[ks], st, 0, 0, 0);
+        }
+        float m_t = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key_abs = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            float s = st[r] * scale;
+            s = key_abs < len ? s : -INFINITY;
+            st[r] = s;
+            m_t = fmaxf(m_t, s);
+        }
+        m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
+        const float m_new = fmaxf(m_run, m_t);           // finite: key0 < len
+        const float alpha = __expf(m_run - m_new);
+        m_run = m_new;
+        float psum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = __expf(st[r] - m_new);
+            st[r] = p;
+            psum += p;
+        }
+        l_run = l_run * alpha + psum;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            union { bf16x8 v; uint32_t u[4]; } pf;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pf.u[j] = pack2bf(st[8 * s + 2 * j], st[8 * s + 2 * j + 1]);
+            float vs[8];
+            kv8_scales4(vew[s][0], vs);
+            kv8_scales4(vew[s][1], vs + 4);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                if (s == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+                }
+                union { bf16x8 v; uint32_t u[4]; } vf;
+                kv8_cvt4((uint32_t)vb[dt][2 * s], vs[0], vs[1], vs[2], vs[3], vf.u[0], vf.u[1]);
+                kv8_cvt4((uint32_t)vb[dt][2 * s + 1], vs[4], vs[5], vs[6], vs[7], vf.u[2], vf.u[3]);
+                // keys >= len carry p == 0; the cache is zero-initialised so 0 * v stays 0
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf.v, pf.v, o[dt], 0, 0, 0);
+            }
+        }
+    }
+    // partial: [pair][wg] -> m[DEC_COLS], l[DEC_COLS], o[HS][DEC_COLS]
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    float* wp = work + ((size_t)pair * nw + wg) * (2 * DEC_COLS + HS * DEC_COLS);
+    if (lr < q_per_kv) {
+        if (lh == 0) {
+            wp[lr] = m_run;
+            wp[DEC_COLS + lr] = l_tot;
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                wp[2 * DEC_COLS + d * DEC_COLS + lr] = o[dt][r];
+            }
+    }
+}
+
 template <int HS>
 __global__ void attn_decode_combine_kernel(const float* __restrict__ work, bf16_t* __restrict__ y, int n_head,
                                            int n_groups, int nw) {
@@ -403,6 +528,34 @@ extern "C" int dh_attn_decode_bf16(const dh_bf16* q, const dh_bf16* k_cache, con
         hipLaunchKernelGGL((attn_decode_combine_kernel<128>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head,
                            n_groups, DEC_NSPLIT * 4);
     }
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_attn_decode_kv8(const dh_bf16* q, const uint8_t* k8, const uint8_t* v8, const int8_t* k_exp, const int8_t* v_exp,
+                                  const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* y, void* work, int n_seq, int n_head,
+                                  int n_groups, int hs, int s_max, void* stream) {
+    DH_CHECK(q && k8 && v8 && k_exp && v_exp && seq_slot && kv_len && y, "dh_attn_decode_kv8: null argument");
+    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DEC_COLS, "dh_attn_decode_kv8: bad head counts");
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_kv8: head_size %d unsupported", hs);
+    DH_CHECK(s_max > 0 && s_max % 64 == 0, "dh_attn_decode_kv8: s_max must be a multiple of 64");
+    DH_CHECK(work != nullptr, "dh_attn_decode_kv8: null workspace");
+    if (n_seq <= 0) return 0;
+    const int pairs = n_seq * n_groups;
+    const float scale = 1.0f / sqrtf((float)hs);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(pairs, DEC_NSPLIT), block(256);
+#define LAUNCH(HS_)                                                                                                          \
+    do {                                                                                                                     \
+        hipLaunchKernelGGL((attn_decode_kv8_kernel<HS_>), grid, block, 0, s, q, k8, v8, k_exp, v_exp, seq_slot, kv_len, (float*)work, \
+                           n_head, n_groups, s_max, scale);                                                                  \
+        hipLaunchKernelGGL((attn_decode_combine_kernel<HS_>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head, n_groups, \
+                           DEC_NSPLIT * 4);                                                                                  \
+    } while (0)
+    if (hs == 64) LAUNCH(64);
+    else if (hs == 96) LAUNCH(96);
+    else LAUNCH(128);
+#undef LAUNCH
     DH_LAUNCH_CHECK();
     return 0;
 }

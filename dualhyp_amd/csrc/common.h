@@ -150,6 +150,61 @@ __device__ __forceinline__ size_t vfrag_off(int key, int d) {
 template <int HS> __device__ __forceinline__ size_t kfrag_blk(int t, int ks) { return (size_t)(t * (HS / 16) + ks) * 512; }
 template <int HS> __device__ __forceinline__ size_t vfrag_blk(int t, int dt, int s2) { return (size_t)((t * (HS / 32) + dt) * 2 + s2) * 512; }
 
+// ---- fp8 KV cache (kv8.hip; attention.hip attn_decode_kv8_kernel) ----------------------------
+// One e4m3fn byte per element and one int8 power-of-two exponent per (slot, group, position) vector: value = e4m3 * 2^e
+// (include/dualhyp_hip.h states the scheme).  The bytes keep the 32-key tiles above, HS*32 bytes each, and a wave-wide
+// contiguous 1-KiB load is still lane i <- 16 B at i*16: a 1-KiB block packs TWO k-step fragments, 8 bytes each per lane
+// (lane = 32 lh + lr as above):
+//   K  tile: [kp = d/32][lh = (d/8)&1][lr = key&31][hf = (d/16)&1][8 d]   bytes 0..7: fragment ks = 2kp, 8..15: ks = 2kp + 1
+//   V^T tile: [dt = d/32][lh][lr = d&31][s2][8 keys]                       bytes 0..7: fragment (dt, s2 = 0), 8..15: (dt, 1),
+//             the 8 keys in the order of vfrag_off.
+// The exponents are plain [slot][group][position] int8 arrays, one for K and one for V.
+// Offsets in bytes from the start of the (slot, group) block of s_max*HS bytes.
+template <int HS>
+__device__ __forceinline__ size_t k8_off(int key, int d) {
+    const int t = key >> 5, lr = key & 31, kp = d >> 5, hf = (d >> 4) & 1, lh = (d >> 3) & 1, e = d & 7;
+    return ((size_t)((t * (HS / 32) + kp) * 2 + lh) * 32 + lr) * 16 + hf * 8 + e;
+}
+template <int HS>
+__device__ __forceinline__ size_t v8_off(int key, int d) {
+    const int t = key >> 5, kk = key & 31, s2 = kk >> 4, r = kk & 15;
+    const int j = ((r >> 3) << 2) | (r & 3), lh = (r >> 2) & 1, dt = d >> 5, lr = d & 31;
+    return ((size_t)((t * (HS / 32) + dt) * 2 + lh) * 32 + lr) * 16 + s2 * 8 + j;
+}
+// start (in bytes) of 1-KiB block b (K: kp, V^T: dt) of tile t; add lane*16
+template <int HS> __device__ __forceinline__ size_t kv8_blk(int t, int b) { return (size_t)(t * (HS / 32) + b) * 1024; }
+
+// 2^e as fp32, e in [-126, 127]
+__device__ __forceinline__ float kv8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+// the exponent of a vector whose largest magnitude has the bf16 bits `abits` (sign cleared): the smallest e with
+// amax <= 448 * 2^e, from the exponent and mantissa fields alone.  amax = 1.f * 2^(E - 127): e = E - 127 - 8 while
+// 1.f <= 1.75 (mantissa <= 0x60 of 0x80), one more above; clamped to [-100, 100]; 0 for an all-zero vector.
+__device__ __forceinline__ int kv8_exponent(uint32_t abits) {
+    if (abits == 0) return 0;
+    const int e = (int)(abits >> 7) - 135 + ((abits & 0x7f) > 0x60 ? 1 : 0);
+    return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+// e4m3fn_rne(x * inv) saturated to +-448 (never the NaN encoding), inv = 2^-e: the scaling is exact
+__device__ __forceinline__ float kv8_scaled(bf16_t x, float inv) { return fminf(fmaxf(bf2f(x) * inv, -448.0f), 448.0f); }
+__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
+    int v = 0;
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);   // OCP e4m3fn on gfx950, round to nearest even
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+    return (uint32_t)v;
+}
+// four e4m3 bytes of `w` times the four scales -> four bf16 (two dwords).  An e4m3 value has 4 significant bits and
+// the scale is a power of two, so the fp32 product is exact and its low 16 bits are zero: truncation is the conversion.
+__device__ __forceinline__ void kv8_cvt4(uint32_t w, float s0, float s1, float s2, float s3, uint32_t& lo, uint32_t& hi) {
+    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    lo = (__float_as_uint(a[0] * s0) >> 16) | (__float_as_uint(a[1] * s1) & 0xffff0000u);
+    hi = (__float_as_uint(b[0] * s2) >> 16) | (__float_as_uint(b[1] * s3) & 0xffff0000u);
+}
+// the four scales 2^e of the int8 exponents packed in `ew` (byte i = exponent i)
+__device__ __forceinline__ void kv8_scales4(uint32_t ew, float* s) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = kv8_pow2((int)(int8_t)(ew >> (8 * i)));
+}
+
 // ---- host-side error plumbing -------------------------------------------------------------
 void dh_set_error(const char* fmt, ...);
 

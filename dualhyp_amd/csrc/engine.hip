@@ -30,7 +30,11 @@ struct dh_engine {
     int row_cap = 0;                                  // rows the single-token-step workspaces hold (logits, part32, dec_ids, ones): max_batch, or what dh_engine_reserve_rows asked for
     int qkv_dim = 0, kv_dim = 0;
     // device memory
-    bf16_t *kc = nullptr, *vtc = nullptr;             // [L][B][G][S][HS], [L][B][G][HS][S]
+    bf16_t *kc = nullptr, *vtc = nullptr;             // [L][B][G][S][HS], [L][B][G][HS][S]; kv8: ONE layer's worth, the prompt attention's scratch
+    bool kv8 = false;                                 // fp8 KV cache (dh_engine_create_ex kv_dtype 1; common.h k8_off / v8_off)
+    uint8_t *k8 = nullptr, *v8 = nullptr;             // kv8: [L][B][G][S * HS] e4m3 bytes of K and of V^T
+    int8_t *ke = nullptr, *ve = nullptr;              // kv8: [L][B][G][S] exponents of the K and of the V vectors
+    size_t exp_layer_elems = 0;                       // B * G * S
     bf16_t *x = nullptr, *xn = nullptr, *qkv = nullptr, *qrot = nullptr, *att = nullptr, *xa = nullptr,
            *act = nullptr, *xlast = nullptr, *logits = nullptr;
     int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B], read through seq_meta() below
@@ -38,6 +42,7 @@ struct dh_engine {
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t** cache_tab = nullptr;                       // [2 L] device table, written once: K cache of layer l at 2l, V^T cache at 2l + 1
+                                                        // (kv8: [4 L], the fp8 bytes like that, then the exponent arrays like that)
     int32_t* last_meta = nullptr;                       // [ones | position of the last token] x [B]: the pruned last layer's attention call
     bf16_t *att_last = nullptr, *xn_last = nullptr, *act_last = nullptr;   // its n_seq-row operands
     uint8_t *row_tail = nullptr, *last_tail = nullptr, *ones = nullptr;   // Q11 rsqrt emulation flags
@@ -381,6 +386,33 @@ int attention(dh_engine* e, bf16_t* kc, bf16_t* vtc, int n_seq, int max_q_len, b
                                 e->s_max, s);
 }
 
+// The two above for an fp8 KV cache (layer l): rope + quantised append, then the split-KV kernel over the fp8 cache for a single-token
+// step; for a prompt the call's sequences are expanded into the one-layer bf16 scratch (e->kc / e->vtc) first, positions
+// [0, kv_pos0 + q_len), and the prefill kernel runs on that — inside the prefill attention's timing class.
+int rope_append_kv8(dh_engine* e, int l, int n_tok, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    return dh_qkv_rope_cache_kv8(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, e->k8 + (size_t)l * e->cache_layer_elems,
+                                 e->v8 + (size_t)l * e->cache_layer_elems, e->ke + (size_t)l * e->exp_layer_elems,
+                                 e->ve + (size_t)l * e->exp_layer_elems, n_tok, D.n_head, D.n_groups, D.head_size, e->s_max, s);
+}
+int attention_kv8(dh_engine* e, int l, int n_seq, int max_q_len, bool last_rows, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    const int hs = D.head_size, H = D.n_head, G = D.n_groups;
+    const SeqMeta m = seq_meta(e);
+    const uint8_t *k8 = e->k8 + (size_t)l * e->cache_layer_elems, *v8 = e->v8 + (size_t)l * e->cache_layer_elems;
+    const int8_t *ke = e->ke + (size_t)l * e->exp_layer_elems, *ve = e->ve + (size_t)l * e->exp_layer_elems;
+    if (e->phase_decode) {
+        TimeScope t(e, 3, s);
+        return dh_attn_decode_kv8(e->qrot, k8, v8, ke, ve, m.seq_slot, m.kv, e->att, e->dec_work, n_seq, H, G, hs, e->s_max, s);
+    }
+    int rc;
+    {
+        TimeScope t(e, 2, s);
+        if ((rc = dh_kv8_expand(k8, v8, ke, ve, m.seq_slot, m.kv, m.q_len, e->kc, e->vtc, n_seq, G, hs, e->s_max, s))) return rc;
+    }
+    return attention(e, e->kc, e->vtc, n_seq, max_q_len, last_rows, s);
+}
+
 // The half of a block behind the attention, in place on `rows` rows: x += proj(att), x += mlp_proj(swiglu(norm_2(x))).  Called on
 // every row of the call with timed = true, or on the last rows of the last block (attention() above) with timed = false: those
 // n_seq-row launches stream the weights, they are not in the timed class of the large prefill GEMMs, and bench.py does not count their
@@ -478,7 +510,14 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
         bf16_t* kc = e->kc + (size_t)l * e->cache_layer_elems;
         bf16_t* vtc = e->vtc + (size_t)l * e->cache_layer_elems;
         if ((rc = dh_rmsnorm_quant_fp8(e->x, W.norm_1, nullptr, e->xq, e->xscale, n_tok, d, D.norm_eps, rt, s))) return rc;
-        if (decode && n_tok <= 128) {     // every streaming-class step (fp8_kernel above): one family, no 32-row boundary
+        if (e->kv8) {                     // fp8 KV cache: QKV GEMM by the phase rule, quantised append, attention over the fp8 cache
+            if ((rc = linear_fp8(e, W.attn_w, W.attn_ws, e->qkv, n_tok, e->qkv_dim, d, DH_EPI_PLAIN, nullptr, nullptr, nullptr, s, true)))
+                return rc;
+            if ((rc = rope_append_kv8(e, l, n_tok, s))) return rc;
+            const bool last_rows = prune_last && l == D.n_layer - 1;
+            if ((rc = attention_kv8(e, l, n_seq, max_q_len, last_rows, s))) return rc;
+            if (last_rows) return post_attention_fp8(e, W, n_seq, e->att_last, e->xlast, e->act_last, rtl, false, s);
+        } else if (decode && n_tok <= 128) {     // every streaming-class step (fp8_kernel above): one family, no 32-row boundary
             // one launch for rope + cache append + split-KV attention + combine (decode_fused.hip): the QKV product
             // is handed over as its single fp32 "partial" (values already rounded to bf16), no LoRA (merged)
             const SeqMeta m = seq_meta(e);
@@ -643,7 +682,7 @@ int alloc_row_ws(dh_engine* e, int rows) {
     return 0;
 }
 
-int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens) {
+int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype) {
     e->d = *desc;
     e->layers.assign(desc->h_layers, desc->h_layers + desc->n_layer);
     e->d.h_layers = nullptr;
@@ -659,13 +698,19 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
         DH_CHECK(desc->lm_head_ws != nullptr, "dh_engine_create: fp8 mode needs lm_head_ws");
         DH_CHECK(d % 128 == 0 && desc->intermediate % 128 == 0, "dh_engine_create: fp8 mode needs n_embd and intermediate %% 128 == 0");
     }
+    e->kv8 = kv_dtype == 1;
+    DH_CHECK(!e->kv8 || e->fp8, "dh_engine_create_ex: an fp8 KV cache (kv_dtype 1) needs an fp8 engine (channel scales, attn_ws != NULL)");
     e->cache_layer_elems = (size_t)max_batch * G * s_max * hs;
+    e->exp_layer_elems = (size_t)max_batch * G * s_max;
+    // bf16: K and V^T of every layer.  fp8: a byte per element and an exponent byte per vector of every layer, one layer of bf16
+    const size_t kv_bytes = e->kv8 ? 2 * (e->cache_layer_elems + e->exp_layer_elems) * desc->n_layer + 2 * e->cache_layer_elems * sizeof(bf16_t)
+                                   : 2 * e->cache_layer_elems * desc->n_layer * sizeof(bf16_t);
+    const size_t bf16_layers = e->kv8 ? 1 : desc->n_layer;
     {
         // a multi-head model's KV cache (Phi-3.5: 12 KiB per position and layer) outgrows the device at batch sizes tuned on
         // TinyLlama: refuse before allocating anything, naming the knob
         size_t free_b = 0, total_b = 0;
         DH_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t kv_bytes = 2 * e->cache_layer_elems * desc->n_layer * sizeof(bf16_t);
         DH_CHECK(kv_bytes <= free_b,
                  "dh_engine_create: the KV cache of %d sequences x %d positions x %d layers needs %.1f GiB and %.1f GiB are free: "
                  "lower the decode batch (--decode_batch)", max_batch, s_max, desc->n_layer, kv_bytes / 1073741824.0,
@@ -673,8 +718,14 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     }
     const size_t T = max_tokens;
     int rc = 0;
-    rc |= dmalloc(e, &e->kc, e->cache_layer_elems * desc->n_layer);
-    rc |= dmalloc(e, &e->vtc, e->cache_layer_elems * desc->n_layer);
+    rc |= dmalloc(e, &e->kc, e->cache_layer_elems * bf16_layers);
+    rc |= dmalloc(e, &e->vtc, e->cache_layer_elems * bf16_layers);
+    if (e->kv8) {
+        rc |= dmalloc(e, &e->k8, e->cache_layer_elems * desc->n_layer);
+        rc |= dmalloc(e, &e->v8, e->cache_layer_elems * desc->n_layer);
+        rc |= dmalloc(e, &e->ke, e->exp_layer_elems * desc->n_layer);
+        rc |= dmalloc(e, &e->ve, e->exp_layer_elems * desc->n_layer);
+    }
     rc |= dmalloc(e, &e->x, T * d);
     rc |= dmalloc(e, &e->xn, T * d);
     rc |= dmalloc(e, &e->qkv, T * e->qkv_dim);
@@ -694,7 +745,7 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     rc |= dmalloc(e, &e->step_dev, 1);
     rc |= dmalloc(e, &e->slot_list, (size_t)max_batch);
     rc |= dmalloc(e, &e->copy_dst, (size_t)max_batch);
-    rc |= dmalloc(e, &e->cache_tab, (size_t)2 * desc->n_layer);
+    rc |= dmalloc(e, &e->cache_tab, (size_t)(e->kv8 ? 4 : 2) * desc->n_layer);
     rc |= alloc_row_ws(e, max_batch);
     if (e->fp8) {
         rc |= dmalloc(e, &e->xq, T * (size_t)(desc->intermediate > d ? desc->intermediate : d));
@@ -706,14 +757,28 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     if (!rc) { hipError_t he = hipMalloc(&e->dec_work, wb); if (he != hipSuccess) rc = 2; e->dev_bytes += wb; }
     if (rc) { dh_set_error("dh_engine_create: device allocation failed (%s)", dh_last_error()); return 2; }
     // the attention kernels rely on finite (zero) cache contents beyond the written positions
-    DH_HIP(hipMemset(e->kc, 0, e->cache_layer_elems * desc->n_layer * sizeof(bf16_t)));
-    DH_HIP(hipMemset(e->vtc, 0, e->cache_layer_elems * desc->n_layer * sizeof(bf16_t)));
+    DH_HIP(hipMemset(e->kc, 0, e->cache_layer_elems * bf16_layers * sizeof(bf16_t)));
+    DH_HIP(hipMemset(e->vtc, 0, e->cache_layer_elems * bf16_layers * sizeof(bf16_t)));
+    if (e->kv8) {   // zero bytes are 0.0 and zero exponents 2^0
+        DH_HIP(hipMemset(e->k8, 0, e->cache_layer_elems * desc->n_layer));
+        DH_HIP(hipMemset(e->v8, 0, e->cache_layer_elems * desc->n_layer));
+        DH_HIP(hipMemset(e->ke, 0, e->exp_layer_elems * desc->n_layer));
+        DH_HIP(hipMemset(e->ve, 0, e->exp_layer_elems * desc->n_layer));
+    }
     DH_HIP(hipMemset(e->step_dev, 0, sizeof(int32_t)));
     {
-        std::vector<bf16_t*> tab(2 * (size_t)desc->n_layer);
-        for (int l = 0; l < desc->n_layer; ++l) {
-            tab[2 * l] = e->kc + (size_t)l * e->cache_layer_elems;
-            tab[2 * l + 1] = e->vtc + (size_t)l * e->cache_layer_elems;
+        const size_t L = desc->n_layer;
+        std::vector<bf16_t*> tab((e->kv8 ? 4 : 2) * L);
+        for (size_t l = 0; l < L; ++l) {
+            if (e->kv8) {   // the copy kernel moves 16-byte units: the element type of the table is nominal
+                tab[2 * l] = reinterpret_cast<bf16_t*>(e->k8 + l * e->cache_layer_elems);
+                tab[2 * l + 1] = reinterpret_cast<bf16_t*>(e->v8 + l * e->cache_layer_elems);
+                tab[2 * L + 2 * l] = reinterpret_cast<bf16_t*>(e->ke + l * e->exp_layer_elems);
+                tab[2 * L + 2 * l + 1] = reinterpret_cast<bf16_t*>(e->ve + l * e->exp_layer_elems);
+                continue;
+            }
+            tab[2 * l] = e->kc + l * e->cache_layer_elems;
+            tab[2 * l + 1] = e->vtc + l * e->cache_layer_elems;
         }
         DH_HIP(hipMemcpy(e->cache_tab, tab.data(), tab.size() * sizeof(bf16_t*), hipMemcpyHostToDevice));
     }
@@ -871,7 +936,12 @@ int launch_steps(dh_engine* e, const dh_engine::GKey& key, int n_steps, hipStrea
 }  // namespace
 
 extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, dh_engine** out) {
+    return dh_engine_create_ex(desc, max_batch, s_max, max_tokens, 0, out);
+}
+
+extern "C" int dh_engine_create_ex(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, dh_engine** out) {
     DH_CHECK(desc && out, "dh_engine_create: null argument");
+    DH_CHECK(kv_dtype == 0 || kv_dtype == 1, "dh_engine_create_ex: kv_dtype %d is neither 0 (bf16) nor 1 (fp8)", kv_dtype);
     DH_CHECK(desc->head_size == 64 || desc->head_size == 96 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
     DH_CHECK(desc->n_head % desc->n_groups == 0, "dh_engine_create: n_head %% n_groups != 0");
     DH_CHECK(desc->n_embd == desc->n_head * desc->head_size, "dh_engine_create: n_embd != n_head*head_size");
@@ -880,7 +950,7 @@ extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_
     DH_CHECK(max_batch > 0 && max_tokens >= max_batch, "dh_engine_create: bad batch/token capacity");
     DH_CHECK(desc->rope_cos && desc->rope_sin && desc->wte && desc->ln_f && desc->lm_head && desc->h_layers, "dh_engine_create: null weight pointer");
     dh_engine* e = new dh_engine();
-    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens);
+    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens, kv_dtype);
     if (rc) { dh_engine_destroy(e); return rc; }   // one cleanup path: nothing allocated so far leaks
     {
         std::lock_guard<std::mutex> lock(g_engines_mu);
@@ -897,7 +967,7 @@ extern "C" void dh_engine_destroy(dh_engine* e) {
         g_engines.erase(std::remove(g_engines.begin(), g_engines.end(), e), g_engines.end());
     }
     for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
-    void* ptrs[] = {e->kc, e->vtc, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
+    void* ptrs[] = {e->kc, e->vtc, e->k8, e->v8, e->ke, e->ve, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
                     e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->copy_dst, e->cache_tab, e->dec_ids, e->dec_work,
                     e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale};
     for (void* p : ptrs)
@@ -921,7 +991,21 @@ extern "C" int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int6
     switch (what) {
         case 0: src = e->xn; avail = (int64_t)e->max_tokens * e->d.n_embd * 2; break;
         case 3: src = e->x; avail = (int64_t)e->max_tokens * e->d.n_embd * 2; break;
+        case 6: case 7:
+            DH_CHECK(e->kv8, "dh_engine_read: selector %d reads an fp8 KV cache; this engine's is bf16 (selectors 1 / 2)", what);
+            DH_CHECK(layer >= 0 && layer < e->d.n_layer, "dh_engine_read: layer %d out of range", layer);
+            {   // every slot (seq_meta row 0 is the identity), every position
+                const int rc = dh_kv8_expand(e->k8 + (size_t)layer * e->cache_layer_elems, e->v8 + (size_t)layer * e->cache_layer_elems,
+                                             e->ke + (size_t)layer * e->exp_layer_elems, e->ve + (size_t)layer * e->exp_layer_elems,
+                                             e->seq_meta, nullptr, nullptr, e->kc, e->vtc, e->max_batch, e->d.n_groups, e->d.head_size,
+                                             e->s_max, stream);
+                if (rc) return rc;
+            }
+            src = what == 6 ? e->kc : e->vtc;
+            avail = cache_bytes;
+            break;
         case 1: case 2:
+            DH_CHECK(!e->kv8, "dh_engine_read: selector %d reads a bf16 KV cache; this engine's is fp8 (selectors 6 / 7)", what);
             DH_CHECK(layer >= 0 && layer < e->d.n_layer, "dh_engine_read: layer %d out of range", layer);
             src = (what == 1 ? e->kc : e->vtc) + (size_t)layer * e->cache_layer_elems;
             avail = cache_bytes;
@@ -986,13 +1070,21 @@ extern "C" int dh_engine_copy_prefix(dh_engine* e, int src_slot, const int32_t* 
     DH_HIP(hipMemcpyAsync(e->copy_dst, h.seq_slot, n_dst * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DH_HIP(hipEventRecord(e->ev_stage, s));
     const int hs = e->d.head_size, G = e->d.n_groups;
-    const int run16 = n_pos * hs / 8;            // 16-byte units per (layer, cache, group) block: n_pos / 32 tiles of hs * 32 elements
-    const dim3 grid(cdiv(run16, 256), 2 * e->d.n_layer * G, 1);
-    // a short prefix in a shallow model makes few pieces: split the destination list until some 2048 blocks are in flight
-    const int shares = std::min<int64_t>(n_dst, std::max<int64_t>(1, 2048 / ((int64_t)grid.x * grid.y)));
-    const int dst_per_block = cdiv(n_dst, shares);
-    hipLaunchKernelGGL(kv_copy_prefix_kernel, dim3(grid.x, grid.y, cdiv(n_dst, dst_per_block)), dim3(256), 0, s, e->cache_tab, e->copy_dst,
-                       n_dst, dst_per_block, src_slot, G, (size_t)e->s_max * hs, run16);
+    // one launch per kind of block: `block_elems` 2-byte elements per (slot, group), the first run16 16-byte units of each copied
+    auto copy = [&](bf16_t* const* tab, size_t block_elems, int run16) {
+        const dim3 grid(cdiv(run16, 256), 2 * e->d.n_layer * G, 1);
+        // a short prefix in a shallow model makes few pieces: split the destination list until some 2048 blocks are in flight
+        const int shares = std::min<int64_t>(n_dst, std::max<int64_t>(1, 2048 / ((int64_t)grid.x * grid.y)));
+        const int dst_per_block = cdiv(n_dst, shares);
+        hipLaunchKernelGGL(kv_copy_prefix_kernel, dim3(grid.x, grid.y, cdiv(n_dst, dst_per_block)), dim3(256), 0, s, tab, e->copy_dst,
+                           n_dst, dst_per_block, src_slot, G, block_elems, run16);
+    };
+    if (e->kv8) {   // bytes: n_pos / 32 tiles of hs * 32 bytes; exponents: n_pos bytes (n_pos and s_max are multiples of 32)
+        copy(e->cache_tab, (size_t)e->s_max * hs / 2, n_pos * hs / 16);
+        copy(e->cache_tab + 2 * e->d.n_layer, (size_t)e->s_max / 2, n_pos / 16);
+    } else {
+        copy(e->cache_tab, (size_t)e->s_max * hs, n_pos * hs / 8);   // n_pos / 32 tiles of hs * 32 elements
+    }
     DH_LAUNCH_CHECK();
     return 0;
 }

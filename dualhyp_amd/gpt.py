@@ -295,6 +295,11 @@ class _Engine:
             return t.data_ptr()
 
         fp8 = bool(getattr(model, "fp8", False))
+        self.kv_cache_dtype = getattr(model, "kv_cache_dtype", "bf16")
+        if self.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype is 'bf16' or 'fp8', got {self.kv_cache_dtype!r}")
+        if self.kv_cache_dtype == "fp8" and not fp8:
+            raise _lib.DualHypHipError("an fp8 KV cache needs an fp8 model: quantize_model_fp8(model, kv_cache='fp8')")
 
         def wptr(lin) -> Optional[int]:
             """bf16 weight, or the e4m3 bytes of a quantised layer (dualhyp_amd.quant)"""
@@ -345,7 +350,8 @@ class _Engine:
         self.device = model.transformer.wte.weight.device
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(lib.dh_engine_create(C.byref(desc), max_batch, s_max, max_tokens, C.byref(handle)))
+            _lib.check(lib.dh_engine_create_ex(C.byref(desc), max_batch, s_max, max_tokens, int(self.kv_cache_dtype == "fp8"),
+                                               C.byref(handle)))
         self.handle = handle
         self.lib = lib
         self.signature = model._param_signature()
@@ -475,7 +481,8 @@ class _Engine:
         return ms.value, n.value
 
     def read(self, what: int, layer: int, shape) -> torch.Tensor:
-        """Copy of engine state (dh_engine_read): 0 ln_f(x), 1 K cache, 2 V^T cache, 3 residual x."""
+        """Copy of engine state (dh_engine_read): 0 ln_f(x), 1 K cache, 2 V^T cache, 3 residual x; 6 / 7 the K / V^T cache of an
+        fp8-KV engine expanded to bf16."""
         out = torch.empty(shape, dtype=torch.bfloat16, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_read(self.handle, what, layer, out.data_ptr(), out.numel() * 2,
@@ -506,6 +513,7 @@ class GPT(nn.Module):
         # compare with the reference's CPU tensors set 32 (AVX-512 hosts; 16 = AVX2): torch's CPU bf16 rsqrt
         # rounds twice in its scalar tail loop and dh_rmsnorm_bf16 can reproduce that per row.
         self.cpu_rsqrt_vec_width = 0
+        self.kv_cache_dtype = "bf16"                      # "fp8": quantize_model_fp8(model, kv_cache="fp8")
         self._engine: Optional[_Engine] = None
         self._capacity = dict(max_batch=1, s_max=0, max_tokens=0)
         self._cache_len: List[int] = []                   # tokens currently valid per cache slot
@@ -585,7 +593,8 @@ class GPT(nn.Module):
             else:
                 s_need = max(cap["s_max"], need_pos, self.max_seq_length)
                 self.set_capacity(mb, s_need, max(cap["max_tokens"], need_tokens, mb * min(s_need, 1024)))
-        if self._engine is not None and self._engine.signature != self._param_signature():
+        if self._engine is not None and (self._engine.signature != self._param_signature()
+                                         or self._engine.kv_cache_dtype != getattr(self, "kv_cache_dtype", "bf16")):
             self._drop_engine()
         if self._engine is None:
             w = self.transformer.wte.weight

@@ -149,6 +149,9 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         if rank == 0:
             print("Missing:", missing)
             print("Unexpected:", unexpected)
+    if getattr(args, "quantize", "none") == "fp8":     # after the checkpoint: a quantised model has no bf16 weights to load into
+        from .quant import quantize_model_fp8
+        quantize_model_fp8(model, kv_cache=getattr(args, "kv_cache", "bf16"))
     fmt = args.prompts_format
     if args.dual_hypotheses and "Dual" not in fmt and fmt != "RelPrompt":
         print("Warning: dual hypotheses is enabled, but prompts format is not Dual.")
@@ -194,6 +197,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     if torch.cuda.is_available() and model.transformer.wte.weight.is_cuda:
         c_ = model.config
         kv_per_pos = c_.n_layer * 2 * c_.n_query_groups * c_.head_size * 2
+        if getattr(model, "kv_cache_dtype", "bf16") == "fp8":      # a byte per element, an exponent per vector, one layer of bf16 scratch
+            kv_per_pos = c_.n_layer * 2 * c_.n_query_groups * (c_.head_size + 1) + 2 * c_.n_query_groups * c_.head_size * 2
         longest = max((int(e["input_ids_no_response"].numel()) for e in examples), default=1) + args.max_new_tokens
         free, _total = torch.cuda.mem_get_info(model.transformer.wte.weight.device)
         fit = int(0.8 * free // max(kv_per_pos * longest, 1))
@@ -243,13 +248,9 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     return out
 
 
-def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
-    """`python -m dualhyp_amd.inference --test_path x.json --model_path runs/exp/best_model.pth --llm_checkpoint
-    checkpoints/TinyLlama/TinyLlama-1.1B-Chat-v1.0 --dual_hypotheses --prompts_format DualHyp` — the flags of
-    inference/ger.py:129-153; `--d N` shards the utterances over N GPUs (one process each)."""
+def build_parser():
+    """The harness's flags: those of inference/ger.py:129-153 and this build's additions."""
     import argparse
-    import random
-    from pathlib import Path
     p = argparse.ArgumentParser(prog="python -m dualhyp_amd.inference")
     p.add_argument("--test_path", type=str, required=True)
     p.add_argument("--model_path", type=str, default="", help="fine-tuned checkpoint ({'model': state_dict}); empty with --random_init")
@@ -284,6 +285,12 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
                    help="D in 1..7: a decode step verifies D tokens drafted by prompt lookup (the correction mostly copies spans of its "
                         "prompt) next to each sequence's last one and keeps those the greedy arg-max confirms; --schedule batch only; "
                         "the predictions do not depend on it.  Default 0: off (acceptance on real corpora is unmeasured)")
+    p.add_argument("--quantize", choices=("none", "fp8"), default="none",
+                   help="fp8: after the checkpoint is loaded, LoRA is merged and every dense weight becomes e4m3 rows with channel scales "
+                        "(quantize_model_fp8); activations are quantised per token and every product runs on the fp8 MFMA")
+    p.add_argument("--kv_cache", choices=("bf16", "fp8"), default="bf16",
+                   help="fp8 (with --quantize fp8): cached K and V vectors are stored as e4m3 bytes with one power-of-two exponent each, "
+                        "half the cache bytes per token; the predictions are those of attention over the rounded cache")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)
@@ -293,11 +300,31 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
     p.add_argument("--time_window", type=float, default=0.4)
     p.add_argument("--pool_size", type=int, default=10)
     p.add_argument("--enc_features_dir", type=str, default=None)
+    return p
+
+
+def parse_args(argv: Optional[Sequence[str]] = None):
+    """The parsed flags, with the combinations that cannot run refused before anything is loaded."""
+    p = build_parser()
     args = p.parse_args(argv)
+    if args.kv_cache == "fp8" and args.quantize != "fp8":
+        p.error("--kv_cache fp8 goes with --quantize fp8: the fp8 KV cache belongs to the fp8 serving path")
+    if args.speculate and args.quantize == "fp8":             # speculate.check_arguments refuses it too
+        p.error(f"--speculate {args.speculate} does not go with --quantize fp8: an fp8 engine has no verify step")
     if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet
         p.error(f"--speculate {args.speculate} goes with --schedule batch: continuous batching steps a row list one token at a time")
     if not 0 <= args.speculate <= 7:
         p.error(f"--speculate {args.speculate}: D is 0 (off) or 1..7")
+    return args
+
+
+def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Any]:
+    """`python -m dualhyp_amd.inference --test_path x.json --model_path runs/exp/best_model.pth --llm_checkpoint
+    checkpoints/TinyLlama/TinyLlama-1.1B-Chat-v1.0 --dual_hypotheses --prompts_format DualHyp` — the flags of
+    inference/ger.py:129-153; `--d N` shards the utterances over N GPUs (one process each)."""
+    import random
+    from pathlib import Path
+    args = parse_args(argv)
     rank, world, dev = init_distributed(args.d)
     random.seed(args.seed)
     torch.manual_seed(args.seed)

@@ -270,6 +270,84 @@ def linear_fp8(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scal
     return y
 
 
+# ------------------------------------------------------------------------------------------ fp8 KV cache
+def kv8_alloc(n_slots: int, n_groups: int, s_max: int, hs: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A zeroed fp8 KV cache: (k8 uint8 [slot, group, s_max, hs], v8 uint8 [slot, group, hs, s_max], k_exp, v_exp int8
+    [slot, group, s_max]).  The uint8 shapes are nominal, as the bf16 caches' are: the bytes of a (slot, group) block are in the
+    fragment order of csrc/common.h k8_off / v8_off (kv8_unpack)."""
+    return (torch.zeros((n_slots, n_groups, s_max, hs), dtype=torch.uint8, device=device),
+            torch.zeros((n_slots, n_groups, hs, s_max), dtype=torch.uint8, device=device),
+            torch.zeros((n_slots, n_groups, s_max), dtype=torch.int8, device=device),
+            torch.zeros((n_slots, n_groups, s_max), dtype=torch.int8, device=device))
+
+
+def _kv8_check(k8: torch.Tensor, v8: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor) -> Tuple[int, int, int, int]:
+    B, G, s_max, hs = k8.shape
+    for t, dt, shape, nm in ((k8, torch.uint8, (B, G, s_max, hs), "k8"), (v8, torch.uint8, (B, G, hs, s_max), "v8"),
+                             (k_exp, torch.int8, (B, G, s_max), "k_exp"), (v_exp, torch.int8, (B, G, s_max), "v_exp")):
+        if not t.is_cuda:
+            raise _lib.DualHypHipError(f"{nm} must live on the GPU: the HIP path has no CPU fallback")
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError(f"{nm} must be a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    return B, G, s_max, hs
+
+
+def qkv_rope_cache_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, tok_slot: torch.Tensor, tok_pos: torch.Tensor,
+                       k8: torch.Tensor, v8: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor, n_head: int,
+                       n_groups: int) -> torch.Tensor:
+    """-> rotated q [n_tok, n_head, hs] (the bits of qkv_rope_cache); k (after rope) and v of every token are quantised into
+    the fp8 cache in place; dh_qkv_rope_cache_kv8."""
+    k = _Keep()
+    qkv = _dev(qkv, name="qkv")
+    _, _, s_max, hs = _kv8_check(k8, v8, k_exp, v_exp)
+    n_tok = qkv.numel() // ((n_head + 2 * n_groups) * hs)
+    q = torch.empty((n_tok, n_head, hs), dtype=torch.bfloat16, device=qkv.device)
+    check(_lib.load().dh_qkv_rope_cache_kv8(_p(qkv), k(cos), k(sin), k(tok_slot, torch.int32), k(tok_pos, torch.int32), _p(q),
+                                            _p(k8), _p(v8), _p(k_exp), _p(v_exp), n_tok, n_head, n_groups, hs, s_max, _stream()))
+    return q
+
+
+def attn_decode_kv8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor,
+                    seq_slot: torch.Tensor, kv_len: torch.Tensor) -> torch.Tensor:
+    """attn_decode over the fp8 cache; dh_attn_decode_kv8."""
+    k = _Keep()
+    n_seq, n_head, hs = q.shape
+    _, n_groups, s_max, hs_c = _kv8_check(k8, v8, k_exp, v_exp)
+    assert hs_c == hs, f"q has head size {hs}, the cache {hs_c}"
+    lib = _lib.load()
+    work = torch.empty(lib.dh_attn_decode_work_bytes(n_seq, n_head, hs, s_max), dtype=torch.uint8, device=q.device)
+    y = torch.empty((n_seq, n_head * hs), dtype=torch.bfloat16, device=q.device)
+    i32 = torch.int32
+    check(lib.dh_attn_decode_kv8(k(q), _p(k8), _p(v8), _p(k_exp), _p(v_exp), k(seq_slot, i32), k(kv_len, i32), _p(y), _p(work),
+                                 n_seq, n_head, n_groups, hs, s_max, _stream()))
+    return y
+
+
+def kv8_expand(k8: torch.Tensor, v8: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor, seq_slot: torch.Tensor,
+               kv_len: Optional[torch.Tensor], k_out: torch.Tensor, vT_out: torch.Tensor) -> None:
+    """Positions [0, kv_len[i]) of slot seq_slot[i] (kv_len None: every position) dequantised into the bf16 caches k_out
+    [slot, group, s_max, hs] / vT_out [slot, group, hs, s_max] in place, whole 32-key tiles; dh_kv8_expand."""
+    k = _Keep()
+    B, G, s_max, hs = _kv8_check(k8, v8, k_exp, v_exp)
+    assert tuple(_dev(k_out, name="k_out").shape) == (B, G, s_max, hs) and k_out.is_contiguous()
+    assert tuple(_dev(vT_out, name="vT_out").shape) == (B, G, hs, s_max) and vT_out.is_contiguous()
+    i32 = torch.int32
+    check(_lib.load().dh_kv8_expand(_p(k8), _p(v8), _p(k_exp), _p(v_exp), k(seq_slot, i32), k(kv_len, i32), None, _p(k_out),
+                                    _p(vT_out), seq_slot.numel(), G, hs, s_max, _stream()))
+
+
+def kv8_unpack(k8: torch.Tensor, v8: torch.Tensor, k_exp: torch.Tensor,
+               v_exp: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fp8 cache buffers as stored -> (K bytes, V bytes: uint8 [slot, group, pos, hs]; K exponents, V exponents: int8
+    [slot, group, pos]).  Host index math of csrc/common.h k8_off / v8_off; works on any device.  Test/debug helper."""
+    B, G, S, hs = k8.shape
+    k = k8.reshape(B, G, S // 32, hs // 32, 2, 32, 2, 8)                 # tile, kp, lh, lr, hf, e
+    k = k.permute(0, 1, 2, 5, 3, 6, 4, 7).reshape(B, G, S, hs)           # key = (tile, lr); d = 32 kp + 16 hf + 8 lh + e
+    v = v8.reshape(B, G, S // 32, hs // 32, 2, 32, 2, 2, 4)              # tile, dt, lh, lr, s2, jh, jl
+    v = v.permute(0, 1, 2, 6, 7, 4, 8, 3, 5).reshape(B, G, S, hs)        # key = 32 tile + 16 s2 + 8 jh + 4 lh + jl; d = 32 dt + lr
+    return k, v, k_exp, v_exp
+
+
 def im2col3(x: torch.Tensor, ld: int, relu: bool = False) -> torch.Tensor:
     """[B*T, ld] im2col matrix of a k=3, pad=1 convolution over x [B,T,C] with a ones column at 3C; dh_im2col3_bf16."""
     x = _dev(x, name="x")

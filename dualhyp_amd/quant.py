@@ -1,6 +1,6 @@
 """fp8 (OCP e4m3fn) serving path — BASELINE config 5 / SURVEY.md §8f-4.
 
-`quantize_model_fp8(model)` folds every LoRA update into its base weight exactly as the reference's
+`quantize_model_fp8(model, kv_cache="bf16" | "fp8")` folds every LoRA update into its base weight exactly as the reference's
 `merge_lora_weights` does (ger/lora.py:707-711 -> `:152-157`, `:349-365`) and then replaces each dense weight (the
 seven matrices of every block and lm_head) by e4m3 rows with one fp32 scale per output channel:
 
@@ -38,14 +38,25 @@ def dequantize_rows_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q.view(torch.float8_e4m3fn).float() * scale.view(-1, 1)
 
 
-def quantize_model_fp8(model) -> None:
+def quantize_model_fp8(model, kv_cache: str = "bf16") -> None:
     """Serving-only, one way: merge LoRA, replace every dense weight by e4m3 rows + channel scales (non-persistent
     buffers).  The bf16 weights are gone afterwards, so `GPT.load_state_dict` and `save_checkpoint` refuse a quantised
-    model (quantise a freshly loaded model instead)."""
+    model (quantise a freshly loaded model instead).
+
+    kv_cache: "bf16" (default) keeps the KV cache as it is; "fp8" stores every cached K (after rope) and V vector as e4m3
+    bytes with one power-of-two exponent (include/dualhyp_hip.h "fp8 KV cache": 66 048 instead of 131 072 bytes per token at
+    Llama-3-8B).  It sets `model.kv_cache_dtype`; calling again on a quantised model changes that setting alone (the engine
+    is rebuilt, the cache contents are dropped)."""
     from .gpt import GPT, _FrozenLinear, merge_lora_weights
     assert isinstance(model, GPT)
+    if kv_cache not in ("bf16", "fp8"):
+        raise ValueError(f"kv_cache is 'bf16' or 'fp8', got {kv_cache!r}")
     if getattr(model, "fp8", False):
+        if model.kv_cache_dtype != kv_cache:
+            model.kv_cache_dtype = kv_cache
+            model.refresh_engine()
         return
+    model.kv_cache_dtype = kv_cache
     merge_lora_weights(model)
     for m in model.modules():
         if isinstance(m, _FrozenLinear):

@@ -382,6 +382,37 @@ int dh_linear_fp8_ex(const uint8_t* xq, const float* x_scale, const uint8_t* wq,
 int dh_linear_fp8_f32(const uint8_t* xq, const float* x_scale, const uint8_t* wq, const float* w_scale, float* y32, int M,
                       int N, int K, void* stream);
 
+/* ------------------------------------------------------------------ fp8 KV cache (csrc/kv8.hip, csrc/attention.hip)
+ * Scheme.  Each KV group of each token has one K vector (after rope: the bf16 values dh_qkv_rope_cache_bf16 caches) and one V
+ * vector of hs elements.  amax = max |x|; e = the smallest integer with amax <= 448 * 2^e (amax = m * 2^ex, m in [0.5, 1):
+ * e = ex - 9 if m <= 0.875, else ex - 8; from the exponent and mantissa fields, no logarithm), clamped to [-100, 100], 0 when
+ * amax == 0; byte = e4m3fn_rne(x * 2^-e), saturated to +-448, never the NaN encoding.  The dequantised value e4m3 * 2^e has
+ * 4 significant bits and an exponent in range: it is exactly representable in bf16, so attention over this cache is, bit for
+ * bit, the bf16 attention over its expansion.  Zero bytes with zero exponents are 0.0: the cache is zero-initialised like
+ * the bf16 one.  The CPU restatement is tests/kv8_reference.py.
+ * Layout.  k8 / v8: uint8, per (slot, group) a block of s_max * hs bytes in 32-key tiles of hs * 32 bytes; a tile is hs / 32
+ * blocks of 1 KiB, lane i <- 16 B at i * 16, holding two MFMA A-operand fragments of 8 bytes per lane (csrc/common.h
+ * k8_off / v8_off; dualhyp_amd.ops.kv8_unpack is the host index math).  k_exp / v_exp: int8 [max_batch, g, s_max].
+ * hs 64, 96 or 128; s_max % 64 == 0. */
+
+/* dh_qkv_rope_cache_bf16 with the cache writes replaced: q_out is bit for bit that op's, k (after rope) and v of every
+ * token go to the fp8 cache at (tok_slot, tok_pos). */
+int dh_qkv_rope_cache_kv8(const dh_bf16* qkv, const dh_bf16* cos, const dh_bf16* sin, const int32_t* tok_slot,
+                          const int32_t* tok_pos, dh_bf16* q_out, uint8_t* k8, uint8_t* v8, int8_t* k_exp, int8_t* v_exp,
+                          int n_tok, int n_head, int n_groups, int hs, int s_max, void* stream);
+/* dh_attn_decode_bf16 reading the fp8 cache: fragments become bf16 in registers (exactly), same walk, same partials
+ * (`work`: dh_attn_decode_work_bytes), same combine — bit for bit dh_attn_decode_bf16 over the dh_kv8_expand of the cache. */
+int dh_attn_decode_kv8(const dh_bf16* q, const uint8_t* k8, const uint8_t* v8, const int8_t* k_exp, const int8_t* v_exp,
+                       const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* y, void* work, int n_seq, int n_head,
+                       int n_groups, int hs, int s_max, void* stream);
+/* Dequantises positions [0, n_i) of slot seq_slot[i], i < n_seq, into bf16 K / V^T buffers [max_batch, g, s_max, hs] /
+ * [max_batch, g, hs, s_max] in the fragment layout of the bf16 cache (same slot).  n_i = kv_len[i] + kv_extra[i] (kv_extra
+ * NULL: kv_len[i]; both NULL: s_max), at most s_max.  Whole 32-key tiles are written, positions >= n_i of the last one as
+ * +0.0 (zero bits); tiles behind it are left alone. */
+int dh_kv8_expand(const uint8_t* k8, const uint8_t* v8, const int8_t* k_exp, const int8_t* v_exp, const int32_t* seq_slot,
+                  const int32_t* kv_len, const int32_t* kv_extra, dh_bf16* k_out, dh_bf16* vT_out, int n_seq, int n_groups,
+                  int hs, int s_max, void* stream);
+
 /* ------------------------------------------------------------------ decoder engine
  * Native runtime that owns the kernel sequence of ger/lora.py:504-549 for a whole batch:
  * embed -> n_layer x [norm_1, qkv(+LoRA), rope+cache, attention, proj(+LoRA)+residual,
@@ -436,6 +467,17 @@ typedef struct dh_engine dh_engine;
  * allocating when the KV cache alone exceeds the device's free memory. */
 int dh_engine_create(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens,
                      dh_engine** h_out);
+/* dh_engine_create with the KV cache's element type: kv_dtype 0 = bf16 (dh_engine_create itself), 1 = fp8 (the scheme and
+ * layout of "fp8 KV cache" above).  kv_dtype 1 needs an fp8 engine (attn_ws != NULL).  It allocates, per layer, k8 / v8
+ * [max_batch, g, s_max * hs] bytes and k_exp / v_exp [max_batch, g, s_max] int8, plus ONE layer's worth of bf16 K / V^T
+ * [max_batch, g, s_max, hs] that every layer's prompt attention reuses: a prompt forward writes the fp8 cache
+ * (dh_qkv_rope_cache_kv8), expands the call's sequences into that scratch (dh_kv8_expand) and runs dh_attn_prefill_bf16 on
+ * it, so a prompt token attends to the values the decode steps (dh_attn_decode_kv8) will read; the <= 128-row fused decode
+ * launch is not used.  With n = max_batch * g * s_max, dh_engine_device_bytes is smaller than the bf16 engine's of the same
+ * capacity by n_layer * n * (2 hs - 2) - 4 * n * hs - 16 * n_layer bytes (the scratch, and 2 n_layer more pointers in the
+ * table dh_engine_copy_prefix reads).  A kv_dtype 0 engine runs the launches of dh_engine_create's. */
+int dh_engine_create_ex(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens, int kv_dtype,
+                        dh_engine** h_out);
 void dh_engine_destroy(dh_engine* e);
 int64_t dh_engine_device_bytes(const dh_engine* e);
 
@@ -481,7 +523,8 @@ int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const int32_t* h_s
  * (slot, group) block, so the copy is one contiguous run of n_pos * head_size elements per block at every head
  * size), 0 < n_pos <= s_max.  Slots are in [0, max_batch); the destinations are distinct and exclude src_slot.
  * Positions >= n_pos of the destinations and every other slot keep their contents.  The cache is bf16 in bf16
- * and fp8 engines alike.  n_dst = 0 is a no-op. */
+ * and fp8 engines alike, unless the engine was made with kv_dtype 1 (dh_engine_create_ex): then the fp8 bytes (runs of
+ * n_pos * head_size bytes) and the exponents (n_pos bytes per block) are copied, by two launches.  n_dst = 0 is a no-op. */
 int dh_engine_copy_prefix(dh_engine* e, int src_slot, const int32_t* h_dst_slots, int n_dst, int n_pos,
                           void* stream);
 
@@ -552,7 +595,9 @@ int dh_engine_graph_count(const dh_engine* e, int n_draft);
  *   what 2: V^T cache of `layer`  [max_batch, g, hs, s_max]
  *   what 3: residual stream x after the last layer of the last forward, [n_tok, d]
  *   what 4: int64 ids of the last step's rows (a verify step: row i * S + j = last token, then the drafts)
- *   what 5: int32 kv_len of the last step's sequences (a verify step: the lengths its drafts were proposed from) */
+ *   what 5: int32 kv_len of the last step's sequences (a verify step: the lengths its drafts were proposed from)
+ *   what 6 / 7: an fp8-KV engine's K / V^T cache of `layer` EXPANDED to bf16 (every slot, every position), in the form of
+ *               what 1 / 2; overwrites the engine's one-layer scratch.  what 1 / 2 are refused by an fp8-KV engine. */
 int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int64_t n_bytes, void* stream);
 /* HIP-event timing of the dominant kernels inside the last forward/decode call (bench.py
  * roofline): returns accumulated milliseconds and launch count for kernel class `which`
