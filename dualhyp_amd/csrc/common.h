@@ -237,12 +237,12 @@ void dh_set_error(const char* fmt, ...);
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
-// dh_sample_rows_bf16
+// dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
-                   float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, void* stream);
+                   float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, float* logprobs, void* stream);
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
-                        int top_k, int64_t eos_id, uint64_t seed, void* stream);
+                        int top_k, int64_t eos_id, uint64_t seed, float* logprobs, void* stream);
 
 // the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
 // acceptance kernel (sampling.hip)
@@ -252,7 +252,7 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
                               dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream);
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, void* stream);
+                        const int32_t* step_dev, int32_t* counters, float* logprobs, void* stream);
 
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads

@@ -176,19 +176,98 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
     return choice;
 }
 
+// log softmax(lg)[token] of the RAW row (temperature 1, no crop: the model's distribution, not the sampler's) by the whole block;
+// every thread returns it.  lp = lg[token] - m - log(sum_i exp(lg[i] - m)), m = max_i lg[i]: bf16 widened to fp32, fp32 sum, expf / logf
+// (the fast intrinsics lose the last bits of large arguments).  -inf entries add 0; a -inf token gives -inf.
+// The summation order is a function of vocab alone: thread t adds the 8-element chunks t, t + NT, t + 2 NT, .. in index order into one
+// chain, a wave adds its 64 chains by the xor butterfly, the 16 wave sums are added by a butterfly too.  (The 16 wave maxima before
+// it are read one after the other by every thread: a maximum is exact in any order.)  The 16-byte loads (vocab % 8 == 0
+// and an aligned row, as in pick_token) and the scalar loop visit the same elements in the same order, so a row's bits do not depend
+// on where it lies, and never on the row index or the row count.
+__device__ __forceinline__ float token_logprob(const bf16_t* __restrict__ lg, int vocab, int token) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float s_lp[NT / 64];
+    const bool vec = (vocab & 7) == 0 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
+    const uint4* lg4 = reinterpret_cast<const uint4*>(lg);
+    const int n4 = (vocab + 7) >> 3;
+    // ---- m = max_i lg[i] (exact in any order)
+    float mx = -INFINITY;
+    if (vec) {
+        for (int c0 = tid; c0 < n4; c0 += 4 * NT) {
+            uint4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = c0 + u * NT < n4 ? lg4[c0 + u * NT] : uint4{0xFF80FF80u, 0xFF80FF80u, 0xFF80FF80u, 0xFF80FF80u};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bf16_t* e8 = reinterpret_cast<const bf16_t*>(&q[u]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) mx = fmaxf(mx, bf2f(e8[e]));
+            }
+        }
+    } else {
+        for (int i = tid; i < vocab; i += NT) mx = fmaxf(mx, bf2f(lg[i]));
+    }
+    mx = wave_max(mx);
+    if (lane == 0) s_lp[wave] = mx;
+    __syncthreads();
+    mx = s_lp[0];
+    for (int w = 1; w < NT / 64; ++w) mx = fmaxf(mx, s_lp[w]);
+    __syncthreads();
+    // ---- sum_i exp(lg[i] - m): one chain per thread over its chunks, in index order
+    auto term = [&](bf16_t b) -> float {
+        const float v = bf2f(b);
+        return v == -INFINITY ? 0.f : expf(v - mx);
+    };
+    float sum = 0.f;
+    if (vec) {
+        for (int c0 = tid; c0 < n4; c0 += 4 * NT) {
+            uint4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = c0 + u * NT < n4 ? lg4[c0 + u * NT] : uint4{0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (c0 + u * NT >= n4) break;
+                const bf16_t* e8 = reinterpret_cast<const bf16_t*>(&q[u]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sum += term(e8[e]);
+            }
+        }
+    } else {
+        for (int c = tid; c < n4; c += NT) {
+            const int hi = min(vocab, c * 8 + 8);
+            for (int i = c * 8; i < hi; ++i) sum += term(lg[i]);
+        }
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) s_lp[wave] = sum;
+    __syncthreads();
+    float tot = s_lp[lane & (NT / 64 - 1)];
+#pragma unroll
+    for (int o = NT / 128; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+    __syncthreads();                       // s_lp is free for the next call
+    const float lt = bf2f(lg[token]);
+    if (lt == -INFINITY) return -INFINITY;
+    return (lt - mx) - logf(tot);
+}
+
+template <bool LP>
 __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                     int64_t* __restrict__ tokens, int tok_ld,
                                                     int32_t* __restrict__ length, int32_t* __restrict__ done,
                                                     float temperature, int top_k, int64_t eos_id, uint64_t seed,
-                                                    int step_arg, const int32_t* __restrict__ step_dev) {
+                                                    int step_arg, const int32_t* __restrict__ step_dev,
+                                                    float* __restrict__ logprobs) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
     const int choice = pick_token(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq);
+    float lp = 0.f;
+    if constexpr (LP) lp = token_logprob(logits + (size_t)seq * vocab, vocab, choice);
     if (tid == 0) {
         const int n = length[seq];
         if (n < tok_ld) {
             tokens[(size_t)seq * tok_ld + n] = choice;
+            if constexpr (LP) logprobs[(size_t)seq * tok_ld + n] = lp;
             length[seq] = n + 1;
         }
         if (eos_id >= 0 && choice == eos_id) done[seq] = 1;
@@ -201,20 +280,25 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
 // (seed, step, row) is when all sequences start together — so a sequence's ids do not depend on when or where it was scheduled.
 // limit[u] = prompt length + max_new is the sequence's own budget (done = 2 when reached).  Several padding rows may name one
 // finished sequence: they return at once.
+template <bool LP>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                          int64_t* __restrict__ tokens, int tok_ld,
                                                          int32_t* __restrict__ length, int32_t* __restrict__ done,
                                                          const int32_t* __restrict__ limit,
                                                          const int32_t* __restrict__ row_seq, int n_seq, int max_new,
-                                                         float temperature, int top_k, int64_t eos_id, uint64_t seed) {
+                                                         float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                                         float* __restrict__ logprobs) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
     const int step = n - (limit[u] - max_new);          // tokens generated so far
     const int choice = pick_token(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u);
+    float lp = 0.f;
+    if constexpr (LP) lp = token_logprob(logits + (size_t)blockIdx.x * vocab, vocab, choice);
     if (tid == 0) {
         if (n < lim) {
             tokens[(size_t)u * tok_ld + n] = choice;
+            if constexpr (LP) logprobs[(size_t)u * tok_ld + n] = lp;
             length[u] = n + 1;
         }
         if (eos_id >= 0 && choice == eos_id) done[u] = 1;
@@ -228,11 +312,13 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
 // i = 1 .. j.  The picks are appended one by one exactly as sample_kernel appends its one: nothing behind an EOS (done = 1) or
 // behind the sequence's budget limit[u] = prompt length + max_new (done = 2), and a finished sequence is left alone.
 // counters: [0] the last step (1-based, *step_dev) at which a sequence was live, [1] drafts verified, [2] drafts appended.
+// LP: the log-probability of an appended pick_j, from its own row u * S + j, goes to logprobs beside the token.
+template <bool LP>
 __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
                                                          int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
                                                          int32_t* __restrict__ done, const int32_t* __restrict__ limit,
                                                          float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
-                                                         int32_t* __restrict__ counters) {
+                                                         int32_t* __restrict__ counters, float* __restrict__ logprobs) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (done[u]) return;
     int n = length[u];
@@ -245,7 +331,11 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
         }
         const int choice = pick_token(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u);
         prev = choice;
-        if (n < lim) {
+        if (n < lim) {                                                    // the same for every thread
+            if constexpr (LP) {
+                const float lp = token_logprob(logits + ((size_t)u * S + j) * vocab, vocab, choice);
+                if (tid == 0) logprobs[(size_t)u * tok_ld + n] = lp;
+            }
             if (tid == 0) tokens[(size_t)u * tok_ld + n] = choice;
             ++n;
             ++appended;
@@ -262,58 +352,98 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
     }
 }
 
+// out[r] = log softmax(logits[r, :])[ids[r]]; an id outside [0, vocab) reads nothing and gives NaN (the Python wrapper refuses it)
+__global__ __launch_bounds__(NT) void token_logprobs_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ ids,
+                                                            float* __restrict__ out) {
+    const int r = blockIdx.x;
+    const int64_t t = ids[r];
+    if (t < 0 || t >= vocab) {                                             // the same for every thread
+        if (threadIdx.x == 0) out[r] = __builtin_nanf("");
+        return;
+    }
+    const float lp = token_logprob(logits + (size_t)r * vocab, vocab, (int)t);
+    if (threadIdx.x == 0) out[r] = lp;
+}
+
 }  // namespace
 
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
-                   const int32_t* step_dev, void* stream) {
+                   const int32_t* step_dev, float* logprobs, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
-    hipLaunchKernelGGL(sample_kernel, dim3(n_seq), dim3(NT), 0, (hipStream_t)stream, logits, vocab, tokens, tok_ld,
-                       length, done, temperature, top_k, eos_id, seed, step, step_dev);
+    // logprobs null: the kernel without the log-probability pass (the code it always was)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(logprobs ? sample_kernel<true> : sample_kernel<false>), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
+                       logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs);
     DH_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                 int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                 int step, void* stream, float* logprobs) {
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, stream);
 }
 
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                               int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                               int step, void* stream) {
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, stream);
+    return dh_sample_bf16_ex(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, stream,
+                             nullptr);
 }
 
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
-                        int top_k, int64_t eos_id, uint64_t seed, void* stream) {
+                        int top_k, int64_t eos_id, uint64_t seed, float* logprobs, void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(sample_rows_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, tokens, tok_ld,
-                       length, done, limit, row_seq, n_seq, max_new, temperature, top_k, eos_id, seed);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(logprobs ? sample_rows_kernel<true> : sample_rows_kernel<false>), dim3(n_rows), dim3(NT), 0,
+                       (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
+                       top_k, eos_id, seed, logprobs);
     DH_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                      int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                      int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                      float* logprobs) {
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
+                               temperature, top_k, eos_id, seed, logprobs, stream);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                    int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
                                    int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
-    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, stream);
+    return dh_sample_rows_bf16_ex(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
+                                  temperature, top_k, eos_id, seed, stream, nullptr);
 }
 
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, void* stream) {
+                        const int32_t* step_dev, int32_t* counters, float* logprobs, void* stream) {
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
-    hipLaunchKernelGGL(spec_accept_kernel, dim3(n_seq), dim3(NT), 0, (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld,
-                       length, done, limit, temperature, eos_id, step_dev, counters);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(logprobs ? spec_accept_kernel<true> : spec_accept_kernel<false>), dim3(n_seq), dim3(NT), 0,
+                       (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
+                       counters, logprobs);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_token_logprobs_bf16(const dh_bf16* logits, int vocab, const int64_t* ids, float* out, int n_rows, void* stream) {
+    DH_CHECK(logits && ids && out, "dh_token_logprobs_bf16: null argument");
+    DH_CHECK(vocab > 0 && n_rows >= 0, "dh_token_logprobs_bf16: bad shape");
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(token_logprobs_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, ids, out);
     DH_LAUNCH_CHECK();
     return 0;
 }

@@ -55,7 +55,8 @@ def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: S
 def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
-                   share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None):
+                   share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
+                   return_logprobs: bool = False):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -74,7 +75,16 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     the arg-max confirms plus one (dh_engine_decode_spec) — the same ids as speculate=0, bit for bit, in fewer steps where the
     drafts are right.  drafts None: drafted by prompt lookup (speculate.propose); a [B, max_new_tokens] int64 tensor: drafts[u, i]
     is proposed as the i-th generated token of sequence u (a scripted proposer for tests and tools/bench_speculate.py).
-    timing gains spec_steps (verify steps until the last sequence finished), spec_drafted and spec_accepted."""
+    timing gains spec_steps (verify steps until the last sequence finished), spec_drafted and spec_accepted.
+
+    return_logprobs: the call returns (out, logprobs[, state]); logprobs[i] is a 1-D float32 tensor with the log-probability of every
+    token the model produced for sequence i, in order, the EOS token's last when the sequence ended on one (so its length is
+    len(out[i]) - len(prompts[i]), plus 1 behind an EOS).  It is log softmax of the raw logits row the token was picked from
+    (temperature 1, no top-k crop: the model's distribution, whatever the call samples with; include/dualhyp_hip.h, "Token
+    log-probabilities"), written by the sampling kernels into a NaN-filled float32 buffer beside the token buffer
+    (state["logprobs"]): the first token's by the prefill's sample call, the others inside the captured decode steps.  Ids, steps
+    and read-backs are those of the call without the flag; the values do not depend on the schedule (speculate, share_prefix,
+    generate_stream)."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     D = _check_speculate(model, speculate, top_k, B)
@@ -102,6 +112,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         tokens = torch.nn.utils.rnn.pad_sequence([p.to(dev) for p in prompts], batch_first=True)
         tokens = torch.nn.functional.pad(tokens, (0, tok_ld - tokens.size(1)))
     tokens = tokens.contiguous()
+    lp_buf = torch.full((B, tok_ld), float("nan"), dtype=torch.float32, device=dev) if return_logprobs else None
     if D:   # lengths, flags and the three counters side by side: one read-back
         state = torch.cat([torch.tensor(lens, dtype=torch.int32), torch.zeros(B + 3, dtype=torch.int32)]).to(dev)
         length, done, counters = state[:B], state[B:2 * B], state[2 * B:]
@@ -123,35 +134,41 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], list(range(a, b)), prompt_phase=True, pos0=P)
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
-    ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0)
+    ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf)
     if ev:
         ev[1].record()
-    steps_run = 0
-    if max_new_tokens > 1:
-        n = max_new_tokens - 1
-        if D:
-            # a step yields 1 .. D + 1 tokens per live sequence, so at most n steps are needed; EOS_CHECK_EVERY at a time, until
-            # every sequence has met its EOS or its budget (done != 0)
-            while steps_run < n:
-                c = min(EOS_CHECK_EVERY, n - steps_run)
-                eng.decode_spec(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature, eos_id,
-                                first_step=steps_run)
-                steps_run += c
-                if steps_run < n and bool((done != 0).all()):
-                    break
-        elif eos_id is None:
-            eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
-            steps_run = n
-        else:
-            # with an EOS the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
-            # (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens, inference/ger.py:71, and a
-            # correction is usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps
-            while steps_run < n:
-                c = min(EOS_CHECK_EVERY, n - steps_run)
-                eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=steps_run)
-                steps_run += c
-                if steps_run < n and bool((done != 0).all()):
-                    break
+    if lp_buf is not None:
+        eng.set_logprobs(lp_buf)        # part of the captured step's key; without it the call runs the steps it always ran
+    try:
+        steps_run = 0
+        if max_new_tokens > 1:
+            n = max_new_tokens - 1
+            if D:
+                # a step yields 1 .. D + 1 tokens per live sequence, so at most n steps are needed; EOS_CHECK_EVERY at a time, until
+                # every sequence has met its EOS or its budget (done != 0)
+                while steps_run < n:
+                    c = min(EOS_CHECK_EVERY, n - steps_run)
+                    eng.decode_spec(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature, eos_id,
+                                    first_step=steps_run)
+                    steps_run += c
+                    if steps_run < n and bool((done != 0).all()):
+                        break
+            elif eos_id is None:
+                eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
+                steps_run = n
+            else:
+                # with an EOS the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
+                # (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens, inference/ger.py:71, and a
+                # correction is usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps
+                while steps_run < n:
+                    c = min(EOS_CHECK_EVERY, n - steps_run)
+                    eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=steps_run)
+                    steps_run += c
+                    if steps_run < n and bool((done != 0).all()):
+                        break
+    finally:
+        if lp_buf is not None:
+            eng.set_logprobs(None)      # the buffer is this call's
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -177,18 +194,24 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         if done_h[i] == 1:
             n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
         out.append(tokens[i, :n])       # a view of this call's own buffer (640 clone launches per 20-batch group otherwise)
+    res = (out,)
+    if return_logprobs:                 # views too: what was produced, the EOS included
+        res += ([lp_buf[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(B)],)
     if return_state:
         st = dict(tokens=tokens, length=length, done=done)
+        if return_logprobs:
+            st["logprobs"] = lp_buf
         if D and steps_run:             # the last verify step's drafts and the lengths they were proposed from
             st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
-        return out, st
-    return out
+        res += (st,)
+    return res if len(res) > 1 else out
 
 
 class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
-    def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0) -> None:
+    def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
+                 logprobs: bool = False) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -202,6 +225,8 @@ class _StreamBackend:
         self.limit = torch.tensor([n + max_new_tokens for n in lens] + [1], dtype=torch.int32, device=dev)
         self.done = torch.zeros(N + 1, dtype=torch.int32, device=dev)
         self.done[N] = 2
+        # beside `tokens`: the log-probability of every sampled token (generate_batch's return_logprobs), NaN where none was
+        self.logprobs = torch.full(tuple(self.tokens.shape), float("nan"), dtype=torch.float32, device=dev) if logprobs else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -223,7 +248,7 @@ class _StreamBackend:
         # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
-                        self.max_new, **self.kw)
+                        self.max_new, logprobs=self.logprobs, **self.kw)
         if end:
             end.record()
 
@@ -247,7 +272,7 @@ class _StreamBackend:
 def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
-                    share_prefix: Union[bool, str] = False, speculate: int = 0):
+                    share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -260,7 +285,9 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 
     share_prefix: as in generate_batch.  The shared positions are forwarded once and copied into every slot the scheduler
     hands out before the first prefill; no sequence of the call writes below position P, so they outlive every refill, and a
-    refill is a prefill of the tokens [P:] at position P.  The scheduler's decisions are those of the unshared call."""
+    refill is a prefill of the tokens [P:] at position P.  The scheduler's decisions are those of the unshared call.
+
+    return_logprobs: as in generate_batch — (out, logprobs), the same values bit for bit."""
     from .schedule import StreamScheduler
     if speculate:
         raise ValueError(f"speculate={speculate}: continuous batching steps a row list one token at a time; speculative decoding runs "
@@ -278,13 +305,19 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng = model.engine(sched.max_rows + 1, need_pos, max(P, sum(sorted(n - P for n in lens)[-prefill_batch:])), exact=True)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
-                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P)
+                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
         if end:
             end.record()
-    sched.run(be)
+    if return_logprobs:
+        eng.set_logprobs(be.logprobs)   # part of the captured steps' key; without it the call runs the steps it always ran
+    try:
+        sched.run(be)
+    finally:
+        if return_logprobs:
+            eng.set_logprobs(None)      # the buffer is this call's
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
@@ -303,16 +336,83 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         if done_h[i] == 1:
             n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
         out.append(be.tokens[i, :n])
+    if return_logprobs:
+        return out, [be.logprobs[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(N)]
     return out
 
 
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
-             top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0) -> torch.Tensor:
-    """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch."""
+             top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False):
+    """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
+    result is (ids, logprobs), logprobs as generate_batch's for the one sequence."""
     T = idx.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
-    return generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                          speculate=speculate)[0]
+    res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
+                         speculate=speculate, return_logprobs=return_logprobs)
+    return (res[0][0], res[1][0]) if return_logprobs else res[0]
+
+
+@torch.inference_mode()
+def score_batch(model: GPT, prompts: Sequence[torch.Tensor], continuations: Sequence[torch.Tensor], *,
+                max_tokens: Optional[int] = None) -> List[torch.Tensor]:
+    """Teacher-forced scoring: result[i] is a 1-D float32 tensor with the log-probability of every token of continuations[i] given
+    prompts[i] and the continuation's tokens before it (both 1-D int64, len(prompt) >= 1, the continuation non-empty) — the values
+    generate_batch(return_logprobs=True) reports for the tokens it produces, by the same definition (ops.token_logprobs), so a
+    generated answer and given hypotheses compare on one scale.  The prompt-phase kernels compute the logits here and the decode
+    kernels there: the two agree as closely as those kernel families do, not bit for bit.
+
+    prompt + continuation[:-1] of several sequences are packed into one prompt-phase forward with the logits of every row, in groups
+    of whole sequences whose token count fits max_tokens (default: what 64 MB of bf16 logits hold; a longer single sequence goes
+    alone); a sequence's values do not depend on the grouping.  The head runs on the prompt rows too — a head restricted to the
+    rows that predict the continuation is left for later."""
+    N = len(prompts)
+    if N == 0 or len(continuations) != N:
+        raise ValueError(f"score_batch takes as many continuations as prompts, at least one ({N} prompts, {len(continuations)} continuations)")
+    dev = model.transformer.wte.weight.device
+    V = model.config.padded_vocab_size
+    seqs, plen = [], []
+    for i, (p, c) in enumerate(zip(prompts, continuations)):
+        p, c = p.reshape(-1), c.reshape(-1)
+        if p.dtype != torch.int64 or c.dtype != torch.int64:
+            raise TypeError(f"sequence {i}: prompts and continuations are int64 tensors, got {p.dtype} and {c.dtype}")
+        if p.numel() < 1 or c.numel() < 1:
+            raise ValueError(f"sequence {i}: a prompt of at least one token and a non-empty continuation are needed, "
+                             f"got {p.numel()} and {c.numel()} tokens")
+        if p.numel() + c.numel() - 1 > model.max_seq_length:
+            raise NotImplementedError(f"sequence {i}: {p.numel() + c.numel() - 1} positions, max_seq_length is {model.max_seq_length}")
+        seqs.append((p.to(dev), c.to(dev)))
+        plen.append(int(p.numel()))
+    lo, hi = (int(v) for v in torch.aminmax(torch.cat([c for _, c in seqs])))      # one read-back for the whole call
+    if lo < 0 or hi >= V:
+        raise ValueError(f"continuation ids span [{lo}, {hi}], outside [0, {V})")
+    rows = [int(p.numel() + c.numel() - 1) for p, c in seqs]
+    if max_tokens is None:
+        max_tokens = max(1, (64 << 20) // (2 * V))
+    groups, cur = [], []
+    for i in range(N):      # whole sequences, in order
+        if cur and sum(rows[j] for j in cur) + rows[i] > max_tokens:
+            groups.append(cur)
+            cur = []
+        cur.append(i)
+    groups.append(cur)
+    eng = model.engine(max(len(g) for g in groups), max(rows), max(sum(rows[j] for j in g) for g in groups))
+    eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
+    out: List[Optional[torch.Tensor]] = [None] * N
+    for g in groups:
+        packed = torch.cat([torch.cat([seqs[j][0], seqs[j][1][:-1]]) for j in g])
+        # a group of one-token sequences alone is still a prompt forward (the engine would take it for a decode step)
+        la = eng.forward_slots(packed, [rows[j] for j in g], list(range(len(g))), prompt_phase=True, want_all=True)
+        start = 0
+        pick, ids = [], []
+        for j in g:         # row plen - 1 + k of the sequence predicts continuation token k
+            pick.append(torch.arange(start + plen[j] - 1, start + rows[j], device=dev))
+            ids.append(seqs[j][1])
+            start += rows[j]
+        lp = ops.token_logprobs(la[torch.cat(pick)], torch.cat(ids), check_ids=False)     # checked above
+        for j, v in zip(g, lp.split([int(seqs[j][1].numel()) for j in g])):
+            out[j] = v
+    model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
+    return out

@@ -385,6 +385,7 @@ class _Engine:
 
     def decode(self, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, n_steps: int, temperature: float,
                top_k: Optional[int], eos_id: Optional[int], seed: int, first_step: int = 0) -> None:
+        self._check_logprobs(tokens)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_decode(
                 self.handle, tokens.data_ptr(), tokens.size(1), length.data_ptr(), done.data_ptr(), tokens.size(0),
@@ -393,19 +394,20 @@ class _Engine:
                 torch.cuda.current_stream().cuda_stream))
 
     def forward_slots(self, ids: torch.Tensor, seq_len: List[int], slots: List[int], prompt_phase: bool = False,
-                      pos0: int = 0) -> torch.Tensor:
+                      pos0: int = 0, want_all: bool = False) -> torch.Tensor:
         """Prompt forward of sequence i into KV slot slots[i], its tokens at positions pos0.. (0: whole prompts; P: what follows
         a shared prefix that copy_prefix has put into the slots): the last positions' logits (dh_engine_forward_slots).
-        prompt_phase: prefill kernels even when every sequence has one token."""
+        prompt_phase: prefill kernels even when every sequence has one token.
+        want_all: the logits of every packed row, [sum(seq_len), vocab], instead of the last positions'."""
         n = len(seq_len)
         ids = ids.reshape(-1)
         assert len(slots) == n and ids.numel() == int(sum(seq_len)) and ids.dtype == torch.int64 and ids.is_cuda
         ids = ids.contiguous()
-        ll = torch.empty((n, self.vocab), dtype=torch.bfloat16, device=self.device)
+        ll = torch.empty((ids.numel() if want_all else n, self.vocab), dtype=torch.bfloat16, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_forward_slots(self.handle, ids.data_ptr(), (C.c_int32 * n)(*seq_len), (C.c_int32 * n)(*([int(pos0)] * n)),
-                                                        (C.c_int32 * n)(*slots), n, int(prompt_phase), None, ll.data_ptr(),
-                                                        torch.cuda.current_stream().cuda_stream))
+                                                        (C.c_int32 * n)(*slots), n, int(prompt_phase), ll.data_ptr() if want_all else None,
+                                                        None if want_all else ll.data_ptr(), torch.cuda.current_stream().cuda_stream))
         return ll
 
     def copy_prefix(self, src_slot: int, dst_slots: List[int], n_pos: int) -> None:
@@ -428,6 +430,7 @@ class _Engine:
         """n_steps decode steps over the first n_rows entries of row_arrays() (dh_engine_decode_rows)."""
         row_seq, row_slot = self.row_arrays()
         assert 0 < n_rows <= self.max_batch and length.numel() == done.numel() == limit.numel() == tokens.size(0)
+        self._check_logprobs(tokens)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_decode_rows(
                 self.handle, tokens.data_ptr(), tokens.size(1), length.data_ptr(), done.data_ptr(), limit.data_ptr(), tokens.size(0),
@@ -447,11 +450,24 @@ class _Engine:
         B = tokens.size(0)
         assert length.numel() == done.numel() == limit.numel() == B and counters.numel() >= 3 and counters.dtype == torch.int32
         assert drafts is None or (drafts.dtype == torch.int64 and drafts.is_contiguous() and tuple(drafts.shape) == (B, int(max_new_tokens)))
+        self._check_logprobs(tokens)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_decode_spec(
                 self.handle, tokens.data_ptr(), tokens.size(1), length.data_ptr(), done.data_ptr(), limit.data_ptr(), B,
                 int(max_new_tokens), int(n_draft), None if drafts is None else drafts.data_ptr(), counters.data_ptr(), int(n_steps),
                 float(temperature), -1 if eos_id is None else int(eos_id), int(first_step), torch.cuda.current_stream().cuda_stream))
+
+    def set_logprobs(self, buf: Optional[torch.Tensor]) -> None:
+        """The float32 buffer, shaped like the decode calls' `tokens`, that later decode / decode_rows / decode_spec calls write each
+        appended token's log-probability into (dh_engine_set_logprobs); None turns it off.  The caller keeps it alive while set."""
+        if buf is not None and (buf.dtype != torch.float32 or not buf.is_cuda or not buf.is_contiguous() or buf.dim() != 2):
+            raise TypeError("set_logprobs takes a contiguous 2-D float32 tensor on the GPU, or None")
+        self._logprobs = buf
+        _lib.check(self.lib.dh_engine_set_logprobs(self.handle, None if buf is None else buf.data_ptr()))
+
+    def _check_logprobs(self, tokens: torch.Tensor) -> None:
+        buf = getattr(self, "_logprobs", None)
+        assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"
 
     def graph_count(self, n_draft: int = -1) -> int:
         """Captured decode steps kept for n_draft drafts (0: the plain steps, -1: all)."""

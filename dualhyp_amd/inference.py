@@ -50,16 +50,25 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                   device="cpu") -> Dict[str, Any]:
     """examples[i] needs 'input_ids_no_response' (1-D ids) and 'ground_truth'.  `generate_fn` maps a
     list of prompts to a list of prompt+continuation id tensors (dualhyp_amd.generate_batch bound to a
-    model; a stub in the CPU tests).  Returns corpus metrics on every rank and predictions on rank 0."""
+    model; a stub in the CPU tests), or to the pair (that list, a list of 1-D float tensors with the log-probability of every
+    generated token, the EOS included: generate_batch(return_logprobs=True)); with the pair every prediction record gains
+    'sum_logprob' and 'avg_logprob' (the mean over those tokens).  Returns corpus metrics on every rank and predictions on rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
     for b in range(0, len(mine), batch_size):
         idxs = mine[b:b + batch_size]
         prompts = [examples[i]["input_ids_no_response"] for i in idxs]
         outs = generate_fn(prompts)
-        for i, p, o in zip(idxs, prompts, outs):
+        lps = None
+        if isinstance(outs, tuple):
+            outs, lps = outs
+        for k, (i, p, o) in enumerate(zip(idxs, prompts, outs)):
             preds[i] = {"inference": extract_answer(decode(o), decode(p)),
                         "ground_truth": examples[i]["ground_truth"].strip()}
+            if lps is not None:
+                total = float(lps[k].double().sum())
+                preds[i]["sum_logprob"] = total
+                preds[i]["avg_logprob"] = total / max(int(lps[k].numel()), 1)
     order = sorted(preds)
     pr = [preds[i]["inference"] for i in order]
     gt = [preds[i]["ground_truth"] for i in order]
@@ -214,16 +223,20 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     continuous = getattr(args, "schedule", "batch") == "continuous"
     share = "auto" if getattr(args, "share_prefix", "off") == "auto" else False
     spec = int(getattr(args, "speculate", 0) or 0)
+    want_lp = bool(getattr(args, "logprobs", False))
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
-                                   share_prefix=share, speculate=spec)
-            return [o.cpu() for o in outs]
-        outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
-                              prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec)
+                                   share_prefix=share, speculate=spec, return_logprobs=want_lp)
+        else:
+            outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
+                                  prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
+                                  return_logprobs=want_lp)
+        if want_lp:
+            return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]]
         return [o.cpu() for o in outs]
 
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world,
@@ -291,6 +304,10 @@ def build_parser():
     p.add_argument("--kv_cache", choices=("bf16", "fp8"), default="bf16",
                    help="fp8 (with --quantize fp8): cached K and V vectors are stored as e4m3 bytes with one power-of-two exponent each, "
                         "half the cache bytes per token; the predictions are those of attention over the rounded cache")
+    p.add_argument("--logprobs", action="store_true",
+                   help="every record of the predictions file gains sum_logprob and avg_logprob: the model's log-probability of the tokens "
+                        "it generated (the EOS included; temperature 1, no top-k crop), computed inside the decode steps; the predictions "
+                        "do not depend on it.  Default off: the file is what it always was")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)

@@ -198,34 +198,73 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, vT_cache: torch.Tensor, 
     return y
 
 
+def _logprobs_buffer(logprobs: Optional[torch.Tensor], tokens: torch.Tensor) -> Optional[torch.Tensor]:
+    """The fp32 buffer beside `tokens` that the sampling kernels write in place: refused unless it is exactly that."""
+    if logprobs is None:
+        return None
+    if not logprobs.is_cuda:
+        raise _lib.DualHypHipError("logprobs must live on the GPU: the HIP path has no CPU fallback")
+    if logprobs.dtype != torch.float32:
+        raise TypeError(f"logprobs must be {torch.float32}, got {logprobs.dtype}")
+    if tuple(logprobs.shape) != tuple(tokens.shape) or not logprobs.is_contiguous():
+        raise ValueError(f"logprobs must be a contiguous {tuple(tokens.shape)} tensor like tokens, got {tuple(logprobs.shape)}")
+    return logprobs
+
+
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool = True) -> torch.Tensor:
+    """float32 [rows]: log softmax(logits[r])[ids[r]] of the raw bf16 rows (dh_token_logprobs_bf16; the definition is in
+    include/dualhyp_hip.h, "Token log-probabilities").  An id outside [0, vocab) raises before anything is launched
+    (one read-back of the ids' range; check_ids=False: the caller has checked them, as score_batch does once per call)."""
+    logits = _dev(logits, name="logits")
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
+    rows, vocab = logits.shape
+    ids = _dev(ids.reshape(-1), torch.int64, "ids")
+    if ids.numel() != rows:
+        raise ValueError(f"{ids.numel()} ids for {rows} logits rows")
+    out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if rows == 0:
+        return out
+    if check_ids:
+        lo, hi = (int(v) for v in torch.aminmax(ids))
+        if lo < 0 or hi >= vocab:
+            raise ValueError(f"token ids span [{lo}, {hi}], outside [0, {vocab})")
+    check(_lib.load().dh_token_logprobs_bf16(_p(logits), vocab, _p(ids), _p(out), rows, _stream()))
+    return out
+
+
 def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, *,
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
-           step: int = 0) -> None:
-    """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16."""
+           step: int = 0, logprobs: Optional[torch.Tensor] = None) -> None:
+    """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
+    tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_seq, vocab = logits.shape
     assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.size(0) == n_seq
-    check(_lib.load().dh_sample_bf16(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
-                                     k(done, torch.int32), n_seq, float(temperature),
-                                     0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id),
-                                     int(seed) & ((1 << 64) - 1), int(step), _stream()))
+    logprobs = _logprobs_buffer(logprobs, tokens)
+    check(_lib.load().dh_sample_bf16_ex(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
+                                        k(done, torch.int32), n_seq, float(temperature),
+                                        0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id),
+                                        int(seed) & ((1 << 64) - 1), int(step), _stream(), _p(logprobs)))
 
 
 def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor,
                 row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
-                eos_id: Optional[int] = None, seed: int = 0) -> None:
-    """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16."""
+                eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None) -> None:
+    """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs: as in sample()."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_rows, vocab = logits.shape
     n_seq = tokens.size(0)
     assert tokens.dtype == torch.int64 and tokens.is_contiguous() and row_seq.numel() == n_rows
     assert length.numel() == done.numel() == limit.numel() == n_seq
-    check(_lib.load().dh_sample_rows_bf16(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
-                                          k(done, torch.int32), k(limit, torch.int32), k(row_seq, torch.int32), n_rows, n_seq,
-                                          int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
-                                          -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream()))
+    logprobs = _logprobs_buffer(logprobs, tokens)
+    check(_lib.load().dh_sample_rows_bf16_ex(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
+                                             k(done, torch.int32), k(limit, torch.int32), k(row_seq, torch.int32), n_rows, n_seq,
+                                             int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
+                                             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(),
+                                             _p(logprobs)))
 
 
 def quant_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -26,6 +26,8 @@ extern "C" {
 
 typedef uint16_t dh_bf16;
 
+/* ABI 6 gained entries without a change to any existing one (so the number stays): dh_token_logprobs_bf16, dh_sample_bf16_ex,
+ * dh_sample_rows_bf16_ex and dh_engine_set_logprobs (token log-probabilities). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -353,6 +355,28 @@ int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int t
                         int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                         void* stream);
 
+/* Token log-probabilities.  ONE definition for every entry below: under a logits row l (bf16, vocab columns, what the sampler reads)
+ *   lp(t) = l[t] - m - log(sum_i exp(l[i] - m)),  m = max_i l[i]
+ * of the RAW row — temperature 1, no top-k crop, whatever the call samples with: the model's distribution, not the sampler's.  The
+ * bf16 values are widened to fp32, the sum and the result are fp32 (expf / logf, not the fast intrinsics).  -inf entries add 0, a
+ * -inf token gives -inf, NaN logits are not supported.  One 1024-thread block per row; thread t adds the 8-element chunks t,
+ * t + 1024, .. of the row in index order, the 1024 chains are added by a fixed butterfly: the order is a function of vocab alone, so
+ * equal row contents give equal bits at any row index, row count or address.  |lp - exact| <= 2e-5 + 2.4e-7 |lp| up to vocab 128256. */
+
+/* out[r] (fp32, [n_rows]) = lp(ids[r]) under logits row r.  ids: device int64 [n_rows]; an id outside [0, vocab) reads nothing and
+ * gives NaN (the caller checks its ids: dualhyp_amd.ops.token_logprobs raises). */
+int dh_token_logprobs_bf16(const dh_bf16* logits, int vocab, const int64_t* ids, float* out, int n_rows, void* stream);
+/* dh_sample_bf16 / dh_sample_rows_bf16 with logprobs (nullable; fp32 [n_seq, tok_ld], the shape of `tokens`): the thread that stores
+ * tokens[u, n] also stores logprobs[u, n] = lp(that token) under the row it was picked from; nothing is written where no token is
+ * appended (finished sequence, budget, buffer full).  Null: the old entries, which call these with null — the kernels they always ran. */
+int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                      int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                      uint64_t seed, int step, void* stream, float* logprobs);
+int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                           int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                           int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                           void* stream, float* logprobs);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -585,6 +609,12 @@ int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* le
  * n_seq * (n_draft + 1) rows and the KV cache stays at max_batch slots.  Growing drops the captured steps.
  * If the larger workspaces cannot be allocated the call fails and the engine keeps the ones it had. */
 int dh_engine_reserve_rows(dh_engine* e, int rows);
+/* The buffer (device fp32 [n_seq, tok_ld], the shape of `tokens`; null = off, the default) into which later dh_engine_decode,
+ * dh_engine_decode_rows and dh_engine_decode_spec calls write the log-probability of every token they append, beside the token
+ * (see "Token log-probabilities" above; a verify step's pick j is scored under its own logits row).  The pointer is part of the
+ * captured step's key: a step captured without it is never replayed with it, and the reverse, and with it off the steps hold the
+ * kernels they always held.  The caller keeps the buffer alive while it is set. */
+int dh_engine_set_logprobs(dh_engine* e, float* buf);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
