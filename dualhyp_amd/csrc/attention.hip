@@ -211,122 +211,104 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
 // leaves an (m, l, O^T) partial; attn_decode_combine_kernel merges them.
 constexpr int DEC_COLS = 16;   // padded head columns in the partials
 
+// The cache a decode step reads, passed by value: the bf16 fragment caches, or the fp8 bytes and their exponents (common.h k8_off /
+// v8_off; written by kv8.hip).  A DecodeTile owns exactly what differs between the two: where a tile lives, how it is loaded, and where
+// the A operands of the two MFMAs come from.  Everything else is attn_decode_kernel, once.
+struct CacheBf16 {
+    const bf16_t *k, *vT;
+};
+struct CacheFp8 {
+    const uint8_t *k8, *v8;
+    const int8_t *k_exp, *v_exp;
+};
+
+template <int HS, class Cache>
+struct DecodeTile;
+
+// one 32-key tile = 8 coalesced 1-KiB loads that ARE the MFMA fragments (K: KS x 16 B, V^T: DT x 2 x 2 x 8 B per lane)
 template <int HS>
-__global__ __launch_bounds__(256) void attn_decode_kernel(
-    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_cache, const bf16_t* __restrict__ vT_cache,
-    const int32_t* __restrict__ seq_slot, const int32_t* __restrict__ kv_len, float* __restrict__ work,
-    int n_head, int n_groups, int s_max, float scale) {
-    constexpr int KS = HS / 16, DT = HS / 32;
-    const int pair = blockIdx.x, seq = pair / n_groups, g = pair % n_groups;
-    const int nw = gridDim.y * 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wg = blockIdx.y * 4 + wave;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int q_per_kv = n_head / n_groups;
-    const int slot = seq_slot[seq], len = kv_len[seq];
-    const int n_tiles = (len + 31) / 32;
+struct DecodeTile<HS, CacheBf16> {
+    static constexpr int KS = HS / 16, DT = HS / 32;
+    struct VF { bf16x8 v; };
+    struct VScales {};
+    const bf16_t *kbase, *vbase;
+    bf16x8 kf[KS];
+    VF vf[DT][2];
 
-    bf16x8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (lr < q_per_kv)
-            z = *reinterpret_cast<const bf16x8*>(q + ((size_t)seq * n_head + g * q_per_kv + lr) * HS + ks * 16 + lh * 8);
-        qf[ks] = z;
-    }
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-    const bf16_t* kbase = k_cache + ((size_t)slot * n_groups + g) * s_max * HS;
-    const bf16_t* vbase = vT_cache + ((size_t)slot * n_groups + g) * HS * s_max;
-
-    for (int t = wg; t < n_tiles; t += nw) {
-        const int key0 = t * 32;
-        // issue all loads of the tile first (K: KS x 16 B, V^T: DT x 2 x 2 x 8 B per lane)
-        // one 32-key tile = 8 coalesced 1-KiB loads that ARE the MFMA fragments (keys >= len are
-        // masked below; their cache bytes are finite)
-        bf16x8 kf[KS];
+    __device__ __forceinline__ DecodeTile(const CacheBf16& c, int slot, int g, int n_groups, int s_max)
+        : kbase(c.k + ((size_t)slot * n_groups + g) * s_max * HS), vbase(c.vT + ((size_t)slot * n_groups + g) * HS * s_max) {}
+    __device__ __forceinline__ void load(int t, int lane, int lr, int lh) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
             kf[ks] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kbase + kfrag_blk<HS>(t, ks) + lane * 8));
-        struct VF { bf16x8 v; };
-        VF vf[DT][2];
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
             for (int s = 0; s < 2; ++s)
                 vf[dt][s].v = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vbase + vfrag_blk<HS>(t, dt, s) + lane * 8));
-        f32x16 st;
+    }
+    __device__ __forceinline__ bf16x8 k(int ks) const { return kf[ks]; }
+    __device__ __forceinline__ VScales v_scales(int) const { return {}; }
+    __device__ __forceinline__ bf16x8 v(int dt, int s, const VScales&) const { return vf[dt][s].v; }
+};
+
+// A tile is HS/32 + HS/32 coalesced 1-KiB loads of 16 B per lane, each holding two k-step fragments, plus 32 + 32 exponent bytes.
+// A fragment becomes bf16 in registers, e4m3 -> fp32 (v_cvt_pk_f32_fp8), times the power-of-two scale of its key, truncated to
+// bf16 — all exact, and applied to the OPERAND: the MFMAs see the values the bf16 tile reads from the expanded cache
+// (dh_kv8_expand), so the two instantiations agree bit for bit.
+template <int HS>
+struct DecodeTile<HS, CacheFp8> {
+    static constexpr int KS = HS / 16, DT = HS / 32;
+    struct VScales { float s[8]; };
+    const uint8_t *kbase, *vbase;
+    const int8_t *kebase, *vebase;
+    i32x4 kb[DT], vb[DT];
+    float ksc;               // the A row of this lane is key lr
+    uint32_t vew[2][2];      // exponents of the lane's 8 keys of k-step s: keys 16s + 4lh + 0..3, + 8
+
+    __device__ __forceinline__ DecodeTile(const CacheFp8& c, int slot, int g, int n_groups, int s_max) {
+        const size_t blk = (size_t)slot * n_groups + g;
+        kbase = c.k8 + blk * s_max * HS, vbase = c.v8 + blk * s_max * HS;
+        kebase = c.k_exp + blk * s_max, vebase = c.v_exp + blk * s_max;
+    }
+    __device__ __forceinline__ void load(int t, int lane, int lr, int lh) {
+        const int key0 = t * 32;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], st, 0, 0, 0);
-        float m_t = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key_abs = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            float s = st[r] * scale;
-            s = key_abs < len ? s : -INFINITY;
-            st[r] = s;
-            m_t = fmaxf(m_t, s);
+        for (int b = 0; b < DT; ++b) {
+            kb[b] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(kbase + kv8_blk<HS>(t, b) + lane * 16));
+            vb[b] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(vbase + kv8_blk<HS>(t, b) + lane * 16));
         }
-        m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
-        const float m_new = fmaxf(m_run, m_t);           // finite: key0 < len
-        const float alpha = __expf(m_run - m_new);
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float p = __expf(st[r] - m_new);
-            st[r] = p;
-            psum += p;
-        }
-        l_run = l_run * alpha + psum;
+        ksc = kv8_pow2(kebase[key0 + lr]);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            union { bf16x8 v; uint32_t u[4]; } pf;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pf.u[j] = pack2bf(st[8 * s + 2 * j], st[8 * s + 2 * j + 1]);
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                if (s == 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-                }
-                // keys >= len carry p == 0; the cache is zero-initialised so 0 * v stays 0
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][s].v, pf.v, o[dt], 0, 0, 0);
-            }
+            vew[s][0] = *reinterpret_cast<const uint32_t*>(vebase + key0 + 16 * s + 4 * lh);
+            vew[s][1] = *reinterpret_cast<const uint32_t*>(vebase + key0 + 16 * s + 4 * lh + 8);
         }
     }
-    // partial: [pair][wg] -> m[DEC_COLS], l[DEC_COLS], o[HS][DEC_COLS]
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    float* wp = work + ((size_t)pair * nw + wg) * (2 * DEC_COLS + HS * DEC_COLS);
-    if (lr < q_per_kv) {
-        if (lh == 0) {
-            wp[lr] = m_run;
-            wp[DEC_COLS + lr] = l_tot;
-        }
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                wp[2 * DEC_COLS + d * DEC_COLS + lr] = o[dt][r];
-            }
+    __device__ __forceinline__ bf16x8 k(int ks) const {
+        union { bf16x8 v; uint32_t u[4]; } kf;
+        const int w = (ks & 1) * 2;
+        kv8_cvt4((uint32_t)kb[ks >> 1][w], ksc, ksc, ksc, ksc, kf.u[0], kf.u[1]);
+        kv8_cvt4((uint32_t)kb[ks >> 1][w + 1], ksc, ksc, ksc, ksc, kf.u[2], kf.u[3]);
+        return kf.v;
     }
-}
+    __device__ __forceinline__ VScales v_scales(int s) const {
+        VScales vs;
+        kv8_scales4(vew[s][0], vs.s);
+        kv8_scales4(vew[s][1], vs.s + 4);
+        return vs;
+    }
+    __device__ __forceinline__ bf16x8 v(int dt, int s, const VScales& vs) const {
+        union { bf16x8 v; uint32_t u[4]; } vf;
+        kv8_cvt4((uint32_t)vb[dt][2 * s], vs.s[0], vs.s[1], vs.s[2], vs.s[3], vf.u[0], vf.u[1]);
+        kv8_cvt4((uint32_t)vb[dt][2 * s + 1], vs.s[4], vs.s[5], vs.s[6], vs.s[7], vf.u[2], vf.u[3]);
+        return vf.v;
+    }
+};
 
-// attn_decode_kernel over the fp8 KV cache (common.h k8_off / v8_off; written by kv8.hip): same grid, same tile-to-wave deal, same
-// per-tile update, same partials.  A tile is HS/32 + HS/32 coalesced 1-KiB loads of 16 B per lane, each holding two k-step
-// fragments, plus 32 + 32 exponent bytes.  A fragment becomes bf16 in registers, e4m3 -> fp32 (v_cvt_pk_f32_fp8), times the
-// power-of-two scale of its key, truncated to bf16 — all exact, and applied to the OPERAND: the MFMAs see the values the bf16
-// kernel reads from the expanded cache (dh_kv8_expand), so the two kernels agree bit for bit.
-template <int HS>
-__global__ __launch_bounds__(256) void attn_decode_kv8_kernel(
-    const bf16_t* __restrict__ q, const uint8_t* __restrict__ k8, const uint8_t* __restrict__ v8, const int8_t* __restrict__ k_exp,
-    const int8_t* __restrict__ v_exp, const int32_t* __restrict__ seq_slot, const int32_t* __restrict__ kv_len,
+template <int HS, class Cache>
+__global__ __launch_bounds__(256) void attn_decode_kernel(
+    const bf16_t* __restrict__ q, const Cache cache, const int32_t* __restrict__ seq_slot, const int32_t* __restrict__ kv_len,
     float* __restrict__ work, int n_head, int n_groups, int s_max, float scale) {
     constexpr int KS = HS / 16, DT = HS / 32;
     const int pair = blockIdx.x, seq = pair / n_groups, g = pair % n_groups;
@@ -351,37 +333,17 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-    const size_t blk = (size_t)slot * n_groups + g;
-    const uint8_t *kbase = k8 + blk * s_max * HS, *vbase = v8 + blk * s_max * HS;
-    const int8_t *kebase = k_exp + blk * s_max, *vebase = v_exp + blk * s_max;
+    DecodeTile<HS, Cache> tile(cache, slot, g, n_groups, s_max);
 
     for (int t = wg; t < n_tiles; t += nw) {
         const int key0 = t * 32;
-        // all loads of the tile first (keys >= len are masked below; their bytes and exponents are finite values)
-        i32x4 kb[DT], vb[DT];
-#pragma unroll
-        for (int b = 0; b < DT; ++b) {
-            kb[b] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(kbase + kv8_blk<HS>(t, b) + lane * 16));
-            vb[b] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(vbase + kv8_blk<HS>(t, b) + lane * 16));
-        }
-        const float ksc = kv8_pow2(kebase[key0 + lr]);      // the A row of this lane is key lr
-        uint32_t vew[2][2];                                  // exponents of the lane's 8 keys of k-step s: keys 16s + 4lh + 0..3, + 8
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            vew[s][0] = *reinterpret_cast<const uint32_t*>(vebase + key0 + 16 * s + 4 * lh);
-            vew[s][1] = *reinterpret_cast<const uint32_t*>(vebase + key0 + 16 * s + 4 * lh + 8);
-        }
+        // issue all loads of the tile first (keys >= len are masked below; their cache bytes, and exponents, are finite)
+        tile.load(t, lane, lr, lh);
         f32x16 st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            union { bf16x8 v; uint32_t u[4]; } kf;
-            const int w = (ks & 1) * 2;
-            kv8_cvt4((uint32_t)kb[ks >> 1][w], ksc, ksc, ksc, ksc, kf.u[0], kf.u[1]);
-            kv8_cvt4((uint32_t)kb[ks >> 1][w + 1], ksc, ksc, ksc, ksc, kf.u[2], kf.u[3]);
-            st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.v, qf[ks], st, 0, 0, 0);
-        }
+        for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tile.k(ks), qf[ks], st, 0, 0, 0);
         float m_t = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -408,20 +370,15 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(
             union { bf16x8 v; uint32_t u[4]; } pf;
 #pragma unroll
             for (int j = 0; j < 4; ++j) pf.u[j] = pack2bf(st[8 * s + 2 * j], st[8 * s + 2 * j + 1]);
-            float vs[8];
-            kv8_scales4(vew[s][0], vs);
-            kv8_scales4(vew[s][1], vs + 4);
+            const auto vs = tile.v_scales(s);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 if (s == 0) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
                 }
-                union { bf16x8 v; uint32_t u[4]; } vf;
-                kv8_cvt4((uint32_t)vb[dt][2 * s], vs[0], vs[1], vs[2], vs[3], vf.u[0], vf.u[1]);
-                kv8_cvt4((uint32_t)vb[dt][2 * s + 1], vs[4], vs[5], vs[6], vs[7], vf.u[2], vf.u[3]);
                 // keys >= len carry p == 0; the cache is zero-initialised so 0 * v stays 0
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf.v, pf.v, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tile.v(dt, s, vs), pf.v, o[dt], 0, 0, 0);
             }
         }
     }
@@ -467,6 +424,30 @@ __global__ void attn_decode_combine_kernel(const float* __restrict__ work, bf16_
 
 constexpr int DEC_NSPLIT = 4;
 
+// the split-KV kernel over either cache, then the combine: the checks the two entries share (`name` is the entry's), the grid, the
+// head-size dispatch
+template <class Cache>
+int attn_decode_launch(const char* name, const Cache cache, const dh_bf16* q, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* y,
+                       void* work, int n_seq, int n_head, int n_groups, int hs, int s_max, void* stream) {
+    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DEC_COLS, "%s: bad head counts", name);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "%s: head_size %d unsupported", name, hs);
+    DH_CHECK(work != nullptr, "%s: null workspace", name);
+    if (n_seq <= 0) return 0;
+    const int pairs = n_seq * n_groups;
+    const float scale = 1.0f / sqrtf((float)hs);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(pairs, DEC_NSPLIT), block(256);
+    dispatch_hs(hs, [&](auto hs_c) {
+        constexpr int HS = decltype(hs_c)::value;
+        hipLaunchKernelGGL((attn_decode_kernel<HS, Cache>), grid, block, 0, s, q, cache, seq_slot, kv_len, (float*)work, n_head, n_groups,
+                           s_max, scale);
+        hipLaunchKernelGGL((attn_decode_combine_kernel<HS>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head, n_groups,
+                           DEC_NSPLIT * 4);
+    });
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int dh_attn_prefill_bf16(const dh_bf16* q, const dh_bf16* k_cache, const dh_bf16* vT_cache,
@@ -481,15 +462,11 @@ extern "C" int dh_attn_prefill_bf16(const dh_bf16* q, const dh_bf16* k_cache, co
     dim3 grid(cdiv(max_q_len, 32), n_groups, n_seq), block(64 * (n_head / n_groups));
     const float scale = 1.0f / sqrtf((float)hs);
     hipStream_t s = (hipStream_t)stream;
-    if (hs == 64)
-        hipLaunchKernelGGL((attn_prefill_kernel<64, true>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len,   // scale = 1/8
-                           kv_pos0, y, lse, n_head, n_groups, s_max, scale);
-    else if (hs == 96)   // 1/sqrt(96) is not a power of two: scaled per score, as at 128
-        hipLaunchKernelGGL((attn_prefill_kernel<96>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len,
-                           kv_pos0, y, lse, n_head, n_groups, s_max, scale);
-    else
-        hipLaunchKernelGGL((attn_prefill_kernel<128>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len,
-                           kv_pos0, y, lse, n_head, n_groups, s_max, scale);
+    dispatch_hs(hs, [&](auto hs_c) {   // head size 64: scale = 1/8, applied to Q; 1/sqrt(96) is not a power of two: scaled per score, as at 128
+        constexpr int HS = decltype(hs_c)::value;
+        hipLaunchKernelGGL((attn_prefill_kernel<HS, HS == 64>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len, kv_pos0, y,
+                           lse, n_head, n_groups, s_max, scale);
+    });
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -503,59 +480,16 @@ extern "C" int64_t dh_attn_decode_work_bytes(int n_seq, int n_head, int hs, int 
 extern "C" int dh_attn_decode_bf16(const dh_bf16* q, const dh_bf16* k_cache, const dh_bf16* vT_cache,
                                    const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* y, void* work, int n_seq,
                                    int n_head, int n_groups, int hs, int s_max, void* stream) {
-    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DEC_COLS, "dh_attn_decode_bf16: bad head counts");
-    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_bf16: head_size %d unsupported", hs);
     DH_CHECK(s_max % 64 == 0, "dh_attn_decode_bf16: s_max must be a multiple of 64");
-    DH_CHECK(work != nullptr, "dh_attn_decode_bf16: null workspace");
-    if (n_seq <= 0) return 0;
-    const int pairs = n_seq * n_groups;
-    const float scale = 1.0f / sqrtf((float)hs);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(pairs, DEC_NSPLIT), block(256);
-    if (hs == 64) {
-        hipLaunchKernelGGL((attn_decode_kernel<64>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, kv_len,
-                           (float*)work, n_head, n_groups, s_max, scale);
-        hipLaunchKernelGGL((attn_decode_combine_kernel<64>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head,
-                           n_groups, DEC_NSPLIT * 4);
-    } else if (hs == 96) {
-        hipLaunchKernelGGL((attn_decode_kernel<96>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, kv_len,
-                           (float*)work, n_head, n_groups, s_max, scale);
-        hipLaunchKernelGGL((attn_decode_combine_kernel<96>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head,
-                           n_groups, DEC_NSPLIT * 4);
-    } else {
-        hipLaunchKernelGGL((attn_decode_kernel<128>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, kv_len,
-                           (float*)work, n_head, n_groups, s_max, scale);
-        hipLaunchKernelGGL((attn_decode_combine_kernel<128>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head,
-                           n_groups, DEC_NSPLIT * 4);
-    }
-    DH_LAUNCH_CHECK();
-    return 0;
+    return attn_decode_launch("dh_attn_decode_bf16", CacheBf16{k_cache, vT_cache}, q, seq_slot, kv_len, y, work, n_seq, n_head, n_groups,
+                              hs, s_max, stream);
 }
 
 extern "C" int dh_attn_decode_kv8(const dh_bf16* q, const uint8_t* k8, const uint8_t* v8, const int8_t* k_exp, const int8_t* v_exp,
                                   const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* y, void* work, int n_seq, int n_head,
                                   int n_groups, int hs, int s_max, void* stream) {
     DH_CHECK(q && k8 && v8 && k_exp && v_exp && seq_slot && kv_len && y, "dh_attn_decode_kv8: null argument");
-    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DEC_COLS, "dh_attn_decode_kv8: bad head counts");
-    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_kv8: head_size %d unsupported", hs);
     DH_CHECK(s_max > 0 && s_max % 64 == 0, "dh_attn_decode_kv8: s_max must be a multiple of 64");
-    DH_CHECK(work != nullptr, "dh_attn_decode_kv8: null workspace");
-    if (n_seq <= 0) return 0;
-    const int pairs = n_seq * n_groups;
-    const float scale = 1.0f / sqrtf((float)hs);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(pairs, DEC_NSPLIT), block(256);
-#define LAUNCH(HS_)                                                                                                          \
-    do {                                                                                                                     \
-        hipLaunchKernelGGL((attn_decode_kv8_kernel<HS_>), grid, block, 0, s, q, k8, v8, k_exp, v_exp, seq_slot, kv_len, (float*)work, \
-                           n_head, n_groups, s_max, scale);                                                                  \
-        hipLaunchKernelGGL((attn_decode_combine_kernel<HS_>), dim3(pairs), dim3(256), 0, s, (const float*)work, y, n_head, n_groups, \
-                           DEC_NSPLIT * 4);                                                                                  \
-    } while (0)
-    if (hs == 64) LAUNCH(64);
-    else if (hs == 96) LAUNCH(96);
-    else LAUNCH(128);
-#undef LAUNCH
-    DH_LAUNCH_CHECK();
-    return 0;
+    return attn_decode_launch("dh_attn_decode_kv8", CacheFp8{k8, v8, k_exp, v_exp}, q, seq_slot, kv_len, y, work, n_seq, n_head, n_groups,
+                              hs, s_max, stream);
 }

@@ -150,7 +150,30 @@ __device__ __forceinline__ size_t vfrag_off(int key, int d) {
 template <int HS> __device__ __forceinline__ size_t kfrag_blk(int t, int ks) { return (size_t)(t * (HS / 16) + ks) * 512; }
 template <int HS> __device__ __forceinline__ size_t vfrag_blk(int t, int dt, int s2) { return (size_t)((t * (HS / 32) + dt) * 2 + s2) * 512; }
 
-// ---- fp8 KV cache (kv8.hip; attention.hip attn_decode_kv8_kernel) ----------------------------
+// ---- rope of one 16-B chunk pair (ger/model.py:349-355) -------------------------------------
+// out = bf16( bf16(x*cos) + bf16(rot*sin) ), rot = [-x2, x1]: channels d0..d0+7 (o1) and HS/2 + d0..+7 (o2) of the head row `src`
+// at position pos.  Phase 1 of both cache writers (elementwise.hip, kv8.hip); what becomes of o1 / o2 is theirs.
+template <int HS>
+__device__ __forceinline__ void rope_chunk_pair(const bf16_t* src, const bf16_t* cos, const bf16_t* sin, int pos, int d0, uint4& o1, uint4& o2) {
+    constexpr int HALF = HS / 2;
+    uint4 a = *reinterpret_cast<const uint4*>(src + d0);
+    uint4 b = *reinterpret_cast<const uint4*>(src + HALF + d0);
+    uint4 c1 = *reinterpret_cast<const uint4*>(cos + (size_t)pos * HS + d0);
+    uint4 c2 = *reinterpret_cast<const uint4*>(cos + (size_t)pos * HS + HALF + d0);
+    uint4 s1 = *reinterpret_cast<const uint4*>(sin + (size_t)pos * HS + d0);
+    uint4 s2 = *reinterpret_cast<const uint4*>(sin + (size_t)pos * HS + HALF + d0);
+    const bf16_t *ap = (const bf16_t*)&a, *bp = (const bf16_t*)&b, *c1p = (const bf16_t*)&c1,
+                 *c2p = (const bf16_t*)&c2, *s1p = (const bf16_t*)&s1, *s2p = (const bf16_t*)&s2;
+    bf16_t *o1p = (bf16_t*)&o1, *o2p = (bf16_t*)&o2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float x1 = bf2f(ap[e]), x2 = bf2f(bp[e]);
+        o1p[e] = f2bf(rbf(x1 * bf2f(c1p[e])) + rbf(-x2 * bf2f(s1p[e])));
+        o2p[e] = f2bf(rbf(x2 * bf2f(c2p[e])) + rbf(x1 * bf2f(s2p[e])));
+    }
+}
+
+// ---- fp8 KV cache (kv8.hip; attention.hip DecodeTile<HS, CacheFp8>) --------------------------
 // One e4m3fn byte per element and one int8 power-of-two exponent per (slot, group, position) vector: value = e4m3 * 2^e
 // (include/dualhyp_hip.h states the scheme).  The bytes keep the 32-key tiles above, HS*32 bytes each, and a wave-wide
 // contiguous 1-KiB load is still lane i <- 16 B at i*16: a 1-KiB block packs TWO k-step fragments, 8 bytes each per lane
@@ -235,6 +258,14 @@ void dh_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// the runtime head size (which the caller has checked: 64, 96 or 128) as a compile-time constant: f(std::integral_constant<int, HS>{})
+template <class F>
+inline void dispatch_hs(int hs, F&& f) {
+    if (hs == 64) f(std::integral_constant<int, 64>{});
+    else if (hs == 96) f(std::integral_constant<int, 96>{});
+    else f(std::integral_constant<int, 128>{});
+}
 
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
 // dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability

@@ -143,22 +143,8 @@ __global__ __launch_bounds__(256) void qkv_rope_cache_kernel(
         if (t >= n_tok) continue;
         const int pos = tok_pos[t];
         const bf16_t* src = qkv + (size_t)t * row_elems + grp_off + j * HS;
-        uint4 a = *reinterpret_cast<const uint4*>(src + c * 8);
-        uint4 b = *reinterpret_cast<const uint4*>(src + HALF + c * 8);
-        uint4 c1 = *reinterpret_cast<const uint4*>(cos + (size_t)pos * HS + c * 8);
-        uint4 c2 = *reinterpret_cast<const uint4*>(cos + (size_t)pos * HS + HALF + c * 8);
-        uint4 s1 = *reinterpret_cast<const uint4*>(sin + (size_t)pos * HS + c * 8);
-        uint4 s2 = *reinterpret_cast<const uint4*>(sin + (size_t)pos * HS + HALF + c * 8);
-        const bf16_t *ap = (const bf16_t*)&a, *bp = (const bf16_t*)&b, *c1p = (const bf16_t*)&c1,
-                     *c2p = (const bf16_t*)&c2, *s1p = (const bf16_t*)&s1, *s2p = (const bf16_t*)&s2;
         uint4 o1, o2;
-        bf16_t *o1p = (bf16_t*)&o1, *o2p = (bf16_t*)&o2;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x1 = bf2f(ap[e]), x2 = bf2f(bp[e]);
-            o1p[e] = f2bf(rbf(x1 * bf2f(c1p[e])) + rbf(-x2 * bf2f(s1p[e])));
-            o2p[e] = f2bf(rbf(x2 * bf2f(c2p[e])) + rbf(x1 * bf2f(s2p[e])));
-        }
+        rope_chunk_pair<HS>(src, cos, sin, pos, c * 8, o1, o2);
         if (j < q_per_kv) {
             bf16_t* dst = q_out + ((size_t)t * n_head + g * q_per_kv + j) * HS;
             *reinterpret_cast<uint4*>(dst + c * 8) = o1;
@@ -203,15 +189,10 @@ extern "C" int dh_qkv_rope_cache_bf16(const dh_bf16* qkv, const dh_bf16* cos, co
     if (n_tok == 0) return 0;
     dim3 grid(cdiv(n_tok, 64), n_groups), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (hs == 64)
-        hipLaunchKernelGGL((qkv_rope_cache_kernel<64>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,
+    dispatch_hs(hs, [&](auto hs_c) {   // head size 96: rope pairs (i, i + 48), six 16-B chunk pairs per head
+        hipLaunchKernelGGL((qkv_rope_cache_kernel<decltype(hs_c)::value>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,
                            k_cache, vT_cache, k_out, v_out, n_tok, n_head, n_groups, s_max);
-    else if (hs == 96)   // rope pairs (i, i + 48): six 16-B chunk pairs per head
-        hipLaunchKernelGGL((qkv_rope_cache_kernel<96>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,
-                           k_cache, vT_cache, k_out, v_out, n_tok, n_head, n_groups, s_max);
-    else
-        hipLaunchKernelGGL((qkv_rope_cache_kernel<128>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out,
-                           k_cache, vT_cache, k_out, v_out, n_tok, n_head, n_groups, s_max);
+    });
     DH_LAUNCH_CHECK();
     return 0;
 }

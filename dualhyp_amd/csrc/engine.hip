@@ -355,22 +355,44 @@ int linear_fp8(dh_engine* e, const bf16_t* w, const float* ws, bf16_t* y, int M,
 }
 
 // ---- the pieces of a layer ---------------------------------------------------------------------------------------------------
-// rope + KV-cache append of the n_tok rows of e->qkv; the rotated queries land in e->qrot
-int rope_append(dh_engine* e, bf16_t* kc, bf16_t* vtc, int n_tok, hipStream_t s) {
+// rope + append to layer l's KV cache (quantised into the fp8 cache of a kv8 engine) of the n_tok rows of e->qkv; the rotated queries
+// land in e->qrot
+int rope_append(dh_engine* e, int l, int n_tok, hipStream_t s) {
     const dh_model_desc& D = e->d;
-    return dh_qkv_rope_cache_bf16(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, kc, vtc, nullptr, nullptr, n_tok,
-                                  D.n_head, D.n_groups, D.head_size, e->s_max, s);
+    const size_t co = (size_t)l * e->cache_layer_elems, eo = (size_t)l * e->exp_layer_elems;
+    if (e->kv8)
+        return dh_qkv_rope_cache_kv8(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, e->k8 + co, e->v8 + co, e->ke + eo,
+                                     e->ve + eo, n_tok, D.n_head, D.n_groups, D.head_size, e->s_max, s);
+    return dh_qkv_rope_cache_bf16(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, e->kc + co, e->vtc + co, nullptr, nullptr,
+                                  n_tok, D.n_head, D.n_groups, D.head_size, e->s_max, s);
 }
 
-// Attention of e->qrot over one layer's cache into e->att: the split-KV kernel of a single-token step or the prefill kernel.
+// Attention of e->qrot over layer l's cache into e->att: the split-KV kernel of a single-token step or the prefill kernel.
 // last_rows (last block of a call that wants the last position's logits only, g_prune_last_layer): attention of each sequence's LAST
 // query alone (a one-row tile at position pos0 + len - 1 over the same 64-key steps as in the full call); its n_seq output rows are
 // then gathered into e->att_last and the block's input rows into e->xlast, where the block's n_seq-row second half continues.
-int attention(dh_engine* e, bf16_t* kc, bf16_t* vtc, int n_seq, int max_q_len, bool last_rows, hipStream_t s) {
+// fp8 KV cache: a single-token step runs the split-KV kernel over the fp8 cache; for a prompt the call's sequences are expanded into
+// the one-layer bf16 scratch (e->kc / e->vtc) first, positions [0, kv_pos0 + q_len), and the prefill kernel runs on that — inside the
+// prefill attention's timing class.
+int attention(dh_engine* e, int l, int n_seq, int max_q_len, bool last_rows, hipStream_t s) {
     const dh_model_desc& D = e->d;
     const int hs = D.head_size, H = D.n_head, G = D.n_groups;
     const SeqMeta m = seq_meta(e);
+    const size_t co = (size_t)l * e->cache_layer_elems, eo = (size_t)l * e->exp_layer_elems;
+    const bf16_t *kc = e->kv8 ? e->kc : e->kc + co, *vtc = e->kv8 ? e->vtc : e->vtc + co;
     int rc;
+    if (e->phase_decode) {
+        TimeScope t(e, 3, s);
+        if (e->kv8)
+            return dh_attn_decode_kv8(e->qrot, e->k8 + co, e->v8 + co, e->ke + eo, e->ve + eo, m.seq_slot, m.kv, e->att, e->dec_work, n_seq, H,
+                                      G, hs, e->s_max, s);
+        return dh_attn_decode_bf16(e->qrot, kc, vtc, m.seq_slot, m.kv, e->att, e->dec_work, n_seq, H, G, hs, e->s_max, s);
+    }
+    if (e->kv8) {
+        TimeScope t(e, 2, s);
+        if ((rc = dh_kv8_expand(e->k8 + co, e->v8 + co, e->ke + eo, e->ve + eo, m.seq_slot, m.kv, m.q_len, e->kc, e->vtc, n_seq, G, hs,
+                                e->s_max, s))) return rc;
+    }
     if (last_rows) {
         {
             TimeScope t(e, 2, s);
@@ -380,40 +402,9 @@ int attention(dh_engine* e, bf16_t* kc, bf16_t* vtc, int n_seq, int max_q_len, b
         if ((rc = gather_last_rows(e, e->att, e->att_last, n_seq, s))) return rc;
         return gather_last_rows(e, e->x, e->xlast, n_seq, s);
     }
-    if (e->phase_decode) {
-        TimeScope t(e, 3, s);
-        return dh_attn_decode_bf16(e->qrot, kc, vtc, m.seq_slot, m.kv, e->att, e->dec_work, n_seq, H, G, hs, e->s_max, s);
-    }
     TimeScope t(e, 2, s);
     return dh_attn_prefill_bf16(e->qrot, kc, vtc, m.seq_slot, m.q_start, m.q_len, m.kv, e->att, nullptr, n_seq, max_q_len, H, G, hs,
                                 e->s_max, s);
-}
-
-// The two above for an fp8 KV cache (layer l): rope + quantised append, then the split-KV kernel over the fp8 cache for a single-token
-// step; for a prompt the call's sequences are expanded into the one-layer bf16 scratch (e->kc / e->vtc) first, positions
-// [0, kv_pos0 + q_len), and the prefill kernel runs on that — inside the prefill attention's timing class.
-int rope_append_kv8(dh_engine* e, int l, int n_tok, hipStream_t s) {
-    const dh_model_desc& D = e->d;
-    return dh_qkv_rope_cache_kv8(e->qkv, D.rope_cos, D.rope_sin, e->tok_slot, e->tok_pos, e->qrot, e->k8 + (size_t)l * e->cache_layer_elems,
-                                 e->v8 + (size_t)l * e->cache_layer_elems, e->ke + (size_t)l * e->exp_layer_elems,
-                                 e->ve + (size_t)l * e->exp_layer_elems, n_tok, D.n_head, D.n_groups, D.head_size, e->s_max, s);
-}
-int attention_kv8(dh_engine* e, int l, int n_seq, int max_q_len, bool last_rows, hipStream_t s) {
-    const dh_model_desc& D = e->d;
-    const int hs = D.head_size, H = D.n_head, G = D.n_groups;
-    const SeqMeta m = seq_meta(e);
-    const uint8_t *k8 = e->k8 + (size_t)l * e->cache_layer_elems, *v8 = e->v8 + (size_t)l * e->cache_layer_elems;
-    const int8_t *ke = e->ke + (size_t)l * e->exp_layer_elems, *ve = e->ve + (size_t)l * e->exp_layer_elems;
-    if (e->phase_decode) {
-        TimeScope t(e, 3, s);
-        return dh_attn_decode_kv8(e->qrot, k8, v8, ke, ve, m.seq_slot, m.kv, e->att, e->dec_work, n_seq, H, G, hs, e->s_max, s);
-    }
-    int rc;
-    {
-        TimeScope t(e, 2, s);
-        if ((rc = dh_kv8_expand(k8, v8, ke, ve, m.seq_slot, m.kv, m.q_len, e->kc, e->vtc, n_seq, G, hs, e->s_max, s))) return rc;
-    }
-    return attention(e, e->kc, e->vtc, n_seq, max_q_len, last_rows, s);
 }
 
 // The half of a block behind the attention, in place on `rows` rows: x += proj(att), x += mlp_proj(swiglu(norm_2(x))).  Called on
@@ -485,10 +476,10 @@ int run_layers(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int max_q
                 if ((rc = lora(e, e->xn, W.attn_w, e->qkv, n_tok, e->qkv_dim, d, e->xa, 48, W.attn_lora_b, d, d + e->kv_dim, s, true)))
                     return rc;
             } else if ((rc = plain(e, e->xn, W.attn_w, e->qkv, n_tok, e->qkv_dim, d, nullptr, s, true))) return rc;
-            if ((rc = rope_append(e, kc, vtc, n_tok, s))) return rc;
+            if ((rc = rope_append(e, l, n_tok, s))) return rc;
         }
         const bool last_rows = prune_last && l == D.n_layer - 1;
-        if ((rc = attention(e, kc, vtc, n_seq, max_q_len, last_rows, s))) return rc;
+        if ((rc = attention(e, l, n_seq, max_q_len, last_rows, s))) return rc;
         if (last_rows) return post_attention(e, W, n_seq, e->att_last, e->xlast, e->xn_last, e->act_last, rtl, false, s);
         if ((rc = post_attention(e, W, n_tok, e->att, e->x, e->xn, e->act, rt, true, s))) return rc;
     }
@@ -513,14 +504,7 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
         bf16_t* kc = e->kc + (size_t)l * e->cache_layer_elems;
         bf16_t* vtc = e->vtc + (size_t)l * e->cache_layer_elems;
         if ((rc = dh_rmsnorm_quant_fp8(e->x, W.norm_1, nullptr, e->xq, e->xscale, n_tok, d, D.norm_eps, rt, s))) return rc;
-        if (e->kv8) {                     // fp8 KV cache: QKV GEMM by the phase rule, quantised append, attention over the fp8 cache
-            if ((rc = linear_fp8(e, W.attn_w, W.attn_ws, e->qkv, n_tok, e->qkv_dim, d, DH_EPI_PLAIN, nullptr, nullptr, nullptr, s, true)))
-                return rc;
-            if ((rc = rope_append_kv8(e, l, n_tok, s))) return rc;
-            const bool last_rows = prune_last && l == D.n_layer - 1;
-            if ((rc = attention_kv8(e, l, n_seq, max_q_len, last_rows, s))) return rc;
-            if (last_rows) return post_attention_fp8(e, W, n_seq, e->att_last, e->xlast, e->act_last, rtl, false, s);
-        } else if (decode && n_tok <= 128) {     // every streaming-class step (fp8_kernel above): one family, no 32-row boundary
+        if (!e->kv8 && decode && n_tok <= 128) {     // every streaming-class step over a bf16 cache (fp8_kernel above): one family, no 32-row boundary
             // one launch for rope + cache append + split-KV attention + combine (decode_fused.hip): the QKV product
             // is handed over as its single fp32 "partial" (values already rounded to bf16), no LoRA (merged)
             const SeqMeta m = seq_meta(e);
@@ -533,13 +517,13 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
             if ((rc = dh_attn_decode_fused_bf16(e->part32, 1, 0, n_seq, e->qkv_dim, 0, nullptr, 0.f, e->qkv_dim, e->qkv_dim,
                                                 D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
                                                 e->s_max, s))) return rc;
-        } else {
+        } else {   // QKV GEMM by the phase rule, (quantised) append, attention over the layer's cache
             if ((rc = linear_fp8(e, W.attn_w, W.attn_ws, e->qkv, n_tok, e->qkv_dim, d, DH_EPI_PLAIN, nullptr, nullptr, nullptr, s, true)))
                 return rc;
-            if ((rc = rope_append(e, kc, vtc, n_tok, s))) return rc;
+            if ((rc = rope_append(e, l, n_tok, s))) return rc;
             // the last block of a prompt forward that wants the last position's logits only stays on the phase's (tiled) kernel
             const bool last_rows = prune_last && l == D.n_layer - 1;
-            if ((rc = attention(e, kc, vtc, n_seq, max_q_len, last_rows, s))) return rc;
+            if ((rc = attention(e, l, n_seq, max_q_len, last_rows, s))) return rc;
             if (last_rows) return post_attention_fp8(e, W, n_seq, e->att_last, e->xlast, e->act_last, rtl, false, s);
         }
         if ((rc = post_attention_fp8(e, W, n_tok, e->att, e->x, e->act, rt, true, s))) return rc;

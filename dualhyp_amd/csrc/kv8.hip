@@ -1,5 +1,5 @@
-// fp8 KV cache of the fp8 serving path: the cache writer and the expansion back to bf16.  The reader of a decode step,
-// attn_decode_kv8_kernel, sits next to the kernel it mirrors in attention.hip.
+// fp8 KV cache of the fp8 serving path: the cache writer and the expansion back to bf16.  The reader of a decode step is
+// attn_decode_kernel over a CacheFp8 (attention.hip): the bf16 kernel's body with DecodeTile<HS, CacheFp8> as its tile.
 //
 // Scheme (include/dualhyp_hip.h, common.h): per (token, KV group) one K vector (after rope) and one V vector of head_size bf16
 // values each become head_size e4m3fn bytes and one int8 exponent e, the smallest with amax <= 448 * 2^e; byte = e4m3fn_rne(x * 2^-e).
@@ -9,8 +9,8 @@
 namespace {
 
 // ------------------------------------------------------------------------------ QKV split + RoPE + fp8 cache
-// qkv_rope_cache_kernel (elementwise.hip) with the cache writes replaced: same grid (ceil(n_tok/64), n_groups), 256 threads, same
-// rope arithmetic.  The rotated k rows and the v rows of the block's 64 tokens wait in LDS for their exponents.
+// qkv_rope_cache_kernel (elementwise.hip) with the cache writes replaced: same grid (ceil(n_tok/64), n_groups), 256 threads, the
+// same rope step (common.h rope_chunk_pair).  The rotated k rows and the v rows of the block's 64 tokens wait in LDS for their exponents.
 template <int HS>
 __global__ __launch_bounds__(256) void qkv_rope_cache_kv8_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ cos, const bf16_t* __restrict__ sin,
@@ -37,22 +37,8 @@ __global__ __launch_bounds__(256) void qkv_rope_cache_kv8_kernel(
         if (t >= n_tok) continue;
         const int pos = tok_pos[t];
         const bf16_t* src = qkv + (size_t)t * row_elems + grp_off + j * HS;
-        uint4 a = *reinterpret_cast<const uint4*>(src + c * 8);
-        uint4 b = *reinterpret_cast<const uint4*>(src + HALF + c * 8);
-        uint4 c1 = *reinterpret_cast<const uint4*>(cos + (size_t)pos * HS + c * 8);
-        uint4 c2 = *reinterpret_cast<const uint4*>(cos + (size_t)pos * HS + HALF + c * 8);
-        uint4 s1 = *reinterpret_cast<const uint4*>(sin + (size_t)pos * HS + c * 8);
-        uint4 s2 = *reinterpret_cast<const uint4*>(sin + (size_t)pos * HS + HALF + c * 8);
-        const bf16_t *ap = (const bf16_t*)&a, *bp = (const bf16_t*)&b, *c1p = (const bf16_t*)&c1,
-                     *c2p = (const bf16_t*)&c2, *s1p = (const bf16_t*)&s1, *s2p = (const bf16_t*)&s2;
         uint4 o1, o2;
-        bf16_t *o1p = (bf16_t*)&o1, *o2p = (bf16_t*)&o2;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x1 = bf2f(ap[e]), x2 = bf2f(bp[e]);
-            o1p[e] = f2bf(rbf(x1 * bf2f(c1p[e])) + rbf(-x2 * bf2f(s1p[e])));
-            o2p[e] = f2bf(rbf(x2 * bf2f(c2p[e])) + rbf(x1 * bf2f(s2p[e])));
-        }
+        rope_chunk_pair<HS>(src, cos, sin, pos, c * 8, o1, o2);
         if (j < q_per_kv) {
             bf16_t* dst = q_out + ((size_t)t * n_head + g * q_per_kv + j) * HS;
             *reinterpret_cast<uint4*>(dst + c * 8) = o1;
@@ -174,13 +160,10 @@ extern "C" int dh_qkv_rope_cache_kv8(const dh_bf16* qkv, const dh_bf16* cos, con
     if (n_tok == 0) return 0;
     dim3 grid(cdiv(n_tok, 64), n_groups), block(256);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(HS_)                                                                                                        \
-    hipLaunchKernelGGL((qkv_rope_cache_kv8_kernel<HS_>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out, k8, v8, k_exp, \
-                       v_exp, n_tok, n_head, n_groups, s_max)
-    if (hs == 64) LAUNCH(64);
-    else if (hs == 96) LAUNCH(96);
-    else LAUNCH(128);
-#undef LAUNCH
+    dispatch_hs(hs, [&](auto hs_c) {
+        hipLaunchKernelGGL((qkv_rope_cache_kv8_kernel<decltype(hs_c)::value>), grid, block, 0, s, qkv, cos, sin, tok_slot, tok_pos, q_out, k8,
+                           v8, k_exp, v_exp, n_tok, n_head, n_groups, s_max);
+    });
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -196,13 +179,10 @@ extern "C" int dh_kv8_expand(const uint8_t* k8, const uint8_t* v8, const int8_t*
     if (n_seq <= 0) return 0;
     dim3 grid(s_max / 32, n_groups, n_seq), block(256);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(HS_)                                                                                                      \
-    hipLaunchKernelGGL((kv8_expand_kernel<HS_>), grid, block, 0, s, k8, v8, k_exp, v_exp, seq_slot, kv_len, kv_extra, k_out, vT_out, \
-                       n_groups, s_max)
-    if (hs == 64) LAUNCH(64);
-    else if (hs == 96) LAUNCH(96);
-    else LAUNCH(128);
-#undef LAUNCH
+    dispatch_hs(hs, [&](auto hs_c) {
+        hipLaunchKernelGGL((kv8_expand_kernel<decltype(hs_c)::value>), grid, block, 0, s, k8, v8, k_exp, v_exp, seq_slot, kv_len, kv_extra,
+                           k_out, vT_out, n_groups, s_max);
+    });
     DH_LAUNCH_CHECK();
     return 0;
 }

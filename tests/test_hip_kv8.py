@@ -1,4 +1,4 @@
-"""GPU tests of the fp8 KV cache (csrc/kv8.hip, attn_decode_kv8_kernel in csrc/attention.hip, the kv8 mode of csrc/engine.hip).
+"""GPU tests of the fp8 KV cache (csrc/kv8.hip, attn_decode_kernel over a CacheFp8 in csrc/attention.hip, the kv8 mode of csrc/engine.hip).
 
 Op level, bit for bit: the quantising cache writer against tests/kv8_reference.py applied to what the bf16 writer cached, the
 expansion against the reference's dequantisation, and decode attention over the fp8 cache against the bf16 kernel over the
