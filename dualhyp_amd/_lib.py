@@ -75,6 +75,9 @@ SIGNATURES = {
     "dh_token_logprobs_bf16": (I, [P, I, P, P, I, P]),
     "dh_sample_bf16_ex": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P]),
     "dh_sample_rows_bf16_ex": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P]),
+    "dh_token_top_logprobs_bf16": (I, [P, I, I, P, P, I, P]),
+    "dh_sample_bf16_top": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P]),
+    "dh_sample_rows_bf16_top": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P]),
     "dh_quant_rows_fp8": (I, [P, P, P, I, I, P]),
     "dh_rmsnorm_quant_fp8": (I, [P, P, P, P, P, I, I, F, P, P]),
     "dh_linear_fp8": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
@@ -103,6 +106,7 @@ SIGNATURES = {
     "dh_engine_decode_spec": (I, [P, P, I, P, P, P, I, I, I, P, P, I, F, I64, I, P]),
     "dh_engine_reserve_rows": (I, [P, I]),
     "dh_engine_set_logprobs": (I, [P, P]),
+    "dh_engine_set_top_logprobs": (I, [P, I, P, P]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

@@ -40,6 +40,9 @@ struct dh_engine {
     int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B], read through seq_meta() below
     int32_t *last_row = nullptr, *step_dev = nullptr;
     float* logprobs = nullptr;                          // dh_engine_set_logprobs: the caller's buffer beside `tokens` (null: off)
+    int top_n = 0;                                      // dh_engine_set_top_logprobs: alternatives per token (0: off) and the
+    int32_t* top_ids = nullptr;                         // caller's [n_seq, tok_ld, top_n] buffers
+    float* top_lp = nullptr;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t** cache_tab = nullptr;                       // [2 L] device table, written once: K cache of layer l at 2l, V^T cache at 2l + 1
@@ -68,12 +71,13 @@ struct dh_engine {
         const int32_t *limit, *row_seq, *row_slot; int n_all, max_new;
         int spec; const int64_t* drafts; int32_t* counters;   // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
         float* logprobs;                                      // dh_engine_set_logprobs: a step captured without the buffer is another kernel
+        int top_n; int32_t* top_ids; float* top_lp;           // dh_engine_set_top_logprobs: likewise, and top_n is a kernel argument
         bool operator==(const GKey& k) const {
             return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
-                   logprobs == k.logprobs;
+                   logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp;
         }
     };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
@@ -860,7 +864,7 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
     if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
     return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
-                               e->step_dev, k.counters, k.logprobs, s);
+                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
 }
 
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
@@ -874,9 +878,9 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_model(e, e->dec_ids, k.n_seq, k.n_seq, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
-                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, s);
+                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
-                          e->step_dev, k.logprobs, s);
+                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1091,7 +1095,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_LAUNCH_CHECK();
     // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
-                              nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs};
+                              nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1106,7 +1110,7 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
-                              limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs};
+                              limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1153,13 +1157,23 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
-                              limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs};
+                              limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp};
     return launch_steps(e, key, n_steps, s);
 }
 
 extern "C" int dh_engine_set_logprobs(dh_engine* e, float* buf) {
     DH_CHECK(e, "dh_engine_set_logprobs: null engine");
     e->logprobs = buf;
+    return 0;
+}
+
+extern "C" int dh_engine_set_top_logprobs(dh_engine* e, int k, int32_t* ids, float* lp) {
+    DH_CHECK(e, "dh_engine_set_top_logprobs: null engine");
+    DH_CHECK(k >= 0 && k <= 8 && k <= e->d.vocab, "dh_engine_set_top_logprobs: k must be 0 .. min(8, vocab)");
+    const bool on = k > 0 && ids && lp;
+    e->top_n = on ? k : 0;
+    e->top_ids = on ? ids : nullptr;
+    e->top_lp = on ? lp : nullptr;
     return 0;
 }
 

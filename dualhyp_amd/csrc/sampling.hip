@@ -184,7 +184,8 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
 // it are read one after the other by every thread: a maximum is exact in any order.)  The 16-byte loads (vocab % 8 == 0
 // and an aligned row, as in pick_token) and the scalar loop visit the same elements in the same order, so a row's bits do not depend
 // on where it lies, and never on the row index or the row count.
-__device__ __forceinline__ float token_logprob(const bf16_t* __restrict__ lg, int vocab, int token) {
+// row_logsum: m and tot = the sum, by the whole block, every thread gets both; logprob_at: the last step; token_logprob: the two.
+__device__ __forceinline__ void row_logsum(const bf16_t* __restrict__ lg, int vocab, float& m_out, float& tot_out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float s_lp[NT / 64];
     const bool vec = (vocab & 7) == 0 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
@@ -245,29 +246,150 @@ __device__ __forceinline__ float token_logprob(const bf16_t* __restrict__ lg, in
 #pragma unroll
     for (int o = NT / 128; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
     __syncthreads();                       // s_lp is free for the next call
+    m_out = mx;
+    tot_out = tot;
+}
+
+// lp(token) from the row's m and tot: the one expression behind every log-probability this file writes
+__device__ __forceinline__ float logprob_at(const bf16_t* __restrict__ lg, int token, float mx, float tot) {
     const float lt = bf2f(lg[token]);
     if (lt == -INFINITY) return -INFINITY;
     return (lt - mx) - logf(tot);
 }
 
-template <bool LP>
+__device__ __forceinline__ float token_logprob(const bf16_t* __restrict__ lg, int vocab, int token) {
+    float mx, tot;
+    row_logsum(lg, vocab, mx, tot);
+    return logprob_at(lg, token, mx, tot);
+}
+
+constexpr int MAX_TOP = 8;     // MAX_TOP_LOGPROBS of the header
+
+// The k (1 .. min(MAX_TOP, vocab)) alternatives of one row, by the whole block: rank j is the entry at place j when the RAW row is
+// ordered by value descending, then by index ascending (-0 == +0; -inf is an ordinary value that ranks last), and its value is
+// logprob_at(lg, id_j, mx, tot) with the caller's m and tot, so it is bit-equal to token_logprob(lg, vocab, id_j).  Every thread gets
+// pointers to the k ids and values in LDS, valid until the block's next call.
+// One pass over the row: an entry's sort key is (bf16_key << 32) | ~index, unique per entry, so the order of a set of entries does
+// not depend on the order they were visited in (the 16-byte loads and the scalar loop agree) and no atomic decides anything.  Every
+// thread keeps the MAX_TOP largest keys of its own entries, sorted, in registers (0 = none: every real key is above it); k rounds of
+// a block-wide maximum over the 1024 list heads, the winner's thread popping its head, merge them.  A NaN is just a key here: ids stay
+// inside [0, vocab) as long as k <= vocab.
+__device__ __forceinline__ void row_top(const bf16_t* __restrict__ lg, int vocab, int k, float mx, float tot,
+                                        const int32_t*& ids_out, const float*& lp_out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ uint64_t s_head[2][NT / 64];
+    __shared__ uint64_t s_win[MAX_TOP];
+    __shared__ int32_t s_tid[MAX_TOP];
+    __shared__ float s_tlp[MAX_TOP];
+    uint64_t c[MAX_TOP];
+#pragma unroll
+    for (int j = 0; j < MAX_TOP; ++j) c[j] = 0;
+    auto offer = [&](bf16_t b, int i) {
+        uint64_t key = ((uint64_t)bf16_key(b) << 32) | (uint32_t)~(uint32_t)i;
+        if (key > c[MAX_TOP - 1]) {
+#pragma unroll
+            for (int j = 0; j < MAX_TOP; ++j) {                // c stays sorted: the smaller of each pair moves on
+                const uint64_t hi = key > c[j] ? key : c[j];
+                key = key > c[j] ? c[j] : key;
+                c[j] = hi;
+            }
+        }
+    };
+    if ((vocab & 7) == 0 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0) {
+        const uint4* lg4 = reinterpret_cast<const uint4*>(lg);
+        const int n4 = vocab >> 3;
+        for (int c0 = tid; c0 < n4; c0 += 4 * NT) {
+            uint4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = c0 + u * NT < n4 ? lg4[c0 + u * NT] : uint4{0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (c0 + u * NT >= n4) break;
+                const bf16_t* e8 = reinterpret_cast<const bf16_t*>(&q[u]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) offer(e8[e], (c0 + u * NT) * 8 + e);
+            }
+        }
+    } else {
+        for (int i = tid; i < vocab; i += NT) offer(lg[i], i);
+    }
+    for (int r = 0; r < k; ++r) {
+        uint64_t best = c[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t ov = __shfl_xor(best, o, 64);
+            best = ov > best ? ov : best;
+        }
+        if (lane == 0) s_head[r & 1][wave] = best;
+        __syncthreads();                   // two buffers: round r + 2 writes this one after every thread has passed round r + 1's barrier
+        best = s_head[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) best = s_head[r & 1][w] > best ? s_head[r & 1][w] : best;
+        if (c[0] == best) {                // keys are unique: one thread (best > 0 while r < vocab)
+#pragma unroll
+            for (int j = 0; j + 1 < MAX_TOP; ++j) c[j] = c[j + 1];
+            c[MAX_TOP - 1] = 0;
+        }
+        if (tid == 0) s_win[r] = best;
+    }
+    __syncthreads();
+    if (tid < k) {
+        const uint32_t i = ~(uint32_t)s_win[tid];
+        const int id = i < (uint32_t)vocab ? (int)i : 0;        // k > vocab is refused by the host; never an index outside the row
+        s_tid[tid] = id;
+        s_tlp[tid] = logprob_at(lg, id, mx, tot);
+    }
+    __syncthreads();
+    ids_out = s_tid;
+    lp_out = s_tlp;
+}
+
+// What a sampling kernel writes beside a token: LP its log-probability; TOP (with LP) the row's top_n alternatives as well, m and tot
+// computed once for both.  Every thread returns lp and, with TOP, the LDS pointers of row_top.
+template <bool LP, bool TOP>
+__device__ __forceinline__ float row_report(const bf16_t* __restrict__ lg, int vocab, int choice, int top_n,
+                                            const int32_t*& ti, const float*& tl) {
+    if constexpr (TOP) {
+        float mx, tot;
+        row_logsum(lg, vocab, mx, tot);
+        row_top(lg, vocab, top_n, mx, tot, ti, tl);
+        return logprob_at(lg, choice, mx, tot);
+    } else if constexpr (LP) {
+        return token_logprob(lg, vocab, choice);
+    }
+    return 0.f;
+}
+
+// top_ids / top_lp ([n_seq, tok_ld, top_n]) at token place `at` = u * tok_ld + n, by the thread that stores the token
+__device__ __forceinline__ void store_top(int32_t* __restrict__ top_ids, float* __restrict__ top_lp, size_t at, int top_n,
+                                          const int32_t* ti, const float* tl) {
+    for (int j = 0; j < top_n; ++j) {
+        top_ids[at * top_n + j] = ti[j];
+        top_lp[at * top_n + j] = tl[j];
+    }
+}
+
+template <bool LP, bool TOP = false>
 __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                     int64_t* __restrict__ tokens, int tok_ld,
                                                     int32_t* __restrict__ length, int32_t* __restrict__ done,
                                                     float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                                     int step_arg, const int32_t* __restrict__ step_dev,
-                                                    float* __restrict__ logprobs) {
+                                                    float* __restrict__ logprobs, int top_n,
+                                                    int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
     const int choice = pick_token(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq);
-    float lp = 0.f;
-    if constexpr (LP) lp = token_logprob(logits + (size_t)seq * vocab, vocab, choice);
+    const int32_t* ti = nullptr;
+    const float* tl = nullptr;
+    const float lp = row_report<LP, TOP>(logits + (size_t)seq * vocab, vocab, choice, top_n, ti, tl);
     if (tid == 0) {
         const int n = length[seq];
         if (n < tok_ld) {
             tokens[(size_t)seq * tok_ld + n] = choice;
             if constexpr (LP) logprobs[(size_t)seq * tok_ld + n] = lp;
+            if constexpr (TOP) store_top(top_ids, top_lp, (size_t)seq * tok_ld + n, top_n, ti, tl);
             length[seq] = n + 1;
         }
         if (eos_id >= 0 && choice == eos_id) done[seq] = 1;
@@ -280,25 +402,28 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
 // (seed, step, row) is when all sequences start together — so a sequence's ids do not depend on when or where it was scheduled.
 // limit[u] = prompt length + max_new is the sequence's own budget (done = 2 when reached).  Several padding rows may name one
 // finished sequence: they return at once.
-template <bool LP>
+template <bool LP, bool TOP = false>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                          int64_t* __restrict__ tokens, int tok_ld,
                                                          int32_t* __restrict__ length, int32_t* __restrict__ done,
                                                          const int32_t* __restrict__ limit,
                                                          const int32_t* __restrict__ row_seq, int n_seq, int max_new,
                                                          float temperature, int top_k, int64_t eos_id, uint64_t seed,
-                                                         float* __restrict__ logprobs) {
+                                                         float* __restrict__ logprobs, int top_n,
+                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
     const int step = n - (limit[u] - max_new);          // tokens generated so far
     const int choice = pick_token(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u);
-    float lp = 0.f;
-    if constexpr (LP) lp = token_logprob(logits + (size_t)blockIdx.x * vocab, vocab, choice);
+    const int32_t* ti = nullptr;
+    const float* tl = nullptr;
+    const float lp = row_report<LP, TOP>(logits + (size_t)blockIdx.x * vocab, vocab, choice, top_n, ti, tl);
     if (tid == 0) {
         if (n < lim) {
             tokens[(size_t)u * tok_ld + n] = choice;
             if constexpr (LP) logprobs[(size_t)u * tok_ld + n] = lp;
+            if constexpr (TOP) store_top(top_ids, top_lp, (size_t)u * tok_ld + n, top_n, ti, tl);
             length[u] = n + 1;
         }
         if (eos_id >= 0 && choice == eos_id) done[u] = 1;
@@ -312,13 +437,15 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
 // i = 1 .. j.  The picks are appended one by one exactly as sample_kernel appends its one: nothing behind an EOS (done = 1) or
 // behind the sequence's budget limit[u] = prompt length + max_new (done = 2), and a finished sequence is left alone.
 // counters: [0] the last step (1-based, *step_dev) at which a sequence was live, [1] drafts verified, [2] drafts appended.
-// LP: the log-probability of an appended pick_j, from its own row u * S + j, goes to logprobs beside the token.
-template <bool LP>
+// LP: the log-probability of an appended pick_j, from its own row u * S + j, goes to logprobs beside the token; TOP: that row's
+// alternatives too.
+template <bool LP, bool TOP = false>
 __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
                                                          int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
                                                          int32_t* __restrict__ done, const int32_t* __restrict__ limit,
                                                          float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
-                                                         int32_t* __restrict__ counters, float* __restrict__ logprobs) {
+                                                         int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
+                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (done[u]) return;
     int n = length[u];
@@ -333,8 +460,11 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
         prev = choice;
         if (n < lim) {                                                    // the same for every thread
             if constexpr (LP) {
-                const float lp = token_logprob(logits + ((size_t)u * S + j) * vocab, vocab, choice);
+                const int32_t* ti = nullptr;
+                const float* tl = nullptr;
+                const float lp = row_report<LP, TOP>(logits + ((size_t)u * S + j) * vocab, vocab, choice, top_n, ti, tl);
                 if (tid == 0) logprobs[(size_t)u * tok_ld + n] = lp;
+                if constexpr (TOP) if (tid == 0) store_top(top_ids, top_lp, (size_t)u * tok_ld + n, top_n, ti, tl);
             }
             if (tid == 0) tokens[(size_t)u * tok_ld + n] = choice;
             ++n;
@@ -365,18 +495,39 @@ __global__ __launch_bounds__(NT) void token_logprobs_kernel(const bf16_t* __rest
     if (threadIdx.x == 0) out[r] = lp;
 }
 
+// out_ids / out_lp[r, 0..k) = the k alternatives of logits row r
+__global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __restrict__ logits, int vocab, int k,
+                                                                int32_t* __restrict__ out_ids, float* __restrict__ out_lp) {
+    const int r = blockIdx.x;
+    const bf16_t* lg = logits + (size_t)r * vocab;
+    const int32_t* ti = nullptr;
+    const float* tl = nullptr;
+    float mx, tot;
+    row_logsum(lg, vocab, mx, tot);
+    row_top(lg, vocab, k, mx, tot, ti, tl);
+    if (threadIdx.x == 0) store_top(out_ids, out_lp, (size_t)r, k, ti, tl);
+}
+
+// the three kernels' variant for (logprobs, top_n): top_n > 0 needs the three buffers
+#define DH_PICK_VARIANT(kernel) (top_n > 0 ? kernel<true, true> : logprobs ? kernel<true> : kernel<false>)
+#define DH_CHECK_TOP(name)                                                                                                     \
+    DH_CHECK(top_n >= 0 && top_n <= MAX_TOP && top_n <= vocab, name ": top_logprobs must be 0 .. min(8, vocab)");              \
+    DH_CHECK(top_n == 0 || (logprobs && top_ids && top_lp), name ": top_logprobs needs the logprobs, top_ids and top_lp buffers")
+
 }  // namespace
 
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
-                   const int32_t* step_dev, float* logprobs, void* stream) {
+                   const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
+    DH_CHECK_TOP("dh_sample_bf16");
     DH_CHECK(temperature > 0.f, "dh_sample_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
     // logprobs null: the kernel without the log-probability pass (the code it always was)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(logprobs ? sample_kernel<true> : sample_kernel<false>), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
-                       logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs);
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
+                       logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
+                       top_ids, top_lp);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -385,7 +536,14 @@ extern "C" int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* toke
                                  int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                  int step, void* stream, float* logprobs) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, stream);
+                          nullptr, logprobs, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int dh_sample_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                  int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                  int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, stream);
 }
 
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -397,15 +555,17 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
 
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
-                        int top_k, int64_t eos_id, uint64_t seed, float* logprobs, void* stream) {
+                        int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
+                        void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
+    DH_CHECK_TOP("dh_sample_rows_bf16");
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(logprobs ? sample_rows_kernel<true> : sample_rows_kernel<false>), dim3(n_rows), dim3(NT), 0,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -415,7 +575,15 @@ extern "C" int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t*
                                       int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                       float* logprobs) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, stream);
+                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                       int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                       int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                       float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, stream);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -427,14 +595,16 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
 
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, float* logprobs, void* stream) {
+                        const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
+                        void* stream) {
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
+    DH_CHECK_TOP("spec_accept");
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(logprobs ? spec_accept_kernel<true> : spec_accept_kernel<false>), dim3(n_seq), dim3(NT), 0,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
-                       counters, logprobs);
+                       counters, logprobs, top_n, top_ids, top_lp);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -444,6 +614,17 @@ extern "C" int dh_token_logprobs_bf16(const dh_bf16* logits, int vocab, const in
     DH_CHECK(vocab > 0 && n_rows >= 0, "dh_token_logprobs_bf16: bad shape");
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(token_logprobs_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, ids, out);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_token_top_logprobs_bf16(const dh_bf16* logits, int vocab, int k, int32_t* out_ids, float* out_lp, int n_rows,
+                                          void* stream) {
+    DH_CHECK(logits && out_ids && out_lp, "dh_token_top_logprobs_bf16: null argument");
+    DH_CHECK(vocab > 0 && n_rows >= 0, "dh_token_top_logprobs_bf16: bad shape");
+    DH_CHECK(k >= 1 && k <= MAX_TOP && k <= vocab, "dh_token_top_logprobs_bf16: k must be 1 .. min(8, vocab)");
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(token_top_logprobs_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, k, out_ids, out_lp);
     DH_LAUNCH_CHECK();
     return 0;
 }

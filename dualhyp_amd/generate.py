@@ -43,6 +43,22 @@ def _shared_prefix(model: GPT, prompts: Sequence[torch.Tensor], share_prefix: Un
     return shared_prefix_len([p.to(dev).reshape(-1) for p in prompts])
 
 
+def _check_top_logprobs(model: GPT, top_logprobs, return_logprobs: bool) -> int:
+    """K of a call (0: off), refused before anything is launched: an int in 0 .. min(8, vocab), and K > 0 only beside return_logprobs."""
+    K = ops.check_top_logprobs(top_logprobs)
+    if K:
+        ops.check_top_logprobs(K, model.config.padded_vocab_size)
+    if K and not return_logprobs:
+        raise ValueError(f"top_logprobs={K} needs return_logprobs=True: the alternatives are returned beside the tokens' own log-probabilities")
+    return K
+
+
+def _top_buffers(shape, K: int, dev):
+    """The alternatives' buffers beside a token buffer of `shape`: ids -1 and values NaN where no token was produced."""
+    return (torch.full(tuple(shape) + (K,), -1, dtype=torch.int32, device=dev),
+            torch.full(tuple(shape) + (K,), float("nan"), dtype=torch.float32, device=dev))
+
+
 def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: Sequence[int]) -> None:
     """The call's first P tokens through the layers once, into KV slot `slot` (a prompt-phase forward, no logits), and their K / V
     of every layer from there into other_slots."""
@@ -56,7 +72,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
                    share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
-                   return_logprobs: bool = False):
+                   return_logprobs: bool = False, top_logprobs: int = 0):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -84,9 +100,17 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     log-probabilities"), written by the sampling kernels into a NaN-filled float32 buffer beside the token buffer
     (state["logprobs"]): the first token's by the prefill's sample call, the others inside the captured decode steps.  Ids, steps
     and read-backs are those of the call without the flag; the values do not depend on the schedule (speculate, share_prefix,
-    generate_stream)."""
+    generate_stream).
+
+    top_logprobs=K (1..8, with return_logprobs): the call returns (out, logprobs, top[, state]); top[i] = (ids [n_i, K] int32,
+    lp [n_i, K] float32), aligned with logprobs[i]: at every produced token, the EOS included, the K most probable tokens of the
+    raw logits row it was picked from — by value descending, then by index ascending (-0 == +0) — and their log-probabilities by
+    the definition above, sharing its m and its sum (include/dualhyp_hip.h, "Token alternatives").  Written by the same kernels
+    into [B, tok_ld, K] buffers filled with -1 / NaN (state["top_ids"], state["top_logprobs"]).  Ids, logprobs, steps and
+    read-backs are those of the call without it."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
+    K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     D = _check_speculate(model, speculate, top_k, B)
     if drafts is not None and (D == 0 or drafts.dtype != torch.int64 or tuple(drafts.shape) != (B, max_new_tokens)):
         raise ValueError(f"drafts goes with speculate > 0 and is a [{B}, {max_new_tokens}] int64 tensor")
@@ -113,6 +137,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         tokens = torch.nn.functional.pad(tokens, (0, tok_ld - tokens.size(1)))
     tokens = tokens.contiguous()
     lp_buf = torch.full((B, tok_ld), float("nan"), dtype=torch.float32, device=dev) if return_logprobs else None
+    top_buf = _top_buffers((B, tok_ld), K, dev) if K else None
     if D:   # lengths, flags and the three counters side by side: one read-back
         state = torch.cat([torch.tensor(lens, dtype=torch.int32), torch.zeros(B + 3, dtype=torch.int32)]).to(dev)
         length, done, counters = state[:B], state[B:2 * B], state[2 * B:]
@@ -134,11 +159,14 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], list(range(a, b)), prompt_phase=True, pos0=P)
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
-    ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf)
+    ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
+               top_logprobs=top_buf)
     if ev:
         ev[1].record()
     if lp_buf is not None:
         eng.set_logprobs(lp_buf)        # part of the captured step's key; without it the call runs the steps it always ran
+    if top_buf is not None:
+        eng.set_top_logprobs(*top_buf)  # likewise
     try:
         steps_run = 0
         if max_new_tokens > 1:
@@ -169,6 +197,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     finally:
         if lp_buf is not None:
             eng.set_logprobs(None)      # the buffer is this call's
+        if top_buf is not None:
+            eng.set_top_logprobs(None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -197,10 +227,14 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     res = (out,)
     if return_logprobs:                 # views too: what was produced, the EOS included
         res += ([lp_buf[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(B)],)
+    if K:
+        res += ([tuple(t[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for t in top_buf) for i in range(B)],)
     if return_state:
         st = dict(tokens=tokens, length=length, done=done)
         if return_logprobs:
             st["logprobs"] = lp_buf
+        if K:
+            st["top_ids"], st["top_logprobs"] = top_buf
         if D and steps_run:             # the last verify step's drafts and the lengths they were proposed from
             st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
         res += (st,)
@@ -211,7 +245,7 @@ class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
-                 logprobs: bool = False) -> None:
+                 logprobs: bool = False, top_logprobs: int = 0) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -227,6 +261,7 @@ class _StreamBackend:
         self.done[N] = 2
         # beside `tokens`: the log-probability of every sampled token (generate_batch's return_logprobs), NaN where none was
         self.logprobs = torch.full(tuple(self.tokens.shape), float("nan"), dtype=torch.float32, device=dev) if logprobs else None
+        self.top = _top_buffers(self.tokens.shape, top_logprobs, dev) if top_logprobs else None   # generate_batch's top_logprobs
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -248,7 +283,7 @@ class _StreamBackend:
         # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
-                        self.max_new, logprobs=self.logprobs, **self.kw)
+                        self.max_new, logprobs=self.logprobs, top_logprobs=self.top, **self.kw)
         if end:
             end.record()
 
@@ -272,7 +307,8 @@ class _StreamBackend:
 def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
-                    share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False):
+                    share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
+                    top_logprobs: int = 0):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -287,8 +323,9 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     hands out before the first prefill; no sequence of the call writes below position P, so they outlive every refill, and a
     refill is a prefill of the tokens [P:] at position P.  The scheduler's decisions are those of the unshared call.
 
-    return_logprobs: as in generate_batch — (out, logprobs), the same values bit for bit."""
+    return_logprobs, top_logprobs: as in generate_batch — (out, logprobs[, top]), the same values bit for bit."""
     from .schedule import StreamScheduler
+    K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     if speculate:
         raise ValueError(f"speculate={speculate}: continuous batching steps a row list one token at a time; speculative decoding runs "
                          "under generate_batch (--schedule batch) only")
@@ -305,7 +342,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng = model.engine(sched.max_rows + 1, need_pos, max(P, sum(sorted(n - P for n in lens)[-prefill_batch:])), exact=True)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
-                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs)
+                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
+                        top_logprobs=K)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -313,11 +351,15 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             end.record()
     if return_logprobs:
         eng.set_logprobs(be.logprobs)   # part of the captured steps' key; without it the call runs the steps it always ran
+    if K:
+        eng.set_top_logprobs(*be.top)
     try:
         sched.run(be)
     finally:
         if return_logprobs:
             eng.set_logprobs(None)      # the buffer is this call's
+        if K:
+            eng.set_top_logprobs(None)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
@@ -337,27 +379,35 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
         out.append(be.tokens[i, :n])
     if return_logprobs:
-        return out, [be.logprobs[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(N)]
+        res = (out, [be.logprobs[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(N)])
+        if K:
+            res += ([tuple(t[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for t in be.top) for i in range(N)],)
+        return res
     return out
 
 
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
-             top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False):
+             top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
+             top_logprobs: int = 0):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
-    result is (ids, logprobs), logprobs as generate_batch's for the one sequence."""
+    result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
+    top values))."""
+    _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                         speculate=speculate, return_logprobs=return_logprobs)
+                         speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs)
+    if top_logprobs:
+        return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]
 
 
 @torch.inference_mode()
 def score_batch(model: GPT, prompts: Sequence[torch.Tensor], continuations: Sequence[torch.Tensor], *,
-                max_tokens: Optional[int] = None) -> List[torch.Tensor]:
+                max_tokens: Optional[int] = None, top_logprobs: int = 0):
     """Teacher-forced scoring: result[i] is a 1-D float32 tensor with the log-probability of every token of continuations[i] given
     prompts[i] and the continuation's tokens before it (both 1-D int64, len(prompt) >= 1, the continuation non-empty) — the values
     generate_batch(return_logprobs=True) reports for the tokens it produces, by the same definition (ops.token_logprobs), so a
@@ -367,7 +417,14 @@ def score_batch(model: GPT, prompts: Sequence[torch.Tensor], continuations: Sequ
     prompt + continuation[:-1] of several sequences are packed into one prompt-phase forward with the logits of every row, in groups
     of whole sequences whose token count fits max_tokens (default: what 64 MB of bf16 logits hold; a longer single sequence goes
     alone); a sequence's values do not depend on the grouping.  The head runs on the prompt rows too — a head restricted to the
-    rows that predict the continuation is left for later."""
+    rows that predict the continuation is left for later.
+
+    top_logprobs=K (1..8): the result is (scores, top); top[i] = (ids [len(continuation i), K] int32, lp float32 of that shape), the
+    K most probable tokens at every continuation position with their log-probabilities (ops.token_top_logprobs on the rows the
+    scores are read from; generate_batch's top_logprobs).  The scores are those of the call without it."""
+    K = ops.check_top_logprobs(top_logprobs)
+    if K:
+        ops.check_top_logprobs(K, model.config.padded_vocab_size)
     N = len(prompts)
     if N == 0 or len(continuations) != N:
         raise ValueError(f"score_batch takes as many continuations as prompts, at least one ({N} prompts, {len(continuations)} continuations)")
@@ -401,6 +458,7 @@ def score_batch(model: GPT, prompts: Sequence[torch.Tensor], continuations: Sequ
     eng = model.engine(max(len(g) for g in groups), max(rows), max(sum(rows[j] for j in g) for g in groups))
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     out: List[Optional[torch.Tensor]] = [None] * N
+    top: List[Optional[tuple]] = [None] * N
     for g in groups:
         packed = torch.cat([torch.cat([seqs[j][0], seqs[j][1][:-1]]) for j in g])
         # a group of one-token sequences alone is still a prompt forward (the engine would take it for a decode step)
@@ -411,8 +469,14 @@ def score_batch(model: GPT, prompts: Sequence[torch.Tensor], continuations: Sequ
             pick.append(torch.arange(start + plen[j] - 1, start + rows[j], device=dev))
             ids.append(seqs[j][1])
             start += rows[j]
-        lp = ops.token_logprobs(la[torch.cat(pick)], torch.cat(ids), check_ids=False)     # checked above
-        for j, v in zip(g, lp.split([int(seqs[j][1].numel()) for j in g])):
+        picked = la[torch.cat(pick)]
+        sizes = [int(seqs[j][1].numel()) for j in g]
+        lp = ops.token_logprobs(picked, torch.cat(ids), check_ids=False)     # checked above
+        for j, v in zip(g, lp.split(sizes)):
             out[j] = v
+        if K:
+            t_ids, t_lp = ops.token_top_logprobs(picked, K)
+            for j, a, b in zip(g, t_ids.split(sizes), t_lp.split(sizes)):
+                top[j] = (a, b)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
-    return out
+    return (out, top) if K else out

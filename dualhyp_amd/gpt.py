@@ -465,9 +465,28 @@ class _Engine:
         self._logprobs = buf
         _lib.check(self.lib.dh_engine_set_logprobs(self.handle, None if buf is None else buf.data_ptr()))
 
+    def set_top_logprobs(self, ids: Optional[torch.Tensor], lp: Optional[torch.Tensor] = None) -> None:
+        """The int32 / float32 buffers, [rows of `tokens`, tok_ld, K] with 1 <= K <= 8, that later decode / decode_rows / decode_spec
+        calls write each appended token's K alternatives into (dh_engine_set_top_logprobs; it goes with set_logprobs); None turns
+        it off.  The caller keeps them alive while set."""
+        if ids is None:
+            self._top = None
+            _lib.check(self.lib.dh_engine_set_top_logprobs(self.handle, 0, None, None))
+            return
+        if (lp is None or ids.dtype != torch.int32 or lp.dtype != torch.float32 or not (ids.is_cuda and lp.is_cuda) or ids.dim() != 3
+                or tuple(ids.shape) != tuple(lp.shape) or not (ids.is_contiguous() and lp.is_contiguous())):
+            raise TypeError("set_top_logprobs takes contiguous 3-D int32 ids and float32 values of one shape on the GPU, or None")
+        if not 1 <= ids.size(2) <= ops.MAX_TOP_LOGPROBS:
+            raise ValueError(f"set_top_logprobs: K = {ids.size(2)} is outside 1 .. {ops.MAX_TOP_LOGPROBS}")
+        self._top = (ids, lp)
+        _lib.check(self.lib.dh_engine_set_top_logprobs(self.handle, ids.size(2), ids.data_ptr(), lp.data_ptr()))
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"
+        top = getattr(self, "_top", None)
+        assert top is None or (buf is not None and tuple(top[0].shape[:2]) == tuple(tokens.shape)), \
+            "the top_logprobs buffers go with a logprobs buffer and have the shape of tokens, times K"
 
     def graph_count(self, n_draft: int = -1) -> int:
         """Captured decode steps kept for n_draft drafts (0: the plain steps, -1: all)."""

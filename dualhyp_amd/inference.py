@@ -7,6 +7,7 @@ integers (edit errors, reference words, exact matches, count) for the corpus WER
 gathered to rank 0.  No collective runs inside the decode loop."""
 from __future__ import annotations
 
+import math
 from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import torch
@@ -45,23 +46,36 @@ def _gather(obj: Any) -> List[Any]:
     return out
 
 
+def _finite_or_none(v: float) -> Optional[float]:
+    """JSON has no NaN or infinity: they are written as null."""
+    v = float(v)
+    return v if math.isfinite(v) else None
+
+
 def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]], examples: Sequence[Dict[str, Any]],
                   decode: Callable[[torch.Tensor], str], *, batch_size: int = 32, rank: int = 0, world: int = 1,
-                  device="cpu") -> Dict[str, Any]:
+                  device="cpu", eos_id: Optional[int] = None) -> Dict[str, Any]:
     """examples[i] needs 'input_ids_no_response' (1-D ids) and 'ground_truth'.  `generate_fn` maps a
     list of prompts to a list of prompt+continuation id tensors (dualhyp_amd.generate_batch bound to a
     model; a stub in the CPU tests), or to the pair (that list, a list of 1-D float tensors with the log-probability of every
     generated token, the EOS included: generate_batch(return_logprobs=True)); with the pair every prediction record gains
-    'sum_logprob' and 'avg_logprob' (the mean over those tokens).  Returns corpus metrics on every rank and predictions on rank 0."""
+    'sum_logprob' and 'avg_logprob' (the mean over those tokens); or to the triple (those two, a list of (ids [n, K], values [n, K])
+    with the K alternatives of every generated token: generate_batch(top_logprobs=K)), with which a record also gains, one entry per
+    generated token, 'token_ids' (the EOS, which the id tensors leave out, is `eos_id`), 'token_logprobs' and 'top_logprobs' (K
+    [id, log-probability] pairs); values that are not finite are written as null.  Returns corpus metrics on every rank and
+    predictions on rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
     for b in range(0, len(mine), batch_size):
         idxs = mine[b:b + batch_size]
         prompts = [examples[i]["input_ids_no_response"] for i in idxs]
         outs = generate_fn(prompts)
-        lps = None
+        lps = tops = None
         if isinstance(outs, tuple):
-            outs, lps = outs
+            if len(outs) == 3:
+                outs, lps, tops = outs
+            else:
+                outs, lps = outs
         for k, (i, p, o) in enumerate(zip(idxs, prompts, outs)):
             preds[i] = {"inference": extract_answer(decode(o), decode(p)),
                         "ground_truth": examples[i]["ground_truth"].strip()}
@@ -69,6 +83,13 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 total = float(lps[k].double().sum())
                 preds[i]["sum_logprob"] = total
                 preds[i]["avg_logprob"] = total / max(int(lps[k].numel()), 1)
+            if tops is not None:
+                ids = o.reshape(-1)[p.numel():].tolist()
+                ids += [eos_id] * (int(lps[k].numel()) - len(ids))       # behind an EOS the log-probabilities have one entry more
+                t_ids, t_lp = (t.tolist() for t in tops[k])
+                preds[i]["token_ids"] = ids
+                preds[i]["token_logprobs"] = [_finite_or_none(v) for v in lps[k].tolist()]
+                preds[i]["top_logprobs"] = [[[int(a), _finite_or_none(b)] for a, b in zip(ra, rb)] for ra, rb in zip(t_ids, t_lp)]
     order = sorted(preds)
     pr = [preds[i]["inference"] for i in order]
     gt = [preds[i]["ground_truth"] for i in order]
@@ -223,23 +244,26 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     continuous = getattr(args, "schedule", "batch") == "continuous"
     share = "auto" if getattr(args, "share_prefix", "off") == "auto" else False
     spec = int(getattr(args, "speculate", 0) or 0)
-    want_lp = bool(getattr(args, "logprobs", False))
+    top_n = int(getattr(args, "top_logprobs", 0) or 0)
+    want_lp = bool(getattr(args, "logprobs", False)) or top_n > 0
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
-                                   share_prefix=share, speculate=spec, return_logprobs=want_lp)
+                                   share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n)
         else:
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
-                                  return_logprobs=want_lp)
+                                  return_logprobs=want_lp, top_logprobs=top_n)
+        if top_n:
+            return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]], [(a.cpu(), b.cpu()) for a, b in outs[2]]
         if want_lp:
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]]
         return [o.cpu() for o in outs]
 
-    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world,
+    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
     if mask_stats:
@@ -308,6 +332,10 @@ def build_parser():
                    help="every record of the predictions file gains sum_logprob and avg_logprob: the model's log-probability of the tokens "
                         "it generated (the EOS included; temperature 1, no top-k crop), computed inside the decode steps; the predictions "
                         "do not depend on it.  Default off: the file is what it always was")
+    p.add_argument("--top_logprobs", type=int, default=0, metavar="K",
+                   help="K in 1..8 (implies --logprobs): every record also gains token_ids, token_logprobs and top_logprobs — per generated "
+                        "token the K most probable tokens of the model's distribution as [id, log-probability] pairs, by value descending, "
+                        "then by id ascending — computed inside the decode steps; the predictions do not depend on it.  Default 0: off")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)
@@ -330,6 +358,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error(f"--speculate {args.speculate} does not go with --quantize fp8: an fp8 engine has no verify step")
     if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet
         p.error(f"--speculate {args.speculate} goes with --schedule batch: continuous batching steps a row list one token at a time")
+    if not 0 <= args.top_logprobs <= 8:
+        p.error(f"--top_logprobs {args.top_logprobs}: K is 0 (off) or 1..8")
+    if args.top_logprobs:
+        args.logprobs = True
     if not 0 <= args.speculate <= 7:
         p.error(f"--speculate {args.speculate}: D is 0 (off) or 1..7")
     return args

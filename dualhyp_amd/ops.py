@@ -211,6 +211,52 @@ def _logprobs_buffer(logprobs: Optional[torch.Tensor], tokens: torch.Tensor) -> 
     return logprobs
 
 
+MAX_TOP_LOGPROBS = 8       # the header's cap on the alternatives per token
+
+
+def check_top_logprobs(k, vocab: Optional[int] = None, *, lowest: int = 0) -> int:
+    """k as an int in lowest .. min(MAX_TOP_LOGPROBS, vocab); a bool, a float or a value outside raises."""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"top_logprobs is an int, not {k!r}")
+    hi = MAX_TOP_LOGPROBS if vocab is None else min(MAX_TOP_LOGPROBS, int(vocab))
+    if not lowest <= k <= hi:
+        raise ValueError(f"top_logprobs={k} is outside {lowest} .. {hi}")
+    return k
+
+
+def _top_buffers(top: Optional[Tuple[torch.Tensor, torch.Tensor]], logprobs: Optional[torch.Tensor], tokens: torch.Tensor, vocab: int):
+    """(K, ids, lp) of the alternatives' buffers beside `tokens` that the sampling kernels write in place; (0, None, None) without."""
+    if top is None:
+        return 0, None, None
+    if logprobs is None:
+        raise ValueError("top_logprobs buffers go with a logprobs buffer")
+    ids, lp = top
+    if not (ids.is_cuda and lp.is_cuda):
+        raise _lib.DualHypHipError("top_logprobs buffers must live on the GPU: the HIP path has no CPU fallback")
+    if ids.dtype != torch.int32 or lp.dtype != torch.float32:
+        raise TypeError(f"top_logprobs buffers are ({torch.int32}, {torch.float32}), got ({ids.dtype}, {lp.dtype})")
+    if ids.dim() != 3 or tuple(ids.shape) != tuple(lp.shape) or tuple(ids.shape[:2]) != tuple(tokens.shape) \
+            or not (ids.is_contiguous() and lp.is_contiguous()):
+        raise ValueError(f"top_logprobs buffers are contiguous {tuple(tokens.shape)} + (K,) tensors, got {tuple(ids.shape)} and {tuple(lp.shape)}")
+    return check_top_logprobs(int(ids.size(2)), vocab, lowest=1), ids, lp
+
+
+def token_top_logprobs(logits: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
+    index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
+    definition is in include/dualhyp_hip.h, "Token alternatives").  1 <= k <= min(8, vocab)."""
+    logits = _dev(logits, name="logits")
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
+    rows, vocab = logits.shape
+    k = check_top_logprobs(k, vocab, lowest=1)
+    ids = torch.empty((rows, k), dtype=torch.int32, device=logits.device)
+    lp = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
+    if rows:
+        check(_lib.load().dh_token_top_logprobs_bf16(_p(logits), vocab, k, _p(ids), _p(lp), rows, _stream()))
+    return ids, lp
+
+
 def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool = True) -> torch.Tensor:
     """float32 [rows]: log softmax(logits[r])[ids[r]] of the raw bf16 rows (dh_token_logprobs_bf16; the definition is in
     include/dualhyp_hip.h, "Token log-probabilities").  An id outside [0, vocab) raises before anything is launched
@@ -235,24 +281,31 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool =
 
 def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, *,
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
-           step: int = 0, logprobs: Optional[torch.Tensor] = None) -> None:
+           step: int = 0, logprobs: Optional[torch.Tensor] = None,
+           top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
-    tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex)."""
+    tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
+    int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
+    same place in them (dh_sample_bf16_top)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_seq, vocab = logits.shape
     assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.size(0) == n_seq
     logprobs = _logprobs_buffer(logprobs, tokens)
-    check(_lib.load().dh_sample_bf16_ex(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
-                                        k(done, torch.int32), n_seq, float(temperature),
-                                        0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id),
-                                        int(seed) & ((1 << 64) - 1), int(step), _stream(), _p(logprobs)))
+    top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
+    check(_lib.load().dh_sample_bf16_top(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
+                                         k(done, torch.int32), n_seq, float(temperature),
+                                         0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id),
+                                         int(seed) & ((1 << 64) - 1), int(step), _stream(), _p(logprobs), top_n, _p(top_ids),
+                                         _p(top_lp)))
 
 
 def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor,
                 row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
-                eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None) -> None:
-    """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs: as in sample()."""
+                eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None,
+                top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
+    """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
+    in sample()."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_rows, vocab = logits.shape
@@ -260,11 +313,12 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     assert tokens.dtype == torch.int64 and tokens.is_contiguous() and row_seq.numel() == n_rows
     assert length.numel() == done.numel() == limit.numel() == n_seq
     logprobs = _logprobs_buffer(logprobs, tokens)
-    check(_lib.load().dh_sample_rows_bf16_ex(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
-                                             k(done, torch.int32), k(limit, torch.int32), k(row_seq, torch.int32), n_rows, n_seq,
-                                             int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
-                                             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(),
-                                             _p(logprobs)))
+    top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
+    check(_lib.load().dh_sample_rows_bf16_top(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
+                                              k(done, torch.int32), k(limit, torch.int32), k(row_seq, torch.int32), n_rows, n_seq,
+                                              int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
+                                              -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(),
+                                              _p(logprobs), top_n, _p(top_ids), _p(top_lp)))
 
 
 def quant_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

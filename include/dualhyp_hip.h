@@ -27,7 +27,8 @@ extern "C" {
 typedef uint16_t dh_bf16;
 
 /* ABI 6 gained entries without a change to any existing one (so the number stays): dh_token_logprobs_bf16, dh_sample_bf16_ex,
- * dh_sample_rows_bf16_ex and dh_engine_set_logprobs (token log-probabilities). */
+ * dh_sample_rows_bf16_ex and dh_engine_set_logprobs (token log-probabilities); dh_token_top_logprobs_bf16, dh_sample_bf16_top,
+ * dh_sample_rows_bf16_top and dh_engine_set_top_logprobs (token alternatives). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -377,6 +378,35 @@ int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t* tokens, in
                            int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                            void* stream, float* logprobs);
 
+/* Token alternatives.  ONE definition for every entry below: for a logits row l (bf16, vocab columns) and 1 <= K <= min(8, vocab)
+ * (DH_MAX_TOP_LOGPROBS), alternative j = 0 .. K-1 is
+ *   id_j = the index at rank j when the entries of l are ordered by value descending, then by index ascending,
+ *   lp_j = lp(id_j) of "Token log-probabilities" above: (l[id_j] - m) - logf(tot) with the row's one m and one tot, summed in the
+ *          same order, so lp_j is bit-equal to what dh_token_logprobs_bf16 gives for (l, id_j).
+ * Values compare as numbers: -0 == +0, so two zeros tie and the lower index goes first; -inf entries are ordinary values that rank
+ * last (lp = -inf).  The order is over the RAW row — temperature 1, no top-k crop: the model's distribution, not the sampler's
+ * bf16(l / temperature), which can merge distinct raw values into ties.  Rows that hold a NaN are outside the definition (their
+ * log-sum is NaN already); their ids are still inside [0, vocab).  A row's result depends on its bytes and on vocab alone: not on
+ * the row index, the row count, the row's alignment or the sampler's parameters.  The selection is one more pass over the row in
+ * the block that holds it: every entry has the unique sort key (value key, ~index), each thread keeps its 8 largest, and K
+ * block-wide maxima merge them — no atomic decides anything.  m and tot are computed once per row for the chosen token and the K
+ * alternatives. */
+#define DH_MAX_TOP_LOGPROBS 8
+
+/* out_ids (int32) / out_lp (fp32), both [n_rows, k]: the k alternatives of every logits row. */
+int dh_token_top_logprobs_bf16(const dh_bf16* logits, int vocab, int k, int32_t* out_ids, float* out_lp, int n_rows, void* stream);
+/* dh_sample_bf16_ex / dh_sample_rows_bf16_ex with the alternatives' buffers top_ids (int32) and top_lp (fp32), both
+ * [n_seq, tok_ld, top_logprobs]: the thread that stores tokens[u, n] also stores top_ids[u, n, 0..K) and top_lp[u, n, 0..K), the
+ * alternatives of the row the token was picked from; nothing is written where no token is.  top_logprobs = 0 (the buffers may then
+ * be null) is the _ex entry; top_logprobs > 0 needs logprobs, top_ids and top_lp. */
+int dh_sample_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                       int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                       uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp);
+int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                            int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                            int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                            void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -615,6 +645,12 @@ int dh_engine_reserve_rows(dh_engine* e, int rows);
  * captured step's key: a step captured without it is never replayed with it, and the reverse, and with it off the steps hold the
  * kernels they always held.  The caller keeps the buffer alive while it is set. */
 int dh_engine_set_logprobs(dh_engine* e, float* buf);
+/* The buffers (device int32 ids and fp32 lp, both [n_seq, tok_ld, k]; k = 0 or a null pointer = off, the default) into which later
+ * dh_engine_decode, dh_engine_decode_rows and dh_engine_decode_spec calls write the k alternatives of every token they append (see
+ * "Token alternatives" above; a verify step's pick j gets those of its own logits row).  It goes with dh_engine_set_logprobs: a
+ * decode call with k > 0 and no logprobs buffer fails.  k and both pointers are part of the captured step's key, exactly as the
+ * logprobs pointer is.  The caller keeps the buffers alive while they are set. */
+int dh_engine_set_top_logprobs(dh_engine* e, int k, int32_t* ids, float* lp);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
