@@ -33,6 +33,12 @@ class ModelDesc(C.Structure):
                 ("h_layers", C.POINTER(LayerWeights)), ("lm_head_ws", P)]
 
 
+class BeamState(C.Structure):
+    """dh_beam_state: the device arrays of one beam search call (include/dualhyp_hip.h, "Beam search")"""
+    _fields_ = [(n, P) for n in ("cum", "n_steps", "done", "beam_tok", "beam_parent", "beam_lp", "beam_cum", "fin_step", "fin_parent",
+                                 "fin_score", "fin_lp", "n_fin")]
+
+
 # name -> (restype, argtypes); must list every function declared in include/dualhyp_hip.h
 SIGNATURES = {
     "dh_abi_version": (I, []),
@@ -78,6 +84,7 @@ SIGNATURES = {
     "dh_token_top_logprobs_bf16": (I, [P, I, I, P, P, I, P]),
     "dh_sample_bf16_top": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P]),
     "dh_sample_rows_bf16_top": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P]),
+    "dh_beam_select_bf16": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P]),
     "dh_quant_rows_fp8": (I, [P, P, P, I, I, P]),
     "dh_rmsnorm_quant_fp8": (I, [P, P, P, P, P, I, I, F, P, P]),
     "dh_linear_fp8": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
@@ -105,6 +112,8 @@ SIGNATURES = {
     "dh_engine_decode_rows": (I, [P, P, I, P, P, P, I, I, P, P, I, I, F, I, I64, U64, P]),
     "dh_engine_decode_spec": (I, [P, P, I, P, P, P, I, I, I, P, P, I, F, I64, I, P]),
     "dh_engine_reserve_rows": (I, [P, I]),
+    "dh_engine_reserve_beams": (I, [P, I, I]),
+    "dh_engine_decode_beam": (I, [P, C.POINTER(BeamState), P, I, I, I, I, I64, I, P]),
     "dh_engine_set_logprobs": (I, [P, P]),
     "dh_engine_set_top_logprobs": (I, [P, I, P, P]),
     "dh_engine_graph_count": (I, [P, I]),

@@ -1,0 +1,106 @@
+// The selection step of beam search (include/dualhyp_hip.h, "Beam search"): the rows' 2 W candidates by dh_token_top_logprobs_bf16 —
+// row_logsum + row_top of sampling.hip, untouched — then this file's kernel, one wave per utterance, that merges the at most 32
+// candidates, walks them and writes the step's records.  tests/beam_reference.py is the host model.
+#include "common.h"
+
+namespace {
+
+constexpr int MAX_W = DH_MAX_BEAMS;
+constexpr int MAX_CAND = MAX_W * 2 * MAX_W;
+static_assert(2 * MAX_W <= DH_MAX_TOP_LOGPROBS, "a row offers 2 W alternatives");
+
+// Candidate (b, j) = alternative j of live row b, score = cum[b] + lp: one fp32 add.  A row's list is sorted already (value
+// descending, then index ascending, and the add of one cum keeps the order), so the order of the definition — score descending, then
+// b ascending, then j ascending — is the merge of the rows' lists by their heads, the lower b winning a tie.  Lane 0 does the merge and
+// the walk, 2 W places of at most W compares each: nothing here is worth a second lane, and no atomic decides anything.
+__global__ __launch_bounds__(64) void beam_merge_kernel(const int32_t* __restrict__ cand_ids, const float* __restrict__ cand_lp,
+                                                        int rows_per_utt, int W, int max_new, int64_t eos_id, int step_arg,
+                                                        const int32_t* __restrict__ step_dev, dh_beam_state st) {
+    const int u = blockIdx.x, tid = threadIdx.x;
+    if (st.done[u]) return;                                          // frozen
+    const int step = step_dev ? *step_dev : step_arg;                // device counter keeps a captured graph replayable
+    if (step < 0 || step >= max_new) return;                         // never a record outside the arrays
+    __shared__ int32_t s_id[MAX_CAND];
+    __shared__ float s_lp[MAX_CAND], s_sc[MAX_CAND];
+    __shared__ int s_head[MAX_W];
+    const int K = 2 * W, n = rows_per_utt * K;
+    if (tid < n) {
+        const int b = tid / K;
+        const float lp = cand_lp[(size_t)u * n + tid];
+        s_id[tid] = cand_ids[(size_t)u * n + tid];
+        s_lp[tid] = lp;
+        s_sc[tid] = st.cum[(size_t)u * W + b] + lp;
+    }
+    if (tid < MAX_W) s_head[tid] = 0;
+    __syncthreads();
+    if (tid != 0) return;
+    int n_live = 0, nf = st.n_fin[u];
+    const size_t rec = ((size_t)u * max_new + step) * W;
+    for (int p = 0; p < K && n_live < W; ++p) {
+        int b = -1;
+        float best = 0.f;
+        for (int r = 0; r < rows_per_utt; ++r) {
+            if (s_head[r] >= K) continue;
+            const float sc = s_sc[r * K + s_head[r]];
+            if (b < 0 || sc > best) { b = r; best = sc; }
+        }
+        if (b < 0) break;
+        const int c = b * K + s_head[b]++;
+        if (eos_id >= 0 && (int64_t)s_id[c] == eos_id) {
+            if (p < W && nf < W) {
+                st.fin_step[(size_t)u * W + nf] = step;
+                st.fin_parent[(size_t)u * W + nf] = b;
+                st.fin_score[(size_t)u * W + nf] = best;
+                st.fin_lp[(size_t)u * W + nf] = s_lp[c];
+                ++nf;
+            }
+            continue;
+        }
+        st.beam_parent[rec + n_live] = b;
+        st.beam_tok[rec + n_live] = s_id[c];
+        st.beam_lp[rec + n_live] = s_lp[c];
+        st.beam_cum[rec + n_live] = best;
+        st.cum[(size_t)u * W + n_live] = best;                       // every cum was read before the barrier
+        ++n_live;
+    }
+    for (; n_live < W; ++n_live) {     // rows outside the definition (NaN) can run the lists dry: a beam that continues itself nowhere
+        st.beam_parent[rec + n_live] = rows_per_utt == 1 ? 0 : n_live;
+        st.beam_tok[rec + n_live] = 0;
+        st.beam_lp[rec + n_live] = -INFINITY;
+        st.beam_cum[rec + n_live] = -INFINITY;
+        st.cum[(size_t)u * W + n_live] = -INFINITY;
+    }
+    st.n_fin[u] = nf;
+    st.n_steps[u] = step + 1;
+    if (nf >= W) st.done[u] = 1;
+    else if (step + 1 >= max_new) st.done[u] = 2;                    // budget spent
+}
+
+}  // namespace
+
+int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
+                        const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, void* stream) {
+    DH_CHECK(logits && cand_ids && cand_lp, "dh_beam_select_bf16: null argument");
+    DH_CHECK(st.cum && st.n_steps && st.done && st.beam_tok && st.beam_parent && st.beam_lp && st.beam_cum && st.fin_step &&
+             st.fin_parent && st.fin_score && st.fin_lp && st.n_fin, "dh_beam_select_bf16: the beam state has a null array");
+    DH_CHECK(W >= 1 && W <= MAX_W, "dh_beam_select_bf16: W=%d beams, 1 .. %d are supported", W, MAX_W);
+    DH_CHECK(rows_per_utt == 1 || rows_per_utt == W, "dh_beam_select_bf16: rows_per_utt=%d is neither 1 (step 0) nor W=%d", rows_per_utt, W);
+    DH_CHECK(vocab >= 2 * W, "dh_beam_select_bf16: vocab=%d is below the 2 W = %d candidates of a row", vocab, 2 * W);
+    DH_CHECK(n_utt >= 0 && max_new > 0, "dh_beam_select_bf16: bad shape");
+    DH_CHECK(step_dev || (step >= 0 && step < max_new), "dh_beam_select_bf16: step %d is outside the %d recorded steps", step, max_new);
+    if (n_utt == 0) return 0;
+    const int rc = dh_token_top_logprobs_bf16(logits, vocab, 2 * W, cand_ids, cand_lp, n_utt * rows_per_utt, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, cand_ids, cand_lp, rows_per_utt, W, max_new,
+                       eos_id, step, step_dev, st);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_beam_select_bf16(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens,
+                                   int64_t eos_id, int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids,
+                                   float* cand_lp, void* stream) {
+    DH_CHECK(st, "dh_beam_select_bf16: null beam state");
+    return dh_beam_select_impl(logits, vocab, n_utt, rows_per_utt, W, max_new_tokens, eos_id, step, step_dev, *st, cand_ids, cand_lp,
+                               stream);
+}

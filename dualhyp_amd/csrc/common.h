@@ -289,6 +289,10 @@ int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids
                         const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
                         void* stream);
 
+// the selection step of beam search (beam.hip, dh_beam_select_bf16), as the engine's captured step calls it
+int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
+                        const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, void* stream);
+
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads
 // racing on the first launch both set it, which is harmless.  `kernel` must be parenthesised if it contains commas.

@@ -45,6 +45,10 @@ struct dh_engine {
     float* top_lp = nullptr;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
+    bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
+    size_t beam_scratch_elems = 0;
+    int32_t* beam_cand_ids = nullptr;                   // [B, 2 W_max] candidates of a beam step's rows (dh_beam_select_bf16's workspace)
+    float* beam_cand_lp = nullptr;
     bf16_t** cache_tab = nullptr;                       // [2 L] device table, written once: K cache of layer l at 2l, V^T cache at 2l + 1
                                                         // (kv8: [4 L], the fp8 bytes like that, then the exponent arrays like that)
     int32_t* last_meta = nullptr;                       // [ones | position of the last token] x [B]: the pruned last layer's attention call
@@ -72,12 +76,16 @@ struct dh_engine {
         int spec; const int64_t* drafts; int32_t* counters;   // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
         float* logprobs;                                      // dh_engine_set_logprobs: a step captured without the buffer is another kernel
         int top_n; int32_t* top_ids; float* top_lp;           // dh_engine_set_top_logprobs: likewise, and top_n is a kernel argument
+        // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
+        // n_seq = n_utt * W rows
+        int beam_w; dh_beam_state beam;
         bool operator==(const GKey& k) const {
             return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
-                   logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp;
+                   logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && beam_w == k.beam_w &&
+                   memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
@@ -278,6 +286,67 @@ __global__ __launch_bounds__(256) void kv_copy_prefix_kernel(bf16_t* const* __re
     const i32x4 v = *(const gi32x4*)(base + (size_t)src_slot * slot_elems);
     const int d0 = blockIdx.z * dst_per_block, d1 = min(d0 + dst_per_block, n_dst);
     for (int i = d0; i < d1; ++i) *(gi32x4*)(base + (size_t)dst_slots[i] * slot_elems) = v;
+}
+
+// The ids of a beam step (dh_engine_decode_beam): row u * W + w feeds beam_tok[u, t - 1, w] at position prompt_len[u] + t - 1 in slot
+// u * W + w, t = n_steps[u] — the step about to be taken for a live utterance; a finished one's rows write the position behind their
+// last one again, the same bits every time.  t, the prompt length and the position are clamped to the records, the cache and the rope
+// table, an id to the embedding table: nothing is trusted to index.
+__global__ void beam_prep_kernel(const int32_t* __restrict__ beam_tok, const int32_t* __restrict__ n_steps,
+                                 const int32_t* __restrict__ plen, int W, int max_new, int64_t* __restrict__ ids,
+                                 int32_t* __restrict__ tok_slot, int32_t* __restrict__ tok_pos, int32_t* __restrict__ kv_len,
+                                 int32_t* step_dev, int n_rows, int cap, int n_vocab) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r == 0) *step_dev += 1;
+    if (r < n_rows) {
+        const int u = r / W, w = r % W;
+        int t = n_steps[u], P = plen[u];
+        t = t < 1 ? 1 : (t > max_new ? max_new : t);
+        P = P < 1 ? 1 : P;
+        int pos = P + t - 1;
+        pos = pos < cap ? pos : cap - 1;
+        int id = beam_tok[((size_t)u * max_new + t - 1) * W + w];
+        id = id < 0 || id >= n_vocab ? 0 : id;
+        ids[r] = id;
+        tok_slot[r] = r;
+        tok_pos[r] = pos;
+        kv_len[r] = pos + 1;
+    }
+}
+
+// KV re-parenting of a beam step: behind the selection of step t, slot u * W + w must hold the cache of slot u * W + parent,
+// parent = beam_parent[u, t, w], in the tiles prompt_len[u] / 32 .. (prompt_len[u] + t - 1) / 32 that hold generated keys (32-key tiles
+// back to back from the start of a (slot, group) block, tile_units 16-byte units each).  Two launches of this kernel through the
+// engine's scratch — to_scratch: the parent's tiles into the row's own scratch block; then: that block into the row's own slot — so
+// no launch reads what it writes and any parent map is right.  grid (pieces of 256 units of the nt_max tiles, 2 L tables x groups,
+// rows): fixed, what there is to do is read from the device.  A row that continues itself, an utterance that did not take step t
+// (n_steps[u] != t + 1: finished before) and units behind the row's last tile return at once.
+__global__ __launch_bounds__(256) void beam_reparent_kernel(bf16_t* const* __restrict__ cache_tab, bf16_t* __restrict__ scratch,
+                                                            const int32_t* __restrict__ beam_parent, const int32_t* __restrict__ n_steps,
+                                                            const int32_t* __restrict__ plen, const int32_t* __restrict__ step_dev, int W,
+                                                            int max_new, int n_groups, size_t block_elems, int tile_units, int nt_max,
+                                                            int cache_tiles, int to_scratch) {
+    const int row = blockIdx.z, u = row / W, w = row % W;
+    const int step = *step_dev;
+    if (step < 1 || step >= max_new || n_steps[u] != step + 1) return;
+    const int parent = beam_parent[((size_t)u * max_new + step) * W + w];
+    if (parent == w || parent < 0 || parent >= W) return;
+    const int P = plen[u];
+    if (P < 1) return;
+    const int tile0 = P >> 5;
+    int nt = ((P + step - 1) >> 5) - tile0 + 1;
+    nt = nt < nt_max ? nt : nt_max;
+    nt = nt < cache_tiles - tile0 ? nt : cache_tiles - tile0;         // never past the (slot, group) block
+    const int unit = blockIdx.x * 256 + threadIdx.x;
+    if (unit >= nt * tile_units) return;
+    const int g = blockIdx.y % n_groups;
+    typedef __attribute__((address_space(1))) bf16_t gbf16_t;
+    typedef __attribute__((address_space(1))) i32x4 gi32x4;
+    gbf16_t* cache = (gbf16_t*)cache_tab[blockIdx.y / n_groups] + (size_t)g * block_elems + ((size_t)tile0 * tile_units + unit) * 8;
+    const size_t slot_elems = (size_t)n_groups * block_elems;
+    gbf16_t* sc = (gbf16_t*)scratch + (((size_t)row * gridDim.y + blockIdx.y) * nt_max * tile_units + unit) * 8;
+    if (to_scratch) *(gi32x4*)sc = *(const gi32x4*)(cache + (size_t)(u * W + parent) * slot_elems);
+    else *(gi32x4*)(cache + (size_t)row * slot_elems) = *(const gi32x4*)sc;
 }
 
 // dst[i, :] = src[last_row[i], :] for the n_seq sequences of the call
@@ -867,7 +936,35 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
                                e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
 }
 
+// tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends
+int beam_tiles(int max_new) { return (max_new + 30) / 32 + 1; }
+
+// One beam step (dh_engine_decode_beam): prep, the single-token step over the n_utt * W rows, the selection, the re-parenting.
+int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
+    const dh_model_desc& D = e->d;
+    const int rows = k.n_seq, W = k.beam_w;
+    const int cap = e->s_max < D.block_size ? e->s_max : D.block_size;
+    hipLaunchKernelGGL(beam_prep_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, s, k.beam.beam_tok, k.length, k.limit, W, k.max_new, e->dec_ids,
+                       e->tok_slot, e->tok_pos, seq_meta(e).kv, e->step_dev, rows, cap, D.wte_rows);
+    DH_LAUNCH_CHECK();
+    int rc;
+    if ((rc = run_model(e, e->dec_ids, rows, rows, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
+    if ((rc = dh_beam_select_impl(e->logits, D.vocab, rows / W, W, W, k.max_new, k.eos, 0, e->step_dev, k.beam, e->beam_cand_ids,
+                                  e->beam_cand_lp, s))) return rc;
+    if (W == 1) return 0;                                   // a single beam continues itself
+    const int tile_units = D.head_size * 4, nt_max = std::min(beam_tiles(k.max_new), e->s_max / 32);
+    const dim3 grid(cdiv(nt_max * tile_units, 256), 2 * D.n_layer * D.n_groups, rows);
+    for (int to_scratch = 1; to_scratch >= 0; --to_scratch) {
+        hipLaunchKernelGGL(beam_reparent_kernel, grid, dim3(256), 0, s, e->cache_tab, e->beam_scratch, k.beam.beam_parent, k.length, k.limit,
+                           e->step_dev, W, k.max_new, D.n_groups, (size_t)e->s_max * D.head_size, tile_units, nt_max, e->s_max / 32,
+                           to_scratch);
+        DH_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
+    if (k.beam_w) return beam_step(e, k, s);
     if (k.spec) return verify_step(e, k, s);
     const bool rows = k.row_seq != nullptr;
     hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(k.n_seq, 64)), dim3(64), 0, s, k.tokens, k.tok_ld, k.length, k.row_seq, k.row_slot,
@@ -960,6 +1057,7 @@ extern "C" void dh_engine_destroy(dh_engine* e) {
     for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
     void* ptrs[] = {e->kc, e->vtc, e->k8, e->v8, e->ke, e->ve, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
                     e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->copy_dst, e->cache_tab, e->dec_ids, e->dec_work,
+                    e->beam_scratch, e->beam_cand_ids, e->beam_cand_lp,
                     e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale};
     for (void* p : ptrs)
         if (p) hipFree(p);
@@ -1158,6 +1256,71 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
                               limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp};
+    return launch_steps(e, key, n_steps, s);
+}
+
+extern "C" int dh_engine_reserve_beams(dh_engine* e, int W, int max_new_tokens) {
+    DH_CHECK(e, "dh_engine_reserve_beams: null engine");
+    DH_CHECK(W >= 1 && W <= DH_MAX_BEAMS && max_new_tokens > 0, "dh_engine_reserve_beams: W=%d (1 .. %d) beams, %d new tokens", W,
+             DH_MAX_BEAMS, max_new_tokens);
+    DH_CHECK(!e->kv8 && !e->fp8, "dh_engine_reserve_beams: an fp8 engine has no beam step");
+    const int nt_max = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
+    const size_t need = W == 1 ? 0 : (size_t)e->max_batch * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32;
+    if (e->beam_cand_ids && need <= e->beam_scratch_elems) return 0;
+    // the captured steps hold the old addresses
+    DH_HIP(hipDeviceSynchronize());
+    for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
+    e->graphs.clear();
+    if (!e->beam_cand_ids) {
+        const size_t n = (size_t)e->max_batch * 2 * DH_MAX_BEAMS;
+        if (dmalloc(e, &e->beam_cand_ids, n) || dmalloc(e, &e->beam_cand_lp, n)) {
+            dh_set_error("dh_engine_reserve_beams: device allocation failed (%s)", dh_last_error());
+            return 2;
+        }
+    }
+    if (need > e->beam_scratch_elems) {      // on failure the engine keeps the scratch it had
+        bf16_t* p = nullptr;
+        if (hipMalloc((void**)&p, need * sizeof(bf16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            dh_set_error("dh_engine_reserve_beams: %.2f GiB of re-parenting scratch could not be allocated", need * 2 / 1073741824.0);
+            return 2;
+        }
+        hipFree(e->beam_scratch);
+        e->dev_bytes += (int64_t)((need - e->beam_scratch_elems) * sizeof(bf16_t));
+        e->beam_scratch = p;
+        e->beam_scratch_elems = need;
+    }
+    return 0;
+}
+
+extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, const int32_t* prompt_len, int n_utt, int W,
+                                     int max_new_tokens, int n_steps, int64_t eos_id, int first_step, void* stream) {
+    DH_CHECK(e && st && prompt_len, "dh_engine_decode_beam: null argument");
+    DH_CHECK(st->cum && st->n_steps && st->done && st->beam_tok && st->beam_parent && st->beam_lp && st->beam_cum && st->fin_step &&
+             st->fin_parent && st->fin_score && st->fin_lp && st->n_fin, "dh_engine_decode_beam: the beam state has a null array");
+    DH_CHECK(W >= 1 && W <= DH_MAX_BEAMS, "dh_engine_decode_beam: W=%d beams, 1 .. %d are supported", W, DH_MAX_BEAMS);
+    DH_CHECK(n_utt > 0 && max_new_tokens > 0, "dh_engine_decode_beam: bad shape");
+    DH_CHECK(first_step >= 1, "dh_engine_decode_beam: first_step=%d, step 0 is the caller's dh_beam_select_bf16 on the prefill's logits", first_step);
+    const int64_t rows = (int64_t)n_utt * W;
+    DH_CHECK(rows <= e->max_batch, "dh_engine_decode_beam: %d utterances x %d beams exceed the engine's %d KV slots", n_utt, W, e->max_batch);
+    DH_CHECK(rows <= MAX_DECODE_ROWS, "dh_engine_decode_beam: %d x %d rows exceed the streaming step's %d", n_utt, W, MAX_DECODE_ROWS);
+    DH_CHECK(rows <= e->row_cap && rows <= e->max_tokens, "dh_engine_decode_beam: %d rows, the workspaces hold %d of max_tokens = %d",
+             (int)rows, e->row_cap, e->max_tokens);
+    DH_CHECK(e->d.vocab >= 2 * W, "dh_engine_decode_beam: vocab=%d is below the 2 W = %d candidates of a row", e->d.vocab, 2 * W);
+    DH_CHECK(!e->fp8, "dh_engine_decode_beam: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
+    DH_CHECK(!e->kv8, "dh_engine_decode_beam: the re-parenting copies bf16 cache tiles; an fp8 KV cache is not supported");
+    DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_beam: the CPU rsqrt emulation flags rows by their place in a call; not supported");
+    DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_beam: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
+    const int nt_max = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
+    DH_CHECK(e->beam_cand_ids && (W == 1 || (size_t)rows * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32 <= e->beam_scratch_elems),
+             "dh_engine_decode_beam: the re-parenting scratch is too small for W=%d and %d new tokens (dh_engine_reserve_beams)", W, max_new_tokens);
+    if (n_steps <= 0) return 0;
+    e->seq_slot = e->seq_meta;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)(first_step - 1));   // the prep kernel counts it up
+    DH_LAUNCH_CHECK();
+    dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
+                        prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 

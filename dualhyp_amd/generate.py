@@ -12,6 +12,7 @@ from typing import List, Optional, Sequence, Union
 
 import torch
 
+from . import beam as _beam
 from . import ops
 from .gpt import GPT
 from .schedule import shared_prefix_len
@@ -239,6 +240,95 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
         res += (st,)
     return res if len(res) > 1 else out
+
+
+@torch.inference_mode()
+def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
+                      length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False):
+    """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
+    tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
+      tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
+      token_logprobs  1-D float32 CPU tensor, one value per generated token, the EOS's included — generate_batch's return_logprobs,
+      sum_logprob     the device's fp32 cumulative score (their sequential fp32 sum), as a float,
+      finished        True when the hypothesis ended on the EOS; False for a live beam that completed the pool at the budget.
+    Ranked by sum_logprob / n ** length_penalty in Python floats, n = generated tokens with the EOS counted, descending, stable on
+    pool order.  The scores compare directly with score_batch and with generate_batch(return_logprobs=True).
+
+    The prompts are prefilled as generate_batch prefills them, prompt i into KV slot i * W, and forked into the W - 1 slots behind
+    (dh_engine_copy_prefix, whole tiles).  Step 0 selects from the prefill's last-position logits; every later step is one captured
+    chain — ids of the W live beams, the single-token step over all n * W rows, the selection, the KV re-parenting — replayed
+    EOS_CHECK_EVERY at a time until every utterance is done (dh_engine_decode_beam).  A decode row's bits do not depend on the rows
+    beside it, so a hypothesis has the scores it would have alone; num_beams=1 gives generate_batch(temperature=1.0, top_k=1)'s ids
+    and log-probabilities.  The cache holds one position more per slot than generate_batch's: the rows of a finished utterance keep
+    stepping at the position behind their last one.
+
+    The fork is one dh_engine_copy_prefix call per utterance (a source slot each): a host synchronisation, a small upload and two
+    launches per utterance inside the window timed as prefill_ms — a first version; one launch over a list of (source, destinations)
+    is open.
+
+    timing gains prefill_ms, decode_ms, decode_steps, decode_row_steps, and beam_step_rows / beam_copied_rows: the rows of the steps
+    that utterances took, and those among them that continued another beam and were copied."""
+    B = len(prompts)
+    assert B > 0 and max_new_tokens > 0
+    W = _beam.check_arguments(model, num_beams, B)
+    length_penalty = _beam.check_length_penalty(length_penalty)
+    lens = [int(p.numel()) for p in prompts]
+    T_max = max(lens)
+    need_pos = T_max + max_new_tokens
+    if model.max_seq_length < need_pos:
+        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    dev = model.transformer.wte.weight.device
+    chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
+    rows = B * W
+    eng = model.engine(rows, need_pos, max(rows, max(sum(lens[a:b]) for a, b in chunks)), exact=rows > prefill_batch)
+    eng.set_rsqrt_emulation(0, whole_call=False)
+    eng.reserve_beams(W, max_new_tokens)
+    state = _beam.BeamState(B, W, max_new_tokens, dev)
+    plen = torch.tensor(lens, dtype=torch.int32, device=dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    on_dev = [p.to(dev).reshape(-1) for p in prompts]
+    last = torch.empty((B, eng.vocab), dtype=torch.bfloat16, device=dev)
+    for a, b in chunks:
+        last[a:b] = eng.forward_slots(torch.cat(on_dev[a:b]), lens[a:b], [u * W for u in range(a, b)])
+    if W > 1:
+        for u in range(B):      # positions at or behind the prompt's end are overwritten before causality lets anything read them
+            eng.copy_prefix(u * W, list(range(u * W + 1, (u + 1) * W)), -(-lens[u] // 32) * 32)
+    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0)
+    if ev:
+        ev[1].record()
+    step = 1
+    while step < max_new_tokens:
+        c = max_new_tokens - step if eos_id is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
+        eng.decode_beam(state, plen, c, eos_id, first_step=step)
+        step += c
+        if step < max_new_tokens and bool((state.done != 0).all()):
+            break
+    if ev:
+        ev[2].record()
+    model._cache_len = []  # slots now hold these hypotheses; a later cached forward must start at 0
+    h = state.host()        # the read-back: two copies
+    prompts_h = torch.cat(on_dev).cpu().split(lens)
+    if ev:
+        timing["prefill_ms"] = timing.get("prefill_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
+        timing["decode_steps"] = timing.get("decode_steps", 0) + step - 1
+        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + rows * (step - 1)
+        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens)
+        took = sum(W * (n - 1) for n in h["n_steps"])
+        moved = sum(p != w for u in range(B) for t in range(1, h["n_steps"][u]) for w, p in enumerate(h["beam_parent"][u][t]))
+        timing["beam_step_rows"] = timing.get("beam_step_rows", 0) + took
+        timing["beam_copied_rows"] = timing.get("beam_copied_rows", 0) + moved
+    out = []
+    for u in range(B):
+        hyps = _beam.hypotheses(h, u, W, length_penalty)
+        for hyp in hyps:
+            hyp["tokens"] = torch.cat([prompts_h[u], torch.tensor(hyp["tokens"], dtype=torch.int64)])
+        out.append(hyps)
+    if return_state:
+        return out, dict(beam=state, host=h, prompt_len=plen)
+    return out
 
 
 class _StreamBackend:

@@ -457,6 +457,20 @@ class _Engine:
                 int(max_new_tokens), int(n_draft), None if drafts is None else drafts.data_ptr(), counters.data_ptr(), int(n_steps),
                 float(temperature), -1 if eos_id is None else int(eos_id), int(first_step), torch.cuda.current_stream().cuda_stream))
 
+    def reserve_beams(self, num_beams: int, max_new_tokens: int) -> None:
+        """Size the KV re-parenting scratch and the candidates' workspace of decode_beam (dh_engine_reserve_beams)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_reserve_beams(self.handle, int(num_beams), int(max_new_tokens)))
+
+    def decode_beam(self, state, prompt_len: torch.Tensor, n_steps: int, eos_id: Optional[int], first_step: int) -> None:
+        """n_steps beam steps of state.n_utt utterances x state.W beams, the first one step number first_step >= 1
+        (dh_engine_decode_beam; `state` is a dualhyp_amd.beam.BeamState, prompt_len int32 [n_utt] on the GPU)."""
+        assert prompt_len.dtype == torch.int32 and prompt_len.is_cuda and prompt_len.is_contiguous() and prompt_len.numel() == state.n_utt
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_decode_beam(
+                self.handle, C.byref(state.c_struct()), prompt_len.data_ptr(), state.n_utt, state.W, state.max_new, int(n_steps),
+                -1 if eos_id is None else int(eos_id), int(first_step), torch.cuda.current_stream().cuda_stream))
+
     def set_logprobs(self, buf: Optional[torch.Tensor]) -> None:
         """The float32 buffer, shaped like the decode calls' `tokens`, that later decode / decode_rows / decode_spec calls write each
         appended token's log-probability into (dh_engine_set_logprobs); None turns it off.  The caller keeps it alive while set."""

@@ -62,16 +62,22 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     'sum_logprob' and 'avg_logprob' (the mean over those tokens); or to the triple (those two, a list of (ids [n, K], values [n, K])
     with the K alternatives of every generated token: generate_batch(top_logprobs=K)), with which a record also gains, one entry per
     generated token, 'token_ids' (the EOS, which the id tensors leave out, is `eos_id`), 'token_logprobs' and 'top_logprobs' (K
-    [id, log-probability] pairs); values that are not finite are written as null.  Returns corpus metrics on every rank and
-    predictions on rank 0."""
+    [id, log-probability] pairs); values that are not finite are written as null.  Or to a dict {'beams': per prompt the ranked
+    hypotheses of dualhyp_amd.beam_search_batch, 'logprobs': bool}: the prediction is the best hypothesis, every record gains
+    'beams', one {'text', 'sum_logprob', 'avg_logprob', 'finished'} per hypothesis in rank order, and with 'logprobs' the best
+    one's 'sum_logprob' and 'avg_logprob' as above.  Returns corpus metrics on every rank and predictions on rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
     for b in range(0, len(mine), batch_size):
         idxs = mine[b:b + batch_size]
         prompts = [examples[i]["input_ids_no_response"] for i in idxs]
         outs = generate_fn(prompts)
-        lps = tops = None
-        if isinstance(outs, tuple):
+        lps = tops = beams = None
+        if isinstance(outs, dict):
+            beams = outs["beams"]
+            lps = [hyps[0]["token_logprobs"] for hyps in beams] if outs.get("logprobs") else None
+            outs = [hyps[0]["tokens"] for hyps in beams]
+        elif isinstance(outs, tuple):
             if len(outs) == 3:
                 outs, lps, tops = outs
             else:
@@ -79,6 +85,11 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
         for k, (i, p, o) in enumerate(zip(idxs, prompts, outs)):
             preds[i] = {"inference": extract_answer(decode(o), decode(p)),
                         "ground_truth": examples[i]["ground_truth"].strip()}
+            if beams is not None:
+                text = decode(p)
+                preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
+                                      "avg_logprob": _finite_or_none(hyp["sum_logprob"] / max(int(hyp["token_logprobs"].numel()), 1)),
+                                      "finished": bool(hyp["finished"])} for hyp in beams[k]]
             if lps is not None:
                 total = float(lps[k].double().sum())
                 preds[i]["sum_logprob"] = total
@@ -172,7 +183,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     from pathlib import Path
     from .checkpoint import load_checkpoint
     from .data import HypothesesDataset, prompt_ids
-    from .generate import generate_batch, generate_stream
+    from .generate import beam_search_batch, generate_batch, generate_stream
     if adapter_path:
         sd = load_checkpoint(adapter_path)
         missing, unexpected = model.load_state_dict(sd, strict=False)
@@ -246,9 +257,15 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     spec = int(getattr(args, "speculate", 0) or 0)
     top_n = int(getattr(args, "top_logprobs", 0) or 0)
     want_lp = bool(getattr(args, "logprobs", False)) or top_n > 0
+    beams = int(getattr(args, "num_beams", 1) or 1)
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
+        if beams > 1:      # --decode_batch counts decode rows: W per utterance
+            hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
+                                     length_penalty=float(getattr(args, "length_penalty", 1.0)),
+                                     prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)))
+            return {"beams": hyps, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
@@ -263,7 +280,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]]
         return [o.cpu() for o in outs]
 
-    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else args.decode_batch, rank=rank, world=world, eos_id=eos,
+    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
     if mask_stats:
@@ -336,6 +353,12 @@ def build_parser():
                    help="K in 1..8 (implies --logprobs): every record also gains token_ids, token_logprobs and top_logprobs — per generated "
                         "token the K most probable tokens of the model's distribution as [id, log-probability] pairs, by value descending, "
                         "then by id ascending — computed inside the decode steps; the predictions do not depend on it.  Default 0: off")
+    p.add_argument("--num_beams", type=int, default=1, metavar="W",
+                   help="W in 2..4: beam search over W hypotheses per utterance (beam_search_batch), --decode_batch // W utterances at a "
+                        "time; the prediction is the best hypothesis and every record gains beams, the ranked hypotheses with text, "
+                        "sum_logprob, avg_logprob and finished.  Default 1: greedy decoding, the path it always was")
+    p.add_argument("--length_penalty", type=float, default=1.0,
+                   help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
     p.add_argument("--max_new_tokens", type=int, default=150, help="inference/ger.py:71")
     p.add_argument("--predict_dir", type=str, default=None)
@@ -358,6 +381,16 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error(f"--speculate {args.speculate} does not go with --quantize fp8: an fp8 engine has no verify step")
     if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet
         p.error(f"--speculate {args.speculate} goes with --schedule batch: continuous batching steps a row list one token at a time")
+    if not 1 <= args.num_beams <= 4:
+        p.error(f"--num_beams {args.num_beams}: W is 1 (greedy) or 2..4")
+    if args.num_beams > 1:
+        for on, flag, why in ((args.schedule == "continuous", "--schedule continuous", "continuous batching steps a row list one token at a time"),
+                              (bool(args.speculate), f"--speculate {args.speculate}", "a verify step follows one greedy hypothesis"),
+                              (args.quantize == "fp8", "--quantize fp8", "an fp8 engine's step changes its GEMM kernel with the row count"),
+                              (args.share_prefix == "auto", "--share_prefix auto", "the beams' KV slots are forked from whole prompts"),
+                              (bool(args.top_logprobs), f"--top_logprobs {args.top_logprobs}", "the records carry the beams instead")):
+            if on:
+                p.error(f"--num_beams {args.num_beams} does not go with {flag}: {why}")
     if not 0 <= args.top_logprobs <= 8:
         p.error(f"--top_logprobs {args.top_logprobs}: K is 0 (off) or 1..8")
     if args.top_logprobs:

@@ -257,6 +257,34 @@ def token_top_logprobs(logits: torch.Tensor, k: int) -> Tuple[torch.Tensor, torc
     return ids, lp
 
 
+def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optional[int] = None, step: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One beam search step in place on `state` (a dualhyp_amd.beam.BeamState): logits [n_utt * rows_per_utt, vocab], rows_per_utt 1
+    (step 0: the one live beam) or state.W; every utterance with done == 0 gets its W next beams, its records of `step` and its pool
+    entries (dh_beam_select_bf16; the definition is in include/dualhyp_hip.h, "Beam search").  Returns the rows' candidates
+    (ids int32, lp float32, both [rows, 2 W]): token_top_logprobs(logits, 2 W)."""
+    logits = _dev(logits, name="logits")
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
+    rows, vocab = logits.shape
+    W = state.W
+    if rows_per_utt not in (1, W) or rows != state.n_utt * rows_per_utt:
+        raise ValueError(f"beam_select: {rows} rows for {state.n_utt} utterances x rows_per_utt={rows_per_utt} (1 or W={W})")
+    if vocab < 2 * W:
+        raise ValueError(f"beam_select: vocab={vocab} is below the 2 W = {2 * W} candidates of a row")
+    if not 0 <= int(step) < state.max_new:
+        raise ValueError(f"beam_select: step {step} is outside the {state.max_new} recorded steps")
+    if state.device != logits.device:
+        raise ValueError(f"beam_select: the state lives on {state.device}, the logits on {logits.device}")
+    ids = torch.empty((rows, 2 * W), dtype=torch.int32, device=logits.device)
+    lp = torch.empty((rows, 2 * W), dtype=torch.float32, device=logits.device)
+    if rows:
+        import ctypes
+        check(_lib.load().dh_beam_select_bf16(_p(logits), vocab, state.n_utt, int(rows_per_utt), W, state.max_new,
+                                              -1 if eos_id is None else int(eos_id), int(step), None, ctypes.byref(state.c_struct()),
+                                              _p(ids), _p(lp), _stream()))
+    return ids, lp
+
+
 def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool = True) -> torch.Tensor:
     """float32 [rows]: log softmax(logits[r])[ids[r]] of the raw bf16 rows (dh_token_logprobs_bf16; the definition is in
     include/dualhyp_hip.h, "Token log-probabilities").  An id outside [0, vocab) raises before anything is launched

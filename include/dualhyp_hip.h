@@ -28,7 +28,8 @@ typedef uint16_t dh_bf16;
 
 /* ABI 6 gained entries without a change to any existing one (so the number stays): dh_token_logprobs_bf16, dh_sample_bf16_ex,
  * dh_sample_rows_bf16_ex and dh_engine_set_logprobs (token log-probabilities); dh_token_top_logprobs_bf16, dh_sample_bf16_top,
- * dh_sample_rows_bf16_top and dh_engine_set_top_logprobs (token alternatives). */
+ * dh_sample_rows_bf16_top and dh_engine_set_top_logprobs (token alternatives); dh_beam_select_bf16, dh_engine_reserve_beams and
+ * dh_engine_decode_beam (beam search). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -407,6 +408,52 @@ int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, i
                             int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                             void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp);
 
+/* Beam search.  ONE definition for the entries below; tests/beam_reference.py is its host model.
+ * An utterance holds up to W live beams, 1 <= W <= DH_MAX_BEAMS (2 W <= DH_MAX_TOP_LOGPROBS), each with a cumulative score cum
+ * (fp32).  A step takes one raw bf16 logits row per live beam; step 0 has ONE live beam, the prompt's last-position row, cum = 0.
+ *   Candidates of row b: its 2 W alternatives of "Token alternatives" above — ids in that order (value descending, then index
+ *     ascending), lp bit-equal to dh_token_logprobs_bf16.  Candidate (b, j) has score = cum[b] + lp_j, one fp32 add.  Rows are
+ *     finite: NaN / -inf logits are outside the definition (ids still stay inside [0, vocab)); vocab >= 2 W.
+ *   Order: by score descending, then beam b ascending, then rank j ascending.  Within a row the score does not increase with j, so
+ *     the best 2 W of all W * vocab continuations are among these W * 2 W candidates.
+ *   Walk the first 2 W candidates in that order, p = 0, 1, .. being the place in the walk:
+ *     token == eos_id and p < W:  (step, parent b, score, lp_j) is appended to the utterance's finished pool if it holds fewer than W;
+ *     token == eos_id and p >= W: dropped;
+ *     any other token: the next live beam, in walk order — (parent b, token, lp_j, cum' = score) is recorded;
+ *     stop once W live beams are chosen (a row holds eos_id once, so at most W of the 2 W candidates are EOS).
+ *   End: done = 1 when the pool holds W entries; else done = 2 after the step that appends generated token number max_new_tokens.
+ *     The step that ends an utterance still records its W live beams.  eos_id < 0: never finished early.  An utterance with
+ *     done != 0 is left alone: its state and records are frozen.
+ * Histories are never gathered on the device: the records below are per step, and the host backtracks through beam_parent
+ * (dualhyp_amd/beam.py), completes a pool that holds fewer than W entries with the live beams in live order (marked unfinished)
+ * and ranks the pool by sum_logprob / n ** length_penalty in Python floats, n = generated tokens with the EOS counted,
+ * descending, stable on pool order.  No powf runs on the device. */
+#define DH_MAX_BEAMS 4
+/* Device arrays of one beam search call (n_utt utterances, W beams, max_new_tokens steps).  The caller zeroes cum, n_steps, done
+ * and n_fin; the other arrays are written where something is recorded and nowhere else. */
+typedef struct dh_beam_state {
+    float* cum;             /* [n_utt, W]  cumulative score of the live beams */
+    int32_t* n_steps;       /* [n_utt]     steps recorded so far = generated tokens of every live beam */
+    int32_t* done;          /* [n_utt]     0 live, 1 pool full, 2 budget spent */
+    int32_t* beam_tok;      /* [n_utt, max_new_tokens, W]  token of live beam w chosen at step t */
+    int32_t* beam_parent;   /* [n_utt, max_new_tokens, W]  the live beam of step t - 1 it continues (0 at step 0) */
+    float* beam_lp;         /* [n_utt, max_new_tokens, W]  that token's log-probability under its parent's row */
+    float* beam_cum;        /* [n_utt, max_new_tokens, W]  the beam's cumulative score behind that token */
+    int32_t* fin_step;      /* [n_utt, W]  pool: the step whose EOS finished the hypothesis, */
+    int32_t* fin_parent;    /* [n_utt, W]        the live beam of step fin_step - 1 it ends, */
+    float* fin_score;       /* [n_utt, W]        its score, the EOS included, */
+    float* fin_lp;          /* [n_utt, W]        and the EOS's log-probability under the parent's row (score = cum[parent] + fin_lp) */
+    int32_t* n_fin;         /* [n_utt]     entries in the pool */
+} dh_beam_state;
+/* One step of every utterance with done == 0.  logits: [n_utt * rows_per_utt, vocab], rows_per_utt = 1 (step 0: the one live beam
+ * is beam 0) or W (row u * W + b is live beam b of utterance u).  step (0 .. max_new_tokens - 1) indexes the records; step_dev
+ * non-null: read from the device instead (a captured graph stays replayable).  cand_ids (int32) / cand_lp (fp32), both
+ * [n_utt * rows_per_utt, 2 W]: workspace, left holding the rows' candidates.  Two launches: dh_token_top_logprobs_bf16 over the
+ * rows (the per-row part is exactly that entry), then one wave per utterance that merges at most 32 candidates and walks them —
+ * no atomic decides anything. */
+int dh_beam_select_bf16(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens, int64_t eos_id,
+                        int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp, void* stream);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -639,6 +686,27 @@ int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* le
  * n_seq * (n_draft + 1) rows and the KV cache stays at max_batch slots.  Growing drops the captured steps.
  * If the larger workspaces cannot be allocated the call fails and the engine keeps the ones it had. */
 int dh_engine_reserve_rows(dh_engine* e, int rows);
+/* Beam search inside the engine (see "Beam search" above): n_steps x { prep ; forward of n_utt * W rows ; dh_beam_select ; KV
+ * re-parenting }, one linear chain captured on the engine's stream and replayed as dh_engine_decode's step is.  Row u * W + w
+ * feeds beam_tok[u, t - 1, w] at position prompt_len[u] + t - 1 in KV slot u * W + w, t = n_steps[u]; the rows of an utterance
+ * with done != 0 keep stepping with frozen state (they write the position behind their last one, again and again).  After the
+ * selection slot u * W + w must hold the cache of slot u * W + beam_parent[u, t, w]: every layer, K and V^T, the 32-key tiles
+ * prompt_len[u] / 32 .. (prompt_len[u] + t - 1) / 32 (the tiles below are equal in all W slots already) are copied through the
+ * engine's scratch by two launches — parents' tiles to the scratch, scratch to the own slot — so any parent map (swap, fan-out,
+ * identity) is right; rows that continue themselves skip both.  parent, prompt_len and the step are read from device memory: the
+ * captured grid is fixed.
+ * Before the call: the prompts prefilled into slots u * W and forked into the W - 1 slots behind (dh_engine_copy_prefix), step 0
+ * taken by dh_beam_select_bf16 on the prefill's last-position logits (rows_per_utt = 1); first_step >= 1 is the index of the call's
+ * first step, i.e. the steps taken so far.
+ * prompt_len: device int32 [n_utt].  Needs n_utt * W <= max_batch slots and <= 2048 rows of workspace, prompt_len + max_new_tokens
+ * positions in the cache, dh_engine_reserve_beams, and a bf16 engine without the CPU rsqrt emulation (an fp8 engine's step changes
+ * its GEMM kernel with the row count). */
+int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, const int32_t* prompt_len, int n_utt, int W, int max_new_tokens,
+                          int n_steps, int64_t eos_id, int first_step, void* stream);
+/* Size the re-parenting scratch — max_batch rows x every layer's K and V^T x groups x the (max_new_tokens + 30) / 32 + 1 tiles
+ * generated keys can span — and the candidates' workspace for dh_engine_decode_beam calls of up to W beams and max_new_tokens
+ * steps.  W = 1 needs no tile scratch.  Growing drops the captured steps; on failure the engine keeps what it had. */
+int dh_engine_reserve_beams(dh_engine* e, int W, int max_new_tokens);
 /* The buffer (device fp32 [n_seq, tok_ld], the shape of `tokens`; null = off, the default) into which later dh_engine_decode,
  * dh_engine_decode_rows and dh_engine_decode_spec calls write the log-probability of every token they append, beside the token
  * (see "Token log-probabilities" above; a verify step's pick j is scored under its own logits row).  The pointer is part of the
