@@ -1,5 +1,6 @@
 // The selection step of beam search (include/dualhyp_hip.h, "Beam search"): the rows' 2 W candidates by dh_token_top_logprobs_bf16 —
-// row_logsum + row_top of sampling.hip, untouched — then this file's kernel, one wave per utterance, that merges the at most 32
+// row_logsum + row_top of sampling.hip, untouched; under a token mask by dh_token_top_logprobs_bf16_mask, the first 2 W allowed ids of
+// the raw row's order with the raw row's values — then this file's kernel, one wave per utterance, that merges the at most 32
 // candidates, walks them and writes the step's records.  tests/beam_reference.py is the host model.
 #include "common.h"
 
@@ -79,8 +80,11 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const int32_t* __restric
 }  // namespace
 
 int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
-                        const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, void* stream) {
+                        const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, const uint32_t* mask,
+                        int mask_ld, void* stream) {
     DH_CHECK(logits && cand_ids && cand_lp, "dh_beam_select_bf16: null argument");
+    DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, "dh_beam_select_bf16: mask_ld=%d is below the %d words of a %d-token mask row", mask_ld,
+             (vocab + 31) / 32, vocab);
     DH_CHECK(st.cum && st.n_steps && st.done && st.beam_tok && st.beam_parent && st.beam_lp && st.beam_cum && st.fin_step &&
              st.fin_parent && st.fin_score && st.fin_lp && st.n_fin, "dh_beam_select_bf16: the beam state has a null array");
     DH_CHECK(W >= 1 && W <= MAX_W, "dh_beam_select_bf16: W=%d beams, 1 .. %d are supported", W, MAX_W);
@@ -89,7 +93,10 @@ int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_pe
     DH_CHECK(n_utt >= 0 && max_new > 0, "dh_beam_select_bf16: bad shape");
     DH_CHECK(step_dev || (step >= 0 && step < max_new), "dh_beam_select_bf16: step %d is outside the %d recorded steps", step, max_new);
     if (n_utt == 0) return 0;
-    const int rc = dh_token_top_logprobs_bf16(logits, vocab, 2 * W, cand_ids, cand_lp, n_utt * rows_per_utt, stream);
+    // mask row u serves every beam row of utterance u
+    const int rc = mask ? dh_token_top_logprobs_bf16_mask(logits, vocab, 2 * W, cand_ids, cand_lp, n_utt * rows_per_utt, mask, mask_ld,
+                                                          rows_per_utt, stream)
+                        : dh_token_top_logprobs_bf16(logits, vocab, 2 * W, cand_ids, cand_lp, n_utt * rows_per_utt, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(beam_merge_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, cand_ids, cand_lp, rows_per_utt, W, max_new,
                        eos_id, step, step_dev, st);
@@ -102,5 +109,14 @@ extern "C" int dh_beam_select_bf16(const dh_bf16* logits, int vocab, int n_utt, 
                                    float* cand_lp, void* stream) {
     DH_CHECK(st, "dh_beam_select_bf16: null beam state");
     return dh_beam_select_impl(logits, vocab, n_utt, rows_per_utt, W, max_new_tokens, eos_id, step, step_dev, *st, cand_ids, cand_lp,
-                               stream);
+                               nullptr, 0, stream);
+}
+
+extern "C" int dh_beam_select_bf16_mask(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens,
+                                        int64_t eos_id, int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids,
+                                        float* cand_lp, const uint32_t* mask, int mask_ld, void* stream) {
+    DH_CHECK(st, "dh_beam_select_bf16_mask: null beam state");
+    DH_CHECK(mask, "dh_beam_select_bf16_mask: null mask (dh_beam_select_bf16 is the entry without one)");
+    return dh_beam_select_impl(logits, vocab, n_utt, rows_per_utt, W, max_new_tokens, eos_id, step, step_dev, *st, cand_ids, cand_lp,
+                               mask, mask_ld, stream);
 }

@@ -43,6 +43,8 @@ struct dh_engine {
     int top_n = 0;                                      // dh_engine_set_top_logprobs: alternatives per token (0: off) and the
     int32_t* top_ids = nullptr;                         // caller's [n_seq, tok_ld, top_n] buffers
     float* top_lp = nullptr;
+    const uint32_t* mask = nullptr;                     // dh_engine_set_token_mask: the caller's [n_seq, mask_ld] allowed-token words (null: off)
+    int mask_ld = 0;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -76,6 +78,7 @@ struct dh_engine {
         int spec; const int64_t* drafts; int32_t* counters;   // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
         float* logprobs;                                      // dh_engine_set_logprobs: a step captured without the buffer is another kernel
         int top_n; int32_t* top_ids; float* top_lp;           // dh_engine_set_top_logprobs: likewise, and top_n is a kernel argument
+        const uint32_t* mask; int mask_ld;                    // dh_engine_set_token_mask: likewise (beam steps too)
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
@@ -84,7 +87,8 @@ struct dh_engine {
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
-                   logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && beam_w == k.beam_w &&
+                   logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
+                   mask_ld == k.mask_ld && beam_w == k.beam_w &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
@@ -933,7 +937,7 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
     if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
     return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
-                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
+                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, s);
 }
 
 // tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends
@@ -950,7 +954,7 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     int rc;
     if ((rc = run_model(e, e->dec_ids, rows, rows, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if ((rc = dh_beam_select_impl(e->logits, D.vocab, rows / W, W, W, k.max_new, k.eos, 0, e->step_dev, k.beam, e->beam_cand_ids,
-                                  e->beam_cand_lp, s))) return rc;
+                                  e->beam_cand_lp, k.mask, k.mask_ld, s))) return rc;
     if (W == 1) return 0;                                   // a single beam continues itself
     const int tile_units = D.head_size * 4, nt_max = std::min(beam_tiles(k.max_new), e->s_max / 32);
     const dim3 grid(cdiv(nt_max * tile_units, 256), 2 * D.n_layer * D.n_groups, rows);
@@ -975,9 +979,9 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_model(e, e->dec_ids, k.n_seq, k.n_seq, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
-                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
+                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, s);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
-                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, s);
+                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, s);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1193,7 +1197,8 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_LAUNCH_CHECK();
     // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
-                              nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp};
+                              nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
+                              e->mask, e->mask_ld};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1208,7 +1213,8 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
-                              limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp};
+                              limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
+                              e->mask, e->mask_ld};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1255,7 +1261,8 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
-                              limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp};
+                              limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
+                              e->mask, e->mask_ld};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1320,7 +1327,8 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)(first_step - 1));   // the prep kernel counts it up
     DH_LAUNCH_CHECK();
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
-                        prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, W, *st};
+                        prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                        e->mask, e->mask_ld, W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1337,6 +1345,15 @@ extern "C" int dh_engine_set_top_logprobs(dh_engine* e, int k, int32_t* ids, flo
     e->top_n = on ? k : 0;
     e->top_ids = on ? ids : nullptr;
     e->top_lp = on ? lp : nullptr;
+    return 0;
+}
+
+extern "C" int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int mask_ld) {
+    DH_CHECK(e, "dh_engine_set_token_mask: null engine");
+    DH_CHECK(!mask || mask_ld >= (e->d.vocab + 31) / 32, "dh_engine_set_token_mask: mask_ld=%d is below the %d words of a %d-token mask row",
+             mask_ld, (e->d.vocab + 31) / 32, e->d.vocab);
+    e->mask = mask;
+    e->mask_ld = mask ? mask_ld : 0;
     return 0;
 }
 

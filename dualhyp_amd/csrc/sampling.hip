@@ -20,11 +20,21 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 }
 
 constexpr int NT = 1024;
+constexpr bf16_t BF16_NEG_INF = 0xFF80u;
+
+// Token masks (include/dualhyp_hip.h): bit i & 31 of word i >> 5 of the sequence's mask row is set when token i is allowed.  Only
+// columns below vocab are ever asked for, so the bits behind them are never read.
+__device__ __forceinline__ bool mask_allows(const uint32_t* __restrict__ mrow, int i) { return (mrow[i >> 5] >> (i & 31)) & 1u; }
+// the mask byte of the 8 columns 8 c .. 8 c + 7 (a 16-byte load of the row)
+__device__ __forceinline__ uint32_t mask_byte(const uint32_t* __restrict__ mrow, int c) { return (mrow[c >> 2] >> ((c & 3) * 8)) & 255u; }
 
 // The pick of one sequence's next token from its logits row `lg`, by the whole 1024-thread block; every thread
 // returns it.  The draw is keyed by (seed, step, seq).
+// MASK: every logit that feeds the pick goes through the sequence's mask row `mrow` first and is bf16 -inf where the token is not
+// allowed, so the pick is the unmasked pick on a copy of the row with -inf in those columns.  Off: `mrow` is not read.
+template <bool MASK>
 __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k,
-                                          uint64_t seed, int step, int seq) {
+                                          uint64_t seed, int step, int seq, const uint32_t* __restrict__ mrow) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float s_f[NT / 64];
     __shared__ int s_i[NT / 64];
@@ -32,7 +42,10 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
     __shared__ unsigned s_sel[2];
 
     // l = bf16(logit / temperature)   (generate/base.py:62, bf16 tensor / python float)
-    auto scaled = [&](int i) -> bf16_t { return f2bf(bf2f(lg[i]) / temperature); };
+    auto scaled = [&](int i) -> bf16_t {
+        if constexpr (MASK) { if (!mask_allows(mrow, i)) return BF16_NEG_INF; }      // -inf / temperature
+        return f2bf(bf2f(lg[i]) / temperature);
+    };
 
     int choice = 0;
     if (top_k == 1) {
@@ -49,6 +62,11 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
                 uint4 q[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) q[u] = c0 + u * NT < n4 ? lg4[c0 + u * NT] : uint4{0, 0, 0, 0};
+                uint32_t mb[4];
+                if constexpr (MASK) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) mb[u] = c0 + u * NT < n4 ? mask_byte(mrow, c0 + u * NT) : 0u;
+                }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (c0 + u * NT >= n4) break;
@@ -56,7 +74,8 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const int i = (c0 + u * NT) * 8 + e;
-                        const float v = bf2f(f2bf(bf2f(e8[e]) / temperature));
+                        float v = bf2f(f2bf(bf2f(e8[e]) / temperature));
+                        if constexpr (MASK) { if (!((mb[u] >> e) & 1u)) v = -INFINITY; }
                         if (v > best || (v == best && i < bi)) { best = v; bi = i; }
                     }
                 }
@@ -274,8 +293,12 @@ constexpr int MAX_TOP = 8;     // MAX_TOP_LOGPROBS of the header
 // thread keeps the MAX_TOP largest keys of its own entries, sorted, in registers (0 = none: every real key is above it); k rounds of
 // a block-wide maximum over the 1024 list heads, the winner's thread popping its head, merge them.  A NaN is just a key here: ids stay
 // inside [0, vocab) as long as k <= vocab.
+// MASK (the beam candidates under a token mask): the order is taken over the allowed entries only — the first k allowed ids in the
+// raw row's order — and the values are still logprob_at under the raw row's m and tot.  Fewer than k allowed entries leave id 0 in
+// the places behind them (the host refuses such a mask).
+template <bool MASK>
 __device__ __forceinline__ void row_top(const bf16_t* __restrict__ lg, int vocab, int k, float mx, float tot,
-                                        const int32_t*& ids_out, const float*& lp_out) {
+                                        const int32_t*& ids_out, const float*& lp_out, const uint32_t* __restrict__ mrow) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ uint64_t s_head[2][NT / 64];
     __shared__ uint64_t s_win[MAX_TOP];
@@ -307,11 +330,17 @@ __device__ __forceinline__ void row_top(const bf16_t* __restrict__ lg, int vocab
                 if (c0 + u * NT >= n4) break;
                 const bf16_t* e8 = reinterpret_cast<const bf16_t*>(&q[u]);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) offer(e8[e], (c0 + u * NT) * 8 + e);
+                for (int e = 0; e < 8; ++e) {
+                    if constexpr (MASK) { if (!((mask_byte(mrow, c0 + u * NT) >> e) & 1u)) continue; }
+                    offer(e8[e], (c0 + u * NT) * 8 + e);
+                }
             }
         }
     } else {
-        for (int i = tid; i < vocab; i += NT) offer(lg[i], i);
+        for (int i = tid; i < vocab; i += NT) {
+            if constexpr (MASK) { if (!mask_allows(mrow, i)) continue; }
+            offer(lg[i], i);
+        }
     }
     for (int r = 0; r < k; ++r) {
         uint64_t best = c[0];
@@ -352,7 +381,7 @@ __device__ __forceinline__ float row_report(const bf16_t* __restrict__ lg, int v
     if constexpr (TOP) {
         float mx, tot;
         row_logsum(lg, vocab, mx, tot);
-        row_top(lg, vocab, top_n, mx, tot, ti, tl);
+        row_top<false>(lg, vocab, top_n, mx, tot, ti, tl, nullptr);     // the reported alternatives are the raw row's, mask or not
         return logprob_at(lg, choice, mx, tot);
     } else if constexpr (LP) {
         return token_logprob(lg, vocab, choice);
@@ -369,18 +398,20 @@ __device__ __forceinline__ void store_top(int32_t* __restrict__ top_ids, float* 
     }
 }
 
-template <bool LP, bool TOP = false>
+template <bool LP, bool TOP = false, bool MASK = false>
 __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                     int64_t* __restrict__ tokens, int tok_ld,
                                                     int32_t* __restrict__ length, int32_t* __restrict__ done,
                                                     float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                                     int step_arg, const int32_t* __restrict__ step_dev,
                                                     float* __restrict__ logprobs, int top_n,
-                                                    int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
+                                                    int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
+                                                    const uint32_t* __restrict__ mask, int mask_ld) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
-    const int choice = pick_token(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq);
+    const int choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
+                                        MASK ? mask + (size_t)seq * mask_ld : nullptr);
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
     const float lp = row_report<LP, TOP>(logits + (size_t)seq * vocab, vocab, choice, top_n, ti, tl);
@@ -402,7 +433,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
 // (seed, step, row) is when all sequences start together — so a sequence's ids do not depend on when or where it was scheduled.
 // limit[u] = prompt length + max_new is the sequence's own budget (done = 2 when reached).  Several padding rows may name one
 // finished sequence: they return at once.
-template <bool LP, bool TOP = false>
+template <bool LP, bool TOP = false, bool MASK = false>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                          int64_t* __restrict__ tokens, int tok_ld,
                                                          int32_t* __restrict__ length, int32_t* __restrict__ done,
@@ -410,12 +441,14 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          const int32_t* __restrict__ row_seq, int n_seq, int max_new,
                                                          float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                                          float* __restrict__ logprobs, int top_n,
-                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
+                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
+                                                         const uint32_t* __restrict__ mask, int mask_ld) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
     const int step = n - (limit[u] - max_new);          // tokens generated so far
-    const int choice = pick_token(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u);
+    const int choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
+                                        MASK ? mask + (size_t)u * mask_ld : nullptr);     // the sequence's mask row, not the logits row's
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
     const float lp = row_report<LP, TOP>(logits + (size_t)blockIdx.x * vocab, vocab, choice, top_n, ti, tl);
@@ -438,14 +471,15 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
 // behind the sequence's budget limit[u] = prompt length + max_new (done = 2), and a finished sequence is left alone.
 // counters: [0] the last step (1-based, *step_dev) at which a sequence was live, [1] drafts verified, [2] drafts appended.
 // LP: the log-probability of an appended pick_j, from its own row u * S + j, goes to logprobs beside the token; TOP: that row's
-// alternatives too.
-template <bool LP, bool TOP = false>
+// alternatives too.  MASK: all S positions of sequence u are picked under mask row u.
+template <bool LP, bool TOP = false, bool MASK = false>
 __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
                                                          int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
                                                          int32_t* __restrict__ done, const int32_t* __restrict__ limit,
                                                          float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
                                                          int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
-                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
+                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
+                                                         const uint32_t* __restrict__ mask, int mask_ld) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (done[u]) return;
     int n = length[u];
@@ -456,7 +490,8 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
             if (row_ids[(size_t)u * S + j] != (int64_t)prev) break;      // the same for every thread
             __syncthreads();                                             // pick_token's shared scratch is free again
         }
-        const int choice = pick_token(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u);
+        const int choice = pick_token<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u,
+                                            MASK ? mask + (size_t)u * mask_ld : nullptr);
         prev = choice;
         if (n < lim) {                                                    // the same for every thread
             if constexpr (LP) {
@@ -495,21 +530,29 @@ __global__ __launch_bounds__(NT) void token_logprobs_kernel(const bf16_t* __rest
     if (threadIdx.x == 0) out[r] = lp;
 }
 
-// out_ids / out_lp[r, 0..k) = the k alternatives of logits row r
+// out_ids / out_lp[r, 0..k) = the k alternatives of logits row r; MASK: the first k among the ids that mask row r / rows_per_mask
+// allows, with the raw row's values
+template <bool MASK>
 __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __restrict__ logits, int vocab, int k,
-                                                                int32_t* __restrict__ out_ids, float* __restrict__ out_lp) {
+                                                                int32_t* __restrict__ out_ids, float* __restrict__ out_lp,
+                                                                const uint32_t* __restrict__ mask, int mask_ld, int rows_per_mask) {
     const int r = blockIdx.x;
     const bf16_t* lg = logits + (size_t)r * vocab;
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
     float mx, tot;
     row_logsum(lg, vocab, mx, tot);
-    row_top(lg, vocab, k, mx, tot, ti, tl);
+    row_top<MASK>(lg, vocab, k, mx, tot, ti, tl, MASK ? mask + (size_t)(r / rows_per_mask) * mask_ld : nullptr);
     if (threadIdx.x == 0) store_top(out_ids, out_lp, (size_t)r, k, ti, tl);
 }
 
 // the three kernels' variant for (logprobs, top_n): top_n > 0 needs the three buffers
-#define DH_PICK_VARIANT(kernel) (top_n > 0 ? kernel<true, true> : logprobs ? kernel<true> : kernel<false>)
+// and for the token mask: null is the kernel without it (the code it always was)
+#define DH_PICK_VARIANT_M(kernel, M) (top_n > 0 ? kernel<true, true, M> : logprobs ? kernel<true, false, M> : kernel<false, false, M>)
+#define DH_PICK_VARIANT(kernel) (mask ? DH_PICK_VARIANT_M(kernel, true) : DH_PICK_VARIANT_M(kernel, false))
+#define DH_CHECK_MASK(name)                                                                                                    \
+    DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, name ": mask_ld=%d is below the %d words of a %d-token mask row", mask_ld, \
+             (vocab + 31) / 32, vocab)
 #define DH_CHECK_TOP(name)                                                                                                     \
     DH_CHECK(top_n >= 0 && top_n <= MAX_TOP && top_n <= vocab, name ": top_logprobs must be 0 .. min(8, vocab)");              \
     DH_CHECK(top_n == 0 || (logprobs && top_ids && top_lp), name ": top_logprobs needs the logprobs, top_ids and top_lp buffers")
@@ -518,16 +561,18 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
-                   const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, void* stream) {
+                   const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                   int mask_ld, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
     DH_CHECK_TOP("dh_sample_bf16");
+    DH_CHECK_MASK("dh_sample_bf16");
     DH_CHECK(temperature > 0.f, "dh_sample_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
     // logprobs null: the kernel without the log-probability pass (the code it always was)
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp);
+                       top_ids, top_lp, mask, mask_ld);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -536,14 +581,23 @@ extern "C" int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* toke
                                  int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                  int step, void* stream, float* logprobs) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, 0, nullptr, nullptr, stream);
+                          nullptr, logprobs, 0, nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int dh_sample_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, stream);
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, stream);
+}
+
+extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                   const uint32_t* mask, int mask_ld) {
+    DH_CHECK(mask, "dh_sample_bf16_mask: null mask (dh_sample_bf16_top is the entry without one)");
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, stream);
 }
 
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -556,16 +610,17 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        void* stream) {
+                        const uint32_t* mask, int mask_ld, void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
     DH_CHECK_TOP("dh_sample_rows_bf16");
+    DH_CHECK_MASK("dh_sample_rows_bf16");
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -575,7 +630,7 @@ extern "C" int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t*
                                       int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                       float* logprobs) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, stream);
+                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -583,7 +638,17 @@ extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t
                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, stream);
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, stream);
+}
+
+extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                        int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                        int mask_ld) {
+    DH_CHECK(mask, "dh_sample_rows_bf16_mask: null mask (dh_sample_rows_bf16_top is the entry without one)");
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, stream);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -596,15 +661,16 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
                         const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        void* stream) {
+                        const uint32_t* mask, int mask_ld, void* stream) {
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
     DH_CHECK_TOP("spec_accept");
+    DH_CHECK_MASK("spec_accept");
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
-                       counters, logprobs, top_n, top_ids, top_lp);
+                       counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -624,7 +690,22 @@ extern "C" int dh_token_top_logprobs_bf16(const dh_bf16* logits, int vocab, int 
     DH_CHECK(vocab > 0 && n_rows >= 0, "dh_token_top_logprobs_bf16: bad shape");
     DH_CHECK(k >= 1 && k <= MAX_TOP && k <= vocab, "dh_token_top_logprobs_bf16: k must be 1 .. min(8, vocab)");
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(token_top_logprobs_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, k, out_ids, out_lp);
+    hipLaunchKernelGGL(token_top_logprobs_kernel<false>, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, k, out_ids, out_lp,
+                       nullptr, 0, 1);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_token_top_logprobs_bf16_mask(const dh_bf16* logits, int vocab, int k, int32_t* out_ids, float* out_lp, int n_rows,
+                                               const uint32_t* mask, int mask_ld, int rows_per_mask, void* stream) {
+    DH_CHECK(logits && out_ids && out_lp, "dh_token_top_logprobs_bf16_mask: null argument");
+    DH_CHECK(mask, "dh_token_top_logprobs_bf16_mask: null mask (dh_token_top_logprobs_bf16 is the entry without one)");
+    DH_CHECK(vocab > 0 && n_rows >= 0 && rows_per_mask >= 1, "dh_token_top_logprobs_bf16_mask: bad shape");
+    DH_CHECK(k >= 1 && k <= MAX_TOP && k <= vocab, "dh_token_top_logprobs_bf16_mask: k must be 1 .. min(8, vocab)");
+    DH_CHECK_MASK("dh_token_top_logprobs_bf16_mask");
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(token_top_logprobs_kernel<true>, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, k, out_ids, out_lp,
+                       mask, mask_ld, rows_per_mask);
     DH_LAUNCH_CHECK();
     return 0;
 }

@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import beam as _beam
+from . import constrain as _constrain
 from . import ops
 from .gpt import GPT
 from .schedule import shared_prefix_len
@@ -54,6 +55,19 @@ def _check_top_logprobs(model: GPT, top_logprobs, return_logprobs: bool) -> int:
     return K
 
 
+def _token_mask(model: GPT, token_mask, n: int, need: int, dev) -> Optional[torch.Tensor]:
+    """The call's token mask on the device, checked before anything is launched (constrain.check_mask: one read-back), or None.
+    token_mask: an int32 [n, ceil(vocab / 32)] tensor on the model's device, or a list of n id lists, packed here."""
+    if token_mask is None:
+        return None
+    vocab = model.config.padded_vocab_size
+    if not isinstance(token_mask, torch.Tensor):
+        if len(token_mask) != n:
+            raise ValueError(f"token_mask holds {len(token_mask)} id lists for {n} prompts")
+        token_mask = _constrain.pack_mask(token_mask, vocab, dev)
+    return _constrain.check_mask(token_mask, n, vocab, need, device=dev)
+
+
 def _top_buffers(shape, K: int, dev):
     """The alternatives' buffers beside a token buffer of `shape`: ids -1 and values NaN where no token was produced."""
     return (torch.full(tuple(shape) + (K,), -1, dtype=torch.int32, device=dev),
@@ -73,7 +87,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
                    share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
-                   return_logprobs: bool = False, top_logprobs: int = 0):
+                   return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -108,7 +122,14 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     raw logits row it was picked from — by value descending, then by index ascending (-0 == +0) — and their log-probabilities by
     the definition above, sharing its m and its sum (include/dualhyp_hip.h, "Token alternatives").  Written by the same kernels
     into [B, tok_ld, K] buffers filled with -1 / NaN (state["top_ids"], state["top_logprobs"]).  Ids, logprobs, steps and
-    read-backs are those of the call without it."""
+    read-backs are those of the call without it.
+
+    token_mask (constrained decoding; include/dualhyp_hip.h, "Token masks"): an int32 [B, ceil(vocab / 32)] tensor on the model's
+    device (constrain.pack_mask), or a list of B id lists that is packed here — sequence i produces only ids that row i allows
+    (allow the EOS if the sequence is to end on it), as if every other logit were -inf, with whatever sampler the call uses.  Every
+    row allows at least one id (checked with one read-back before anything is launched).  The pick happens inside the sampling
+    kernels — the prefill's first pick and every captured decode or verify step — and the log-probabilities and alternatives stay
+    the raw row's.  It goes with speculate, share_prefix, return_logprobs and top_logprobs, none of which it touches."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
@@ -121,6 +142,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     if model.max_seq_length < need_pos:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     dev = model.transformer.wte.weight.device
+    mask = _token_mask(model, token_mask, B, 1, dev)
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
     P = _shared_prefix(model, prompts, share_prefix, dev)
     # a verify step writes K / V up to D positions behind the last token (as far as the model has positions) and runs D + 1 rows per
@@ -161,13 +183,15 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
-               top_logprobs=top_buf)
+               top_logprobs=top_buf, mask=mask)
     if ev:
         ev[1].record()
     if lp_buf is not None:
         eng.set_logprobs(lp_buf)        # part of the captured step's key; without it the call runs the steps it always ran
     if top_buf is not None:
         eng.set_top_logprobs(*top_buf)  # likewise
+    if mask is not None:
+        eng.set_token_mask(mask)        # likewise
     try:
         steps_run = 0
         if max_new_tokens > 1:
@@ -200,6 +224,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             eng.set_logprobs(None)      # the buffer is this call's
         if top_buf is not None:
             eng.set_top_logprobs(None)
+        if mask is not None:
+            eng.set_token_mask(None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -244,7 +270,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
 
 @torch.inference_mode()
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
-                      length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False):
+                      length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
+                      token_mask=None):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
@@ -267,7 +294,11 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     is open.
 
     timing gains prefill_ms, decode_ms, decode_steps, decode_row_steps, and beam_step_rows / beam_copied_rows: the rows of the steps
-    that utterances took, and those among them that continued another beam and were copied."""
+    that utterances took, and those among them that continued another beam and were copied.
+
+    token_mask (as in generate_batch, one row per utterance, serving all of its W beams): a beam row's 2 W candidates are the first
+    2 W allowed ids of its raw row's order, each with the raw row's log-probability ("Token masks" of the header), so every row
+    allows at least 2 W ids (checked before anything is launched); everything behind the candidates is unchanged."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     W = _beam.check_arguments(model, num_beams, B)
@@ -278,6 +309,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     if model.max_seq_length < need_pos:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     dev = model.transformer.wte.weight.device
+    mask = _token_mask(model, token_mask, B, 2 * W, dev)
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
     rows = B * W
     eng = model.engine(rows, need_pos, max(rows, max(sum(lens[a:b]) for a, b in chunks)), exact=rows > prefill_batch)
@@ -295,16 +327,22 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     if W > 1:
         for u in range(B):      # positions at or behind the prompt's end are overwritten before causality lets anything read them
             eng.copy_prefix(u * W, list(range(u * W + 1, (u + 1) * W)), -(-lens[u] // 32) * 32)
-    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0)
+    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0, mask=mask)
     if ev:
         ev[1].record()
     step = 1
-    while step < max_new_tokens:
-        c = max_new_tokens - step if eos_id is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
-        eng.decode_beam(state, plen, c, eos_id, first_step=step)
-        step += c
-        if step < max_new_tokens and bool((state.done != 0).all()):
-            break
+    if mask is not None:
+        eng.set_token_mask(mask)        # part of the captured step's key; without it the call runs the steps it always ran
+    try:
+        while step < max_new_tokens:
+            c = max_new_tokens - step if eos_id is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
+            eng.decode_beam(state, plen, c, eos_id, first_step=step)
+            step += c
+            if step < max_new_tokens and bool((state.done != 0).all()):
+                break
+    finally:
+        if mask is not None:
+            eng.set_token_mask(None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these hypotheses; a later cached forward must start at 0
@@ -335,7 +373,7 @@ class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
-                 logprobs: bool = False, top_logprobs: int = 0) -> None:
+                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -352,6 +390,8 @@ class _StreamBackend:
         # beside `tokens`: the log-probability of every sampled token (generate_batch's return_logprobs), NaN where none was
         self.logprobs = torch.full(tuple(self.tokens.shape), float("nan"), dtype=torch.float32, device=dev) if logprobs else None
         self.top = _top_buffers(self.tokens.shape, top_logprobs, dev) if top_logprobs else None   # generate_batch's top_logprobs
+        # the call's token mask (generate_batch's token_mask) and an all-ones row for the dummy sequence, which never picks
+        self.mask = None if mask is None else torch.cat([mask, torch.full_like(mask[:1], -1)]).contiguous()
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -373,7 +413,7 @@ class _StreamBackend:
         # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
-                        self.max_new, logprobs=self.logprobs, top_logprobs=self.top, **self.kw)
+                        self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, **self.kw)
         if end:
             end.record()
 
@@ -398,7 +438,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
-                    top_logprobs: int = 0):
+                    top_logprobs: int = 0, token_mask=None):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -413,7 +453,10 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     hands out before the first prefill; no sequence of the call writes below position P, so they outlive every refill, and a
     refill is a prefill of the tokens [P:] at position P.  The scheduler's decisions are those of the unshared call.
 
-    return_logprobs, top_logprobs: as in generate_batch — (out, logprobs[, top]), the same values bit for bit."""
+    return_logprobs, top_logprobs: as in generate_batch — (out, logprobs[, top]), the same values bit for bit.
+
+    token_mask: as in generate_batch, one row per prompt; a sequence is picked under its own row wherever it is scheduled (the
+    row-list sampler reads mask row row_seq[r]); the dummy sequence of the padding rows gets an all-ones row."""
     from .schedule import StreamScheduler
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     if speculate:
@@ -427,13 +470,14 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
     dev = model.transformer.wte.weight.device
+    mask = _token_mask(model, token_mask, N, 1, dev)
     P = _shared_prefix(model, prompts, share_prefix, dev)
     # slots 0..max_rows-1 and the spare one; a prefill packs at most the prefill_batch longest prompts (their tokens behind the prefix)
     eng = model.engine(sched.max_rows + 1, need_pos, max(P, sum(sorted(n - P for n in lens)[-prefill_batch:])), exact=True)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K)
+                        top_logprobs=K, mask=mask)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -443,6 +487,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         eng.set_logprobs(be.logprobs)   # part of the captured steps' key; without it the call runs the steps it always ran
     if K:
         eng.set_top_logprobs(*be.top)
+    if mask is not None:
+        eng.set_token_mask(be.mask)
     try:
         sched.run(be)
     finally:
@@ -450,6 +496,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             eng.set_logprobs(None)      # the buffer is this call's
         if K:
             eng.set_top_logprobs(None)
+        if mask is not None:
+            eng.set_token_mask(None)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
@@ -479,17 +527,17 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
-             top_logprobs: int = 0):
+             top_logprobs: int = 0, token_mask=None):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
-    top values))."""
+    top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list."""
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                         speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs)
+                         speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

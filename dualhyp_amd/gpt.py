@@ -466,6 +466,8 @@ class _Engine:
         """n_steps beam steps of state.n_utt utterances x state.W beams, the first one step number first_step >= 1
         (dh_engine_decode_beam; `state` is a dualhyp_amd.beam.BeamState, prompt_len int32 [n_utt] on the GPU)."""
         assert prompt_len.dtype == torch.int32 and prompt_len.is_cuda and prompt_len.is_contiguous() and prompt_len.numel() == state.n_utt
+        mask = getattr(self, "_token_mask", None)
+        assert mask is None or mask.size(0) == state.n_utt, "the token mask has one row per utterance"
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_decode_beam(
                 self.handle, C.byref(state.c_struct()), prompt_len.data_ptr(), state.n_utt, state.W, state.max_new, int(n_steps),
@@ -495,12 +497,24 @@ class _Engine:
         self._top = (ids, lp)
         _lib.check(self.lib.dh_engine_set_top_logprobs(self.handle, ids.size(2), ids.data_ptr(), lp.data_ptr()))
 
+    def set_token_mask(self, mask: Optional[torch.Tensor]) -> None:
+        """The int32 token mask, [sequences or utterances of the decode calls, ceil(vocab / 32)], under which later decode /
+        decode_rows / decode_spec / decode_beam calls pick (dh_engine_set_token_mask; include/dualhyp_hip.h, "Token masks"); None
+        turns it off.  The caller keeps it alive while set."""
+        if mask is not None and (mask.dtype != torch.int32 or not mask.is_cuda or not mask.is_contiguous() or mask.dim() != 2):
+            raise TypeError("set_token_mask takes a contiguous 2-D int32 tensor on the GPU, or None")
+        self._token_mask = mask
+        _lib.check(self.lib.dh_engine_set_token_mask(self.handle, None if mask is None else mask.data_ptr(),
+                                                     0 if mask is None else mask.size(1)))
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"
         top = getattr(self, "_top", None)
         assert top is None or (buf is not None and tuple(top[0].shape[:2]) == tuple(tokens.shape)), \
             "the top_logprobs buffers go with a logprobs buffer and have the shape of tokens, times K"
+        mask = getattr(self, "_token_mask", None)
+        assert mask is None or mask.size(0) == tokens.size(0), "the token mask has one row per row of tokens"
 
     def graph_count(self, n_draft: int = -1) -> int:
         """Captured decode steps kept for n_draft drafts (0: the plain steps, -1: all)."""

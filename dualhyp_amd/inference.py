@@ -8,6 +8,7 @@ gathered to rank 0.  No collective runs inside the decode loop.
 from __future__ import annotations
 
 import math
+from pathlib import Path
 from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import torch
@@ -65,7 +66,9 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     [id, log-probability] pairs); values that are not finite are written as null.  Or to a dict {'beams': per prompt the ranked
     hypotheses of dualhyp_amd.beam_search_batch, 'logprobs': bool}: the prediction is the best hypothesis, every record gains
     'beams', one {'text', 'sum_logprob', 'avg_logprob', 'finished'} per hypothesis in rank order, and with 'logprobs' the best
-    one's 'sum_logprob' and 'avg_logprob' as above.  Returns corpus metrics on every rank and predictions on rank 0."""
+    one's 'sum_logprob' and 'avg_logprob' as above.  A generate_fn with a true attribute `constrained` (--constrain: it decodes under
+    per-utterance token masks) marks every record with 'constrained': true.  Returns corpus metrics on every rank and predictions on
+    rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
     for b in range(0, len(mine), batch_size):
@@ -85,6 +88,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
         for k, (i, p, o) in enumerate(zip(idxs, prompts, outs)):
             preds[i] = {"inference": extract_answer(decode(o), decode(p)),
                         "ground_truth": examples[i]["ground_truth"].strip()}
+            if getattr(generate_fn, "constrained", False):
+                preds[i]["constrained"] = True
             if beams is not None:
                 text = decode(p)
                 preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
@@ -117,6 +122,19 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
 
 
 # ------------------------------------------------------------------------------------------ harness
+def read_token_ids(path) -> List[int]:
+    """The token ids of a --constrain_extra file: one non-negative integer per line; blank lines and `#` comments are skipped."""
+    ids = []
+    for n, line in enumerate(Path(path).read_text().splitlines(), 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        if not line.isdigit():
+            raise ValueError(f"{path}:{n}: a token id is a non-negative integer, got {line!r}")
+        ids.append(int(line))
+    return ids
+
+
 def add_lora_arguments(parser) -> None:
     """The LoRA flags shared by both reference harnesses (inference/ger.py:145-153, finetune/ger.py:386-394).
     `type=bool` is the reference's: any non-empty string is True, so the flags are effectively constants."""
@@ -183,6 +201,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     from pathlib import Path
     from .checkpoint import load_checkpoint
     from .data import HypothesesDataset, prompt_ids
+    from .constrain import allowed_from_prompts, pack_mask
     from .generate import beam_search_batch, generate_batch, generate_stream
     if adapter_path:
         sd = load_checkpoint(adapter_path)
@@ -258,28 +277,33 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     top_n = int(getattr(args, "top_logprobs", 0) or 0)
     want_lp = bool(getattr(args, "logprobs", False)) or top_n > 0
     beams = int(getattr(args, "num_beams", 1) or 1)
+    constrain = getattr(args, "constrain", "off") == "prompt"
+    extra = read_token_ids(args.constrain_extra) if constrain and getattr(args, "constrain_extra", None) else ()
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
+        # --constrain prompt: an utterance may emit the ids of its own prompt (its hypotheses and the template), the EOS and the extras
+        mask = pack_mask(allowed_from_prompts(prompts, eos, extra), model.config.padded_vocab_size, dev) if constrain else None
         if beams > 1:      # --decode_batch counts decode rows: W per utterance
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
-                                     prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)))
+                                     prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask)
             return {"beams": hyps, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
-                                   share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n)
+                                   share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask)
         else:
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
-                                  return_logprobs=want_lp, top_logprobs=top_n)
+                                  return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask)
         if top_n:
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]], [(a.cpu(), b.cpu()) for a, b in outs[2]]
         if want_lp:
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]]
         return [o.cpu() for o in outs]
 
+    gen.constrained = constrain
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -357,6 +381,13 @@ def build_parser():
                    help="W in 2..4: beam search over W hypotheses per utterance (beam_search_batch), --decode_batch // W utterances at a "
                         "time; the prediction is the best hypothesis and every record gains beams, the ranked hypotheses with text, "
                         "sum_logprob, avg_logprob and finished.  Default 1: greedy decoding, the path it always was")
+    p.add_argument("--constrain", choices=("off", "prompt"), default="off",
+                   help="prompt: constrained decoding — an utterance may emit only token ids that occur in its own prompt (its n-best "
+                        "hypotheses and the template), the EOS and the ids of --constrain_extra; the mask is applied inside the sampling "
+                        "kernels, under both schedules and with --num_beams; every record gains constrained: true.  Default off: the "
+                        "path it always was")
+    p.add_argument("--constrain_extra", type=str, default=None, metavar="FILE",
+                   help="with --constrain prompt: a file of token ids, one per line, allowed for every utterance")
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
@@ -391,6 +422,8 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                               (bool(args.top_logprobs), f"--top_logprobs {args.top_logprobs}", "the records carry the beams instead")):
             if on:
                 p.error(f"--num_beams {args.num_beams} does not go with {flag}: {why}")
+    if args.constrain_extra and args.constrain == "off":
+        p.error("--constrain_extra goes with --constrain prompt")
     if not 0 <= args.top_logprobs <= 8:
         p.error(f"--top_logprobs {args.top_logprobs}: K is 0 (off) or 1..8")
     if args.top_logprobs:

@@ -241,10 +241,32 @@ def _top_buffers(top: Optional[Tuple[torch.Tensor, torch.Tensor]], logprobs: Opt
     return check_top_logprobs(int(ids.size(2)), vocab, lowest=1), ids, lp
 
 
-def token_top_logprobs(logits: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def _mask_arg(mask: Optional[torch.Tensor], n_rows: int, vocab: int, device):
+    """(pointer, mask_ld) of a token mask for n_rows sequences (include/dualhyp_hip.h, "Token masks"): int32 [n_rows, >= ceil(vocab /
+    32) words] on the logits' device, unit stride within a row, any row stride that holds the words; (None, 0) without one."""
+    if mask is None:
+        return None, 0
+    if not mask.is_cuda:
+        raise _lib.DualHypHipError("mask must live on the GPU: the HIP path has no CPU fallback")
+    if mask.dtype != torch.int32:
+        raise TypeError(f"mask must be {torch.int32}, got {mask.dtype}")
+    words = (vocab + 31) // 32
+    if mask.dim() != 2 or mask.size(0) != n_rows or mask.size(1) < words:
+        raise ValueError(f"mask must be [{n_rows}, >= {words}] for {n_rows} sequences over {vocab} tokens, got {tuple(mask.shape)}")
+    if mask.device != device:
+        raise ValueError(f"the mask lives on {mask.device}, the logits on {device}")
+    ld = int(mask.stride(0)) if n_rows > 1 else max(int(mask.stride(0)), int(mask.size(1)))
+    if mask.stride(1) != 1 or ld < words:
+        raise ValueError(f"mask rows must have unit stride and a row stride of at least {words} words, got strides {tuple(mask.stride())}")
+    return mask.data_ptr(), ld
+
+
+def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
     index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
-    definition is in include/dualhyp_hip.h, "Token alternatives").  1 <= k <= min(8, vocab)."""
+    definition is in include/dualhyp_hip.h, "Token alternatives").  1 <= k <= min(8, vocab).  mask (int32 [rows, words], "Token
+    masks"): the first k ids that the row's mask allows, in that order, with the raw row's values — the beam candidates under a
+    mask (dh_token_top_logprobs_bf16_mask)."""
     logits = _dev(logits, name="logits")
     if logits.dim() != 2:
         raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
@@ -252,16 +274,21 @@ def token_top_logprobs(logits: torch.Tensor, k: int) -> Tuple[torch.Tensor, torc
     k = check_top_logprobs(k, vocab, lowest=1)
     ids = torch.empty((rows, k), dtype=torch.int32, device=logits.device)
     lp = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
-    if rows:
+    m_ptr, m_ld = _mask_arg(mask, rows, vocab, logits.device)
+    if rows and mask is not None:
+        check(_lib.load().dh_token_top_logprobs_bf16_mask(_p(logits), vocab, k, _p(ids), _p(lp), rows, m_ptr, m_ld, 1, _stream()))
+    elif rows:
         check(_lib.load().dh_token_top_logprobs_bf16(_p(logits), vocab, k, _p(ids), _p(lp), rows, _stream()))
     return ids, lp
 
 
-def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optional[int] = None, step: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optional[int] = None, step: int = 0,
+                mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One beam search step in place on `state` (a dualhyp_amd.beam.BeamState): logits [n_utt * rows_per_utt, vocab], rows_per_utt 1
     (step 0: the one live beam) or state.W; every utterance with done == 0 gets its W next beams, its records of `step` and its pool
     entries (dh_beam_select_bf16; the definition is in include/dualhyp_hip.h, "Beam search").  Returns the rows' candidates
-    (ids int32, lp float32, both [rows, 2 W]): token_top_logprobs(logits, 2 W)."""
+    (ids int32, lp float32, both [rows, 2 W]): token_top_logprobs(logits, 2 W).  mask (int32 [n_utt, words], "Token masks"): row u
+    serves every beam row of utterance u; the candidates are the first 2 W allowed ids of each row (dh_beam_select_bf16_mask)."""
     logits = _dev(logits, name="logits")
     if logits.dim() != 2:
         raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
@@ -277,11 +304,15 @@ def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optio
         raise ValueError(f"beam_select: the state lives on {state.device}, the logits on {logits.device}")
     ids = torch.empty((rows, 2 * W), dtype=torch.int32, device=logits.device)
     lp = torch.empty((rows, 2 * W), dtype=torch.float32, device=logits.device)
+    m_ptr, m_ld = _mask_arg(mask, state.n_utt, vocab, logits.device)
     if rows:
         import ctypes
-        check(_lib.load().dh_beam_select_bf16(_p(logits), vocab, state.n_utt, int(rows_per_utt), W, state.max_new,
-                                              -1 if eos_id is None else int(eos_id), int(step), None, ctypes.byref(state.c_struct()),
-                                              _p(ids), _p(lp), _stream()))
+        args = (_p(logits), vocab, state.n_utt, int(rows_per_utt), W, state.max_new, -1 if eos_id is None else int(eos_id), int(step), None,
+                ctypes.byref(state.c_struct()), _p(ids), _p(lp))
+        if mask is not None:
+            check(_lib.load().dh_beam_select_bf16_mask(*args, m_ptr, m_ld, _stream()))
+        else:
+            check(_lib.load().dh_beam_select_bf16(*args, _stream()))
     return ids, lp
 
 
@@ -310,30 +341,35 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool =
 def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, *,
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
            step: int = 0, logprobs: Optional[torch.Tensor] = None,
-           top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
+           top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
-    same place in them (dh_sample_bf16_top)."""
+    same place in them (dh_sample_bf16_top).  mask (int32 [n_seq, words], "Token masks" of the header): row u holds the tokens
+    sequence u may pick; the log-probabilities and alternatives stay the raw row's (dh_sample_bf16_mask)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_seq, vocab = logits.shape
     assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.size(0) == n_seq
     logprobs = _logprobs_buffer(logprobs, tokens)
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
-    check(_lib.load().dh_sample_bf16_top(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
-                                         k(done, torch.int32), n_seq, float(temperature),
-                                         0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id),
-                                         int(seed) & ((1 << 64) - 1), int(step), _stream(), _p(logprobs), top_n, _p(top_ids),
-                                         _p(top_lp)))
+    m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
+    args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
+            0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
+            _p(logprobs), top_n, _p(top_ids), _p(top_lp))
+    if mask is not None:
+        check(_lib.load().dh_sample_bf16_mask(*args, m_ptr, m_ld))
+    else:
+        check(_lib.load().dh_sample_bf16_top(*args))
 
 
 def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor,
                 row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
                 eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None,
-                top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
+                top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
-    in sample()."""
+    in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
+    (dh_sample_rows_bf16_mask)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_rows, vocab = logits.shape
@@ -342,11 +378,14 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     assert length.numel() == done.numel() == limit.numel() == n_seq
     logprobs = _logprobs_buffer(logprobs, tokens)
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
-    check(_lib.load().dh_sample_rows_bf16_top(_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32),
-                                              k(done, torch.int32), k(limit, torch.int32), k(row_seq, torch.int32), n_rows, n_seq,
-                                              int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
-                                              -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(),
-                                              _p(logprobs), top_n, _p(top_ids), _p(top_lp)))
+    m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
+    args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
+            k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
+            -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
+    if mask is not None:
+        check(_lib.load().dh_sample_rows_bf16_mask(*args, m_ptr, m_ld))
+    else:
+        check(_lib.load().dh_sample_rows_bf16_top(*args))
 
 
 def quant_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -29,7 +29,8 @@ typedef uint16_t dh_bf16;
 /* ABI 6 gained entries without a change to any existing one (so the number stays): dh_token_logprobs_bf16, dh_sample_bf16_ex,
  * dh_sample_rows_bf16_ex and dh_engine_set_logprobs (token log-probabilities); dh_token_top_logprobs_bf16, dh_sample_bf16_top,
  * dh_sample_rows_bf16_top and dh_engine_set_top_logprobs (token alternatives); dh_beam_select_bf16, dh_engine_reserve_beams and
- * dh_engine_decode_beam (beam search). */
+ * dh_engine_decode_beam (beam search); dh_sample_bf16_mask, dh_sample_rows_bf16_mask, dh_token_top_logprobs_bf16_mask,
+ * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -454,6 +455,45 @@ typedef struct dh_beam_state {
 int dh_beam_select_bf16(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens, int64_t eos_id,
                         int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp, void* stream);
 
+/* Token masks (constrained decoding).  ONE definition for every entry below.
+ * A token mask is a device array of 32-bit words [n_seq, mask_ld], mask_ld >= ceil(vocab / 32): bit i & 31 of word i >> 5 of row u is
+ * set when token i is allowed for sequence u.  Bits at or beyond vocab are ignored, whatever they hold.  A null mask means the
+ * feature is off: the entries without `_mask`, and the kernels they always ran.  The mask is only read.
+ *   The mask belongs to the sampler, as top_k and temperature do.  A disallowed column takes part in the pick as if its logit were
+ *     bf16 -inf (0xFF80): it is never the arg-max (on ties the lowest ALLOWED index wins), it does not count toward the top_k
+ *     threshold (the k largest among the allowed ids are kept), and it adds 0 to the sampler's softmax.  For any row with at least
+ *     one allowed logit above -inf the picked id equals what the entry without a mask picks on a copy of the row with 0xFF80 in every
+ *     disallowed column — for top_k 1, k and none, and for the same (seed, step, seq) draw.  A row whose allowed logits are all -inf
+ *     is outside the definition, as NaN is: it still produces an id in [0, vocab) and writes nothing else.
+ *   Log-probabilities stay the model's: logprobs[u, n] is lp(picked id) of "Token log-probabilities" under the RAW row, with the
+ *     same m and the same sum, and top_ids / top_lp are the raw row's alternatives, allowed or not — scores still compare with
+ *     dh_token_logprobs_bf16 and with unconstrained runs.
+ *   Which mask row a kernel reads: dh_sample_* row u of the block's sequence; dh_sample_rows_* row row_seq[r]; a verify step
+ *     (dh_engine_decode_spec) row u for all D + 1 positions of sequence u; beam search row u of the utterance for all W beams.
+ *   Beam candidates under a mask: the 2 W candidates of a beam row are the first 2 W ALLOWED ids in the raw row's order (value
+ *     descending, index ascending, -0 == +0), each with the raw row's log-probability, bit-equal to dh_token_logprobs_bf16 for the
+ *     id.  Every utterance's row allows at least 2 W ids below vocab (the caller checks: dualhyp_amd.constrain.check_mask).  The
+ *     merge, the walk, the pool and the re-parenting are unchanged. */
+
+/* dh_sample_bf16_top / dh_sample_rows_bf16_top under a mask (non-null; mask_ld >= ceil(vocab / 32), refused before any launch). */
+int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                        int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                        uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                        const uint32_t* mask, int mask_ld);
+int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                             int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                             int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                             void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                             const uint32_t* mask, int mask_ld);
+/* dh_token_top_logprobs_bf16 over the allowed ids: out_ids[r, 0..k) are the first k ids that mask row r / rows_per_mask allows, in
+ * the raw row's order; out_lp are their raw log-probabilities.  A row that allows fewer than k ids leaves id 0 behind them. */
+int dh_token_top_logprobs_bf16_mask(const dh_bf16* logits, int vocab, int k, int32_t* out_ids, float* out_lp, int n_rows,
+                                    const uint32_t* mask, int mask_ld, int rows_per_mask, void* stream);
+/* dh_beam_select_bf16 with the candidates taken under mask [n_utt, mask_ld] (see "Beam candidates under a mask"). */
+int dh_beam_select_bf16_mask(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens, int64_t eos_id,
+                             int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp,
+                             const uint32_t* mask, int mask_ld, void* stream);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -719,6 +759,12 @@ int dh_engine_set_logprobs(dh_engine* e, float* buf);
  * decode call with k > 0 and no logprobs buffer fails.  k and both pointers are part of the captured step's key, exactly as the
  * logprobs pointer is.  The caller keeps the buffers alive while they are set. */
 int dh_engine_set_top_logprobs(dh_engine* e, int k, int32_t* ids, float* lp);
+/* The token mask (device words [n_seq, mask_ld], mask_ld >= ceil(vocab / 32); null = off, the default) under which later
+ * dh_engine_decode, dh_engine_decode_rows, dh_engine_decode_spec and dh_engine_decode_beam calls pick their tokens and beam
+ * candidates (see "Token masks" above: row u is sequence u's, or utterance u's).  The pointer and mask_ld are part of the captured
+ * step's key, exactly as the logprobs pointer is: with the mask unset a decode call runs the graphs it always ran.  The caller
+ * keeps the mask alive, and may change its contents between calls, while it is set. */
+int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int mask_ld);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
