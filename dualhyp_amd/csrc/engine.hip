@@ -45,6 +45,8 @@ struct dh_engine {
     float* top_lp = nullptr;
     const uint32_t* mask = nullptr;                     // dh_engine_set_token_mask: the caller's [n_seq, mask_ld] allowed-token words (null: off)
     int mask_ld = 0;
+    int ngram = 0;                                      // dh_engine_set_no_repeat_ngram: n (0: off) and the caller's [n_seq] prompt lengths
+    const int32_t* ngram_start = nullptr;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -79,6 +81,7 @@ struct dh_engine {
         float* logprobs;                                      // dh_engine_set_logprobs: a step captured without the buffer is another kernel
         int top_n; int32_t* top_ids; float* top_lp;           // dh_engine_set_top_logprobs: likewise, and top_n is a kernel argument
         const uint32_t* mask; int mask_ld;                    // dh_engine_set_token_mask: likewise (beam steps too)
+        int ngram; const int32_t* ngram_start;                // dh_engine_set_no_repeat_ngram: likewise (0 / null in a beam step's key)
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
@@ -88,7 +91,7 @@ struct dh_engine {
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
                    logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
-                   mask_ld == k.mask_ld && beam_w == k.beam_w &&
+                   mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && beam_w == k.beam_w &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
@@ -937,7 +940,7 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
     if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
     return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
-                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, s);
+                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram, k.ngram_start, s);
 }
 
 // tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends
@@ -979,9 +982,10 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_model(e, e->dec_ids, k.n_seq, k.n_seq, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
-                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, s);
+                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
+                                   k.ngram_start, s);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
-                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, s);
+                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram, k.ngram_start, s);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1198,7 +1202,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1214,7 +1218,7 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1262,7 +1266,7 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
                               limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1313,6 +1317,8 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_CHECK(rows <= MAX_DECODE_ROWS, "dh_engine_decode_beam: %d x %d rows exceed the streaming step's %d", n_utt, W, MAX_DECODE_ROWS);
     DH_CHECK(rows <= e->row_cap && rows <= e->max_tokens, "dh_engine_decode_beam: %d rows, the workspaces hold %d of max_tokens = %d",
              (int)rows, e->row_cap, e->max_tokens);
+    DH_CHECK(e->ngram == 0, "dh_engine_decode_beam: no_repeat_ngram=%d is set; a beam's history lives on the host, so the device cannot "
+             "form its ban set", e->ngram);
     DH_CHECK(e->d.vocab >= 2 * W, "dh_engine_decode_beam: vocab=%d is below the 2 W = %d candidates of a row", e->d.vocab, 2 * W);
     DH_CHECK(!e->fp8, "dh_engine_decode_beam: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(!e->kv8, "dh_engine_decode_beam: the re-parenting copies bf16 cache tiles; an fp8 KV cache is not supported");
@@ -1328,7 +1334,7 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_LAUNCH_CHECK();
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
                         prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                        e->mask, e->mask_ld, W, *st};
+                        e->mask, e->mask_ld, 0, nullptr, W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1354,6 +1360,17 @@ extern "C" int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int 
              mask_ld, (e->d.vocab + 31) / 32, e->d.vocab);
     e->mask = mask;
     e->mask_ld = mask ? mask_ld : 0;
+    return 0;
+}
+
+extern "C" int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int32_t* start) {
+    DH_CHECK(e, "dh_engine_set_no_repeat_ngram: null engine");
+    DH_CHECK(ngram >= 0 && ngram <= 8, "dh_engine_set_no_repeat_ngram: ngram=%d is not in 0 .. 8", ngram);
+    DH_CHECK(ngram == 0 || start, "dh_engine_set_no_repeat_ngram: ngram=%d needs `start`, the sequences' prompt lengths", ngram);
+    DH_CHECK(ngram == 0 || e->d.vocab <= 131072, "dh_engine_set_no_repeat_ngram: vocab=%d exceeds the 131072 ids of the sampler's LDS row",
+             e->d.vocab);
+    e->ngram = ngram;
+    e->ngram_start = ngram ? start : nullptr;
     return 0;
 }
 

@@ -195,6 +195,70 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
     return choice;
 }
 
+// No-repeat n-grams (include/dualhyp_hip.h): the static LDS row of allowed-minus-banned bits, ceil(vocab / 32) words
+constexpr int BAN_MAX_VOCAB = 131072;
+constexpr int MAX_NGRAM = 8;
+
+// The sequence's pick row under no_repeat_ngram = ngram (1 .. MAX_NGRAM), by the whole block: g[0..m) are the tokens it has generated,
+// the row starts from the mask row `mrow` (MASK) or from all ones, loses bit g[i + ngram - 1] for every i in [0, m - ngram] with
+// g[i .. i + ngram - 1) == g[m - ngram + 1 .. m), and is the start row again when that left no bit below vocab (the fallback: the pick
+// is never taken from an empty set).  Every thread gets the LDS row, in the mask row's layout with the bits at and behind vocab clear;
+// it holds until the block's next call, which the caller separates from the pick's last read by a barrier (pick_token ends on one).
+template <bool MASK>
+__device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int ngram, int vocab, const uint32_t* __restrict__ mrow) {
+    __shared__ uint32_t s_row[BAN_MAX_VOCAB / 32];
+    __shared__ int s_cnt[NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nw = (vocab + 31) >> 5;
+    const uint32_t tail = (vocab & 31) ? (1u << (vocab & 31)) - 1u : ~0u;
+    auto start_word = [&](int w) -> uint32_t {
+        uint32_t v = ~0u;
+        if constexpr (MASK) v = mrow[w];
+        return w == nw - 1 ? v & tail : v;
+    };
+    for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
+    __syncthreads();
+    if (m < ngram) return s_row;                        // the same for every thread: no n-gram is complete yet
+    int64_t suf[MAX_NGRAM - 1];                         // the (ngram - 1)-token suffix every candidate is tested against
+#pragma unroll
+    for (int j = 0; j < MAX_NGRAM - 1; ++j) suf[j] = j < ngram - 1 ? g[m - ngram + 1 + j] : 0;
+    for (int i = tid; i <= m - ngram; i += NT) {
+        bool eq = true;
+#pragma unroll
+        for (int j = 0; j < MAX_NGRAM - 1; ++j)
+            if (j < ngram - 1 && g[i + j] != suf[j]) eq = false;
+        if (eq) {
+            const int64_t t = g[i + ngram - 1];
+            if (t >= 0 && t < vocab) atomicAnd(&s_row[t >> 5], ~(1u << (t & 31)));
+        }
+    }
+    __syncthreads();
+    // everything banned?  popcount of the row (an integer sum: exact in any order)
+    int cnt = 0;
+    for (int w = tid; w < nw; w += NT) cnt += __popc(s_row[w]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0) s_cnt[wave] = cnt;
+    __syncthreads();
+    cnt = 0;
+    for (int w = 0; w < NT / 64; ++w) cnt += s_cnt[w];
+    if (cnt == 0) {                                     // the same for every thread
+        for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
+        __syncthreads();
+    }
+    return s_row;
+}
+
+// pick_token under no_repeat_ngram: under the row ban_row builds from the sequence's history g[0..m), through the masked paths of
+// pick_token (the 16-byte mask_byte loads included), so the pick is the unmasked pick on a copy of the row with -inf in every column that
+// the mask disallows or the history bans.  The kernels' BAN = false instantiations call pick_token<MASK> as they always did.
+template <bool MASK>
+__device__ __forceinline__ int pick_token_banned(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k, uint64_t seed,
+                                             int step, int seq, const uint32_t* __restrict__ mrow, const int64_t* g, int m, int ngram) {
+    const uint32_t* row = ban_row<MASK>(g, m, ngram, vocab, mrow);
+    return pick_token<true>(lg, vocab, temperature, top_k, seed, step, seq, row);
+}
+
 // log softmax(lg)[token] of the RAW row (temperature 1, no crop: the model's distribution, not the sampler's) by the whole block;
 // every thread returns it.  lp = lg[token] - m - log(sum_i exp(lg[i] - m)), m = max_i lg[i]: bf16 widened to fp32, fp32 sum, expf / logf
 // (the fast intrinsics lose the last bits of large arguments).  -inf entries add 0; a -inf token gives -inf.
@@ -398,7 +462,7 @@ __device__ __forceinline__ void store_top(int32_t* __restrict__ top_ids, float* 
     }
 }
 
-template <bool LP, bool TOP = false, bool MASK = false>
+template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
 __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                     int64_t* __restrict__ tokens, int tok_ld,
                                                     int32_t* __restrict__ length, int32_t* __restrict__ done,
@@ -406,12 +470,20 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
                                                     int step_arg, const int32_t* __restrict__ step_dev,
                                                     float* __restrict__ logprobs, int top_n,
                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
-                                                    const uint32_t* __restrict__ mask, int mask_ld) {
+                                                    const uint32_t* __restrict__ mask, int mask_ld, int ngram,
+                                                    const int32_t* __restrict__ start) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
-    const int choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
-                                        MASK ? mask + (size_t)seq * mask_ld : nullptr);
+    int choice;
+    if constexpr (BAN) {                                // the history is what lies behind the prompt
+        const int p0 = start[seq];
+        choice = pick_token_banned<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
+                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram);
+    } else {
+        choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
+                                  MASK ? mask + (size_t)seq * mask_ld : nullptr);
+    }
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
     const float lp = row_report<LP, TOP>(logits + (size_t)seq * vocab, vocab, choice, top_n, ti, tl);
@@ -433,7 +505,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
 // (seed, step, row) is when all sequences start together — so a sequence's ids do not depend on when or where it was scheduled.
 // limit[u] = prompt length + max_new is the sequence's own budget (done = 2 when reached).  Several padding rows may name one
 // finished sequence: they return at once.
-template <bool LP, bool TOP = false, bool MASK = false>
+template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                          int64_t* __restrict__ tokens, int tok_ld,
                                                          int32_t* __restrict__ length, int32_t* __restrict__ done,
@@ -442,13 +514,21 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                                          float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
-                                                         const uint32_t* __restrict__ mask, int mask_ld) {
+                                                         const uint32_t* __restrict__ mask, int mask_ld, int ngram,
+                                                         const int32_t* __restrict__ start) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
     const int step = n - (limit[u] - max_new);          // tokens generated so far
-    const int choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
-                                        MASK ? mask + (size_t)u * mask_ld : nullptr);     // the sequence's mask row, not the logits row's
+    int choice;
+    if constexpr (BAN) {
+        const int p0 = start ? start[u] : limit[u] - max_new;           // the prompt length, which limit[u] - max_new is
+        choice = pick_token_banned<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
+                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram);
+    } else {
+        choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
+                                  MASK ? mask + (size_t)u * mask_ld : nullptr);     // the sequence's mask row, not the logits row's
+    }
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
     const float lp = row_report<LP, TOP>(logits + (size_t)blockIdx.x * vocab, vocab, choice, top_n, ti, tl);
@@ -471,27 +551,37 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
 // behind the sequence's budget limit[u] = prompt length + max_new (done = 2), and a finished sequence is left alone.
 // counters: [0] the last step (1-based, *step_dev) at which a sequence was live, [1] drafts verified, [2] drafts appended.
 // LP: the log-probability of an appended pick_j, from its own row u * S + j, goes to logprobs beside the token; TOP: that row's
-// alternatives too.  MASK: all S positions of sequence u are picked under mask row u.
-template <bool LP, bool TOP = false, bool MASK = false>
+// alternatives too.  MASK: all S positions of sequence u are picked under mask row u.  BAN: position j's history runs up to the picks
+// appended at the positions before it in this launch — thread 0's stores, which the barrier at the top of the loop orders before the
+// block reads them back (a workgroup-scope fence: the block's waves share the CU's vector cache).
+template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
 __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
                                                          int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
                                                          int32_t* __restrict__ done, const int32_t* __restrict__ limit,
                                                          float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
                                                          int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
-                                                         const uint32_t* __restrict__ mask, int mask_ld) {
+                                                         const uint32_t* __restrict__ mask, int mask_ld, int ngram,
+                                                         const int32_t* __restrict__ start) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (done[u]) return;
     int n = length[u];
     const int lim = min(limit[u], tok_ld);
+    int p0 = 0;
+    if constexpr (BAN) p0 = start[u];
     int appended = 0, state = 0, prev = 0;
     for (int j = 0; j < S; ++j) {
         if (j > 0) {
             if (row_ids[(size_t)u * S + j] != (int64_t)prev) break;      // the same for every thread
             __syncthreads();                                             // pick_token's shared scratch is free again
         }
-        const int choice = pick_token<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u,
-                                            MASK ? mask + (size_t)u * mask_ld : nullptr);
+        int choice;
+        if constexpr (BAN)
+            choice = pick_token_banned<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u,
+                                         MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram);
+        else
+            choice = pick_token<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u,
+                                      MASK ? mask + (size_t)u * mask_ld : nullptr);
         prev = choice;
         if (n < lim) {                                                    // the same for every thread
             if constexpr (LP) {
@@ -548,8 +638,17 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 
 // the three kernels' variant for (logprobs, top_n): top_n > 0 needs the three buffers
 // and for the token mask: null is the kernel without it (the code it always was)
-#define DH_PICK_VARIANT_M(kernel, M) (top_n > 0 ? kernel<true, true, M> : logprobs ? kernel<true, false, M> : kernel<false, false, M>)
-#define DH_PICK_VARIANT(kernel) (mask ? DH_PICK_VARIANT_M(kernel, true) : DH_PICK_VARIANT_M(kernel, false))
+// and for no_repeat_ngram: 0 is the kernel without it, likewise
+#define DH_PICK_VARIANT_MB(kernel, M, B) \
+    (top_n > 0 ? kernel<true, true, M, B> : logprobs ? kernel<true, false, M, B> : kernel<false, false, M, B>)
+#define DH_PICK_VARIANT_B(kernel, B) (mask ? DH_PICK_VARIANT_MB(kernel, true, B) : DH_PICK_VARIANT_MB(kernel, false, B))
+#define DH_PICK_VARIANT(kernel) (ngram > 0 ? DH_PICK_VARIANT_B(kernel, true) : DH_PICK_VARIANT_B(kernel, false))
+// start_needed: the kernel has no other way to the prompt lengths
+#define DH_CHECK_NGRAM(name, start_needed)                                                                                      \
+    DH_CHECK(ngram >= 0 && ngram <= MAX_NGRAM, name ": no_repeat_ngram=%d is not in 0 .. %d", ngram, MAX_NGRAM);                   \
+    DH_CHECK(ngram == 0 || vocab <= BAN_MAX_VOCAB, name ": no_repeat_ngram keeps a sequence's allowed-minus-banned bits in a static " \
+             "LDS row of %d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                  \
+    DH_CHECK(ngram == 0 || start || !(start_needed), name ": no_repeat_ngram needs `start`, the prompt lengths")
 #define DH_CHECK_MASK(name)                                                                                                    \
     DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, name ": mask_ld=%d is below the %d words of a %d-token mask row", mask_ld, \
              (vocab + 31) / 32, vocab)
@@ -562,17 +661,18 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
                    const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
-                   int mask_ld, void* stream) {
+                   int mask_ld, int ngram, const int32_t* start, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
     DH_CHECK_TOP("dh_sample_bf16");
     DH_CHECK_MASK("dh_sample_bf16");
+    DH_CHECK_NGRAM("dh_sample_bf16", true);
     DH_CHECK(temperature > 0.f, "dh_sample_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
     // logprobs null: the kernel without the log-probability pass (the code it always was)
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp, mask, mask_ld);
+                       top_ids, top_lp, mask, mask_ld, ngram, start);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -581,14 +681,14 @@ extern "C" int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* toke
                                  int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                  int step, void* stream, float* logprobs) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, 0, nullptr, nullptr, nullptr, 0, stream);
+                          nullptr, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
 }
 
 extern "C" int dh_sample_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, stream);
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, stream);
 }
 
 extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -597,7 +697,16 @@ extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* to
                                    const uint32_t* mask, int mask_ld) {
     DH_CHECK(mask, "dh_sample_bf16_mask: null mask (dh_sample_bf16_top is the entry without one)");
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, stream);
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, stream);
+}
+
+extern "C" int dh_sample_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                    int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                    int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                    const uint32_t* mask, int mask_ld, int ngram, const int32_t* start) {
+    DH_CHECK(ngram >= 1, "dh_sample_bf16_ngram: ngram=%d (dh_sample_bf16_mask / dh_sample_bf16_top are the entries without one)", ngram);
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, stream);
 }
 
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -610,17 +719,18 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, void* stream) {
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
     DH_CHECK_TOP("dh_sample_rows_bf16");
     DH_CHECK_MASK("dh_sample_rows_bf16");
+    DH_CHECK_NGRAM("dh_sample_rows_bf16", false);
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -630,7 +740,7 @@ extern "C" int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t*
                                       int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                       float* logprobs) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, nullptr, 0, stream);
+                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -638,7 +748,7 @@ extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t
                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, stream);
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -648,7 +758,18 @@ extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_
                                         int mask_ld) {
     DH_CHECK(mask, "dh_sample_rows_bf16_mask: null mask (dh_sample_rows_bf16_top is the entry without one)");
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, stream);
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, stream);
+}
+
+extern "C" int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                         int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                         int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                         float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                         int mask_ld, int ngram, const int32_t* start) {
+    DH_CHECK(ngram >= 1, "dh_sample_rows_bf16_ngram: ngram=%d (dh_sample_rows_bf16_mask / dh_sample_rows_bf16_top are the entries without one)",
+             ngram);
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, stream);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -661,16 +782,17 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
                         const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, void* stream) {
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, void* stream) {
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
     DH_CHECK_TOP("spec_accept");
     DH_CHECK_MASK("spec_accept");
+    DH_CHECK_NGRAM("spec_accept", true);
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
-                       counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld);
+                       counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start);
     DH_LAUNCH_CHECK();
     return 0;
 }

@@ -14,6 +14,7 @@ import torch
 
 from . import beam as _beam
 from . import constrain as _constrain
+from . import ngram as _ngram
 from . import ops
 from .gpt import GPT
 from .schedule import shared_prefix_len
@@ -87,7 +88,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
                    share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
-                   return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None):
+                   return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -129,10 +130,21 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     (allow the EOS if the sequence is to end on it), as if every other logit were -inf, with whatever sampler the call uses.  Every
     row allows at least one id (checked with one read-back before anything is launched).  The pick happens inside the sampling
     kernels — the prefill's first pick and every captured decode or verify step — and the log-probabilities and alternatives stay
-    the raw row's.  It goes with speculate, share_prefix, return_logprobs and top_logprobs, none of which it touches."""
+    the raw row's.  It goes with speculate, share_prefix, return_logprobs and top_logprobs, none of which it touches.
+
+    no_repeat_ngram=n (1..8; include/dualhyp_hip.h, "No-repeat n-grams"): a sequence never produces a token that would complete an
+    n-gram its GENERATED text already holds (the prompt's n-grams stay free: a correction copies its prompt) — as if the logit were
+    -inf, with whatever sampler the call uses, and on top of token_mask; where that would leave nothing to pick, the ban is ignored
+    for the step.  The ban set is built inside the sampling kernels from the token buffer, per sequence and step, with no launch or
+    read-back of its own; the first pick of a prompt is unaffected, and log-probabilities and alternatives stay the raw row's.  It
+    goes with token_mask, speculate (a banned draft is simply not confirmed), share_prefix, return_logprobs and top_logprobs, and
+    with fp8 weights and an fp8 KV cache.  0 (the default): the call it always was."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
+    ngram = _ngram.check_ngram(no_repeat_ngram)
+    if ngram:
+        _ngram.check_ngram(ngram, model.config.padded_vocab_size)
     D = _check_speculate(model, speculate, top_k, B)
     if drafts is not None and (D == 0 or drafts.dtype != torch.int64 or tuple(drafts.shape) != (B, max_new_tokens)):
         raise ValueError(f"drafts goes with speculate > 0 and is a [{B}, {max_new_tokens}] int64 tensor")
@@ -169,6 +181,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     else:
         length = torch.tensor(lens, dtype=torch.int32, device=dev)
         done = torch.zeros(B, dtype=torch.int32, device=dev)
+    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram else None      # the prompt lengths: the ban's history begins there
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -183,7 +196,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
-               top_logprobs=top_buf, mask=mask)
+               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start)
     if ev:
         ev[1].record()
     if lp_buf is not None:
@@ -192,6 +205,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         eng.set_top_logprobs(*top_buf)  # likewise
     if mask is not None:
         eng.set_token_mask(mask)        # likewise
+    if ngram:
+        eng.set_no_repeat_ngram(ngram, start)   # likewise
     try:
         steps_run = 0
         if max_new_tokens > 1:
@@ -226,6 +241,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             eng.set_top_logprobs(None)
         if mask is not None:
             eng.set_token_mask(None)
+        if ngram:
+            eng.set_no_repeat_ngram(0)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -271,7 +288,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
 @torch.inference_mode()
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
                       length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
-                      token_mask=None):
+                      token_mask=None, no_repeat_ngram: int = 0):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
@@ -298,9 +315,15 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
 
     token_mask (as in generate_batch, one row per utterance, serving all of its W beams): a beam row's 2 W candidates are the first
     2 W allowed ids of its raw row's order, each with the raw row's log-probability ("Token masks" of the header), so every row
-    allows at least 2 W ids (checked before anything is launched); everything behind the candidates is unchanged."""
+    allows at least 2 W ids (checked before anything is launched); everything behind the candidates is unchanged.
+
+    no_repeat_ngram: refused unless 0 — a beam's history is re-parented on the host, so the device cannot form a beam's ban set
+    (DESIGN.md §9)."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
+    if _ngram.check_ngram(no_repeat_ngram):
+        raise ValueError(f"no_repeat_ngram={no_repeat_ngram} does not go with beam search: the beams' histories live on the host, so the "
+                         "sampling kernels cannot form a beam's ban set; it runs under generate_batch and generate_stream")
     W = _beam.check_arguments(model, num_beams, B)
     length_penalty = _beam.check_length_penalty(length_penalty)
     lens = [int(p.numel()) for p in prompts]
@@ -373,7 +396,7 @@ class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
-                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None) -> None:
+                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -392,6 +415,9 @@ class _StreamBackend:
         self.top = _top_buffers(self.tokens.shape, top_logprobs, dev) if top_logprobs else None   # generate_batch's top_logprobs
         # the call's token mask (generate_batch's token_mask) and an all-ones row for the dummy sequence, which never picks
         self.mask = None if mask is None else torch.cat([mask, torch.full_like(mask[:1], -1)]).contiguous()
+        # generate_batch's no_repeat_ngram and the sequences' prompt lengths (the dummy sequence's one token is all prompt)
+        self.ngram = ngram
+        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -413,7 +439,8 @@ class _StreamBackend:
         # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
-                        self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, **self.kw)
+                        self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
+                        start=self.start, **self.kw)
         if end:
             end.record()
 
@@ -438,7 +465,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
-                    top_logprobs: int = 0, token_mask=None):
+                    top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -456,9 +483,15 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     return_logprobs, top_logprobs: as in generate_batch — (out, logprobs[, top]), the same values bit for bit.
 
     token_mask: as in generate_batch, one row per prompt; a sequence is picked under its own row wherever it is scheduled (the
-    row-list sampler reads mask row row_seq[r]); the dummy sequence of the padding rows gets an all-ones row."""
+    row-list sampler reads mask row row_seq[r]); the dummy sequence of the padding rows gets an all-ones row.
+
+    no_repeat_ngram: as in generate_batch — a sequence's ban set is formed from its own row of the token buffer wherever it is
+    scheduled, so the ids do not depend on the schedule."""
     from .schedule import StreamScheduler
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
+    ngram = _ngram.check_ngram(no_repeat_ngram)
+    if ngram:
+        _ngram.check_ngram(ngram, model.config.padded_vocab_size)
     if speculate:
         raise ValueError(f"speculate={speculate}: continuous batching steps a row list one token at a time; speculative decoding runs "
                          "under generate_batch (--schedule batch) only")
@@ -477,7 +510,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask)
+                        top_logprobs=K, mask=mask, ngram=ngram)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -489,6 +522,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         eng.set_top_logprobs(*be.top)
     if mask is not None:
         eng.set_token_mask(be.mask)
+    if ngram:
+        eng.set_no_repeat_ngram(ngram, be.start)
     try:
         sched.run(be)
     finally:
@@ -498,6 +533,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             eng.set_top_logprobs(None)
         if mask is not None:
             eng.set_token_mask(None)
+        if ngram:
+            eng.set_no_repeat_ngram(0)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
@@ -527,17 +564,19 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
-             top_logprobs: int = 0, token_mask=None):
+             top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
-    top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list."""
+    top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
+    generate_batch's."""
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                         speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask)
+                         speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
+                         no_repeat_ngram=no_repeat_ngram)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

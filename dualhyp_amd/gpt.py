@@ -507,6 +507,15 @@ class _Engine:
         _lib.check(self.lib.dh_engine_set_token_mask(self.handle, None if mask is None else mask.data_ptr(),
                                                      0 if mask is None else mask.size(1)))
 
+    def set_no_repeat_ngram(self, ngram: int, start: Optional[torch.Tensor] = None) -> None:
+        """no_repeat_ngram = ngram (1..8) for later decode / decode_rows / decode_spec calls, with start, the int32 prompt lengths of
+        their sequences (dh_engine_set_no_repeat_ngram; include/dualhyp_hip.h, "No-repeat n-grams"); 0 turns it off.  decode_beam
+        refuses to run while it is set.  The caller keeps start alive while set."""
+        if ngram and (start is None or start.dtype != torch.int32 or not start.is_cuda or not start.is_contiguous() or start.dim() != 1):
+            raise TypeError("set_no_repeat_ngram takes a contiguous 1-D int32 tensor of prompt lengths on the GPU beside ngram > 0")
+        _lib.check(self.lib.dh_engine_set_no_repeat_ngram(self.handle, int(ngram), start.data_ptr() if ngram else None))
+        self._ngram_start = start if ngram else None
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"
@@ -515,6 +524,8 @@ class _Engine:
             "the top_logprobs buffers go with a logprobs buffer and have the shape of tokens, times K"
         mask = getattr(self, "_token_mask", None)
         assert mask is None or mask.size(0) == tokens.size(0), "the token mask has one row per row of tokens"
+        start = getattr(self, "_ngram_start", None)
+        assert start is None or start.numel() == tokens.size(0), "no_repeat_ngram's start has one prompt length per row of tokens"
 
     def graph_count(self, n_draft: int = -1) -> int:
         """Captured decode steps kept for n_draft drafts (0: the plain steps, -1: all)."""

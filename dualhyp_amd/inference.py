@@ -67,7 +67,9 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     hypotheses of dualhyp_amd.beam_search_batch, 'logprobs': bool}: the prediction is the best hypothesis, every record gains
     'beams', one {'text', 'sum_logprob', 'avg_logprob', 'finished'} per hypothesis in rank order, and with 'logprobs' the best
     one's 'sum_logprob' and 'avg_logprob' as above.  A generate_fn with a true attribute `constrained` (--constrain: it decodes under
-    per-utterance token masks) marks every record with 'constrained': true.  Returns corpus metrics on every rank and predictions on
+    per-utterance token masks) marks every record with 'constrained': true.  A generate_fn with an attribute `no_repeat_ngram` = N > 0
+    (--no_repeat_ngram) gives every record 'no_repeat_ngram': N and 'ngram_bans': the generated positions (of the ids it returned)
+    whose pick had a non-empty ban set, counted on the host from those ids (dualhyp_amd.ngram.ban_positions).  Returns corpus metrics on every rank and predictions on
     rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
@@ -90,6 +92,10 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                         "ground_truth": examples[i]["ground_truth"].strip()}
             if getattr(generate_fn, "constrained", False):
                 preds[i]["constrained"] = True
+            if getattr(generate_fn, "no_repeat_ngram", 0):
+                from .ngram import ban_positions
+                preds[i]["no_repeat_ngram"] = int(generate_fn.no_repeat_ngram)
+                preds[i]["ngram_bans"] = len(ban_positions(o.reshape(-1)[p.numel():].tolist(), int(generate_fn.no_repeat_ngram)))
             if beams is not None:
                 text = decode(p)
                 preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
@@ -279,6 +285,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     beams = int(getattr(args, "num_beams", 1) or 1)
     constrain = getattr(args, "constrain", "off") == "prompt"
     extra = read_token_ids(args.constrain_extra) if constrain and getattr(args, "constrain_extra", None) else ()
+    ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
@@ -287,16 +294,18 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         if beams > 1:      # --decode_batch counts decode rows: W per utterance
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
-                                     prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask)
+                                     prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask,
+                                     no_repeat_ngram=ngram)
             return {"beams": hyps, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
-                                   share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask)
+                                   share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask,
+                                   no_repeat_ngram=ngram)
         else:
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
-                                  return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask)
+                                  return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram)
         if top_n:
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]], [(a.cpu(), b.cpu()) for a, b in outs[2]]
         if want_lp:
@@ -304,6 +313,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         return [o.cpu() for o in outs]
 
     gen.constrained = constrain
+    gen.no_repeat_ngram = ngram
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -388,6 +398,12 @@ def build_parser():
                         "path it always was")
     p.add_argument("--constrain_extra", type=str, default=None, metavar="FILE",
                    help="with --constrain prompt: a file of token ids, one per line, allowed for every utterance")
+    p.add_argument("--no_repeat_ngram", type=int, default=0, metavar="N",
+                   help="N in 1..8: an utterance never emits a token that would complete an N-gram its generated text already holds "
+                        "(the prompt's N-grams stay free), which ends the loops a greedy corrector can fall into; the ban set is built "
+                        "inside the sampling kernels, under both schedules, with --constrain and --speculate; every record gains "
+                        "no_repeat_ngram: N and ngram_bans, the generated positions with a non-empty ban set; not with --num_beams.  "
+                        "Default 0: off, the path it always was (the WER effect on real corpora is unmeasured)")
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
@@ -422,6 +438,11 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                               (bool(args.top_logprobs), f"--top_logprobs {args.top_logprobs}", "the records carry the beams instead")):
             if on:
                 p.error(f"--num_beams {args.num_beams} does not go with {flag}: {why}")
+    if not 0 <= args.no_repeat_ngram <= 8:
+        p.error(f"--no_repeat_ngram {args.no_repeat_ngram}: N is 0 (off) or 1..8")
+    if args.no_repeat_ngram and args.num_beams > 1:         # beam_search_batch refuses it too; here nothing has been loaded yet
+        p.error(f"--no_repeat_ngram {args.no_repeat_ngram} does not go with --num_beams {args.num_beams}: the beams' histories live on "
+                "the host, so the sampling kernels cannot form a beam's ban set")
     if args.constrain_extra and args.constrain == "off":
         p.error("--constrain_extra goes with --constrain prompt")
     if not 0 <= args.top_logprobs <= 8:

@@ -261,6 +261,28 @@ def _mask_arg(mask: Optional[torch.Tensor], n_rows: int, vocab: int, device):
     return mask.data_ptr(), ld
 
 
+def _ngram_arg(no_repeat_ngram: int, start: Optional[torch.Tensor], n_seq: int, vocab: int, device, keep, start_optional: bool = False):
+    """(ngram, start pointer) of a sampler call (include/dualhyp_hip.h, "No-repeat n-grams"): n in 0 .. 8, and with n > 0 the int32
+    [n_seq] prompt lengths on the logits' device (start_optional: None is the row-list sampler's limit - max_new_tokens)."""
+    from .ngram import check_ngram
+    n = check_ngram(no_repeat_ngram, vocab)
+    if n == 0:
+        if start is not None:
+            raise ValueError("start goes with no_repeat_ngram > 0")
+        return 0, None
+    if start is None:
+        if not start_optional:
+            raise ValueError(f"no_repeat_ngram={n} needs start, the int32 [{n_seq}] prompt lengths: the history it bans from begins there")
+        return n, None
+    if not start.is_cuda:
+        raise _lib.DualHypHipError("start must live on the GPU: the HIP path has no CPU fallback")
+    if start.dtype != torch.int32 or start.numel() != n_seq:
+        raise ValueError(f"start must be {torch.int32} [{n_seq}], got {start.dtype} {tuple(start.shape)}")
+    if start.device != device:
+        raise ValueError(f"start lives on {start.device}, the logits on {device}")
+    return n, keep(start, torch.int32)
+
+
 def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
     index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
@@ -341,12 +363,15 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool =
 def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, *,
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
            step: int = 0, logprobs: Optional[torch.Tensor] = None,
-           top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None) -> None:
+           top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
+           no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
     same place in them (dh_sample_bf16_top).  mask (int32 [n_seq, words], "Token masks" of the header): row u holds the tokens
-    sequence u may pick; the log-probabilities and alternatives stay the raw row's (dh_sample_bf16_mask)."""
+    sequence u may pick; the log-probabilities and alternatives stay the raw row's (dh_sample_bf16_mask).  no_repeat_ngram (1..8, with
+    start: int32 [n_seq] prompt lengths; "No-repeat n-grams" of the header): a token that would complete an n-gram already in
+    tokens[u, start[u]:length[u]] is not picked, with or without a mask (dh_sample_bf16_ngram)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_seq, vocab = logits.shape
@@ -354,10 +379,13 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     logprobs = _logprobs_buffer(logprobs, tokens)
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
     m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
+    ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
             0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
             _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if mask is not None:
+    if ngram:
+        check(_lib.load().dh_sample_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
+    elif mask is not None:
         check(_lib.load().dh_sample_bf16_mask(*args, m_ptr, m_ld))
     else:
         check(_lib.load().dh_sample_bf16_top(*args))
@@ -366,10 +394,12 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
 def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor,
                 row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
                 eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None,
-                top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None) -> None:
+                top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
+                no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
     in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
-    (dh_sample_rows_bf16_mask)."""
+    (dh_sample_rows_bf16_mask).  no_repeat_ngram, start: as in sample(), one entry of start per SEQUENCE; start None is
+    limit - max_new_tokens (dh_sample_rows_bf16_ngram)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_rows, vocab = logits.shape
@@ -379,10 +409,13 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     logprobs = _logprobs_buffer(logprobs, tokens)
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
     m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
+    ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=True)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
             k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if mask is not None:
+    if ngram:
+        check(_lib.load().dh_sample_rows_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
+    elif mask is not None:
         check(_lib.load().dh_sample_rows_bf16_mask(*args, m_ptr, m_ld))
     else:
         check(_lib.load().dh_sample_rows_bf16_top(*args))

@@ -30,7 +30,8 @@ typedef uint16_t dh_bf16;
  * dh_sample_rows_bf16_ex and dh_engine_set_logprobs (token log-probabilities); dh_token_top_logprobs_bf16, dh_sample_bf16_top,
  * dh_sample_rows_bf16_top and dh_engine_set_top_logprobs (token alternatives); dh_beam_select_bf16, dh_engine_reserve_beams and
  * dh_engine_decode_beam (beam search); dh_sample_bf16_mask, dh_sample_rows_bf16_mask, dh_token_top_logprobs_bf16_mask,
- * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks). */
+ * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks); dh_sample_bf16_ngram, dh_sample_rows_bf16_ngram and
+ * dh_engine_set_no_repeat_ngram (no-repeat n-grams). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -494,6 +495,38 @@ int dh_beam_select_bf16_mask(const dh_bf16* logits, int vocab, int n_utt, int ro
                              int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp,
                              const uint32_t* mask, int mask_ld, void* stream);
 
+/* No-repeat n-grams (no_repeat_ngram_size of the text-generation stacks; extends the decode loop of generate/base.py:62-80).  ONE
+ * definition for every entry below.
+ * For a sequence, g[0 .. m) are the tokens it has GENERATED so far: tokens[u, start[u] .. length[u]), start[u] its prompt length.  The
+ * prompt is excluded on purpose: a correction copies its prompt, so the prompt's n-grams stay free.  For n = ngram in 1 .. 8 the ban
+ * set of the step is
+ *     { g[i + n - 1] : 0 <= i <= m - n,  g[i .. i + n - 1) == g[m - n + 1 .. m) },
+ * every token that would complete an n-gram the generated text already holds.  It is empty while m < n (the first pick of a prompt,
+ * m = 0, is never affected); for n = 1 it is every id generated so far.  ngram = 0 means the feature is off: the entries without
+ * `_ngram`, and the kernels they always ran.
+ *   The ban belongs to the sampler, exactly as the mask does: the picked id is, bit for bit, what the entry without mask and ban
+ *     picks on a copy of the row with 0xFF80 in every column that the token mask (if any) disallows or the ban set holds — for the
+ *     arg-max, the top_k threshold and the softmax draw alike, and for the same (seed, step, seq) draw.
+ *   One fallback: when every id the step would otherwise allow (the mask row's ids below vocab; every id without a mask) is banned,
+ *     the ban set is ignored at that step.  The pick is never taken from an empty set.
+ *   Log-probabilities and top_ids / top_lp stay the RAW row's, as under a mask.
+ *   Where it is computed: inside the sampling kernel, by the sequence's own 1024-thread block, from the token buffer — no launch and
+ *     no read-back of its own.  The allowed-minus-banned bits of the row live in a static LDS row of 131072 ids (16 KB); a larger
+ *     vocab is refused.  A verify step's position j sees the picks the same launch appended before it. */
+
+/* dh_sample_bf16_mask / dh_sample_rows_bf16_mask with ngram in 1 .. 8 (generate/base.py:62-80).  mask: nullable here (null: every
+ * id is allowed, mask_ld is ignored).  start: int32 [n_seq], the prompt lengths; dh_sample_rows_bf16_ngram takes null for
+ * limit[u] - max_new_tokens, which is the same number. */
+int dh_sample_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                         int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                         uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                         const uint32_t* mask, int mask_ld, int ngram, const int32_t* start);
+int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                              int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                              int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                              void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                              const uint32_t* mask, int mask_ld, int ngram, const int32_t* start);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -765,6 +798,11 @@ int dh_engine_set_top_logprobs(dh_engine* e, int k, int32_t* ids, float* lp);
  * step's key, exactly as the logprobs pointer is: with the mask unset a decode call runs the graphs it always ran.  The caller
  * keeps the mask alive, and may change its contents between calls, while it is set. */
 int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int mask_ld);
+/* No-repeat n-grams (see above; generate/base.py:62-80) for later dh_engine_decode, dh_engine_decode_rows and dh_engine_decode_spec
+ * calls: ngram in 1 .. 8 with start, device int32 [n_seq] prompt lengths of the calls' sequences; ngram = 0 = off, the default.
+ * (ngram, start) is part of the captured step's key, beside the mask: with it unset a decode call runs the graphs it always ran.
+ * dh_engine_decode_beam refuses to run while it is set: beam histories live on the host.  The caller keeps start alive while set. */
+int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int32_t* start);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
