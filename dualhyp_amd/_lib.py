@@ -39,6 +39,11 @@ class BeamState(C.Structure):
                                  "fin_score", "fin_lp", "n_fin")]
 
 
+class StopSpec(C.Structure):
+    """dh_stop_spec: a stop specification (include/dualhyp_hip.h, "Stop conditions"); h_seq_len is a host pointer"""
+    _fields_ = [("set", P), ("seqs", P), ("h_seq_len", P), ("n_seqs", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/dualhyp_hip.h
 SIGNATURES = {
     "dh_abi_version": (I, []),
@@ -89,6 +94,9 @@ SIGNATURES = {
     "dh_sample_rows_bf16_mask": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I]),
     "dh_sample_bf16_ngram": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P]),
     "dh_sample_rows_bf16_ngram": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P]),
+    "dh_sample_bf16_stop": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec)]),
+    "dh_sample_rows_bf16_stop": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec)]),
+    "dh_beam_select_bf16_stop": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P, P]),
     "dh_token_top_logprobs_bf16_mask": (I, [P, I, I, P, P, I, P, I, I, P]),
     "dh_beam_select_bf16_mask": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, P]),
     "dh_quant_rows_fp8": (I, [P, P, P, I, I, P]),
@@ -124,6 +132,7 @@ SIGNATURES = {
     "dh_engine_set_top_logprobs": (I, [P, I, P, P]),
     "dh_engine_set_token_mask": (I, [P, P, I]),
     "dh_engine_set_no_repeat_ngram": (I, [P, I, P]),
+    "dh_engine_set_stop": (I, [P, C.POINTER(StopSpec), P, P]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

@@ -63,6 +63,13 @@ class BeamState:
             for n, v in zip(names, block.split(sizes)):
                 setattr(self, n, v.view(shapes[n]))
         self._c = None
+        self.fin_tok = None         # int32 [n_utt, W] beside fin_step, under a stop set only: the id that ended pool entry k
+
+    def fin_tok_buffer(self) -> torch.Tensor:
+        """fin_tok, made at its first use (-1: no entry): what dh_beam_select_bf16_stop and dh_engine_set_stop write."""
+        if self.fin_tok is None:
+            self.fin_tok = torch.full((self.n_utt, self.W), -1, dtype=torch.int32, device=self.device)
+        return self.fin_tok
 
     def c_struct(self):
         from . import _lib
@@ -78,6 +85,8 @@ class BeamState:
             sizes = [int(torch.Size(self.shapes[n]).numel()) for n in names]
             for n, v in zip(names, block.split(sizes)):
                 out[n] = v.view(self.shapes[n]).tolist()      # a Python float holds an fp32 value exactly
+        if self.fin_tok is not None:                          # a call under a stop set: one small copy more
+            out["fin_tok"] = self.fin_tok.tolist()
         return out
 
 
@@ -92,12 +101,14 @@ def backtrack(beam_parent, step: int, beam: int) -> List[int]:
     return path
 
 
-def hypotheses(h: Dict[str, list], u: int, W: int, length_penalty: float = 1.0) -> List[dict]:
+def hypotheses(h: Dict[str, list], u: int, W: int, length_penalty: float = 1.0, eos_id=None) -> List[dict]:
     """The ranked hypotheses of utterance u from the host copy `h` of a finished call's state (BeamState.host()): the pool, completed
     with the live beams in live order (unfinished) while it holds fewer than W entries, ranked by sum_logprob / n ** length_penalty
     in Python floats — n the generated tokens, the EOS counted — descending, stable on pool order.  Each entry: tokens (generated,
     without the EOS), token_logprobs (float32 tensor, the EOS's included), sum_logprob (the device's fp32 cumulative score, as a
-    float), finished."""
+    float), finished, and finish_reason: "eos" for a pool entry that ended on the EOS, "stop" for one that ended on a stop id (h holds
+    fin_tok then — a call under a stop set — and the id differs from eos_id; the stop id stays in tokens and counts in n), "length" for
+    a live beam."""
     n_steps, n_fin = int(h["n_steps"][u]), int(h["n_fin"][u])
     tok, par, lp = h["beam_tok"][u], h["beam_parent"][u], h["beam_lp"][u]
     pool = []
@@ -109,13 +120,18 @@ def hypotheses(h: Dict[str, list], u: int, W: int, length_penalty: float = 1.0) 
     for i in range(min(n_fin, W)):
         s = int(h["fin_step"][u][i])
         toks, lps = read(s - 1, int(h["fin_parent"][u][i]))
+        reason = "eos"
+        if "fin_tok" in h and (eos_id is None or int(h["fin_tok"][u][i]) != int(eos_id)):     # the EOS wins where an id is both
+            reason = "stop"
+            toks = toks + [int(h["fin_tok"][u][i])]
         pool.append(dict(tokens=toks, token_logprobs=torch.tensor(lps + [h["fin_lp"][u][i]], dtype=torch.float32),
-                         sum_logprob=float(h["fin_score"][u][i]), finished=True))
+                         sum_logprob=float(h["fin_score"][u][i]), finished=True, finish_reason=reason))
     for w in range(W):
         if len(pool) >= W or n_steps == 0:
             break
         toks, lps = read(n_steps - 1, w)
-        pool.append(dict(tokens=toks, token_logprobs=torch.tensor(lps, dtype=torch.float32), sum_logprob=float(h["beam_cum"][u][n_steps - 1][w]), finished=False))
+        pool.append(dict(tokens=toks, token_logprobs=torch.tensor(lps, dtype=torch.float32), sum_logprob=float(h["beam_cum"][u][n_steps - 1][w]), finished=False,
+                         finish_reason="length"))
     return rank(pool, length_penalty)
 
 

@@ -16,7 +16,8 @@ static_assert(2 * MAX_W <= DH_MAX_TOP_LOGPROBS, "a row offers 2 W alternatives")
 // the walk, 2 W places of at most W compares each: nothing here is worth a second lane, and no atomic decides anything.
 __global__ __launch_bounds__(64) void beam_merge_kernel(const int32_t* __restrict__ cand_ids, const float* __restrict__ cand_lp,
                                                         int rows_per_utt, int W, int max_new, int64_t eos_id, int step_arg,
-                                                        const int32_t* __restrict__ step_dev, dh_beam_state st) {
+                                                        const int32_t* __restrict__ step_dev, dh_beam_state st,
+                                                        const uint32_t* __restrict__ stop_set, int32_t* __restrict__ fin_tok) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (st.done[u]) return;                                          // frozen
     const int step = step_dev ? *step_dev : step_arg;                // device counter keeps a captured graph replayable
@@ -47,8 +48,11 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const int32_t* __restric
         }
         if (b < 0) break;
         const int c = b * K + s_head[b]++;
-        if (eos_id >= 0 && (int64_t)s_id[c] == eos_id) {
+        // a stop id (include/dualhyp_hip.h, "Stop conditions") ends the hypothesis exactly as the EOS does; fin_tok tells them apart
+        const bool ends = (eos_id >= 0 && (int64_t)s_id[c] == eos_id) || (stop_set && s_id[c] >= 0 && ((stop_set[s_id[c] >> 5] >> (s_id[c] & 31)) & 1u));
+        if (ends) {
             if (p < W && nf < W) {
+                if (fin_tok) fin_tok[(size_t)u * W + nf] = s_id[c];
                 st.fin_step[(size_t)u * W + nf] = step;
                 st.fin_parent[(size_t)u * W + nf] = b;
                 st.fin_score[(size_t)u * W + nf] = best;
@@ -81,8 +85,9 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const int32_t* __restric
 
 int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
                         const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, const uint32_t* mask,
-                        int mask_ld, void* stream) {
+                        int mask_ld, const uint32_t* stop_set, int32_t* fin_tok, void* stream) {
     DH_CHECK(logits && cand_ids && cand_lp, "dh_beam_select_bf16: null argument");
+    DH_CHECK(!stop_set || fin_tok, "dh_beam_select_bf16: a stop set needs fin_tok, the ids that ended the pool entries");
     DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, "dh_beam_select_bf16: mask_ld=%d is below the %d words of a %d-token mask row", mask_ld,
              (vocab + 31) / 32, vocab);
     DH_CHECK(st.cum && st.n_steps && st.done && st.beam_tok && st.beam_parent && st.beam_lp && st.beam_cum && st.fin_step &&
@@ -99,7 +104,7 @@ int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_pe
                         : dh_token_top_logprobs_bf16(logits, vocab, 2 * W, cand_ids, cand_lp, n_utt * rows_per_utt, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(beam_merge_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, cand_ids, cand_lp, rows_per_utt, W, max_new,
-                       eos_id, step, step_dev, st);
+                       eos_id, step, step_dev, st, stop_set, fin_tok);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -109,7 +114,7 @@ extern "C" int dh_beam_select_bf16(const dh_bf16* logits, int vocab, int n_utt, 
                                    float* cand_lp, void* stream) {
     DH_CHECK(st, "dh_beam_select_bf16: null beam state");
     return dh_beam_select_impl(logits, vocab, n_utt, rows_per_utt, W, max_new_tokens, eos_id, step, step_dev, *st, cand_ids, cand_lp,
-                               nullptr, 0, stream);
+                               nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int dh_beam_select_bf16_mask(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens,
@@ -118,5 +123,16 @@ extern "C" int dh_beam_select_bf16_mask(const dh_bf16* logits, int vocab, int n_
     DH_CHECK(st, "dh_beam_select_bf16_mask: null beam state");
     DH_CHECK(mask, "dh_beam_select_bf16_mask: null mask (dh_beam_select_bf16 is the entry without one)");
     return dh_beam_select_impl(logits, vocab, n_utt, rows_per_utt, W, max_new_tokens, eos_id, step, step_dev, *st, cand_ids, cand_lp,
-                               mask, mask_ld, stream);
+                               mask, mask_ld, nullptr, nullptr, stream);
+}
+
+extern "C" int dh_beam_select_bf16_stop(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens,
+                                        int64_t eos_id, int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids,
+                                        float* cand_lp, const uint32_t* mask, int mask_ld, const dh_stop_spec* stop, int32_t* fin_tok,
+                                        void* stream) {
+    DH_CHECK(st, "dh_beam_select_bf16_stop: null beam state");
+    DH_CHECK(!stop || stop->n_seqs == 0, "dh_beam_select_bf16_stop: %d stop sequences; the beams' histories live on the host, so the device "
+             "cannot match a sequence against a beam's text (the stop set alone goes with beam search)", stop->n_seqs);
+    return dh_beam_select_impl(logits, vocab, n_utt, rows_per_utt, W, max_new_tokens, eos_id, step, step_dev, *st, cand_ids, cand_lp,
+                               mask, mask ? mask_ld : 0, stop ? stop->set : nullptr, fin_tok, stream);
 }

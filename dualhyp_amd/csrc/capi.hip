@@ -15,6 +15,29 @@ void dh_set_error(const char* fmt, ...) {
 extern "C" const char* dh_last_error(void) { return g_err; }
 extern "C" int dh_abi_version(void) { return DH_ABI_VERSION; }
 
+// dh_stop_spec -> what the kernels take by value, with the header's argument checks ("Stop conditions"): nothing is launched
+int dh_stop_pack(const char* name, const dh_stop_spec* stop, bool start_ok, dh_stop_args& out) {
+    out = dh_stop_args{};
+    if (!stop) return 0;
+    DH_CHECK(stop->n_seqs >= 0 && stop->n_seqs <= DH_MAX_STOP_SEQS, "%s: %d stop sequences, at most %d are supported", name, stop->n_seqs,
+             DH_MAX_STOP_SEQS);
+    DH_CHECK(stop->n_seqs == 0 || (stop->seqs && stop->h_seq_len), "%s: %d stop sequences without their ids or their lengths", name,
+             stop->n_seqs);
+    uint32_t lens = 0;
+    for (int i = 0; i < stop->n_seqs; ++i) {
+        const int L = stop->h_seq_len[i];
+        DH_CHECK(L >= 2 && L <= DH_MAX_STOP_LEN, "%s: stop sequence %d has %d tokens, 2 .. %d are supported (one token belongs in the stop set)",
+                 name, i, L, DH_MAX_STOP_LEN);
+        lens |= (uint32_t)L << (4 * i);
+    }
+    DH_CHECK(stop->n_seqs == 0 || start_ok, "%s: stop sequences need `start`, the prompt lengths: a match never reaches into the prompt", name);
+    out.set = stop->set;
+    out.seqs = stop->n_seqs ? stop->seqs : nullptr;
+    out.lens = lens;
+    out.n_seqs = stop->n_seqs;
+    return 0;
+}
+
 extern "C" int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t* h_hbm_bytes) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

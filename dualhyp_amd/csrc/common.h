@@ -267,19 +267,33 @@ inline void dispatch_hs(int hs, F&& f) {
     else f(std::integral_constant<int, 128>{});
 }
 
+// Stop conditions (include/dualhyp_hip.h): a dh_stop_spec as the kernels take it, by value.  set / seqs are the caller's device arrays;
+// the sequences' lengths (2 .. 8) ride in the kernel arguments, 4 bits each.  All zero: off, the tail the kernels always had.
+struct dh_stop_args {
+    const uint32_t* set = nullptr;
+    const int32_t* seqs = nullptr;
+    uint32_t lens = 0;
+    int n_seqs = 0;
+    __host__ __device__ bool on() const { return set != nullptr || n_seqs != 0; }
+    bool operator==(const dh_stop_args& o) const { return set == o.set && seqs == o.seqs && lens == o.lens && n_seqs == o.n_seqs; }
+};
+// the checks of every entry that takes a dh_stop_spec (capi.hip); start_ok: the entry has a way to the prompt lengths
+int dh_stop_pack(const char* name, const dh_stop_spec* stop, bool start_ok, dh_stop_args& out);
+
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
 // dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability;
 // top_n (0: off) with top_ids / top_lp ([n_seq, tok_ld, top_n], dh_engine_set_top_logprobs): the row's top_n alternatives as well;
 // mask (nullable, [n_seq, mask_ld] words, dh_engine_set_token_mask): the sequences' allowed tokens, null = the kernels without one;
-// ngram (0: off) with start ([n_seq] prompt lengths, dh_engine_set_no_repeat_ngram): no-repeat n-grams, 0 = the kernels without it
+// ngram (0: off) with start ([n_seq] prompt lengths, dh_engine_set_no_repeat_ngram): no-repeat n-grams, 0 = the kernels without it;
+// stop (dh_engine_set_stop; its sequences count from the same `start`): the stop test behind the pick, all zero = off
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
                    float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, float* logprobs,
                    int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask, int mask_ld, int ngram, const int32_t* start,
-                   void* stream);
+                   const dh_stop_args& stop, void* stream);
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, void* stream);
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream);
 
 // the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
 // acceptance kernel (sampling.hip)
@@ -290,12 +304,12 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
                         const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, void* stream);
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream);
 
 // the selection step of beam search (beam.hip, dh_beam_select_bf16), as the engine's captured step calls it
 int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
                         const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, const uint32_t* mask,
-                        int mask_ld, void* stream);
+                        int mask_ld, const uint32_t* stop_set, int32_t* fin_tok, void* stream);
 
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads

@@ -47,6 +47,9 @@ struct dh_engine {
     int mask_ld = 0;
     int ngram = 0;                                      // dh_engine_set_no_repeat_ngram: n (0: off) and the caller's [n_seq] prompt lengths
     const int32_t* ngram_start = nullptr;
+    dh_stop_args stop;                                  // dh_engine_set_stop: the stop specification (all zero: off), the caller's [n_seq] prompt
+    const int32_t* stop_start = nullptr;                // lengths its sequences count from, and a beam call's [n_utt, W] ending ids
+    int32_t* stop_fin_tok = nullptr;
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -82,6 +85,7 @@ struct dh_engine {
         int top_n; int32_t* top_ids; float* top_lp;           // dh_engine_set_top_logprobs: likewise, and top_n is a kernel argument
         const uint32_t* mask; int mask_ld;                    // dh_engine_set_token_mask: likewise (beam steps too)
         int ngram; const int32_t* ngram_start;                // dh_engine_set_no_repeat_ngram: likewise (0 / null in a beam step's key)
+        dh_stop_args stop; const int32_t* stop_start; int32_t* stop_fin_tok;   // dh_engine_set_stop: likewise (a beam step's key: the set and fin_tok)
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
@@ -91,7 +95,8 @@ struct dh_engine {
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
                    logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
-                   mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && beam_w == k.beam_w &&
+                   mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && stop == k.stop && stop_start == k.stop_start &&
+                   stop_fin_tok == k.stop_fin_tok && beam_w == k.beam_w &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
@@ -940,7 +945,8 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
     if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
     return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
-                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram, k.ngram_start, s);
+                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
+                               k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s);
 }
 
 // tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends
@@ -957,7 +963,7 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     int rc;
     if ((rc = run_model(e, e->dec_ids, rows, rows, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if ((rc = dh_beam_select_impl(e->logits, D.vocab, rows / W, W, W, k.max_new, k.eos, 0, e->step_dev, k.beam, e->beam_cand_ids,
-                                  e->beam_cand_lp, k.mask, k.mask_ld, s))) return rc;
+                                  e->beam_cand_lp, k.mask, k.mask_ld, k.stop.set, k.stop_fin_tok, s))) return rc;
     if (W == 1) return 0;                                   // a single beam continues itself
     const int tile_units = D.head_size * 4, nt_max = std::min(beam_tiles(k.max_new), e->s_max / 32);
     const dim3 grid(cdiv(nt_max * tile_units, 256), 2 * D.n_layer * D.n_groups, rows);
@@ -983,9 +989,10 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
                                    k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                                   k.ngram_start, s);
+                                   k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
-                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram, k.ngram_start, s);
+                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
+                          k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1202,7 +1209,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1218,7 +1225,7 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1266,7 +1273,7 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
                               limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1319,6 +1326,9 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
              (int)rows, e->row_cap, e->max_tokens);
     DH_CHECK(e->ngram == 0, "dh_engine_decode_beam: no_repeat_ngram=%d is set; a beam's history lives on the host, so the device cannot "
              "form its ban set", e->ngram);
+    DH_CHECK(e->stop.n_seqs == 0, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
+             "cannot match a sequence against it (the stop set alone goes with beam search)", e->stop.n_seqs);
+    DH_CHECK(!e->stop.set || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
     DH_CHECK(e->d.vocab >= 2 * W, "dh_engine_decode_beam: vocab=%d is below the 2 W = %d candidates of a row", e->d.vocab, 2 * W);
     DH_CHECK(!e->fp8, "dh_engine_decode_beam: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(!e->kv8, "dh_engine_decode_beam: the re-parenting copies bf16 cache tiles; an fp8 KV cache is not supported");
@@ -1334,7 +1344,7 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_LAUNCH_CHECK();
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
                         prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                        e->mask, e->mask_ld, 0, nullptr, W, *st};
+                        e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1371,6 +1381,16 @@ extern "C" int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int3
              e->d.vocab);
     e->ngram = ngram;
     e->ngram_start = ngram ? start : nullptr;
+    return 0;
+}
+
+extern "C" int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const int32_t* start, int32_t* beam_fin_tok) {
+    DH_CHECK(e, "dh_engine_set_stop: null engine");
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_engine_set_stop", stop, start != nullptr, sa)) return rc;
+    e->stop = sa;
+    e->stop_start = sa.n_seqs ? start : nullptr;
+    e->stop_fin_tok = sa.set ? beam_fin_tok : nullptr;
     return 0;
 }
 

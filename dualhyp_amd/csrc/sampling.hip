@@ -462,6 +462,35 @@ __device__ __forceinline__ void store_top(int32_t* __restrict__ top_ids, float* 
     }
 }
 
+// Stop conditions (include/dualhyp_hip.h): w[0] is the pick that has just been appended, w[k] the generated token k places before it
+// (-1 where that place is prompt), m the tokens generated with the pick counted.  True when the pick is in the stop set or the
+// generated text now ends on one of the stop sequences.  A few uniform loads behind the pick; it never changes one.
+__device__ __forceinline__ bool stop_hit(const dh_stop_args& sa, const int (&w)[DH_MAX_STOP_LEN], int m) {
+    const int t = w[0];
+    if (sa.set && ((sa.set[t >> 5] >> (t & 31)) & 1u)) return true;
+    for (int s = 0; s < sa.n_seqs; ++s) {
+        const int L = (int)((sa.lens >> (4 * s)) & 15u);
+        if (L > m) continue;                                    // a match never reaches back into the prompt
+        const int32_t* q = sa.seqs + s * DH_MAX_STOP_LEN;
+        bool eq = true;
+#pragma unroll
+        for (int k = 0; k < DH_MAX_STOP_LEN; ++k)
+            if (k < L && q[L - 1 - k] != w[k]) eq = false;
+        if (eq) return true;
+    }
+    return false;
+}
+
+// the same for a pick stored at place n of the sequence's token row `row` whose prompt is p0 tokens long: the window comes from the
+// places before n, which earlier launches wrote
+__device__ __forceinline__ bool stop_hit_at(const dh_stop_args& sa, const int64_t* row, int n, int p0, int choice) {
+    int w[DH_MAX_STOP_LEN];
+    w[0] = choice;
+#pragma unroll
+    for (int k = 1; k < DH_MAX_STOP_LEN; ++k) w[k] = sa.n_seqs && n - k >= p0 && n - k >= 0 ? (int)row[n - k] : -1;
+    return stop_hit(sa, w, n + 1 - p0);
+}
+
 template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
 __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ logits, int vocab,
                                                     int64_t* __restrict__ tokens, int tok_ld,
@@ -471,7 +500,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
                                                     float* __restrict__ logprobs, int top_n,
                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                     const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                    const int32_t* __restrict__ start) {
+                                                    const int32_t* __restrict__ start, dh_stop_args sa) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
@@ -495,8 +524,10 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
             if constexpr (TOP) store_top(top_ids, top_lp, (size_t)seq * tok_ld + n, top_n, ti, tl);
             length[seq] = n + 1;
         }
-        if (eos_id >= 0 && choice == eos_id) done[seq] = 1;
-        else if (n + 1 >= tok_ld) done[seq] = 2;   // buffer full
+        if (eos_id >= 0 && choice == eos_id) done[seq] = DH_DONE_EOS;
+        else if (sa.on() && n < tok_ld && stop_hit_at(sa, tokens + (size_t)seq * tok_ld, n, sa.n_seqs ? start[seq] : 0, choice))
+            done[seq] = DH_DONE_STOP;              // uniform per launch: off, the tail it always was
+        else if (n + 1 >= tok_ld) done[seq] = DH_DONE_LENGTH;   // buffer full
     }
 }
 
@@ -515,7 +546,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                         const int32_t* __restrict__ start) {
+                                                         const int32_t* __restrict__ start, dh_stop_args sa) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
@@ -539,8 +570,10 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
             if constexpr (TOP) store_top(top_ids, top_lp, (size_t)u * tok_ld + n, top_n, ti, tl);
             length[u] = n + 1;
         }
-        if (eos_id >= 0 && choice == eos_id) done[u] = 1;
-        else if (n + 1 >= lim) done[u] = 2;        // budget spent
+        if (eos_id >= 0 && choice == eos_id) done[u] = DH_DONE_EOS;
+        else if (sa.on() && n < lim && stop_hit_at(sa, tokens + (size_t)u * tok_ld, n, start ? start[u] : limit[u] - max_new, choice))
+            done[u] = DH_DONE_STOP;
+        else if (n + 1 >= lim) done[u] = DH_DONE_LENGTH;        // budget spent
     }
 }
 
@@ -554,6 +587,8 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
 // alternatives too.  MASK: all S positions of sequence u are picked under mask row u.  BAN: position j's history runs up to the picks
 // appended at the positions before it in this launch — thread 0's stores, which the barrier at the top of the loop orders before the
 // block reads them back (a workgroup-scope fence: the block's waves share the CU's vector cache).
+// sa (stop conditions): an appended pick that stops ends the loop with done = 3 exactly where an EOS ends it with 1; every thread decides
+// it from its own copy of the window of the last DH_MAX_STOP_LEN generated tokens, never from thread 0's stores of this launch.
 template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
 __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
                                                          int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
@@ -562,13 +597,19 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
                                                          int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                         const int32_t* __restrict__ start) {
+                                                         const int32_t* __restrict__ start, dh_stop_args sa) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (done[u]) return;
     int n = length[u];
     const int lim = min(limit[u], tok_ld);
     int p0 = 0;
     if constexpr (BAN) p0 = start[u];
+    else if (sa.n_seqs) p0 = start[u];
+    // the stop window, in every thread's registers: w[k] = the generated token k places before the coming pick, from places that
+    // earlier launches wrote; every pick shifts it, so the decision below is the same for every thread without a read-back
+    int w[DH_MAX_STOP_LEN];
+#pragma unroll
+    for (int k = 1; k < DH_MAX_STOP_LEN; ++k) w[k] = sa.n_seqs && n - k >= p0 && n - k >= 0 ? (int)tokens[(size_t)u * tok_ld + n - k] : -1;
     int appended = 0, state = 0, prev = 0;
     for (int j = 0; j < S; ++j) {
         if (j > 0) {
@@ -594,9 +635,15 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
             if (tid == 0) tokens[(size_t)u * tok_ld + n] = choice;
             ++n;
             ++appended;
+            if (sa.on() && !(eos_id >= 0 && choice == eos_id)) {          // the same for every thread
+                w[0] = choice;
+                if (stop_hit(sa, w, n - p0)) { state = DH_DONE_STOP; break; }
+#pragma unroll
+                for (int k = DH_MAX_STOP_LEN - 1; k > 0; --k) w[k] = w[k - 1];
+            }
         }
-        if (eos_id >= 0 && choice == eos_id) { state = 1; break; }
-        if (n >= lim) { state = 2; break; }                               // budget spent
+        if (eos_id >= 0 && choice == eos_id) { state = DH_DONE_EOS; break; }
+        if (n >= lim) { state = DH_DONE_LENGTH; break; }                  // budget spent
     }
     if (tid == 0) {
         length[u] = n;
@@ -661,8 +708,9 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
                    const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
-                   int mask_ld, int ngram, const int32_t* start, void* stream) {
+                   int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
+    DH_CHECK(sa.n_seqs == 0 || start, "dh_sample_bf16: stop sequences need `start`, the prompt lengths");
     DH_CHECK_TOP("dh_sample_bf16");
     DH_CHECK_MASK("dh_sample_bf16");
     DH_CHECK_NGRAM("dh_sample_bf16", true);
@@ -672,7 +720,7 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
     // logprobs null: the kernel without the log-probability pass (the code it always was)
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp, mask, mask_ld, ngram, start);
+                       top_ids, top_lp, mask, mask_ld, ngram, start, sa);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -681,14 +729,14 @@ extern "C" int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* toke
                                  int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                  int step, void* stream, float* logprobs) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
+                          nullptr, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
 }
 
 extern "C" int dh_sample_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, stream);
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
 }
 
 extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -697,7 +745,7 @@ extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* to
                                    const uint32_t* mask, int mask_ld) {
     DH_CHECK(mask, "dh_sample_bf16_mask: null mask (dh_sample_bf16_top is the entry without one)");
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, stream);
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, dh_stop_args{}, stream);
 }
 
 extern "C" int dh_sample_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -706,7 +754,17 @@ extern "C" int dh_sample_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* t
                                     const uint32_t* mask, int mask_ld, int ngram, const int32_t* start) {
     DH_CHECK(ngram >= 1, "dh_sample_bf16_ngram: ngram=%d (dh_sample_bf16_mask / dh_sample_bf16_top are the entries without one)", ngram);
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, stream);
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, dh_stop_args{}, stream);
+}
+
+extern "C" int dh_sample_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                   const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop) {
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_bf16_stop", stop, start != nullptr, sa)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream);
 }
 
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -719,7 +777,7 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, void* stream) {
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
     DH_CHECK_TOP("dh_sample_rows_bf16");
     DH_CHECK_MASK("dh_sample_rows_bf16");
@@ -730,7 +788,7 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -740,7 +798,7 @@ extern "C" int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t*
                                       int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                       float* logprobs) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
+                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -748,7 +806,7 @@ extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t
                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, stream);
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -758,7 +816,7 @@ extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_
                                         int mask_ld) {
     DH_CHECK(mask, "dh_sample_rows_bf16_mask: null mask (dh_sample_rows_bf16_top is the entry without one)");
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, stream);
+                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, dh_stop_args{}, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -769,7 +827,18 @@ extern "C" int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64
     DH_CHECK(ngram >= 1, "dh_sample_rows_bf16_ngram: ngram=%d (dh_sample_rows_bf16_mask / dh_sample_rows_bf16_top are the entries without one)",
              ngram);
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
-                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, stream);
+                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, dh_stop_args{}, stream);
+}
+
+extern "C" int dh_sample_rows_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                        int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                        int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop) {
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_rows_bf16_stop", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -782,7 +851,8 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
                         const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, void* stream) {
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream) {
+    DH_CHECK(sa.n_seqs == 0 || start, "spec_accept: stop sequences need `start`, the prompt lengths");
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
     DH_CHECK_TOP("spec_accept");
     DH_CHECK_MASK("spec_accept");
@@ -792,7 +862,7 @@ int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids
     if (n_seq == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
-                       counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start);
+                       counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa);
     DH_LAUNCH_CHECK();
     return 0;
 }

@@ -16,6 +16,7 @@ from . import beam as _beam
 from . import constrain as _constrain
 from . import ngram as _ngram
 from . import ops
+from . import stop as _stop
 from .gpt import GPT
 from .schedule import shared_prefix_len
 from .speculate import check_arguments as _check_speculate
@@ -88,7 +89,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337,
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
                    share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
-                   return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0):
+                   return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
+                   stop=None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -138,7 +140,17 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     for the step.  The ban set is built inside the sampling kernels from the token buffer, per sequence and step, with no launch or
     read-back of its own; the first pick of a prompt is unaffected, and log-probabilities and alternatives stay the raw row's.  It
     goes with token_mask, speculate (a banned draft is simply not confirmed), share_prefix, return_logprobs and top_logprobs, and
-    with fp8 weights and an fp8 KV cache.  0 (the default): the call it always was."""
+    with fp8 weights and an fp8 KV cache.  0 (the default): the call it always was.
+
+    stop (include/dualhyp_hip.h, "Stop conditions"): a compiled specification (stop.compile_stop), or a list whose ints are stop ids
+    and whose lists are stop sequences of 2..8 ids (at most 8 of them).  A sequence ends, with done = 3 in the returned state, right
+    behind the first token it GENERATES that is a stop id or completes a stop sequence (a match never reaches into the prompt); that
+    token is an ordinary produced token and stays in the result, with its log-probability and alternatives — only an EOS is cut.
+    The EOS wins where both hold, and a stop on the last place of the budget is a stop.  The test sits behind the pick in the
+    sampling kernels (the prefill's first pick and every captured decode or verify step) and never changes a pick: tokens,
+    log-probabilities and alternatives are the unstopped call's up to and including that token, bit for bit, with every sampler.  What
+    it saves are steps: the EOS_CHECK_EVERY loop runs whenever an EOS or a stop can end a sequence early.  It goes with speculate,
+    share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram and fp8.  None (the default): the call it always was."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
@@ -155,6 +167,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     dev = model.transformer.wte.weight.device
     mask = _token_mask(model, token_mask, B, 1, dev)
+    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
     P = _shared_prefix(model, prompts, share_prefix, dev)
     # a verify step writes K / V up to D positions behind the last token (as far as the model has positions) and runs D + 1 rows per
@@ -181,7 +194,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     else:
         length = torch.tensor(lens, dtype=torch.int32, device=dev)
         done = torch.zeros(B, dtype=torch.int32, device=dev)
-    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram else None      # the prompt lengths: the ban's history begins there
+    # the prompt lengths: the ban's history, and a stop sequence's match, begin there
+    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -196,7 +210,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
-               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start)
+               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop)
     if ev:
         ev[1].record()
     if lp_buf is not None:
@@ -207,6 +221,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         eng.set_token_mask(mask)        # likewise
     if ngram:
         eng.set_no_repeat_ngram(ngram, start)   # likewise
+    if stop is not None:
+        eng.set_stop(stop, start)               # likewise
     try:
         steps_run = 0
         if max_new_tokens > 1:
@@ -221,11 +237,11 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                     steps_run += c
                     if steps_run < n and bool((done != 0).all()):
                         break
-            elif eos_id is None:
+            elif eos_id is None and stop is None:
                 eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
                 steps_run = n
             else:
-                # with an EOS the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
+                # with an EOS or a stop specification the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
                 # (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens, inference/ger.py:71, and a
                 # correction is usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps
                 while steps_run < n:
@@ -243,6 +259,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             eng.set_token_mask(None)
         if ngram:
             eng.set_no_repeat_ngram(0)
+        if stop is not None:
+            eng.set_stop(None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -288,13 +306,14 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
 @torch.inference_mode()
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
                       length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
-                      token_mask=None, no_repeat_ngram: int = 0):
+                      token_mask=None, no_repeat_ngram: int = 0, stop=None):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
       token_logprobs  1-D float32 CPU tensor, one value per generated token, the EOS's included — generate_batch's return_logprobs,
       sum_logprob     the device's fp32 cumulative score (their sequential fp32 sum), as a float,
-      finished        True when the hypothesis ended on the EOS; False for a live beam that completed the pool at the budget.
+      finished        True when the hypothesis ended on the EOS or a stop id; False for a live beam that completed the pool at the budget,
+      finish_reason   "eos", "stop" (it ended on an id of the stop set, which stays in tokens and counts in n) or "length" (a live beam).
     Ranked by sum_logprob / n ** length_penalty in Python floats, n = generated tokens with the EOS counted, descending, stable on
     pool order.  The scores compare directly with score_batch and with generate_batch(return_logprobs=True).
 
@@ -318,9 +337,17 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     allows at least 2 W ids (checked before anything is launched); everything behind the candidates is unchanged.
 
     no_repeat_ngram: refused unless 0 — a beam's history is re-parented on the host, so the device cannot form a beam's ban set
-    (DESIGN.md §9)."""
+    (DESIGN.md §9).
+
+    stop (as in generate_batch, the stop set only): a candidate whose id is in the set ends its hypothesis into the pool exactly as
+    the EOS does — same place rule, score and pool order — and the id stays in the hypothesis.  Stop sequences are refused before
+    anything is launched: the beams' histories live on the host."""
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
+    if stop is not None and not isinstance(stop, _stop.StopSpec):
+        stop = _stop.compile_stop(*_stop.split_entries(stop), vocab=model.config.padded_vocab_size)
+    if stop is not None and stop.sequences:
+        raise ValueError(_stop.BEAM_REFUSAL)
     if _ngram.check_ngram(no_repeat_ngram):
         raise ValueError(f"no_repeat_ngram={no_repeat_ngram} does not go with beam search: the beams' histories live on the host, so the "
                          "sampling kernels cannot form a beam's ban set; it runs under generate_batch and generate_stream")
@@ -333,6 +360,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
     dev = model.transformer.wte.weight.device
     mask = _token_mask(model, token_mask, B, 2 * W, dev)
+    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
     rows = B * W
     eng = model.engine(rows, need_pos, max(rows, max(sum(lens[a:b]) for a, b in chunks)), exact=rows > prefill_batch)
@@ -350,15 +378,17 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     if W > 1:
         for u in range(B):      # positions at or behind the prompt's end are overwritten before causality lets anything read them
             eng.copy_prefix(u * W, list(range(u * W + 1, (u + 1) * W)), -(-lens[u] // 32) * 32)
-    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0, mask=mask)
+    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0, mask=mask, stop=stop)
     if ev:
         ev[1].record()
     step = 1
     if mask is not None:
         eng.set_token_mask(mask)        # part of the captured step's key; without it the call runs the steps it always ran
+    if stop is not None:
+        eng.set_stop(stop, None, state.fin_tok_buffer())     # likewise
     try:
         while step < max_new_tokens:
-            c = max_new_tokens - step if eos_id is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
+            c = max_new_tokens - step if eos_id is None and stop is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
             eng.decode_beam(state, plen, c, eos_id, first_step=step)
             step += c
             if step < max_new_tokens and bool((state.done != 0).all()):
@@ -366,6 +396,8 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     finally:
         if mask is not None:
             eng.set_token_mask(None)
+        if stop is not None:
+            eng.set_stop(None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these hypotheses; a later cached forward must start at 0
@@ -383,7 +415,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
         timing["beam_copied_rows"] = timing.get("beam_copied_rows", 0) + moved
     out = []
     for u in range(B):
-        hyps = _beam.hypotheses(h, u, W, length_penalty)
+        hyps = _beam.hypotheses(h, u, W, length_penalty, eos_id=eos_id)
         for hyp in hyps:
             hyp["tokens"] = torch.cat([prompts_h[u], torch.tensor(hyp["tokens"], dtype=torch.int64)])
         out.append(hyps)
@@ -396,7 +428,7 @@ class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
-                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0) -> None:
+                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -417,7 +449,8 @@ class _StreamBackend:
         self.mask = None if mask is None else torch.cat([mask, torch.full_like(mask[:1], -1)]).contiguous()
         # generate_batch's no_repeat_ngram and the sequences' prompt lengths (the dummy sequence's one token is all prompt)
         self.ngram = ngram
-        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram else None
+        self.stop = stop                     # generate_batch's stop; its sequences count from the same prompt lengths
+        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram or (stop is not None and stop.sequences) else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -440,7 +473,7 @@ class _StreamBackend:
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
                         self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
-                        start=self.start, **self.kw)
+                        start=self.start, stop=self.stop, **self.kw)
         if end:
             end.record()
 
@@ -465,7 +498,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
-                    top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0):
+                    top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -486,7 +519,11 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     row-list sampler reads mask row row_seq[r]); the dummy sequence of the padding rows gets an all-ones row.
 
     no_repeat_ngram: as in generate_batch — a sequence's ban set is formed from its own row of the token buffer wherever it is
-    scheduled, so the ids do not depend on the schedule."""
+    scheduled, so the ids do not depend on the schedule.
+
+    stop: as in generate_batch — a stopped sequence (done = 3) leaves its row at the next check like one that met its EOS, and the
+    next prompt takes its KV slot.  return_state: the result gains a last element, the dict of the call's device state (tokens,
+    length, done — one row per prompt — and logprobs, top_ids, top_logprobs where asked for), as generate_batch's."""
     from .schedule import StreamScheduler
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     ngram = _ngram.check_ngram(no_repeat_ngram)
@@ -504,13 +541,14 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
     dev = model.transformer.wte.weight.device
     mask = _token_mask(model, token_mask, N, 1, dev)
+    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     P = _shared_prefix(model, prompts, share_prefix, dev)
     # slots 0..max_rows-1 and the spare one; a prefill packs at most the prefill_batch longest prompts (their tokens behind the prefix)
     eng = model.engine(sched.max_rows + 1, need_pos, max(P, sum(sorted(n - P for n in lens)[-prefill_batch:])), exact=True)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask, ngram=ngram)
+                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -524,6 +562,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         eng.set_token_mask(be.mask)
     if ngram:
         eng.set_no_repeat_ngram(ngram, be.start)
+    if stop is not None:
+        eng.set_stop(stop, be.start)
     try:
         sched.run(be)
     finally:
@@ -535,6 +575,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             eng.set_token_mask(None)
         if ngram:
             eng.set_no_repeat_ngram(0)
+        if stop is not None:
+            eng.set_stop(None)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
@@ -553,22 +595,29 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         if done_h[i] == 1:
             n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
         out.append(be.tokens[i, :n])
+    res = (out,)
     if return_logprobs:
-        res = (out, [be.logprobs[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(N)])
+        res += ([be.logprobs[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(N)],)
         if K:
             res += ([tuple(t[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for t in be.top) for i in range(N)],)
-        return res
-    return out
+    if return_state:        # the dummy sequence's row stays behind
+        st = dict(tokens=be.tokens[:N], length=be.length[:N], done=be.done[:N])
+        if return_logprobs:
+            st["logprobs"] = be.logprobs[:N]
+        if K:
+            st["top_ids"], st["top_logprobs"] = be.top[0][:N], be.top[1][:N]
+        res += (st,)
+    return res if len(res) > 1 else out
 
 
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
-             top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0):
+             top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
-    generate_batch's."""
+    generate_batch's.  stop: generate_batch's."""
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
     assert max_returned_tokens > T
@@ -576,7 +625,7 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
                          speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
-                         no_repeat_ngram=no_repeat_ngram)
+                         no_repeat_ngram=no_repeat_ngram, stop=stop)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

@@ -516,6 +516,23 @@ class _Engine:
         _lib.check(self.lib.dh_engine_set_no_repeat_ngram(self.handle, int(ngram), start.data_ptr() if ngram else None))
         self._ngram_start = start if ngram else None
 
+    def set_stop(self, stop, start: Optional[torch.Tensor] = None, beam_fin_tok: Optional[torch.Tensor] = None) -> None:
+        """The stop specification (a dualhyp_amd.stop.StopSpec on the engine's device; include/dualhyp_hip.h, "Stop conditions") for
+        later decode / decode_rows / decode_spec / decode_beam calls; None turns it off.  start: the int32 prompt lengths of their
+        sequences, needed with stop sequences; beam_fin_tok: a beam call's int32 [n_utt, W] ending ids, needed there with a stop set
+        (dh_engine_set_stop).  The caller keeps all three alive while set."""
+        if stop is not None and not stop:
+            stop = None
+        for t, name in ((start, "start"), (beam_fin_tok, "beam_fin_tok")):
+            if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous()):
+                raise TypeError(f"set_stop takes {name} as a contiguous int32 tensor on the GPU")
+        if stop is not None and stop.sequences and start is None:
+            raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
+        _lib.check(self.lib.dh_engine_set_stop(self.handle, None if stop is None else C.byref(stop.c_struct()),
+                                               None if stop is None or start is None else start.data_ptr(),
+                                               None if stop is None or beam_fin_tok is None else beam_fin_tok.data_ptr()))
+        self._stop = (stop, start, beam_fin_tok) if stop is not None else None
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"
@@ -526,6 +543,8 @@ class _Engine:
         assert mask is None or mask.size(0) == tokens.size(0), "the token mask has one row per row of tokens"
         start = getattr(self, "_ngram_start", None)
         assert start is None or start.numel() == tokens.size(0), "no_repeat_ngram's start has one prompt length per row of tokens"
+        stop = getattr(self, "_stop", None)
+        assert stop is None or stop[1] is None or stop[1].numel() == tokens.size(0), "stop's start has one prompt length per row of tokens"
 
     def graph_count(self, n_draft: int = -1) -> int:
         """Captured decode steps kept for n_draft drafts (0: the plain steps, -1: all)."""

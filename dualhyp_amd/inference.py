@@ -69,7 +69,11 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     one's 'sum_logprob' and 'avg_logprob' as above.  A generate_fn with a true attribute `constrained` (--constrain: it decodes under
     per-utterance token masks) marks every record with 'constrained': true.  A generate_fn with an attribute `no_repeat_ngram` = N > 0
     (--no_repeat_ngram) gives every record 'no_repeat_ngram': N and 'ngram_bans': the generated positions (of the ids it returned)
-    whose pick had a non-empty ban set, counted on the host from those ids (dualhyp_amd.ngram.ban_positions).  Returns corpus metrics on every rank and predictions on
+    whose pick had a non-empty ban set, counted on the host from those ids (dualhyp_amd.ngram.ban_positions).  A generate_fn with a
+    true attribute `stop` (--stop / --stop_file: it decodes under a stop specification) gives every record 'finish_reason', "eos",
+    "length" or "stop": it leaves them, one per prompt of the call it has just answered, in its attribute `finish_reasons` (from
+    the call's `done` flags, dualhyp_amd.stop.finish_reasons); with beams the best hypothesis' own 'finish_reason' is taken and every
+    entry of 'beams' carries its own.  Returns corpus metrics on every rank and predictions on
     rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
@@ -77,16 +81,22 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
         idxs = mine[b:b + batch_size]
         prompts = [examples[i]["input_ids_no_response"] for i in idxs]
         outs = generate_fn(prompts)
+        stopping = bool(getattr(generate_fn, "stop", False))
+        reasons = list(getattr(generate_fn, "finish_reasons", None) or ()) if stopping else []
         lps = tops = beams = None
         if isinstance(outs, dict):
             beams = outs["beams"]
             lps = [hyps[0]["token_logprobs"] for hyps in beams] if outs.get("logprobs") else None
+            if stopping:
+                reasons = [hyps[0].get("finish_reason") for hyps in beams]
             outs = [hyps[0]["tokens"] for hyps in beams]
         elif isinstance(outs, tuple):
             if len(outs) == 3:
                 outs, lps, tops = outs
             else:
                 outs, lps = outs
+        if stopping and len(reasons) != len(prompts):
+            raise ValueError(f"generate_fn.stop is set, but generate_fn.finish_reasons holds {len(reasons)} reasons for {len(prompts)} prompts")
         for k, (i, p, o) in enumerate(zip(idxs, prompts, outs)):
             preds[i] = {"inference": extract_answer(decode(o), decode(p)),
                         "ground_truth": examples[i]["ground_truth"].strip()}
@@ -96,11 +106,14 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 from .ngram import ban_positions
                 preds[i]["no_repeat_ngram"] = int(generate_fn.no_repeat_ngram)
                 preds[i]["ngram_bans"] = len(ban_positions(o.reshape(-1)[p.numel():].tolist(), int(generate_fn.no_repeat_ngram)))
+            if stopping:
+                preds[i]["finish_reason"] = reasons[k]
             if beams is not None:
                 text = decode(p)
                 preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
                                       "avg_logprob": _finite_or_none(hyp["sum_logprob"] / max(int(hyp["token_logprobs"].numel()), 1)),
-                                      "finished": bool(hyp["finished"])} for hyp in beams[k]]
+                                      "finished": bool(hyp["finished"]),
+                                      **({"finish_reason": hyp.get("finish_reason")} if stopping else {})} for hyp in beams[k]]
             if lps is not None:
                 total = float(lps[k].double().sum())
                 preds[i]["sum_logprob"] = total
@@ -139,6 +152,20 @@ def read_token_ids(path) -> List[int]:
             raise ValueError(f"{path}:{n}: a token id is a non-negative integer, got {line!r}")
         ids.append(int(line))
     return ids
+
+
+def stop_from_args(args, tokenizer, vocab: int, device=None):
+    """The stop specification of --stop and --stop_file (dualhyp_amd.stop.compile_stop), or None when both are off."""
+    from .stop import compile_stop, newline_ids, read_stop_file
+    ids, seqs = [], []
+    if getattr(args, "stop", "off") == "newline":
+        ids += newline_ids(tokenizer, vocab)
+    if getattr(args, "stop_file", None):
+        f_ids, f_seqs = read_stop_file(args.stop_file)
+        ids += f_ids
+        seqs += f_seqs
+    spec = compile_stop(ids, seqs, vocab, device) if ids or seqs else None
+    return spec if spec else None
 
 
 def add_lora_arguments(parser) -> None:
@@ -286,6 +313,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     constrain = getattr(args, "constrain", "off") == "prompt"
     extra = read_token_ids(args.constrain_extra) if constrain and getattr(args, "constrain_extra", None) else ()
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
+    stop = stop_from_args(args, tokenizer, model.config.padded_vocab_size, model.transformer.wte.weight.device)
+    skw = dict(stop=stop, return_state=True) if stop is not None else {}       # the reasons are read from the state's done flags
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
@@ -295,17 +324,22 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
                                      prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask,
-                                     no_repeat_ngram=ngram)
+                                     no_repeat_ngram=ngram, stop=stop)
             return {"beams": hyps, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
                                    share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask,
-                                   no_repeat_ngram=ngram)
+                                   no_repeat_ngram=ngram, **skw)
         else:
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
-                                  return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram)
+                                  return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram,
+                                  **skw)
+        if stop is not None:
+            from .stop import finish_reasons
+            gen.finish_reasons = finish_reasons(outs[-1]["done"])
+            outs = outs[:-1] if len(outs) > 2 else outs[0]
         if top_n:
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]], [(a.cpu(), b.cpu()) for a, b in outs[2]]
         if want_lp:
@@ -314,6 +348,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
 
     gen.constrained = constrain
     gen.no_repeat_ngram = ngram
+    gen.stop = stop is not None
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -404,6 +439,17 @@ def build_parser():
                         "inside the sampling kernels, under both schedules, with --constrain and --speculate; every record gains "
                         "no_repeat_ngram: N and ngram_bans, the generated positions with a non-empty ban set; not with --num_beams.  "
                         "Default 0: off, the path it always was (the WER effect on real corpora is unmeasured)")
+    p.add_argument("--stop", choices=("off", "newline"), default="off",
+                   help="newline: a sequence ends right behind the first token it generates whose text holds a newline — the harness "
+                        "keeps the first line of the answer only, so what lies behind it is decoded and thrown away; the test runs inside "
+                        "the sampling kernels, under both schedules and with every other flag; every record gains finish_reason (eos, "
+                        "length or stop).  The predictions do not depend on it where the tokenizer decodes a token prefix to a prefix of "
+                        "the text (true for the byte tokenizer, assumed for the others).  Default off: the path it always was (the "
+                        "effect on real corpora is unmeasured)")
+    p.add_argument("--stop_file", type=str, default=None, metavar="FILE",
+                   help="a stop specification, one entry per line of token ids separated by blanks: a line of one id adds to the stop "
+                        "set, a line of 2..8 ids is a stop sequence (at most 8 of them); blank lines and # comments are skipped; adds to "
+                        "--stop; stop sequences do not go with --num_beams")
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
@@ -443,6 +489,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     if args.no_repeat_ngram and args.num_beams > 1:         # beam_search_batch refuses it too; here nothing has been loaded yet
         p.error(f"--no_repeat_ngram {args.no_repeat_ngram} does not go with --num_beams {args.num_beams}: the beams' histories live on "
                 "the host, so the sampling kernels cannot form a beam's ban set")
+    if args.stop_file and args.num_beams > 1:               # beam_search_batch refuses it too; here nothing has been loaded yet
+        from .stop import BEAM_REFUSAL, read_stop_file
+        if read_stop_file(args.stop_file)[1]:
+            p.error(f"--stop_file {args.stop_file} with --num_beams {args.num_beams}: {BEAM_REFUSAL}")
     if args.constrain_extra and args.constrain == "off":
         p.error("--constrain_extra goes with --constrain prompt")
     if not 0 <= args.top_logprobs <= 8:

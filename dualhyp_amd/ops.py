@@ -283,6 +283,37 @@ def _ngram_arg(no_repeat_ngram: int, start: Optional[torch.Tensor], n_seq: int, 
     return n, keep(start, torch.int32)
 
 
+def _stop_arg(stop, vocab: int, device):
+    """The dh_stop_spec pointer of a sampler call's `stop` (a dualhyp_amd.stop.StopSpec on the logits' device, "Stop conditions" of
+    the header), or None when it is off."""
+    if stop is None or not stop:
+        return None
+    from .stop import StopSpec
+    if not isinstance(stop, StopSpec):
+        raise TypeError(f"stop is a compiled specification (dualhyp_amd.stop.compile_stop), not {stop!r}")
+    if stop.vocab != vocab:
+        raise ValueError(f"the stop specification was compiled for {stop.vocab} tokens, the logits have {vocab}")
+    if stop.device is None:
+        raise _lib.DualHypHipError("the stop specification must live on the GPU: the HIP path has no CPU fallback")
+    if stop.device != device:
+        raise ValueError(f"the stop specification lives on {stop.device}, the logits on {device}")
+    import ctypes
+    return ctypes.byref(stop.c_struct())
+
+
+def _start_arg(start: Optional[torch.Tensor], n_seq: int, device, keep):
+    """The pointer of `start`, the int32 [n_seq] prompt lengths on the logits' device, beside a stop specification."""
+    if start is None:
+        return None
+    if not start.is_cuda:
+        raise _lib.DualHypHipError("start must live on the GPU: the HIP path has no CPU fallback")
+    if start.dtype != torch.int32 or start.numel() != n_seq:
+        raise ValueError(f"start must be {torch.int32} [{n_seq}], got {start.dtype} {tuple(start.shape)}")
+    if start.device != device:
+        raise ValueError(f"start lives on {start.device}, the logits on {device}")
+    return keep(start, torch.int32)
+
+
 def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
     index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
@@ -305,12 +336,14 @@ def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor
 
 
 def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optional[int] = None, step: int = 0,
-                mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                mask: Optional[torch.Tensor] = None, stop=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One beam search step in place on `state` (a dualhyp_amd.beam.BeamState): logits [n_utt * rows_per_utt, vocab], rows_per_utt 1
     (step 0: the one live beam) or state.W; every utterance with done == 0 gets its W next beams, its records of `step` and its pool
     entries (dh_beam_select_bf16; the definition is in include/dualhyp_hip.h, "Beam search").  Returns the rows' candidates
     (ids int32, lp float32, both [rows, 2 W]): token_top_logprobs(logits, 2 W).  mask (int32 [n_utt, words], "Token masks"): row u
-    serves every beam row of utterance u; the candidates are the first 2 W allowed ids of each row (dh_beam_select_bf16_mask)."""
+    serves every beam row of utterance u; the candidates are the first 2 W allowed ids of each row (dh_beam_select_bf16_mask).
+    stop (a compiled specification, its stop set only): a candidate in the set ends its hypothesis into the pool as the EOS does, and
+    state.fin_tok_buffer() receives the id that ended each pool entry; stop sequences are refused (dh_beam_select_bf16_stop)."""
     logits = _dev(logits, name="logits")
     if logits.dim() != 2:
         raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
@@ -327,11 +360,17 @@ def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optio
     ids = torch.empty((rows, 2 * W), dtype=torch.int32, device=logits.device)
     lp = torch.empty((rows, 2 * W), dtype=torch.float32, device=logits.device)
     m_ptr, m_ld = _mask_arg(mask, state.n_utt, vocab, logits.device)
+    st_ptr = _stop_arg(stop, vocab, logits.device)
+    if st_ptr is not None and stop.sequences:
+        from .stop import BEAM_REFUSAL
+        raise ValueError(BEAM_REFUSAL)
     if rows:
         import ctypes
         args = (_p(logits), vocab, state.n_utt, int(rows_per_utt), W, state.max_new, -1 if eos_id is None else int(eos_id), int(step), None,
                 ctypes.byref(state.c_struct()), _p(ids), _p(lp))
-        if mask is not None:
+        if st_ptr is not None:
+            check(_lib.load().dh_beam_select_bf16_stop(*args, m_ptr, m_ld, st_ptr, _p(state.fin_tok_buffer()), _stream()))
+        elif mask is not None:
             check(_lib.load().dh_beam_select_bf16_mask(*args, m_ptr, m_ld, _stream()))
         else:
             check(_lib.load().dh_beam_select_bf16(*args, _stream()))
@@ -364,14 +403,16 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
            step: int = 0, logprobs: Optional[torch.Tensor] = None,
            top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
-           no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None) -> None:
+           no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
     same place in them (dh_sample_bf16_top).  mask (int32 [n_seq, words], "Token masks" of the header): row u holds the tokens
     sequence u may pick; the log-probabilities and alternatives stay the raw row's (dh_sample_bf16_mask).  no_repeat_ngram (1..8, with
     start: int32 [n_seq] prompt lengths; "No-repeat n-grams" of the header): a token that would complete an n-gram already in
-    tokens[u, start[u]:length[u]] is not picked, with or without a mask (dh_sample_bf16_ngram)."""
+    tokens[u, start[u]:length[u]] is not picked, with or without a mask (dh_sample_bf16_ngram).  stop (a compiled specification,
+    dualhyp_amd.stop.compile_stop; "Stop conditions" of the header): a sequence whose appended token is in the stop set, or completes
+    a stop sequence within tokens[u, start[u]:], gets done = 3; stop sequences need start (dh_sample_bf16_stop)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_seq, vocab = logits.shape
@@ -379,11 +420,19 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     logprobs = _logprobs_buffer(logprobs, tokens)
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
     m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
-    ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k)
+    st_ptr = _stop_arg(stop, vocab, logits.device)
+    if st_ptr is not None and stop.sequences and start is None:
+        raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
+    if st_ptr is not None and not no_repeat_ngram:
+        ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
+    else:
+        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
             0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
             _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if ngram:
+    if st_ptr is not None:
+        check(_lib.load().dh_sample_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
+    elif ngram:
         check(_lib.load().dh_sample_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
     elif mask is not None:
         check(_lib.load().dh_sample_bf16_mask(*args, m_ptr, m_ld))
@@ -395,11 +444,12 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
                 row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
                 eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None,
                 top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
-                no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None) -> None:
+                no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
     in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
     (dh_sample_rows_bf16_mask).  no_repeat_ngram, start: as in sample(), one entry of start per SEQUENCE; start None is
-    limit - max_new_tokens (dh_sample_rows_bf16_ngram)."""
+    limit - max_new_tokens (dh_sample_rows_bf16_ngram).  stop: as in sample(); start None is limit - max_new_tokens here too
+    (dh_sample_rows_bf16_stop)."""
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_rows, vocab = logits.shape
@@ -409,11 +459,17 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     logprobs = _logprobs_buffer(logprobs, tokens)
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
     m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
-    ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=True)
+    st_ptr = _stop_arg(stop, vocab, logits.device)
+    if st_ptr is not None and not no_repeat_ngram:
+        ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
+    else:
+        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=True)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
             k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if ngram:
+    if st_ptr is not None:
+        check(_lib.load().dh_sample_rows_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
+    elif ngram:
         check(_lib.load().dh_sample_rows_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
     elif mask is not None:
         check(_lib.load().dh_sample_rows_bf16_mask(*args, m_ptr, m_ld))

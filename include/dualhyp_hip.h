@@ -31,7 +31,8 @@ typedef uint16_t dh_bf16;
  * dh_sample_rows_bf16_top and dh_engine_set_top_logprobs (token alternatives); dh_beam_select_bf16, dh_engine_reserve_beams and
  * dh_engine_decode_beam (beam search); dh_sample_bf16_mask, dh_sample_rows_bf16_mask, dh_token_top_logprobs_bf16_mask,
  * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks); dh_sample_bf16_ngram, dh_sample_rows_bf16_ngram and
- * dh_engine_set_no_repeat_ngram (no-repeat n-grams). */
+ * dh_engine_set_no_repeat_ngram (no-repeat n-grams); dh_sample_bf16_stop, dh_sample_rows_bf16_stop, dh_beam_select_bf16_stop and
+ * dh_engine_set_stop (stop conditions). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -527,6 +528,62 @@ int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens,
                               void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                               const uint32_t* mask, int mask_ld, int ngram, const int32_t* start);
 
+/* Stop conditions (the "stop" of the serving interfaces; extends the decode loop of generate/base.py:62-80).  ONE definition for every
+ * entry below.
+ * A stop specification (dh_stop_spec) of a call holds
+ *   a stop SET: one row of ceil(vocab / 32) words in the token masks' bit layout — bit i & 31 of word i >> 5 is set when id i stops
+ *     a sequence — shared by all sequences of the call, and
+ *   up to DH_MAX_STOP_SEQS stop SEQUENCES of 2 .. DH_MAX_STOP_LEN ids each: int32 [n_seqs, DH_MAX_STOP_LEN] on the device, row i's
+ *     first h_seq_len[i] entries, and the lengths on the HOST (they are checked before a launch and travel in the kernel arguments).
+ *     A sequence of one id belongs in the set.
+ * For a sequence, g[0 .. m) are the tokens it has GENERATED: tokens[u, start[u] .. length[u]), start[u] its prompt length.  The prompt
+ * is excluded, as for no-repeat n-grams: a DualHyp prompt is full of newlines and "###".  After a pick t has been appended, so that
+ * g[m - 1] = t, the stop condition holds when t is in the stop set, or when g[m - L .. m) == s for some stop sequence s of length
+ * L <= m (a match never reaches back into the prompt).
+ *   The end states, in this order: t == eos_id gives done = DH_DONE_EOS; otherwise the stop condition gives done = DH_DONE_STOP, also
+ *     when that token took the last place of the budget or the buffer; otherwise the budget or buffer rule gives DH_DONE_LENGTH.
+ *   The stopping token is an ordinary produced token: appended, with its log-probability and alternatives beside it, and left in the
+ *     result (only the EOS is cut, quirk Q7).  The test is on the picked id, after mask and ban, and never changes a pick: a stopped
+ *     call's tokens, log-probabilities and alternatives are, bit for bit, the unstopped call's up to and including the first place at
+ *     which the condition holds, and nothing comes behind it.
+ *   A null specification (a null pointer, or set == null and n_seqs == 0) is off: the entries, launches and bits without it.
+ *   Where it is computed: in the tail of the sampling kernels, a few loads behind the pick; the branch is uniform per launch.  A verify
+ *     step keeps the last DH_MAX_STOP_LEN generated tokens in registers, so a pick that stops ends the step where an EOS would.
+ *   Beam search takes the stop set only: a candidate whose id is in the set ends its hypothesis into the pool exactly as the EOS does
+ *     (place rule, score, pool order), and fin_tok[u, k] receives the id that ended pool entry k.  Stop sequences are refused there:
+ *     the beams' histories live on the host. */
+#define DH_MAX_STOP_SEQS 8
+#define DH_MAX_STOP_LEN 8
+/* the values of `done` (0: live) */
+#define DH_DONE_EOS 1
+#define DH_DONE_LENGTH 2
+#define DH_DONE_STOP 3
+typedef struct dh_stop_spec {
+    const uint32_t* set;        /* device, ceil(vocab / 32) words; null: no stop ids */
+    const int32_t* seqs;        /* device, [n_seqs, DH_MAX_STOP_LEN] */
+    const int32_t* h_seq_len;   /* host, [n_seqs], each 2 .. DH_MAX_STOP_LEN */
+    int n_seqs;                 /* 0 .. DH_MAX_STOP_SEQS */
+} dh_stop_spec;
+
+/* dh_sample_bf16_ngram / dh_sample_rows_bf16_ngram with a stop specification; here mask is nullable and ngram may be 0, so with
+ * stop == null each is the entry it extends.  start: the prompt lengths, shared with ngram; stop sequences need it
+ * (dh_sample_rows_bf16_stop takes null for limit[u] - max_new_tokens).  Refused without a launch: more than DH_MAX_STOP_SEQS
+ * sequences, a length outside 2 .. DH_MAX_STOP_LEN, sequences where no start can be had. */
+int dh_sample_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                        int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                        uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop);
+int dh_sample_rows_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                             int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                             int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                             void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                             const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop);
+/* dh_beam_select_bf16_mask (mask nullable) with the stop set of `stop`; fin_tok: int32 [n_utt, W] beside st->fin_step, needed with a
+ * set.  stop == null: dh_beam_select_bf16 / dh_beam_select_bf16_mask.  A specification with sequences is refused. */
+int dh_beam_select_bf16_stop(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens, int64_t eos_id,
+                             int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp,
+                             const uint32_t* mask, int mask_ld, const dh_stop_spec* stop, int32_t* fin_tok, void* stream);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -803,6 +860,13 @@ int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int mask_ld);
  * (ngram, start) is part of the captured step's key, beside the mask: with it unset a decode call runs the graphs it always ran.
  * dh_engine_decode_beam refuses to run while it is set: beam histories live on the host.  The caller keeps start alive while set. */
 int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int32_t* start);
+/* The stop specification (see "Stop conditions" above; null = off, the default) for later dh_engine_decode, dh_engine_decode_rows,
+ * dh_engine_decode_spec and dh_engine_decode_beam calls.  start: device int32 [n_seq] prompt lengths, needed with stop sequences (the
+ * same numbers as dh_engine_set_no_repeat_ngram's, which win where both are set); beam_fin_tok: device int32 [n_utt, W], needed by a
+ * beam call under a stop set, which refuses to run under stop sequences.  The specification is copied (the lengths) and pointed to
+ * (the device arrays, which the caller keeps alive while set); it is part of the captured step's key, beside the mask and (ngram,
+ * start): with it unset a decode call runs the graphs it always ran. */
+int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const int32_t* start, int32_t* beam_fin_tok);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
