@@ -48,6 +48,7 @@ class StopSpec(C.Structure):
 SIGNATURES = {
     "dh_abi_version": (I, []),
     "dh_set_tuning": (I, [I, I]),
+    "dh_debug_gemm_routes": (U64, [I]),
     "dh_last_error": (C.c_char_p, []),
     "dh_device_info": (I, [C.c_char_p, I, C.POINTER(I), C.POINTER(I64)]),
     "dh_embed_bf16": (I, [P, P, P, I, I, I, P]),

@@ -35,6 +35,38 @@ struct GemmArgs {
 
 constexpr int DH_EPI_QKV = 4;   // internal: LoRA (optional) + rope + cache append, see dh_linear_qkv_rope_cache_bf16
 
+// Route record (host side only): one bit per GEMM launch site, OR-ed into a thread-local mask next to the launch and read by
+// dh_debug_gemm_routes (include/dualhyp_hip.h).  The tests assert which kernels a call took; tests/gemm_exact_reference.py
+// mirrors the numbering.
+enum DhGemmRoute : int {
+    DH_ROUTE_T128_S2 = 0,      // gemm.hip: 128-tile kernel, 2 stages
+    DH_ROUTE_T128_S4,          //           4 stages
+    DH_ROUTE_W8_PIPE0,         // gemm256.hip: 8-wave 256-tile kernel, per PIPE (0 BK = 64 double buffer, 1 4-stage, 2 ping-pong, 3 persistent)
+    DH_ROUTE_W8_PIPE1,
+    DH_ROUTE_W8_PIPE2,
+    DH_ROUTE_W8_PIPE3,
+    DH_ROUTE_W4_TILE,          // 4-wave 256-tile kernel, one block per tile
+    DH_ROUTE_W4_PERSIST,       //   persistent blocks
+    DH_ROUTE_W4_XA,            //   with the in-GEMM LoRA down-projection (set together with one of the two above)
+    DH_ROUTE_MID_NG1,          // gemm_mid.hip: W straight to VGPRs, 1 / 2 / 4 row groups
+    DH_ROUTE_MID_NG2,
+    DH_ROUTE_MID_NG4,
+    DH_ROUTE_MID_NG1_RING,     //   W through the per-wave LDS ring (1 or 2 row groups only)
+    DH_ROUTE_MID_NG2_RING,
+    DH_ROUTE_DT_FUSED,         // gemm_dt.hip: fused epilogues (SwiGLU, adapter, plain + resid)
+    DH_ROUTE_SKINNY,           // gemm_skinny.hip: gemm_skinny_kernel
+    DH_ROUTE_SWIGLU_SKINNY2,
+    DH_ROUTE_SKINNY_N,
+    DH_ROUTE_K64,
+    DH_ROUTE_K64_MUL,
+    DH_ROUTE_ROWS,             // partial sums: the rows kernel
+    DH_ROUTE_PARTIAL_WAVES,    //   K split over the waves of a block
+    DH_ROUTE_PAIRS_TILED,      // gemm_dt.hip: pair sums
+    DH_ROUTE_CHAIN_TILED,      //   the one-launch total
+    DH_ROUTE_COUNT
+};
+void dh_gemm_route(int route);      // gemm.hip
+
 // M <= 32: one pass over W straight from HBM to registers (gemm_skinny.hip)
 int dh_linear_skinny(const GemmArgs& a, int epilogue, hipStream_t s);
 // y[M, N] = bf16(x . W^T), N = 16 .. 64, thousands of rows (gemm_skinny.hip: gemm_skinny_n_kernel); the bits of the tiled kernels

@@ -231,6 +231,7 @@ template <int EPI, bool RESID, int NST>
 int launch_n(const GemmArgs& a, hipStream_t s) {
     constexpr int lds = NST * 2 * TILE_BYTES;
     DH_MAX_LDS_ONCE((gemm_nt_kernel<EPI, RESID, NST>), lds);
+    dh_gemm_route(NST == 4 ? DH_ROUTE_T128_S4 : DH_ROUTE_T128_S2);
     hipLaunchKernelGGL((gemm_nt_kernel<EPI, RESID, NST>), dim3(a.nb_n * a.nb_m), dim3(256), lds, s, a);
     DH_LAUNCH_CHECK();
     return 0;
@@ -245,6 +246,15 @@ int launch(const GemmArgs& a, hipStream_t s) {
 }
 
 }  // namespace
+
+// the route record: which GEMM kernels this thread has launched since the last reset (gemm.h, dh_debug_gemm_routes)
+static thread_local uint64_t g_gemm_routes = 0;
+void dh_gemm_route(int route) { g_gemm_routes |= 1ull << route; }
+extern "C" uint64_t dh_debug_gemm_routes(int reset) {
+    const uint64_t r = g_gemm_routes;
+    if (reset) g_gemm_routes = 0;
+    return r;
+}
 
 int g_gemm_variant = 5;
 int g_tail_split = 1;     // dh_set_tuning(28, 0): no row split of grids with a small last round (A/B)
@@ -311,12 +321,18 @@ extern "C" int dh_linear_qkv_lora_rope_cache_bf16(const dh_bf16* x, const dh_bf1
                                n_head, n_groups, hs, s_max, stream);
 }
 
+// A segment boundary inside [0, N) must be a multiple of 32 (a lane's group of output columns lies in one segment); "no such segment"
+// is any value >= N — the header's "pass N,N for a single segment" holds for every N the GEMMs take (N % 8 == 0), not only N % 32 == 0.
+static bool lora_splits_ok(int split0, int split1, int N) {
+    return (split0 % 32 == 0 || split0 >= N) && (split1 % 32 == 0 || split1 >= N) && split0 <= split1;
+}
+
 // dh_linear_bf16's LORA epilogue with the down-projection computed by the library (include/dualhyp_hip.h)
 int dh_linear_lora_impl(const dh_bf16* x, const dh_bf16* w, dh_bf16* y, int M, int N, int K, const dh_bf16* lora_a, const dh_bf16* lora_b,
                         float lora_scale, int split0, int split1, const dh_bf16* resid, dh_bf16* xa_work, int kernel, hipStream_t s) {
     DH_CHECK(x && w && y && lora_a && lora_b && xa_work, "dh_linear_lora_bf16: null argument");
     DH_CHECK(M >= 0 && N > 0 && K > 0 && K % BK == 0 && N % 8 == 0, "dh_linear_lora_bf16: bad shape M=%d N=%d K=%d", M, N, K);
-    DH_CHECK(split0 % 32 == 0 && split1 % 32 == 0 && split0 <= split1, "dh_linear_lora_bf16: LoRA splits must be multiples of 32");
+    DH_CHECK(lora_splits_ok(split0, split1, N), "dh_linear_lora_bf16: LoRA splits must be multiples of 32 (or N: no such segment)");
     if (M == 0) return 0;
     const int nseg = 1 + (split0 < N) + (split1 < N);
     if (kernel != 2 && M > 32 && dh_linear_is_big(M, N, DH_EPI_LORA)) {
@@ -433,7 +449,7 @@ int dh_linear_impl(const dh_bf16* x, const dh_bf16* w, dh_bf16* y, int M, int N,
     if (big) {
         if (epilogue == DH_EPI_LORA) {
             DH_CHECK(xa && lora_b && xa_ld >= 16 && xa_ld % 8 == 0, "dh_linear_bf16: LORA epilogue needs xa/lora_b");
-            DH_CHECK(split0 % 32 == 0 && split1 % 32 == 0 && split0 <= split1, "dh_linear_bf16: LoRA splits must be multiples of 32");
+            DH_CHECK(lora_splits_ok(split0, split1, N), "dh_linear_bf16: LoRA splits must be multiples of 32 (or N: no such segment)");
             DH_CHECK(xa_ld >= 16 * (1 + (split0 < N) + (split1 < N)), "dh_linear_bf16: xa_ld too small for the segments");
         }
         if (epilogue == DH_EPI_SWIGLU) DH_CHECK(w2 != nullptr && resid == nullptr && N % 32 == 0, "dh_linear_bf16: bad SWIGLU arguments");
@@ -446,7 +462,7 @@ int dh_linear_impl(const dh_bf16* x, const dh_bf16* w, dh_bf16* y, int M, int N,
             return skinny ? dh_linear_skinny(a, epilogue, s) : launch<DH_EPI_PLAIN>(a, s);
         case DH_EPI_LORA:
             DH_CHECK(xa && lora_b && xa_ld >= 16 && xa_ld % 8 == 0, "dh_linear_bf16: LORA epilogue needs xa/lora_b");
-            DH_CHECK(split0 % 32 == 0 && split1 % 32 == 0 && split0 <= split1, "dh_linear_bf16: LoRA splits must be multiples of 32");
+            DH_CHECK(lora_splits_ok(split0, split1, N), "dh_linear_bf16: LoRA splits must be multiples of 32 (or N: no such segment)");
             DH_CHECK(xa_ld >= 16 * (1 + (split0 < N) + (split1 < N)), "dh_linear_bf16: xa_ld too small for the segments");
             return skinny ? dh_linear_skinny(a, epilogue, s) : launch<DH_EPI_LORA>(a, s);
         case DH_EPI_SWIGLU:

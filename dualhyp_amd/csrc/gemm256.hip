@@ -1360,6 +1360,8 @@ int launch_w4p(const GemmArgs& a, hipStream_t s) {
     DH_MAX_LDS_ONCE(kfn, lds);
     int blocks = a.nb_n * a.nb_m;
     if (PERSIST) blocks = blocks < g256_cu_count() ? blocks : g256_cu_count();   // one block per CU walks the tiles
+    dh_gemm_route(PERSIST ? DH_ROUTE_W4_PERSIST : DH_ROUTE_W4_TILE);
+    if (XA) dh_gemm_route(DH_ROUTE_W4_XA);
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, s, a);
     DH_LAUNCH_CHECK();
     return 0;
@@ -1407,6 +1409,7 @@ int launch_one(const GemmArgs& a, hipStream_t s) {
         }
         blocks = blocks < cu ? blocks : cu;
     }
+    dh_gemm_route(DH_ROUTE_W8_PIPE0 + PIPE);
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), 4 * TILE_B, s, a);
     DH_LAUNCH_CHECK();
     return 0;

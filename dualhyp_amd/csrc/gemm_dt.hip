@@ -325,6 +325,7 @@ template <int MODE, int NSTAGE, int WN = 2>
 int launch_dt_n(const DtArgs& a, int blocks, hipStream_t s, int ny = 1) {
     constexpr int lds = NSTAGE * stage_bytes<WN>();     // WN 2: 128 KiB / 64 KiB; WN 4: 144 KiB
     DH_MAX_LDS_ONCE((gemm_dt_kernel<MODE, NSTAGE, WN>), lds);
+    dh_gemm_route(MODE == 0 ? DH_ROUTE_CHAIN_TILED : MODE == 4 ? DH_ROUTE_PAIRS_TILED : DH_ROUTE_DT_FUSED);
     hipLaunchKernelGGL((gemm_dt_kernel<MODE, NSTAGE, WN>), dim3(blocks, ny), dim3(WN * 128), lds, s, a);
     DH_LAUNCH_CHECK();
     return 0;

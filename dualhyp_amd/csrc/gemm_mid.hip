@@ -320,12 +320,14 @@ int launch_mid(const GemmArgs& a, hipStream_t s) {
         if (g_mid_wlds && a.K % (64 * MidShape<EPI>::KQ) == 0) {
             constexpr int lds = xlds + 8 * wl_ring_bytes<NG>();
             DH_MAX_LDS_ONCE((gemm_mid_kernel<EPI, NG, true>), lds);
+            dh_gemm_route(NG == 1 ? DH_ROUTE_MID_NG1_RING : DH_ROUTE_MID_NG2_RING);
             hipLaunchKernelGGL((gemm_mid_kernel<EPI, NG, true>), grid, block, lds, s, a);
             DH_LAUNCH_CHECK();
             return 0;
         }
     }
     if (xlds > 48 * 1024) DH_MAX_LDS_ONCE((gemm_mid_kernel<EPI, NG, false>), xlds);
+    dh_gemm_route(NG == 1 ? DH_ROUTE_MID_NG1 : NG == 2 ? DH_ROUTE_MID_NG2 : DH_ROUTE_MID_NG4);
     hipLaunchKernelGGL((gemm_mid_kernel<EPI, NG, false>), grid, block, xlds, s, a);
     DH_LAUNCH_CHECK();
     return 0;

@@ -430,6 +430,7 @@ int launch_rows(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float* y3
     static_assert(lds <= 160 * 1024, "x rounds do not fit in LDS");
     if (lds > 48 * 1024) DH_MAX_LDS_ONCE((gemm_skinny_rows_kernel<KPS, NG, NGL, CT>), lds);
     dim3 grid(cdiv(N, 128 * CT), ksplit, cdiv(M, NG * 32)), block(512);
+    dh_gemm_route(DH_ROUTE_ROWS);
     hipLaunchKernelGGL((gemm_skinny_rows_kernel<KPS, NG, NGL, CT>), grid, block, lds, s, x, w, w_ext, y32, M, n_main, N, K);
     DH_LAUNCH_CHECK();
     return 0;
@@ -465,6 +466,7 @@ int launch_rows_ng(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float*
 template <int EPI>
 int launch(const GemmArgs& a, hipStream_t s) {
     dim3 grid(cdiv(a.N, ROWS)), block(512);
+    dh_gemm_route(DH_ROUTE_SKINNY);
     if (a.resid)
         hipLaunchKernelGGL((gemm_skinny_kernel<EPI, true>), grid, block, 0, s, a);
     else
@@ -637,6 +639,7 @@ extern "C" int dh_linear_partial_bf16(const dh_bf16* x, const dh_bf16* w, const 
     }
     DH_CHECK(ksplit <= 8, "dh_linear_partial_bf16: ksplit must be 1..8 for this shape");
     // K-split-over-waves kernel: 32 rows per launch
+    dh_gemm_route(DH_ROUTE_PARTIAL_WAVES);
     for (int m0 = 0; m0 < M; m0 += 32) {
         const int mm = M - m0 < 32 ? M - m0 : 32;
         hipLaunchKernelGGL(gemm_skinny_partial_kernel, dim3(N / ROWS, ksplit), dim3(512), 0, s, x + (size_t)m0 * K, w,
@@ -692,6 +695,7 @@ bool dh_linear_skinny_n_ok(int M, int N, int K, const void* x, const void* w, co
 int dh_linear_skinny_n(const dh_bf16* x, const dh_bf16* w, dh_bf16* y, int M, int N, int K, hipStream_t s) {
     const dim3 grid(cdiv(M, 64)), block(256);
     const int nt = N / 16, lds = 4 * (64 * 128 + nt * 16 * 128);
+    dh_gemm_route(DH_ROUTE_SKINNY_N);
     switch (nt) {
         case 1: hipLaunchKernelGGL((gemm_skinny_n_kernel<1>), grid, block, lds, s, x, w, y, M, K, N); break;
         case 2: hipLaunchKernelGGL((gemm_skinny_n_kernel<2>), grid, block, lds, s, x, w, y, M, K, N); break;
@@ -709,6 +713,7 @@ bool dh_linear_k64_ok(int M, int N, int K, const void* x, const void* w, const v
 }
 int dh_linear_k64(const dh_bf16* x, const dh_bf16* w, const dh_bf16* mul, dh_bf16* y, int M, int N, hipStream_t s) {
     const dim3 grid(cdiv(N, 256), cdiv(M, 64)), block(256);
+    dh_gemm_route(mul ? DH_ROUTE_K64_MUL : DH_ROUTE_K64);
     if (mul) hipLaunchKernelGGL((gemm_k64_kernel<true>), grid, block, 0, s, x, w, mul, y, M, N);
     else hipLaunchKernelGGL((gemm_k64_kernel<false>), grid, block, 0, s, x, w, mul, y, M, N);
     DH_LAUNCH_CHECK();
@@ -718,6 +723,7 @@ int dh_linear_k64(const dh_bf16* x, const dh_bf16* w, const dh_bf16* mul, dh_bf1
 int dh_linear_skinny(const GemmArgs& a, int epilogue, hipStream_t s) {
     if (epilogue == DH_EPI_SWIGLU && g_swiglu2 && a.N % 32 == 0) {
         DH_MAX_LDS_ONCE(swiglu_skinny2_kernel, 64 * 1024);
+        dh_gemm_route(DH_ROUTE_SWIGLU_SKINNY2);
         hipLaunchKernelGGL(swiglu_skinny2_kernel, dim3(a.N / 32), dim3(512), 64 * 1024, s, a);
         DH_LAUNCH_CHECK();
         return 0;

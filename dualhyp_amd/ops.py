@@ -46,6 +46,16 @@ class _Keep(list):
         return t.data_ptr()
 
 
+def _out(out: Optional[torch.Tensor], shape, dtype, device, name: str = "out") -> torch.Tensor:
+    """The caller's output buffer (checked: on the GPU, contiguous, right dtype and shape), or a fresh one."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    shape = tuple(int(d) for d in shape)
+    if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise ValueError(f"{name} must be a contiguous {dtype} GPU tensor of shape {shape}, got {tuple(out.shape)} {out.dtype}")
+    return out
+
+
 def embed(ids: torch.Tensor, wte: torch.Tensor) -> torch.Tensor:
     ids = _dev(ids.reshape(-1), torch.int64, "ids")
     wte = _dev(wte, name="wte")
@@ -84,7 +94,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, *, epilogue: int = EPI_PLAIN, w2: O
     M = x.numel() // K
     N = w.size(0)
     assert w.size(1) == K, f"weight is {tuple(w.shape)}, input feature size {K}"
-    y = out if out is not None else torch.empty((*x.shape[:-1], N), dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (*x.shape[:-1], N), torch.bfloat16, x.device)
     s0, s1 = splits if splits is not None else (N, N)
     xa_ld = 0
     if xa is not None:
@@ -136,9 +146,11 @@ def linear_qkv_rope_cache(x: torch.Tensor, w: torch.Tensor, cos: torch.Tensor, s
 
 
 def linear_lora(x: torch.Tensor, w: torch.Tensor, lora_a: torch.Tensor, lora_b: torch.Tensor, *, lora_scale: float = 1.0,
-                splits: Optional[Tuple[int, int]] = None, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+                splits: Optional[Tuple[int, int]] = None, resid: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, xa_work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x W^T + scale * bf16(x A^T) B^T (+ resid) with the down-projection computed by the library (inside the GEMM's K loop on the
-    4-wave 256-tile kernel, else one more launch); lora_a [16 * nseg, K], lora_b [N, 16]; dh_linear_lora_bf16."""
+    4-wave 256-tile kernel, else one more launch); lora_a [16 * nseg, K], lora_b [N, 16]; dh_linear_lora_bf16.  `out` [.., N] and
+    `xa_work` [M, 16 * nseg] (the down-projection's work buffer): caller-owned contiguous bf16 buffers instead of fresh ones."""
     x, w, lora_a, lora_b = _dev(x, name="x"), _dev(w, name="w"), _dev(lora_a, name="lora_a"), _dev(lora_b, name="lora_b")
     K = x.size(-1)
     M, N = x.numel() // K, w.size(0)
@@ -147,8 +159,8 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, lora_a: torch.Tensor, lora_b: 
     assert lora_a.shape == (16 * nseg, K) and lora_b.shape == (N, 16), (lora_a.shape, lora_b.shape)
     if resid is not None:
         _dev(resid, name="resid")
-    y = torch.empty((*x.shape[:-1], N), dtype=torch.bfloat16, device=x.device)
-    work = torch.empty((M, 16 * nseg), dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (*x.shape[:-1], N), torch.bfloat16, x.device)
+    work = _out(xa_work, (M, 16 * nseg), torch.bfloat16, x.device, "xa_work")
     check(_lib.load().dh_linear_lora_bf16(_p(x), _p(w), _p(y), M, N, K, _p(lora_a), _p(lora_b), float(lora_scale), s0, s1, _p(resid),
                                           _p(work), _stream()))
     return y
@@ -667,25 +679,27 @@ def cross_entropy_bwd(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Te
     return out.view(logits.shape)
 
 
-def linear_partial(x: torch.Tensor, w: torch.Tensor, w_ext: Optional[torch.Tensor] = None, ksplit: int = 1) -> torch.Tensor:
+def linear_partial(x: torch.Tensor, w: torch.Tensor, w_ext: Optional[torch.Tensor] = None, ksplit: int = 1,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 partial sums [ksplit, M, n_main+n_ext] of x @ [w; w_ext].T (decode rows, M <= 4096); dh_linear_partial_bf16."""
     x, w = _dev(x, name="x"), _dev(w, name="w")
     K = x.size(-1)
     M = x.numel() // K
     n_ext = 0 if w_ext is None else _dev(w_ext, name="w_ext").size(0)
-    y = torch.empty((ksplit, M, w.size(0) + n_ext), dtype=torch.float32, device=x.device)
+    y = _out(out, (ksplit, M, w.size(0) + n_ext), torch.float32, x.device)
     check(_lib.load().dh_linear_partial_bf16(_p(x), _p(w), _p(w_ext), _p(y), M, w.size(0), n_ext, K, ksplit, _stream()))
     return y
 
 
-def linear_partial_pairs(x: torch.Tensor, w: torch.Tensor, w_ext: Optional[torch.Tensor] = None, ksplit: int = 1) -> torch.Tensor:
+def linear_partial_pairs(x: torch.Tensor, w: torch.Tensor, w_ext: Optional[torch.Tensor] = None, ksplit: int = 1,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 [(ksplit+1)//2, M, n_main+n_ext]: sums of adjacent pairs of `linear_partial`'s slices, from the tiled split-K
     kernel; dh_linear_partial_pairs_bf16."""
     x, w = _dev(x, name="x"), _dev(w, name="w")
     K = x.size(-1)
     M = x.numel() // K
     n_ext = 0 if w_ext is None else _dev(w_ext, name="w_ext").size(0)
-    y = torch.empty(((ksplit + 1) // 2, M, w.size(0) + n_ext), dtype=torch.float32, device=x.device)
+    y = _out(out, ((ksplit + 1) // 2, M, w.size(0) + n_ext), torch.float32, x.device)
     check(_lib.load().dh_linear_partial_pairs_bf16(_p(x), _p(w), _p(w_ext), _p(y), M, w.size(0), n_ext, K, ksplit, _stream()))
     return y
 
@@ -702,14 +716,15 @@ def combine_partials(parts: torch.Tensor, pairs: bool = True) -> torch.Tensor:
     return out
 
 
-def linear_chain(x: torch.Tensor, w: torch.Tensor, w_ext: Optional[torch.Tensor] = None, ksplit: int = 1) -> torch.Tensor:
+def linear_chain(x: torch.Tensor, w: torch.Tensor, w_ext: Optional[torch.Tensor] = None, ksplit: int = 1,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 [M, n_main+n_ext]: the ksplit slices of `linear_partial` combined in the family's order (`combine_partials`)
     by one launch of the tiled kernel (M >= 65); dh_linear_chain_bf16."""
     x, w = _dev(x, name="x"), _dev(w, name="w")
     K = x.size(-1)
     M = x.numel() // K
     n_ext = 0 if w_ext is None else _dev(w_ext, name="w_ext").size(0)
-    y = torch.empty((M, w.size(0) + n_ext), dtype=torch.float32, device=x.device)
+    y = _out(out, (M, w.size(0) + n_ext), torch.float32, x.device)
     check(_lib.load().dh_linear_chain_bf16(_p(x), _p(w), _p(w_ext), _p(y), M, w.size(0), n_ext, K, ksplit, _stream()))
     return y
 
@@ -800,28 +815,31 @@ def swiglu_fwd(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     return act
 
 
-def linear_swiglu_train(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor):
+def linear_swiglu_train(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
     """-> (act, g, u): the training forward of fc_1 / fc_2 (ger/model.py:313-315) in one GEMM launch that also keeps the rounded
     pre-activations for the backward; the bits of linear(x, w1), linear(x, w2), swiglu_fwd(g, u)."""
     k = _Keep()
     M, K = x.shape
     I = w1.size(0)
-    act = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
-    g, u = torch.empty_like(act), torch.empty_like(act)
+    oa, og, ou = out if out is not None else (None, None, None)       # `out`: caller-owned (act, g, u)
+    act = _out(oa, (M, I), torch.bfloat16, x.device, "out[0]")
+    g, u = _out(og, (M, I), torch.bfloat16, x.device, "out[1]"), _out(ou, (M, I), torch.bfloat16, x.device, "out[2]")
     check(_lib.load().dh_linear_swiglu_train_bf16(k(x), k(w1), k(w2), _p(act), _p(g), _p(u), M, I, K, _stream()))
     return act, g, u
 
 
-def linear_mul(x: torch.Tensor, w: torch.Tensor, mul: torch.Tensor) -> torch.Tensor:
+def linear_mul(x: torch.Tensor, w: torch.Tensor, mul: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16(bf16(x @ w.T) * mul): the multiply inside the GEMM's epilogue for large shapes (dh_linear_mul_bf16), else linear then *."""
     M, K = x.shape
     N = w.size(0)
     if (M >= 256 and N >= 256 and -(-M // 256) * -(-N // 256) >= 128 and mul.is_contiguous() and mul.shape == (M, N)
             and not os.environ.get("DUALHYP_NO_LINEAR_MUL")):        # (the variable: same-box A/B of the fused multiply)
         k = _Keep()
-        y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        y = _out(out, (M, N), torch.bfloat16, x.device)
         check(_lib.load().dh_linear_mul_bf16(k(x), k(w), _p(y), M, N, K, k(mul), _stream()))
         return y
+    if out is not None:
+        return torch.mul(linear(x, w), mul, out=_out(out, (M, N), torch.bfloat16, x.device))
     return linear(x, w) * mul
 
 

@@ -51,6 +51,10 @@ int dh_abi_version(void);
  * 2 always); 23 a forward asked for the last position's logits only runs the last block's attention output, projection and MLP on each
  * sequence's last row (1, default) or on every row (0) — same bits either way (dh_engine_forward). */
 int dh_set_tuning(int key, int value);
+/* Debug aid for tests: a bit mask of the GEMM kernels launched on the calling thread since the last reset, one bit per launch
+ * site (enum DhGemmRoute in csrc/gemm.h; tests/gemm_exact_reference.py mirrors the numbering); reset != 0 clears it after
+ * the read.  Host side only: a thread-local OR next to each launch. */
+uint64_t dh_debug_gemm_routes(int reset);
 const char* dh_last_error(void);
 /* Name of the first visible device's gcnArch ("gfx950") into buf; fails when no GPU. */
 int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t* h_hbm_bytes);
@@ -99,8 +103,8 @@ int dh_qkv_rope_cache_bf16(const dh_bf16* qkv, const dh_bf16* cos, const dh_bf16
  *  LORA   : xa [M, xa_ld] = bf16(x·A^T) (from dh_linear_bf16 PLAIN with W=A), lora_b [N,16]
  *           (rank zero-padded to 16).  Output column n uses xa columns
  *           [16*seg, 16*seg+16) with seg = (n >= split0) + (n >= split1): the contiguous
- *           [Q|K|V] placement of ger/lora.py:226-234,343-347 (quirk Q2).  split0/1 % 32 == 0;
- *           pass N,N for a single segment.
+ *           [Q|K|V] placement of ger/lora.py:226-234,343-347 (quirk Q2).  A boundary inside [0, N) must be
+ *           a multiple of 32; pass N,N for a single segment (any value >= N means "no such segment").
  *  SWIGLU : w2 [N,K] second weight (fc_2); W is fc_1.
  *  ADAPTER: vec_a = adapter_scale[N], vec_b = adapter_bias[N].
  *  resid  : if non-NULL, y = bf16(resid + y_epilogue)  (residual add of ger/model.py:185-186)
@@ -144,6 +148,9 @@ int dh_linear_qkv_lora_rope_cache_bf16(const dh_bf16* x, const dh_bf16* w, int M
  *   y32[p][m][n] = sum over K-slice p of x[m,:] . W'[n,:],  W' = [w (n_main rows) ; w_ext (n_ext rows)]
  * y32: [ksplit][M][n_main+n_ext] fp32.  w_ext is the rank-padded LoRA A (so x·A^T comes out of the
  * same pass over x as x·W^T and never needs its own launch).  K %% 32 == 0, rows %% 16 == 0.
+ * K-slices, in k-steps of 32: where ksplit slices of 8 or 16 k-steps tile K exactly (ceil(K/32/ksplit) = 8 or 16, the shapes the
+ * engine uses), slice p is the contiguous run of k-steps [p kps, (p+1) kps).  Any other (K, ksplit <= 8): runs of 8 k-steps dealt
+ * round robin, k-step ks in slice (ks / 8) %% ksplit (a slice may be empty: zeros).  The slices always add up to the full product.
  *
  * K-SLICE COMBINE ORDER of the decode family (round 3; one order for every row count, so a row's bits do not depend on
  * how many rows are decoded with it): a slice is one fp32 chain of v_mfma_f32_16x16x32_bf16 from zero, k ascending;
