@@ -97,6 +97,9 @@ SIGNATURES = {
     "dh_sample_rows_bf16_ngram": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P]),
     "dh_sample_bf16_stop": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec)]),
     "dh_sample_rows_bf16_stop": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec)]),
+    "dh_sample_bf16_nucleus": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F]),
+    "dh_sample_rows_bf16_nucleus": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
+                                        F, F]),
     "dh_beam_select_bf16_stop": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P, P]),
     "dh_token_top_logprobs_bf16_mask": (I, [P, I, I, P, P, I, P, I, I, P]),
     "dh_beam_select_bf16_mask": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, P]),
@@ -134,6 +137,7 @@ SIGNATURES = {
     "dh_engine_set_token_mask": (I, [P, P, I]),
     "dh_engine_set_no_repeat_ngram": (I, [P, I, P]),
     "dh_engine_set_stop": (I, [P, C.POINTER(StopSpec), P, P]),
+    "dh_engine_set_nucleus": (I, [P, F, F]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

@@ -38,6 +38,18 @@ int dh_stop_pack(const char* name, const dh_stop_spec* stop, bool start_ok, dh_s
     return 0;
 }
 
+// (top_p, min_p) -> what the kernels take by value, with the header's argument checks ("Nucleus and min-p"): nothing is launched
+int dh_nucleus_pack(const char* name, float top_p, float min_p, dh_nucleus_args& out) {
+    out = dh_nucleus_args{};
+    DH_CHECK(top_p > 0.f && top_p <= 1.f, "%s: top_p=%g is not in (0, 1] (1 = off)", name, (double)top_p);      // false for a NaN
+    DH_CHECK(min_p >= 0.f && min_p <= 1.f, "%s: min_p=%g is not in [0, 1] (0 = off)", name, (double)min_p);
+    out.top_p = top_p;
+    out.min_p = min_p;
+    out.min_p_on = min_p > 0.f;
+    out.lmin = out.min_p_on ? (float)log((double)min_p) : 0.f;
+    return 0;
+}
+
 extern "C" int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t* h_hbm_bytes) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

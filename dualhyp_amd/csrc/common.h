@@ -280,20 +280,36 @@ struct dh_stop_args {
 // the checks of every entry that takes a dh_stop_spec (capi.hip); start_ok: the entry has a way to the prompt lengths
 int dh_stop_pack(const char* name, const dh_stop_spec* stop, bool start_ok, dh_stop_args& out);
 
+// Nucleus and min-p (include/dualhyp_hip.h): the two parameters as the kernels take them, by value.  top_p is the caller's fp32 value
+// (1: off); lmin = (float)log((double)min_p), computed once here on the host, is read only when min_p_on.  The default is off: the
+// sampled branch the kernels always had.
+struct dh_nucleus_args {
+    float top_p = 1.f;
+    float lmin = 0.f;
+    int min_p_on = 0;
+    float min_p = 0.f;                                  // the caller's value, for the key of a captured step
+    __host__ __device__ bool on() const { return top_p < 1.f || min_p_on != 0; }
+    bool operator==(const dh_nucleus_args& o) const { return top_p == o.top_p && min_p == o.min_p; }
+};
+// the checks of every entry that takes (top_p, min_p) (capi.hip): top_p in (0, 1], min_p in [0, 1], neither NaN
+int dh_nucleus_pack(const char* name, float top_p, float min_p, dh_nucleus_args& out);
+
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
 // dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability;
 // top_n (0: off) with top_ids / top_lp ([n_seq, tok_ld, top_n], dh_engine_set_top_logprobs): the row's top_n alternatives as well;
 // mask (nullable, [n_seq, mask_ld] words, dh_engine_set_token_mask): the sequences' allowed tokens, null = the kernels without one;
 // ngram (0: off) with start ([n_seq] prompt lengths, dh_engine_set_no_repeat_ngram): no-repeat n-grams, 0 = the kernels without it;
-// stop (dh_engine_set_stop; its sequences count from the same `start`): the stop test behind the pick, all zero = off
+// stop (dh_engine_set_stop; its sequences count from the same `start`): the stop test behind the pick, all zero = off;
+// nuc (dh_engine_set_nucleus): top_p / min_p of the sampled branch, the default = off
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
                    float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, float* logprobs,
                    int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask, int mask_ld, int ngram, const int32_t* start,
-                   const dh_stop_args& stop, void* stream);
+                   const dh_stop_args& stop, void* stream, const dh_nucleus_args& nuc = dh_nucleus_args{});
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream);
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream,
+                        const dh_nucleus_args& nuc = dh_nucleus_args{});
 
 // the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
 // acceptance kernel (sampling.hip)

@@ -50,6 +50,7 @@ struct dh_engine {
     dh_stop_args stop;                                  // dh_engine_set_stop: the stop specification (all zero: off), the caller's [n_seq] prompt
     const int32_t* stop_start = nullptr;                // lengths its sequences count from, and a beam call's [n_utt, W] ending ids
     int32_t* stop_fin_tok = nullptr;
+    dh_nucleus_args nuc;                                // dh_engine_set_nucleus: top_p / min_p of later decode / decode_rows calls (default: off)
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -86,6 +87,7 @@ struct dh_engine {
         const uint32_t* mask; int mask_ld;                    // dh_engine_set_token_mask: likewise (beam steps too)
         int ngram; const int32_t* ngram_start;                // dh_engine_set_no_repeat_ngram: likewise (0 / null in a beam step's key)
         dh_stop_args stop; const int32_t* stop_start; int32_t* stop_fin_tok;   // dh_engine_set_stop: likewise (a beam step's key: the set and fin_tok)
+        dh_nucleus_args nuc;                                  // dh_engine_set_nucleus: likewise (off in an arg-max, a verify or a beam step's key)
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
@@ -96,7 +98,7 @@ struct dh_engine {
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
                    logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
                    mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && stop == k.stop && stop_start == k.stop_start &&
-                   stop_fin_tok == k.stop_fin_tok && beam_w == k.beam_w &&
+                   stop_fin_tok == k.stop_fin_tok && nuc == k.nuc && beam_w == k.beam_w &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
@@ -989,10 +991,10 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
                                    k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                                   k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s);
+                                   k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s, k.nuc);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
                           e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                          k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s);
+                          k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s, k.nuc);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1116,6 +1118,7 @@ extern "C" int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int6
             break;
         case 4: src = e->dec_ids; avail = (int64_t)e->row_cap * sizeof(int64_t); break;
         case 5: src = seq_meta(e).kv; avail = (int64_t)e->max_batch * sizeof(int32_t); break;
+        case 8: src = e->logits; avail = (int64_t)e->row_cap * e->d.vocab * 2; break;       // the last single-token step's rows
         default: DH_CHECK(false, "dh_engine_read: unknown selector %d", what);
     }
     DH_CHECK(n_bytes <= avail, "dh_engine_read: %lld bytes requested, %lld available", (long long)n_bytes, (long long)avail);
@@ -1209,7 +1212,8 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
+                              top_k == 1 ? dh_nucleus_args{} : e->nuc};     // the arg-max takes neither parameter: its step is the plain one
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1225,7 +1229,8 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
+                              top_k == 1 ? dh_nucleus_args{} : e->nuc};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1273,7 +1278,7 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
                               limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr, dh_nucleus_args{}};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1344,7 +1349,7 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_LAUNCH_CHECK();
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
                         prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                        e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, W, *st};
+                        e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, dh_nucleus_args{}, W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1391,6 +1396,14 @@ extern "C" int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const 
     e->stop = sa;
     e->stop_start = sa.n_seqs ? start : nullptr;
     e->stop_fin_tok = sa.set ? beam_fin_tok : nullptr;
+    return 0;
+}
+
+extern "C" int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p) {
+    DH_CHECK(e, "dh_engine_set_nucleus: null engine");
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_engine_set_nucleus", top_p, min_p, nuc)) return rc;
+    e->nuc = nuc;
     return 0;
 }
 

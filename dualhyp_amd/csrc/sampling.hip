@@ -1,5 +1,5 @@
 // The tail of the decode loop (generate/base.py:62-80) fused into one kernel per step:
-// temperature -> top-k crop -> softmax -> draw -> append token -> EOS flag.  One 1024-thread
+// temperature -> top-k crop (-> nucleus / min-p crop, where asked for) -> softmax -> draw -> append token -> EOS flag.  One 1024-thread
 // block per sequence; nothing returns to the host.
 #include "common.h"
 
@@ -32,9 +32,21 @@ __device__ __forceinline__ uint32_t mask_byte(const uint32_t* __restrict__ mrow,
 // returns it.  The draw is keyed by (seed, step, seq).
 // MASK: every logit that feeds the pick goes through the sequence's mask row `mrow` first and is bf16 -inf where the token is not
 // allowed, so the pick is the unmasked pick on a copy of the row with -inf in those columns.  Off: `mrow` is not read.
+// nuc ("Nucleus and min-p" of the header; launch-uniform, off: the sampled branch runs what it always ran): the crop's threshold key is
+// raised to that of the kept set K0 n nucleus(K0) n min_p before the sums.  The scheme:
+//   m is the maximum of the scaled row (top_k keeps it), w_i = __expf(l_i - m), the term the CDF walk itself adds.
+//   min_p  an entry passes iff fl32(l_i - m) >= lmin; the smallest key that passes is a block-wide integer minimum.
+//   top_p  masses are fixed-point integers q_i = (uint64)(w_i * 2^40), added with 64-bit integer LDS atomics: exact in any order, and
+//          131072 entries of at most 2^40 fit.  Pass 0 histograms the entries of K0 into 256 bins by the high byte of bf16_key, thread 0
+//          walks the bins from the top until the mass above a bin plus the bin reaches P = clamp((uint64)(top_p * T_int), 1, T_int),
+//          T_int the sum of all bins; pass 1 repeats it on the low byte inside that bin.  The value found is the lowest v with
+//          A(v) < P, A the mass strictly above v: ties share a key, so they stay together, and the clamp makes a crossing exist.
+// No floating-point sum feeds the threshold, and every entry goes through scaled(i): the kept set is a function of the row's bytes,
+// vocab and the parameters, wherever the row lies.
 template <bool MASK>
 __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k,
-                                          uint64_t seed, int step, int seq, const uint32_t* __restrict__ mrow) {
+                                          uint64_t seed, int step, int seq, const uint32_t* __restrict__ mrow,
+                                          const dh_nucleus_args nuc = dh_nucleus_args{}) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float s_f[NT / 64];
     __shared__ int s_i[NT / 64];
@@ -143,6 +155,65 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
         mx = s_f[0];
         for (int w = 1; w < NT / 64; ++w) mx = fmaxf(mx, s_f[w]);
         __syncthreads();
+        if (nuc.on()) {                                    // the same for every thread of the launch
+            __shared__ unsigned long long s_mass[256];
+            __shared__ unsigned long long s_need;
+            __shared__ unsigned s_minkey;
+            uint32_t nuc_key = 0;
+            if (nuc.top_p < 1.f) {
+                uint32_t prefix = 0;
+                unsigned long long need = 0;
+                for (int pass = 0; pass < 2; ++pass) {
+                    for (int i = tid; i < 256; i += NT) s_mass[i] = 0ull;
+                    __syncthreads();
+                    for (int i = tid; i < vocab; i += NT) {
+                        const bf16_t v = scaled(i);
+                        const uint32_t k = bf16_key(v);
+                        if (k < thr_key) continue;
+                        if (pass == 1 && (k >> 8) != prefix) continue;
+                        const unsigned long long q = (unsigned long long)(__expf(bf2f(v) - mx) * 1099511627776.0f);   // 2^40
+                        if (q) atomicAdd(&s_mass[pass == 0 ? k >> 8 : k & 255], q);
+                    }
+                    __syncthreads();
+                    if (tid == 0) {
+                        if (pass == 0) {
+                            unsigned long long tot = 0;
+                            for (int b = 0; b < 256; ++b) tot += s_mass[b];
+                            need = (unsigned long long)((double)nuc.top_p * (double)tot);
+                            need = need < 1ull ? 1ull : need > tot ? tot : need;
+                        }
+                        int b = 255;
+                        unsigned long long acc = 0;
+                        for (; b > 0; --b) {
+                            if (acc + s_mass[b] >= need) break;
+                            acc += s_mass[b];
+                        }
+                        s_sel[0] = b;
+                        s_need = need - acc;                   // the mass still wanted inside bin b
+                    }
+                    __syncthreads();
+                    if (pass == 0) prefix = s_sel[0]; else nuc_key = (prefix << 8) | s_sel[0];
+                    need = s_need;
+                    __syncthreads();
+                }
+            }
+            if (nuc.min_p_on) {
+                if (tid == 0) s_minkey = 0xFFFFFFFFu;
+                __syncthreads();
+                uint32_t lowest = 0xFFFFFFFFu;
+                for (int i = tid; i < vocab; i += NT) {
+                    const bf16_t v = scaled(i);
+                    if (bf2f(v) - mx >= nuc.lmin) lowest = min(lowest, bf16_key(v));
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) lowest = min(lowest, (uint32_t)__shfl_xor((int)lowest, o, 64));
+                if (lane == 0) atomicMin(&s_minkey, lowest);
+                __syncthreads();
+                nuc_key = max(nuc_key, s_minkey);
+                __syncthreads();
+            }
+            thr_key = max(thr_key, nuc_key);
+        }
         // contiguous slab per thread so the CDF is in index order
         const int per = (vocab + NT - 1) / NT;
         const int lo = tid * per, hi = min(vocab, lo + per);
@@ -254,9 +325,10 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
 // the mask disallows or the history bans.  The kernels' BAN = false instantiations call pick_token<MASK> as they always did.
 template <bool MASK>
 __device__ __forceinline__ int pick_token_banned(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k, uint64_t seed,
-                                             int step, int seq, const uint32_t* __restrict__ mrow, const int64_t* g, int m, int ngram) {
+                                             int step, int seq, const uint32_t* __restrict__ mrow, const int64_t* g, int m, int ngram,
+                                             const dh_nucleus_args nuc = dh_nucleus_args{}) {
     const uint32_t* row = ban_row<MASK>(g, m, ngram, vocab, mrow);
-    return pick_token<true>(lg, vocab, temperature, top_k, seed, step, seq, row);
+    return pick_token<true>(lg, vocab, temperature, top_k, seed, step, seq, row, nuc);
 }
 
 // log softmax(lg)[token] of the RAW row (temperature 1, no crop: the model's distribution, not the sampler's) by the whole block;
@@ -500,7 +572,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
                                                     float* __restrict__ logprobs, int top_n,
                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                     const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                    const int32_t* __restrict__ start, dh_stop_args sa) {
+                                                    const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
@@ -508,10 +580,10 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
     if constexpr (BAN) {                                // the history is what lies behind the prompt
         const int p0 = start[seq];
         choice = pick_token_banned<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
-                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram);
+                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram, nuc);
     } else {
         choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
-                                  MASK ? mask + (size_t)seq * mask_ld : nullptr);
+                                  MASK ? mask + (size_t)seq * mask_ld : nullptr, nuc);
     }
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
@@ -546,7 +618,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                         const int32_t* __restrict__ start, dh_stop_args sa) {
+                                                         const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
@@ -555,10 +627,10 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
     if constexpr (BAN) {
         const int p0 = start ? start[u] : limit[u] - max_new;           // the prompt length, which limit[u] - max_new is
         choice = pick_token_banned<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
-                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram);
+                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc);
     } else {
         choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
-                                  MASK ? mask + (size_t)u * mask_ld : nullptr);     // the sequence's mask row, not the logits row's
+                                  MASK ? mask + (size_t)u * mask_ld : nullptr, nuc);     // the sequence's mask row, not the logits row's
     }
     const int32_t* ti = nullptr;
     const float* tl = nullptr;
@@ -708,7 +780,7 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
                    const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
-                   int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream) {
+                   int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream, const dh_nucleus_args& nuc) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
     DH_CHECK(sa.n_seqs == 0 || start, "dh_sample_bf16: stop sequences need `start`, the prompt lengths");
     DH_CHECK_TOP("dh_sample_bf16");
@@ -720,7 +792,7 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
     // logprobs null: the kernel without the log-probability pass (the code it always was)
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp, mask, mask_ld, ngram, start, sa);
+                       top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -767,6 +839,19 @@ extern "C" int dh_sample_bf16_stop(const dh_bf16* logits, int vocab, int64_t* to
                           nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream);
 }
 
+extern "C" int dh_sample_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                      int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                      int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                      const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                      float top_p, float min_p) {
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_sample_bf16_nucleus", top_p, min_p, nuc)) return rc;
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_bf16_nucleus", stop, start != nullptr, sa)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc);
+}
+
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                               int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                               int step, void* stream) {
@@ -777,7 +862,8 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream) {
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream,
+                        const dh_nucleus_args& nuc) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
     DH_CHECK_TOP("dh_sample_rows_bf16");
     DH_CHECK_MASK("dh_sample_rows_bf16");
@@ -788,7 +874,7 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -839,6 +925,20 @@ extern "C" int dh_sample_rows_bf16_stop(const dh_bf16* logits, int vocab, int64_
     if (int rc = dh_stop_pack("dh_sample_rows_bf16_stop", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
                                eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream);
+}
+
+extern "C" int dh_sample_rows_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                           int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                           int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                           float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                           int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
+                                           float min_p) {
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_sample_rows_bf16_nucleus", top_p, min_p, nuc)) return rc;
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_rows_bf16_nucleus", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,

@@ -15,6 +15,7 @@ import torch
 from . import beam as _beam
 from . import constrain as _constrain
 from . import ngram as _ngram
+from . import nucleus as _nucleus
 from . import ops
 from . import stop as _stop
 from .gpt import GPT
@@ -90,7 +91,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
                    share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
                    return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
-                   stop=None):
+                   stop=None, top_p: Optional[float] = None, min_p: Optional[float] = None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -150,7 +151,17 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     sampling kernels (the prefill's first pick and every captured decode or verify step) and never changes a pick: tokens,
     log-probabilities and alternatives are the unstopped call's up to and including that token, bit for bit, with every sampler.  What
     it saves are steps: the EOS_CHECK_EVERY loop runs whenever an EOS or a stop can end a sequence early.  It goes with speculate,
-    share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram and fp8.  None (the default): the call it always was."""
+    share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram and fp8.  None (the default): the call it always was.
+
+    top_p (in (0, 1]) and min_p (in [0, 1]; include/dualhyp_hip.h, "Nucleus and min-p"): a sampled call (top_k != 1) draws from the
+    entries top_k keeps, cropped to their nucleus — values from the best down until the mass above a value reaches top_p of the kept
+    mass, the crossing value kept whole, ties together — and to the entries whose scaled logit is within log(min_p) of the best.  The
+    crop is taken on the row the sampler uses, after temperature, token_mask and no_repeat_ngram, inside the sampling kernels: the
+    prefill's first pick and every captured decode step, with no launch or read-back of its own.  Log-probabilities and alternatives
+    stay the raw row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop and fp8; the
+    arg-max (top_k = 1, and with it speculate) takes neither.  None, 1.0 and 0.0 (the defaults) are off: the call it always was."""
+    top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
+    nuc = top_p < 1.0 or min_p > 0.0
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
@@ -210,7 +221,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
-               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop)
+               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p)
     if ev:
         ev[1].record()
     if lp_buf is not None:
@@ -223,6 +234,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         eng.set_no_repeat_ngram(ngram, start)   # likewise
     if stop is not None:
         eng.set_stop(stop, start)               # likewise
+    if nuc:
+        eng.set_nucleus(top_p, min_p)           # likewise
     try:
         steps_run = 0
         if max_new_tokens > 1:
@@ -261,6 +274,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             eng.set_no_repeat_ngram(0)
         if stop is not None:
             eng.set_stop(None)
+        if nuc:
+            eng.set_nucleus(None, None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -428,7 +443,8 @@ class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
-                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None) -> None:
+                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None,
+                 top_p: float = 1.0, min_p: float = 0.0) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -450,6 +466,7 @@ class _StreamBackend:
         # generate_batch's no_repeat_ngram and the sequences' prompt lengths (the dummy sequence's one token is all prompt)
         self.ngram = ngram
         self.stop = stop                     # generate_batch's stop; its sequences count from the same prompt lengths
+        self.top_p, self.min_p = top_p, min_p    # generate_batch's top_p / min_p (the decode steps get them through the engine)
         self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram or (stop is not None and stop.sequences) else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
@@ -473,7 +490,7 @@ class _StreamBackend:
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
                         self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
-                        start=self.start, stop=self.stop, **self.kw)
+                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **self.kw)
         if end:
             end.record()
 
@@ -498,7 +515,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 1337, max_rows: int = 640,
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
-                    top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False):
+                    top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False,
+                    top_p: Optional[float] = None, min_p: Optional[float] = None):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -523,8 +541,12 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 
     stop: as in generate_batch — a stopped sequence (done = 3) leaves its row at the next check like one that met its EOS, and the
     next prompt takes its KV slot.  return_state: the result gains a last element, the dict of the call's device state (tokens,
-    length, done — one row per prompt — and logprobs, top_ids, top_logprobs where asked for), as generate_batch's."""
+    length, done — one row per prompt — and logprobs, top_ids, top_logprobs where asked for), as generate_batch's.
+
+    top_p, min_p: as in generate_batch — a row's kept set is a function of the row alone, so the ids do not depend on the schedule."""
     from .schedule import StreamScheduler
+    top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
+    nuc = top_p < 1.0 or min_p > 0.0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     ngram = _ngram.check_ngram(no_repeat_ngram)
     if ngram:
@@ -548,7 +570,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop)
+                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -564,6 +586,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         eng.set_no_repeat_ngram(ngram, be.start)
     if stop is not None:
         eng.set_stop(stop, be.start)
+    if nuc:
+        eng.set_nucleus(top_p, min_p)
     try:
         sched.run(be)
     finally:
@@ -577,6 +601,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             eng.set_no_repeat_ngram(0)
         if stop is not None:
             eng.set_stop(None)
+        if nuc:
+            eng.set_nucleus(None, None)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
@@ -613,11 +639,13 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 @torch.inference_mode()
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
-             top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None):
+             top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, top_p: Optional[float] = None,
+             min_p: Optional[float] = None):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
-    generate_batch's.  stop: generate_batch's."""
+    generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's."""
+    _nucleus.check_nucleus(top_p, min_p)
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
     assert max_returned_tokens > T
@@ -625,7 +653,7 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
                          speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
-                         no_repeat_ngram=no_repeat_ngram, stop=stop)
+                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

@@ -533,6 +533,13 @@ class _Engine:
                                                None if stop is None or beam_fin_tok is None else beam_fin_tok.data_ptr()))
         self._stop = (stop, start, beam_fin_tok) if stop is not None else None
 
+    def set_nucleus(self, top_p: Optional[float] = None, min_p: Optional[float] = None) -> None:
+        """top_p and min_p (include/dualhyp_hip.h, "Nucleus and min-p") for later decode / decode_rows calls with top_k != 1; None, 1.0
+        and 0.0 turn them off (dh_engine_set_nucleus).  Both are part of a captured step's key."""
+        from .nucleus import check_nucleus
+        top_p, min_p = check_nucleus(top_p, min_p)
+        _lib.check(self.lib.dh_engine_set_nucleus(self.handle, top_p, min_p))
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"
@@ -560,6 +567,14 @@ class _Engine:
             _lib.check(self.lib.dh_engine_read(self.handle, 4, 0, ids.data_ptr(), ids.numel() * 8, st))
             _lib.check(self.lib.dh_engine_read(self.handle, 5, 0, kv.data_ptr(), kv.numel() * 4, st))
         return ids[:, 1:].contiguous(), kv
+
+    def read_step_logits(self, n_rows: int) -> torch.Tensor:
+        """The bf16 logits rows [n_rows, vocab] of the last single-token step (test hook, dh_engine_read what 8)."""
+        out = torch.empty((n_rows, self.vocab), dtype=torch.bfloat16, device=self.device)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(self.lib.dh_engine_read(self.handle, 8, 0, out.data_ptr(), out.numel() * 2, st))
+        return out
 
     def set_rsqrt_emulation(self, vec_width: int, whole_call: bool) -> None:
         _lib.check(self.lib.dh_engine_set_cpu_rsqrt_emulation(self.handle, int(vec_width), int(whole_call)))

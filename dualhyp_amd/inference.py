@@ -73,7 +73,9 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     true attribute `stop` (--stop / --stop_file: it decodes under a stop specification) gives every record 'finish_reason', "eos",
     "length" or "stop": it leaves them, one per prompt of the call it has just answered, in its attribute `finish_reasons` (from
     the call's `done` flags, dualhyp_amd.stop.finish_reasons); with beams the best hypothesis' own 'finish_reason' is taken and every
-    entry of 'beams' carries its own.  Returns corpus metrics on every rank and predictions on
+    entry of 'beams' carries its own.  A generate_fn with an attribute `sampling` (--temperature / --top_k / --top_p / --min_p: a dict
+    {temperature, top_k, top_p, min_p, seed}, set when any of them is not the default) gives every record 'sampling', a copy of it.
+    Returns corpus metrics on every rank and predictions on
     rank 0."""
     mine = shard_indices(len(examples), rank, world)
     preds: Dict[int, Dict[str, str]] = {}
@@ -108,6 +110,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["ngram_bans"] = len(ban_positions(o.reshape(-1)[p.numel():].tolist(), int(generate_fn.no_repeat_ngram)))
             if stopping:
                 preds[i]["finish_reason"] = reasons[k]
+            if getattr(generate_fn, "sampling", None):
+                preds[i]["sampling"] = dict(generate_fn.sampling)
             if beams is not None:
                 text = decode(p)
                 preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
@@ -166,6 +170,20 @@ def stop_from_args(args, tokenizer, vocab: int, device=None):
         seqs += f_seqs
     spec = compile_stop(ids, seqs, vocab, device) if ids or seqs else None
     return spec if spec else None
+
+
+SAMPLING_DEFAULTS = dict(temperature=0.2, top_k=1, top_p=1.0, min_p=0.0)      # inference/ger.py:71-72 decodes greedily at 0.2
+
+
+def sampling_from_args(args) -> Optional[Dict[str, Any]]:
+    """{temperature, top_k, top_p, min_p, seed} of --temperature / --top_k / --top_p / --min_p when any of them is not the default,
+    None for the default run (whose calls and records are the ones they always were)."""
+    got = {k: getattr(args, k, v) for k, v in SAMPLING_DEFAULTS.items()}
+    got = dict(temperature=float(got["temperature"]), top_k=int(got["top_k"]), top_p=float(got["top_p"]), min_p=float(got["min_p"]))
+    if got == SAMPLING_DEFAULTS:
+        return None
+    got["seed"] = int(getattr(args, "seed", 1337))
+    return got
 
 
 def add_lora_arguments(parser) -> None:
@@ -315,6 +333,11 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
     stop = stop_from_args(args, tokenizer, model.config.padded_vocab_size, model.transformer.wte.weight.device)
     skw = dict(stop=stop, return_state=True) if stop is not None else {}       # the reasons are read from the state's done flags
+    sampling = sampling_from_args(args)
+    # the default run passes what it always passed: temperature 0.2, top_k 1 and the functions' own seed
+    samp = dict(temperature=0.2, top_k=1) if sampling is None else dict(
+        temperature=sampling["temperature"], top_k=sampling["top_k"] or None, top_p=sampling["top_p"], min_p=sampling["min_p"],
+        seed=sampling["seed"])
 
     def gen(prompts):
         dev = model.transformer.wte.weight.device
@@ -327,15 +350,15 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
                                      no_repeat_ngram=ngram, stop=stop)
             return {"beams": hyps, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
-            outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
+            outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
                                    share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask,
-                                   no_repeat_ngram=ngram, **skw)
+                                   no_repeat_ngram=ngram, **samp, **skw)
         else:
-            outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, temperature=0.2, top_k=1, eos_id=eos,
+            outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
                                   return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram,
-                                  **skw)
+                                  **samp, **skw)
         if stop is not None:
             from .stop import finish_reasons
             gen.finish_reasons = finish_reasons(outs[-1]["done"])
@@ -349,6 +372,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.constrained = constrain
     gen.no_repeat_ngram = ngram
     gen.stop = stop is not None
+    gen.sampling = sampling
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -450,6 +474,18 @@ def build_parser():
                    help="a stop specification, one entry per line of token ids separated by blanks: a line of one id adds to the stop "
                         "set, a line of 2..8 ids is a stop sequence (at most 8 of them); blank lines and # comments are skipped; adds to "
                         "--stop; stop sequences do not go with --num_beams")
+    p.add_argument("--temperature", type=float, default=0.2,
+                   help="the sampler's temperature (inference/ger.py:71 decodes at 0.2); with the default --top_k 1 it changes no pick")
+    p.add_argument("--top_k", type=int, default=1, metavar="K",
+                   help="1: greedy arg-max, the path it always was; K > 1: sample among the K best tokens; 0: no crop by count")
+    p.add_argument("--top_p", type=float, default=1.0, metavar="P",
+                   help="P in (0, 1], with --top_k other than 1: nucleus sampling — the draw is made from the best tokens down to the one "
+                        "whose mass crosses P of what --top_k keeps, ties kept together; the crop is taken inside the sampling kernels, "
+                        "under both schedules and with every flag that goes with sampling.  Default 1.0: off")
+    p.add_argument("--min_p", type=float, default=0.0, metavar="P",
+                   help="P in [0, 1], with --top_k other than 1: only tokens whose probability is at least P times the best token's are "
+                        "drawn from.  Default 0.0: off.  A run with any of --temperature, --top_k, --top_p, --min_p off its default "
+                        "gives every record sampling: {temperature, top_k, top_p, min_p, seed}")
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
@@ -501,6 +537,23 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         args.logprobs = True
     if not 0 <= args.speculate <= 7:
         p.error(f"--speculate {args.speculate}: D is 0 (off) or 1..7")
+    from .nucleus import check_min_p, check_top_p
+    for check, flag, value in ((check_top_p, "--top_p", args.top_p), (check_min_p, "--min_p", args.min_p)):
+        try:
+            check(value)
+        except ValueError as e:
+            p.error(f"{flag}: {e}")
+    if not args.temperature > 0.0:
+        p.error(f"--temperature {args.temperature}: the temperature is positive")
+    if args.top_k < 0:
+        p.error(f"--top_k {args.top_k}: K is 0 (no crop), 1 (greedy) or more")
+    if args.top_k != 1:
+        if args.speculate:          # speculate.check_arguments refuses it too; here nothing has been loaded yet
+            p.error(f"--speculate {args.speculate} does not go with --top_k {args.top_k}: a verify step confirms drafts against the greedy "
+                    "arg-max, so it runs with --top_k 1 only")
+        if args.num_beams > 1:
+            p.error(f"--num_beams {args.num_beams} does not go with --top_k {args.top_k}: beam search ranks hypotheses by score and "
+                    "draws nothing")
     return args
 
 

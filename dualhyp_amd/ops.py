@@ -415,7 +415,8 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
            step: int = 0, logprobs: Optional[torch.Tensor] = None,
            top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
-           no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None) -> None:
+           no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
+           min_p: Optional[float] = None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
@@ -424,7 +425,11 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     start: int32 [n_seq] prompt lengths; "No-repeat n-grams" of the header): a token that would complete an n-gram already in
     tokens[u, start[u]:length[u]] is not picked, with or without a mask (dh_sample_bf16_ngram).  stop (a compiled specification,
     dualhyp_amd.stop.compile_stop; "Stop conditions" of the header): a sequence whose appended token is in the stop set, or completes
-    a stop sequence within tokens[u, start[u]:], gets done = 3; stop sequences need start (dh_sample_bf16_stop)."""
+    a stop sequence within tokens[u, start[u]:], gets done = 3; stop sequences need start (dh_sample_bf16_stop).  top_p (in (0, 1]) and
+    min_p (in [0, 1]; "Nucleus and min-p" of the header): the draw is made from the entries top_k keeps, cropped to their nucleus and to
+    those within min_p of the best; None, 1.0 and 0.0 are off, and top_k = 1 takes neither (dh_sample_bf16_nucleus)."""
+    from .nucleus import check_nucleus
+    top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_seq, vocab = logits.shape
@@ -442,7 +447,9 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
             0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
             _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if st_ptr is not None:
+    if top_p < 1.0 or min_p > 0.0:
+        check(_lib.load().dh_sample_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
+    elif st_ptr is not None:
         check(_lib.load().dh_sample_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
     elif ngram:
         check(_lib.load().dh_sample_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
@@ -456,12 +463,15 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
                 row_seq: torch.Tensor, max_new_tokens: int, *, temperature: float = 1.0, top_k: Optional[int] = None,
                 eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None,
                 top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
-                no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None) -> None:
+                no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
+                min_p: Optional[float] = None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
     in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
     (dh_sample_rows_bf16_mask).  no_repeat_ngram, start: as in sample(), one entry of start per SEQUENCE; start None is
     limit - max_new_tokens (dh_sample_rows_bf16_ngram).  stop: as in sample(); start None is limit - max_new_tokens here too
-    (dh_sample_rows_bf16_stop)."""
+    (dh_sample_rows_bf16_stop).  top_p, min_p: as in sample() (dh_sample_rows_bf16_nucleus)."""
+    from .nucleus import check_nucleus
+    top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
     logits = _dev(logits, name="logits")
     n_rows, vocab = logits.shape
@@ -479,7 +489,9 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
             k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if st_ptr is not None:
+    if top_p < 1.0 or min_p > 0.0:
+        check(_lib.load().dh_sample_rows_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
+    elif st_ptr is not None:
         check(_lib.load().dh_sample_rows_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
     elif ngram:
         check(_lib.load().dh_sample_rows_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))

@@ -32,7 +32,8 @@ typedef uint16_t dh_bf16;
  * dh_engine_decode_beam (beam search); dh_sample_bf16_mask, dh_sample_rows_bf16_mask, dh_token_top_logprobs_bf16_mask,
  * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks); dh_sample_bf16_ngram, dh_sample_rows_bf16_ngram and
  * dh_engine_set_no_repeat_ngram (no-repeat n-grams); dh_sample_bf16_stop, dh_sample_rows_bf16_stop, dh_beam_select_bf16_stop and
- * dh_engine_set_stop (stop conditions). */
+ * dh_engine_set_stop (stop conditions); dh_sample_bf16_nucleus, dh_sample_rows_bf16_nucleus and dh_engine_set_nucleus (nucleus
+ * and min-p sampling). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -591,6 +592,47 @@ int dh_beam_select_bf16_stop(const dh_bf16* logits, int vocab, int n_utt, int ro
                              int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp,
                              const uint32_t* mask, int mask_ld, const dh_stop_spec* stop, int32_t* fin_tok, void* stream);
 
+/* Nucleus and min-p (the "top_p" and "min_p" of the serving interfaces; the sampler of generate/base.py:62-80 has temperature and top_k
+ * only).  ONE definition for every entry below.
+ * The row is the one the sampler already draws from: l_i = bf16(logit_i / temperature), bf16 -inf where the token mask disallows or the
+ * n-gram ban bans; -0 == +0; m = max l; w_i = exp(l_i - m).  K0 is the set top_k keeps: ties at the k-th value are all kept, top_k = 0
+ * keeps all.
+ *   min_p in [0, 1], 0 = off: i is kept iff fl32(l_i - m) >= lmin, lmin = (float)log((double)min_p) computed once on the host inside the
+ *     C entry; the subtraction is one fp32 IEEE subtraction and the comparison is >=, so min_p = 1 keeps exactly the entries equal to
+ *     the maximum.  The test is relative to the best token: it depends on no normalisation.
+ *   top_p in (0, 1], 1 = off; the value used is the fp32 one passed.  For a value v among the entries of K0, A(v) is the mass (sum of w)
+ *     of the entries of K0 strictly above v and T the mass of K0: v is kept iff A(v) < top_p * T.  So the best value is always kept, and
+ *     the value whose mass crosses top_p is kept WHOLE: ties stay together.  This differs from the text-generation stacks, which sort
+ *     and cut by position, so that of two equal logits at the crossing one may stay and one may go.
+ *   Kept set = K0 n nucleus of K0 n min_p.  Every part is a threshold on the value, so the kept set is again one threshold: the
+ *     existing crop and the existing CDF walk (ascending index, slab per thread, the same fp32 sums) draw from it.
+ *   Equivalence: for the same (seed, step, seq) the pick equals, bit for bit, what dh_sample_bf16_mask picks with top_k off under a mask
+ *     that allows exactly the kept set (a masked entry adds 0.f to the same sums).
+ *   top_k == 1, the arg-max: both parameters are accepted and do nothing (the arg-max is always kept).  Verify steps and beam search
+ *     take neither.  Log-probabilities and alternatives stay the raw row's, as under a mask.
+ *   Determinism: a row's kept set is a function of the row's bytes, vocab and the parameters; not of the row index, the row count, the
+ *     alignment (the 16-byte and the scalar paths agree) or timing.  The kernel adds the masses as fixed-point integers
+ *     (uint64)(w_i * 2^40) with integer atomics, exact in any order; no floating-point atomic feeds the threshold (sampling.hip).
+ *   The device's exp is not the host's to the last bit, so the kept set is decided only where no A(v) / T lies within a band of
+ *     2^-18 + 2^-22 of top_p (tests/nucleus_reference.py derives it); inside the band either neighbour is a correct answer.  NaN rows and
+ *     rows whose allowed logits are all -inf stay outside the definition, as they are for the sampler; they still give an id in
+ *     [0, vocab). */
+
+/* dh_sample_bf16_stop / dh_sample_rows_bf16_stop with top_p and min_p; mask, ngram and stop stay nullable / 0, so with top_p = 1 and
+ * min_p = 0 each is the entry it extends.  Refused without a launch, with the value in the message: top_p outside (0, 1] or NaN, min_p
+ * outside [0, 1] or NaN. */
+int dh_sample_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                           int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                           uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                           const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                           float top_p, float min_p);
+int dh_sample_rows_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                float top_p, float min_p);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -874,6 +916,11 @@ int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int32_t* start)
  * (the device arrays, which the caller keeps alive while set); it is part of the captured step's key, beside the mask and (ngram,
  * start): with it unset a decode call runs the graphs it always ran. */
 int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const int32_t* start, int32_t* beam_fin_tok);
+/* top_p and min_p (see "Nucleus and min-p" above; 1 and 0 = off, the default) for later dh_engine_decode and dh_engine_decode_rows
+ * calls with top_k != 1.  Both values are part of the captured step's key, beside the mask, (ngram, start) and the stop specification:
+ * with them unset, or with top_k == 1, a decode call runs the graphs it always ran.  Verify and beam steps take neither.  Refused like
+ * dh_sample_bf16_nucleus. */
+int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
@@ -886,7 +933,8 @@ int dh_engine_graph_count(const dh_engine* e, int n_draft);
  *   what 4: int64 ids of the last step's rows (a verify step: row i * S + j = last token, then the drafts)
  *   what 5: int32 kv_len of the last step's sequences (a verify step: the lengths its drafts were proposed from)
  *   what 6 / 7: an fp8-KV engine's K / V^T cache of `layer` EXPANDED to bf16 (every slot, every position), in the form of
- *               what 1 / 2; overwrites the engine's one-layer scratch.  what 1 / 2 are refused by an fp8-KV engine. */
+ *               what 1 / 2; overwrites the engine's one-layer scratch.  what 1 / 2 are refused by an fp8-KV engine.
+ *   what 8: the bf16 logits rows of the last single-token step, [n_rows, vocab] */
 int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int64_t n_bytes, void* stream);
 /* HIP-event timing of the dominant kernels inside the last forward/decode call (bench.py
  * roofline): returns accumulated milliseconds and launch count for kernel class `which`
