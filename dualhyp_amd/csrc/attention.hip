@@ -20,17 +20,55 @@
 // to bf16 for the second product; O/l is rounded to bf16 once (as the reference's fused CPU/GPU
 // SDPA kernels do).
 #include "common.h"
+#include "tuning.h"
+
+#ifdef DH_PREFILL_STAMPS   // diagnostic build only (tools/probe_attn_prefill.py): 100 MHz timestamps of lane 0 of wave 0 of each block
+// per block 40 slots: 0 entry, 1 metadata read, 2 Q fragments in registers, 3 first stage landed (barrier 0), then for key step
+// kt < 8 at 4 + 4 kt: S MFMAs issued, softmax done, last PV issued, barrier passed; 36 last store issued; 37 the wave's HW_ID
+// register (bits 8-15: CU, shader array, shader engine), 38 its XCC_ID: which CU the block ran on; 39 its query tile.  Vector
+// stores only.
+constexpr int PF_STAMP_BLOCKS = 16384, PF_STAMP_SLOTS = 40, PF_STAMP_STEPS = 8;
+__device__ unsigned long long g_prefill_stamps[PF_STAMP_BLOCKS * PF_STAMP_SLOTS];
+#define PF_STAMP(i)                                                                                                        \
+    do {                                                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                                                 \
+        if (threadIdx.x == 0 && pf_blk < PF_STAMP_BLOCKS) g_prefill_stamps[pf_blk * PF_STAMP_SLOTS + (i)] = __builtin_amdgcn_s_memrealtime(); \
+        __builtin_amdgcn_sched_barrier(0);                                                                                 \
+    } while (0)
+#define PF_STAMP_STEP(kt, j) do { if ((kt) < PF_STAMP_STEPS) PF_STAMP(4 + 4 * (kt) + (j)); } while (0)
+#define PF_HAVE(...) asm volatile("" ::__VA_ARGS__)     // the stamp that follows is taken once these values have arrived
+extern "C" int dh_debug_prefill_stamps(unsigned long long* out, int clear) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prefill_stamps), sizeof(g_prefill_stamps)) != hipSuccess) return 1;
+    if (!clear) return 0;
+    void* p = nullptr;
+    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_prefill_stamps)) == hipSuccess && hipMemset(p, 0, sizeof(g_prefill_stamps)) == hipSuccess ? 0 : 1;
+}
+#else
+#define PF_STAMP(i)
+#define PF_STAMP_STEP(kt, j)
+#define PF_HAVE(...)
+#endif
+
+// dh_set_tuning 42: waves per block of the prefill attention at head sizes 64 and 128 (0: all q_per_kv heads of a KV group in one
+// block, 2 | 4: that many, a group's K / V^T stages copied by q_per_kv / WPB blocks).  Same bits on every arm.  Read at launch.
+int g_prefill_wpb = 4;
 
 namespace {
 
 // ------------------------------------------------------------------------------------ prefill
-// grid (q tiles of 32, n_groups, n_seq); block = 64 * q_per_kv threads: one wave per query head
-// of the group, all waves share the K / V^T tiles of 64 keys staged in LDS.  Head size 96 (Phi-3.5, multi-head: q_per_kv 1)
-// runs one wave per block: 48 KiB of stages, three blocks per CU by LDS.
+// grid (q tiles of 32, n_groups * (q_per_kv / WPB), n_seq); block = 64 * WPB threads: one wave per query head, the WPB heads
+// head = g * q_per_kv + part * WPB + wave of a block share the K / V^T tiles of 64 keys staged in LDS and meet at one barrier per
+// key step.  WPB 0: all q_per_kv heads of the group in one block (block size from the launch).  Head size 96 (Phi-3.5,
+// multi-head: q_per_kv 1) runs one wave per block: 48 KiB of stages, three blocks per CU by LDS.
 // PS: scale is a power of two (head size 64: 1/8), so it is applied to the Q fragments once — exact in bf16 and in the
 // fp32 products and sums (barring underflow) — instead of to every score: the loop is bound by its softmax VALU work.
-template <int HS, bool PS = false>
-__global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
+// The register budget follows the waves a SIMD can hold by LDS (160 KiB per CU): 32-KiB blocks at head size 64 are five per CU, so
+// four waves per SIMD (128 VGPRs) from four-wave blocks on, as the 16-wave block always had, and two from two-wave blocks; the
+// 64-KiB blocks of head size 128 are two per CU.  Without the second argument a small block is handed registers that cost residency.
+constexpr int pf_waves_per_simd(int hs, int wpb) { return hs == 64 ? (wpb == 2 ? 2 : 4) : (wpb == 2 ? 1 : 2); }
+
+template <int HS, bool PS, int WPB>
+__global__ __launch_bounds__(WPB ? 64 * WPB : HS == 64 ? 1024 : 512, pf_waves_per_simd(HS, WPB)) void attn_prefill_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_cache, const bf16_t* __restrict__ vT_cache,
     const int32_t* __restrict__ seq_slot, const int32_t* __restrict__ q_start, const int32_t* __restrict__ q_len,
     const int32_t* __restrict__ kv_pos0, bf16_t* __restrict__ y, float* __restrict__ lse, int n_head, int n_groups,
@@ -47,42 +85,53 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
     //  of the softmax of step kt (software pipelining inside the wave, bit-identical, one more S tile: 163 VGPRs = one block per
     //  CU 284 us, forced to 128 with 17 spills 277 us).  Round 4: all eight K fragments of a step read in one batch in front of the
     //  eight S MFMAs and the eight V^T fragments in front of the PV MFMAs (sched_barrier; 128 VGPRs, 5 spilled): 200-209 us against 200-203,
-    //  tools/time_attn_prefill.py — the operand reads' LDS latency is not it either.)
+    //  tools/time_attn_prefill.py — the operand reads' LDS latency is not it either.
+    //  Then the block's life was stamped (-DDH_PREFILL_STAMPS, tools/probe_attn_prefill.py, profiles/prefill_attn_stamps_*.txt) and
+    //  the waits turned out to be CUs without work: a CU got one tile index for all its blocks (the comment at qt below), 8 key
+    //  steps per block on some CUs and 1 on others, 57 of 209 us with no block at all on the median CU.  With the tile order rotated
+    //  and folded the launch is 146 us with the group's 8 heads in one block, 139 us with 4 waves per block (WPB, the default: the
+    //  stage is copied twice per group, but the barrier holds 4 waves, not 8, and a CU holds four blocks in four phases) and 168 us
+    //  with 2 (five blocks per CU by LDS, four copies of the stage); tools/ab_attn_prefill.py, spreads 1.0-1.3 us; head size 128 at
+    //  32 x 1536 tokens, 4 heads per group: 866 / 824 / 1277 us.  On top of the 4-wave blocks the packed subtraction and log2 e
+    //  product of round 3 were measured again: 139.2-139.3 us against 139.3, not kept.)
     __shared__ __attribute__((aligned(16))) char sKV[2][4 * TILE_B];
 
-    const int seq = blockIdx.z, g = blockIdx.y;
-    const int qt = gridDim.x - 1 - blockIdx.x;          // longest (latest) tiles first
+    const int q_per_kv = n_head / n_groups;
+    const int parts = WPB ? q_per_kv / WPB : 1;         // blocks per KV group
+    const int seq = blockIdx.z, g = blockIdx.y / parts, part = blockIdx.y % parts;
+    // Query tile of block x: x is rotated by the block's row (y, z) and then folded, so that the first half of the grid's x walks
+    // the tiles down from the last (longest) one and the second half up from tile 0.  Workgroups go to the chip's 8 XCDs round
+    // robin by linear id, and inside an XCD to its 32 CUs round robin again: blocks 256 ids apart share a CU.  With x reversed
+    // only (as it was) and 16 tiles, XCD k got the tiles 15 - k and 7 - k of every 512-token sequence, and a CU got ONE tile
+    // index for all its blocks: 8 key steps per block on some CUs, 1 on others, and the launch lasted as long as the former
+    // (tools/probe_attn_prefill.py).  The fold gives x and x + 8, one XCD's blocks of a row, 9 steps together whatever the
+    // rotation is; the rotation moves on by one with every row and by one more every 16 rows, so a CU sees every tile index.
+    const int row = blockIdx.z * gridDim.y + blockIdx.y;
+    const int xr = (blockIdx.x + row + (row >> 4)) % gridDim.x;
+    const int half = (gridDim.x + 1) >> 1;
+    const int qt = xr < half ? gridDim.x - 1 - xr : xr - half;
+#ifdef DH_PREFILL_STAMPS
+    const int pf_blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+#endif
+    PF_STAMP(0);
+#ifdef DH_PREFILL_STAMPS
+    if (threadIdx.x == 0 && pf_blk < PF_STAMP_BLOCKS) {
+        g_prefill_stamps[pf_blk * PF_STAMP_SLOTS + 37] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_REG_HW_ID, 32 bits
+        g_prefill_stamps[pf_blk * PF_STAMP_SLOTS + 38] = __builtin_amdgcn_s_getreg(20 | (3 << 11));    // HW_REG_XCC_ID, bits 0-3
+        g_prefill_stamps[pf_blk * PF_STAMP_SLOTS + 39] = qt;
+    }
+#endif
     const int qlen = q_len[seq];
     const int q0 = qt * 32;
     if (q0 >= qlen) return;                             // uniform for the whole block
     const int slot = seq_slot[seq], qs = q_start[seq], p0 = kv_pos0[seq] + q0;
-    const int q_per_kv = n_head / n_groups;
-    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform: the stage deal below is scalar code, not a lane loop
+    const int nwaves = WPB ? WPB : (int)(blockDim.x >> 6);
     const int lr = lane & 31, lh = lane >> 5;
-    const int head = g * q_per_kv + wave;
-
-    // Q fragments (B operand): lane holds Q[q0+lr][ks*16 + lh*8 .. +8)
-    bf16x8 qf[KS];
-    {
-        int row = q0 + lr;
-        row = row < qlen ? row : qlen - 1;
-        const bf16_t* qp = q + ((size_t)(qs + row) * n_head + head) * HS + lh * 8;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
-        if (PS) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qf[ks][e] = (short)f2bf(bf2f((bf16_t)qf[ks][e]) * scale);
-        }
-    }
-
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
+    const int head = g * q_per_kv + part * nwaves + wave;
+    PF_HAVE("s"(slot), "s"(qs), "s"(p0));
+    PF_STAMP(1);
 
     const bf16_t* kbase = k_cache + ((size_t)slot * n_groups + g) * s_max * HS;
     const bf16_t* vbase = vT_cache + ((size_t)slot * n_groups + g) * HS * s_max;
@@ -93,18 +142,55 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
 
     // one-KiB groups (64 lanes x 16 B) of a stage dealt over the waves: 2*TILE_B/1024 of K then as many of V^T
     constexpr int GRP = 2 * TILE_B / 1024;
-    const int nwaves = nthr >> 6;
     auto stage = [&](int buf, int kt) __attribute__((always_inline)) {
         const char* gk = reinterpret_cast<const char*>(kbase + (size_t)(2 * kt) * HS * 32);
         const char* gv = reinterpret_cast<const char*>(vbase + (size_t)(2 * kt) * HS * 32);
-        for (int gidx = wave; gidx < 2 * GRP; gidx += nwaves) {
+        auto copy = [&](int gidx) __attribute__((always_inline)) {
             const char* src = gidx < GRP ? gk + gidx * 1024 : gv + (gidx - GRP) * 1024;
             glds16(src + lane * 16, sKV[buf] + gidx * 1024);
+        };
+        if constexpr (WPB != 0) {                       // 2 GRP is 16, 24 or 32: the same number of groups for every wave, no branches
+#pragma unroll
+            for (int i = 0; i < 2 * GRP / (WPB ? WPB : 1); ++i) copy(wave + i * WPB);
+        } else {
+            for (int gidx = wave; gidx < 2 * GRP; gidx += nwaves) copy(gidx);
         }
     };
+    // The prologue is ONE round trip: stage 0 is requested as soon as the slot is known, the Q loads follow it, and both are waited
+    // for once (it was Q loads, wait, scale, stage 0, wait: two dependent trips per block, and a group now runs q_per_kv / WPB blocks).
     stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+    // Q fragments (B operand): lane holds Q[q0+lr][ks*16 + lh*8 .. +8)
+    bf16x8 qf[KS];
+    {
+        int row = q0 + lr;
+        row = row < qlen ? row : qlen - 1;
+        const bf16_t* qp = q + ((size_t)(qs + row) * n_head + head) * HS + lh * 8;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // Q and this wave's share of stage 0
+        // Q's first use is pinned here, where the wait is: left to the first MFMA (hs 96 / 128 do not scale Q) it would sit behind
+        // the DMA of stage 1, and a wait for an ordinary load drains every DMA in front of it
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
+        if (PS) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) qf[ks][e] = (short)f2bf(bf2f((bf16_t)qf[ks][e]) * scale);
+        }
+    }
+    PF_STAMP(2);
+
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
     __syncthreads();
+    PF_STAMP(3);
     for (int kt = 0; kt < n_tiles; ++kt) {
         const int key0 = kt * 64;
         // buffer (kt+1)&1 was last read in iteration kt-1, which ended with a barrier
@@ -124,6 +210,7 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
                 st[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], st[rt], 0, 0, 0);
             }
         }
+        PF_STAMP_STEP(kt, 0);
         // ---- scale, causal mask (only a tile that reaches past the block's first query can hold masked keys), tile max
         if (!PS) {
 #pragma unroll
@@ -166,6 +253,8 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
                 for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
         }
 
+        PF_STAMP_STEP(kt, 1);
+
         // ---- O^T += V^T · P^T
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
@@ -180,8 +269,10 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf.v, o[dt], 0, 0, 0);
                 }
             }
+        PF_STAMP_STEP(kt, 2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next stage has landed
         __syncthreads();                                    // ... everybody's, and this stage's reads are done
+        PF_STAMP_STEP(kt, 3);
     }
 
     // ---- normalise and store y[q][head*HS + d]
@@ -201,6 +292,7 @@ __global__ __launch_bounds__(HS == 64 ? 1024 : 512) void attn_prefill_kernel(
                 *reinterpret_cast<uint2*>(yp + d) = pk;
             }
     }
+    PF_STAMP(36);
 }
 
 // ------------------------------------------------------------------------------------ decode
@@ -459,13 +551,22 @@ extern "C" int dh_attn_prefill_bf16(const dh_bf16* q, const dh_bf16* k_cache, co
     DH_CHECK(s_max % 64 == 0, "dh_attn_prefill_bf16: s_max must be a multiple of 64");
     DH_CHECK(64 * (n_head / n_groups) <= (hs == 64 ? 1024 : 512), "dh_attn_prefill_bf16: too many query heads per group");
     if (n_seq <= 0 || max_q_len <= 0) return 0;
-    dim3 grid(cdiv(max_q_len, 32), n_groups, n_seq), block(64 * (n_head / n_groups));
+    const int q_per_kv = n_head / n_groups;
+    int wpb = g_prefill_wpb;            // waves per block; 0, head size 96 or a count that does not divide the group: the whole group
+    if (hs == 96 || wpb <= 0 || q_per_kv % wpb != 0) wpb = 0;
+    dim3 grid(cdiv(max_q_len, 32), wpb ? n_groups * (q_per_kv / wpb) : n_groups, n_seq), block(64 * (wpb ? wpb : q_per_kv));
     const float scale = 1.0f / sqrtf((float)hs);
     hipStream_t s = (hipStream_t)stream;
     dispatch_hs(hs, [&](auto hs_c) {   // head size 64: scale = 1/8, applied to Q; 1/sqrt(96) is not a power of two: scaled per score, as at 128
         constexpr int HS = decltype(hs_c)::value;
-        hipLaunchKernelGGL((attn_prefill_kernel<HS, HS == 64>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot, q_start, q_len, kv_pos0, y,
-                           lse, n_head, n_groups, s_max, scale);
+        auto launch = [&](auto wpb_c) {
+            hipLaunchKernelGGL((attn_prefill_kernel<HS, HS == 64, decltype(wpb_c)::value>), grid, block, 0, s, q, k_cache, vT_cache, seq_slot,
+                               q_start, q_len, kv_pos0, y, lse, n_head, n_groups, s_max, scale);
+        };
+        if constexpr (HS == 96) launch(std::integral_constant<int, 0>{});
+        else if (wpb == 4) launch(std::integral_constant<int, 4>{});
+        else if (wpb == 2) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 0>{});
     });
     DH_LAUNCH_CHECK();
     return 0;

@@ -112,6 +112,7 @@ const TuningRow TUNING[] = {
     // 32 stays unassigned: it is the key tests/test_capi.py uses as the unknown one
     {40, &g_attn_chain, BOOL, 0, 0, 0},
     {41, &g_finish_hoist_rows, RANGE, -1, NO_MAX, 0},   // -1: the built-in crossover
+    {42, &g_prefill_wpb, ONE_OF, 0, 2, 4},
 };
 
 }  // namespace
