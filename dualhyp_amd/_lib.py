@@ -125,6 +125,7 @@ SIGNATURES = {
     "dh_engine_forward_at": (I, [P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, I, P, P, P]),
     "dh_engine_forward_slots": (I, [P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, I, P, P, P]),
     "dh_engine_copy_prefix": (I, [P, I, C.POINTER(C.c_int32), I, I, P]),
+    "dh_engine_fork_slots": (I, [P, P, I, I, I, P]),
     "dh_engine_set_cpu_rsqrt_emulation": (I, [P, I, I]),
     "dh_engine_decode": (I, [P, P, I, P, P, I, I, F, I, I64, U64, I, P]),
     "dh_engine_decode_rows": (I, [P, P, I, P, P, P, I, I, P, P, I, I, F, I, I64, U64, P]),

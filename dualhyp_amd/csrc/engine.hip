@@ -302,6 +302,33 @@ __global__ __launch_bounds__(256) void kv_copy_prefix_kernel(bf16_t* const* __re
     for (int i = d0; i < d1; ++i) *(gi32x4*)(base + (size_t)dst_slots[i] * slot_elems) = v;
 }
 
+// Fork of every utterance's prompt cache into its decode slots (dh_engine_fork_slots): slot u * n_copies is utterance u's source; the
+// tiles 0 .. ceil(plen[u] / 32) - 1 of its (layer, cache, group) blocks — one contiguous run from the start of each block, tile_units
+// 16-byte units per tile — go to the same place of slots u * n_copies + 1 .. u * n_copies + n_copies - 1.  grid (pieces of 256 units
+// of the longest prompt's tiles, 2 L tables x groups, utterances x shares of the n_copies - 1 destinations): sized by the host's
+// maximum, what there is to do is read from the device — a block whose units lie behind its utterance's last tile returns, and the
+// tile count is clamped to the cache_tiles of a block, as beam_reparent_kernel clamps.  A thread loads its unit once and stores it to
+// each destination of the block's share.  The host has checked n_utt * n_copies against max_batch.
+__global__ __launch_bounds__(256) void kv_fork_slots_kernel(bf16_t* const* __restrict__ cache_tab, const int32_t* __restrict__ plen,
+                                                            int n_copies, int shares, int dst_per_block, int n_groups,
+                                                            size_t block_elems, int tile_units, int cache_tiles) {
+    const int u = blockIdx.z / shares, share = blockIdx.z % shares;
+    const int P = plen[u];
+    if (P < 1) return;
+    int nt = ((P - 1) >> 5) + 1;
+    nt = nt < cache_tiles ? nt : cache_tiles;                         // never past the (slot, group) block
+    const int unit = blockIdx.x * 256 + threadIdx.x;
+    if (unit >= nt * tile_units) return;
+    const int tab = blockIdx.y / n_groups, g = blockIdx.y % n_groups;
+    typedef __attribute__((address_space(1))) bf16_t gbf16_t;
+    typedef __attribute__((address_space(1))) i32x4 gi32x4;
+    const size_t slot_elems = (size_t)n_groups * block_elems;
+    gbf16_t* src = (gbf16_t*)cache_tab[tab] + (size_t)u * n_copies * slot_elems + (size_t)g * block_elems + (size_t)unit * 8;
+    const i32x4 v = *(const gi32x4*)src;
+    const int d0 = 1 + share * dst_per_block, d1 = min(d0 + dst_per_block, n_copies);
+    for (int j = d0; j < d1; ++j) *(gi32x4*)(src + (size_t)j * slot_elems) = v;
+}
+
 // The ids of a beam step (dh_engine_decode_beam): row u * W + w feeds beam_tok[u, t - 1, w] at position prompt_len[u] + t - 1 in slot
 // u * W + w, t = n_steps[u] — the step about to be taken for a live utterance; a finished one's rows write the position behind their
 // last one again, the same bits every time.  t, the prompt length and the position are clamped to the records, the cache and the rope
@@ -1116,6 +1143,12 @@ extern "C" int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int6
             src = (what == 1 ? e->kc : e->vtc) + (size_t)layer * e->cache_layer_elems;
             avail = cache_bytes;
             break;
+        case 9: case 10: case 11: case 12:
+            DH_CHECK(e->kv8, "dh_engine_read: selector %d reads an fp8 KV cache's bytes or exponents; this engine's is bf16", what);
+            DH_CHECK(layer >= 0 && layer < e->d.n_layer, "dh_engine_read: layer %d out of range", layer);
+            if (what <= 10) { src = (what == 9 ? e->k8 : e->v8) + (size_t)layer * e->cache_layer_elems; avail = (int64_t)e->cache_layer_elems; }
+            else { src = (what == 11 ? e->ke : e->ve) + (size_t)layer * e->exp_layer_elems; avail = (int64_t)e->exp_layer_elems; }
+            break;
         case 4: src = e->dec_ids; avail = (int64_t)e->row_cap * sizeof(int64_t); break;
         case 5: src = seq_meta(e).kv; avail = (int64_t)e->max_batch * sizeof(int32_t); break;
         case 8: src = e->logits; avail = (int64_t)e->row_cap * e->d.vocab * 2; break;       // the last single-token step's rows
@@ -1191,6 +1224,39 @@ extern "C" int dh_engine_copy_prefix(dh_engine* e, int src_slot, const int32_t* 
         copy(e->cache_tab + 2 * e->d.n_layer, (size_t)e->s_max / 2, n_pos / 16);
     } else {
         copy(e->cache_tab, (size_t)e->s_max * hs, n_pos * hs / 8);   // n_pos / 32 tiles of hs * 32 elements
+    }
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dh_engine_fork_slots(dh_engine* e, const int32_t* d_prompt_len, int n_utt, int n_copies, int max_len, void* stream) {
+    DH_CHECK(n_copies >= 2 && n_copies <= DH_MAX_SAMPLES,
+             "dh_engine_fork_slots: n_copies=%d: an utterance is forked into 2 .. %d slots, its own included", n_copies, DH_MAX_SAMPLES);
+    DH_CHECK(max_len >= 1, "dh_engine_fork_slots: max_len=%d: the longest prompt has at least one token (it sizes the grid)", max_len);
+    DH_CHECK(e, "dh_engine_fork_slots: null engine");
+    DH_CHECK(engine_is_live(e), "dh_engine_fork_slots: %p is not an engine of dh_engine_create (or was destroyed)", (void*)e);
+    DH_CHECK(d_prompt_len, "dh_engine_fork_slots: null prompt lengths (a device array of n_utt int32)");
+    DH_CHECK(n_utt >= 1 && (int64_t)n_utt * n_copies <= e->max_batch,
+             "dh_engine_fork_slots: %d utterances x %d slots exceed the engine's %d", n_utt, n_copies, e->max_batch);
+    DH_CHECK(max_len <= e->s_max, "dh_engine_fork_slots: max_len=%d exceeds s_max=%d", max_len, e->s_max);
+    hipStream_t s = (hipStream_t)stream;
+    const int hs = e->d.head_size, G = e->d.n_groups, max_tiles = cdiv(max_len, 32), n_dst = n_copies - 1;
+    // one launch per kind of block: `block_elems` 2-byte elements per (slot, group), tiles of tile_units 16-byte units; nothing here
+    // touches the host staging buffer or waits for the stream
+    auto fork = [&](bf16_t* const* tab, size_t block_elems, int tile_units) {
+        const dim3 grid(cdiv(max_tiles * tile_units, 256), 2 * e->d.n_layer * G, n_utt);
+        // short prompts in a shallow model make few pieces: split the destinations until some 2048 blocks are in flight
+        const int shares = std::min<int64_t>(n_dst, std::max<int64_t>(1, 2048 / ((int64_t)grid.x * grid.y * grid.z)));
+        const int dst_per_block = cdiv(n_dst, shares);
+        const int z = cdiv(n_dst, dst_per_block);
+        hipLaunchKernelGGL(kv_fork_slots_kernel, dim3(grid.x, grid.y, n_utt * z), dim3(256), 0, s, tab, d_prompt_len, n_copies, z,
+                           dst_per_block, G, block_elems, tile_units, e->s_max / 32);
+    };
+    if (e->kv8) {   // bytes: tiles of hs * 32 bytes; exponents: 32 bytes per tile (s_max is a multiple of 64)
+        fork(e->cache_tab, (size_t)e->s_max * hs / 2, hs * 2);
+        fork(e->cache_tab + 2 * e->d.n_layer, (size_t)e->s_max / 2, 2);
+    } else {
+        fork(e->cache_tab, (size_t)e->s_max * hs, hs * 4);           // tiles of hs * 32 elements
     }
     DH_LAUNCH_CHECK();
     return 0;

@@ -8,6 +8,7 @@ device state back once at the end instead of once per token (generate/base.py:79
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -83,6 +84,69 @@ def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: S
     eng.forward(prompt[:P].to(eng.device), [P], [0], want_all=False, want_last=False, slot_base=slot)
     if other_slots:
         eng.copy_prefix(slot, list(other_slots), P)
+
+
+@contextlib.contextmanager
+def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float):
+    """What a call hands the engine for its captured decode steps, each only where the call uses it — every one is part of a captured
+    step's key, so without it the call runs the steps it always ran — and takes back behind them: the buffers are the call's."""
+    nuc = top_p < 1.0 or min_p > 0.0
+    if lp_buf is not None:
+        eng.set_logprobs(lp_buf)
+    if top_buf is not None:
+        eng.set_top_logprobs(*top_buf)
+    if mask is not None:
+        eng.set_token_mask(mask)
+    if ngram:
+        eng.set_no_repeat_ngram(ngram, start)
+    if stop is not None:
+        eng.set_stop(stop, start)
+    if nuc:
+        eng.set_nucleus(top_p, min_p)
+    try:
+        yield
+    finally:
+        if lp_buf is not None:
+            eng.set_logprobs(None)
+        if top_buf is not None:
+            eng.set_top_logprobs(None)
+        if mask is not None:
+            eng.set_token_mask(None)
+        if ngram:
+            eng.set_no_repeat_ngram(0)
+        if stop is not None:
+            eng.set_stop(None)
+        if nuc:
+            eng.set_nucleus(None, None)
+
+
+def _decode_steps(eng, tokens, length, done, n: int, temperature, top_k, eos_id, seed, early: bool) -> int:
+    """n single-token steps over every row of `tokens` (eng.decode); the steps issued.  early (an EOS or a stop specification can end
+    a sequence): the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
+    (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens, inference/ger.py:71, and a correction is
+    usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps."""
+    if not early:
+        eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
+        return n
+    steps_run = 0
+    while steps_run < n:
+        c = min(EOS_CHECK_EVERY, n - steps_run)
+        eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=steps_run)
+        steps_run += c
+        if steps_run < n and bool((done != 0).all()):
+            break
+    return steps_run
+
+
+def _token_buffer(prompts, lens, tok_ld: int, dev) -> torch.Tensor:
+    """[len(prompts), tok_ld] int64: every prompt at the start of its row, zeros behind."""
+    T_max = max(lens)
+    if min(lens) == T_max:             # equal lengths: one copy
+        tokens = torch.nn.functional.pad(torch.stack([p.to(dev) for p in prompts]), (0, tok_ld - T_max))
+    else:                              # ragged: right-pad with 0 (pad_sequence), then out to the buffer width
+        tokens = torch.nn.utils.rnn.pad_sequence([p.to(dev) for p in prompts], batch_first=True)
+        tokens = torch.nn.functional.pad(tokens, (0, tok_ld - tokens.size(1)))
+    return tokens.contiguous()
 
 
 @torch.inference_mode()
@@ -161,7 +225,6 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     stay the raw row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop and fp8; the
     arg-max (top_k = 1, and with it speculate) takes neither.  None, 1.0 and 0.0 (the defaults) are off: the call it always was."""
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
-    nuc = top_p < 1.0 or min_p > 0.0
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
@@ -189,12 +252,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     if D:
         eng.reserve_rows(B * (D + 1))
     tok_ld = T_max + max_new_tokens
-    if min(lens) == T_max:             # equal lengths: one copy
-        tokens = torch.nn.functional.pad(torch.stack([p.to(dev) for p in prompts]), (0, tok_ld - T_max))
-    else:                              # ragged: right-pad with 0 (pad_sequence), then out to the buffer width
-        tokens = torch.nn.utils.rnn.pad_sequence([p.to(dev) for p in prompts], batch_first=True)
-        tokens = torch.nn.functional.pad(tokens, (0, tok_ld - tokens.size(1)))
-    tokens = tokens.contiguous()
+    tokens = _token_buffer(prompts, lens, tok_ld, dev)
     lp_buf = torch.full((B, tok_ld), float("nan"), dtype=torch.float32, device=dev) if return_logprobs else None
     top_buf = _top_buffers((B, tok_ld), K, dev) if K else None
     if D:   # lengths, flags and the three counters side by side: one read-back
@@ -224,19 +282,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p)
     if ev:
         ev[1].record()
-    if lp_buf is not None:
-        eng.set_logprobs(lp_buf)        # part of the captured step's key; without it the call runs the steps it always ran
-    if top_buf is not None:
-        eng.set_top_logprobs(*top_buf)  # likewise
-    if mask is not None:
-        eng.set_token_mask(mask)        # likewise
-    if ngram:
-        eng.set_no_repeat_ngram(ngram, start)   # likewise
-    if stop is not None:
-        eng.set_stop(stop, start)               # likewise
-    if nuc:
-        eng.set_nucleus(top_p, min_p)           # likewise
-    try:
+    # each of these is part of the captured step's key; without it the call runs the steps it always ran
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p):
         steps_run = 0
         if max_new_tokens > 1:
             n = max_new_tokens - 1
@@ -250,32 +297,9 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                     steps_run += c
                     if steps_run < n and bool((done != 0).all()):
                         break
-            elif eos_id is None and stop is None:
-                eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
-                steps_run = n
             else:
-                # with an EOS or a stop specification the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
-                # (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens, inference/ger.py:71, and a
-                # correction is usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps
-                while steps_run < n:
-                    c = min(EOS_CHECK_EVERY, n - steps_run)
-                    eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=steps_run)
-                    steps_run += c
-                    if steps_run < n and bool((done != 0).all()):
-                        break
-    finally:
-        if lp_buf is not None:
-            eng.set_logprobs(None)      # the buffer is this call's
-        if top_buf is not None:
-            eng.set_top_logprobs(None)
-        if mask is not None:
-            eng.set_token_mask(None)
-        if ngram:
-            eng.set_no_repeat_ngram(0)
-        if stop is not None:
-            eng.set_stop(None)
-        if nuc:
-            eng.set_nucleus(None, None)
+                steps_run = _decode_steps(eng, tokens, length, done, n, temperature, top_k, eos_id, seed,
+                                          early=eos_id is not None or stop is not None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -316,6 +340,154 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
         res += (st,)
     return res if len(res) > 1 else out
+
+
+MAX_SAMPLES = 8           # DH_MAX_SAMPLES: the slots dh_engine_fork_slots gives an utterance, its own included
+
+
+def check_num_samples(num_samples) -> int:
+    """N of a sample_batch call, or a ValueError."""
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 2 <= num_samples <= MAX_SAMPLES:
+        raise ValueError(f"num_samples is the number of sampled candidates per utterance, an int in 2..{MAX_SAMPLES}, not {num_samples!r} "
+                         "(one candidate is generate_batch's call)")
+    return num_samples
+
+
+@torch.inference_mode()
+def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_samples: int, temperature: float = 1.0,
+                 top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, seed: int = 1337,
+                 eos_id: Optional[int] = None, prefill_batch: int = 32, share_prefix: Union[bool, str] = False, token_mask=None,
+                 no_repeat_ngram: int = 0, stop=None, top_logprobs: int = 0, timing: Optional[dict] = None,
+                 return_state: bool = False, speculate: int = 0):
+    """num_samples = N (2..8) sampled candidates per prompt from ONE prefill of it (include/dualhyp_hip.h, "Sampled candidates").
+
+    DEFINITION: sample j of utterance u is row u * N + j of generate_batch over [p for p in prompts for _ in range(N)] with the same
+    keyword arguments and return_logprobs=True — the same ids, log-probabilities, alternatives and done flags, bit for bit.  It holds
+    by construction: the draw is keyed by (seed, step, row); utterance u is prefilled into KV slot u * N (prefill_batch utterances at
+    a time; with share_prefix the shared positions go into the source slots first) and one dh_engine_fork_slots launch copies every
+    prompt's tiles into the N - 1 slots behind, the bytes a prefill of their own would have written, since a prefill row's bits do
+    not depend on the rows beside it; the first pick is ops.sample on the last-position logits repeated N times per utterance; the
+    decode steps are generate_batch's over B * N rows.  (A chunk of one-token prompts alone is forwarded by the single-token
+    kernels, as generate_batch forwards it; the chunks here hold utterances, there rows.)
+
+    token_mask: one row, or id list, per UTTERANCE, serving its N samples.  The other arguments are generate_batch's.
+
+    Returns, per utterance, the list of its N samples in sample order, each a dict of
+      tokens          1-D int64 CPU tensor, the generated ids, cut before the EOS as generate_batch cuts,
+      token_logprobs  1-D float32 CPU tensor, one value per produced token, the EOS's included (generate_batch's return_logprobs),
+      sum_logprob     their sum in double precision, as a float (NaN-free: every produced token has a value),
+      avg_logprob     sum_logprob / max(1, the number of produced tokens),
+      finish_reason   "eos", "length" or "stop" (dualhyp_amd.stop.finish_reasons of the row's done flag),
+      top_logprobs    with top_logprobs=K: (ids [n, K] int32, values [n, K] float32) CPU tensors, generate_batch's.
+    return_state: (that, the dict of the call's device state: tokens, length, done, logprobs[, top_ids, top_logprobs], B * N rows).
+
+    timing gains generate_batch's keys, with prefill_tokens counting every prompt once, and fork_ms: the fork launch between its own
+    two events, inside prefill_ms.
+
+    Refused with a ValueError before anything is launched: num_samples outside 2..8; top_k == 1 (the arg-max gives N equal rows);
+    speculate (a verify step confirms drafts against the arg-max); RelPrompt models (their prompts carry spliced embeddings)."""
+    N = check_num_samples(num_samples)
+    if top_k is not None and int(top_k) == 1:
+        raise ValueError(f"num_samples={N} does not go with top_k=1: the arg-max gives {N} equal rows; sample with top_k != 1")
+    if speculate:
+        raise ValueError(f"num_samples={N} does not go with speculate={speculate}: a verify step confirms drafts against the arg-max, "
+                         "and sampled candidates are not greedy")
+    from .relprompt import GPT as RelGPT
+    if isinstance(model, RelGPT):
+        raise ValueError(f"num_samples={N}: the RelPrompt decoder's prompts carry spliced reliability embeddings, which a prefill by "
+                         "ids into the source slots does not hold")
+    top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
+    B = len(prompts)
+    assert B > 0 and max_new_tokens > 0
+    R = B * N
+    K = _check_top_logprobs(model, top_logprobs, True)
+    ngram = _ngram.check_ngram(no_repeat_ngram)
+    if ngram:
+        _ngram.check_ngram(ngram, model.config.padded_vocab_size)
+    lens = [int(p.numel()) for p in prompts]
+    T_max = max(lens)
+    need_pos = T_max + max_new_tokens - 1
+    if model.max_seq_length < need_pos:
+        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    dev = model.transformer.wte.weight.device
+    mask = _token_mask(model, token_mask, B, 1, dev)
+    if mask is not None:
+        mask = mask.repeat_interleave(N, dim=0).contiguous()      # a row per decode row
+    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
+    chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
+    P = _shared_prefix(model, prompts, share_prefix, dev)
+    eng = model.engine(R, min(need_pos, -(-model.config.block_size // 64) * 64),
+                       max(P, R, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)), exact=R > prefill_batch)
+    row_lens = [n for n in lens for _ in range(N)]
+    tok_ld = T_max + max_new_tokens
+    tokens = _token_buffer([p for p in prompts for _ in range(N)], row_lens, tok_ld, dev)
+    lp_buf = torch.full((R, tok_ld), float("nan"), dtype=torch.float32, device=dev)
+    top_buf = _top_buffers((R, tok_ld), K, dev) if K else None
+    length = torch.tensor(row_lens, dtype=torch.int32, device=dev)
+    done = torch.zeros(R, dtype=torch.int32, device=dev)
+    plen = torch.tensor(lens, dtype=torch.int32, device=dev)      # what the fork reads
+    start = length.clone() if ngram or (stop is not None and stop.sequences) else None
+    eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # independent batch-1 runs
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    last = torch.empty((B, eng.vocab), dtype=torch.bfloat16, device=dev)
+    if P:
+        _forward_prefix(eng, prompts[0], P, 0, [u * N for u in range(1, B)])
+    for a, b in chunks:
+        packed = torch.cat([p.to(dev).reshape(-1)[P:] for p in prompts[a:b]])
+        last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], [u * N for u in range(a, b)], prompt_phase=bool(P), pos0=P)
+    if ev:
+        ev[3].record()
+    # positions at or behind a prompt's end in its last tile are overwritten before causality lets anything read them
+    eng.fork_slots(plen, N, T_max)
+    if ev:
+        ev[4].record()
+    ops.sample(last.repeat_interleave(N, dim=0), tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed,
+               step=0, logprobs=lp_buf, top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p,
+               min_p=min_p)
+    if ev:
+        ev[1].record()
+    steps_run = 0
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p):
+        if max_new_tokens > 1:
+            steps_run = _decode_steps(eng, tokens, length, done, max_new_tokens - 1, temperature, top_k, eos_id, seed,
+                                      early=eos_id is not None or stop is not None)
+    if ev:
+        ev[2].record()
+    model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
+    length_h = length.tolist()          # the read-back: lengths, flags, tokens and log-probabilities
+    done_h = done.tolist()
+    tokens_h, lp_h = tokens.cpu(), lp_buf.cpu()
+    top_h = tuple(t.cpu() for t in top_buf) if K else None
+    if ev:   # the read-back above has synchronised the stream
+        timing["prefill_ms"] = timing.get("prefill_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["fork_ms"] = timing.get("fork_ms", 0.0) + ev[3].elapsed_time(ev[4])
+        timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
+        timing["decode_steps"] = timing.get("decode_steps", 0) + steps_run
+        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + R * steps_run
+        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens) - (B - 1) * P
+        timing["shared_prefix"] = P
+    reasons = _stop.finish_reasons(done_h)
+    out = []
+    for u in range(B):
+        samples = []
+        for r in range(u * N, (u + 1) * N):
+            end = min(length_h[r], lens[u] + max_new_tokens)
+            lp = lp_h[r, lens[u]:end]
+            total = float(lp.double().sum())
+            smp = dict(tokens=tokens_h[r, lens[u]:end - 1 if done_h[r] == 1 else end], token_logprobs=lp, sum_logprob=total,
+                       avg_logprob=total / max(int(lp.numel()), 1), finish_reason=reasons[r])
+            if K:
+                smp["top_logprobs"] = tuple(t[r, lens[u]:end] for t in top_h)
+            samples.append(smp)
+        out.append(samples)
+    if return_state:
+        st = dict(tokens=tokens, length=length, done=done, logprobs=lp_buf)
+        if K:
+            st["top_ids"], st["top_logprobs"] = top_buf
+        return out, st
+    return out
 
 
 @torch.inference_mode()

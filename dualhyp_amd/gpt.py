@@ -347,6 +347,7 @@ class _Engine:
             adapter_bias=ptr(model.lm_head.adapter_bias.data), h_layers=layers, lm_head_ws=sptr(model.lm_head.linear))
         self.max_batch, self.s_max, self.max_tokens = max_batch, s_max, max_tokens
         self.vocab = desc.vocab
+        self.kv_dims = (cfg.n_query_groups, cfg.head_size)
         self.device = model.transformer.wte.weight.device
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -416,6 +417,26 @@ class _Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_copy_prefix(self.handle, int(src_slot), (C.c_int32 * n)(*dst_slots), n, int(n_pos),
                                                       torch.cuda.current_stream().cuda_stream))
+
+    def fork_slots(self, prompt_len: torch.Tensor, n_copies: int, max_len: int) -> None:
+        """The prompt cache of slot u * n_copies — the tiles that hold its first prompt_len[u] positions, every layer — into the
+        n_copies - 1 slots behind it, for every utterance u, by one launch that reads the lengths on the device
+        (dh_engine_fork_slots).  prompt_len: int32 [n_utt] on the GPU; max_len: its maximum as the host knows it."""
+        if prompt_len.dtype != torch.int32 or not prompt_len.is_cuda or not prompt_len.is_contiguous() or prompt_len.dim() != 1:
+            raise TypeError("fork_slots takes the prompt lengths as a contiguous 1-D int32 tensor on the GPU")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_fork_slots(self.handle, prompt_len.data_ptr(), prompt_len.numel(), int(n_copies), int(max_len),
+                                                     torch.cuda.current_stream().cuda_stream))
+
+    def read_kv8(self, what: int, layer: int) -> torch.Tensor:
+        """An fp8-KV engine's stored cache of `layer` (test hook, dh_engine_read): 9 / 10 the K / V^T bytes [max_batch, g, s_max * hs]
+        uint8, 11 / 12 the K / V exponents [max_batch, g, s_max] int8."""
+        assert what in (9, 10, 11, 12)
+        G, hs = self.kv_dims
+        out = torch.empty((self.max_batch, G, self.s_max * (hs if what <= 10 else 1)), dtype=torch.uint8 if what <= 10 else torch.int8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_read(self.handle, what, layer, out.data_ptr(), out.numel(), torch.cuda.current_stream().cuda_stream))
+        return out
 
     def row_arrays(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """The (row_seq, row_slot) device arrays of decode_rows: allocated once per engine, so their addresses stay

@@ -75,6 +75,11 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     the call's `done` flags, dualhyp_amd.stop.finish_reasons); with beams the best hypothesis' own 'finish_reason' is taken and every
     entry of 'beams' carries its own.  A generate_fn with an attribute `sampling` (--temperature / --top_k / --top_p / --min_p: a dict
     {temperature, top_k, top_p, min_p, seed}, set when any of them is not the default) gives every record 'sampling', a copy of it.
+    Or to a dict {'samples': per prompt the N sampled candidates of dualhyp_amd.sample_batch, 'select': 'avg_logprob' | 'sum_logprob' |
+    'mbr', 'logprobs': bool}: the prediction is the text of the candidate dualhyp_amd.select.select chooses among the candidates'
+    answers, every record gains 'samples', one {'text', 'sum_logprob', 'avg_logprob', 'finish_reason', 'key'} per candidate in sample
+    order ('key' is its selection key: the score, or the mbr risk), and 'selected', the chosen index; 'logprobs', 'finish_reason' and
+    the alternatives, where asked for, are the chosen candidate's.
     Returns corpus metrics on every rank and predictions on
     rank 0."""
     mine = shard_indices(len(examples), rank, world)
@@ -85,8 +90,21 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
         outs = generate_fn(prompts)
         stopping = bool(getattr(generate_fn, "stop", False))
         reasons = list(getattr(generate_fn, "finish_reasons", None) or ()) if stopping else []
-        lps = tops = beams = None
-        if isinstance(outs, dict):
+        lps = tops = beams = sampled = None
+        if isinstance(outs, dict) and "samples" in outs:
+            from .select import select
+            sampled = []                # per prompt: (candidates, their answers, the chosen index, the selection keys)
+            for p, cands in zip(prompts, outs["samples"]):
+                text = decode(p)
+                texts = [extract_answer(decode(torch.cat([p.reshape(-1).cpu(), c["tokens"].reshape(-1).cpu()])), text) for c in cands]
+                sampled.append((cands, texts) + select(cands, texts, outs.get("select", "avg_logprob")))
+            chosen = [cands[best] for cands, _, best, _ in sampled]
+            lps = [c["token_logprobs"] for c in chosen] if outs.get("logprobs") else None
+            tops = [c["top_logprobs"] for c in chosen] if lps is not None and all("top_logprobs" in c for c in chosen) else None
+            if stopping:
+                reasons = [c.get("finish_reason") for c in chosen]
+            outs = [torch.cat([p.reshape(-1).cpu(), c["tokens"].reshape(-1).cpu()]) for p, c in zip(prompts, chosen)]
+        elif isinstance(outs, dict):
             beams = outs["beams"]
             lps = [hyps[0]["token_logprobs"] for hyps in beams] if outs.get("logprobs") else None
             if stopping:
@@ -118,6 +136,12 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                                       "avg_logprob": _finite_or_none(hyp["sum_logprob"] / max(int(hyp["token_logprobs"].numel()), 1)),
                                       "finished": bool(hyp["finished"]),
                                       **({"finish_reason": hyp.get("finish_reason")} if stopping else {})} for hyp in beams[k]]
+            if sampled is not None:
+                cands, texts, best, keys = sampled[k]
+                preds[i]["samples"] = [{"text": t, "sum_logprob": _finite_or_none(c["sum_logprob"]), "avg_logprob": _finite_or_none(c["avg_logprob"]),
+                                        "finish_reason": c.get("finish_reason"), "key": None if key is None else _finite_or_none(key)}
+                                       for c, t, key in zip(cands, texts, keys)]
+                preds[i]["selected"] = int(best)
             if lps is not None:
                 total = float(lps[k].double().sum())
                 preds[i]["sum_logprob"] = total
@@ -253,7 +277,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     from .checkpoint import load_checkpoint
     from .data import HypothesesDataset, prompt_ids
     from .constrain import allowed_from_prompts, pack_mask
-    from .generate import beam_search_batch, generate_batch, generate_stream
+    from .generate import beam_search_batch, generate_batch, generate_stream, sample_batch
     if adapter_path:
         sd = load_checkpoint(adapter_path)
         missing, unexpected = model.load_state_dict(sd, strict=False)
@@ -328,6 +352,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     top_n = int(getattr(args, "top_logprobs", 0) or 0)
     want_lp = bool(getattr(args, "logprobs", False)) or top_n > 0
     beams = int(getattr(args, "num_beams", 1) or 1)
+    n_samples = int(getattr(args, "num_samples", 1) or 1)
+    how = getattr(args, "select", None) or "avg_logprob"
     constrain = getattr(args, "constrain", "off") == "prompt"
     extra = read_token_ids(args.constrain_extra) if constrain and getattr(args, "constrain_extra", None) else ()
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
@@ -349,6 +375,11 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
                                      prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask,
                                      no_repeat_ngram=ngram, stop=stop)
             return {"beams": hyps, "logprobs": want_lp}
+        if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
+            cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
+                                 prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, token_mask=mask,
+                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp)
+            return {"samples": cands, "select": how, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
@@ -373,7 +404,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.no_repeat_ngram = ngram
     gen.stop = stop is not None
     gen.sampling = sampling
-    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams), rank=rank, world=world, eos_id=eos,
+    out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams // n_samples), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
     if mask_stats:
@@ -450,6 +481,17 @@ def build_parser():
                    help="W in 2..4: beam search over W hypotheses per utterance (beam_search_batch), --decode_batch // W utterances at a "
                         "time; the prediction is the best hypothesis and every record gains beams, the ranked hypotheses with text, "
                         "sum_logprob, avg_logprob and finished.  Default 1: greedy decoding, the path it always was")
+    p.add_argument("--num_samples", type=int, default=1, metavar="N",
+                   help="N in 2..8 (with --top_k other than 1): N sampled candidates per utterance from one prefill of its prompt "
+                        "(sample_batch: the prompt's KV cache is forked into N decode slots by one launch), --decode_batch // N "
+                        "utterances at a time; the prediction is the candidate --select chooses and every record gains samples (text, "
+                        "sum_logprob, avg_logprob, finish_reason and the selection key of every candidate) and selected, the chosen "
+                        "index; --schedule batch only, not with --num_beams or --speculate.  Default 1: the path it always was (the "
+                        "effect on a real corpus's WER is unmeasured)")
+    p.add_argument("--select", choices=("avg_logprob", "sum_logprob", "mbr"), default=None,
+                   help="with --num_samples N > 1: the candidate kept — the highest avg_logprob (the default) or sum_logprob, or mbr: "
+                        "the candidate with the lowest word edit distance to the other N - 1, each standing in as a reference (minimum "
+                        "Bayes risk; ties go to the higher avg_logprob)")
     p.add_argument("--constrain", choices=("off", "prompt"), default="off",
                    help="prompt: constrained decoding — an utterance may emit only token ids that occur in its own prompt (its n-best "
                         "hypotheses and the template), the EOS and the ids of --constrain_extra; the mask is applied inside the sampling "
@@ -520,6 +562,19 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                               (bool(args.top_logprobs), f"--top_logprobs {args.top_logprobs}", "the records carry the beams instead")):
             if on:
                 p.error(f"--num_beams {args.num_beams} does not go with {flag}: {why}")
+    if not 1 <= args.num_samples <= 8:
+        p.error(f"--num_samples {args.num_samples}: N is 1 (one answer) or 2..8")
+    if args.select is not None and args.num_samples < 2:
+        p.error(f"--select {args.select} goes with --num_samples N > 1: one answer leaves nothing to select among")
+    if args.num_samples > 1:
+        for on, flag, why in ((args.num_beams > 1, f"--num_beams {args.num_beams}", "beam search ranks hypotheses by score and draws nothing"),
+                              (bool(args.speculate), f"--speculate {args.speculate}", "a verify step confirms drafts against the greedy arg-max"),
+                              (args.schedule == "continuous", "--schedule continuous", "an utterance's N decode slots are forked and stepped together"),
+                              (args.top_k == 1, "--top_k 1", f"the arg-max gives {args.num_samples} equal candidates; sample with --top_k 0 or K > 1")):
+            if on:
+                p.error(f"--num_samples {args.num_samples} does not go with {flag}: {why}")
+        if args.select is None:
+            args.select = "avg_logprob"
     if not 0 <= args.no_repeat_ngram <= 8:
         p.error(f"--no_repeat_ngram {args.no_repeat_ngram}: N is 0 (off) or 1..8")
     if args.no_repeat_ngram and args.num_beams > 1:         # beam_search_batch refuses it too; here nothing has been loaded yet

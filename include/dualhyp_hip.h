@@ -33,7 +33,7 @@ typedef uint16_t dh_bf16;
  * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks); dh_sample_bf16_ngram, dh_sample_rows_bf16_ngram and
  * dh_engine_set_no_repeat_ngram (no-repeat n-grams); dh_sample_bf16_stop, dh_sample_rows_bf16_stop, dh_beam_select_bf16_stop and
  * dh_engine_set_stop (stop conditions); dh_sample_bf16_nucleus, dh_sample_rows_bf16_nucleus and dh_engine_set_nucleus (nucleus
- * and min-p sampling). */
+ * and min-p sampling); dh_engine_fork_slots (sampled candidates). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -808,6 +808,27 @@ int dh_engine_forward_slots(dh_engine* e, const int64_t* ids, const int32_t* h_s
 int dh_engine_copy_prefix(dh_engine* e, int src_slot, const int32_t* h_dst_slots, int n_dst, int n_pos,
                           void* stream);
 
+/* ---- Sampled candidates ----------------------------------------------------------------------------------------------------
+ * N candidates per utterance from one prefill (dualhyp_amd/generate.py:sample_batch).  DEFINITION: sample j of utterance u is row
+ * u * N + j of a dh_engine_decode run over the prompt list with every prompt repeated N times — the same ids, log-probabilities,
+ * alternatives and done flags, bit for bit.  It holds by construction: the draw is keyed by (seed, step, row), the decode steps are
+ * dh_engine_decode over n_utt * N rows, and a forked slot holds the bytes a prefill of its own would have written, because a
+ * prefill row's bits do not depend on the rows beside it.  So utterance u is prefilled once, into slot u * N, and
+ * dh_engine_fork_slots copies its prompt cache into the N - 1 slots behind.
+ *
+ * For every utterance u < n_utt the 32-key tiles 0 .. ceil(prompt_len[u] / 32) - 1 of slot u * n_copies — K and V^T of every layer
+ * and group — are copied into slots u * n_copies + 1 .. u * n_copies + n_copies - 1, by ONE launch on `stream` over all utterances
+ * (an engine made with kv_dtype 1: two launches, the fp8 bytes and then the exponents, as dh_engine_copy_prefix splits them).
+ * d_prompt_len is a DEVICE array of n_utt int32 and is read by the kernel: the call makes no host synchronisation and no upload,
+ * and it can be captured.  max_len, the host's maximum of the lengths (1 .. s_max), only sizes the grid: a length above it is the
+ * caller's error and is copied as far as the grid reaches, a length < 1 copies nothing, and the tile count is clamped to the cache
+ * on the device, so no length writes outside a slot's blocks.
+ * n_copies is N, 2 .. DH_MAX_SAMPLES, and n_utt * n_copies <= max_batch.  Positions at or behind a prompt's end inside its last
+ * tile carry the source's bytes (the decode steps overwrite them before causality lets anything read them); every tile behind,
+ * the source slots and the slots at or above n_utt * n_copies keep their contents. */
+#define DH_MAX_SAMPLES 8
+int dh_engine_fork_slots(dh_engine* e, const int32_t* d_prompt_len, int n_utt, int n_copies, int max_len, void* stream);
+
 /* Reproduce the rsqrt rounding of the reference's CPU path (see dh_rmsnorm_bf16 row_tail):
  * vec_width = lanes of torch's bf16 vector loop on the reference host (32 on AVX-512, 16 on
  * AVX2), 0 = off (every row uses bf16(1/sqrt(t)), as a GPU run of the reference would).
@@ -934,7 +955,9 @@ int dh_engine_graph_count(const dh_engine* e, int n_draft);
  *   what 5: int32 kv_len of the last step's sequences (a verify step: the lengths its drafts were proposed from)
  *   what 6 / 7: an fp8-KV engine's K / V^T cache of `layer` EXPANDED to bf16 (every slot, every position), in the form of
  *               what 1 / 2; overwrites the engine's one-layer scratch.  what 1 / 2 are refused by an fp8-KV engine.
- *   what 8: the bf16 logits rows of the last single-token step, [n_rows, vocab] */
+ *   what 8: the bf16 logits rows of the last single-token step, [n_rows, vocab]
+ *   what 9 / 10: an fp8-KV engine's K / V^T bytes of `layer` as stored, [max_batch, g, s_max * hs] uint8
+ *   what 11 / 12: its K / V exponents of `layer` as stored, [max_batch, g, s_max] int8 */
 int dh_engine_read(dh_engine* e, int what, int layer, void* dst, int64_t n_bytes, void* stream);
 /* HIP-event timing of the dominant kernels inside the last forward/decode call (bench.py
  * roofline): returns accumulated milliseconds and launch count for kernel class `which`
