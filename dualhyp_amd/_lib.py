@@ -44,6 +44,11 @@ class StopSpec(C.Structure):
     _fields_ = [("set", P), ("seqs", P), ("h_seq_len", P), ("n_seqs", C.c_int32)]
 
 
+class PenaltyArgs(C.Structure):
+    """dh_penalty_args: the three penalties of one call (include/dualhyp_hip.h, "Penalties")"""
+    _fields_ = [("repetition", F), ("frequency", F), ("presence", F)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/dualhyp_hip.h
 SIGNATURES = {
     "dh_abi_version": (I, []),
@@ -100,6 +105,10 @@ SIGNATURES = {
     "dh_sample_bf16_nucleus": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F]),
     "dh_sample_rows_bf16_nucleus": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
                                         F, F]),
+    "dh_sample_bf16_penalty": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F,
+                                   C.POINTER(PenaltyArgs)]),
+    "dh_sample_rows_bf16_penalty": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
+                                        F, F, C.POINTER(PenaltyArgs)]),
     "dh_beam_select_bf16_stop": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P, P]),
     "dh_token_top_logprobs_bf16_mask": (I, [P, I, I, P, P, I, P, I, I, P]),
     "dh_beam_select_bf16_mask": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, P]),
@@ -139,6 +148,7 @@ SIGNATURES = {
     "dh_engine_set_no_repeat_ngram": (I, [P, I, P]),
     "dh_engine_set_stop": (I, [P, C.POINTER(StopSpec), P, P]),
     "dh_engine_set_nucleus": (I, [P, F, F]),
+    "dh_engine_set_penalties": (I, [P, C.POINTER(PenaltyArgs), P]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

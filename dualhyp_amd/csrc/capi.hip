@@ -50,6 +50,17 @@ int dh_nucleus_pack(const char* name, float top_p, float min_p, dh_nucleus_args&
     return 0;
 }
 
+// dh_penalty_args checked, with the header's ranges ("Penalties"): nothing is launched.  Null is off.  Every comparison is false for a NaN.
+int dh_penalty_pack(const char* name, const dh_penalty_args* in, dh_penalty_args& out) {
+    out = DH_PENALTY_OFF;
+    if (!in) return 0;
+    DH_CHECK(in->repetition >= 0.125f && in->repetition <= 8.f, "%s: repetition=%g is not in [1/8, 8] (1 = off)", name, (double)in->repetition);
+    DH_CHECK(in->frequency >= -8.f && in->frequency <= 8.f, "%s: frequency=%g is not in [-8, 8] (0 = off)", name, (double)in->frequency);
+    DH_CHECK(in->presence >= -8.f && in->presence <= 8.f, "%s: presence=%g is not in [-8, 8] (0 = off)", name, (double)in->presence);
+    out = *in;
+    return 0;
+}
+
 extern "C" int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t* h_hbm_bytes) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

@@ -294,22 +294,33 @@ struct dh_nucleus_args {
 // the checks of every entry that takes (top_p, min_p) (capi.hip): top_p in (0, 1], min_p in [0, 1], neither NaN
 int dh_nucleus_pack(const char* name, float top_p, float min_p, dh_nucleus_args& out);
 
+// Penalties (include/dualhyp_hip.h): dh_penalty_args goes to the kernels as it is, by value.  Off: nothing reads a history for it.
+constexpr dh_penalty_args DH_PENALTY_OFF{1.f, 0.f, 0.f};
+__host__ __device__ inline bool dh_penalty_on(const dh_penalty_args& p) { return p.repetition != 1.f || p.frequency != 0.f || p.presence != 0.f; }
+inline bool dh_penalty_same(const dh_penalty_args& a, const dh_penalty_args& b) {
+    return a.repetition == b.repetition && a.frequency == b.frequency && a.presence == b.presence;
+}
+// the checks of every entry that takes a dh_penalty_args (capi.hip): null is off; finite, repetition in [1/8, 8], the others in [-8, 8]
+int dh_penalty_pack(const char* name, const dh_penalty_args* in, dh_penalty_args& out);
+
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
 // dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability;
 // top_n (0: off) with top_ids / top_lp ([n_seq, tok_ld, top_n], dh_engine_set_top_logprobs): the row's top_n alternatives as well;
 // mask (nullable, [n_seq, mask_ld] words, dh_engine_set_token_mask): the sequences' allowed tokens, null = the kernels without one;
 // ngram (0: off) with start ([n_seq] prompt lengths, dh_engine_set_no_repeat_ngram): no-repeat n-grams, 0 = the kernels without it;
 // stop (dh_engine_set_stop; its sequences count from the same `start`): the stop test behind the pick, all zero = off;
-// nuc (dh_engine_set_nucleus): top_p / min_p of the sampled branch, the default = off
+// nuc (dh_engine_set_nucleus): top_p / min_p of the sampled branch, the default = off;
+// pen (dh_engine_set_penalties; its history counts from the same `start`): the three penalties, the default = off
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
                    float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, float* logprobs,
                    int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask, int mask_ld, int ngram, const int32_t* start,
-                   const dh_stop_args& stop, void* stream, const dh_nucleus_args& nuc = dh_nucleus_args{});
+                   const dh_stop_args& stop, void* stream, const dh_nucleus_args& nuc = dh_nucleus_args{},
+                   const dh_penalty_args& pen = DH_PENALTY_OFF);
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
                         const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream,
-                        const dh_nucleus_args& nuc = dh_nucleus_args{});
+                        const dh_nucleus_args& nuc = dh_nucleus_args{}, const dh_penalty_args& pen = DH_PENALTY_OFF);
 
 // the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
 // acceptance kernel (sampling.hip)

@@ -51,6 +51,8 @@ struct dh_engine {
     const int32_t* stop_start = nullptr;                // lengths its sequences count from, and a beam call's [n_utt, W] ending ids
     int32_t* stop_fin_tok = nullptr;
     dh_nucleus_args nuc;                                // dh_engine_set_nucleus: top_p / min_p of later decode / decode_rows calls (default: off)
+    dh_penalty_args pen = DH_PENALTY_OFF;               // dh_engine_set_penalties: the penalties of later decode / decode_rows calls (default: off)
+    const int32_t* pen_start = nullptr;                 // and the caller's [n_seq] prompt lengths their history counts from
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -88,6 +90,7 @@ struct dh_engine {
         int ngram; const int32_t* ngram_start;                // dh_engine_set_no_repeat_ngram: likewise (0 / null in a beam step's key)
         dh_stop_args stop; const int32_t* stop_start; int32_t* stop_fin_tok;   // dh_engine_set_stop: likewise (a beam step's key: the set and fin_tok)
         dh_nucleus_args nuc;                                  // dh_engine_set_nucleus: likewise (off in an arg-max, a verify or a beam step's key)
+        dh_penalty_args pen; const int32_t* pen_start;        // dh_engine_set_penalties: likewise (off / null in a verify or a beam step's key)
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
@@ -98,7 +101,8 @@ struct dh_engine {
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
                    logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
                    mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && stop == k.stop && stop_start == k.stop_start &&
-                   stop_fin_tok == k.stop_fin_tok && nuc == k.nuc && beam_w == k.beam_w &&
+                   stop_fin_tok == k.stop_fin_tok && nuc == k.nuc && dh_penalty_same(pen, k.pen) && pen_start == k.pen_start &&
+                   beam_w == k.beam_w &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
@@ -1005,6 +1009,9 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     return 0;
 }
 
+// the prompt lengths of a step's history readers: the setters were given the same numbers
+const int32_t* hist_start(const dh_engine::GKey& k) { return k.ngram_start ? k.ngram_start : k.pen_start ? k.pen_start : k.stop_start; }
+
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (k.beam_w) return beam_step(e, k, s);
     if (k.spec) return verify_step(e, k, s);
@@ -1018,10 +1025,10 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
                                    k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                                   k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s, k.nuc);
+                                   hist_start(k), k.stop, s, k.nuc, k.pen);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
                           e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                          k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s, k.nuc);
+                          hist_start(k), k.stop, s, k.nuc, k.pen);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1268,6 +1275,8 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_CHECK(e && tokens && length && done, "dh_engine_decode: null argument");
     DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
+    DH_CHECK(!dh_penalty_on(e->pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
+             "LDS tables of %d entries; tok_ld=%d may not fit", "dh_engine_decode", DH_MAX_PENALTY_HISTORY, tok_ld);
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
@@ -1279,7 +1288,8 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
                               e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
-                              top_k == 1 ? dh_nucleus_args{} : e->nuc};     // the arg-max takes neither parameter: its step is the plain one
+                              top_k == 1 ? dh_nucleus_args{} : e->nuc,      // the arg-max takes neither parameter: its step is the plain one
+                              e->pen, e->pen_start};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1290,13 +1300,15 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(n_rows > 0 && n_rows <= e->max_batch, "dh_engine_decode_rows: n_rows=%d exceeds max_batch=%d", n_rows, e->max_batch);
     DH_CHECK(n_seq > 0 && tok_ld > 0 && max_new_tokens > 0, "dh_engine_decode_rows: bad shape");
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
+    DH_CHECK(!dh_penalty_on(e->pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
+             "LDS tables of %d entries; tok_ld=%d may not fit", "dh_engine_decode_rows", DH_MAX_PENALTY_HISTORY, tok_ld);
     if (n_steps <= 0) return 0;
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
                               e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
-                              top_k == 1 ? dh_nucleus_args{} : e->nuc};
+                              top_k == 1 ? dh_nucleus_args{} : e->nuc, e->pen, e->pen_start};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1334,6 +1346,8 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(n_seq * S <= MAX_DECODE_ROWS, "dh_engine_decode_spec: %d x %d rows exceed the streaming step's %d", n_seq, S, MAX_DECODE_ROWS);
     DH_CHECK(n_seq * S <= e->row_cap && n_seq * S <= e->max_tokens,
              "dh_engine_decode_spec: %d rows, the workspaces hold %d (dh_engine_reserve_rows) of max_tokens = %d", n_seq * S, e->row_cap, e->max_tokens);
+    DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_spec: penalties are set (repetition=%g, frequency=%g, presence=%g); a verify position's "
+             "history would have to include this launch's own picks", (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence);
     DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
     DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
@@ -1344,7 +1358,8 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_LAUNCH_CHECK();
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
                               limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr, dh_nucleus_args{}};
+                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr, dh_nucleus_args{},
+                              DH_PENALTY_OFF, nullptr};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1397,6 +1412,8 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
              (int)rows, e->row_cap, e->max_tokens);
     DH_CHECK(e->ngram == 0, "dh_engine_decode_beam: no_repeat_ngram=%d is set; a beam's history lives on the host, so the device cannot "
              "form its ban set", e->ngram);
+    DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_beam: penalties are set (repetition=%g, frequency=%g, presence=%g); a beam's history "
+             "lives on the host, so the device cannot count it", (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence);
     DH_CHECK(e->stop.n_seqs == 0, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
              "cannot match a sequence against it (the stop set alone goes with beam search)", e->stop.n_seqs);
     DH_CHECK(!e->stop.set || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
@@ -1415,7 +1432,8 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_LAUNCH_CHECK();
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
                         prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                        e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, dh_nucleus_args{}, W, *st};
+                        e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, dh_nucleus_args{}, DH_PENALTY_OFF, nullptr,
+                        W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1470,6 +1488,18 @@ extern "C" int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p) {
     dh_nucleus_args nuc;
     if (int rc = dh_nucleus_pack("dh_engine_set_nucleus", top_p, min_p, nuc)) return rc;
     e->nuc = nuc;
+    return 0;
+}
+
+extern "C" int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* penalties, const int32_t* start) {
+    DH_CHECK(e, "dh_engine_set_penalties: null engine");
+    dh_penalty_args pen;
+    if (int rc = dh_penalty_pack("dh_engine_set_penalties", penalties, pen)) return rc;
+    const bool on = dh_penalty_on(pen);
+    DH_CHECK(!on || start, "dh_engine_set_penalties: penalties need `start`, the sequences' prompt lengths");
+    DH_CHECK(!on || e->d.vocab <= 131072, "dh_engine_set_penalties: vocab=%d exceeds the 131072 ids of the sampler's LDS row", e->d.vocab);
+    e->pen = on ? pen : DH_PENALTY_OFF;
+    e->pen_start = on ? start : nullptr;
     return 0;
 }
 

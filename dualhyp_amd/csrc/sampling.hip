@@ -28,6 +28,35 @@ __device__ __forceinline__ bool mask_allows(const uint32_t* __restrict__ mrow, i
 // the mask byte of the 8 columns 8 c .. 8 c + 7 (a 16-byte load of the row)
 __device__ __forceinline__ uint32_t mask_byte(const uint32_t* __restrict__ mrow, int c) { return (mrow[c >> 2] >> ((c & 3) * 8)) & 255u; }
 
+// Penalties (include/dualhyp_hip.h): the columns a sequence's history overrides, as pen_build leaves them in LDS.  bits: the mask row's
+// layout, bit t set when id t occurs in the history; pre[w]: the number of set bits in the words before w, so a set bit's rank among
+// the set bits — its place in val — is pre[w] plus the set bits below it in its word; val[rank]: a_t.
+struct pen_view {
+    const uint32_t* bits = nullptr;
+    const uint16_t* pre = nullptr;
+    const bf16_t* val = nullptr;
+};
+__device__ __forceinline__ int pen_rank(const pen_view& ov, int t) {
+    return (int)ov.pre[t >> 5] + __popc(ov.bits[t >> 5] & ((1u << (t & 31)) - 1u));
+}
+// column i of the row the pick sees
+__device__ __forceinline__ bf16_t pen_value(const pen_view& ov, const bf16_t* __restrict__ lg, int i) {
+    bf16_t v = lg[i];                                   // a global load and, for the few overridden columns, an LDS load: never a flat one
+    if (mask_allows(ov.bits, i)) v = ov.val[pen_rank(ov, i)];
+    return v;
+}
+// a_t of the header from the raw value and the id's count c: the HF rule, then three separately rounded fp32 operations (the compiler
+// contracts a product and a difference into an FMA unless told not to), then the bf16 rounding
+__device__ __forceinline__ bf16_t penalised(bf16_t raw, int c, const dh_penalty_args& pen) {
+#pragma clang fp contract(off)
+    const float x = bf2f(raw);
+    const float y = x < 0.f ? x * pen.repetition : x / pen.repetition;
+    const float p = pen.frequency * (float)c;
+    const float d = y - p;
+    const float z = d - pen.presence;
+    return f2bf(z);
+}
+
 // The pick of one sequence's next token from its logits row `lg`, by the whole 1024-thread block; every thread
 // returns it.  The draw is keyed by (seed, step, seq).
 // MASK: every logit that feeds the pick goes through the sequence's mask row `mrow` first and is bf16 -inf where the token is not
@@ -43,10 +72,13 @@ __device__ __forceinline__ uint32_t mask_byte(const uint32_t* __restrict__ mrow,
 //          A(v) < P, A the mass strictly above v: ties share a key, so they stay together, and the clamp makes a crossing exist.
 // No floating-point sum feeds the threshold, and every entry goes through scaled(i): the kept set is a function of the row's bytes,
 // vocab and the parameters, wherever the row lies.
-template <bool MASK>
+// PEN ("Penalties" of the header; only pick_token_banned asks for it): every read of the row that feeds the pick takes column i's value
+// from `ov` where the sequence's history overrides it (pen_value below), so the pick is the PEN = false pick on a copy of the row with
+// a_t in those columns.  Off: `ov` is not read, and the code is what it always was.
+template <bool MASK, bool PEN = false>
 __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k,
                                           uint64_t seed, int step, int seq, const uint32_t* __restrict__ mrow,
-                                          const dh_nucleus_args nuc = dh_nucleus_args{}) {
+                                          const dh_nucleus_args nuc = dh_nucleus_args{}, const pen_view ov = pen_view{}) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float s_f[NT / 64];
     __shared__ int s_i[NT / 64];
@@ -56,6 +88,7 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
     // l = bf16(logit / temperature)   (generate/base.py:62, bf16 tensor / python float)
     auto scaled = [&](int i) -> bf16_t {
         if constexpr (MASK) { if (!mask_allows(mrow, i)) return BF16_NEG_INF; }      // -inf / temperature
+        if constexpr (PEN) return f2bf(bf2f(pen_value(ov, lg, i)) / temperature);
         return f2bf(bf2f(lg[i]) / temperature);
     };
 
@@ -83,10 +116,14 @@ __device__ __forceinline__ int pick_token(const bf16_t* __restrict__ lg, int voc
                 for (int u = 0; u < 4; ++u) {
                     if (c0 + u * NT >= n4) break;
                     const bf16_t* e8 = reinterpret_cast<const bf16_t*>(&q[u]);
+                    uint32_t ob = 0u;                           // PEN: which of the 8 columns are overridden (mostly none); read here, one
+                    if constexpr (PEN) ob = mask_byte(ov.bits, c0 + u * NT);     // at a time: four held across the loads cost registers
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const int i = (c0 + u * NT) * 8 + e;
-                        float v = bf2f(f2bf(bf2f(e8[e]) / temperature));
+                        bf16_t raw = e8[e];
+                        if constexpr (PEN) { if ((ob >> e) & 1u) raw = ov.val[pen_rank(ov, i)]; }
+                        float v = bf2f(f2bf(bf2f(raw) / temperature));
                         if constexpr (MASK) { if (!((mb[u] >> e) & 1u)) v = -INFINITY; }
                         if (v > best || (v == best && i < bi)) { best = v; bi = i; }
                     }
@@ -289,7 +326,7 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
     };
     for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
     __syncthreads();
-    if (m < ngram) return s_row;                        // the same for every thread: no n-gram is complete yet
+    if (ngram == 0 || m < ngram) return s_row;          // the same for every thread: no ban (a penalty alone), or no n-gram is complete yet
     int64_t suf[MAX_NGRAM - 1];                         // the (ngram - 1)-token suffix every candidate is tested against
 #pragma unroll
     for (int j = 0; j < MAX_NGRAM - 1; ++j) suf[j] = j < ngram - 1 ? g[m - ngram + 1 + j] : 0;
@@ -320,14 +357,90 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
     return s_row;
 }
 
+// Penalties (include/dualhyp_hip.h): the static LDS tables bound the history, and with it the distinct ids, of a penalised pick
+constexpr int PEN_MAX_HISTORY = DH_MAX_PENALTY_HISTORY;
+constexpr size_t PEN_LDS_BYTES = (BAN_MAX_VOCAB / 32) * (sizeof(uint32_t) + sizeof(uint16_t)) + PEN_MAX_HISTORY * (sizeof(uint32_t) + sizeof(bf16_t));
+static_assert(PEN_MAX_HISTORY <= 65535 && BAN_MAX_VOCAB / 32 == 4 * NT, "pen_build: uint16 ranks, four words of the bit row per thread");
+
+// The columns the history g[0..m) of a sequence overrides under the penalties `pen`, by the whole block: the distinct ids of g below
+// vocab with their counts c_t, and a_t = penalised(lg[t], c_t) for each (pen_view above says where).  Set membership is an LDS atomicOr,
+// a count an integer LDS atomicAdd, a rank a prefix sum of popcounts: exact whatever order the threads arrive in.  Every occurrence of an
+// id writes the id's value, the same bits from the same operands.  Every thread gets the view; it holds until the block's next call.
+// m <= PEN_MAX_HISTORY is the host's to refuse (DH_CHECK_PENALTY); the clamp only keeps a longer history inside the tables.
+__device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int vocab, const int64_t* g, int m, const dh_penalty_args& pen) {
+    // the tables live in the launch's dynamic LDS (PEN_LDS_BYTES, asked for only when a penalty is on): the n-gram-only launches of the
+    // family keep the static LDS, and with it the residency, they had
+    extern __shared__ __align__(16) unsigned char s_pen[];
+    uint32_t* s_bits = reinterpret_cast<uint32_t*>(s_pen);                 // [BAN_MAX_VOCAB / 32]
+    uint32_t* s_cnt = s_bits + BAN_MAX_VOCAB / 32;                          // [PEN_MAX_HISTORY]
+    uint16_t* s_pre = reinterpret_cast<uint16_t*>(s_cnt + PEN_MAX_HISTORY); // [BAN_MAX_VOCAB / 32]
+    bf16_t* s_val = s_pre + BAN_MAX_VOCAB / 32;                             // [PEN_MAX_HISTORY]
+    __shared__ uint32_t s_wtot[NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nw = (vocab + 31) >> 5;
+    m = m < PEN_MAX_HISTORY ? m : PEN_MAX_HISTORY;
+    for (int w = tid; w < nw; w += NT) s_bits[w] = 0u;
+    for (int i = tid; i < PEN_MAX_HISTORY; i += NT) s_cnt[i] = 0u;
+    __syncthreads();
+    for (int i = tid; i < m; i += NT) {
+        const int64_t t = g[i];
+        if (t >= 0 && t < vocab) atomicOr(&s_bits[t >> 5], 1u << (t & 31));
+    }
+    __syncthreads();
+    // exclusive prefix of the words' popcounts: thread t owns words 4 t .. 4 t + 3, a wave scan, then the wave totals
+    uint32_t pc[4], mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        pc[j] = 4 * tid + j < nw ? __popc(s_bits[4 * tid + j]) : 0u;
+        mine += pc[j];
+    }
+    uint32_t incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_wtot[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - mine;
+    for (int w = 0; w < wave; ++w) run += s_wtot[w];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (4 * tid + j < nw) s_pre[4 * tid + j] = (uint16_t)run;
+        run += pc[j];
+    }
+    __syncthreads();
+    const pen_view ov{s_bits, s_pre, s_val};
+    for (int i = tid; i < m; i += NT) {
+        const int64_t t = g[i];
+        if (t >= 0 && t < vocab) atomicAdd(&s_cnt[pen_rank(ov, (int)t)], 1u);
+    }
+    __syncthreads();
+    for (int i = tid; i < m; i += NT) {
+        const int64_t t = g[i];
+        if (t >= 0 && t < vocab) {
+            const int r = pen_rank(ov, (int)t);
+            s_val[r] = penalised(lg[t], (int)s_cnt[r], pen);
+        }
+    }
+    __syncthreads();
+    return ov;
+}
+
 // pick_token under no_repeat_ngram: under the row ban_row builds from the sequence's history g[0..m), through the masked paths of
 // pick_token (the 16-byte mask_byte loads included), so the pick is the unmasked pick on a copy of the row with -inf in every column that
 // the mask disallows or the history bans.  The kernels' BAN = false instantiations call pick_token<MASK> as they always did.
+// pen (launch-uniform; ngram may be 0 then): the columns of the history's ids hold a_t as well, through pick_token's PEN paths.  Off,
+// the pick runs the instantiation it always ran.
 template <bool MASK>
 __device__ __forceinline__ int pick_token_banned(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k, uint64_t seed,
                                              int step, int seq, const uint32_t* __restrict__ mrow, const int64_t* g, int m, int ngram,
-                                             const dh_nucleus_args nuc = dh_nucleus_args{}) {
+                                             const dh_nucleus_args nuc = dh_nucleus_args{}, const dh_penalty_args pen = DH_PENALTY_OFF) {
     const uint32_t* row = ban_row<MASK>(g, m, ngram, vocab, mrow);
+    if (dh_penalty_on(pen)) {                           // the same for every thread of the launch
+        const pen_view ov = pen_build(lg, vocab, g, m, pen);
+        return pick_token<true, true>(lg, vocab, temperature, top_k, seed, step, seq, row, nuc, ov);
+    }
     return pick_token<true>(lg, vocab, temperature, top_k, seed, step, seq, row, nuc);
 }
 
@@ -572,7 +685,8 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
                                                     float* __restrict__ logprobs, int top_n,
                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                     const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                    const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc) {
+                                                    const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc,
+                                                    dh_penalty_args pen) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
@@ -580,7 +694,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
     if constexpr (BAN) {                                // the history is what lies behind the prompt
         const int p0 = start[seq];
         choice = pick_token_banned<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
-                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram, nuc);
+                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram, nuc, pen);
     } else {
         choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
                                   MASK ? mask + (size_t)seq * mask_ld : nullptr, nuc);
@@ -618,7 +732,8 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                         const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc) {
+                                                         const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc,
+                                                    dh_penalty_args pen) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
@@ -627,7 +742,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
     if constexpr (BAN) {
         const int p0 = start ? start[u] : limit[u] - max_new;           // the prompt length, which limit[u] - max_new is
         choice = pick_token_banned<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
-                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc);
+                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc, pen);
     } else {
         choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
                                   MASK ? mask + (size_t)u * mask_ld : nullptr, nuc);     // the sequence's mask row, not the logits row's
@@ -757,17 +872,25 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 
 // the three kernels' variant for (logprobs, top_n): top_n > 0 needs the three buffers
 // and for the token mask: null is the kernel without it (the code it always was)
-// and for no_repeat_ngram: 0 is the kernel without it, likewise
+// and for no_repeat_ngram: 0 is the kernel without it, likewise; `hist` (a local of the launcher) is ngram > 0, or a penalty on: the
+// history-reading family
 #define DH_PICK_VARIANT_MB(kernel, M, B) \
     (top_n > 0 ? kernel<true, true, M, B> : logprobs ? kernel<true, false, M, B> : kernel<false, false, M, B>)
 #define DH_PICK_VARIANT_B(kernel, B) (mask ? DH_PICK_VARIANT_MB(kernel, true, B) : DH_PICK_VARIANT_MB(kernel, false, B))
-#define DH_PICK_VARIANT(kernel) (ngram > 0 ? DH_PICK_VARIANT_B(kernel, true) : DH_PICK_VARIANT_B(kernel, false))
+#define DH_PICK_VARIANT(kernel) (hist ? DH_PICK_VARIANT_B(kernel, true) : DH_PICK_VARIANT_B(kernel, false))
 // start_needed: the kernel has no other way to the prompt lengths
 #define DH_CHECK_NGRAM(name, start_needed)                                                                                      \
     DH_CHECK(ngram >= 0 && ngram <= MAX_NGRAM, name ": no_repeat_ngram=%d is not in 0 .. %d", ngram, MAX_NGRAM);                   \
     DH_CHECK(ngram == 0 || vocab <= BAN_MAX_VOCAB, name ": no_repeat_ngram keeps a sequence's allowed-minus-banned bits in a static " \
              "LDS row of %d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                  \
     DH_CHECK(ngram == 0 || start || !(start_needed), name ": no_repeat_ngram needs `start`, the prompt lengths")
+// hist_max: the longest history a pick of the call can see
+#define DH_CHECK_PENALTY(name, hist_max)                                                                                        \
+    DH_CHECK(!dh_penalty_on(pen) || start, name ": penalties need `start`, the prompt lengths: the history is what lies behind the prompt"); \
+    DH_CHECK(!dh_penalty_on(pen) || vocab <= BAN_MAX_VOCAB, name ": penalties keep a sequence's overridden columns in a static LDS row of " \
+             "%d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                             \
+    DH_CHECK(!dh_penalty_on(pen) || (hist_max) <= PEN_MAX_HISTORY, name ": penalties keep a sequence's distinct ids in static LDS tables " \
+             "of %d entries; a history of up to %d tokens may not fit", PEN_MAX_HISTORY, (int)(hist_max))
 #define DH_CHECK_MASK(name)                                                                                                    \
     DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, name ": mask_ld=%d is below the %d words of a %d-token mask row", mask_ld, \
              (vocab + 31) / 32, vocab)
@@ -780,8 +903,11 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
                    const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
-                   int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream, const dh_nucleus_args& nuc) {
+                   int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream, const dh_nucleus_args& nuc,
+                   const dh_penalty_args& pen) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
+    DH_CHECK_PENALTY("dh_sample_bf16", tok_ld);
+    const bool hist = ngram > 0 || dh_penalty_on(pen);
     DH_CHECK(sa.n_seqs == 0 || start, "dh_sample_bf16: stop sequences need `start`, the prompt lengths");
     DH_CHECK_TOP("dh_sample_bf16");
     DH_CHECK_MASK("dh_sample_bf16");
@@ -790,9 +916,9 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
     // logprobs null: the kernel without the log-probability pass (the code it always was)
-    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), dh_penalty_on(pen) ? PEN_LDS_BYTES : 0, (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc);
+                       top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -852,6 +978,21 @@ extern "C" int dh_sample_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t*
                           nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc);
 }
 
+extern "C" int dh_sample_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                      int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                      int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                      const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                      float top_p, float min_p, const dh_penalty_args* penalties) {
+    dh_penalty_args pen;
+    if (int rc = dh_penalty_pack("dh_sample_bf16_penalty", penalties, pen)) return rc;
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_sample_bf16_penalty", top_p, min_p, nuc)) return rc;
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_bf16_penalty", stop, start != nullptr, sa)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc, pen);
+}
+
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                               int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                               int step, void* stream) {
@@ -863,8 +1004,10 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
                         const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream,
-                        const dh_nucleus_args& nuc) {
+                        const dh_nucleus_args& nuc, const dh_penalty_args& pen) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
+    DH_CHECK_PENALTY("dh_sample_rows_bf16", tok_ld);
+    const bool hist = ngram > 0 || dh_penalty_on(pen);
     DH_CHECK_TOP("dh_sample_rows_bf16");
     DH_CHECK_MASK("dh_sample_rows_bf16");
     DH_CHECK_NGRAM("dh_sample_rows_bf16", false);
@@ -872,9 +1015,9 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), 0,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), dh_penalty_on(pen) ? PEN_LDS_BYTES : 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -941,6 +1084,23 @@ extern "C" int dh_sample_rows_bf16_nucleus(const dh_bf16* logits, int vocab, int
                                eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc);
 }
 
+extern "C" int dh_sample_rows_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                           int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                           int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                           float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                           int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
+                                           float min_p, const dh_penalty_args* penalties) {
+    dh_penalty_args pen;
+    if (int rc = dh_penalty_pack("dh_sample_rows_bf16_penalty", penalties, pen)) return rc;
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_sample_rows_bf16_penalty", top_p, min_p, nuc)) return rc;
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_rows_bf16_penalty", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc,
+                               pen);
+}
+
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                    int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
                                    int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
@@ -960,6 +1120,7 @@ int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
+    const bool hist = ngram > 0;                        // a verify step takes no penalty
     hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
                        counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa);

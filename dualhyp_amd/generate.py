@@ -17,6 +17,7 @@ from . import beam as _beam
 from . import constrain as _constrain
 from . import ngram as _ngram
 from . import nucleus as _nucleus
+from . import penalty as _penalty
 from . import ops
 from . import stop as _stop
 from .gpt import GPT
@@ -86,8 +87,24 @@ def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: S
         eng.copy_prefix(slot, list(other_slots), P)
 
 
+def _penalty_kw(pen) -> dict:
+    """The sampling ops' keywords of a checked triple (none when it is off)."""
+    return dict(repetition_penalty=pen[0], frequency_penalty=pen[1], presence_penalty=pen[2]) if pen else {}
+
+
+def _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate: int = 0):
+    """The checked (repetition, frequency, presence) of a call, or None when all three are off.  Needs nothing but the arguments."""
+    pen = _penalty.check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
+    if not _penalty.penalties_on(*pen):
+        return None
+    if speculate:
+        raise ValueError(f"speculate={speculate} does not go with penalties (repetition={pen[0]}, frequency={pen[1]}, presence={pen[2]}): "
+                         "a verify position's history would have to include the picks of its own step")
+    return pen
+
+
 @contextlib.contextmanager
-def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float):
+def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float, pen=None):
     """What a call hands the engine for its captured decode steps, each only where the call uses it — every one is part of a captured
     step's key, so without it the call runs the steps it always ran — and takes back behind them: the buffers are the call's."""
     nuc = top_p < 1.0 or min_p > 0.0
@@ -103,9 +120,13 @@ def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p:
         eng.set_stop(stop, start)
     if nuc:
         eng.set_nucleus(top_p, min_p)
+    if pen:
+        eng.set_penalties(*pen, start=start)
     try:
         yield
     finally:
+        if pen:
+            eng.set_penalties()
         if lp_buf is not None:
             eng.set_logprobs(None)
         if top_buf is not None:
@@ -155,7 +176,9 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    return_state: bool = False, prefill_batch: int = 32, timing: Optional[dict] = None,
                    share_prefix: Union[bool, str] = False, speculate: int = 0, drafts: Optional[torch.Tensor] = None,
                    return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
-                   stop=None, top_p: Optional[float] = None, min_p: Optional[float] = None):
+                   stop=None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                   repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+                   presence_penalty: Optional[float] = None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -223,7 +246,18 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     crop is taken on the row the sampler uses, after temperature, token_mask and no_repeat_ngram, inside the sampling kernels: the
     prefill's first pick and every captured decode step, with no launch or read-back of its own.  Log-probabilities and alternatives
     stay the raw row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop and fp8; the
-    arg-max (top_k = 1, and with it speculate) takes neither.  None, 1.0 and 0.0 (the defaults) are off: the call it always was."""
+    arg-max (top_k = 1, and with it speculate) takes neither.  None, 1.0 and 0.0 (the defaults) are off: the call it always was.
+
+    repetition_penalty (theta in [1/8, 8]), frequency_penalty and presence_penalty (alpha_f, alpha_p in [-8, 8]; include/dualhyp_hip.h,
+    "Penalties"): a token the sequence has already GENERATED (the prompt stays free, as for no_repeat_ngram) becomes less likely, with
+    whatever sampler the call uses, the arg-max included — the pick is the same call's pick on a copy of the logits row in which the
+    column of every such id t, generated c_t times, holds bf16(((x < 0 ? x * theta : x / theta) - alpha_f * c_t) - alpha_p), each
+    operation rounded to fp32.  The values are computed inside the sampling kernels from the token buffer, per sequence and step, with
+    no launch or read-back of their own and without writing the logits; the first pick of a prompt is unaffected, a masked or banned
+    column stays -inf, and log-probabilities and alternatives stay the raw row's.  It goes with share_prefix, return_logprobs,
+    top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p and fp8; speculate is refused, and the token buffer (the longest
+    prompt plus max_new_tokens) may have at most 2048 places.  None, 1.0 and 0.0 (the defaults) are off: the call it always was."""
+    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
@@ -239,6 +273,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     need_pos = T_max + max_new_tokens - 1
     if model.max_seq_length < need_pos:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    if pen:
+        _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
     dev = model.transformer.wte.weight.device
     mask = _token_mask(model, token_mask, B, 1, dev)
     stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
@@ -263,8 +299,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     else:
         length = torch.tensor(lens, dtype=torch.int32, device=dev)
         done = torch.zeros(B, dtype=torch.int32, device=dev)
-    # the prompt lengths: the ban's history, and a stop sequence's match, begin there
-    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram or (stop is not None and stop.sequences) else None
+    # the prompt lengths: the ban's and the penalties' history, and a stop sequence's match, begin there
+    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram or pen or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -279,11 +315,12 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         else:
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
-               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p)
+               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p,
+               **_penalty_kw(pen))
     if ev:
         ev[1].record()
     # each of these is part of the captured step's key; without it the call runs the steps it always ran
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen):
         steps_run = 0
         if max_new_tokens > 1:
             n = max_new_tokens - 1
@@ -358,7 +395,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                  top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, seed: int = 1337,
                  eos_id: Optional[int] = None, prefill_batch: int = 32, share_prefix: Union[bool, str] = False, token_mask=None,
                  no_repeat_ngram: int = 0, stop=None, top_logprobs: int = 0, timing: Optional[dict] = None,
-                 return_state: bool = False, speculate: int = 0):
+                 return_state: bool = False, speculate: int = 0, repetition_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None):
     """num_samples = N (2..8) sampled candidates per prompt from ONE prefill of it (include/dualhyp_hip.h, "Sampled candidates").
 
     DEFINITION: sample j of utterance u is row u * N + j of generate_batch over [p for p in prompts for _ in range(N)] with the same
@@ -396,6 +434,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     if isinstance(model, RelGPT):
         raise ValueError(f"num_samples={N}: the RelPrompt decoder's prompts carry spliced reliability embeddings, which a prefill by "
                          "ids into the source slots does not hold")
+    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
@@ -409,6 +448,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     need_pos = T_max + max_new_tokens - 1
     if model.max_seq_length < need_pos:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    if pen:
+        _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
     dev = model.transformer.wte.weight.device
     mask = _token_mask(model, token_mask, B, 1, dev)
     if mask is not None:
@@ -426,7 +467,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     length = torch.tensor(row_lens, dtype=torch.int32, device=dev)
     done = torch.zeros(R, dtype=torch.int32, device=dev)
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)      # what the fork reads
-    start = length.clone() if ngram or (stop is not None and stop.sequences) else None
+    start = length.clone() if ngram or pen or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
     if ev:
@@ -445,11 +486,11 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         ev[4].record()
     ops.sample(last.repeat_interleave(N, dim=0), tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed,
                step=0, logprobs=lp_buf, top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p,
-               min_p=min_p)
+               min_p=min_p, **_penalty_kw(pen))
     if ev:
         ev[1].record()
     steps_run = 0
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen):
         if max_new_tokens > 1:
             steps_run = _decode_steps(eng, tokens, length, done, max_new_tokens - 1, temperature, top_k, eos_id, seed,
                                       early=eos_id is not None or stop is not None)
@@ -616,7 +657,7 @@ class _StreamBackend:
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
                  logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None,
-                 top_p: float = 1.0, min_p: float = 0.0) -> None:
+                 top_p: float = 1.0, min_p: float = 0.0, pen=None) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -639,7 +680,8 @@ class _StreamBackend:
         self.ngram = ngram
         self.stop = stop                     # generate_batch's stop; its sequences count from the same prompt lengths
         self.top_p, self.min_p = top_p, min_p    # generate_batch's top_p / min_p (the decode steps get them through the engine)
-        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram or (stop is not None and stop.sequences) else None
+        self.pen = pen                       # generate_batch's penalties, checked (None: off); their history counts from the same lengths
+        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram or pen or (stop is not None and stop.sequences) else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -662,7 +704,7 @@ class _StreamBackend:
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
                         self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
-                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **self.kw)
+                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **_penalty_kw(self.pen), **self.kw)
         if end:
             end.record()
 
@@ -688,7 +730,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     prefill_batch: int = 64, check_every: int = EOS_CHECK_EVERY, timing: Optional[dict] = None,
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
                     top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False,
-                    top_p: Optional[float] = None, min_p: Optional[float] = None):
+                    top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -715,8 +758,12 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     next prompt takes its KV slot.  return_state: the result gains a last element, the dict of the call's device state (tokens,
     length, done — one row per prompt — and logprobs, top_ids, top_logprobs where asked for), as generate_batch's.
 
-    top_p, min_p: as in generate_batch — a row's kept set is a function of the row alone, so the ids do not depend on the schedule."""
+    top_p, min_p: as in generate_batch — a row's kept set is a function of the row alone, so the ids do not depend on the schedule.
+
+    repetition_penalty, frequency_penalty, presence_penalty: as in generate_batch — a sequence's adjusted values are formed from its own
+    row of the token buffer wherever it is scheduled, so the ids do not depend on the schedule."""
     from .schedule import StreamScheduler
+    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     nuc = top_p < 1.0 or min_p > 0.0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
@@ -732,6 +779,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     need_pos = max(lens) + max_new_tokens - 1
     if model.max_seq_length < need_pos:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    if pen:
+        _penalty.check_history(max(lens) + max_new_tokens, model.config.padded_vocab_size)
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
     dev = model.transformer.wte.weight.device
     mask = _token_mask(model, token_mask, N, 1, dev)
@@ -742,7 +791,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p)
+                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p, pen=pen)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -760,9 +809,13 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         eng.set_stop(stop, be.start)
     if nuc:
         eng.set_nucleus(top_p, min_p)
+    if pen:
+        eng.set_penalties(*pen, start=be.start)
     try:
         sched.run(be)
     finally:
+        if pen:
+            eng.set_penalties()
         if return_logprobs:
             eng.set_logprobs(None)      # the buffer is this call's
         if K:
@@ -812,11 +865,14 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
              top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, top_p: Optional[float] = None,
-             min_p: Optional[float] = None):
+             min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+             presence_penalty: Optional[float] = None):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
-    generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's."""
+    generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's.  repetition_penalty, frequency_penalty,
+    presence_penalty: generate_batch's."""
+    _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
     _nucleus.check_nucleus(top_p, min_p)
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
@@ -825,7 +881,8 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
                          speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
-                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p)
+                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

@@ -561,6 +561,26 @@ class _Engine:
         top_p, min_p = check_nucleus(top_p, min_p)
         _lib.check(self.lib.dh_engine_set_nucleus(self.handle, top_p, min_p))
 
+    def set_penalties(self, repetition: Optional[float] = None, frequency: Optional[float] = None, presence: Optional[float] = None,
+                      start: Optional[torch.Tensor] = None) -> None:
+        """The repetition, frequency and presence penalties (include/dualhyp_hip.h, "Penalties") for later decode / decode_rows calls;
+        None, 1.0 and 0.0 turn them off (dh_engine_set_penalties).  start: the int32 [n_seq] prompt lengths on the engine's device, the
+        array set_no_repeat_ngram / set_stop take; kept alive here while set.  The values are part of a captured step's key.  While
+        set, decode_spec and decode_beam refuse."""
+        from .penalty import check_penalties, penalties_on
+        r, f, p = check_penalties(repetition, frequency, presence)
+        if not penalties_on(r, f, p):
+            _lib.check(self.lib.dh_engine_set_penalties(self.handle, None, None))
+            self._pen_start = None
+            return
+        if start is None:
+            raise ValueError("penalties need start, the int32 prompt lengths: the history they count begins there")
+        if not start.is_cuda or start.dtype != torch.int32 or not start.is_contiguous() or start.dim() != 1:
+            raise TypeError("set_penalties takes start as a contiguous 1-D int32 tensor of prompt lengths on the GPU")
+        args = _lib.PenaltyArgs(r, f, p)
+        _lib.check(self.lib.dh_engine_set_penalties(self.handle, C.byref(args), start.data_ptr()))
+        self._pen_start = start
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"

@@ -75,6 +75,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     the call's `done` flags, dualhyp_amd.stop.finish_reasons); with beams the best hypothesis' own 'finish_reason' is taken and every
     entry of 'beams' carries its own.  A generate_fn with an attribute `sampling` (--temperature / --top_k / --top_p / --min_p: a dict
     {temperature, top_k, top_p, min_p, seed}, set when any of them is not the default) gives every record 'sampling', a copy of it.
+    A generate_fn with an attribute `penalties` (--repetition_penalty / --frequency_penalty / --presence_penalty: a dict {repetition,
+    frequency, presence}, set when any of them is not the default) gives every record 'penalties', a copy of it.
     Or to a dict {'samples': per prompt the N sampled candidates of dualhyp_amd.sample_batch, 'select': 'avg_logprob' | 'sum_logprob' |
     'mbr', 'logprobs': bool}: the prediction is the text of the candidate dualhyp_amd.select.select chooses among the candidates'
     answers, every record gains 'samples', one {'text', 'sum_logprob', 'avg_logprob', 'finish_reason', 'key'} per candidate in sample
@@ -130,6 +132,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["finish_reason"] = reasons[k]
             if getattr(generate_fn, "sampling", None):
                 preds[i]["sampling"] = dict(generate_fn.sampling)
+            if getattr(generate_fn, "penalties", None):
+                preds[i]["penalties"] = dict(generate_fn.penalties)
             if beams is not None:
                 text = decode(p)
                 preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
@@ -359,6 +363,12 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
     stop = stop_from_args(args, tokenizer, model.config.padded_vocab_size, model.transformer.wte.weight.device)
     skw = dict(stop=stop, return_state=True) if stop is not None else {}       # the reasons are read from the state's done flags
+    from .penalty import record as penalty_record
+    penalties = penalty_record(getattr(args, "repetition_penalty", 1.0), getattr(args, "frequency_penalty", 0.0),
+                               getattr(args, "presence_penalty", 0.0))
+    # the default run passes no penalty keyword at all
+    pkw = {} if penalties is None else dict(repetition_penalty=penalties["repetition"], frequency_penalty=penalties["frequency"],
+                                            presence_penalty=penalties["presence"])
     sampling = sampling_from_args(args)
     # the default run passes what it always passed: temperature 0.2, top_k 1 and the functions' own seed
     samp = dict(temperature=0.2, top_k=1) if sampling is None else dict(
@@ -378,18 +388,18 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
             cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
                                  prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, token_mask=mask,
-                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp)
+                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw)
             return {"samples": cands, "select": how, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
                                    share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask,
-                                   no_repeat_ngram=ngram, **samp, **skw)
+                                   no_repeat_ngram=ngram, **samp, **skw, **pkw)
         else:
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
                                   return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram,
-                                  **samp, **skw)
+                                  **samp, **skw, **pkw)
         if stop is not None:
             from .stop import finish_reasons
             gen.finish_reasons = finish_reasons(outs[-1]["done"])
@@ -404,6 +414,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.no_repeat_ngram = ngram
     gen.stop = stop is not None
     gen.sampling = sampling
+    gen.penalties = penalties
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams // n_samples), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -528,6 +539,18 @@ def build_parser():
                    help="P in [0, 1], with --top_k other than 1: only tokens whose probability is at least P times the best token's are "
                         "drawn from.  Default 0.0: off.  A run with any of --temperature, --top_k, --top_p, --min_p off its default "
                         "gives every record sampling: {temperature, top_k, top_p, min_p, seed}")
+    p.add_argument("--repetition_penalty", type=float, default=1.0, metavar="T",
+                   help="T in [1/8, 8]: the logit x of every token an utterance has already generated (its prompt stays free) becomes "
+                        "x * T where negative and x / T otherwise before the pick; the values are computed inside the sampling kernels, "
+                        "under both schedules and with --share_prefix, --constrain, --no_repeat_ngram, --stop, --logprobs, --top_logprobs, "
+                        "--top_p, --min_p, --num_samples and fp8; not with --speculate or --num_beams.  Default 1.0: off")
+    p.add_argument("--frequency_penalty", type=float, default=0.0, metavar="A",
+                   help="A in [-8, 8]: A times the number of times the utterance has generated a token is taken off its logit; goes "
+                        "with what --repetition_penalty goes with.  Default 0.0: off")
+    p.add_argument("--presence_penalty", type=float, default=0.0, metavar="A",
+                   help="A in [-8, 8]: A is taken off the logit of every token the utterance has generated; goes with what "
+                        "--repetition_penalty goes with.  Default 0.0: off.  A run with any of the three penalties off its default gives "
+                        "every record penalties: {repetition, frequency, presence}")
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
@@ -598,6 +621,19 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             check(value)
         except ValueError as e:
             p.error(f"{flag}: {e}")
+    from .penalty import check_penalties, penalties_on
+    try:
+        pen = check_penalties(args.repetition_penalty, args.frequency_penalty, args.presence_penalty)
+    except ValueError as e:
+        p.error(f"--repetition_penalty / --frequency_penalty / --presence_penalty: {e}")
+    if penalties_on(*pen):
+        flags = f"--repetition_penalty {pen[0]} --frequency_penalty {pen[1]} --presence_penalty {pen[2]}"
+        if args.speculate:          # generate_batch refuses it too; here nothing has been loaded yet
+            p.error(f"--speculate {args.speculate} does not go with {flags}: a verify position's history would have to include the picks "
+                    "of its own step")
+        if args.num_beams > 1:
+            p.error(f"--num_beams {args.num_beams} does not go with {flags}: the beams' histories live on the host, so the sampling "
+                    "kernels cannot count them")
     if not args.temperature > 0.0:
         p.error(f"--temperature {args.temperature}: the temperature is positive")
     if args.top_k < 0:

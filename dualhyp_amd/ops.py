@@ -326,6 +326,22 @@ def _start_arg(start: Optional[torch.Tensor], n_seq: int, device, keep):
     return keep(start, torch.int32)
 
 
+def _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start: Optional[torch.Tensor], tok_ld: int, vocab: int, keep):
+    """The dh_penalty_args pointer of a sampler call ("Penalties" of the header), or None when all three are off.  On, the call needs
+    start, and a token buffer and a vocab the sampler's LDS tables hold."""
+    from .penalty import check_history, check_penalties, penalties_on
+    r, f, p = check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
+    if not penalties_on(r, f, p):
+        return None
+    if start is None:
+        raise ValueError("penalties need start, the int32 prompt lengths: the history they count begins there")
+    check_history(tok_ld, vocab)
+    import ctypes
+    args = _lib.PenaltyArgs(r, f, p)
+    keep.append(args)
+    return ctypes.byref(args)
+
+
 def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
     index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
@@ -416,7 +432,8 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
            step: int = 0, logprobs: Optional[torch.Tensor] = None,
            top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
            no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
-           min_p: Optional[float] = None) -> None:
+           min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+           presence_penalty: Optional[float] = None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
@@ -427,7 +444,11 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     dualhyp_amd.stop.compile_stop; "Stop conditions" of the header): a sequence whose appended token is in the stop set, or completes
     a stop sequence within tokens[u, start[u]:], gets done = 3; stop sequences need start (dh_sample_bf16_stop).  top_p (in (0, 1]) and
     min_p (in [0, 1]; "Nucleus and min-p" of the header): the draw is made from the entries top_k keeps, cropped to their nucleus and to
-    those within min_p of the best; None, 1.0 and 0.0 are off, and top_k = 1 takes neither (dh_sample_bf16_nucleus)."""
+    those within min_p of the best; None, 1.0 and 0.0 are off, and top_k = 1 takes neither (dh_sample_bf16_nucleus).
+    repetition_penalty (in [1/8, 8]), frequency_penalty and presence_penalty (in [-8, 8]; "Penalties" of the header; they need start): the
+    pick is the same call's pick on a copy of the row in which the column of every id in tokens[u, start[u]:length[u]] holds its adjusted
+    value; logits is not written, and the log-probabilities and alternatives stay the raw row's.  None, 1.0 and 0.0 are off
+    (dh_sample_bf16_penalty)."""
     from .nucleus import check_nucleus
     top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
@@ -440,14 +461,17 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     st_ptr = _stop_arg(stop, vocab, logits.device)
     if st_ptr is not None and stop.sequences and start is None:
         raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
-    if st_ptr is not None and not no_repeat_ngram:
+    pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tokens.size(1), vocab, k)
+    if (st_ptr is not None or pen is not None) and not no_repeat_ngram:
         ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
     else:
         ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
             0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
             _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if top_p < 1.0 or min_p > 0.0:
+    if pen is not None:
+        check(_lib.load().dh_sample_bf16_penalty(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen))
+    elif top_p < 1.0 or min_p > 0.0:
         check(_lib.load().dh_sample_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
     elif st_ptr is not None:
         check(_lib.load().dh_sample_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
@@ -464,12 +488,14 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
                 eos_id: Optional[int] = None, seed: int = 0, logprobs: Optional[torch.Tensor] = None,
                 top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
                 no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
-                min_p: Optional[float] = None) -> None:
+                min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+                presence_penalty: Optional[float] = None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
     in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
     (dh_sample_rows_bf16_mask).  no_repeat_ngram, start: as in sample(), one entry of start per SEQUENCE; start None is
     limit - max_new_tokens (dh_sample_rows_bf16_ngram).  stop: as in sample(); start None is limit - max_new_tokens here too
-    (dh_sample_rows_bf16_stop).  top_p, min_p: as in sample() (dh_sample_rows_bf16_nucleus)."""
+    (dh_sample_rows_bf16_stop).  top_p, min_p: as in sample() (dh_sample_rows_bf16_nucleus).  repetition_penalty, frequency_penalty,
+    presence_penalty: as in sample(), start included (dh_sample_rows_bf16_penalty)."""
     from .nucleus import check_nucleus
     top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
@@ -482,14 +508,17 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
     m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
     st_ptr = _stop_arg(stop, vocab, logits.device)
-    if st_ptr is not None and not no_repeat_ngram:
+    pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tokens.size(1), vocab, k)
+    if (st_ptr is not None or pen is not None) and not no_repeat_ngram:
         ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
     else:
         ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=True)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
             k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if top_p < 1.0 or min_p > 0.0:
+    if pen is not None:
+        check(_lib.load().dh_sample_rows_bf16_penalty(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen))
+    elif top_p < 1.0 or min_p > 0.0:
         check(_lib.load().dh_sample_rows_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
     elif st_ptr is not None:
         check(_lib.load().dh_sample_rows_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))

@@ -33,7 +33,8 @@ typedef uint16_t dh_bf16;
  * dh_beam_select_bf16_mask and dh_engine_set_token_mask (token masks); dh_sample_bf16_ngram, dh_sample_rows_bf16_ngram and
  * dh_engine_set_no_repeat_ngram (no-repeat n-grams); dh_sample_bf16_stop, dh_sample_rows_bf16_stop, dh_beam_select_bf16_stop and
  * dh_engine_set_stop (stop conditions); dh_sample_bf16_nucleus, dh_sample_rows_bf16_nucleus and dh_engine_set_nucleus (nucleus
- * and min-p sampling); dh_engine_fork_slots (sampled candidates). */
+ * and min-p sampling); dh_engine_fork_slots (sampled candidates); dh_sample_bf16_penalty, dh_sample_rows_bf16_penalty and
+ * dh_engine_set_penalties (penalties). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -633,6 +634,54 @@ int dh_sample_rows_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* token
                                 const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
                                 float top_p, float min_p);
 
+/* Penalties (the "repetition_penalty" of the Hugging Face stacks, the "frequency_penalty" and "presence_penalty" of the OpenAI-style
+ * servers): value controls that make a token less likely because the sequence has already produced it.  ONE definition for every entry
+ * below.  The parameters are per call:
+ *   repetition = theta, finite, in [1/8, 8]; 1 = off.
+ *   frequency = alpha_f and presence = alpha_p, finite, in [-8, 8]; 0 = off.
+ * All three off is the call it always was: nothing is set and the kernels are the ones without a penalty.
+ * The history of sequence u at a pick is H = tokens[u, start[u] : length[u]], the tokens it has generated; the prompt is excluded, for the
+ * reason no_repeat_ngram excludes it (a correction copies its prompt).  c_t is the number of times id t occurs in H.
+ * The pick is, bit for bit, the existing pick — the same temperature, top_k, top_p, min_p, mask, n-gram ban, seed, step and row — on a
+ * copy of the logits row in which every column t with c_t > 0 and 0 <= t < vocab holds a_t; every other column is unchanged:
+ *   x   = fp32(row[t])                       (bf16 widened)
+ *   y   = x < 0 ? fl32(x * theta) : fl32(x / theta)   (the HF rule; NaN and +-0 take the division; IEEE division)
+ *   p   = fl32(alpha_f * (float)c_t)
+ *   z   = fl32(fl32(y - p) - alpha_p)        (three separately rounded fp32 operations: no FMA contraction)
+ *   a_t = bf16 round-to-nearest-even of z
+ *   Temperature is applied afterwards, by the sampler's l = bf16(a / temperature): the double rounding is part of the definition.
+ *   Masks and bans: a column the mask disallows or the n-gram ban removes is -inf whatever a_t is; the ban's "everything banned"
+ *     fallback works on bits and is untouched.
+ *   Log-probabilities and alternatives stay the raw row's, as under every other control.  Stop conditions never change a pick.
+ *   The prefill's first pick has an empty history: it is the plain pick.
+ *   Verify steps (a position's history would have to include the launch's own picks) and beam steps (a beam's history lives on the
+ *     host) take no penalty: dh_engine_decode_spec and dh_engine_decode_beam refuse while penalties are set.
+ *   The logits buffer is read only.  The sequence's block finds the distinct ids of H and their counts with integer LDS atomics (exact
+ *     in any order), computes one a_t per distinct id, and every read of the row that feeds the pick takes an overridden column from
+ *     LDS (sampling.hip).  The tables are static: a call whose history could pass DH_MAX_PENALTY_HISTORY tokens (tok_ld above it), or
+ *     whose vocab is above 131072, is refused before anything is launched. */
+#define DH_MAX_PENALTY_HISTORY 2048
+typedef struct dh_penalty_args {
+    float repetition;           /* theta: 1 = off */
+    float frequency;            /* alpha_f: 0 = off */
+    float presence;             /* alpha_p: 0 = off */
+} dh_penalty_args;
+
+/* dh_sample_bf16_nucleus / dh_sample_rows_bf16_nucleus with the penalties; mask, ngram, stop, top_p and min_p stay nullable / 0 / 1 / 0,
+ * and `penalties` null or all off makes each the entry it extends.  `start` is needed when a penalty is on.  Refused without a launch,
+ * with the value in the message: a parameter outside its range or NaN, a penalty without start, tok_ld above DH_MAX_PENALTY_HISTORY. */
+int dh_sample_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                           int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                           uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                           const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                           float top_p, float min_p, const dh_penalty_args* penalties);
+int dh_sample_rows_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                float top_p, float min_p, const dh_penalty_args* penalties);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -942,6 +991,13 @@ int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const int32_t* st
  * with them unset, or with top_k == 1, a decode call runs the graphs it always ran.  Verify and beam steps take neither.  Refused like
  * dh_sample_bf16_nucleus. */
 int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p);
+/* The penalties (see "Penalties" above; null or all off clears them, the default) for later dh_engine_decode and dh_engine_decode_rows
+ * calls, with any top_k.  `start` ([n_seq] int32 on the device, needed when a penalty is on) is the array dh_engine_set_no_repeat_ngram
+ * and dh_engine_set_stop take and holds the same numbers; the caller keeps it alive while set.  The values and `start` are part of the
+ * captured step's key: with them unset a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec and
+ * dh_engine_decode_beam refuse, and a decode call with tok_ld above DH_MAX_PENALTY_HISTORY is refused before anything is launched.
+ * Refused like dh_sample_bf16_penalty. */
+int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* penalties, const int32_t* start);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
