@@ -124,6 +124,8 @@ const TuningRow TUNING[] = {
     {40, &g_attn_chain, BOOL, 0, 0, 0},
     {41, &g_finish_hoist_rows, RANGE, -1, NO_MAX, 0},   // -1: the built-in crossover
     {42, &g_prefill_wpb, ONE_OF, 0, 2, 4},
+    {43, &g_finish_rows_min, RANGE, -1, NO_MAX, 0},     // -1: the built-in crossover
+    {44, &g_finish_rpb, RANGE, 0, 64, 0},               // 0: the built-in count
 };
 
 }  // namespace

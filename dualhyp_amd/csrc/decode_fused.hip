@@ -16,6 +16,11 @@ int g_attn_chain = 1;
 // dh_set_tuning 41: finish_norm requests its independent loads ahead of the hand-over barrier from this many rows on
 // (0: never).  Chosen by the row count only.  Default and the sweep behind it: FINISH_HOIST_ROWS below.
 int g_finish_hoist_rows = -1;
+// dh_set_tuning 43: finish_norm_rows_kernel (several rows per block, loads a row ahead, lora_b in registers) from this many rows
+// on; 0: finish_norm_kernel at every row count (the A/B arm; both give the same bits); -1: FINISH_ROWS_MIN below.
+int g_finish_rows_min = -1;
+// dh_set_tuning 44: rows per block of finish_norm_rows_kernel (0: FINISH_RPB below).
+int g_finish_rpb = 0;
 
 #ifdef DH_ATTN_STAMPS   // diagnostic build only (tools/probe_attn_chain.py): 100 MHz timestamps of thread 0 of each block
 __device__ unsigned long long g_attn_stamps[4096 * 8];
@@ -968,6 +973,190 @@ __global__ __launch_bounds__(256) void finish_norm_kernel(const float* __restric
     }
 }
 
+// The same finish for SEVERAL consecutive rows per block (grid = ceil(rows / rpb)), built so that no load waits behind a
+// barrier.  A thread keeps its column chunk of finish_norm_kernel (columns (tid + 256 i) * 8 ..), so a row's `ss` order is
+// that kernel's, and every statement of the arithmetic is that kernel's too; what changes is when the bytes are asked for:
+//   - what a thread needs for its first chunk of row r + 1 (x·A^T partials, the first PF partials, the residual) is
+//     requested before the arithmetic of row r, and rows 0 and 1 of a block are both in flight from the start;
+//   - its 8 x 32 B of lora_b and its norm weights are loaded ONCE per block and stay in registers (64 + 4 VGPRs) over
+//     the block's rows: not one trip to L2 per row behind the hand-over barrier;
+//   - x·A^T of row r + 1 is handed over (sXa, double buffered) in front of the ONE barrier of row r, the one of its
+//     reduction (sRed, double buffered): a row costs one barrier, and that barrier waits for LDS only.
+// Chunks i >= 1 (d > 2048) and partials beyond PF are requested where they are used, as in finish_norm_kernel.
+// PF: partials requested a row ahead (1, 4 or 8); XP >= n_part: x·A^T partials threads 0..15 hold a row ahead.  The dispatcher
+// takes the smallest PF that covers n_part, but 4 for more than 4 partials with LoRA (8 would not fit in 256 VGPRs beside lora_b).
+template <int MAXC, int PF, int XP, bool LORA>
+__global__ __launch_bounds__(256) void finish_norm_rows_kernel(const float* __restrict__ h32, int n_part, int pairs, int rows, int ldh,
+                                                               const bf16_t* __restrict__ lora_b, float lora_scale,
+                                                               const bf16_t* __restrict__ x_resid,
+                                                               const bf16_t* __restrict__ w_norm, bf16_t* __restrict__ x_out,
+                                                               bf16_t* __restrict__ xn_out, int d, float eps,
+                                                               const uint8_t* __restrict__ row_tail, int rpb) {
+    __shared__ float sXa[2][16];
+    __shared__ float sRed[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = blockIdx.x * rpb, nrow = min(rpb, rows - row0);
+    const size_t pstride = (size_t)rows * ldh;
+    const bool own = tid * 8 < d;                // this thread has a first chunk
+    struct Pre { float xa[XP]; float4 a0[PF], a1[PF]; uint4 xr; };
+    auto request = [&](Pre& P, int row) __attribute__((always_inline)) {
+        const float* hrow = h32 + (size_t)row * ldh;
+        if (LORA && tid < 16) {
+#pragma unroll
+            for (int p = 0; p < XP; ++p) P.xa[p] = p < n_part ? hrow[p * pstride + d + tid] : 0.f;
+        }
+        if (own) {
+            const int c0 = tid * 8;
+#pragma unroll
+            for (int q = 0; q < PF; ++q) {
+                const int p = q < n_part ? q : 0;
+                P.a0[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0);
+                P.a1[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0 + 4);
+            }
+            P.xr = *reinterpret_cast<const uint4*>(x_resid + (size_t)row * d + c0);
+        }
+    };
+    auto xa_sum = [&](const Pre& P) __attribute__((always_inline)) {       // finish_norm_kernel's, without its trailing + 0.f terms
+        float s = 0.f;
+        if (pairs) {
+#pragma unroll
+            for (int p = 0; p < XP; p += 2) s += P.xa[p] + (p + 1 < XP ? P.xa[p + 1] : 0.f);
+        } else {
+#pragma unroll
+            for (int p = 0; p < XP; ++p) s += P.xa[p];
+        }
+        return rbf(s);
+    };
+    // G loaded partials p0 .. p0 + G - 1 into acc, in finish_norm_kernel's order
+    auto add_group = [&](float (&acc)[8], const float4* a0, const float4* a1, int p0, auto G_) __attribute__((always_inline)) {
+        constexpr int G = decltype(G_)::value;
+        if (pairs) {      // leaves: adjacent pairs first (a missing partner counts as 0), pair sums in order
+#pragma unroll
+            for (int q = 0; q < G; q += 2) {
+                if (p0 + q < n_part) {
+                    const bool two = q + 1 < G && p0 + q + 1 < n_part;
+                    const float4 b0 = two ? a0[q + 1 < G ? q + 1 : q] : float4{0.f, 0.f, 0.f, 0.f}, b1 = two ? a1[q + 1 < G ? q + 1 : q] : float4{0.f, 0.f, 0.f, 0.f};
+                    acc[0] += a0[q].x + b0.x; acc[1] += a0[q].y + b0.y; acc[2] += a0[q].z + b0.z; acc[3] += a0[q].w + b0.w;
+                    acc[4] += a1[q].x + b1.x; acc[5] += a1[q].y + b1.y; acc[6] += a1[q].z + b1.z; acc[7] += a1[q].w + b1.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                if (p0 + q < n_part) {
+                    acc[0] += a0[q].x; acc[1] += a0[q].y; acc[2] += a0[q].z; acc[3] += a0[q].w;
+                    acc[4] += a1[q].x; acc[5] += a1[q].y; acc[6] += a1[q].z; acc[7] += a1[q].w;
+                }
+            }
+        }
+    };
+
+    Pre pa, pb;
+    request(pa, row0);
+    if (nrow > 1) request(pb, row0 + 1);
+    uint4 bq[LORA ? 8 : 1][2];                   // lora_b rows of the first chunk's 8 columns
+    uint4 hwu = {};
+    if (own) {
+        if (LORA) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const uint4* b4 = reinterpret_cast<const uint4*>(lora_b + (size_t)(tid * 8 + e) * 16);
+                bq[e][0] = b4[0];
+                bq[e][1] = b4[1];
+            }
+        }
+        hwu = *reinterpret_cast<const uint4*>(w_norm + tid * 8);
+    }
+    if (LORA && tid < 16) sXa[0][tid] = xa_sum(pa);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    // row row0 + k from P; Q: row k + 1 (requested already), refilled with row k + 2 once it has been handed on
+    auto do_row = [&](Pre& P, Pre& Q, int k) __attribute__((always_inline)) {
+        const int row = row0 + k, par = k & 1;
+        const float* hrow = h32 + (size_t)row * ldh;
+        const bool tail = row_tail != nullptr && row_tail[row] != 0;      // asked for here, used behind the barrier
+        float v[MAXC][8];
+        float ss = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXC; ++i) {
+            const int c0 = (tid + i * 256) * 8;
+            if (c0 < d) {
+                float acc[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+                if (i == 0) add_group(acc, P.a0, P.a1, 0, std::integral_constant<int, PF>{});
+                // partials in groups of 4: 8 independent 16-B loads in flight before the adds
+                for (int p0 = i == 0 ? PF : 0; p0 < n_part; p0 += 4) {
+                    float4 a0[4], a1[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int p = p0 + q < n_part ? p0 + q : p0;
+                        a0[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0);
+                        a1[q] = *reinterpret_cast<const float4*>(hrow + p * pstride + c0 + 4);
+                    }
+                    add_group(acc, a0, a1, p0, std::integral_constant<int, 4>{});
+                }
+                const uint4 xr = i == 0 ? P.xr : *reinterpret_cast<const uint4*>(x_resid + (size_t)row * d + c0);
+                const bf16_t* xp = reinterpret_cast<const bf16_t*>(&xr);
+                uint4 xo;
+                bf16_t* xop = reinterpret_cast<bf16_t*>(&xo);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float o = rbf(acc[e]);
+                    if (LORA) {
+                        const uint4* b4 = reinterpret_cast<const uint4*>(lora_b + (size_t)(c0 + e) * 16);
+                        float l = 0.f;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            uint4 bv = i == 0 ? bq[e][h] : b4[h];
+                            // keeps the block's copy packed: without it the compiler widens all 128 values to fp32 once per block (+64 VGPRs)
+                            if (i == 0) asm volatile("" : "+v"(bv.x), "+v"(bv.y), "+v"(bv.z), "+v"(bv.w));
+                            const bf16_t* bp = reinterpret_cast<const bf16_t*>(&bv);
+#pragma unroll
+                            for (int kk = 0; kk < 8; ++kk) l = fmaf(sXa[par][h * 8 + kk], bf2f(bp[kk]), l);
+                        }
+                        o = rbf(o + rbf(rbf(l) * lora_scale));
+                    }
+                    xop[e] = f2bf(bf2f(xp[e]) + o);
+                    v[i][e] = bf2f(xop[e]);
+                    ss += rbf(v[i][e] * v[i][e]);
+                }
+                *reinterpret_cast<uint4*>(x_out + (size_t)row * d + c0) = xo;
+            }
+        }
+        if (k + 2 < nrow) request(P, row + 2);      // P's registers are free: its row is in v
+        ss = wave_sum(ss);
+        if (lane == 0) sRed[par][wave] = ss;
+        if (LORA && k + 1 < nrow && tid < 16) sXa[par ^ 1][tid] = xa_sum(Q);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        ss = sRed[par][0] + sRed[par][1] + sRed[par][2] + sRed[par][3];
+        const float ms = rbf(ss / (float)d);
+        const float t = rbf(ms + eps);
+        const float r = tail ? rbf(1.0f / rbf(sqrtf(t))) : rbf(1.0f / sqrtf(t));
+#pragma unroll
+        for (int i = 0; i < MAXC; ++i) {
+            const int c0 = (tid + i * 256) * 8;
+            if (c0 < d) {
+                const uint4 wu = i == 0 ? hwu : *reinterpret_cast<const uint4*>(w_norm + c0);
+                const bf16_t* wp = reinterpret_cast<const bf16_t*>(&wu);
+                uint4 o;
+                bf16_t* op = reinterpret_cast<bf16_t*>(&o);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) op[e] = f2bf(bf2f(wp[e]) * rbf(v[i][e] * r));
+                *reinterpret_cast<uint4*>(xn_out + (size_t)row * d + c0) = o;
+            }
+        }
+    };
+    for (int k = 0; k < nrow; k += 2) {
+        do_row(pa, pb, k);
+        if (k + 1 < nrow) do_row(pb, pa, k + 1);
+    }
+}
+
 }  // namespace
 
 extern "C" int dh_attn_decode_fused_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
@@ -1088,6 +1277,20 @@ extern "C" int dh_attn_verify_fused_bf16(const float* qkv32, int n_part, int pai
 //   640 rows  16.0 | 15.8   12.3 | 11.8   12.0 | 11.8
 // No difference beyond the spread at 32 and 64 rows; ahead in all three shapes from 128 rows on.
 constexpr int FINISH_HOIST_ROWS = 128;
+// finish_norm_rows_kernel from this many rows on (0: never), FINISH_RPB rows per block.  tools/sweep_finish.py, d 2048, us per launch,
+// finish_norm_kernel (the faster of loads behind | ahead) against 2 / 3 / 4 rows per block, three alternating repeats, spread <= 0.2 us:
+//                 4 pair sums + LoRA          6 pair sums               1 partial + LoRA           1 partial
+//    32 rows    4.9 |  8.0 10.5 12.8      3.2 |  5.1  6.6  8.1       4.7 |  7.2  9.3 11.2      2.9 | 3.6 4.4 5.2
+//   128 rows    5.2 |  8.2 11.1 13.0      3.4 |  5.2  7.0  8.3       4.9 |  7.3  9.4 11.3      3.1 | 3.6 4.5 5.3
+//   640 rows   11.7 | 13.8 13.2 15.8      8.4 | 10.1 10.3 11.1       9.6 | 10.8 10.3 12.2      4.5 | 4.8 5.2 6.0
+//  2048 rows   31.4 | 27.8 29.3 25.3     24.0 | 25.0 26.0 24.1      22.5 | 20.7 21.2 18.3      8.6 | 9.0 9.2 9.1
+// Half the blocks with twice the rows each do not hide more latency than the co-resident one-row blocks do up to 640 rows: behind at
+// every shape there.  What the rows kernel saves is lora_b: a thread's 8 x 32 B sit 256 B apart from its neighbour's, 64 cache lines
+// per load instruction, and finish_norm_kernel pays that once per row (LoRA costs it 1.8 us at 128 rows, 5.4 at 640, 14 at 2048);
+// four rows per block pay it once per four rows.  At 2048 rows, where the partial-sum GEMMs hand over one partial (g_chain_min_rows), a
+// layer's two launches take 22.5 + 8.6 against 18.3 + 9.1 us: ahead by 3.7 us, on from there.  MEASUREMENTS.md has the whole table.
+constexpr int FINISH_ROWS_MIN = 2048;
+constexpr int FINISH_RPB = 4;
 
 extern "C" int dh_finish_norm_bf16(const float* h32, int n_part, int pairs, int rows, int d, int n_ext, const dh_bf16* lora_b,
                                    float lora_scale, const dh_bf16* x_resid, const dh_bf16* w_norm, dh_bf16* x_out,
@@ -1106,6 +1309,30 @@ extern "C" int dh_finish_norm_bf16(const float* h32, int n_part, int pairs, int 
         else hipLaunchKernelGGL((finish_norm_kernel<MAXC, false>), grid, block, 0, s, h32, n_part, pairs, rows, ldh, lora_b,       \
                                 lora_scale, x_resid, w_norm, x_out, xn_out, d, eps, row_tail);                        \
     } while (0)
+    const int multi_rows = g_finish_rows_min >= 0 ? g_finish_rows_min : FINISH_ROWS_MIN;
+    if (multi_rows > 0 && rows >= multi_rows) {                   // by the row count only, never by how the rows are packed
+        const int rpb = g_finish_rpb > 0 ? g_finish_rpb : FINISH_RPB;
+        dim3 mgrid((rows + rpb - 1) / rpb);
+#define LAUNCH_ROWS(MAXC, PF, XP, LORA)                                                                                  \
+        hipLaunchKernelGGL((finish_norm_rows_kernel<MAXC, PF, XP, LORA>), mgrid, block, 0, s, h32, n_part, pairs, rows, ldh, lora_b,  \
+                           lora_scale, x_resid, w_norm, x_out, xn_out, d, eps, row_tail, rpb)
+#define LAUNCH_MAXC(MAXC) do {                                                                                        \
+        if (lora_b != nullptr) {                                                                                      \
+            if (n_part <= 1) LAUNCH_ROWS(MAXC, 1, 1, true);                                                           \
+            else if (n_part <= 4) LAUNCH_ROWS(MAXC, 4, 4, true);                                                      \
+            else LAUNCH_ROWS(MAXC, 4, MAXP, true);                                                                    \
+        } else if (n_part <= 1) LAUNCH_ROWS(MAXC, 1, 1, false);                                                       \
+        else if (n_part <= 4) LAUNCH_ROWS(MAXC, 4, 1, false);                                                         \
+        else LAUNCH_ROWS(MAXC, 8, 1, false);                                                                          \
+    } while (0)
+        if (d <= 2048) LAUNCH_MAXC(1);
+        else if (d <= 4096) LAUNCH_MAXC(2);
+        else LAUNCH_MAXC(4);
+#undef LAUNCH_MAXC
+#undef LAUNCH_ROWS
+        DH_LAUNCH_CHECK();
+        return 0;
+    }
     const int hoist_rows = g_finish_hoist_rows >= 0 ? g_finish_hoist_rows : FINISH_HOIST_ROWS;
     const bool hoist = hoist_rows > 0 && rows >= hoist_rows;     // by the row count only, never by how the rows are packed
     if (d <= 2048) { LAUNCH(1); }

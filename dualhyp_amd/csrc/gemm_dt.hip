@@ -52,14 +52,20 @@ struct DtArgs {
 // WN 4 (SwiGLU at >= 256 rows): 8 waves, 256 W rows (128 fc_1/fc_2 pairs) per block, 3 stages of 48 KiB — half the
 // blocks, each moving 1.5x the bytes per stage for 2x the MFMA work (a block's time is set by its stage count, not by
 // the bytes: ~1 us per stage of LDS-DMA latency), and 640 rows become one round of 220 blocks instead of 440.
-template <int MODE, int NSTAGE, int WN = 2>
-__global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
+// WI: 16-row fragments of W per wave (a wave's tile is WI*16 (n) x 64 (m)).  4 everywhere but in gemm_dt_chain_kernel below, whose
+// 128 x 128 tile sits on 8 waves of 32 x 64 (WI 2): each accumulator set is 32 registers instead of 64.
+template <int MODE, int NSTAGE, int WN, int WI>
+__device__ __forceinline__ void gemm_dt_body(const DtArgs& a) {
+    static_assert(WI == 4 || (WI == 2 && MODE == 0 && !(WN == 4 && NSTAGE == 3)), "the 32 x 64 wave tile serves MODE 0 on the plain ring");
     constexpr int STAGE = stage_bytes<WN>();
     constexpr int ASZ = WN * 64 * BKD * 2;                        // bytes of the W tile of a stage
-    constexpr int NB = 16 / (2 * WN);                             // x groups (8 rows x 128 B) staged per wave
-    constexpr int PER = 4 + NB;                                   // LDS-DMA requests per wave and stage
+    constexpr int NWV = WN * 8 / WI;                              // waves: WN*4/WI along n x 2 along m
+    constexpr int NA = WI;                                        // W groups (8 rows x 128 B) staged per wave: 8 WN / NWV
+    constexpr int NB = 16 / NWV;                                  // x groups staged per wave
+    constexpr int PER = NA + NB;                                  // LDS-DMA requests per wave and stage
     extern __shared__ __attribute__((aligned(16))) char smem[];   // NSTAGE stages
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = WI == 2 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;   // WI 2: kept scalar, the tile has no VGPR to spare
     const int wn = wave >> 1, wm = wave & 1;
     const int frow = lane & 15, kg = lane >> 4;
     const int m_tiles = (a.M + TB - 1) / TB;
@@ -77,11 +83,11 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
     const int n0 = MODE == 1 ? tn * (WN * 32) : tn * (WN * 64);     // first output column of the block
 
     // ---- staging sources: 8 WN + 16 one-KiB groups (8 rows of 128 B) per stage, 4 + NB per wave
-    const bf16_t* srcA[4];
+    const bf16_t* srcA[NA];
     const bf16_t* srcB[NB];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int R = wave * 4 + j;
+    for (int j = 0; j < NA; ++j) {
+        const int R = wave * NA + j;
         const int row = R * 8 + (lane >> 3);
         const int chunk = (lane & 7) ^ swz7(row);
         const bf16_t* base = a.w;
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
         char* sA = smem + (kt % NSTAGE) * STAGE;
         char* sB = sA + ASZ;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) glds16(srcA[j] + kt * BKD, sA + (wave * 4 + j) * 1024);
+        for (int j = 0; j < NA; ++j) glds16(srcA[j] + kt * BKD, sA + (wave * NA + j) * 1024);
 #pragma unroll
         for (int j = 0; j < NB; ++j) glds16(srcB[j] + kt * BKD, sB + (wave * NB + j) * 1024);
     };
@@ -123,19 +129,19 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
 
-    f32x4 cur[4][4], tot[4][4];
+    f32x4 cur[WI][4], tot[WI][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < WI; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             cur[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     const int sw = swz7(frow);
-    const int offA = (wn * 64 + frow) * 128, offB = (wm * 64 + frow) * 128;
+    const int offA = (wn * (WI * 16) + frow) * 128, offB = (wm * 64 + frow) * 128;
     const int nk = MODE == 4 ? min(a.split_kt, a.K / BKD - ky * a.split_kt) : a.K / BKD;
     const int seg_kt = a.seg / 2;       // stages per chain segment
-    f32x4 pairacc[MODE == 0 ? 4 : 1][MODE == 0 ? 4 : 1];   // MODE 0: the open pair's first slice
+    f32x4 pairacc[MODE == 0 ? WI : 1][MODE == 0 ? 4 : 1];   // MODE 0: the open pair's first slice
     int seg_idx = 0;
 
     auto fold_segment = [&](bool last) __attribute__((always_inline)) {     // end of a chain segment: fold it in, in order
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
             // index order; an unpaired last slice is added on its own
             const bool second = seg_idx & 1;
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < WI; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (second) tot[i][j] += pairacc[i][j] + cur[i][j];
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
             ++seg_idx;
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < WI; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     tot[i][j] += cur[i][j];
@@ -244,6 +250,18 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int co = ((ks * 4 + kg) ^ sw) << 4;
+            if constexpr (WI == 2) {
+                // x fragments one at a time (12 fragment registers live, not 24): an accumulator still sees its k-steps in order
+                bf16x8 fa[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(sA + offA + i * 2048 + co);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bf16x8 fb = *reinterpret_cast<const bf16x8*>(sB + offB + j * 2048 + co);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) cur[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, cur[i][j], 0, 0, 0);
+                }
+            } else {
             bf16x8 fa[4], fb[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -255,6 +273,7 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     cur[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], cur[i][j], 0, 0, 0);
+            }
         }
         if (++in_seg == seg_kt || kt + 1 == nk) {
             in_seg = 0;
@@ -270,12 +289,12 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
     }
 
     // ---------------------------------------------------------------- epilogue
-    // tot[i][j][r]: LDS row of W = wn*64 + i*16 + 4*kg + r ; m = m0 + wm*64 + j*16 + frow
+    // tot[i][j][r]: LDS row of W = wn*(WI*16) + i*16 + 4*kg + r ; m = m0 + wm*64 + j*16 + frow
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int m = m0 + wm * 64 + j * 16 + frow;
         if (m >= a.M) continue;
-        if (MODE == 1) {
+        if constexpr (MODE == 1) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int n = n0 + wn * 32 + i * 16 + kg * 4;
@@ -290,8 +309,8 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = n0 + wn * 64 + i * 16 + kg * 4;
+            for (int i = 0; i < WI; ++i) {
+                const int n = n0 + wn * (WI * 16) + i * 16 + kg * 4;
                 if (n >= a.N) continue;
                 if (MODE == 0 || MODE == 4) {
                     float* yo = (float*)a.y + (MODE == 4 ? (size_t)ky * a.M * a.N : 0);
@@ -319,6 +338,25 @@ __global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) {
             }
         }
     }
+}
+
+template <int MODE, int NSTAGE, int WN = 2>
+__global__ __launch_bounds__(WN * 128) void gemm_dt_kernel(DtArgs a) { gemm_dt_body<MODE, NSTAGE, WN, 4>(a); }
+
+// MODE 0 on the register-lean tile: 128 x 128 on 8 waves of 32 (n) x 64 (m).  Its three accumulator sets (cur, pairacc, tot)
+// are 3 x 32 registers beside 6 fragments, so four waves per SIMD fit: two blocks per CU with 2 stages (64 KiB of LDS each).
+// Same statements as every other instantiation: the same MFMA chains per accumulator, fold_segment in the family's order.
+template <int NSTAGE>
+__global__ __launch_bounds__(512, NSTAGE == 2 ? 4 : 2) void gemm_dt_chain_kernel(DtArgs a) { gemm_dt_body<0, NSTAGE, 2, 2>(a); }
+
+template <int NSTAGE>
+int launch_chain_n(const DtArgs& a, int blocks, hipStream_t s) {
+    constexpr int lds = NSTAGE * stage_bytes<2>();
+    DH_MAX_LDS_ONCE((gemm_dt_chain_kernel<NSTAGE>), lds);
+    dh_gemm_route(DH_ROUTE_CHAIN_TILED);
+    hipLaunchKernelGGL((gemm_dt_chain_kernel<NSTAGE>), dim3(blocks), dim3(512), lds, s, a);
+    DH_LAUNCH_CHECK();
+    return 0;
 }
 
 template <int MODE, int NSTAGE, int WN = 2>
@@ -356,17 +394,30 @@ int launch_dt(const DtArgs& a, hipStream_t s) {
 // with the rows: the crossover was near 768 rows in round 1; with round 2's K-sliced kernel it lies between 1024 and 2048.
 int g_dt_min_rows = 129;       // fused-epilogue decode GEMMs from this many rows on (dh_set_tuning key 6); the lm_head (N = 32000) already
                                // from 65: measured SwiGLU 24 (streaming) vs 32 us at 128 rows, 40 vs 32 at 130; lm_head 49 vs 39 at 96 rows
-// the one-launch total of the partial-sum GEMMs from this many rows on (dh_set_tuning key 7).  Round 3: OFF by default (1 << 30) — in the
-// family's pair order the kernel needs a third accumulator set (412 registers: one wave per SIMD, one block per CU) and a 2048-row
-// decode step takes 15.25 ms against 13.55 with the pair-sum kernel (round 2's two-set chain in slice order: 13.0).  Kept for the ABI.
-int g_chain_min_rows = 1 << 30;   //
-                               // (8.34 vs 8.53 ms per decode step), this kernel at 2048 (12.9 vs 14.6)
+// the one-launch total of the partial-sum GEMMs from this many rows on (dh_set_tuning key 7).  Round 3 switched it off (1 << 30): in the
+// family's pair order the kernel needs a third accumulator set (on 4 waves of 64 x 64: 412 registers, one wave per SIMD, one block per
+// CU) and a 2048-row decode step took 15.25 ms against 13.55 with the pair-sum kernel (round 2's two-set chain in slice order: 13.0).
+// The route now runs gemm_dt_chain_kernel, the same tile on 8 waves of 32 x 64 (cross-compile for gfx950, kernel-resource-usage):
+//   2 stages: .vgpr_count 126, .agpr_count 0, no VGPR or SGPR spill, no scratch, 4 waves per SIMD (two blocks per CU, 64 KiB of LDS each)
+//   4 stages: .vgpr_count 130, .agpr_count 0, no VGPR or SGPR spill, no scratch, 3 waves per SIMD allowed, one block (2 waves per SIMD) resident
+// tools/sweep_pairs.py --chain, us, producer + consumer (the attention launch at 544 keys, or finish_norm), pair sums | this route with
+// the stage count dh_chain_tiled picks, three alternating repeats, spread <= 0.8 us (1.6 on one qkv' + attention row):
+//   rows      qkv' + attention     proj' + finish_norm     mlp' + finish_norm      the three together
+//    640       89.2 |  94.1           28.6 | 34.8             30.2 |  59.5           148.0 | 188.4      (mlp' alone 22.8 | 54.6)
+//   1024      140.2 | 135.0           40.4 | 38.0             49.9 |  60.8           230.5 | 233.8
+//   1536      206.5 | 189.6           47.9 | 43.8             73.6 |  62.6           328.0 | 296.0
+//   2048      266.6 | 249.7           67.4 | 57.6             89.0 |  66.2           423.0 | 373.5
+// Ahead on the sum at 1536 and 2048 rows, behind at 1024 (mlp': a block walks K = 5632 in 88 stages however few rows there are).
+int g_chain_min_rows = 1536;
 
 // x·[w; w_ext]^T summed over the K-slices of `kps` k-steps in slice order: fp32 [M][n_main + n_ext]
 int dh_chain_tiled(const bf16_t* x, const bf16_t* w, const bf16_t* w_ext, float* y32, int M, int n_main, int n_ext, int K,
                    int kps, hipStream_t s) {
     DtArgs a{x, w, w_ext ? w_ext : w, y32, nullptr, nullptr, nullptr, M, n_main + n_ext, K, n_main, kps, 0, 0};
-    return launch_dt<0>(a, s);
+    const int blocks = cdiv(M, TB) * cdiv(a.N, TB);
+    // as launch_dt: two co-resident blocks on a short ring when the blocks go more than once round the CUs
+    const int stages = g_dt_stages ? g_dt_stages : (blocks > 256 ? 2 : 4);
+    return stages == 2 ? launch_chain_n<2>(a, blocks, s) : launch_chain_n<4>(a, blocks, s);
 }
 
 // The pair sums of the K-slices (kps k-steps each) of x·[w; w_ext]^T: fp32 [ceil(nslices / 2)][M][n_main + n_ext], one

@@ -13,5 +13,5 @@ extern int g_fp8_tile, g_fp8_gm;                                                
 extern int g_decode_tiled_rows, g_short_kps, g_fuse_qkv_rope, g_prune_last_layer;         // engine.hip
 extern int g_attn_bwd_dkdv_img, g_attn_bwd_dq_group;                                      // attention_bwd.hip
 extern int g_tn_mfma;                                                                     // train_kernels.hip
-extern int g_attn_chain, g_finish_hoist_rows;                                             // decode_fused.hip
+extern int g_attn_chain, g_finish_hoist_rows, g_finish_rows_min, g_finish_rpb;                                            // decode_fused.hip
 extern int g_prefill_wpb;                                                                 // attention.hip
