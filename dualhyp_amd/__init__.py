@@ -10,7 +10,7 @@ from .generate import generate, generate_batch, generate_stream, score_batch, be
 from .select import select  # noqa: F401
 from .utils import chunked_cross_entropy  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint, convert_hf_checkpoint  # noqa: F401
-from .quant import quantize_model_fp8  # noqa: F401
+from .quant import quantize_model_fp8, quantize_model_mxfp4  # noqa: F401
 from .stop import compile_stop, first_stop, finish_reasons, newline_ids  # noqa: F401
 
 __version__ = "0.1.0"

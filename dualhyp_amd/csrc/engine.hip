@@ -69,6 +69,7 @@ struct dh_engine {
     void* dec_work = nullptr;
     float* part32 = nullptr;                            // fp32 partial sums of the decode GEMMs
     bool fp8 = false;                                   // e4m3 weights + channel scales (csrc/fp8.hip)
+    bool mx4 = false;                                   // fp8 engine whose block weights are MXFP4 (csrc/mxfp4.hip; lm_head stays e4m3)
     uint8_t* xq = nullptr;                              // fp8 mode: quantised activations [max_tokens, max(d, I)]
     float* xscale = nullptr;                            // fp8 mode: their per-token scales [max_tokens]
     int32_t* h_stage = nullptr;                         // pinned staging for the metadata, carved by stage() below
@@ -468,6 +469,10 @@ inline int fp8_kernel(bool decode, int rows) { return decode && rows <= 128 ? 2 
 int linear_fp8(dh_engine* e, const bf16_t* w, const float* ws, bf16_t* y, int M, int N, int K, int epi, const bf16_t* w2,
                const float* w2s, const bf16_t* resid, hipStream_t s, bool timed) {
     TimeScope t(e, gemm_class(e), s, timed);
+    if (e->mx4)   // the block linears of an MXFP4 engine: w addresses nibbles, ws E8M0 bytes; same phase rule
+        return dh_linear_mxfp4_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), reinterpret_cast<const uint8_t*>(ws), y, M, N, K,
+                                  epi, reinterpret_cast<const uint8_t*>(w2), reinterpret_cast<const uint8_t*>(w2s), nullptr, nullptr,
+                                  resid, fp8_kernel(e->phase_decode, M), s);
     return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), ws, y, M, N, K, epi,
                             reinterpret_cast<const uint8_t*>(w2), w2s, nullptr, nullptr, resid, fp8_kernel(e->phase_decode, M), s);
 }
@@ -628,8 +633,11 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
             const SeqMeta m = seq_meta(e);
             {
                 TimeScope t(e, 1, s);
-                if ((rc = dh_linear_fp8_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w), W.attn_ws, e->part32,
-                                            n_tok, e->qkv_dim, d, s))) return rc;
+                if (e->mx4) rc = dh_linear_mxfp4_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w),
+                                                     reinterpret_cast<const uint8_t*>(W.attn_ws), e->part32, n_tok, e->qkv_dim, d, s);
+                else rc = dh_linear_fp8_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w), W.attn_ws, e->part32,
+                                            n_tok, e->qkv_dim, d, s);
+                if (rc) return rc;
             }
             TimeScope t(e, 3, s);
             if ((rc = dh_attn_decode_fused_bf16(e->part32, 1, 0, n_seq, e->qkv_dim, 0, nullptr, 0.f, e->qkv_dim, e->qkv_dim,
@@ -787,7 +795,7 @@ int alloc_row_ws(dh_engine* e, int rows) {
     return 0;
 }
 
-int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype) {
+int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype) {
     e->d = *desc;
     e->layers.assign(desc->h_layers, desc->h_layers + desc->n_layer);
     e->d.h_layers = nullptr;
@@ -803,6 +811,8 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
         DH_CHECK(desc->lm_head_ws != nullptr, "dh_engine_create: fp8 mode needs lm_head_ws");
         DH_CHECK(d % 128 == 0 && desc->intermediate % 128 == 0, "dh_engine_create: fp8 mode needs n_embd and intermediate %% 128 == 0");
     }
+    e->mx4 = weight_dtype == 1;
+    DH_CHECK(!e->mx4 || e->fp8, "dh_engine_create_q: MXFP4 weights (weight_dtype 1) need the block-scale pointers (attn_ws != NULL)");
     e->kv8 = kv_dtype == 1;
     DH_CHECK(!e->kv8 || e->fp8, "dh_engine_create_ex: an fp8 KV cache (kv_dtype 1) needs an fp8 engine (channel scales, attn_ws != NULL)");
     e->cache_layer_elems = (size_t)max_batch * G * s_max * hs;
@@ -1079,7 +1089,13 @@ extern "C" int dh_engine_create(const dh_model_desc* desc, int max_batch, int s_
 }
 
 extern "C" int dh_engine_create_ex(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, dh_engine** out) {
+    return dh_engine_create_q(desc, max_batch, s_max, max_tokens, kv_dtype, 0, out);
+}
+
+extern "C" int dh_engine_create_q(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype,
+                                  dh_engine** out) {
     DH_CHECK(desc && out, "dh_engine_create: null argument");
+    DH_CHECK(weight_dtype == 0 || weight_dtype == 1, "dh_engine_create_q: weight_dtype %d is neither 0 (as described) nor 1 (MXFP4)", weight_dtype);
     DH_CHECK(kv_dtype == 0 || kv_dtype == 1, "dh_engine_create_ex: kv_dtype %d is neither 0 (bf16) nor 1 (fp8)", kv_dtype);
     DH_CHECK(desc->head_size == 64 || desc->head_size == 96 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
     DH_CHECK(desc->n_head % desc->n_groups == 0, "dh_engine_create: n_head %% n_groups != 0");
@@ -1089,7 +1105,7 @@ extern "C" int dh_engine_create_ex(const dh_model_desc* desc, int max_batch, int
     DH_CHECK(max_batch > 0 && max_tokens >= max_batch, "dh_engine_create: bad batch/token capacity");
     DH_CHECK(desc->rope_cos && desc->rope_sin && desc->wte && desc->ln_f && desc->lm_head && desc->h_layers, "dh_engine_create: null weight pointer");
     dh_engine* e = new dh_engine();
-    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens, kv_dtype);
+    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens, kv_dtype, weight_dtype);
     if (rc) { dh_engine_destroy(e); return rc; }   // one cleanup path: nothing allocated so far leaks
     {
         std::lock_guard<std::mutex> lock(g_engines_mu);

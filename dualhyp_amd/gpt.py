@@ -295,6 +295,7 @@ class _Engine:
             return t.data_ptr()
 
         fp8 = bool(getattr(model, "fp8", False))
+        mx4 = fp8 and getattr(model, "weight_format", "") == "mxfp4"      # block weights MXFP4, lm_head e4m3 (quantize_model_mxfp4)
         self.kv_cache_dtype = getattr(model, "kv_cache_dtype", "bf16")
         if self.kv_cache_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_cache_dtype is 'bf16' or 'fp8', got {self.kv_cache_dtype!r}")
@@ -305,7 +306,7 @@ class _Engine:
             """bf16 weight, or the e4m3 bytes of a quantised layer (dualhyp_amd.quant)"""
             if not fp8:
                 return ptr(lin.weight.data)
-            t = lin.weight_fp8
+            t = lin.weight_mx4 if hasattr(lin, "weight_mx4") else lin.weight_fp8
             assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
             self.keep.append(t)
             return t.data_ptr()
@@ -313,6 +314,11 @@ class _Engine:
         def sptr(lin) -> Optional[int]:
             if not fp8:
                 return None
+            if hasattr(lin, "weight_mx4"):
+                t = lin.weight_mx4_scale       # E8M0 bytes behind the float pointer of dh_layer_weights (dh_engine_create_q)
+                assert mx4 and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+                self.keep.append(t)
+                return t.data_ptr()
             t = lin.weight_scale
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
             self.keep.append(t)
@@ -351,8 +357,8 @@ class _Engine:
         self.device = model.transformer.wte.weight.device
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(lib.dh_engine_create_ex(C.byref(desc), max_batch, s_max, max_tokens, int(self.kv_cache_dtype == "fp8"),
-                                               C.byref(handle)))
+            _lib.check(lib.dh_engine_create_q(C.byref(desc), max_batch, s_max, max_tokens, int(self.kv_cache_dtype == "fp8"),
+                                              int(mx4), C.byref(handle)))
         self.handle = handle
         self.lib = lib
         self.signature = model._param_signature()
@@ -679,7 +685,7 @@ class GPT(nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         # accept both 'x.linear.weight' (reference key) and our holder's 'x.linear.weight' (identical)
         if getattr(self, "fp8", False):
-            raise RuntimeError("load_state_dict: this model was quantised to fp8 (quantize_model_fp8): its bf16 weights no longer "
+            raise RuntimeError("load_state_dict: this model was quantised (quantize_model_fp8 / quantize_model_mxfp4): its bf16 weights no longer "
                                "exist; load the checkpoint into a fresh GPT and quantise that")
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
         self._drop_engine()

@@ -291,6 +291,9 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     if getattr(args, "quantize", "none") == "fp8":     # after the checkpoint: a quantised model has no bf16 weights to load into
         from .quant import quantize_model_fp8
         quantize_model_fp8(model, kv_cache=getattr(args, "kv_cache", "bf16"))
+    elif getattr(args, "quantize", "none") == "mxfp4":
+        from .quant import quantize_model_mxfp4
+        quantize_model_mxfp4(model, kv_cache=getattr(args, "kv_cache", "bf16"))
     fmt = args.prompts_format
     if args.dual_hypotheses and "Dual" not in fmt and fmt != "RelPrompt":
         print("Warning: dual hypotheses is enabled, but prompts format is not Dual.")
@@ -474,11 +477,14 @@ def build_parser():
                    help="D in 1..7: a decode step verifies D tokens drafted by prompt lookup (the correction mostly copies spans of its "
                         "prompt) next to each sequence's last one and keeps those the greedy arg-max confirms; --schedule batch only; "
                         "the predictions do not depend on it.  Default 0: off (acceptance on real corpora is unmeasured)")
-    p.add_argument("--quantize", choices=("none", "fp8"), default="none",
+    p.add_argument("--quantize", choices=("none", "fp8", "mxfp4"), default="none",
                    help="fp8: after the checkpoint is loaded, LoRA is merged and every dense weight becomes e4m3 rows with channel scales "
-                        "(quantize_model_fp8); activations are quantised per token and every product runs on the fp8 MFMA")
+                        "(quantize_model_fp8); activations are quantised per token and every product runs on the fp8 MFMA.  mxfp4: the "
+                        "same path with the five dense matrices of every block stored as OCP MXFP4 (blocks of 32 four-bit elements with "
+                        "one power-of-two scale byte, 4.25 bits per weight; quantize_model_mxfp4), lm_head stays e4m3; what does not go "
+                        "with fp8 does not go with it (its effect on a real corpus's WER is unmeasured)")
     p.add_argument("--kv_cache", choices=("bf16", "fp8"), default="bf16",
-                   help="fp8 (with --quantize fp8): cached K and V vectors are stored as e4m3 bytes with one power-of-two exponent each, "
+                   help="fp8 (with --quantize fp8 or mxfp4): cached K and V vectors are stored as e4m3 bytes with one power-of-two exponent each, "
                         "half the cache bytes per token; the predictions are those of attention over the rounded cache")
     p.add_argument("--logprobs", action="store_true",
                    help="every record of the predictions file gains sum_logprob and avg_logprob: the model's log-probability of the tokens "
@@ -569,10 +575,11 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     """The parsed flags, with the combinations that cannot run refused before anything is loaded."""
     p = build_parser()
     args = p.parse_args(argv)
-    if args.kv_cache == "fp8" and args.quantize != "fp8":
-        p.error("--kv_cache fp8 goes with --quantize fp8: the fp8 KV cache belongs to the fp8 serving path")
-    if args.speculate and args.quantize == "fp8":             # speculate.check_arguments refuses it too
-        p.error(f"--speculate {args.speculate} does not go with --quantize fp8: an fp8 engine has no verify step")
+    fp8_path = args.quantize in ("fp8", "mxfp4")             # mxfp4 is a weight format of the fp8 serving path: one engine, one set of refusals
+    if args.kv_cache == "fp8" and not fp8_path:
+        p.error("--kv_cache fp8 goes with --quantize fp8 (or mxfp4): the fp8 KV cache belongs to the fp8 serving path")
+    if args.speculate and fp8_path:                           # speculate.check_arguments refuses it too
+        p.error(f"--speculate {args.speculate} does not go with --quantize {args.quantize}: an fp8 engine has no verify step")
     if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet
         p.error(f"--speculate {args.speculate} goes with --schedule batch: continuous batching steps a row list one token at a time")
     if not 1 <= args.num_beams <= 4:
@@ -580,7 +587,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     if args.num_beams > 1:
         for on, flag, why in ((args.schedule == "continuous", "--schedule continuous", "continuous batching steps a row list one token at a time"),
                               (bool(args.speculate), f"--speculate {args.speculate}", "a verify step follows one greedy hypothesis"),
-                              (args.quantize == "fp8", "--quantize fp8", "an fp8 engine's step changes its GEMM kernel with the row count"),
+                              (fp8_path, f"--quantize {args.quantize}", "an fp8 engine's step changes its GEMM kernel with the row count"),
                               (args.share_prefix == "auto", "--share_prefix auto", "the beams' KV slots are forked from whole prompts"),
                               (bool(args.top_logprobs), f"--top_logprobs {args.top_logprobs}", "the records carry the beams instead")):
             if on:

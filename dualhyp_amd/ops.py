@@ -572,6 +572,32 @@ def linear_fp8(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scal
     return y
 
 
+def linear_mxfp4(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor, *, epilogue: int = EPI_PLAIN,
+                 w2q: Optional[torch.Tensor] = None, w2_scale: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                 bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, kernel: int = 0,
+                 out32: bool = False) -> torch.Tensor:
+    """bf16 [M, N] = epilogue((xq . dequant(W)^T) * x_scale[m]) with MXFP4 weights as dualhyp_amd.quant.pack_mxfp4 lays them out
+    (wq uint8 [N/16, K/128, 64, 16], w_scale uint8 [N/16, K/128, 64]); dh_linear_mxfp4_ex (kernel: 0 by row count, 1 tiled,
+    2 streaming).  out32: dh_linear_mxfp4_f32, the PLAIN streaming result as fp32."""
+    k = _Keep()
+    M, K = xq.shape
+    assert wq.dim() == 4 and wq.shape[2:] == (64, 16) and w_scale.shape == wq.shape[:3] and wq.size(1) * 128 == K
+    assert xq.dtype == torch.uint8 and wq.dtype == torch.uint8 and w_scale.dtype == torch.uint8
+    N = wq.size(0) * 16
+    if out32:
+        assert epilogue == EPI_PLAIN and resid is None and kernel in (0, 2)
+        y = torch.empty((M, N), dtype=torch.float32, device=xq.device)
+        check(_lib.load().dh_linear_mxfp4_f32(k(xq, torch.uint8, "xq"), k(x_scale, torch.float32, "x_scale"), k(wq, torch.uint8, "wq"),
+                                              k(w_scale, torch.uint8, "w_scale"), _p(y), M, N, K, _stream()))
+        return y
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    check(_lib.load().dh_linear_mxfp4_ex(k(xq, torch.uint8, "xq"), k(x_scale, torch.float32, "x_scale"), k(wq, torch.uint8, "wq"),
+                                         k(w_scale, torch.uint8, "w_scale"), _p(y), M, N, K, epilogue, k(w2q, torch.uint8, "w2q"),
+                                         k(w2_scale, torch.uint8, "w2_scale"), k(scale, name="scale"), k(bias, name="bias"),
+                                         k(resid, name="resid"), int(kernel), _stream()))
+    return y
+
+
 # ------------------------------------------------------------------------------------------ fp8 KV cache
 def kv8_alloc(n_slots: int, n_groups: int, s_max: int, hs: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """A zeroed fp8 KV cache: (k8 uint8 [slot, group, s_max, hs], v8 uint8 [slot, group, hs, s_max], k_exp, v_exp int8

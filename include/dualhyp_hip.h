@@ -711,6 +711,40 @@ int dh_linear_fp8_ex(const uint8_t* xq, const float* x_scale, const uint8_t* wq,
 int dh_linear_fp8_f32(const uint8_t* xq, const float* x_scale, const uint8_t* wq, const float* w_scale, float* y32, int M,
                       int N, int K, void* stream);
 
+/* ------------------------------------------------------------------ MXFP4 weights (csrc/mxfp4.hip)
+ * A third weight format of the fp8 serving path: activations stay e4m3 rows with one fp32 scale per token (the two
+ * quantisation kernels above); the weights are OCP MX v1.0 MXFP4.
+ * Format.  A weight row W[n, :] (K % 128 == 0) is cut into blocks of 32 consecutive k.  Block b has one E8M0 byte s with
+ * value 2^(s - 127) and 32 e2m1 elements: 4 bits each, bit 3 the sign, bits 2..1 the exponent, bit 0 the mantissa; codes
+ * 0..7 are the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6.
+ * Quantiser (dualhyp_amd.quant.quantize_blocks_mxfp4; tests/mxfp4_reference.py is its fp64 restatement).  amax = max |block|.
+ * amax == 0: s = 127, every element +0.  Otherwise e = floor(log2(amax)) - 2, clamped so that s = e + 127 lies in [1, 254];
+ * element = v * 2^-e rounded to the nearest e2m1 value, ties to the even mantissa, saturated at +-6 (0.25 -> 0, 0.75 -> 1,
+ * 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4, >= 6 -> 6); the sign bit is that of v unless the element rounds to zero,
+ * which is always stored as +0 (code 0).  Inputs are the merged bf16 weights widened to fp32; every
+ * step is exact or a single rounding.
+ * Product.  y[m, n] = bf16( (sum_k xq[m, k] * e2m1[n, k] * 2^(s[n, k / 32] - 127)) * x_scale[m] ), fp32 accumulation, then the
+ * epilogues and bf16 rounding points of dh_linear_fp8.  No channel scale: v_mfma_scale_f32_16x16x128_f8f6f4 applies the
+ * block scales (operand format e2m1 on the W side, unit scale on the x side).  Every product is exact in fp32; each kernel
+ * fixes one summation order per output, independent of the row count.
+ * Physical layout (what wq / w_scale address; N % 16 == 0).  Rows are taken in groups of 16 and k in steps of 128.  For
+ * group g = n / 16 and k-step t = k / 128 there is one block of 1024 nibble bytes at byte offset (g * (K / 128) + t) * 1024
+ * of wq and one block of 64 scale bytes at byte offset (g * (K / 128) + t) * 64 of w_scale.  Inside a block, index
+ * l = 16 * q + r (r = n % 16 the row of the group, q = (k % 128) / 32 the MX block of the k-step) selects 16 consecutive
+ * nibble bytes at l * 16 and the scale byte at l.  Nibble byte j (0..15) of those 16 holds element k = 128 t + 32 q + 2 j in
+ * its low four bits and element k + 1 in its high four bits.  The scale byte at l is s of row n, MX block 4 t + q.
+ * So wq has N * K / 2 bytes and w_scale N * K / 32.  dualhyp_amd.quant.pack_mxfp4 writes this layout. */
+
+/* dh_linear_fp8_ex with MXFP4 weights: wq / w2q the nibble bytes, w_scale / w2_scale the E8M0 bytes, both in the layout
+ * above.  K % 128 == 0, N % 16 == 0.  Epilogues and the kernel selector (0 by row count, 1 tiled, 2 streaming with M <= 128)
+ * as dh_linear_fp8_ex. */
+int dh_linear_mxfp4_ex(const uint8_t* xq, const float* x_scale, const uint8_t* wq, const uint8_t* w_scale, dh_bf16* y, int M,
+                       int N, int K, int epilogue, const uint8_t* w2q, const uint8_t* w2_scale, const dh_bf16* vec_a,
+                       const dh_bf16* vec_b, const dh_bf16* resid, int kernel, void* stream);
+/* dh_linear_fp8_f32's counterpart: PLAIN on the streaming kernel, 1 <= M <= 128, the bf16-rounded result as fp32 [M, N]. */
+int dh_linear_mxfp4_f32(const uint8_t* xq, const float* x_scale, const uint8_t* wq, const uint8_t* w_scale, float* y32, int M,
+                        int N, int K, void* stream);
+
 /* ------------------------------------------------------------------ fp8 KV cache (csrc/kv8.hip, csrc/attention.hip)
  * Scheme.  Each KV group of each token has one K vector (after rope: the bf16 values dh_qkv_rope_cache_bf16 caches) and one V
  * vector of hs elements.  amax = max |x|; e = the smallest integer with amax <= 448 * 2^e (amax = m * 2^ex, m in [0.5, 1):
@@ -807,6 +841,14 @@ int dh_engine_create(const dh_model_desc* h_desc, int max_batch, int s_max, int 
  * table dh_engine_copy_prefix reads).  A kv_dtype 0 engine runs the launches of dh_engine_create's. */
 int dh_engine_create_ex(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens, int kv_dtype,
                         dh_engine** h_out);
+/* dh_engine_create_ex with the block weights' format: weight_dtype 0 = as the descriptor says (bf16, or e4m3 with channel
+ * scales when attn_ws != NULL: dh_engine_create_ex itself), 1 = MXFP4.  With weight_dtype 1 the five block weight pointers of
+ * every dh_layer_weights address nibble bytes and the *_ws pointers (cast to const float*) address E8M0 bytes, both in the
+ * layout of "MXFP4 weights" above; lm_head stays e4m3 with lm_head_ws channel scales.  Such an engine is an fp8 engine in
+ * every other respect (layer sequence, activation buffers, the refusals of beam and verify steps, kv_dtype 1 allowed); it
+ * needs n_embd and intermediate % 128 == 0 and merged LoRA. */
+int dh_engine_create_q(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype,
+                       dh_engine** h_out);
 void dh_engine_destroy(dh_engine* e);
 int64_t dh_engine_device_bytes(const dh_engine* e);
 
