@@ -12,5 +12,6 @@ from .utils import chunked_cross_entropy  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint, convert_hf_checkpoint  # noqa: F401
 from .quant import quantize_model_fp8, quantize_model_mxfp4  # noqa: F401
 from .stop import compile_stop, first_stop, finish_reasons, newline_ids  # noqa: F401
+from .bias import compile_bias, bias_hits  # noqa: F401
 
 __version__ = "0.1.0"

@@ -49,6 +49,11 @@ class PenaltyArgs(C.Structure):
     _fields_ = [("repetition", F), ("frequency", F), ("presence", F)]
 
 
+class BiasSpec(C.Structure):
+    """dh_bias_spec: the bias entries of one call, device arrays and their host copies (include/dualhyp_hip.h, "Contextual biasing")"""
+    _fields_ = [("ids", P), ("len", P), ("boost", P), ("h_ids", P), ("h_len", P), ("h_boost", P), ("n", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/dualhyp_hip.h
 SIGNATURES = {
     "dh_abi_version": (I, []),
@@ -109,6 +114,10 @@ SIGNATURES = {
                                    C.POINTER(PenaltyArgs)]),
     "dh_sample_rows_bf16_penalty": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
                                         F, F, C.POINTER(PenaltyArgs)]),
+    "dh_sample_bf16_bias": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F,
+                                C.POINTER(PenaltyArgs), C.POINTER(BiasSpec)]),
+    "dh_sample_rows_bf16_bias": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
+                                     F, F, C.POINTER(PenaltyArgs), C.POINTER(BiasSpec)]),
     "dh_beam_select_bf16_stop": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P, P]),
     "dh_token_top_logprobs_bf16_mask": (I, [P, I, I, P, P, I, P, I, I, P]),
     "dh_beam_select_bf16_mask": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, P]),
@@ -152,6 +161,7 @@ SIGNATURES = {
     "dh_engine_set_stop": (I, [P, C.POINTER(StopSpec), P, P]),
     "dh_engine_set_nucleus": (I, [P, F, F]),
     "dh_engine_set_penalties": (I, [P, C.POINTER(PenaltyArgs), P]),
+    "dh_engine_set_bias": (I, [P, C.POINTER(BiasSpec), P]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

@@ -61,6 +61,36 @@ int dh_penalty_pack(const char* name, const dh_penalty_args* in, dh_penalty_args
     return 0;
 }
 
+// dh_bias_spec -> what the kernels take by value, with the header's argument checks ("Contextual biasing"), made on the host copies:
+// nothing is launched.  Null or no entry is off.
+int dh_bias_pack(const char* name, const dh_bias_spec* spec, int vocab, bool start_ok, dh_bias_args& out) {
+    out = dh_bias_args{};
+    if (!spec || spec->n == 0) return 0;
+    DH_CHECK(spec->n > 0 && spec->n <= DH_MAX_BIAS_ENTRIES, "%s: %d bias entries, 1 .. %d are supported", name, spec->n, DH_MAX_BIAS_ENTRIES);
+    DH_CHECK(spec->ids && spec->len && spec->boost && spec->h_ids && spec->h_len && spec->h_boost,
+             "%s: %d bias entries without their ids, lengths or boosts (device arrays and host copies)", name, spec->n);
+    DH_CHECK(vocab <= 131072, "%s: a bias keeps a sequence's overridden columns in an LDS row of 131072 ids; vocab=%d does not fit", name, vocab);
+    int n_ids = 0;
+    for (int e = 0; e < spec->n; ++e) {
+        const int L = spec->h_len[e];
+        DH_CHECK(L >= 1 && L <= DH_MAX_BIAS_LEN, "%s: bias entry %d has %d ids, 1 .. %d are supported", name, e, L, DH_MAX_BIAS_LEN);
+        for (int k = 0; k < L; ++k) {
+            const int t = spec->h_ids[e * DH_MAX_BIAS_LEN + k];
+            DH_CHECK(t >= 0 && t < vocab, "%s: bias entry %d holds id %d, outside the vocabulary of %d", name, e, t, vocab);
+        }
+        const float b = spec->h_boost[e];
+        DH_CHECK(b - b == 0.f, "%s: bias entry %d has the boost %g, which is not finite", name, e, (double)b);      // false for inf and NaN
+        n_ids += L;
+    }
+    DH_CHECK(start_ok, "%s: a bias needs `start`, the prompt lengths: a match never reaches into the prompt", name);
+    out.ids = spec->ids;
+    out.len = spec->len;
+    out.boost = spec->boost;
+    out.n = spec->n;
+    out.n_ids = n_ids;
+    return 0;
+}
+
 extern "C" int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t* h_hbm_bytes) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

@@ -303,6 +303,21 @@ inline bool dh_penalty_same(const dh_penalty_args& a, const dh_penalty_args& b) 
 // the checks of every entry that takes a dh_penalty_args (capi.hip): null is off; finite, repetition in [1/8, 8], the others in [-8, 8]
 int dh_penalty_pack(const char* name, const dh_penalty_args* in, dh_penalty_args& out);
 
+// Contextual biasing (include/dualhyp_hip.h): a dh_bias_spec as the kernels take it, by value: the caller's three device arrays and the
+// entry count.  n_ids, the ids in all entries, is the host's, for the limit a penalty shares with it.  n = 0: off.
+struct dh_bias_args {
+    const int32_t* ids = nullptr;                       // [n, DH_MAX_BIAS_LEN]
+    const int32_t* len = nullptr;                       // [n]
+    const float* boost = nullptr;                       // [n]
+    int n = 0;
+    int n_ids = 0;
+    bool operator==(const dh_bias_args& o) const { return ids == o.ids && len == o.len && boost == o.boost && n == o.n && n_ids == o.n_ids; }
+};
+// the checks of every entry that takes a dh_bias_spec (capi.hip), made on the spec's host copies: null or n = 0 is off; 1 ..
+// DH_MAX_BIAS_ENTRIES entries of 1 .. DH_MAX_BIAS_LEN ids in [0, vocab), finite boosts, vocab <= 131072; start_ok: the entry was given
+// the prompt lengths
+int dh_bias_pack(const char* name, const dh_bias_spec* spec, int vocab, bool start_ok, dh_bias_args& out);
+
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
 // dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability;
 // top_n (0: off) with top_ids / top_lp ([n_seq, tok_ld, top_n], dh_engine_set_top_logprobs): the row's top_n alternatives as well;
@@ -310,17 +325,19 @@ int dh_penalty_pack(const char* name, const dh_penalty_args* in, dh_penalty_args
 // ngram (0: off) with start ([n_seq] prompt lengths, dh_engine_set_no_repeat_ngram): no-repeat n-grams, 0 = the kernels without it;
 // stop (dh_engine_set_stop; its sequences count from the same `start`): the stop test behind the pick, all zero = off;
 // nuc (dh_engine_set_nucleus): top_p / min_p of the sampled branch, the default = off;
-// pen (dh_engine_set_penalties; its history counts from the same `start`): the three penalties, the default = off
+// pen (dh_engine_set_penalties; its history counts from the same `start`): the three penalties, the default = off;
+// bias (dh_engine_set_bias; its matches count from the same `start`): the bias entries, the default = off
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
                    float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, float* logprobs,
                    int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask, int mask_ld, int ngram, const int32_t* start,
                    const dh_stop_args& stop, void* stream, const dh_nucleus_args& nuc = dh_nucleus_args{},
-                   const dh_penalty_args& pen = DH_PENALTY_OFF);
+                   const dh_penalty_args& pen = DH_PENALTY_OFF, const dh_bias_args& bias = dh_bias_args{});
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
                         const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream,
-                        const dh_nucleus_args& nuc = dh_nucleus_args{}, const dh_penalty_args& pen = DH_PENALTY_OFF);
+                        const dh_nucleus_args& nuc = dh_nucleus_args{}, const dh_penalty_args& pen = DH_PENALTY_OFF,
+                        const dh_bias_args& bias = dh_bias_args{});
 
 // the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
 // acceptance kernel (sampling.hip)

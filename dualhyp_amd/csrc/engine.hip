@@ -53,6 +53,8 @@ struct dh_engine {
     dh_nucleus_args nuc;                                // dh_engine_set_nucleus: top_p / min_p of later decode / decode_rows calls (default: off)
     dh_penalty_args pen = DH_PENALTY_OFF;               // dh_engine_set_penalties: the penalties of later decode / decode_rows calls (default: off)
     const int32_t* pen_start = nullptr;                 // and the caller's [n_seq] prompt lengths their history counts from
+    dh_bias_args bias;                                  // dh_engine_set_bias: the bias of later decode / decode_rows calls (default: off)
+    const int32_t* bias_start = nullptr;                // and the caller's [n_seq] prompt lengths its matches count from
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -92,6 +94,7 @@ struct dh_engine {
         dh_stop_args stop; const int32_t* stop_start; int32_t* stop_fin_tok;   // dh_engine_set_stop: likewise (a beam step's key: the set and fin_tok)
         dh_nucleus_args nuc;                                  // dh_engine_set_nucleus: likewise (off in an arg-max, a verify or a beam step's key)
         dh_penalty_args pen; const int32_t* pen_start;        // dh_engine_set_penalties: likewise (off / null in a verify or a beam step's key)
+        dh_bias_args bias; const int32_t* bias_start;         // dh_engine_set_bias: likewise
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
@@ -103,6 +106,7 @@ struct dh_engine {
                    logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
                    mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && stop == k.stop && stop_start == k.stop_start &&
                    stop_fin_tok == k.stop_fin_tok && nuc == k.nuc && dh_penalty_same(pen, k.pen) && pen_start == k.pen_start &&
+                   bias == k.bias && bias_start == k.bias_start &&
                    beam_w == k.beam_w &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
@@ -1020,7 +1024,9 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
 }
 
 // the prompt lengths of a step's history readers: the setters were given the same numbers
-const int32_t* hist_start(const dh_engine::GKey& k) { return k.ngram_start ? k.ngram_start : k.pen_start ? k.pen_start : k.stop_start; }
+const int32_t* hist_start(const dh_engine::GKey& k) {
+    return k.ngram_start ? k.ngram_start : k.pen_start ? k.pen_start : k.bias_start ? k.bias_start : k.stop_start;
+}
 
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (k.beam_w) return beam_step(e, k, s);
@@ -1035,10 +1041,10 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
                                    k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                                   hist_start(k), k.stop, s, k.nuc, k.pen);
+                                   hist_start(k), k.stop, s, k.nuc, k.pen, k.bias);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
                           e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                          hist_start(k), k.stop, s, k.nuc, k.pen);
+                          hist_start(k), k.stop, s, k.nuc, k.pen, k.bias);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1293,6 +1299,9 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
     DH_CHECK(!dh_penalty_on(e->pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
              "LDS tables of %d entries; tok_ld=%d may not fit", "dh_engine_decode", DH_MAX_PENALTY_HISTORY, tok_ld);
+    DH_CHECK(!dh_penalty_on(e->pen) || e->bias.n == 0 || tok_ld + e->bias.n_ids <= DH_MAX_PENALTY_HISTORY, "%s: penalties and a bias are "
+             "set and share static LDS tables of %d entries; tok_ld=%d and the entries' %d ids may not fit", "dh_engine_decode",
+             DH_MAX_PENALTY_HISTORY, tok_ld, e->bias.n_ids);
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
@@ -1305,7 +1314,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
                               nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
                               e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
                               top_k == 1 ? dh_nucleus_args{} : e->nuc,      // the arg-max takes neither parameter: its step is the plain one
-                              e->pen, e->pen_start};
+                              e->pen, e->pen_start, e->bias, e->bias_start};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1318,13 +1327,16 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
     DH_CHECK(!dh_penalty_on(e->pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
              "LDS tables of %d entries; tok_ld=%d may not fit", "dh_engine_decode_rows", DH_MAX_PENALTY_HISTORY, tok_ld);
+    DH_CHECK(!dh_penalty_on(e->pen) || e->bias.n == 0 || tok_ld + e->bias.n_ids <= DH_MAX_PENALTY_HISTORY, "%s: penalties and a bias are "
+             "set and share static LDS tables of %d entries; tok_ld=%d and the entries' %d ids may not fit", "dh_engine_decode_rows",
+             DH_MAX_PENALTY_HISTORY, tok_ld, e->bias.n_ids);
     if (n_steps <= 0) return 0;
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
                               limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
                               e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
-                              top_k == 1 ? dh_nucleus_args{} : e->nuc, e->pen, e->pen_start};
+                              top_k == 1 ? dh_nucleus_args{} : e->nuc, e->pen, e->pen_start, e->bias, e->bias_start};
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1364,6 +1376,8 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
              "dh_engine_decode_spec: %d rows, the workspaces hold %d (dh_engine_reserve_rows) of max_tokens = %d", n_seq * S, e->row_cap, e->max_tokens);
     DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_spec: penalties are set (repetition=%g, frequency=%g, presence=%g); a verify position's "
              "history would have to include this launch's own picks", (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence);
+    DH_CHECK(e->bias.n == 0, "dh_engine_decode_spec: a bias of %d entries is set; a verify position's tail would have to include this "
+             "launch's own picks, so the step would need per-position tables", e->bias.n);
     DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
     DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
@@ -1375,7 +1389,7 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
                               limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
                               e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr, dh_nucleus_args{},
-                              DH_PENALTY_OFF, nullptr};
+                              DH_PENALTY_OFF, nullptr, dh_bias_args{}, nullptr};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1430,6 +1444,8 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
              "form its ban set", e->ngram);
     DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_beam: penalties are set (repetition=%g, frequency=%g, presence=%g); a beam's history "
              "lives on the host, so the device cannot count it", (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence);
+    DH_CHECK(e->bias.n == 0, "dh_engine_decode_beam: a bias of %d entries is set; a beam's history lives on the host, so the device "
+             "cannot match it", e->bias.n);
     DH_CHECK(e->stop.n_seqs == 0, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
              "cannot match a sequence against it (the stop set alone goes with beam search)", e->stop.n_seqs);
     DH_CHECK(!e->stop.set || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
@@ -1449,7 +1465,7 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
                         prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                         e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, dh_nucleus_args{}, DH_PENALTY_OFF, nullptr,
-                        W, *st};
+                        dh_bias_args{}, nullptr, W, *st};
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1516,6 +1532,15 @@ extern "C" int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* pena
     DH_CHECK(!on || e->d.vocab <= 131072, "dh_engine_set_penalties: vocab=%d exceeds the 131072 ids of the sampler's LDS row", e->d.vocab);
     e->pen = on ? pen : DH_PENALTY_OFF;
     e->pen_start = on ? start : nullptr;
+    return 0;
+}
+
+extern "C" int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const int32_t* start) {
+    DH_CHECK(e, "dh_engine_set_bias: null engine");
+    dh_bias_args ba;
+    if (int rc = dh_bias_pack("dh_engine_set_bias", bias, e->d.vocab, start != nullptr, ba)) return rc;
+    e->bias = ba;
+    e->bias_start = ba.n ? start : nullptr;
     return 0;
 }
 

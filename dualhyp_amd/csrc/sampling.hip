@@ -46,15 +46,31 @@ __device__ __forceinline__ bf16_t pen_value(const pen_view& ov, const bf16_t* __
     return v;
 }
 // a_t of the header from the raw value and the id's count c: the HF rule, then three separately rounded fp32 operations (the compiler
-// contracts a product and a difference into an FMA unless told not to), then the bf16 rounding
-__device__ __forceinline__ bf16_t penalised(bf16_t raw, int c, const dh_penalty_args& pen) {
+// contracts a product and a difference into an FMA unless told not to), then the bf16 rounding.  penalised_z: z, the fp32 value in
+// front of that rounding, which a boost is added to ("Contextual biasing").
+__device__ __forceinline__ float penalised_z(bf16_t raw, int c, const dh_penalty_args& pen) {
 #pragma clang fp contract(off)
     const float x = bf2f(raw);
     const float y = x < 0.f ? x * pen.repetition : x / pen.repetition;
     const float p = pen.frequency * (float)c;
     const float d = y - p;
     const float z = d - pen.presence;
-    return f2bf(z);
+    return z;
+}
+__device__ __forceinline__ bf16_t penalised(bf16_t raw, int c, const dh_penalty_args& pen) { return f2bf(penalised_z(raw, c, pen)); }
+
+// Contextual biasing (include/dualhyp_hip.h): a boost as an unsigned key with the floats' order, so the largest of an id's boosts is an
+// integer atomicMax, exact in any order.  A finite boost's key is never 0, which is "no boost".
+__device__ __forceinline__ uint32_t bias_key(float b) {
+    const uint32_t u = __float_as_uint(b);
+    return (u & 0x80000000u) ? ~u : u | 0x80000000u;
+}
+__device__ __forceinline__ float bias_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k ^ 0x80000000u : ~k); }
+// bf16(y + B): one fp32 add, never part of an FMA, then round to nearest even
+__device__ __forceinline__ bf16_t boosted(float y, float b) {
+#pragma clang fp contract(off)
+    const float s = y + b;
+    return f2bf(s);
 }
 
 // The pick of one sequence's next token from its logits row `lg`, by the whole 1024-thread block; every thread
@@ -359,32 +375,75 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
 
 // Penalties (include/dualhyp_hip.h): the static LDS tables bound the history, and with it the distinct ids, of a penalised pick
 constexpr int PEN_MAX_HISTORY = DH_MAX_PENALTY_HISTORY;
-constexpr size_t PEN_LDS_BYTES = (BAN_MAX_VOCAB / 32) * (sizeof(uint32_t) + sizeof(uint16_t)) + PEN_MAX_HISTORY * (sizeof(uint32_t) + sizeof(bf16_t));
+constexpr size_t PEN_LDS_BYTES = (BAN_MAX_VOCAB / 32) * (sizeof(uint32_t) + sizeof(uint16_t)) + PEN_MAX_HISTORY * (sizeof(uint32_t) + sizeof(bf16_t)) +
+                                 DH_MAX_BIAS_LEN * sizeof(int32_t);     // and the bias' tail of the generated tokens
 static_assert(PEN_MAX_HISTORY <= 65535 && BAN_MAX_VOCAB / 32 == 4 * NT, "pen_build: uint16 ranks, four words of the bit row per thread");
 
-// The columns the history g[0..m) of a sequence overrides under the penalties `pen`, by the whole block: the distinct ids of g below
-// vocab with their counts c_t, and a_t = penalised(lg[t], c_t) for each (pen_view above says where).  Set membership is an LDS atomicOr,
-// a count an integer LDS atomicAdd, a rank a prefix sum of popcounts: exact whatever order the threads arrive in.  Every occurrence of an
-// id writes the id's value, the same bits from the same operands.  Every thread gets the view; it holds until the block's next call.
-// m <= PEN_MAX_HISTORY is the host's to refuse (DH_CHECK_PENALTY); the clamp only keeps a longer history inside the tables.
-__device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int vocab, const int64_t* g, int m, const dh_penalty_args& pen) {
-    // the tables live in the launch's dynamic LDS (PEN_LDS_BYTES, asked for only when a penalty is on): the n-gram-only launches of the
-    // family keep the static LDS, and with it the residency, they had
+// Contextual biasing (include/dualhyp_hip.h): every thread of the block takes two (entry, depth) pairs, and a history's token two places
+static_assert(DH_MAX_BIAS_ENTRIES * DH_MAX_BIAS_LEN == 2 * NT && PEN_MAX_HISTORY == 2 * NT && DH_MAX_BIAS_LEN == 8,
+              "pen_build: two pairs and two history places per thread, depth = pair & 7");
+
+// The columns a sequence overrides at a pick, by the whole block, from its generated tokens g[0..m_all):
+//   under the penalties `pen` (on or off, launch-uniform) the distinct ids of g below vocab with their counts c_t, each holding
+//     a_t = bf16(z), z = penalised_z(lg[t], c_t);
+//   under the bias `bias` (n > 0 or off, launch-uniform) the ids its entries propose, each holding bf16(y + B_t): y is z where the id is
+//     in the penalised history and float(lg[t]) where not, B_t the largest boost of its proposers.
+// pen_view above says where.  Set membership is an LDS atomicOr, a count an integer LDS atomicAdd, a rank a prefix sum of popcounts, B_t
+// an integer LDS atomicMax on bias_key: exact whatever order the threads arrive in.  Every writer of an id's value writes the same bits
+// from the same operands.  With both on, the counts move to registers and their table holds the boost keys: the tables keep their size.
+// Every thread gets the view; it holds until the block's next call.  The host refuses what the tables could not hold
+// (DH_CHECK_PENALTY, DH_CHECK_BIAS); the clamp only keeps a longer history inside them.
+__device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int vocab, const int64_t* g, int m_all, const dh_penalty_args& pen,
+                                              const dh_bias_args& bias) {
+    // the tables live in the launch's dynamic LDS (PEN_LDS_BYTES, asked for only when a penalty or a bias is on): the n-gram-only
+    // launches of the family keep the static LDS, and with it the residency, they had
     extern __shared__ __align__(16) unsigned char s_pen[];
     uint32_t* s_bits = reinterpret_cast<uint32_t*>(s_pen);                 // [BAN_MAX_VOCAB / 32]
-    uint32_t* s_cnt = s_bits + BAN_MAX_VOCAB / 32;                          // [PEN_MAX_HISTORY]
+    uint32_t* s_cnt = s_bits + BAN_MAX_VOCAB / 32;                          // [PEN_MAX_HISTORY]: counts, then (bias on) boost keys
     uint16_t* s_pre = reinterpret_cast<uint16_t*>(s_cnt + PEN_MAX_HISTORY); // [BAN_MAX_VOCAB / 32]
     bf16_t* s_val = s_pre + BAN_MAX_VOCAB / 32;                             // [PEN_MAX_HISTORY]
+    int32_t* s_tail = reinterpret_cast<int32_t*>(s_val + PEN_MAX_HISTORY);  // [DH_MAX_BIAS_LEN - 1]: g[m_all - 7 .. m_all), -1 where none
     __shared__ uint32_t s_wtot[NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nw = (vocab + 31) >> 5;
-    m = m < PEN_MAX_HISTORY ? m : PEN_MAX_HISTORY;
+    const bool pen_on = dh_penalty_on(pen), bias_on = bias.n > 0;
+    const int m = !pen_on ? 0 : m_all < PEN_MAX_HISTORY ? m_all : PEN_MAX_HISTORY;      // the history the penalties count
     for (int w = tid; w < nw; w += NT) s_bits[w] = 0u;
     for (int i = tid; i < PEN_MAX_HISTORY; i += NT) s_cnt[i] = 0u;
+    if (bias_on && tid < DH_MAX_BIAS_LEN - 1) {         // the tail every pair is matched against, read from the token row once
+        const int i = m_all - (DH_MAX_BIAS_LEN - 1) + tid;
+        int32_t v = -1;                                 // no entry id equals it
+        if (i >= 0) {
+            const int64_t t = g[i];
+            if (t >= 0 && t < vocab) v = (int32_t)t;
+        }
+        s_tail[tid] = v;
+    }
     __syncthreads();
     for (int i = tid; i < m; i += NT) {
         const int64_t t = g[i];
         if (t >= 0 && t < vocab) atomicOr(&s_bits[t >> 5], 1u << (t & 31));
+    }
+    // pair p = (entry p >> 3, depth k = p & 7) proposes ids[k] when g's last k tokens are ids[0 .. k)
+    int bt[2] = {-1, -1};
+    uint32_t bk[2] = {0u, 0u};
+    if (bias_on) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int p = tid + j * NT, e = p >> 3, k = p & (DH_MAX_BIAS_LEN - 1);
+            if (e >= bias.n || k >= bias.len[e] || k > m_all) continue;
+            const int32_t* ids = bias.ids + (size_t)e * DH_MAX_BIAS_LEN;
+            bool eq = true;
+#pragma unroll
+            for (int q = 0; q < DH_MAX_BIAS_LEN - 1; ++q)
+                if (q < k && s_tail[DH_MAX_BIAS_LEN - 1 - k + q] != ids[q]) eq = false;
+            const int t = ids[k];
+            if (eq && t >= 0 && t < vocab) {
+                bt[j] = t;
+                bk[j] = bias_key(bias.boost[e]);
+                atomicOr(&s_bits[t >> 5], 1u << (t & 31));
+            }
+        }
     }
     __syncthreads();
     // exclusive prefix of the words' popcounts: thread t owns words 4 t .. 4 t + 3, a wave scan, then the wave totals
@@ -411,34 +470,72 @@ __device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int
     }
     __syncthreads();
     const pen_view ov{s_bits, s_pre, s_val};
-    for (int i = tid; i < m; i += NT) {
-        const int64_t t = g[i];
-        if (t >= 0 && t < vocab) atomicAdd(&s_cnt[pen_rank(ov, (int)t)], 1u);
-    }
-    __syncthreads();
-    for (int i = tid; i < m; i += NT) {
-        const int64_t t = g[i];
-        if (t >= 0 && t < vocab) {
-            const int r = pen_rank(ov, (int)t);
-            s_val[r] = penalised(lg[t], (int)s_cnt[r], pen);
+    if (pen_on) {
+        for (int i = tid; i < m; i += NT) {
+            const int64_t t = g[i];
+            if (t >= 0 && t < vocab) atomicAdd(&s_cnt[pen_rank(ov, (int)t)], 1u);
         }
+        __syncthreads();
     }
-    __syncthreads();
+    uint32_t hc[2] = {0u, 0u};                          // pen and bias on: the counts of this thread's two history places
+    if (bias_on) {
+        if (pen_on) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = tid + j * NT;
+                if (i < m) {
+                    const int64_t t = g[i];
+                    if (t >= 0 && t < vocab) hc[j] = s_cnt[pen_rank(ov, (int)t)];
+                }
+            }
+            __syncthreads();
+            for (int i = tid; i < PEN_MAX_HISTORY; i += NT) s_cnt[i] = 0u;
+            __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (bt[j] >= 0) atomicMax(&s_cnt[pen_rank(ov, bt[j])], bk[j]);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {                   // an id outside the penalised history: y = float(raw); one inside is written below
+            if (bt[j] >= 0) {
+                const int r = pen_rank(ov, bt[j]);
+                s_val[r] = boosted(bf2f(lg[bt[j]]), bias_unkey(s_cnt[r]));
+            }
+        }
+        __syncthreads();
+    }
+    if (pen_on) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int i = tid + j * NT;
+            if (i >= m) continue;
+            const int64_t t = g[i];
+            if (t >= 0 && t < vocab) {
+                const int r = pen_rank(ov, (int)t);
+                const uint32_t key = bias_on ? s_cnt[r] : 0u;
+                const float z = penalised_z(lg[t], (int)(bias_on ? hc[j] : s_cnt[r]), pen);
+                s_val[r] = key ? boosted(z, bias_unkey(key)) : f2bf(z);
+            }
+        }
+        __syncthreads();
+    }
     return ov;
 }
 
 // pick_token under no_repeat_ngram: under the row ban_row builds from the sequence's history g[0..m), through the masked paths of
 // pick_token (the 16-byte mask_byte loads included), so the pick is the unmasked pick on a copy of the row with -inf in every column that
 // the mask disallows or the history bans.  The kernels' BAN = false instantiations call pick_token<MASK> as they always did.
-// pen (launch-uniform; ngram may be 0 then): the columns of the history's ids hold a_t as well, through pick_token's PEN paths.  Off,
-// the pick runs the instantiation it always ran.
+// pen, bias (launch-uniform; ngram may be 0 then): the columns of the history's ids hold a_t, and those of the ids the bias proposes their
+// boosted value, as well, through pick_token's PEN paths.  Both off, the pick runs the instantiation it always ran.
 template <bool MASK>
 __device__ __forceinline__ int pick_token_banned(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k, uint64_t seed,
                                              int step, int seq, const uint32_t* __restrict__ mrow, const int64_t* g, int m, int ngram,
-                                             const dh_nucleus_args nuc = dh_nucleus_args{}, const dh_penalty_args pen = DH_PENALTY_OFF) {
+                                             const dh_nucleus_args nuc = dh_nucleus_args{}, const dh_penalty_args pen = DH_PENALTY_OFF,
+                                             const dh_bias_args bias = dh_bias_args{}) {
     const uint32_t* row = ban_row<MASK>(g, m, ngram, vocab, mrow);
-    if (dh_penalty_on(pen)) {                           // the same for every thread of the launch
-        const pen_view ov = pen_build(lg, vocab, g, m, pen);
+    if (dh_penalty_on(pen) || bias.n > 0) {             // the same for every thread of the launch
+        const pen_view ov = pen_build(lg, vocab, g, m, pen, bias);
         return pick_token<true, true>(lg, vocab, temperature, top_k, seed, step, seq, row, nuc, ov);
     }
     return pick_token<true>(lg, vocab, temperature, top_k, seed, step, seq, row, nuc);
@@ -686,7 +783,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                     const uint32_t* __restrict__ mask, int mask_ld, int ngram,
                                                     const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc,
-                                                    dh_penalty_args pen) {
+                                                    dh_penalty_args pen, dh_bias_args bias) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
@@ -694,7 +791,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
     if constexpr (BAN) {                                // the history is what lies behind the prompt
         const int p0 = start[seq];
         choice = pick_token_banned<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
-                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram, nuc, pen);
+                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram, nuc, pen, bias);
     } else {
         choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
                                   MASK ? mask + (size_t)seq * mask_ld : nullptr, nuc);
@@ -733,7 +830,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
                                                          const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc,
-                                                    dh_penalty_args pen) {
+                                                    dh_penalty_args pen, dh_bias_args bias) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
@@ -742,7 +839,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
     if constexpr (BAN) {
         const int p0 = start ? start[u] : limit[u] - max_new;           // the prompt length, which limit[u] - max_new is
         choice = pick_token_banned<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
-                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc, pen);
+                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc, pen, bias);
     } else {
         choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
                                   MASK ? mask + (size_t)u * mask_ld : nullptr, nuc);     // the sequence's mask row, not the logits row's
@@ -872,8 +969,8 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
 
 // the three kernels' variant for (logprobs, top_n): top_n > 0 needs the three buffers
 // and for the token mask: null is the kernel without it (the code it always was)
-// and for no_repeat_ngram: 0 is the kernel without it, likewise; `hist` (a local of the launcher) is ngram > 0, or a penalty on: the
-// history-reading family
+// and for no_repeat_ngram: 0 is the kernel without it, likewise; `hist` (a local of the launcher) is ngram > 0, or a penalty or a bias on:
+// the history-reading family
 #define DH_PICK_VARIANT_MB(kernel, M, B) \
     (top_n > 0 ? kernel<true, true, M, B> : logprobs ? kernel<true, false, M, B> : kernel<false, false, M, B>)
 #define DH_PICK_VARIANT_B(kernel, B) (mask ? DH_PICK_VARIANT_MB(kernel, true, B) : DH_PICK_VARIANT_MB(kernel, false, B))
@@ -891,6 +988,15 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
              "%d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                             \
     DH_CHECK(!dh_penalty_on(pen) || (hist_max) <= PEN_MAX_HISTORY, name ": penalties keep a sequence's distinct ids in static LDS tables " \
              "of %d entries; a history of up to %d tokens may not fit", PEN_MAX_HISTORY, (int)(hist_max))
+// the bias itself is checked where it is packed (dh_bias_pack); here what depends on the call: with a penalty on, the history's ids and
+// the entries' ids share the tables
+#define DH_CHECK_BIAS(name, hist_max)                                                                                           \
+    DH_CHECK(bias.n == 0 || start, name ": a bias needs `start`, the prompt lengths: a match never reaches into the prompt");          \
+    DH_CHECK(bias.n == 0 || vocab <= BAN_MAX_VOCAB, name ": a bias keeps a sequence's overridden columns in a static LDS row of "      \
+             "%d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                             \
+    DH_CHECK(bias.n == 0 || !dh_penalty_on(pen) || (hist_max) + bias.n_ids <= PEN_MAX_HISTORY, name ": penalties and a bias keep a "    \
+             "sequence's distinct ids in static LDS tables of %d entries; a history of up to %d tokens and the entries' %d ids may not " \
+             "fit", PEN_MAX_HISTORY, (int)(hist_max), bias.n_ids)
 #define DH_CHECK_MASK(name)                                                                                                    \
     DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, name ": mask_ld=%d is below the %d words of a %d-token mask row", mask_ld, \
              (vocab + 31) / 32, vocab)
@@ -904,10 +1010,11 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
                    int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
                    const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
                    int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream, const dh_nucleus_args& nuc,
-                   const dh_penalty_args& pen) {
+                   const dh_penalty_args& pen, const dh_bias_args& bias) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
     DH_CHECK_PENALTY("dh_sample_bf16", tok_ld);
-    const bool hist = ngram > 0 || dh_penalty_on(pen);
+    DH_CHECK_BIAS("dh_sample_bf16", tok_ld);
+    const bool hist = ngram > 0 || dh_penalty_on(pen) || bias.n > 0;
     DH_CHECK(sa.n_seqs == 0 || start, "dh_sample_bf16: stop sequences need `start`, the prompt lengths");
     DH_CHECK_TOP("dh_sample_bf16");
     DH_CHECK_MASK("dh_sample_bf16");
@@ -916,9 +1023,10 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
     // logprobs null: the kernel without the log-probability pass (the code it always was)
-    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), dh_penalty_on(pen) ? PEN_LDS_BYTES : 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), dh_penalty_on(pen) || bias.n > 0 ? PEN_LDS_BYTES : 0,
+                       (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen);
+                       top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen, bias);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -993,6 +1101,23 @@ extern "C" int dh_sample_bf16_penalty(const dh_bf16* logits, int vocab, int64_t*
                           nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc, pen);
 }
 
+extern "C" int dh_sample_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                   const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                   float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias) {
+    dh_bias_args ba;
+    if (int rc = dh_bias_pack("dh_sample_bf16_bias", bias, vocab, start != nullptr, ba)) return rc;
+    dh_penalty_args pen;
+    if (int rc = dh_penalty_pack("dh_sample_bf16_bias", penalties, pen)) return rc;
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_sample_bf16_bias", top_p, min_p, nuc)) return rc;
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_bf16_bias", stop, start != nullptr, sa)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
+                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc, pen, ba);
+}
+
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                               int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                               int step, void* stream) {
@@ -1004,10 +1129,11 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
                         const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream,
-                        const dh_nucleus_args& nuc, const dh_penalty_args& pen) {
+                        const dh_nucleus_args& nuc, const dh_penalty_args& pen, const dh_bias_args& bias) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
     DH_CHECK_PENALTY("dh_sample_rows_bf16", tok_ld);
-    const bool hist = ngram > 0 || dh_penalty_on(pen);
+    DH_CHECK_BIAS("dh_sample_rows_bf16", tok_ld);
+    const bool hist = ngram > 0 || dh_penalty_on(pen) || bias.n > 0;
     DH_CHECK_TOP("dh_sample_rows_bf16");
     DH_CHECK_MASK("dh_sample_rows_bf16");
     DH_CHECK_NGRAM("dh_sample_rows_bf16", false);
@@ -1015,9 +1141,9 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), dh_penalty_on(pen) ? PEN_LDS_BYTES : 0,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), dh_penalty_on(pen) || bias.n > 0 ? PEN_LDS_BYTES : 0,
                        (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen);
+                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen, bias);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -1101,6 +1227,25 @@ extern "C" int dh_sample_rows_bf16_penalty(const dh_bf16* logits, int vocab, int
                                pen);
 }
 
+extern "C" int dh_sample_rows_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                        int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                        int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
+                                        float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias) {
+    dh_bias_args ba;
+    if (int rc = dh_bias_pack("dh_sample_rows_bf16_bias", bias, vocab, start != nullptr, ba)) return rc;
+    dh_penalty_args pen;
+    if (int rc = dh_penalty_pack("dh_sample_rows_bf16_bias", penalties, pen)) return rc;
+    dh_nucleus_args nuc;
+    if (int rc = dh_nucleus_pack("dh_sample_rows_bf16_bias", top_p, min_p, nuc)) return rc;
+    dh_stop_args sa;
+    if (int rc = dh_stop_pack("dh_sample_rows_bf16_bias", stop, true, sa)) return rc;         // start null: limit - max_new_tokens
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc,
+                               pen, ba);
+}
+
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                    int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
                                    int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
@@ -1120,7 +1265,7 @@ int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
-    const bool hist = ngram > 0;                        // a verify step takes no penalty
+    const bool hist = ngram > 0;                        // a verify step takes no penalty and no bias
     hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
                        counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa);

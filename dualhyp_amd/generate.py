@@ -14,6 +14,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import beam as _beam
+from . import bias as _bias
 from . import constrain as _constrain
 from . import ngram as _ngram
 from . import nucleus as _nucleus
@@ -103,8 +104,35 @@ def _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, sp
     return pen
 
 
+def _bias_kw(bias) -> dict:
+    """The sampling ops' keyword of a compiled bias (none when it is off)."""
+    return dict(bias=bias) if bias is not None else {}
+
+
+def _check_bias(bias, speculate: int = 0):
+    """`bias=` looked at before the model is touched: its type, and what it does not go with.  Needs nothing but the arguments; the
+    entries themselves are checked against the model's vocabulary by _compile_bias."""
+    if bias is None or (isinstance(bias, (list, tuple)) and len(bias) == 0):
+        return None
+    if not isinstance(bias, (_bias.BiasSpec, list, tuple)):
+        raise TypeError(f"bias is a compiled specification (dualhyp_amd.bias.compile_bias) or a list of (ids, boost) pairs, not {bias!r}")
+    if speculate:
+        raise ValueError(f"speculate={speculate} does not go with a bias of {len(bias)} entries: {_bias.SPEC_REFUSAL}")
+    return bias
+
+
+def _compile_bias(model, bias, pen, tok_ld: int, dev):
+    """The call's BiasSpec on the model's device (None: off), with the limit it shares with the penalties checked."""
+    if bias is None:
+        return None
+    spec = _bias.as_spec(bias, model.config.padded_vocab_size, dev)
+    if spec is not None and pen:
+        _bias.check_tables(tok_ld, spec.n_ids)
+    return spec
+
+
 @contextlib.contextmanager
-def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float, pen=None):
+def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float, pen=None, bias=None):
     """What a call hands the engine for its captured decode steps, each only where the call uses it — every one is part of a captured
     step's key, so without it the call runs the steps it always ran — and takes back behind them: the buffers are the call's."""
     nuc = top_p < 1.0 or min_p > 0.0
@@ -122,9 +150,13 @@ def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p:
         eng.set_nucleus(top_p, min_p)
     if pen:
         eng.set_penalties(*pen, start=start)
+    if bias is not None:
+        eng.set_bias(bias, start)
     try:
         yield
     finally:
+        if bias is not None:
+            eng.set_bias()
         if pen:
             eng.set_penalties()
         if lp_buf is not None:
@@ -178,7 +210,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
                    stop=None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                    repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                   presence_penalty: Optional[float] = None):
+                   presence_penalty: Optional[float] = None, bias=None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -256,7 +288,20 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     no launch or read-back of their own and without writing the logits; the first pick of a prompt is unaffected, a masked or banned
     column stays -inf, and log-probabilities and alternatives stay the raw row's.  It goes with share_prefix, return_logprobs,
     top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p and fp8; speculate is refused, and the token buffer (the longest
-    prompt plus max_new_tokens) may have at most 2048 places.  None, 1.0 and 0.0 (the defaults) are off: the call it always was."""
+    prompt plus max_new_tokens) may have at most 2048 places.  None, 1.0 and 0.0 (the defaults) are off: the call it always was.
+
+    bias (a dualhyp_amd.bias.BiasSpec from compile_bias, or a list of (ids, boost) pairs: 1 .. 256 entries of 1 .. 8 token ids and a finite
+    boost of either sign, shared by all prompts; include/dualhyp_hip.h, "Contextual biasing"): the continuations of the listed phrases
+    become more (or less) likely, with whatever sampler the call uses, the arg-max included.  An entry proposes its id at depth k when the
+    sequence's last k GENERATED tokens are the entry's first k (the prompt neither starts nor continues a match; depth 0, the first id,
+    is always proposed); the pick is the same call's pick on a copy of the logits row in which every proposed id holds bf16(y + B), B
+    the largest boost of its proposers and y the column's raw — or, where the id is in the penalised history, penalised — fp32 value.
+    The columns are built inside the sampling kernels from the token buffer, per sequence and step, with no launch or read-back of their
+    own and without writing the logits; a masked or banned column stays -inf, and log-probabilities and alternatives stay the raw
+    row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p, the penalties
+    (then the token buffer's places plus the entries' ids may be at most 2048) and fp8; speculate is refused.  None (the default) and
+    an empty list are off: the call it always was."""
+    bias = _check_bias(bias, speculate)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     B = len(prompts)
@@ -276,6 +321,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     if pen:
         _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
     dev = model.transformer.wte.weight.device
+    bias = _compile_bias(model, bias, pen, T_max + max_new_tokens, dev)
     mask = _token_mask(model, token_mask, B, 1, dev)
     stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
@@ -299,8 +345,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     else:
         length = torch.tensor(lens, dtype=torch.int32, device=dev)
         done = torch.zeros(B, dtype=torch.int32, device=dev)
-    # the prompt lengths: the ban's and the penalties' history, and a stop sequence's match, begin there
-    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram or pen or (stop is not None and stop.sequences) else None
+    # the prompt lengths: the ban's and the penalties' history, and a stop sequence's or a bias entry's match, begin there
+    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram or pen or bias is not None or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -316,11 +362,11 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
                top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p,
-               **_penalty_kw(pen))
+               **_penalty_kw(pen), **_bias_kw(bias))
     if ev:
         ev[1].record()
     # each of these is part of the captured step's key; without it the call runs the steps it always ran
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias):
         steps_run = 0
         if max_new_tokens > 1:
             n = max_new_tokens - 1
@@ -396,7 +442,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                  eos_id: Optional[int] = None, prefill_batch: int = 32, share_prefix: Union[bool, str] = False, token_mask=None,
                  no_repeat_ngram: int = 0, stop=None, top_logprobs: int = 0, timing: Optional[dict] = None,
                  return_state: bool = False, speculate: int = 0, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None):
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None):
     """num_samples = N (2..8) sampled candidates per prompt from ONE prefill of it (include/dualhyp_hip.h, "Sampled candidates").
 
     DEFINITION: sample j of utterance u is row u * N + j of generate_batch over [p for p in prompts for _ in range(N)] with the same
@@ -435,6 +481,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         raise ValueError(f"num_samples={N}: the RelPrompt decoder's prompts carry spliced reliability embeddings, which a prefill by "
                          "ids into the source slots does not hold")
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
+    bias = _check_bias(bias)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
@@ -451,6 +498,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     if pen:
         _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
     dev = model.transformer.wte.weight.device
+    bias = _compile_bias(model, bias, pen, T_max + max_new_tokens, dev)
     mask = _token_mask(model, token_mask, B, 1, dev)
     if mask is not None:
         mask = mask.repeat_interleave(N, dim=0).contiguous()      # a row per decode row
@@ -467,7 +515,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     length = torch.tensor(row_lens, dtype=torch.int32, device=dev)
     done = torch.zeros(R, dtype=torch.int32, device=dev)
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)      # what the fork reads
-    start = length.clone() if ngram or pen or (stop is not None and stop.sequences) else None
+    start = length.clone() if ngram or pen or bias is not None or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
     if ev:
@@ -486,11 +534,11 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         ev[4].record()
     ops.sample(last.repeat_interleave(N, dim=0), tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed,
                step=0, logprobs=lp_buf, top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p,
-               min_p=min_p, **_penalty_kw(pen))
+               min_p=min_p, **_penalty_kw(pen), **_bias_kw(bias))
     if ev:
         ev[1].record()
     steps_run = 0
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias):
         if max_new_tokens > 1:
             steps_run = _decode_steps(eng, tokens, length, done, max_new_tokens - 1, temperature, top_k, eos_id, seed,
                                       early=eos_id is not None or stop is not None)
@@ -534,7 +582,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
 @torch.inference_mode()
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
                       length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
-                      token_mask=None, no_repeat_ngram: int = 0, stop=None):
+                      token_mask=None, no_repeat_ngram: int = 0, stop=None, bias=None):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
@@ -569,7 +617,12 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
 
     stop (as in generate_batch, the stop set only): a candidate whose id is in the set ends its hypothesis into the pool exactly as
     the EOS does — same place rule, score and pool order — and the id stays in the hypothesis.  Stop sequences are refused before
-    anything is launched: the beams' histories live on the host."""
+    anything is launched: the beams' histories live on the host.
+
+    bias: refused unless None or empty, for the same reason."""
+    if _check_bias(bias) is not None:
+        raise ValueError(f"a bias of {len(bias)} entries does not go with beam search: {_bias.BEAM_REFUSAL}; it runs under generate_batch "
+                         "and generate_stream")
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     if stop is not None and not isinstance(stop, _stop.StopSpec):
@@ -657,7 +710,7 @@ class _StreamBackend:
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
                  logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None,
-                 top_p: float = 1.0, min_p: float = 0.0, pen=None) -> None:
+                 top_p: float = 1.0, min_p: float = 0.0, pen=None, bias=None) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -681,7 +734,9 @@ class _StreamBackend:
         self.stop = stop                     # generate_batch's stop; its sequences count from the same prompt lengths
         self.top_p, self.min_p = top_p, min_p    # generate_batch's top_p / min_p (the decode steps get them through the engine)
         self.pen = pen                       # generate_batch's penalties, checked (None: off); their history counts from the same lengths
-        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) if ngram or pen or (stop is not None and stop.sequences) else None
+        self.bias = bias                     # generate_batch's bias, compiled (None: off); its matches count from the same lengths
+        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) \
+            if ngram or pen or bias is not None or (stop is not None and stop.sequences) else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -704,7 +759,7 @@ class _StreamBackend:
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
                         self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
-                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **_penalty_kw(self.pen), **self.kw)
+                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **_penalty_kw(self.pen), **_bias_kw(self.bias), **self.kw)
         if end:
             end.record()
 
@@ -731,7 +786,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
                     top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False,
                     top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None):
+                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -761,9 +816,12 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     top_p, min_p: as in generate_batch — a row's kept set is a function of the row alone, so the ids do not depend on the schedule.
 
     repetition_penalty, frequency_penalty, presence_penalty: as in generate_batch — a sequence's adjusted values are formed from its own
-    row of the token buffer wherever it is scheduled, so the ids do not depend on the schedule."""
+    row of the token buffer wherever it is scheduled, so the ids do not depend on the schedule.
+
+    bias: as in generate_batch — a sequence's proposals are matched against its own row of the token buffer wherever it is scheduled."""
     from .schedule import StreamScheduler
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
+    bias = _check_bias(bias, speculate)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     nuc = top_p < 1.0 or min_p > 0.0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
@@ -783,6 +841,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         _penalty.check_history(max(lens) + max_new_tokens, model.config.padded_vocab_size)
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
     dev = model.transformer.wte.weight.device
+    bias = _compile_bias(model, bias, pen, max(lens) + max_new_tokens, dev)
     mask = _token_mask(model, token_mask, N, 1, dev)
     stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     P = _shared_prefix(model, prompts, share_prefix, dev)
@@ -791,7 +850,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p, pen=pen)
+                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p, pen=pen, bias=bias)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
@@ -811,9 +870,13 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         eng.set_nucleus(top_p, min_p)
     if pen:
         eng.set_penalties(*pen, start=be.start)
+    if bias is not None:
+        eng.set_bias(bias, be.start)
     try:
         sched.run(be)
     finally:
+        if bias is not None:
+            eng.set_bias()
         if pen:
             eng.set_penalties()
         if return_logprobs:
@@ -866,13 +929,14 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
              top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, top_p: Optional[float] = None,
              min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-             presence_penalty: Optional[float] = None):
+             presence_penalty: Optional[float] = None, bias=None):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
     generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's.  repetition_penalty, frequency_penalty,
-    presence_penalty: generate_batch's."""
+    presence_penalty: generate_batch's.  bias: generate_batch's."""
     _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
+    _check_bias(bias, speculate)
     _nucleus.check_nucleus(top_p, min_p)
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
@@ -882,7 +946,7 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
                          speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
                          no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

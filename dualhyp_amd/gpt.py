@@ -587,6 +587,22 @@ class _Engine:
         _lib.check(self.lib.dh_engine_set_penalties(self.handle, C.byref(args), start.data_ptr()))
         self._pen_start = start
 
+    def set_bias(self, bias=None, start: Optional[torch.Tensor] = None) -> None:
+        """The bias (a dualhyp_amd.bias.BiasSpec on the engine's device; include/dualhyp_hip.h, "Contextual biasing") for later decode /
+        decode_rows calls; None turns it off (dh_engine_set_bias).  start: the int32 [n_seq] prompt lengths on the engine's device, the
+        array set_no_repeat_ngram / set_stop / set_penalties take; it and the spec are kept alive here while set.  The spec's arrays
+        are part of a captured step's key.  While set, decode_spec and decode_beam refuse."""
+        if bias is None:
+            _lib.check(self.lib.dh_engine_set_bias(self.handle, None, None))
+            self._bias = None
+            return
+        if start is None:
+            raise ValueError("a bias needs start, the int32 prompt lengths: a match never reaches back into the prompt")
+        if not start.is_cuda or start.dtype != torch.int32 or not start.is_contiguous() or start.dim() != 1:
+            raise TypeError("set_bias takes start as a contiguous 1-D int32 tensor of prompt lengths on the GPU")
+        _lib.check(self.lib.dh_engine_set_bias(self.handle, C.byref(bias.c_struct()), start.data_ptr()))
+        self._bias = (bias, start)
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"

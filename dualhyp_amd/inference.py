@@ -77,6 +77,9 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     {temperature, top_k, top_p, min_p, seed}, set when any of them is not the default) gives every record 'sampling', a copy of it.
     A generate_fn with an attribute `penalties` (--repetition_penalty / --frequency_penalty / --presence_penalty: a dict {repetition,
     frequency, presence}, set when any of them is not the default) gives every record 'penalties', a copy of it.
+    A generate_fn with an attribute `bias` (--bias_file: a dict {entries, default_boost}) and `bias_entries` (its (ids, boost) pairs)
+    gives every record 'bias', a copy of the dict, and 'bias_hits', the generated tokens that continued a listed phrase when they were
+    picked (dualhyp_amd.bias.bias_hits).
     Or to a dict {'samples': per prompt the N sampled candidates of dualhyp_amd.sample_batch, 'select': 'avg_logprob' | 'sum_logprob' |
     'mbr', 'logprobs': bool}: the prediction is the text of the candidate dualhyp_amd.select.select chooses among the candidates'
     answers, every record gains 'samples', one {'text', 'sum_logprob', 'avg_logprob', 'finish_reason', 'key'} per candidate in sample
@@ -134,6 +137,10 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["sampling"] = dict(generate_fn.sampling)
             if getattr(generate_fn, "penalties", None):
                 preds[i]["penalties"] = dict(generate_fn.penalties)
+            if getattr(generate_fn, "bias", None):
+                from .bias import bias_hits
+                preds[i]["bias"] = dict(generate_fn.bias)
+                preds[i]["bias_hits"] = bias_hits(o.reshape(-1)[p.numel():].tolist(), generate_fn.bias_entries)
             if beams is not None:
                 text = decode(p)
                 preds[i]["beams"] = [{"text": extract_answer(decode(hyp["tokens"]), text), "sum_logprob": _finite_or_none(hyp["sum_logprob"]),
@@ -198,6 +205,17 @@ def stop_from_args(args, tokenizer, vocab: int, device=None):
         seqs += f_seqs
     spec = compile_stop(ids, seqs, vocab, device) if ids or seqs else None
     return spec if spec else None
+
+
+def bias_from_args(args, tokenizer, vocab: int):
+    """((ids, boost) pairs, the records' `bias` field) of --bias_file and --bias_boost, checked against `vocab`, or (None, None) when
+    the flag is off."""
+    if not getattr(args, "bias_file", None):
+        return None, None
+    from .bias import DEFAULT_BOOST, check_bias, entries_from_lines, read_bias_file, record
+    default = float(getattr(args, "bias_boost", DEFAULT_BOOST))
+    entries = check_bias(entries_from_lines(read_bias_file(args.bias_file, default), tokenizer), vocab)
+    return [(list(ids), b) for ids, b in entries], record(len(entries), default)
 
 
 SAMPLING_DEFAULTS = dict(temperature=0.2, top_k=1, top_p=1.0, min_p=0.0)      # inference/ger.py:71-72 decodes greedily at 0.2
@@ -372,6 +390,10 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     # the default run passes no penalty keyword at all
     pkw = {} if penalties is None else dict(repetition_penalty=penalties["repetition"], frequency_penalty=penalties["frequency"],
                                             presence_penalty=penalties["presence"])
+    bias_entries, bias_rec = bias_from_args(args, tokenizer, model.config.padded_vocab_size)
+    if bias_entries is not None:      # the default run passes no bias keyword at all; compiled once for the run
+        from .bias import compile_bias
+        pkw["bias"] = compile_bias(bias_entries, model.config.padded_vocab_size, model.transformer.wte.weight.device)
     sampling = sampling_from_args(args)
     # the default run passes what it always passed: temperature 0.2, top_k 1 and the functions' own seed
     samp = dict(temperature=0.2, top_k=1) if sampling is None else dict(
@@ -418,6 +440,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.stop = stop is not None
     gen.sampling = sampling
     gen.penalties = penalties
+    gen.bias, gen.bias_entries = bias_rec, bias_entries
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams // n_samples), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -557,6 +580,17 @@ def build_parser():
                    help="A in [-8, 8]: A is taken off the logit of every token the utterance has generated; goes with what "
                         "--repetition_penalty goes with.  Default 0.0: off.  A run with any of the three penalties off its default gives "
                         "every record penalties: {repetition, frequency, presence}")
+    p.add_argument("--bias_file", type=str, default=None, metavar="FILE",
+                   help="contextual biasing: a list of phrases (names, product terms, jargon) whose continuations get a logit bonus inside "
+                        "the sampling kernels.  One entry per line, ENTRY or BOOST<TAB>ENTRY; an entry made only of integers is a list "
+                        "of token ids, anything else is text, encoded by the run's tokenizer with no BOS or EOS, and once more with one "
+                        "leading space when that gives other ids (both forms count); at most 256 entries of 1 .. 8 tokens, shared by all "
+                        "utterances.  Goes with both schedules and with --share_prefix, --constrain, --no_repeat_ngram, --stop, "
+                        "--logprobs, --top_logprobs, --top_p, --min_p, the penalties, --num_samples and fp8; not with --speculate or "
+                        "--num_beams.  Every record gains bias: {entries, default_boost} and bias_hits.  Default: off")
+    p.add_argument("--bias_boost", type=float, default=4.0, metavar="B",
+                   help="with --bias_file: the boost of a line that names none, finite, of either sign.  Default 4.0, an unmeasured "
+                        "starting point: its effect on a real corpus' word error rate has not been measured")
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="with --num_beams: hypotheses are ranked by sum_logprob / n ** length_penalty, n their generated tokens")
     p.add_argument("--prefill_batch", type=int, default=64, help="utterances per packed prefill launch inside a decode batch")
@@ -641,6 +675,16 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         if args.num_beams > 1:
             p.error(f"--num_beams {args.num_beams} does not go with {flags}: the beams' histories live on the host, so the sampling "
                     "kernels cannot count them")
+    import math
+    if not math.isfinite(args.bias_boost):
+        p.error(f"--bias_boost {args.bias_boost}: the boost is finite")
+    if args.bias_file:
+        if args.speculate:          # generate_batch refuses it too; here nothing has been loaded yet
+            from .bias import SPEC_REFUSAL
+            p.error(f"--speculate {args.speculate} does not go with --bias_file {args.bias_file}: {SPEC_REFUSAL}")
+        if args.num_beams > 1:
+            from .bias import BEAM_REFUSAL
+            p.error(f"--num_beams {args.num_beams} does not go with --bias_file {args.bias_file}: {BEAM_REFUSAL}")
     if not args.temperature > 0.0:
         p.error(f"--temperature {args.temperature}: the temperature is positive")
     if args.top_k < 0:

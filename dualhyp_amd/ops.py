@@ -342,6 +342,23 @@ def _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start:
     return ctypes.byref(args)
 
 
+def _bias_arg(bias, pen, start: Optional[torch.Tensor], tok_ld: int, vocab: int, device, keep):
+    """The dh_bias_spec pointer of a sampler call ("Contextual biasing" of the header), or None when there is no bias.  bias: a
+    dualhyp_amd.bias.BiasSpec or a list of (ids, boost) pairs.  On, the call needs start, and with a penalty on (`pen` not None) tables
+    that hold the token buffer and the entries' ids."""
+    from .bias import as_spec, check_tables
+    spec = as_spec(bias, vocab, device)
+    if spec is None:
+        return None
+    if start is None:
+        raise ValueError("a bias needs start, the int32 prompt lengths: a match never reaches back into the prompt")
+    if pen is not None:
+        check_tables(tok_ld, spec.n_ids)
+    import ctypes
+    keep.append(spec)
+    return ctypes.byref(spec.c_struct())
+
+
 def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
     index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
@@ -433,7 +450,7 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
            top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
            no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
            min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-           presence_penalty: Optional[float] = None) -> None:
+           presence_penalty: Optional[float] = None, bias=None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
@@ -448,7 +465,11 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     repetition_penalty (in [1/8, 8]), frequency_penalty and presence_penalty (in [-8, 8]; "Penalties" of the header; they need start): the
     pick is the same call's pick on a copy of the row in which the column of every id in tokens[u, start[u]:length[u]] holds its adjusted
     value; logits is not written, and the log-probabilities and alternatives stay the raw row's.  None, 1.0 and 0.0 are off
-    (dh_sample_bf16_penalty)."""
+    (dh_sample_bf16_penalty).
+    bias (a dualhyp_amd.bias.BiasSpec, or a list of (ids, boost) pairs; "Contextual biasing" of the header; it needs start): the pick is
+    the same call's pick on a copy of the row in which every id an entry proposes behind tokens[u, start[u]:length[u]] holds
+    bf16(y + boost), y its raw or penalised fp32 value; logits is not written, and the log-probabilities and alternatives stay the raw
+    row's.  None and an empty list are off (dh_sample_bf16_bias)."""
     from .nucleus import check_nucleus
     top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
@@ -462,14 +483,17 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     if st_ptr is not None and stop.sequences and start is None:
         raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
     pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tokens.size(1), vocab, k)
-    if (st_ptr is not None or pen is not None) and not no_repeat_ngram:
+    b_ptr = _bias_arg(bias, pen, start, tokens.size(1), vocab, logits.device, k)
+    if (st_ptr is not None or pen is not None or b_ptr is not None) and not no_repeat_ngram:
         ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
     else:
         ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
             0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
             _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if pen is not None:
+    if b_ptr is not None:
+        check(_lib.load().dh_sample_bf16_bias(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr))
+    elif pen is not None:
         check(_lib.load().dh_sample_bf16_penalty(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen))
     elif top_p < 1.0 or min_p > 0.0:
         check(_lib.load().dh_sample_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
@@ -489,13 +513,14 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
                 top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
                 no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
                 min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                presence_penalty: Optional[float] = None) -> None:
+                presence_penalty: Optional[float] = None, bias=None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
     in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
     (dh_sample_rows_bf16_mask).  no_repeat_ngram, start: as in sample(), one entry of start per SEQUENCE; start None is
     limit - max_new_tokens (dh_sample_rows_bf16_ngram).  stop: as in sample(); start None is limit - max_new_tokens here too
     (dh_sample_rows_bf16_stop).  top_p, min_p: as in sample() (dh_sample_rows_bf16_nucleus).  repetition_penalty, frequency_penalty,
-    presence_penalty: as in sample(), start included (dh_sample_rows_bf16_penalty)."""
+    presence_penalty: as in sample(), start included (dh_sample_rows_bf16_penalty).  bias: as in sample(), start included
+    (dh_sample_rows_bf16_bias)."""
     from .nucleus import check_nucleus
     top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
@@ -509,14 +534,17 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
     st_ptr = _stop_arg(stop, vocab, logits.device)
     pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tokens.size(1), vocab, k)
-    if (st_ptr is not None or pen is not None) and not no_repeat_ngram:
+    b_ptr = _bias_arg(bias, pen, start, tokens.size(1), vocab, logits.device, k)
+    if (st_ptr is not None or pen is not None or b_ptr is not None) and not no_repeat_ngram:
         ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
     else:
         ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=True)
     args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
             k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
             -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if pen is not None:
+    if b_ptr is not None:
+        check(_lib.load().dh_sample_rows_bf16_bias(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr))
+    elif pen is not None:
         check(_lib.load().dh_sample_rows_bf16_penalty(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen))
     elif top_p < 1.0 or min_p > 0.0:
         check(_lib.load().dh_sample_rows_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))

@@ -34,7 +34,7 @@ typedef uint16_t dh_bf16;
  * dh_engine_set_no_repeat_ngram (no-repeat n-grams); dh_sample_bf16_stop, dh_sample_rows_bf16_stop, dh_beam_select_bf16_stop and
  * dh_engine_set_stop (stop conditions); dh_sample_bf16_nucleus, dh_sample_rows_bf16_nucleus and dh_engine_set_nucleus (nucleus
  * and min-p sampling); dh_engine_fork_slots (sampled candidates); dh_sample_bf16_penalty, dh_sample_rows_bf16_penalty and
- * dh_engine_set_penalties (penalties). */
+ * dh_engine_set_penalties (penalties); dh_sample_bf16_bias, dh_sample_rows_bf16_bias and dh_engine_set_bias (contextual biasing). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -682,6 +682,60 @@ int dh_sample_rows_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* token
                                 const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
                                 float top_p, float min_p, const dh_penalty_args* penalties);
 
+/* Contextual biasing (the "hot words" of the speech stacks; with one-id entries the "logit_bias" of the text-generation servers): a list
+ * of phrases whose continuations get a logit bonus while decoding.  ONE definition for every entry below.
+ * The bias specification (dh_bias_spec) of a call is shared by all its sequences and holds 1 .. DH_MAX_BIAS_ENTRIES entries.  Entry e is
+ *   len_e in 1 .. DH_MAX_BIAS_LEN token ids, each in [0, vocab), and one finite fp32 boost b_e of either sign: on the device an int32
+ *   [n, DH_MAX_BIAS_LEN] table (row e's first len_e places count), the int32 lengths and the fp32 boosts; the host copies of the three are
+ *   what the argument checks read.  A one-id entry is a plain logit bias.  Null or n = 0 is off: the call it always was.
+ * Which ids are boosted at a pick: let g[0..m) = tokens[u, start[u] : length[u]] be what sequence u has generated; the prompt is excluded,
+ *   as for no_repeat_ngram and the penalties (a correction copies its prompt, so the prompt neither starts nor continues a match).
+ *   Entry e PROPOSES id ids_e[k] at depth k (0 <= k < len_e) when k <= m and g[m-k .. m) == ids_e[0 .. k).  Depth 0 always matches: the
+ *   first id of every entry is always proposed.  A whole emitted phrase proposes nothing further (k < len_e); matching starts again
+ *   from depth 0.  There is NO FAILURE ARC: a bonus that was given is not taken back when the phrase is abandoned, and the boost does not
+ *   grow with the depth.
+ *   The boost of id t is B_t, the maximum of b_e over all (e, k) that propose t.  A maximum is exact in any order: the sequence's block
+ *   takes it with an integer atomic max on an order-preserving key of the float; no floating-point atomic and no order-dependent sum
+ *   decides anything.
+ * What the pick sees: the pick is, bit for bit, the existing pick (the arg-max and the seeded draw alike) on a copy of the logits row in
+ *   which every column t with a boost holds bf16(y + B_t): one fp32 add, never contracted, then round to nearest even.  y is the fp32
+ *   value the column held just in front of its final bf16 rounding: fp32(row[t]) when t is not in the penalised history (no penalty is
+ *   on, or c_t = 0: an id that is boosted but never generated takes no penalty, not even the repetition rule at a count of 0), and the z
+ *   of "Penalties" when it is.  The boost is applied before temperature, top_k, top_p and min_p.  A column the mask disallows or the
+ *   n-gram ban removes stays -inf; a raw -inf stays -inf and a NaN a NaN.  Log-probabilities and alternatives stay the raw row's.  Stop
+ *   conditions never change a pick.  The logits buffer is read only.
+ *   Verify steps (a position's tail would have to include the launch's own picks) and beam steps (a beam's history lives on the host)
+ *   take no bias: dh_engine_decode_spec and dh_engine_decode_beam refuse while one is set.
+ * Refused before any launch, with the value in the message: vocab above 131072, more than DH_MAX_BIAS_ENTRIES entries, a length outside
+ *   1 .. DH_MAX_BIAS_LEN, an id outside the vocabulary, a boost that is not finite, a bias without `start`, and, with a penalty on, tok_ld
+ *   plus the number of ids in all entries above DH_MAX_PENALTY_HISTORY (the ids share the penalties' tables, which keep their size; a
+ *   bias alone always fits, 256 x 8 = 2048). */
+#define DH_MAX_BIAS_ENTRIES 256
+#define DH_MAX_BIAS_LEN 8
+typedef struct dh_bias_spec {
+    const int32_t* ids;         /* device, [n, DH_MAX_BIAS_LEN] */
+    const int32_t* len;         /* device, [n], each 1 .. DH_MAX_BIAS_LEN */
+    const float* boost;         /* device, [n], finite */
+    const int32_t* h_ids;       /* host copies of the three: what the checks read */
+    const int32_t* h_len;
+    const float* h_boost;
+    int n;                      /* 0 (off) .. DH_MAX_BIAS_ENTRIES */
+} dh_bias_spec;
+
+/* dh_sample_bf16_penalty / dh_sample_rows_bf16_penalty with the bias; everything else stays nullable / 0 / 1 / 0, and `bias` null or
+ * without an entry makes each the entry it extends.  `start` is needed when a bias is given, by both. */
+int dh_sample_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                        int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                        uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                        float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias);
+int dh_sample_rows_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                             int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                             int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                             void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                             const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                             float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -1040,6 +1094,13 @@ int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p);
  * dh_engine_decode_beam refuse, and a decode call with tok_ld above DH_MAX_PENALTY_HISTORY is refused before anything is launched.
  * Refused like dh_sample_bf16_penalty. */
 int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* penalties, const int32_t* start);
+/* The bias (see "Contextual biasing" above; null or no entry clears it, the default) for later dh_engine_decode and dh_engine_decode_rows
+ * calls.  The spec's device arrays and `start` ([n_seq] int32 on the device, the array the other history readers take) are the caller's to
+ * keep alive while set; the host copies are read here only.  The pointers, the counts and `start` are part of the captured step's key:
+ * with none set a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec and dh_engine_decode_beam refuse, and,
+ * with penalties set as well, so does a decode call whose tok_ld plus the entries' ids pass DH_MAX_PENALTY_HISTORY.  Refused like
+ * dh_sample_bf16_bias. */
+int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const int32_t* start);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
