@@ -39,6 +39,11 @@ class BeamState(C.Structure):
                                  "fin_score", "fin_lp", "n_fin")]
 
 
+class BeamHist(C.Structure):
+    """dh_beam_hist: the history planes of a beam search call and their ban (include/dualhyp_hip.h, "Beam histories")"""
+    _fields_ = [("tokens", P), ("ngram", C.c_int)]
+
+
 class StopSpec(C.Structure):
     """dh_stop_spec: a stop specification (include/dualhyp_hip.h, "Stop conditions"); h_seq_len is a host pointer"""
     _fields_ = [("set", P), ("seqs", P), ("h_seq_len", P), ("n_seqs", C.c_int32)]
@@ -119,6 +124,8 @@ SIGNATURES = {
     "dh_sample_rows_bf16_bias": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
                                      F, F, C.POINTER(PenaltyArgs), C.POINTER(BiasSpec)]),
     "dh_beam_select_bf16_stop": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P, P]),
+    "dh_beam_select_bf16_hist": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P,
+                                     C.POINTER(BeamHist), P]),
     "dh_token_top_logprobs_bf16_mask": (I, [P, I, I, P, P, I, P, I, I, P]),
     "dh_beam_select_bf16_mask": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, P]),
     "dh_quant_rows_fp8": (I, [P, P, P, I, I, P]),
@@ -159,6 +166,7 @@ SIGNATURES = {
     "dh_engine_set_token_mask": (I, [P, P, I]),
     "dh_engine_set_no_repeat_ngram": (I, [P, I, P]),
     "dh_engine_set_stop": (I, [P, C.POINTER(StopSpec), P, P]),
+    "dh_engine_set_beam_history": (I, [P, P, I]),
     "dh_engine_set_nucleus": (I, [P, F, F]),
     "dh_engine_set_penalties": (I, [P, C.POINTER(PenaltyArgs), P]),
     "dh_engine_set_bias": (I, [P, C.POINTER(BiasSpec), P]),

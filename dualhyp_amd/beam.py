@@ -3,7 +3,9 @@ with the device's per-step records — backtracking, completing the pool and ran
 
 The selection itself runs on the device (dh_beam_select_bf16; include/dualhyp_hip.h, "Beam search", is the definition and
 tests/beam_reference.py its host model).  Histories are never gathered there: a step records, per live beam, the token, the beam of
-the step before that it continues, the token's log-probability and the cumulative score; a hypothesis is read off backwards.
+the step before that it continues, the token's log-probability and the cumulative score; a hypothesis is read off backwards.  With history="device" the device keeps
+the live beams' tokens as well (BeamState.history_buffer(); "Beam histories" of the header), for its own ban and stop-sequence tests;
+the host still reads hypotheses off the records.
 """
 from __future__ import annotations
 
@@ -13,6 +15,10 @@ import torch
 
 MAX_BEAMS = 4             # DH_MAX_BEAMS: a row offers 2 W <= DH_MAX_TOP_LOGPROBS candidates
 MAX_BEAM_ROWS = 2048      # the streaming single-token step's row limit (engine.hip MAX_DECODE_ROWS)
+
+HISTORIES = ("host", "device")      # beam_search_batch(history=), --beam_history
+# the closing clause of the two refusals that device histories lift (no_repeat_ngram, stop sequences)
+HISTORY_HINT = '; history="device" (--beam_history device) keeps the beams\' histories on the device and lifts this'
 
 _I32 = ("n_steps", "done", "n_fin", "fin_step", "fin_parent", "beam_tok", "beam_parent")
 _F32 = ("cum", "fin_score", "fin_lp", "beam_lp", "beam_cum")
@@ -64,12 +70,20 @@ class BeamState:
                 setattr(self, n, v.view(shapes[n]))
         self._c = None
         self.fin_tok = None         # int32 [n_utt, W] beside fin_step, under a stop set only: the id that ended pool entry k
+        self.history = None         # int64 [2, n_utt, W, max_new], under device histories only (history_buffer)
 
     def fin_tok_buffer(self) -> torch.Tensor:
         """fin_tok, made at its first use (-1: no entry): what dh_beam_select_bf16_stop and dh_engine_set_stop write."""
         if self.fin_tok is None:
             self.fin_tok = torch.full((self.n_utt, self.W), -1, dtype=torch.int32, device=self.device)
         return self.fin_tok
+
+    def history_buffer(self) -> torch.Tensor:
+        """The history planes, made at their first use: int64 [2, n_utt, W, max_new], plane t & 1 holding the live beams' tokens behind
+        step t ("Beam histories" of the header): what dh_beam_select_bf16_hist and dh_engine_set_beam_history read and write."""
+        if self.history is None:
+            self.history = torch.zeros((2, self.n_utt, self.W, self.max_new), dtype=torch.int64, device=self.device)
+        return self.history
 
     def c_struct(self):
         from . import _lib
@@ -87,6 +101,9 @@ class BeamState:
                 out[n] = v.view(self.shapes[n]).tolist()      # a Python float holds an fp32 value exactly
         if self.fin_tok is not None:                          # a call under a stop set: one small copy more
             out["fin_tok"] = self.fin_tok.tolist()
+        if self.history is not None:                          # device histories: per utterance the plane its last step wrote,
+            planes = self.history.cpu()                       # [W][max_new], the first n_steps ids of a row are the beam's tokens
+            out["history"] = [planes[(int(n) - 1) & 1, u].tolist() for u, n in enumerate(out["n_steps"])]
         return out
 
 

@@ -277,6 +277,25 @@ struct dh_stop_args {
     __host__ __device__ bool on() const { return set != nullptr || n_seqs != 0; }
     bool operator==(const dh_stop_args& o) const { return set == o.set && seqs == o.seqs && lens == o.lens && n_seqs == o.n_seqs; }
 };
+// Stop conditions (include/dualhyp_hip.h): w[0] is the pick that has just been appended, w[k] the generated token k places before it
+// (-1 where that place is prompt), m the tokens generated with the pick counted.  True when the pick is in the stop set or the
+// generated text now ends on one of the stop sequences.  A few uniform loads behind the pick; it never changes one.  Shared by the
+// sampling kernels' tails (sampling.hip) and the beam merge under device histories (beam.hip).
+__device__ __forceinline__ bool stop_hit(const dh_stop_args& sa, const int (&w)[DH_MAX_STOP_LEN], int m) {
+    const int t = w[0];
+    if (sa.set && ((sa.set[t >> 5] >> (t & 31)) & 1u)) return true;
+    for (int s = 0; s < sa.n_seqs; ++s) {
+        const int L = (int)((sa.lens >> (4 * s)) & 15u);
+        if (L > m) continue;                                    // a match never reaches back into the prompt
+        const int32_t* q = sa.seqs + s * DH_MAX_STOP_LEN;
+        bool eq = true;
+#pragma unroll
+        for (int k = 0; k < DH_MAX_STOP_LEN; ++k)
+            if (k < L && q[L - 1 - k] != w[k]) eq = false;
+        if (eq) return true;
+    }
+    return false;
+}
 // the checks of every entry that takes a dh_stop_spec (capi.hip); start_ok: the entry has a way to the prompt lengths
 int dh_stop_pack(const char* name, const dh_stop_spec* stop, bool start_ok, dh_stop_args& out);
 
@@ -351,9 +370,16 @@ int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids
                         const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream);
 
 // the selection step of beam search (beam.hip, dh_beam_select_bf16), as the engine's captured step calls it
+// stop: its set ends a hypothesis as the EOS does, its sequences as well under device histories; hist (nullable, int64
+// [2][n_utt * W][max_new], "Beam histories" of the header) with ngram (0: no ban): null is the step without histories, the launches it
+// always made
 int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
                         const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, const uint32_t* mask,
-                        int mask_ld, const uint32_t* stop_set, int32_t* fin_tok, void* stream);
+                        int mask_ld, const dh_stop_args& stop, int32_t* fin_tok, void* stream, int64_t* hist = nullptr, int ngram = 0);
+// its candidates under a ban (sampling.hip, beam_top_hist_kernel)
+int dh_beam_top_hist_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int32_t* out_ids,
+                          float* out_lp, const uint32_t* mask, int mask_ld, const int64_t* hist, int ngram, const int32_t* n_steps,
+                          const int32_t* done, void* stream);
 
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads

@@ -50,6 +50,8 @@ struct dh_engine {
     dh_stop_args stop;                                  // dh_engine_set_stop: the stop specification (all zero: off), the caller's [n_seq] prompt
     const int32_t* stop_start = nullptr;                // lengths its sequences count from, and a beam call's [n_utt, W] ending ids
     int32_t* stop_fin_tok = nullptr;
+    int64_t* beam_hist = nullptr;                       // dh_engine_set_beam_history: the caller's [2][n_utt * W][max_new] history planes (null: off)
+    int beam_hist_ngram = 0;                            // and the beam steps' no_repeat_ngram (0: no ban)
     dh_nucleus_args nuc;                                // dh_engine_set_nucleus: top_p / min_p of later decode / decode_rows calls (default: off)
     dh_penalty_args pen = DH_PENALTY_OFF;               // dh_engine_set_penalties: the penalties of later decode / decode_rows calls (default: off)
     const int32_t* pen_start = nullptr;                 // and the caller's [n_seq] prompt lengths their history counts from
@@ -98,6 +100,7 @@ struct dh_engine {
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows
         int beam_w; dh_beam_state beam;
+        int64_t* beam_hist; int beam_ngram;                   // dh_engine_set_beam_history: the history planes and their ban (null / 0 in every other key)
         bool operator==(const GKey& k) const {
             return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
@@ -107,7 +110,7 @@ struct dh_engine {
                    mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && stop == k.stop && stop_start == k.stop_start &&
                    stop_fin_tok == k.stop_fin_tok && nuc == k.nuc && dh_penalty_same(pen, k.pen) && pen_start == k.pen_start &&
                    bias == k.bias && bias_start == k.bias_start &&
-                   beam_w == k.beam_w &&
+                   beam_w == k.beam_w && beam_hist == k.beam_hist && beam_ngram == k.beam_ngram &&
                    memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
@@ -1010,7 +1013,7 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     int rc;
     if ((rc = run_model(e, e->dec_ids, rows, rows, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if ((rc = dh_beam_select_impl(e->logits, D.vocab, rows / W, W, W, k.max_new, k.eos, 0, e->step_dev, k.beam, e->beam_cand_ids,
-                                  e->beam_cand_lp, k.mask, k.mask_ld, k.stop.set, k.stop_fin_tok, s))) return rc;
+                                  e->beam_cand_lp, k.mask, k.mask_ld, k.stop, k.stop_fin_tok, s, k.beam_hist, k.beam_ngram))) return rc;
     if (W == 1) return 0;                                   // a single beam continues itself
     const int tile_units = D.head_size * 4, nt_max = std::min(beam_tiles(k.max_new), e->s_max / 32);
     const dim3 grid(cdiv(nt_max * tile_units, 256), 2 * D.n_layer * D.n_groups, rows);
@@ -1442,13 +1445,20 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
              (int)rows, e->row_cap, e->max_tokens);
     DH_CHECK(e->ngram == 0, "dh_engine_decode_beam: no_repeat_ngram=%d is set; a beam's history lives on the host, so the device cannot "
              "form its ban set", e->ngram);
-    DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_beam: penalties are set (repetition=%g, frequency=%g, presence=%g); a beam's history "
-             "lives on the host, so the device cannot count it", (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence);
-    DH_CHECK(e->bias.n == 0, "dh_engine_decode_beam: a bias of %d entries is set; a beam's history lives on the host, so the device "
-             "cannot match it", e->bias.n);
-    DH_CHECK(e->stop.n_seqs == 0, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
+    // under device histories (dh_engine_set_beam_history) the two that stay refused are refused for what they would mean, not for where
+    // a beam's text lives: a penalised or boosted value would rank the candidates and be summed into the scores
+    DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_beam: penalties are set (repetition=%g, frequency=%g, presence=%g); %s",
+             (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence,
+             e->beam_hist ? "a penalised logit would change what a candidate's rank and a beam's score mean, which beam search does not define"
+                          : "a beam's history lives on the host, so the device cannot count it");
+    DH_CHECK(e->bias.n == 0, "dh_engine_decode_beam: a bias of %d entries is set; %s", e->bias.n,
+             e->beam_hist ? "a boosted logit would change what a candidate's rank and a beam's score mean, which beam search does not define"
+                          : "a beam's history lives on the host, so the device cannot match it");
+    DH_CHECK(e->stop.n_seqs == 0 || e->beam_hist, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
              "cannot match a sequence against it (the stop set alone goes with beam search)", e->stop.n_seqs);
-    DH_CHECK(!e->stop.set || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
+    DH_CHECK(!e->stop.on() || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
+    DH_CHECK(e->beam_hist_ngram == 0 || e->d.vocab <= 131072, "dh_engine_decode_beam: vocab=%d exceeds the 131072 ids of the sampler's LDS row "
+             "(beam history ngram=%d)", e->d.vocab, e->beam_hist_ngram);
     DH_CHECK(e->d.vocab >= 2 * W, "dh_engine_decode_beam: vocab=%d is below the 2 W = %d candidates of a row", e->d.vocab, 2 * W);
     DH_CHECK(!e->fp8, "dh_engine_decode_beam: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(!e->kv8, "dh_engine_decode_beam: the re-parenting copies bf16 cache tiles; an fp8 KV cache is not supported");
@@ -1465,8 +1475,19 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
                         prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                         e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, dh_nucleus_args{}, DH_PENALTY_OFF, nullptr,
-                        dh_bias_args{}, nullptr, W, *st};
+                        dh_bias_args{}, nullptr, W, *st, e->beam_hist, e->beam_hist_ngram};
     return launch_steps(e, key, n_steps, s);
+}
+
+extern "C" int dh_engine_set_beam_history(dh_engine* e, int64_t* tokens, int ngram) {
+    DH_CHECK(e, "dh_engine_set_beam_history: null engine");
+    DH_CHECK(ngram >= 0 && ngram <= 8, "dh_engine_set_beam_history: ngram=%d is not in 0 .. 8", ngram);
+    DH_CHECK(ngram == 0 || e->d.vocab <= 131072, "dh_engine_set_beam_history: ngram=%d with vocab=%d, which exceeds the 131072 ids of the "
+             "sampler's LDS row", ngram, e->d.vocab);
+    DH_CHECK(tokens || ngram == 0, "dh_engine_set_beam_history: ngram=%d without the history planes (null tokens)", ngram);
+    e->beam_hist = tokens;
+    e->beam_hist_ngram = tokens ? ngram : 0;
+    return 0;
 }
 
 extern "C" int dh_engine_set_logprobs(dh_engine* e, float* buf) {
@@ -1511,7 +1532,7 @@ extern "C" int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const 
     if (int rc = dh_stop_pack("dh_engine_set_stop", stop, start != nullptr, sa)) return rc;
     e->stop = sa;
     e->stop_start = sa.n_seqs ? start : nullptr;
-    e->stop_fin_tok = sa.set ? beam_fin_tok : nullptr;
+    e->stop_fin_tok = sa.on() ? beam_fin_tok : nullptr;       // sequences end pool entries too, under device histories
     return 0;
 }
 

@@ -328,8 +328,10 @@ constexpr int MAX_NGRAM = 8;
 // g[i .. i + ngram - 1) == g[m - ngram + 1 .. m), and is the start row again when that left no bit below vocab (the fallback: the pick
 // is never taken from an empty set).  Every thread gets the LDS row, in the mask row's layout with the bits at and behind vocab clear;
 // it holds until the block's next call, which the caller separates from the pick's last read by a barrier (pick_token ends on one).
-template <bool MASK>
-__device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int ngram, int vocab, const uint32_t* __restrict__ mrow) {
+// KEEP (the beam candidates, "Beam histories"): the fallback is taken when fewer than `keep` bits are left, not when none is.
+template <bool MASK, bool KEEP = false>
+__device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int ngram, int vocab, const uint32_t* __restrict__ mrow,
+                                                   int keep = 1) {
     __shared__ uint32_t s_row[BAN_MAX_VOCAB / 32];
     __shared__ int s_cnt[NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -366,7 +368,9 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
     __syncthreads();
     cnt = 0;
     for (int w = 0; w < NT / 64; ++w) cnt += s_cnt[w];
-    if (cnt == 0) {                                     // the same for every thread
+    bool refill = cnt == 0;                             // the same for every thread
+    if constexpr (KEEP) refill = cnt < keep;
+    if (refill) {
         for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
         __syncthreads();
     }
@@ -744,26 +748,7 @@ __device__ __forceinline__ void store_top(int32_t* __restrict__ top_ids, float* 
     }
 }
 
-// Stop conditions (include/dualhyp_hip.h): w[0] is the pick that has just been appended, w[k] the generated token k places before it
-// (-1 where that place is prompt), m the tokens generated with the pick counted.  True when the pick is in the stop set or the
-// generated text now ends on one of the stop sequences.  A few uniform loads behind the pick; it never changes one.
-__device__ __forceinline__ bool stop_hit(const dh_stop_args& sa, const int (&w)[DH_MAX_STOP_LEN], int m) {
-    const int t = w[0];
-    if (sa.set && ((sa.set[t >> 5] >> (t & 31)) & 1u)) return true;
-    for (int s = 0; s < sa.n_seqs; ++s) {
-        const int L = (int)((sa.lens >> (4 * s)) & 15u);
-        if (L > m) continue;                                    // a match never reaches back into the prompt
-        const int32_t* q = sa.seqs + s * DH_MAX_STOP_LEN;
-        bool eq = true;
-#pragma unroll
-        for (int k = 0; k < DH_MAX_STOP_LEN; ++k)
-            if (k < L && q[L - 1 - k] != w[k]) eq = false;
-        if (eq) return true;
-    }
-    return false;
-}
-
-// the same for a pick stored at place n of the sequence's token row `row` whose prompt is p0 tokens long: the window comes from the
+// stop_hit (common.h) for a pick stored at place n of the sequence's token row `row` whose prompt is p0 tokens long: the window comes from the
 // places before n, which earlier launches wrote
 __device__ __forceinline__ bool stop_hit_at(const dh_stop_args& sa, const int64_t* row, int n, int p0, int choice) {
     int w[DH_MAX_STOP_LEN];
@@ -964,6 +949,33 @@ __global__ __launch_bounds__(NT) void token_top_logprobs_kernel(const bf16_t* __
     float mx, tot;
     row_logsum(lg, vocab, mx, tot);
     row_top<MASK>(lg, vocab, k, mx, tot, ti, tl, MASK ? mask + (size_t)(r / rows_per_mask) * mask_ld : nullptr);
+    if (threadIdx.x == 0) store_top(out_ids, out_lp, (size_t)r, k, ti, tl);
+}
+
+// The candidates of a beam step under no_repeat_ngram (include/dualhyp_hip.h, "Beam histories"): row r = u * rows_per_utt + b of the
+// launch is live beam b of utterance u, its history the m = n_steps[u] tokens of row u * W + b of plane (m - 1) & 1 of `hist`
+// ([2][n_utt * W][max_new]) — the plane the step before wrote; this launch writes none.  The k = 2 W candidates are
+// token_top_logprobs_kernel<true>'s under the LDS row of ban_row: the mask row (MASK) or all ones, minus the banned ids, and the start
+// row again where fewer than k ids are left.  A done utterance's rows return at once: nothing reads their candidates.
+template <bool MASK>
+__global__ __launch_bounds__(NT) void beam_top_hist_kernel(const bf16_t* __restrict__ logits, int vocab, int k,
+                                                           int32_t* __restrict__ out_ids, float* __restrict__ out_lp,
+                                                           const uint32_t* __restrict__ mask, int mask_ld, int rows_per_utt, int W,
+                                                           int max_new, const int64_t* __restrict__ hist, int ngram,
+                                                           const int32_t* __restrict__ n_steps, const int32_t* __restrict__ done) {
+    const int r = blockIdx.x, u = r / rows_per_utt, b = r % rows_per_utt;
+    if (done[u]) return;                                                    // the same for every thread
+    int m = n_steps[u];
+    m = m < 0 ? 0 : (m > max_new ? max_new : m);                            // never a read outside the row
+    const size_t plane = (size_t)(gridDim.x / rows_per_utt) * W * max_new;
+    const int64_t* g = hist + (size_t)((m - 1) & 1) * plane + ((size_t)u * W + b) * max_new;
+    const bf16_t* lg = logits + (size_t)r * vocab;
+    const uint32_t* row = ban_row<MASK, true>(g, m, ngram, vocab, MASK ? mask + (size_t)u * mask_ld : nullptr, k);
+    const int32_t* ti = nullptr;
+    const float* tl = nullptr;
+    float mx, tot;
+    row_logsum(lg, vocab, mx, tot);
+    row_top<true>(lg, vocab, k, mx, tot, ti, tl, row);
     if (threadIdx.x == 0) store_top(out_ids, out_lp, (size_t)r, k, ti, tl);
 }
 
@@ -1304,6 +1316,22 @@ extern "C" int dh_token_top_logprobs_bf16_mask(const dh_bf16* logits, int vocab,
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(token_top_logprobs_kernel<true>, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, k, out_ids, out_lp,
                        mask, mask_ld, rows_per_mask);
+    DH_LAUNCH_CHECK();
+    return 0;
+}
+
+// the candidates of a beam step whose rows carry device histories and a ban (beam.hip, dh_beam_select_bf16_hist); the caller has
+// checked the shapes, ngram in 1 .. 8 and vocab <= 131072
+int dh_beam_top_hist_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int32_t* out_ids,
+                          float* out_lp, const uint32_t* mask, int mask_ld, const int64_t* hist, int ngram, const int32_t* n_steps,
+                          const int32_t* done, void* stream) {
+    DH_CHECK(ngram >= 1 && ngram <= MAX_NGRAM && vocab <= BAN_MAX_VOCAB && 2 * W <= MAX_TOP && hist, "dh_beam_select_bf16_hist: bad ban arguments");
+    if (mask)
+        hipLaunchKernelGGL(beam_top_hist_kernel<true>, dim3(n_utt * rows_per_utt), dim3(NT), 0, (hipStream_t)stream, logits, vocab, 2 * W,
+                           out_ids, out_lp, mask, mask_ld, rows_per_utt, W, max_new, hist, ngram, n_steps, done);
+    else
+        hipLaunchKernelGGL(beam_top_hist_kernel<false>, dim3(n_utt * rows_per_utt), dim3(NT), 0, (hipStream_t)stream, logits, vocab, 2 * W,
+                           out_ids, out_lp, nullptr, 0, rows_per_utt, W, max_new, hist, ngram, n_steps, done);
     DH_LAUNCH_CHECK();
     return 0;
 }

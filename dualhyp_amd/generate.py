@@ -582,7 +582,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
 @torch.inference_mode()
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
                       length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
-                      token_mask=None, no_repeat_ngram: int = 0, stop=None, bias=None):
+                      token_mask=None, no_repeat_ngram: int = 0, stop=None, bias=None, history: str = "host"):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
@@ -612,26 +612,39 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     2 W allowed ids of its raw row's order, each with the raw row's log-probability ("Token masks" of the header), so every row
     allows at least 2 W ids (checked before anything is launched); everything behind the candidates is unchanged.
 
-    no_repeat_ngram: refused unless 0 — a beam's history is re-parented on the host, so the device cannot form a beam's ban set
-    (DESIGN.md §9).
+    no_repeat_ngram: with history="host" refused unless 0 — a beam's history is re-parented on the host, so the device cannot form
+    a beam's ban set; see `history`.
 
     stop (as in generate_batch, the stop set only): a candidate whose id is in the set ends its hypothesis into the pool exactly as
-    the EOS does — same place rule, score and pool order — and the id stays in the hypothesis.  Stop sequences are refused before
-    anything is launched: the beams' histories live on the host.
+    the EOS does — same place rule, score and pool order — and the id stays in the hypothesis.  With history="host" stop sequences
+    are refused before anything is launched: the beams' histories live on the host; see `history`.
 
-    bias: refused unless None or empty, for the same reason."""
+    bias: refused unless None or empty, for the same reason.
+
+    history: "host" (the default: everything above, the launches and the refusals it always had) or "device" ("Beam histories" of
+    the header): the live beams' tokens are kept in two int64 planes on the device, re-parented by the selection kernel itself, and
+    the two refusals above are lifted — no_repeat_ngram 1 .. 8 bans on a beam's own generated tokens (its candidates are the first
+    2 W ids that the mask allows and the ban leaves; a row left with fewer than 2 W ignores the ban at that step), and stop
+    sequences end a hypothesis whose own text completes one ("stop", the ids stay in its tokens).  The state of return_state carries
+    the planes (host["history"][u][w][:n_steps[u]] is live beam w's text).  A bias and penalties stay refused: they would change
+    what a candidate's rank and a beam's score mean."""
+    if history not in _beam.HISTORIES:
+        raise ValueError(f'history is "host" or "device", not {history!r}')
+    on_device = history == "device"
     if _check_bias(bias) is not None:
-        raise ValueError(f"a bias of {len(bias)} entries does not go with beam search: {_bias.BEAM_REFUSAL}; it runs under generate_batch "
-                         "and generate_stream")
+        raise ValueError(f"a bias of {len(bias)} entries does not go with beam search: " +
+                         ("a boosted logit would change what a candidate's rank and a beam's score mean" if on_device else _bias.BEAM_REFUSAL) +
+                         "; it runs under generate_batch and generate_stream")
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     if stop is not None and not isinstance(stop, _stop.StopSpec):
         stop = _stop.compile_stop(*_stop.split_entries(stop), vocab=model.config.padded_vocab_size)
-    if stop is not None and stop.sequences:
-        raise ValueError(_stop.BEAM_REFUSAL)
-    if _ngram.check_ngram(no_repeat_ngram):
+    if stop is not None and stop.sequences and not on_device:
+        raise ValueError(_stop.BEAM_REFUSAL + _beam.HISTORY_HINT)
+    ngram = _ngram.check_ngram(no_repeat_ngram, model.config.padded_vocab_size if on_device else 0)
+    if ngram and not on_device:
         raise ValueError(f"no_repeat_ngram={no_repeat_ngram} does not go with beam search: the beams' histories live on the host, so the "
-                         "sampling kernels cannot form a beam's ban set; it runs under generate_batch and generate_stream")
+                         "sampling kernels cannot form a beam's ban set; it runs under generate_batch and generate_stream" + _beam.HISTORY_HINT)
     W = _beam.check_arguments(model, num_beams, B)
     length_penalty = _beam.check_length_penalty(length_penalty)
     lens = [int(p.numel()) for p in prompts]
@@ -648,6 +661,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     eng.set_rsqrt_emulation(0, whole_call=False)
     eng.reserve_beams(W, max_new_tokens)
     state = _beam.BeamState(B, W, max_new_tokens, dev)
+    hist = state.history_buffer() if on_device else None
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -659,14 +673,16 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     if W > 1:
         for u in range(B):      # positions at or behind the prompt's end are overwritten before causality lets anything read them
             eng.copy_prefix(u * W, list(range(u * W + 1, (u + 1) * W)), -(-lens[u] // 32) * 32)
-    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0, mask=mask, stop=stop)
+    ops.beam_select(last, state, rows_per_utt=1, eos_id=eos_id, step=0, mask=mask, stop=stop, history=hist, no_repeat_ngram=ngram)
     if ev:
         ev[1].record()
     step = 1
     if mask is not None:
         eng.set_token_mask(mask)        # part of the captured step's key; without it the call runs the steps it always ran
     if stop is not None:
-        eng.set_stop(stop, None, state.fin_tok_buffer())     # likewise
+        eng.set_stop(stop, plen if stop.sequences else None, state.fin_tok_buffer())     # likewise
+    if on_device:
+        eng.set_beam_history(hist, ngram)                   # likewise
     try:
         while step < max_new_tokens:
             c = max_new_tokens - step if eos_id is None and stop is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
@@ -679,6 +695,8 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
             eng.set_token_mask(None)
         if stop is not None:
             eng.set_stop(None)
+        if on_device:
+            eng.set_beam_history(None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these hypotheses; a later cached forward must start at 0

@@ -495,6 +495,8 @@ class _Engine:
         assert prompt_len.dtype == torch.int32 and prompt_len.is_cuda and prompt_len.is_contiguous() and prompt_len.numel() == state.n_utt
         mask = getattr(self, "_token_mask", None)
         assert mask is None or mask.size(0) == state.n_utt, "the token mask has one row per utterance"
+        hist = getattr(self, "_beam_history", None)
+        assert hist is None or tuple(hist.shape) == (2, state.n_utt, state.W, state.max_new), "the history planes are another state's"
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_decode_beam(
                 self.handle, C.byref(state.c_struct()), prompt_len.data_ptr(), state.n_utt, state.W, state.max_new, int(n_steps),
@@ -559,6 +561,17 @@ class _Engine:
                                                None if stop is None or start is None else start.data_ptr(),
                                                None if stop is None or beam_fin_tok is None else beam_fin_tok.data_ptr()))
         self._stop = (stop, start, beam_fin_tok) if stop is not None else None
+
+    def set_beam_history(self, history: Optional[torch.Tensor], ngram: int = 0) -> None:
+        """Device histories for later decode_beam calls (dh_engine_set_beam_history; include/dualhyp_hip.h, "Beam histories"): the
+        int64 [2, n_utt, W, max_new] planes of a dualhyp_amd.beam.BeamState (history_buffer()) and the beam steps' no_repeat_ngram,
+        0 .. 8; None turns it off.  While set, decode_beam bans under ngram and takes the stop sequences of set_stop; the planes and
+        ngram are part of a beam step's key.  The caller keeps the planes alive while set."""
+        if history is not None and (history.dtype != torch.int64 or not history.is_cuda or not history.is_contiguous() or history.dim() != 4
+                                    or history.size(0) != 2):
+            raise TypeError("set_beam_history takes a contiguous int64 [2, n_utt, W, max_new] tensor on the GPU, or None")
+        _lib.check(self.lib.dh_engine_set_beam_history(self.handle, None if history is None else history.data_ptr(), int(ngram)))
+        self._beam_history = history
 
     def set_nucleus(self, top_p: Optional[float] = None, min_p: Optional[float] = None) -> None:
         """top_p and min_p (include/dualhyp_hip.h, "Nucleus and min-p") for later decode / decode_rows calls with top_k != 1; None, 1.0

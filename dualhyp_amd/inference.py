@@ -382,6 +382,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     constrain = getattr(args, "constrain", "off") == "prompt"
     extra = read_token_ids(args.constrain_extra) if constrain and getattr(args, "constrain_extra", None) else ()
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
+    # --beam_history device: the beams' histories on the device; the default run passes no keyword at all
+    hkw = dict(history="device") if getattr(args, "beam_history", "host") == "device" else {}
     stop = stop_from_args(args, tokenizer, model.config.padded_vocab_size, model.transformer.wte.weight.device)
     skw = dict(stop=stop, return_state=True) if stop is not None else {}       # the reasons are read from the state's done flags
     from .penalty import record as penalty_record
@@ -408,7 +410,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
                                      prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask,
-                                     no_repeat_ngram=ngram, stop=stop)
+                                     no_repeat_ngram=ngram, stop=stop, **hkw)
             return {"beams": hyps, "logprobs": want_lp}
         if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
             cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
@@ -521,6 +523,12 @@ def build_parser():
                    help="W in 2..4: beam search over W hypotheses per utterance (beam_search_batch), --decode_batch // W utterances at a "
                         "time; the prediction is the best hypothesis and every record gains beams, the ranked hypotheses with text, "
                         "sum_logprob, avg_logprob and finished.  Default 1: greedy decoding, the path it always was")
+    p.add_argument("--beam_history", choices=("host", "device"), default="host",
+                   help="with --num_beams W > 1: device keeps every live beam's generated tokens in two planes on the device, "
+                        "re-parented by the selection kernel, which lets --no_repeat_ngram (the ban on a beam's own text; the records gain "
+                        "no_repeat_ngram and ngram_bans of the best hypothesis) and the stop sequences of --stop_file run under beam "
+                        "search; penalties and --bias_file stay refused there: they would change what a candidate's rank means.  Default "
+                        "host: the steps, and the refusals, it always had")
     p.add_argument("--num_samples", type=int, default=1, metavar="N",
                    help="N in 2..8 (with --top_k other than 1): N sampled candidates per utterance from one prefill of its prompt "
                         "(sample_batch: the prompt's KV cache is forked into N decode slots by one launch), --decode_batch // N "
@@ -641,10 +649,13 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             args.select = "avg_logprob"
     if not 0 <= args.no_repeat_ngram <= 8:
         p.error(f"--no_repeat_ngram {args.no_repeat_ngram}: N is 0 (off) or 1..8")
-    if args.no_repeat_ngram and args.num_beams > 1:         # beam_search_batch refuses it too; here nothing has been loaded yet
+    dev_hist = args.beam_history == "device"                # the beams' histories on the device lift the next two refusals
+    if dev_hist and args.num_beams < 2:
+        p.error("--beam_history device goes with --num_beams W > 1: greedy decoding keeps its history in the token buffer")
+    if args.no_repeat_ngram and args.num_beams > 1 and not dev_hist:    # beam_search_batch refuses it too; here nothing has been loaded yet
         p.error(f"--no_repeat_ngram {args.no_repeat_ngram} does not go with --num_beams {args.num_beams}: the beams' histories live on "
                 "the host, so the sampling kernels cannot form a beam's ban set")
-    if args.stop_file and args.num_beams > 1:               # beam_search_batch refuses it too; here nothing has been loaded yet
+    if args.stop_file and args.num_beams > 1 and not dev_hist:          # beam_search_batch refuses it too; here nothing has been loaded yet
         from .stop import BEAM_REFUSAL, read_stop_file
         if read_stop_file(args.stop_file)[1]:
             p.error(f"--stop_file {args.stop_file} with --num_beams {args.num_beams}: {BEAM_REFUSAL}")
@@ -673,8 +684,9 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             p.error(f"--speculate {args.speculate} does not go with {flags}: a verify position's history would have to include the picks "
                     "of its own step")
         if args.num_beams > 1:
-            p.error(f"--num_beams {args.num_beams} does not go with {flags}: the beams' histories live on the host, so the sampling "
-                    "kernels cannot count them")
+            p.error(f"--num_beams {args.num_beams} does not go with {flags}: " +
+                    ("a penalised logit would change what a candidate's rank and a beam's score mean" if dev_hist else
+                     "the beams' histories live on the host, so the sampling kernels cannot count them"))
     import math
     if not math.isfinite(args.bias_boost):
         p.error(f"--bias_boost {args.bias_boost}: the boost is finite")
@@ -684,7 +696,8 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             p.error(f"--speculate {args.speculate} does not go with --bias_file {args.bias_file}: {SPEC_REFUSAL}")
         if args.num_beams > 1:
             from .bias import BEAM_REFUSAL
-            p.error(f"--num_beams {args.num_beams} does not go with --bias_file {args.bias_file}: {BEAM_REFUSAL}")
+            p.error(f"--num_beams {args.num_beams} does not go with --bias_file {args.bias_file}: " +
+                    ("a boosted logit would change what a candidate's rank and a beam's score mean" if dev_hist else BEAM_REFUSAL))
     if not args.temperature > 0.0:
         p.error(f"--temperature {args.temperature}: the temperature is positive")
     if args.top_k < 0:

@@ -381,14 +381,20 @@ def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor
 
 
 def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optional[int] = None, step: int = 0,
-                mask: Optional[torch.Tensor] = None, stop=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                mask: Optional[torch.Tensor] = None, stop=None, history: Optional[torch.Tensor] = None,
+                no_repeat_ngram: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """One beam search step in place on `state` (a dualhyp_amd.beam.BeamState): logits [n_utt * rows_per_utt, vocab], rows_per_utt 1
     (step 0: the one live beam) or state.W; every utterance with done == 0 gets its W next beams, its records of `step` and its pool
     entries (dh_beam_select_bf16; the definition is in include/dualhyp_hip.h, "Beam search").  Returns the rows' candidates
     (ids int32, lp float32, both [rows, 2 W]): token_top_logprobs(logits, 2 W).  mask (int32 [n_utt, words], "Token masks"): row u
     serves every beam row of utterance u; the candidates are the first 2 W allowed ids of each row (dh_beam_select_bf16_mask).
     stop (a compiled specification, its stop set only): a candidate in the set ends its hypothesis into the pool as the EOS does, and
-    state.fin_tok_buffer() receives the id that ended each pool entry; stop sequences are refused (dh_beam_select_bf16_stop)."""
+    state.fin_tok_buffer() receives the id that ended each pool entry; stop sequences are refused (dh_beam_select_bf16_stop).
+    history (state.history_buffer(), "Beam histories" of the header; None: everything above, unchanged): the step reads plane
+    (step - 1) & 1 and writes plane step & 1 of the live beams' tokens; no_repeat_ngram (0 .. 8, needs history) bans on them — the
+    candidates are the first 2 W ids that the mask allows and the ban leaves, the ban dropped for a row it leaves fewer than 2 W — and
+    stop may carry sequences, matched on a beam's own text (dh_beam_select_bf16_hist).  The candidates of a done utterance's rows
+    come back as zeros under a ban."""
     logits = _dev(logits, name="logits")
     if logits.dim() != 2:
         raise ValueError(f"logits must be [rows, vocab], got {tuple(logits.shape)}")
@@ -402,18 +408,33 @@ def beam_select(logits: torch.Tensor, state, *, rows_per_utt: int, eos_id: Optio
         raise ValueError(f"beam_select: step {step} is outside the {state.max_new} recorded steps")
     if state.device != logits.device:
         raise ValueError(f"beam_select: the state lives on {state.device}, the logits on {logits.device}")
-    ids = torch.empty((rows, 2 * W), dtype=torch.int32, device=logits.device)
-    lp = torch.empty((rows, 2 * W), dtype=torch.float32, device=logits.device)
+    from .ngram import check_ngram
+    ngram = check_ngram(no_repeat_ngram, vocab)
+    if history is None and ngram:
+        raise ValueError(f"beam_select: no_repeat_ngram={ngram} needs history, the state's history planes (state.history_buffer())")
+    if history is not None:
+        want = (2, state.n_utt, W, state.max_new)
+        if history.dtype != torch.int64 or tuple(history.shape) != want or not history.is_contiguous() or history.device != logits.device:
+            raise ValueError(f"beam_select: history must be contiguous {torch.int64} {want} on {logits.device}, got {history.dtype} "
+                             f"{tuple(history.shape)} on {history.device}")
+    make = torch.zeros if ngram else torch.empty      # under a ban the rows of a done utterance are not written
+    ids = make((rows, 2 * W), dtype=torch.int32, device=logits.device)
+    lp = make((rows, 2 * W), dtype=torch.float32, device=logits.device)
     m_ptr, m_ld = _mask_arg(mask, state.n_utt, vocab, logits.device)
     st_ptr = _stop_arg(stop, vocab, logits.device)
-    if st_ptr is not None and stop.sequences:
+    if st_ptr is not None and stop.sequences and history is None:
+        from .beam import HISTORY_HINT
         from .stop import BEAM_REFUSAL
-        raise ValueError(BEAM_REFUSAL)
+        raise ValueError(BEAM_REFUSAL + HISTORY_HINT)
     if rows:
         import ctypes
         args = (_p(logits), vocab, state.n_utt, int(rows_per_utt), W, state.max_new, -1 if eos_id is None else int(eos_id), int(step), None,
                 ctypes.byref(state.c_struct()), _p(ids), _p(lp))
-        if st_ptr is not None:
+        if history is not None:
+            hist = _lib.BeamHist(_p(history), ngram)
+            check(_lib.load().dh_beam_select_bf16_hist(*args, m_ptr, m_ld, st_ptr, None if st_ptr is None else _p(state.fin_tok_buffer()),
+                                                       ctypes.byref(hist), _stream()))
+        elif st_ptr is not None:
             check(_lib.load().dh_beam_select_bf16_stop(*args, m_ptr, m_ld, st_ptr, _p(state.fin_tok_buffer()), _stream()))
         elif mask is not None:
             check(_lib.load().dh_beam_select_bf16_mask(*args, m_ptr, m_ld, _stream()))

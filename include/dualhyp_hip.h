@@ -34,7 +34,8 @@ typedef uint16_t dh_bf16;
  * dh_engine_set_no_repeat_ngram (no-repeat n-grams); dh_sample_bf16_stop, dh_sample_rows_bf16_stop, dh_beam_select_bf16_stop and
  * dh_engine_set_stop (stop conditions); dh_sample_bf16_nucleus, dh_sample_rows_bf16_nucleus and dh_engine_set_nucleus (nucleus
  * and min-p sampling); dh_engine_fork_slots (sampled candidates); dh_sample_bf16_penalty, dh_sample_rows_bf16_penalty and
- * dh_engine_set_penalties (penalties); dh_sample_bf16_bias, dh_sample_rows_bf16_bias and dh_engine_set_bias (contextual biasing). */
+ * dh_engine_set_penalties (penalties); dh_sample_bf16_bias, dh_sample_rows_bf16_bias and dh_engine_set_bias (contextual biasing);
+ * dh_beam_select_bf16_hist and dh_engine_set_beam_history (beam histories). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -439,7 +440,29 @@ int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, i
  * Histories are never gathered on the device: the records below are per step, and the host backtracks through beam_parent
  * (dualhyp_amd/beam.py), completes a pool that holds fewer than W entries with the live beams in live order (marked unfinished)
  * and ranks the pool by sum_logprob / n ** length_penalty in Python floats, n = generated tokens with the EOS counted,
- * descending, stable on pool order.  No powf runs on the device. */
+ * descending, stable on pool order.  No powf runs on the device.
+ *
+ * Beam histories (opt-in: dh_beam_select_bf16_hist, dh_engine_set_beam_history; without them every entry launches what it always
+ * launched).  H(u, t, w) is the list of tokens that live beam w of utterance u has generated behind the selection of step t:
+ *   H(u, t, w) = H(u, t - 1, beam_parent[u, t, w]) + [beam_tok[u, t, w]], H(u, -1, .) = [].  It holds t + 1 ids, never a prompt
+ *   token, and equals the host's backtracking read through beam_tok.  Pool entries and frozen (done) utterances have no device
+ *   history: nothing reads one.
+ *   Storage: two int64 planes [2][n_utt * W][max_new_tokens]; plane t & 1 holds H(., t, .) behind step t.  A step reads plane
+ *     (t - 1) & 1 and writes plane t & 1, so no launch reads what it writes and any parent map (swap, fan-out, identity) is right; the
+ *     parity comes from the step the launch reads on the device, so a captured chain stays replayable.
+ *   Ban: with ngram = N in 1 .. 8 the candidates of row (u, b) at step t >= 1 are the first 2 W ids, in the raw row's order (value
+ *     descending, then index ascending), among the ids that mask row u allows (all ids without a mask) and that are not in the ban set
+ *     of the no-repeat n-gram definition below for g = H(u, t - 1, b); each keeps the raw row's log-probability, bit-equal to dh_token_logprobs_bf16.
+ *     If fewer than 2 W such ids exist the ban is ignored for that row at that step (the mask alone guarantees 2 W): the beam form of
+ *     "the pick is never taken from an empty set".  Step 0 has an empty history and no ban.  Everything behind the candidates —
+ *     score add, merge order, walk, pool — is unchanged: the candidates are, bit for bit, dh_token_top_logprobs_bf16_mask(...,
+ *     rows_per_mask = 1) under a per-row mask with the banned bits cleared.  vocab <= 131072 (the sampler's LDS row).
+ *   Stop sequences: a candidate (b, j) with id x ends its hypothesis into the pool — the EOS's place rule, score and pool order —
+ *     when x is in the stop set, as without histories, or when H(u, t - 1, b) + [x] ends on one of the stop sequences (the stop
+ *     definition below, m = t + 1: a match never reaches behind the hypothesis' first generated token, nor into another beam's
+ *     text).  fin_tok receives x, x stays in the hypothesis' tokens, finish_reason is "stop"; the EOS wins where both hold.
+ *   What stays refused under beam search, histories or not, are the penalties and a bias: a penalised or boosted value would have to rank the candidates and enter
+ *     the scores, which this definition does not say. */
 #define DH_MAX_BEAMS 4
 /* Device arrays of one beam search call (n_utt utterances, W beams, max_new_tokens steps).  The caller zeroes cum, n_steps, done
  * and n_fin; the other arrays are written where something is recorded and nowhere else. */
@@ -560,7 +583,8 @@ int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens,
  *     step keeps the last DH_MAX_STOP_LEN generated tokens in registers, so a pick that stops ends the step where an EOS would.
  *   Beam search takes the stop set only: a candidate whose id is in the set ends its hypothesis into the pool exactly as the EOS does
  *     (place rule, score, pool order), and fin_tok[u, k] receives the id that ended pool entry k.  Stop sequences are refused there:
- *     the beams' histories live on the host. */
+ *     the beams' histories live on the host — unless the caller keeps them on the device ("Beam histories" of "Beam search":
+ *     dh_beam_select_bf16_hist, dh_engine_set_beam_history), where a sequence ends the hypothesis whose own text completes it. */
 #define DH_MAX_STOP_SEQS 8
 #define DH_MAX_STOP_LEN 8
 /* the values of `done` (0: live) */
@@ -592,6 +616,21 @@ int dh_sample_rows_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, 
 int dh_beam_select_bf16_stop(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens, int64_t eos_id,
                              int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp,
                              const uint32_t* mask, int mask_ld, const dh_stop_spec* stop, int32_t* fin_tok, void* stream);
+/* The history planes of a beam search call ("Beam histories" of "Beam search"): tokens, device int64 [2][n_utt * W][max_new_tokens],
+ * needs no initialisation; ngram 0 (no ban) .. 8. */
+typedef struct dh_beam_hist {
+    int64_t* tokens;
+    int ngram;
+} dh_beam_hist;
+/* dh_beam_select_bf16_stop (mask, stop and fin_tok nullable as there) over device histories: the step reads plane (step - 1) & 1 of
+ * hist->tokens and writes plane step & 1, its candidates are taken under the ban of hist->ngram, and `stop` may carry sequences
+ * (fin_tok is needed with a set or with sequences).  hist == null: dh_beam_select_bf16_stop's launches, and sequences are refused.
+ * Refused before any launch, with the value in the message: ngram outside 0 .. 8; vocab above 131072 with ngram > 0; null tokens with
+ * ngram > 0 or with sequences. */
+int dh_beam_select_bf16_hist(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new_tokens, int64_t eos_id,
+                             int step, const int32_t* step_dev, const dh_beam_state* st, int32_t* cand_ids, float* cand_lp,
+                             const uint32_t* mask, int mask_ld, const dh_stop_spec* stop, int32_t* fin_tok, const dh_beam_hist* hist,
+                             void* stream);
 
 /* Nucleus and min-p (the "top_p" and "min_p" of the serving interfaces; the sampler of generate/base.py:62-80 has temperature and top_k
  * only).  ONE definition for every entry below.
@@ -1073,15 +1112,24 @@ int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int mask_ld);
 /* No-repeat n-grams (see above; generate/base.py:62-80) for later dh_engine_decode, dh_engine_decode_rows and dh_engine_decode_spec
  * calls: ngram in 1 .. 8 with start, device int32 [n_seq] prompt lengths of the calls' sequences; ngram = 0 = off, the default.
  * (ngram, start) is part of the captured step's key, beside the mask: with it unset a decode call runs the graphs it always ran.
- * dh_engine_decode_beam refuses to run while it is set: beam histories live on the host.  The caller keeps start alive while set. */
+ * dh_engine_decode_beam refuses to run while it is set: beam histories live on the host (a beam call's ban is
+ * dh_engine_set_beam_history's own ngram, formed on the device histories).  The caller keeps start alive while set. */
 int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int32_t* start);
 /* The stop specification (see "Stop conditions" above; null = off, the default) for later dh_engine_decode, dh_engine_decode_rows,
  * dh_engine_decode_spec and dh_engine_decode_beam calls.  start: device int32 [n_seq] prompt lengths, needed with stop sequences (the
  * same numbers as dh_engine_set_no_repeat_ngram's, which win where both are set); beam_fin_tok: device int32 [n_utt, W], needed by a
- * beam call under a stop set, which refuses to run under stop sequences.  The specification is copied (the lengths) and pointed to
+ * beam call under a stop set (and under stop sequences, which a beam call refuses unless dh_engine_set_beam_history is set).  The specification is copied (the lengths) and pointed to
  * (the device arrays, which the caller keeps alive while set); it is part of the captured step's key, beside the mask and (ngram,
  * start): with it unset a decode call runs the graphs it always ran. */
 int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const int32_t* start, int32_t* beam_fin_tok);
+/* Device histories for later dh_engine_decode_beam calls ("Beam histories" of "Beam search"): tokens, device int64
+ * [2][n_utt * W][max_new_tokens] (null = off, the default, and clears ngram), and the beam steps' no_repeat_ngram, 0 .. 8.  The
+ * caller's step 0 (dh_beam_select_bf16_hist) has written plane 0.  While set, dh_engine_decode_beam bans under ngram and accepts the
+ * stop sequences of dh_engine_set_stop (called with the utterances' prompt lengths as start and with beam_fin_tok).
+ * dh_engine_set_no_repeat_ngram being set stays a refusal for beam calls, and penalties and a bias stay refused.  The pointer and ngram
+ * are part of a beam step's key: with it unset a beam call runs the graphs, and refuses what, it always did.  Refused: ngram outside
+ * 0 .. 8, vocab above 131072 with ngram > 0, null tokens with ngram > 0.  The caller keeps the planes alive while set. */
+int dh_engine_set_beam_history(dh_engine* e, int64_t* tokens, int ngram);
 /* top_p and min_p (see "Nucleus and min-p" above; 1 and 0 = off, the default) for later dh_engine_decode and dh_engine_decode_rows
  * calls with top_k != 1.  Both values are part of the captured step's key, beside the mask, (ngram, start) and the stop specification:
  * with them unset, or with top_k == 1, a decode call runs the graphs it always ran.  Verify and beam steps take neither.  Refused like

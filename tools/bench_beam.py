@@ -11,9 +11,14 @@ top_k = 1 on the same rows); "reparent_prep_us_remainder" is difference - (selec
 sampler): a subtraction remainder that holds the prep kernel and the two copy launches, not an event time of them.  Also reported: the
 share of step rows that continued their own beam and skipped the copy, and the bytes dh_engine_reserve_beams added to the engine.
 
+--history adds the device-history arms to every run (beam_search_batch(history="device"): histories alone, no_repeat_ngram = 3, and
+that with two stop sequences), each timed in alternation with the plain call, and the selection's kernels alone with and without
+histories (history_arms below says which figures are subtraction remainders).  Without the flag the tool runs what it always ran, so
+the same command line times the plain beam step on another build of the library (DUALHYP_HIP_LIB) or another checkout.
+
 The parent never touches the GPU and prints ONE JSON line.
 
-    python tools/bench_beam.py [--beams 1 2 4] [--out profiles/beam_search.json]
+    python tools/bench_beam.py [--beams 1 2 4] [--history] [--out profiles/beam_search.json]
 """
 import argparse
 import json
@@ -35,6 +40,9 @@ ap.add_argument("--prefill_batch", type=int, default=32)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--step_timeout", type=int, default=420, help="seconds each child may take")
 ap.add_argument("--out", type=str, default="", help="write the line as a JSON file too")
+ap.add_argument("--history", action="store_true",
+                help="also time the device-history arms (beam_search_batch(history='device')): histories alone, no_repeat_ngram = 3, and "
+                     "that with two stop sequences, each beside the plain call; and the selection's two kernels with and without histories")
 ap.add_argument("--worker", type=int, nargs=2, default=None, metavar=("W", "N"), help="(child) beams and utterances of this run")
 a = ap.parse_args()
 
@@ -103,6 +111,7 @@ def worker(W: int, n: int) -> None:
     sel_us = event_us(select) - event_us(lambda: st.done.zero_())
     smp_us = event_us(sample) - fill_us
     added_us = (b_ms - g_ms) * 1e3
+    hist_fields = history_arms(m, corpus[:n], W, n, new, V, logits, beam) if a.history else {}
     m.refresh_engine()
     torch.cuda.synchronize()
     eng = m.engine(rows, a.prompt_len + new, max(rows, a.prefill_batch * a.prompt_len), exact=True)
@@ -115,7 +124,68 @@ def worker(W: int, n: int) -> None:
                           added_us_per_step=round(added_us, 1), select_us=round(sel_us, 1), greedy_sampler_us=round(smp_us, 1),
                           reparent_prep_us_remainder=round(added_us - (sel_us - smp_us), 1),
                           rows_skipping_copy_share=round(1 - t["beam_copied_rows"] / max(t["beam_step_rows"], 1), 4),
-                          reserve_beams_bytes=int(scratch), engine_bytes=int(bytes_with))), flush=True)
+                          reserve_beams_bytes=int(scratch), engine_bytes=int(bytes_with), **hist_fields)), flush=True)
+
+
+def history_arms(m, prompts, W, n, new, V, logits, plain):
+    """--history: the whole step under device histories (the plain call repeated beside each arm, alternating), and the selection's
+    kernels alone on the step's rows at step new // 2.  merge_us is beam_select minus token_top_logprobs at K = 2 W, and
+    candidates_ban_us is beam_select under N = 3 minus the merge with histories: subtraction remainders of event times, not kernel
+    times of their own."""
+    import torch
+    from dualhyp_amd import beam_search_batch, ops
+    from dualhyp_amd.beam import BeamState
+    from dualhyp_amd.stop import compile_stop
+    dev = logits.device
+    seqs = [[V - 2, V - 3], [V - 4, V - 5, V - 6]]          # ids the hash weights rarely pick: the test runs, nothing ends
+    arms = dict(history_only=dict(history="device"), ngram3=dict(history="device", no_repeat_ngram=3),
+                ngram3_stop2=dict(history="device", no_repeat_ngram=3, stop=seqs))
+    out = {}
+    steps = new - 1
+    for name, kw in arms.items():
+        run = lambda tm=None: beam_search_batch(m, prompts, new, num_beams=W, prefill_batch=a.prefill_batch, timing=tm, **kw)
+        run()
+        t_arm, t_off = [], []
+        for _ in range(a.repeats):
+            tm = {}
+            plain(tm)
+            t_off.append(tm["decode_ms"] / steps)
+            tm = {}
+            run(tm)
+            t_arm.append(tm["decode_ms"] / steps)
+        out[name + "_ms_per_step"] = [round(x, 4) for x in t_arm]
+        out[name + "_off_ms_per_step"] = [round(x, 4) for x in t_off]
+    # the kernels alone: a state in the middle of a call, histories of random ids from a small pool (bans happen)
+    step = new // 2
+    st = BeamState(n, W, new, dev)
+    st.n_steps.fill_(step)
+    hist = st.history_buffer()
+    hist.copy_(torch.randint(0, 64, tuple(hist.shape), device=dev))
+    stop = compile_stop([], seqs, V, dev)
+    keep = (st.n_steps.clone(), st.cum.clone())
+
+    def reset():
+        st.done.zero_()
+        st.n_fin.zero_()
+        st.n_steps.copy_(keep[0])
+        st.cum.copy_(keep[1])
+
+    def select(**kw):
+        reset()
+        ops.beam_select(logits, st, rows_per_utt=W, step=step, **kw)
+
+    reset_us = event_us(reset)
+    top_us = event_us(lambda: ops.token_top_logprobs(logits, 2 * W))
+    plain_us = event_us(select) - reset_us
+    hist_us = event_us(lambda: select(history=hist)) - reset_us
+    ban_us = event_us(lambda: select(history=hist, no_repeat_ngram=3)) - reset_us
+    ban_stop_us = event_us(lambda: select(history=hist, no_repeat_ngram=3, stop=stop)) - reset_us
+    out.update(kernel_step=step, token_top_logprobs_us=round(top_us, 1), select_us_plain=round(plain_us, 1),
+               select_us_history=round(hist_us, 1), select_us_ngram3=round(ban_us, 1), select_us_ngram3_stop2=round(ban_stop_us, 1),
+               merge_us_plain=round(plain_us - top_us, 1), merge_us_history=round(hist_us - top_us, 1),
+               merge_us_history_stop2=round(ban_stop_us - ban_us + hist_us - top_us, 1),
+               candidates_ban_us=round(ban_us - (hist_us - top_us), 1))
+    return out
 
 
 if a.worker is not None:
@@ -127,6 +197,7 @@ else:
             cmd = [sys.executable, str(Path(__file__).resolve()), "--worker", str(W), str(n)]
             for k in ("prompt_len", "max_new_tokens", "prefill_batch", "repeats"):
                 cmd += [f"--{k}", str(getattr(a, k))]
+            cmd += ["--history"] if a.history else []
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=a.step_timeout)      # a run that fails ends the tool
             if r.returncode != 0:
                 sys.exit(f"run W={W} utterances={n} failed with {r.returncode}:\n{r.stdout[-1000:]}{r.stderr[-3000:]}")
