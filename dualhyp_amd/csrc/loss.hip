@@ -2,6 +2,8 @@
 // reference's bf16 autocast: the logits are upcast to fp32 and log-softmax runs in fp32).
 //   forward : loss[r] = logsumexp(logits[r,:]) - logits[r, target[r]]   (0 for ignored rows), lse[r]
 //   backward: dlogits[r, c] = g * (exp(logits[r,c] - lse[r]) - [c == target[r]])   (0 for ignored rows)
+// Every target outside [0, V) is ignored, not -1 alone.  A -inf logit has probability 0: lse and loss stay finite while the
+// row has a finite logit (and a finite target), the gradient at that column is 0; a row with no finite logit is unspecified.
 // One block per row; the row (V = 32000: 64 KB in bf16) is read once, online max/sum per thread,
 // block reduce through LDS.  HBM-bound: V*2 bytes per row forward, V*4 backward.
 #include "common.h"
@@ -25,7 +27,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
     for (int c = tid; c < V; c += 256) {
         const float v = ldf<T>(x + c);
         if (v > m) { s = s * __expf(m - v) + 1.f; m = v; }
-        else s += __expf(v - m);
+        else if (v != -INFINITY) s += __expf(v - m);   // a -inf logit adds nothing (and -inf - m is NaN while m is still -inf)
     }
     const float wm = wave_max(m);
     s = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - wm));
