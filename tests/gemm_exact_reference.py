@@ -322,20 +322,21 @@ def swiglu_failures(got: torch.Tensor, g: torch.Tensor, u: torch.Tensor, ok: tor
 # ---- guard bands ----------------------------------------------------------------------------------------------------------
 SENTINEL_BF16 = 0x7FA5            # a bf16 NaN with a payload: no arithmetic produces this bit pattern
 SENTINEL_F32 = 0x7FA5A5A5
+SENTINEL_U8 = 0x7F                # e4m3fn bytes: the NaN, which the quantisation of a finite row never produces
 GUARD_ROWS = 256                  # output margins: one full band of the largest tile, so that a whole stray tile lands in a guard
 
 
 class Guarded:
     """A tensor embedded in a larger flat buffer, `margin` elements (rounded up to 16 bytes) on both sides, the whole buffer
-    filled with the sentinel NaN of its dtype (bf16 or fp32).  `.t` is the embedded tensor (contiguous, 16-byte aligned as the
+    filled with the sentinel NaN of its dtype (bf16, fp32, or uint8 holding e4m3fn bytes).  `.t` is the embedded tensor (contiguous, 16-byte aligned as the
     ABI requires).  Inputs: `.t.copy_(values)`; a kernel that reads an out-of-range row picks up NaN.  Outputs: after the call
     `check()` wants both margins bit-identical to the sentinel and no sentinel left inside."""
 
     def __init__(self, shape, dtype, device, margin: int, values: Optional[torch.Tensor] = None):
-        assert dtype in (torch.bfloat16, torch.float32)
-        self.idt = torch.int16 if dtype == torch.bfloat16 else torch.int32
-        self.sentinel = SENTINEL_BF16 if dtype == torch.bfloat16 else SENTINEL_F32
-        per16 = 16 // (2 if dtype == torch.bfloat16 else 4)
+        assert dtype in (torch.bfloat16, torch.float32, torch.uint8)
+        self.idt, self.sentinel, size = {torch.bfloat16: (torch.int16, SENTINEL_BF16, 2), torch.float32: (torch.int32, SENTINEL_F32, 4),
+                                         torch.uint8: (torch.uint8, SENTINEL_U8, 1)}[dtype]
+        per16 = 16 // size
         n = 1
         for d in shape:
             n *= int(d)

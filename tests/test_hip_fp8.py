@@ -36,7 +36,7 @@ def test_row_quantisation_is_the_oracles():
         assert torch.equal(q.cpu(), q_ref.view(torch.uint8)), "e4m3 bytes differ from torch's conversion"
         qw, sw = quantize_rows_fp8(x.to(DEV))          # the weight quantiser (torch ops on the device)
         assert torch.equal(qw.cpu(), q_ref.view(torch.uint8)) and torch.equal(sw.cpu(), s_ref.view(-1))
-    # fused with RMSNorm
+    # fused with RMSNorm (bit for bit against a CPU reference at every EPT, with row_tail: tests/test_hip_norm_exact.py)
     d = 4096
     w = (1 + U((d,), 0.25, "nw").float()).bfloat16()
     for rows in (37, 300):

@@ -36,6 +36,7 @@ def check_ulp(got, want, max_ulp, max_frac, what, floor_frac=1.0):
 def test_rmsnorm(dev, rows, d):
     from dualhyp_amd import ops
     from oracle import ger_oracle as O
+    # (row by row and bit for bit, every MAXC class, ragged d and guard bands: tests/test_hip_norm_exact.py::test_rmsnorm)
     x = U((rows, d), 2.0, f"x{d}")
     w = (1 + U((d,), 0.25, f"w{d}").float()).bfloat16()
     # torch's CPU bf16 rsqrt rounds differently in its vector loop and its scalar tail (the last
