@@ -18,6 +18,7 @@
 // MFMA operand map (checked with integer data, tests/test_hip_fp8.py): lane l holds the 32 consecutive k
 // [32 (l >> 4), 32 (l >> 4) + 32) of row (A) / column (B) l & 15 — one MX block per lane, hence one scale per lane.
 #include "common.h"
+#include "gemm.h"
 #include "tuning.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -558,6 +559,7 @@ int launch_tiled_n(const Fp8Args& a, hipStream_t s) {
     DH_MAX_LDS_ONCE((gemm_fp8_kernel<EPI, RESID, NST, WG>), lds);
     hipLaunchKernelGGL((gemm_fp8_kernel<EPI, RESID, NST, WG>), dim3(a.nb_n * a.nb_m), dim3(WG * WG * 64), lds, s, a);
     DH_LAUNCH_CHECK();
+    dh_gemm_route(WG == 4 ? DH_ROUTE_FP8_T256 : NST == 4 ? DH_ROUTE_FP8_T128_S4 : DH_ROUTE_FP8_T128_S2);
     return 0;
 }
 
@@ -583,6 +585,7 @@ int launch_skinny_ng(const Fp8Args& a, hipStream_t s) {
     if (a.resid) hipLaunchKernelGGL((gemm_fp8_skinny_kernel<EPI, true, false, NG>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((gemm_fp8_skinny_kernel<EPI, false, false, NG>), grid, block, 0, s, a);
     DH_LAUNCH_CHECK();
+    dh_gemm_route(NG == 1 ? DH_ROUTE_FP8_STREAM_NG1 : NG == 2 ? DH_ROUTE_FP8_STREAM_NG2 : DH_ROUTE_FP8_STREAM_NG4);
     return 0;
 }
 
@@ -632,6 +635,7 @@ extern "C" int dh_linear_fp8_f32(const uint8_t* xq, const float* x_scale, const 
     else if (M <= 64) hipLaunchKernelGGL((gemm_fp8_skinny_kernel<DH_EPI_PLAIN, false, true, 2>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((gemm_fp8_skinny_kernel<DH_EPI_PLAIN, false, true, 4>), grid, block, 0, s, a);
     DH_LAUNCH_CHECK();
+    dh_gemm_route(M <= 32 ? DH_ROUTE_FP8_STREAM_NG1 : M <= 64 ? DH_ROUTE_FP8_STREAM_NG2 : DH_ROUTE_FP8_STREAM_NG4);
     return 0;
 }
 

@@ -63,6 +63,17 @@ enum DhGemmRoute : int {
     DH_ROUTE_PARTIAL_WAVES,    //   K split over the waves of a block
     DH_ROUTE_PAIRS_TILED,      // gemm_dt.hip: pair sums
     DH_ROUTE_CHAIN_TILED,      //   the one-launch total
+    DH_ROUTE_FP8_STREAM_NG1,   // fp8.hip: streaming kernel (bf16 and fp32 out), 1 / 2 / 4 row groups
+    DH_ROUTE_FP8_STREAM_NG2,
+    DH_ROUTE_FP8_STREAM_NG4,
+    DH_ROUTE_FP8_T128_S4,      //   128-tile kernel, 4 stages
+    DH_ROUTE_FP8_T128_S2,      //   2 stages
+    DH_ROUTE_FP8_T256,         //   256-tile kernel on sixteen waves
+    DH_ROUTE_MX4_STREAM_NG1,   // mxfp4.hip: streaming kernel (bf16 and fp32 out), 1 / 2 / 4 row groups
+    DH_ROUTE_MX4_STREAM_NG2,
+    DH_ROUTE_MX4_STREAM_NG4,
+    DH_ROUTE_MX4_T128_S4,      //   tiled kernel, 4 stages
+    DH_ROUTE_MX4_T128_S2,      //   2 stages
     DH_ROUTE_COUNT
 };
 void dh_gemm_route(int route);      // gemm.hip

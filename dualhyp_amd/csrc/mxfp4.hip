@@ -31,6 +31,7 @@
 // Both fix one fp32 chain per output, independent of the row count (tiled: k ascending in one accumulator; streaming: each
 // wave its k-steps ascending, waves added in order).
 #include "common.h"
+#include "gemm.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
@@ -387,6 +388,7 @@ int launch_tiled_n(const Mx4Args& a, hipStream_t s) {
     DH_MAX_LDS_ONCE((gemm_mxfp4_kernel<EPI, RESID, NST>), lds);
     hipLaunchKernelGGL((gemm_mxfp4_kernel<EPI, RESID, NST>), dim3(a.nb_n * a.nb_m), dim3(256), lds, s, a);
     DH_LAUNCH_CHECK();
+    dh_gemm_route(NST == 4 ? DH_ROUTE_MX4_T128_S4 : DH_ROUTE_MX4_T128_S2);
     return 0;
 }
 
@@ -404,6 +406,7 @@ int launch_skinny_ng(const Mx4Args& a, hipStream_t s) {
     if (a.resid) hipLaunchKernelGGL((gemm_mxfp4_skinny_kernel<EPI, true, false, NG>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((gemm_mxfp4_skinny_kernel<EPI, false, false, NG>), grid, block, 0, s, a);
     DH_LAUNCH_CHECK();
+    dh_gemm_route(NG == 1 ? DH_ROUTE_MX4_STREAM_NG1 : NG == 2 ? DH_ROUTE_MX4_STREAM_NG2 : DH_ROUTE_MX4_STREAM_NG4);
     return 0;
 }
 
@@ -429,6 +432,7 @@ extern "C" int dh_linear_mxfp4_f32(const uint8_t* xq, const float* x_scale, cons
     else if (M <= 64) hipLaunchKernelGGL((gemm_mxfp4_skinny_kernel<DH_EPI_PLAIN, false, true, 2>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((gemm_mxfp4_skinny_kernel<DH_EPI_PLAIN, false, true, 4>), grid, block, 0, s, a);
     DH_LAUNCH_CHECK();
+    dh_gemm_route(M <= 32 ? DH_ROUTE_MX4_STREAM_NG1 : M <= 64 ? DH_ROUTE_MX4_STREAM_NG2 : DH_ROUTE_MX4_STREAM_NG4);
     return 0;
 }
 

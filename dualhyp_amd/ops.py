@@ -606,14 +606,22 @@ def rmsnorm_quant_fp8(x: torch.Tensor, w: torch.Tensor, eps: float, row_tail: Op
 
 def linear_fp8(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor, *, epilogue: int = EPI_PLAIN,
                w2q: Optional[torch.Tensor] = None, w2_scale: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
-               bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, kernel: int = 0) -> torch.Tensor:
+               bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, kernel: int = 0,
+               out32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [M, N] = epilogue((xq . wq^T) * x_scale[m] * w_scale[n]) on the fp8 MFMA; dh_linear_fp8_ex (kernel: 0 by row
-    count, 1 tiled, 2 streaming)."""
+    count, 1 tiled, 2 streaming).  out32: dh_linear_fp8_f32, the PLAIN streaming result as fp32.  out: the caller's result
+    buffer (bf16, or fp32 with out32)."""
     k = _Keep()
     M, K = xq.shape
     N = wq.size(0)
     assert wq.size(1) == K and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    if out32:
+        assert epilogue == EPI_PLAIN and resid is None and kernel in (0, 2)
+        y = _out(out, (M, N), torch.float32, xq.device)
+        check(_lib.load().dh_linear_fp8_f32(k(xq, torch.uint8, "xq"), k(x_scale, torch.float32, "x_scale"), k(wq, torch.uint8, "wq"),
+                                            k(w_scale, torch.float32, "w_scale"), _p(y), M, N, K, _stream()))
+        return y
+    y = _out(out, (M, N), torch.bfloat16, xq.device)
     check(_lib.load().dh_linear_fp8_ex(k(xq, torch.uint8, "xq"), k(x_scale, torch.float32, "x_scale"), k(wq, torch.uint8, "wq"),
                                        k(w_scale, torch.float32, "w_scale"), _p(y), M, N, K, epilogue, k(w2q, torch.uint8, "w2q"),
                                        k(w2_scale, torch.float32, "w2_scale"), k(scale, name="scale"), k(bias, name="bias"),
@@ -624,10 +632,11 @@ def linear_fp8(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scal
 def linear_mxfp4(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor, *, epilogue: int = EPI_PLAIN,
                  w2q: Optional[torch.Tensor] = None, w2_scale: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
                  bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, kernel: int = 0,
-                 out32: bool = False) -> torch.Tensor:
+                 out32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [M, N] = epilogue((xq . dequant(W)^T) * x_scale[m]) with MXFP4 weights as dualhyp_amd.quant.pack_mxfp4 lays them out
     (wq uint8 [N/16, K/128, 64, 16], w_scale uint8 [N/16, K/128, 64]); dh_linear_mxfp4_ex (kernel: 0 by row count, 1 tiled,
-    2 streaming).  out32: dh_linear_mxfp4_f32, the PLAIN streaming result as fp32."""
+    2 streaming).  out32: dh_linear_mxfp4_f32, the PLAIN streaming result as fp32.  out: the caller's result buffer (bf16, or
+    fp32 with out32)."""
     k = _Keep()
     M, K = xq.shape
     assert wq.dim() == 4 and wq.shape[2:] == (64, 16) and w_scale.shape == wq.shape[:3] and wq.size(1) * 128 == K
@@ -635,11 +644,11 @@ def linear_mxfp4(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_sc
     N = wq.size(0) * 16
     if out32:
         assert epilogue == EPI_PLAIN and resid is None and kernel in (0, 2)
-        y = torch.empty((M, N), dtype=torch.float32, device=xq.device)
+        y = _out(out, (M, N), torch.float32, xq.device)
         check(_lib.load().dh_linear_mxfp4_f32(k(xq, torch.uint8, "xq"), k(x_scale, torch.float32, "x_scale"), k(wq, torch.uint8, "wq"),
                                               k(w_scale, torch.uint8, "w_scale"), _p(y), M, N, K, _stream()))
         return y
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    y = _out(out, (M, N), torch.bfloat16, xq.device)
     check(_lib.load().dh_linear_mxfp4_ex(k(xq, torch.uint8, "xq"), k(x_scale, torch.float32, "x_scale"), k(wq, torch.uint8, "wq"),
                                          k(w_scale, torch.uint8, "w_scale"), _p(y), M, N, K, epilogue, k(w2q, torch.uint8, "w2q"),
                                          k(w2_scale, torch.uint8, "w2_scale"), k(scale, name="scale"), k(bias, name="bias"),

@@ -56,7 +56,9 @@ int dh_abi_version(void);
 int dh_set_tuning(int key, int value);
 /* Debug aid for tests: a bit mask of the GEMM kernels launched on the calling thread since the last reset, one bit per launch
  * site (enum DhGemmRoute in csrc/gemm.h; tests/gemm_exact_reference.py mirrors the numbering); reset != 0 clears it after
- * the read.  Host side only: a thread-local OR next to each launch. */
+ * the read.  Host side only: a thread-local OR next to each launch.  The quantised GEMMs are recorded as well: dh_linear_fp8*
+ * (streaming with 1 / 2 / 4 row groups, the 128-tile with 4 or 2 stages, the 256-tile) and dh_linear_mxfp4* (streaming with
+ * 1 / 2 / 4 row groups, tiled with 4 or 2 stages); the fp32-out entry points record the streaming routes of their bf16 forms. */
 uint64_t dh_debug_gemm_routes(int reset);
 const char* dh_last_error(void);
 /* Name of the first visible device's gcnArch ("gfx950") into buf; fails when no GPU. */

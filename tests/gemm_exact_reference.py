@@ -23,7 +23,10 @@ import torch
 # ---- route record: the bit numbers of enum DhGemmRoute (dualhyp_amd/csrc/gemm.h), read through dh_debug_gemm_routes ----------
 ROUTES = ("t128_s2", "t128_s4", "w8_pipe0", "w8_pipe1", "w8_pipe2", "w8_pipe3", "w4_tile", "w4_persist", "w4_xa",
           "mid_ng1", "mid_ng2", "mid_ng4", "mid_ng1_ring", "mid_ng2_ring", "dt_fused", "skinny", "swiglu_skinny2", "skinny_n",
-          "k64", "k64_mul", "rows", "partial_waves", "pairs_tiled", "chain_tiled")
+          "k64", "k64_mul", "rows", "partial_waves", "pairs_tiled", "chain_tiled",
+          # the quantised GEMMs (csrc/fp8.hip, csrc/mxfp4.hip): their cases are tests/qgemm_exact_reference.py's
+          "fp8_stream_ng1", "fp8_stream_ng2", "fp8_stream_ng4", "fp8_t128_s4", "fp8_t128_s2", "fp8_t256",
+          "mx4_stream_ng1", "mx4_stream_ng2", "mx4_stream_ng4", "mx4_t128_s4", "mx4_t128_s2")
 
 
 def route_names(mask: int) -> frozenset:

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import gemm_exact_reference as R
+import qgemm_exact_reference as Q
 
 REPO = Path(__file__).resolve().parent.parent
 GROUPS = sorted({(c.family, c.group) for c in R.CASES})
@@ -56,6 +57,11 @@ def test_route_table_matches_the_library_and_every_route_has_a_case():
     for c in R.CASES:
         assert set(c.routes) <= set(R.ROUTES) and set(c.tail_routes) <= set(R.ROUTES) and c.routes, c.id
         used |= set(c.routes) | set(c.tail_routes)
+    quantised = {r for r in R.ROUTES if r.startswith(("fp8_", "mx4_"))}       # these have their cases in tests/qgemm_exact_reference.py
+    assert not used & quantised
+    for c in Q.CASES:
+        assert set(c.routes) <= quantised and c.routes, c.id
+        used |= set(c.routes)
     assert used == set(R.ROUTES), f"routes without a case: {sorted(set(R.ROUTES) - used)}"
     assert R.route_names(0b101) == {"t128_s2", "w8_pipe0"}
     for c in R.CASES:
