@@ -59,8 +59,33 @@ class BiasSpec(C.Structure):
     _fields_ = [("ids", P), ("len", P), ("boost", P), ("h_ids", P), ("h_len", P), ("h_boost", P), ("n", C.c_int32)]
 
 
+# The sampling entries: the two heads (dh_sample_bf16: ... seed, step, stream; dh_sample_rows_bf16: ... seed, stream) and the options
+# behind them, in the order the entries gained them.  Entry head + suffix takes the tail up to and including its own piece.
+SAMPLE_HEADS = {"dh_sample_bf16": [P, I, P, I, P, P, I, F, I, I64, U64, I, P],
+                "dh_sample_rows_bf16": [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P]}
+SAMPLE_TAIL = (("_ex", [P]),                            # logprobs
+               ("_top", [I, P, P]),                     # top_logprobs, top_ids, top_lp
+               ("_mask", [P, I]),                       # mask, mask_ld
+               ("_ngram", [I, P]),                      # ngram, start
+               ("_stop", [C.POINTER(StopSpec)]),
+               ("_nucleus", [F, F]),                    # top_p, min_p
+               ("_penalty", [C.POINTER(PenaltyArgs)]),
+               ("_bias", [C.POINTER(BiasSpec)]))
+
+
+def _sample_signatures() -> dict:
+    out = {}
+    for head, args in SAMPLE_HEADS.items():
+        out[head] = (I, args)
+        for suffix, piece in SAMPLE_TAIL:
+            args = args + piece
+            out[head + suffix] = (I, args)
+    return out
+
+
 # name -> (restype, argtypes); must list every function declared in include/dualhyp_hip.h
 SIGNATURES = {
+    **_sample_signatures(),
     "dh_abi_version": (I, []),
     "dh_set_tuning": (I, [I, I]),
     "dh_debug_gemm_routes": (U64, [I]),
@@ -97,32 +122,9 @@ SIGNATURES = {
     "dh_attn_bwd_bf16": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "dh_attn_decode_work_bytes": (I64, [I, I, I, I]),
     "dh_attn_decode_bf16": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
-    "dh_sample_bf16": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P]),
-    "dh_sample_rows_bf16": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P]),
     "dh_token_logprobs_bf16": (I, [P, I, P, P, I, P]),
-    "dh_sample_bf16_ex": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P]),
-    "dh_sample_rows_bf16_ex": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P]),
     "dh_token_top_logprobs_bf16": (I, [P, I, I, P, P, I, P]),
-    "dh_sample_bf16_top": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P]),
-    "dh_sample_rows_bf16_top": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P]),
     "dh_beam_select_bf16": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P]),
-    "dh_sample_bf16_mask": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I]),
-    "dh_sample_rows_bf16_mask": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I]),
-    "dh_sample_bf16_ngram": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P]),
-    "dh_sample_rows_bf16_ngram": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P]),
-    "dh_sample_bf16_stop": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec)]),
-    "dh_sample_rows_bf16_stop": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec)]),
-    "dh_sample_bf16_nucleus": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F]),
-    "dh_sample_rows_bf16_nucleus": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
-                                        F, F]),
-    "dh_sample_bf16_penalty": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F,
-                                   C.POINTER(PenaltyArgs)]),
-    "dh_sample_rows_bf16_penalty": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
-                                        F, F, C.POINTER(PenaltyArgs)]),
-    "dh_sample_bf16_bias": (I, [P, I, P, I, P, P, I, F, I, I64, U64, I, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec), F, F,
-                                C.POINTER(PenaltyArgs), C.POINTER(BiasSpec)]),
-    "dh_sample_rows_bf16_bias": (I, [P, I, P, I, P, P, P, P, I, I, I, F, I, I64, U64, P, P, I, P, P, P, I, I, P, C.POINTER(StopSpec),
-                                     F, F, C.POINTER(PenaltyArgs), C.POINTER(BiasSpec)]),
     "dh_beam_select_bf16_stop": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P, P]),
     "dh_beam_select_bf16_hist": (I, [P, I, I, I, I, I, I64, I, P, C.POINTER(BeamState), P, P, P, I, C.POINTER(StopSpec), P,
                                      C.POINTER(BeamHist), P]),

@@ -337,26 +337,39 @@ struct dh_bias_args {
 // the prompt lengths
 int dh_bias_pack(const char* name, const dh_bias_spec* spec, int vocab, bool start_ok, dh_bias_args& out);
 
+// The options of one pick, as the sampling launchers (sampling.hip) take them from the exported entries and from the engine's captured
+// steps, which compare them as part of a step's key.  The default is every option off: the kernels the plain entries always launched.  A
+// new sampler option is one member here, one line of operator==, and its share of the launchers' check and pack functions.
+struct dh_pick_ctl {
+    float* logprobs = nullptr;                          // fp32 beside `tokens`: each appended token's log-probability (dh_engine_set_logprobs)
+    int top_n = 0;                                      // the row's top_n alternatives as well, into top_ids / top_lp
+    int32_t* top_ids = nullptr;                         // ([n_seq, tok_ld, top_n], dh_engine_set_top_logprobs)
+    float* top_lp = nullptr;
+    const uint32_t* mask = nullptr;                     // [n_seq, mask_ld] words: the sequences' allowed tokens, null = the kernels without
+    int mask_ld = 0;                                    // one (dh_engine_set_token_mask)
+    int ngram = 0;                                      // no-repeat n-grams, 0 = the kernels without it (dh_engine_set_no_repeat_ngram)
+    const int32_t* start = nullptr;                     // [n_seq] prompt lengths: what ngram, stop's sequences, pen and bias count from
+    dh_stop_args stop;                                  // the stop test behind the pick (dh_engine_set_stop)
+    dh_nucleus_args nuc;                                // top_p / min_p of the sampled branch (dh_engine_set_nucleus)
+    dh_penalty_args pen = DH_PENALTY_OFF;               // the three penalties (dh_engine_set_penalties)
+    dh_bias_args bias;                                  // the bias entries (dh_engine_set_bias)
+    // ngram, pen or bias on: the history-reading kernel family
+    bool hist() const { return ngram > 0 || dh_penalty_on(pen) || bias.n > 0; }
+    bool operator==(const dh_pick_ctl& o) const {
+        return logprobs == o.logprobs && top_n == o.top_n && top_ids == o.top_ids && top_lp == o.top_lp && mask == o.mask &&
+               mask_ld == o.mask_ld && ngram == o.ngram && start == o.start && stop == o.stop && nuc == o.nuc &&
+               dh_penalty_same(pen, o.pen) && bias == o.bias;
+    }
+};
+
 // the sampling step of the engine's decode graphs (sampling.hip): dh_sample_bf16 with the step counter read from the device, and
-// dh_sample_rows_bf16.  logprobs (nullable, fp32 beside `tokens`, dh_engine_set_logprobs): each appended token's log-probability;
-// top_n (0: off) with top_ids / top_lp ([n_seq, tok_ld, top_n], dh_engine_set_top_logprobs): the row's top_n alternatives as well;
-// mask (nullable, [n_seq, mask_ld] words, dh_engine_set_token_mask): the sequences' allowed tokens, null = the kernels without one;
-// ngram (0: off) with start ([n_seq] prompt lengths, dh_engine_set_no_repeat_ngram): no-repeat n-grams, 0 = the kernels without it;
-// stop (dh_engine_set_stop; its sequences count from the same `start`): the stop test behind the pick, all zero = off;
-// nuc (dh_engine_set_nucleus): top_p / min_p of the sampled branch, the default = off;
-// pen (dh_engine_set_penalties; its history counts from the same `start`): the three penalties, the default = off;
-// bias (dh_engine_set_bias; its matches count from the same `start`): the bias entries, the default = off
+// dh_sample_rows_bf16
 int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
-                   float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev, float* logprobs,
-                   int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask, int mask_ld, int ngram, const int32_t* start,
-                   const dh_stop_args& stop, void* stream, const dh_nucleus_args& nuc = dh_nucleus_args{},
-                   const dh_penalty_args& pen = DH_PENALTY_OFF, const dh_bias_args& bias = dh_bias_args{});
+                   float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev,
+                   const dh_pick_ctl& ctl, void* stream);
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
-                        int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream,
-                        const dh_nucleus_args& nuc = dh_nucleus_args{}, const dh_penalty_args& pen = DH_PENALTY_OFF,
-                        const dh_bias_args& bias = dh_bias_args{});
+                        int top_k, int64_t eos_id, uint64_t seed, const dh_pick_ctl& ctl, void* stream);
 
 // the verify step of speculative greedy decoding (engine.hip, dh_engine_decode_spec): its attention (decode_fused.hip) and its
 // acceptance kernel (sampling.hip)
@@ -366,8 +379,7 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
                               dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream);
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& stop, void* stream);
+                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& ctl, void* stream);   // ctl: nuc, pen and bias off
 
 // the selection step of beam search (beam.hip, dh_beam_select_bf16), as the engine's captured step calls it
 // stop: its set ends a hypothesis as the EOS does, its sequences as well under device histories; hist (nullable, int64

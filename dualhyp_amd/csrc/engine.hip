@@ -39,24 +39,14 @@ struct dh_engine {
            *act = nullptr, *xlast = nullptr, *logits = nullptr;
     int32_t *tok_slot = nullptr, *tok_pos = nullptr, *seq_meta = nullptr;   // seq_meta: 4 x [B], read through seq_meta() below
     int32_t *last_row = nullptr, *step_dev = nullptr;
-    float* logprobs = nullptr;                          // dh_engine_set_logprobs: the caller's buffer beside `tokens` (null: off)
-    int top_n = 0;                                      // dh_engine_set_top_logprobs: alternatives per token (0: off) and the
-    int32_t* top_ids = nullptr;                         // caller's [n_seq, tok_ld, top_n] buffers
-    float* top_lp = nullptr;
-    const uint32_t* mask = nullptr;                     // dh_engine_set_token_mask: the caller's [n_seq, mask_ld] allowed-token words (null: off)
-    int mask_ld = 0;
-    int ngram = 0;                                      // dh_engine_set_no_repeat_ngram: n (0: off) and the caller's [n_seq] prompt lengths
-    const int32_t* ngram_start = nullptr;
-    dh_stop_args stop;                                  // dh_engine_set_stop: the stop specification (all zero: off), the caller's [n_seq] prompt
-    const int32_t* stop_start = nullptr;                // lengths its sequences count from, and a beam call's [n_utt, W] ending ids
-    int32_t* stop_fin_tok = nullptr;
+    // What the dh_engine_set_* calls have set for later steps (common.h describes the members; everything off: the steps the engine always
+    // ran).  `set.start` stays null: the four setters that take the [n_seq] prompt lengths each keep their own pointer, null while their
+    // option is off, and step_ctl() below gives a step the one it reads.
+    dh_pick_ctl set;
+    const int32_t *ngram_start = nullptr, *stop_start = nullptr, *pen_start = nullptr, *bias_start = nullptr;
+    int32_t* stop_fin_tok = nullptr;                    // dh_engine_set_stop: a beam call's [n_utt, W] ending ids
     int64_t* beam_hist = nullptr;                       // dh_engine_set_beam_history: the caller's [2][n_utt * W][max_new] history planes (null: off)
     int beam_hist_ngram = 0;                            // and the beam steps' no_repeat_ngram (0: no ban)
-    dh_nucleus_args nuc;                                // dh_engine_set_nucleus: top_p / min_p of later decode / decode_rows calls (default: off)
-    dh_penalty_args pen = DH_PENALTY_OFF;               // dh_engine_set_penalties: the penalties of later decode / decode_rows calls (default: off)
-    const int32_t* pen_start = nullptr;                 // and the caller's [n_seq] prompt lengths their history counts from
-    dh_bias_args bias;                                  // dh_engine_set_bias: the bias of later decode / decode_rows calls (default: off)
-    const int32_t* bias_start = nullptr;                // and the caller's [n_seq] prompt lengths its matches count from
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -85,33 +75,25 @@ struct dh_engine {
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_stage = nullptr;
     // captured decode steps, keyed by everything baked into the graph (a few batch sizes alternate in practice)
     // (limit, row_seq, row_slot, n_all, max_new: the row-list step of dh_engine_decode_rows; null / 0 in dh_engine_decode's keys)
+    // Every member starts at the value it has in a key whose step does not use it; the entry points assign the rest by name.
     struct GKey {
-        int64_t* tokens; int tok_ld; int32_t *length, *done; int n_seq, top_k; float temp; int64_t eos; uint64_t seed; int rsqrt_vec, tiled_rows;
-        const int32_t *limit, *row_seq, *row_slot; int n_all, max_new;
-        int spec; const int64_t* drafts; int32_t* counters;   // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
-        float* logprobs;                                      // dh_engine_set_logprobs: a step captured without the buffer is another kernel
-        int top_n; int32_t* top_ids; float* top_lp;           // dh_engine_set_top_logprobs: likewise, and top_n is a kernel argument
-        const uint32_t* mask; int mask_ld;                    // dh_engine_set_token_mask: likewise (beam steps too)
-        int ngram; const int32_t* ngram_start;                // dh_engine_set_no_repeat_ngram: likewise (0 / null in a beam step's key)
-        dh_stop_args stop; const int32_t* stop_start; int32_t* stop_fin_tok;   // dh_engine_set_stop: likewise (a beam step's key: the set and fin_tok)
-        dh_nucleus_args nuc;                                  // dh_engine_set_nucleus: likewise (off in an arg-max, a verify or a beam step's key)
-        dh_penalty_args pen; const int32_t* pen_start;        // dh_engine_set_penalties: likewise (off / null in a verify or a beam step's key)
-        dh_bias_args bias; const int32_t* bias_start;         // dh_engine_set_bias: likewise
+        int64_t* tokens = nullptr; int tok_ld = 0; int32_t *length = nullptr, *done = nullptr; int n_seq = 0, top_k = 0; float temp = 0.f;
+        int64_t eos = 0; uint64_t seed = 0; int rsqrt_vec = 0, tiled_rows = 0;
+        const int32_t *limit = nullptr, *row_seq = nullptr, *row_slot = nullptr; int n_all = 0, max_new = 0;
+        // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
+        int spec = 0; const int64_t* drafts = nullptr; int32_t* counters = nullptr;
+        // the options the step's sampling launch takes (step_ctl): a step captured without one of them is another kernel, or other arguments
+        dh_pick_ctl ctl;
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
-        // n_seq = n_utt * W rows
-        int beam_w; dh_beam_state beam;
-        int64_t* beam_hist; int beam_ngram;                   // dh_engine_set_beam_history: the history planes and their ban (null / 0 in every other key)
+        // n_seq = n_utt * W rows; the ending ids of dh_engine_set_stop; the history planes and their ban of dh_engine_set_beam_history
+        int beam_w = 0; dh_beam_state beam{}; int32_t* stop_fin_tok = nullptr; int64_t* beam_hist = nullptr; int beam_ngram = 0;
         bool operator==(const GKey& k) const {
             return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
-                   logprobs == k.logprobs && top_n == k.top_n && top_ids == k.top_ids && top_lp == k.top_lp && mask == k.mask &&
-                   mask_ld == k.mask_ld && ngram == k.ngram && ngram_start == k.ngram_start && stop == k.stop && stop_start == k.stop_start &&
-                   stop_fin_tok == k.stop_fin_tok && nuc == k.nuc && dh_penalty_same(pen, k.pen) && pen_start == k.pen_start &&
-                   bias == k.bias && bias_start == k.bias_start &&
-                   beam_w == k.beam_w && beam_hist == k.beam_hist && beam_ngram == k.beam_ngram &&
-                   memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
+                   ctl == k.ctl && beam_w == k.beam_w && stop_fin_tok == k.stop_fin_tok && beam_hist == k.beam_hist &&
+                   beam_ngram == k.beam_ngram && memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
@@ -995,8 +977,7 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
     if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
     return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
-                               e->step_dev, k.counters, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                               k.ngram_start ? k.ngram_start : k.stop_start, k.stop, s);
+                               e->step_dev, k.counters, k.ctl, s);
 }
 
 // tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends
@@ -1013,7 +994,7 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     int rc;
     if ((rc = run_model(e, e->dec_ids, rows, rows, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if ((rc = dh_beam_select_impl(e->logits, D.vocab, rows / W, W, W, k.max_new, k.eos, 0, e->step_dev, k.beam, e->beam_cand_ids,
-                                  e->beam_cand_lp, k.mask, k.mask_ld, k.stop, k.stop_fin_tok, s, k.beam_hist, k.beam_ngram))) return rc;
+                                  e->beam_cand_lp, k.ctl.mask, k.ctl.mask_ld, k.ctl.stop, k.stop_fin_tok, s, k.beam_hist, k.beam_ngram))) return rc;
     if (W == 1) return 0;                                   // a single beam continues itself
     const int tile_units = D.head_size * 4, nt_max = std::min(beam_tiles(k.max_new), e->s_max / 32);
     const dim3 grid(cdiv(nt_max * tile_units, 256), 2 * D.n_layer * D.n_groups, rows);
@@ -1026,9 +1007,35 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     return 0;
 }
 
-// the prompt lengths of a step's history readers: the setters were given the same numbers
-const int32_t* hist_start(const dh_engine::GKey& k) {
-    return k.ngram_start ? k.ngram_start : k.pen_start ? k.pen_start : k.bias_start ? k.bias_start : k.stop_start;
+// The options of a step an entry point is about to launch: what the setters have set, less what the step's kind does not take.  This is
+// what the step's sampling launch bakes in, so it is what the step's key compares.
+enum StepKind { STEP_DECODE, STEP_DECODE_ROWS, STEP_VERIFY, STEP_BEAM };
+dh_pick_ctl step_ctl(const dh_engine* e, StepKind kind, int top_k) {
+    dh_pick_ctl c;
+    c.mask = e->set.mask;
+    c.mask_ld = e->set.mask_ld;
+    c.stop = e->set.stop;
+    if (kind == STEP_BEAM) return c;                    // the selection takes the mask and the stop specification, nothing else
+    c = e->set;
+    if (kind == STEP_VERIFY) {                          // dh_engine_decode_spec has refused both
+        c.pen = DH_PENALTY_OFF;
+        c.bias = dh_bias_args{};
+    }
+    if (kind == STEP_VERIFY || top_k == 1) c.nuc = dh_nucleus_args{};   // the arg-max takes neither parameter: its step is the plain one
+    // the prompt lengths of the step's history readers and stop sequences: the setters were given the same numbers
+    c.start = c.ngram ? e->ngram_start : dh_penalty_on(c.pen) ? e->pen_start : c.bias.n ? e->bias_start : e->stop_start;
+    return c;
+}
+
+// dh_engine_decode and dh_engine_decode_rows (`name`): the penalties' LDS tables, which a bias shares, hold a call's token buffer
+int check_pen_tables(const dh_engine* e, const char* name, int tok_ld) {
+    const dh_pick_ctl& c = e->set;
+    DH_CHECK(!dh_penalty_on(c.pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
+             "LDS tables of %d entries; tok_ld=%d may not fit", name, DH_MAX_PENALTY_HISTORY, tok_ld);
+    DH_CHECK(!dh_penalty_on(c.pen) || c.bias.n == 0 || tok_ld + c.bias.n_ids <= DH_MAX_PENALTY_HISTORY, "%s: penalties and a bias are "
+             "set and share static LDS tables of %d entries; tok_ld=%d and the entries' %d ids may not fit", name, DH_MAX_PENALTY_HISTORY,
+             tok_ld, c.bias.n_ids);
+    return 0;
 }
 
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
@@ -1043,11 +1050,9 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = run_model(e, e->dec_ids, k.n_seq, k.n_seq, 1, true, e->ones, e->ones, false, e->logits, nullptr, s))) return rc;
     if (rows)
         return dh_sample_rows_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.row_seq, k.n_seq, k.n_all,
-                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                                   hist_start(k), k.stop, s, k.nuc, k.pen, k.bias);
+                                   k.max_new, k.temp, k.top_k, k.eos, k.seed, k.ctl, s);
     return dh_sample_impl(e->logits, e->d.vocab, k.tokens, k.tok_ld, k.length, k.done, k.n_seq, k.temp, k.top_k, k.eos, k.seed, 0,
-                          e->step_dev, k.logprobs, k.top_n, k.top_ids, k.top_lp, k.mask, k.mask_ld, k.ngram,
-                          hist_start(k), k.stop, s, k.nuc, k.pen, k.bias);
+                          e->step_dev, k.ctl, s);
 }
 
 // n_steps launches of the step `key` describes, captured into a hipGraph at its first use (8 graphs are kept)
@@ -1300,11 +1305,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_CHECK(e && tokens && length && done, "dh_engine_decode: null argument");
     DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
-    DH_CHECK(!dh_penalty_on(e->pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
-             "LDS tables of %d entries; tok_ld=%d may not fit", "dh_engine_decode", DH_MAX_PENALTY_HISTORY, tok_ld);
-    DH_CHECK(!dh_penalty_on(e->pen) || e->bias.n == 0 || tok_ld + e->bias.n_ids <= DH_MAX_PENALTY_HISTORY, "%s: penalties and a bias are "
-             "set and share static LDS tables of %d entries; tok_ld=%d and the entries' %d ids may not fit", "dh_engine_decode",
-             DH_MAX_PENALTY_HISTORY, tok_ld, e->bias.n_ids);
+    if (int rc = check_pen_tables(e, "dh_engine_decode", tok_ld)) return rc;
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
@@ -1313,11 +1314,11 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
     DH_LAUNCH_CHECK();
     // rsqrt_vec: `rt = rsqrt_vec > 0 ? flags : nullptr` is resolved while capturing, so it is part of the key
-    const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
-                              nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
-                              top_k == 1 ? dh_nucleus_args{} : e->nuc,      // the arg-max takes neither parameter: its step is the plain one
-                              e->pen, e->pen_start, e->bias, e->bias_start};
+    dh_engine::GKey key;
+    key.tokens = tokens; key.tok_ld = tok_ld; key.length = length; key.done = done;
+    key.n_seq = n_seq; key.top_k = top_k; key.temp = temperature; key.eos = eos_id; key.seed = seed;
+    key.rsqrt_vec = e->rsqrt_vec; key.tiled_rows = g_decode_tiled_rows;
+    key.ctl = step_ctl(e, STEP_DECODE, top_k);
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1328,18 +1329,16 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(n_rows > 0 && n_rows <= e->max_batch, "dh_engine_decode_rows: n_rows=%d exceeds max_batch=%d", n_rows, e->max_batch);
     DH_CHECK(n_seq > 0 && tok_ld > 0 && max_new_tokens > 0, "dh_engine_decode_rows: bad shape");
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
-    DH_CHECK(!dh_penalty_on(e->pen) || tok_ld <= DH_MAX_PENALTY_HISTORY, "%s: penalties are set and keep a sequence's distinct ids in static "
-             "LDS tables of %d entries; tok_ld=%d may not fit", "dh_engine_decode_rows", DH_MAX_PENALTY_HISTORY, tok_ld);
-    DH_CHECK(!dh_penalty_on(e->pen) || e->bias.n == 0 || tok_ld + e->bias.n_ids <= DH_MAX_PENALTY_HISTORY, "%s: penalties and a bias are "
-             "set and share static LDS tables of %d entries; tok_ld=%d and the entries' %d ids may not fit", "dh_engine_decode_rows",
-             DH_MAX_PENALTY_HISTORY, tok_ld, e->bias.n_ids);
+    if (int rc = check_pen_tables(e, "dh_engine_decode_rows", tok_ld)) return rc;
     if (n_steps <= 0) return 0;
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
-    const dh_engine::GKey key{tokens, tok_ld, length, done, n_rows, top_k, temperature, eos_id, seed, e->rsqrt_vec, g_decode_tiled_rows,
-                              limit, row_seq, row_slot, n_seq, max_new_tokens, 0, nullptr, nullptr, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr,
-                              top_k == 1 ? dh_nucleus_args{} : e->nuc, e->pen, e->pen_start, e->bias, e->bias_start};
+    dh_engine::GKey key;
+    key.tokens = tokens; key.tok_ld = tok_ld; key.length = length; key.done = done;
+    key.n_seq = n_rows; key.top_k = top_k; key.temp = temperature; key.eos = eos_id; key.seed = seed;
+    key.rsqrt_vec = e->rsqrt_vec; key.tiled_rows = g_decode_tiled_rows;
+    key.limit = limit; key.row_seq = row_seq; key.row_slot = row_slot; key.n_all = n_seq; key.max_new = max_new_tokens;
+    key.ctl = step_ctl(e, STEP_DECODE_ROWS, top_k);
     return launch_steps(e, key, n_steps, (hipStream_t)stream);
 }
 
@@ -1377,10 +1376,10 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(n_seq * S <= MAX_DECODE_ROWS, "dh_engine_decode_spec: %d x %d rows exceed the streaming step's %d", n_seq, S, MAX_DECODE_ROWS);
     DH_CHECK(n_seq * S <= e->row_cap && n_seq * S <= e->max_tokens,
              "dh_engine_decode_spec: %d rows, the workspaces hold %d (dh_engine_reserve_rows) of max_tokens = %d", n_seq * S, e->row_cap, e->max_tokens);
-    DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_spec: penalties are set (repetition=%g, frequency=%g, presence=%g); a verify position's "
-             "history would have to include this launch's own picks", (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence);
-    DH_CHECK(e->bias.n == 0, "dh_engine_decode_spec: a bias of %d entries is set; a verify position's tail would have to include this "
-             "launch's own picks, so the step would need per-position tables", e->bias.n);
+    DH_CHECK(!dh_penalty_on(e->set.pen), "dh_engine_decode_spec: penalties are set (repetition=%g, frequency=%g, presence=%g); a verify position's "
+             "history would have to include this launch's own picks", (double)e->set.pen.repetition, (double)e->set.pen.frequency, (double)e->set.pen.presence);
+    DH_CHECK(e->set.bias.n == 0, "dh_engine_decode_spec: a bias of %d entries is set; a verify position's tail would have to include this "
+             "launch's own picks, so the step would need per-position tables", e->set.bias.n);
     DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
     DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
@@ -1389,10 +1388,12 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
     DH_LAUNCH_CHECK();
-    const dh_engine::GKey key{tokens, tok_ld, length, done, n_seq, 1, temperature, eos_id, 0, 0, 0,
-                              limit, nullptr, nullptr, n_seq, max_new_tokens, n_draft, drafts, counters, e->logprobs, e->top_n, e->top_ids, e->top_lp,
-                              e->mask, e->mask_ld, e->ngram, e->ngram_start, e->stop, e->stop_start, nullptr, dh_nucleus_args{},
-                              DH_PENALTY_OFF, nullptr, dh_bias_args{}, nullptr};
+    dh_engine::GKey key;                                // seed, rsqrt_vec, tiled_rows: 0, the step reads none of them
+    key.tokens = tokens; key.tok_ld = tok_ld; key.length = length; key.done = done;
+    key.n_seq = n_seq; key.top_k = 1; key.temp = temperature; key.eos = eos_id;
+    key.limit = limit; key.n_all = n_seq; key.max_new = max_new_tokens;
+    key.spec = n_draft; key.drafts = drafts; key.counters = counters;
+    key.ctl = step_ctl(e, STEP_VERIFY, 1);
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1443,20 +1444,20 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_CHECK(rows <= MAX_DECODE_ROWS, "dh_engine_decode_beam: %d x %d rows exceed the streaming step's %d", n_utt, W, MAX_DECODE_ROWS);
     DH_CHECK(rows <= e->row_cap && rows <= e->max_tokens, "dh_engine_decode_beam: %d rows, the workspaces hold %d of max_tokens = %d",
              (int)rows, e->row_cap, e->max_tokens);
-    DH_CHECK(e->ngram == 0, "dh_engine_decode_beam: no_repeat_ngram=%d is set; a beam's history lives on the host, so the device cannot "
-             "form its ban set", e->ngram);
+    DH_CHECK(e->set.ngram == 0, "dh_engine_decode_beam: no_repeat_ngram=%d is set; a beam's history lives on the host, so the device cannot "
+             "form its ban set", e->set.ngram);
     // under device histories (dh_engine_set_beam_history) the two that stay refused are refused for what they would mean, not for where
     // a beam's text lives: a penalised or boosted value would rank the candidates and be summed into the scores
-    DH_CHECK(!dh_penalty_on(e->pen), "dh_engine_decode_beam: penalties are set (repetition=%g, frequency=%g, presence=%g); %s",
-             (double)e->pen.repetition, (double)e->pen.frequency, (double)e->pen.presence,
+    DH_CHECK(!dh_penalty_on(e->set.pen), "dh_engine_decode_beam: penalties are set (repetition=%g, frequency=%g, presence=%g); %s",
+             (double)e->set.pen.repetition, (double)e->set.pen.frequency, (double)e->set.pen.presence,
              e->beam_hist ? "a penalised logit would change what a candidate's rank and a beam's score mean, which beam search does not define"
                           : "a beam's history lives on the host, so the device cannot count it");
-    DH_CHECK(e->bias.n == 0, "dh_engine_decode_beam: a bias of %d entries is set; %s", e->bias.n,
+    DH_CHECK(e->set.bias.n == 0, "dh_engine_decode_beam: a bias of %d entries is set; %s", e->set.bias.n,
              e->beam_hist ? "a boosted logit would change what a candidate's rank and a beam's score mean, which beam search does not define"
                           : "a beam's history lives on the host, so the device cannot match it");
-    DH_CHECK(e->stop.n_seqs == 0 || e->beam_hist, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
-             "cannot match a sequence against it (the stop set alone goes with beam search)", e->stop.n_seqs);
-    DH_CHECK(!e->stop.on() || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
+    DH_CHECK(e->set.stop.n_seqs == 0 || e->beam_hist, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
+             "cannot match a sequence against it (the stop set alone goes with beam search)", e->set.stop.n_seqs);
+    DH_CHECK(!e->set.stop.on() || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
     DH_CHECK(e->beam_hist_ngram == 0 || e->d.vocab <= 131072, "dh_engine_decode_beam: vocab=%d exceeds the 131072 ids of the sampler's LDS row "
              "(beam history ngram=%d)", e->d.vocab, e->beam_hist_ngram);
     DH_CHECK(e->d.vocab >= 2 * W, "dh_engine_decode_beam: vocab=%d is below the 2 W = %d candidates of a row", e->d.vocab, 2 * W);
@@ -1472,10 +1473,11 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)(first_step - 1));   // the prep kernel counts it up
     DH_LAUNCH_CHECK();
-    dh_engine::GKey key{nullptr, max_new_tokens, st->n_steps, st->done, (int)rows, 0, 0.f, eos_id, 0, 0, 0,
-                        prompt_len, nullptr, nullptr, n_utt, max_new_tokens, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                        e->mask, e->mask_ld, 0, nullptr, e->stop, nullptr, e->stop_fin_tok, dh_nucleus_args{}, DH_PENALTY_OFF, nullptr,
-                        dh_bias_args{}, nullptr, W, *st, e->beam_hist, e->beam_hist_ngram};
+    dh_engine::GKey key;                                // tokens, top_k, temp, seed: the selection has none
+    key.tok_ld = max_new_tokens; key.length = st->n_steps; key.done = st->done; key.n_seq = (int)rows; key.eos = eos_id;
+    key.limit = prompt_len; key.n_all = n_utt; key.max_new = max_new_tokens;
+    key.ctl = step_ctl(e, STEP_BEAM, 0);
+    key.beam_w = W; key.beam = *st; key.stop_fin_tok = e->stop_fin_tok; key.beam_hist = e->beam_hist; key.beam_ngram = e->beam_hist_ngram;
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1492,7 +1494,7 @@ extern "C" int dh_engine_set_beam_history(dh_engine* e, int64_t* tokens, int ngr
 
 extern "C" int dh_engine_set_logprobs(dh_engine* e, float* buf) {
     DH_CHECK(e, "dh_engine_set_logprobs: null engine");
-    e->logprobs = buf;
+    e->set.logprobs = buf;
     return 0;
 }
 
@@ -1500,9 +1502,9 @@ extern "C" int dh_engine_set_top_logprobs(dh_engine* e, int k, int32_t* ids, flo
     DH_CHECK(e, "dh_engine_set_top_logprobs: null engine");
     DH_CHECK(k >= 0 && k <= 8 && k <= e->d.vocab, "dh_engine_set_top_logprobs: k must be 0 .. min(8, vocab)");
     const bool on = k > 0 && ids && lp;
-    e->top_n = on ? k : 0;
-    e->top_ids = on ? ids : nullptr;
-    e->top_lp = on ? lp : nullptr;
+    e->set.top_n = on ? k : 0;
+    e->set.top_ids = on ? ids : nullptr;
+    e->set.top_lp = on ? lp : nullptr;
     return 0;
 }
 
@@ -1510,8 +1512,8 @@ extern "C" int dh_engine_set_token_mask(dh_engine* e, const uint32_t* mask, int 
     DH_CHECK(e, "dh_engine_set_token_mask: null engine");
     DH_CHECK(!mask || mask_ld >= (e->d.vocab + 31) / 32, "dh_engine_set_token_mask: mask_ld=%d is below the %d words of a %d-token mask row",
              mask_ld, (e->d.vocab + 31) / 32, e->d.vocab);
-    e->mask = mask;
-    e->mask_ld = mask ? mask_ld : 0;
+    e->set.mask = mask;
+    e->set.mask_ld = mask ? mask_ld : 0;
     return 0;
 }
 
@@ -1521,7 +1523,7 @@ extern "C" int dh_engine_set_no_repeat_ngram(dh_engine* e, int ngram, const int3
     DH_CHECK(ngram == 0 || start, "dh_engine_set_no_repeat_ngram: ngram=%d needs `start`, the sequences' prompt lengths", ngram);
     DH_CHECK(ngram == 0 || e->d.vocab <= 131072, "dh_engine_set_no_repeat_ngram: vocab=%d exceeds the 131072 ids of the sampler's LDS row",
              e->d.vocab);
-    e->ngram = ngram;
+    e->set.ngram = ngram;
     e->ngram_start = ngram ? start : nullptr;
     return 0;
 }
@@ -1530,7 +1532,7 @@ extern "C" int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const 
     DH_CHECK(e, "dh_engine_set_stop: null engine");
     dh_stop_args sa;
     if (int rc = dh_stop_pack("dh_engine_set_stop", stop, start != nullptr, sa)) return rc;
-    e->stop = sa;
+    e->set.stop = sa;
     e->stop_start = sa.n_seqs ? start : nullptr;
     e->stop_fin_tok = sa.on() ? beam_fin_tok : nullptr;       // sequences end pool entries too, under device histories
     return 0;
@@ -1540,7 +1542,7 @@ extern "C" int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p) {
     DH_CHECK(e, "dh_engine_set_nucleus: null engine");
     dh_nucleus_args nuc;
     if (int rc = dh_nucleus_pack("dh_engine_set_nucleus", top_p, min_p, nuc)) return rc;
-    e->nuc = nuc;
+    e->set.nuc = nuc;
     return 0;
 }
 
@@ -1551,7 +1553,7 @@ extern "C" int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* pena
     const bool on = dh_penalty_on(pen);
     DH_CHECK(!on || start, "dh_engine_set_penalties: penalties need `start`, the sequences' prompt lengths");
     DH_CHECK(!on || e->d.vocab <= 131072, "dh_engine_set_penalties: vocab=%d exceeds the 131072 ids of the sampler's LDS row", e->d.vocab);
-    e->pen = on ? pen : DH_PENALTY_OFF;
+    e->set.pen = on ? pen : DH_PENALTY_OFF;
     e->pen_start = on ? start : nullptr;
     return 0;
 }
@@ -1560,7 +1562,7 @@ extern "C" int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const 
     DH_CHECK(e, "dh_engine_set_bias: null engine");
     dh_bias_args ba;
     if (int rc = dh_bias_pack("dh_engine_set_bias", bias, e->d.vocab, start != nullptr, ba)) return rc;
-    e->bias = ba;
+    e->set.bias = ba;
     e->bias_start = ba.n ? start : nullptr;
     return 0;
 }

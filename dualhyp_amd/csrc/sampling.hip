@@ -396,7 +396,7 @@ static_assert(DH_MAX_BIAS_ENTRIES * DH_MAX_BIAS_LEN == 2 * NT && PEN_MAX_HISTORY
 // an integer LDS atomicMax on bias_key: exact whatever order the threads arrive in.  Every writer of an id's value writes the same bits
 // from the same operands.  With both on, the counts move to registers and their table holds the boost keys: the tables keep their size.
 // Every thread gets the view; it holds until the block's next call.  The host refuses what the tables could not hold
-// (DH_CHECK_PENALTY, DH_CHECK_BIAS); the clamp only keeps a longer history inside them.
+// (check_pick); the clamp only keeps a longer history inside them.
 __device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int vocab, const int64_t* g, int m_all, const dh_penalty_args& pen,
                                               const dh_bias_args& bias) {
     // the tables live in the launch's dynamic LDS (PEN_LDS_BYTES, asked for only when a penalty or a bias is on): the n-gram-only
@@ -979,82 +979,103 @@ __global__ __launch_bounds__(NT) void beam_top_hist_kernel(const bf16_t* __restr
     if (threadIdx.x == 0) store_top(out_ids, out_lp, (size_t)r, k, ti, tl);
 }
 
-// the three kernels' variant for (logprobs, top_n): top_n > 0 needs the three buffers
-// and for the token mask: null is the kernel without it (the code it always was)
-// and for no_repeat_ngram: 0 is the kernel without it, likewise; `hist` (a local of the launcher) is ngram > 0, or a penalty or a bias on:
-// the history-reading family
-#define DH_PICK_VARIANT_MB(kernel, M, B) \
-    (top_n > 0 ? kernel<true, true, M, B> : logprobs ? kernel<true, false, M, B> : kernel<false, false, M, B>)
-#define DH_PICK_VARIANT_B(kernel, B) (mask ? DH_PICK_VARIANT_MB(kernel, true, B) : DH_PICK_VARIANT_MB(kernel, false, B))
-#define DH_PICK_VARIANT(kernel) (hist ? DH_PICK_VARIANT_B(kernel, true) : DH_PICK_VARIANT_B(kernel, false))
-// start_needed: the kernel has no other way to the prompt lengths
-#define DH_CHECK_NGRAM(name, start_needed)                                                                                      \
-    DH_CHECK(ngram >= 0 && ngram <= MAX_NGRAM, name ": no_repeat_ngram=%d is not in 0 .. %d", ngram, MAX_NGRAM);                   \
-    DH_CHECK(ngram == 0 || vocab <= BAN_MAX_VOCAB, name ": no_repeat_ngram keeps a sequence's allowed-minus-banned bits in a static " \
-             "LDS row of %d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                  \
-    DH_CHECK(ngram == 0 || start || !(start_needed), name ": no_repeat_ngram needs `start`, the prompt lengths")
-// hist_max: the longest history a pick of the call can see
-#define DH_CHECK_PENALTY(name, hist_max)                                                                                        \
-    DH_CHECK(!dh_penalty_on(pen) || start, name ": penalties need `start`, the prompt lengths: the history is what lies behind the prompt"); \
-    DH_CHECK(!dh_penalty_on(pen) || vocab <= BAN_MAX_VOCAB, name ": penalties keep a sequence's overridden columns in a static LDS row of " \
-             "%d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                             \
-    DH_CHECK(!dh_penalty_on(pen) || (hist_max) <= PEN_MAX_HISTORY, name ": penalties keep a sequence's distinct ids in static LDS tables " \
-             "of %d entries; a history of up to %d tokens may not fit", PEN_MAX_HISTORY, (int)(hist_max))
-// the bias itself is checked where it is packed (dh_bias_pack); here what depends on the call: with a penalty on, the history's ids and
-// the entries' ids share the tables
-#define DH_CHECK_BIAS(name, hist_max)                                                                                           \
-    DH_CHECK(bias.n == 0 || start, name ": a bias needs `start`, the prompt lengths: a match never reaches into the prompt");          \
-    DH_CHECK(bias.n == 0 || vocab <= BAN_MAX_VOCAB, name ": a bias keeps a sequence's overridden columns in a static LDS row of "      \
-             "%d ids; vocab=%d does not fit", BAN_MAX_VOCAB, vocab);                                                             \
-    DH_CHECK(bias.n == 0 || !dh_penalty_on(pen) || (hist_max) + bias.n_ids <= PEN_MAX_HISTORY, name ": penalties and a bias keep a "    \
-             "sequence's distinct ids in static LDS tables of %d entries; a history of up to %d tokens and the entries' %d ids may not " \
-             "fit", PEN_MAX_HISTORY, (int)(hist_max), bias.n_ids)
-#define DH_CHECK_MASK(name)                                                                                                    \
-    DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, name ": mask_ld=%d is below the %d words of a %d-token mask row", mask_ld, \
-             (vocab + 31) / 32, vocab)
-#define DH_CHECK_TOP(name)                                                                                                     \
-    DH_CHECK(top_n >= 0 && top_n <= MAX_TOP && top_n <= vocab, name ": top_logprobs must be 0 .. min(8, vocab)");              \
-    DH_CHECK(top_n == 0 || (logprobs && top_ids && top_lp), name ": top_logprobs needs the logprobs, top_ids and top_lp buffers")
+// the three kernels' variant for the options `c` (a dh_pick_ctl) has on: (logprobs, top_n), top_n > 0 needing the three buffers; the token
+// mask, null being the kernel without it (the code it always was); and c.hist(), the history-reading family
+#define DH_PICK_VARIANT_MB(kernel, c, M, B) \
+    ((c).top_n > 0 ? kernel<true, true, M, B> : (c).logprobs ? kernel<true, false, M, B> : kernel<false, false, M, B>)
+#define DH_PICK_VARIANT_B(kernel, c, B) ((c).mask ? DH_PICK_VARIANT_MB(kernel, c, true, B) : DH_PICK_VARIANT_MB(kernel, c, false, B))
+#define DH_PICK_VARIANT(kernel, c) ((c).hist() ? DH_PICK_VARIANT_B(kernel, c, true) : DH_PICK_VARIANT_B(kernel, c, false))
+
+int check_mask_ld(const char* name, int vocab, const uint32_t* mask, int mask_ld) {
+    DH_CHECK(!mask || mask_ld >= (vocab + 31) / 32, "%s: mask_ld=%d is below the %d words of a %d-token mask row", name, mask_ld,
+             (vocab + 31) / 32, vocab);
+    return 0;
+}
+
+// What the three launchers check of a pick's options.  hist_max: the longest history a pick of the call can see; start_needed: the kernel
+// has no other way to the prompt lengths (the row-list kernel has limit - max_new).  A bias itself is checked where it is packed
+// (dh_bias_pack); here what depends on the call: with a penalty on, the history's ids and the entries' ids share the tables.
+int check_pick(const char* name, int vocab, int hist_max, bool start_needed, const dh_pick_ctl& c) {
+    const bool pen = dh_penalty_on(c.pen), bias = c.bias.n != 0;
+    DH_CHECK(!pen || c.start, "%s: penalties need `start`, the prompt lengths: the history is what lies behind the prompt", name);
+    DH_CHECK(!pen || vocab <= BAN_MAX_VOCAB, "%s: penalties keep a sequence's overridden columns in a static LDS row of %d ids; vocab=%d "
+             "does not fit", name, BAN_MAX_VOCAB, vocab);
+    DH_CHECK(!pen || hist_max <= PEN_MAX_HISTORY, "%s: penalties keep a sequence's distinct ids in static LDS tables of %d entries; a "
+             "history of up to %d tokens may not fit", name, PEN_MAX_HISTORY, hist_max);
+    DH_CHECK(!bias || c.start, "%s: a bias needs `start`, the prompt lengths: a match never reaches into the prompt", name);
+    DH_CHECK(!bias || vocab <= BAN_MAX_VOCAB, "%s: a bias keeps a sequence's overridden columns in a static LDS row of %d ids; vocab=%d does "
+             "not fit", name, BAN_MAX_VOCAB, vocab);
+    DH_CHECK(!bias || !pen || hist_max + c.bias.n_ids <= PEN_MAX_HISTORY, "%s: penalties and a bias keep a sequence's distinct ids in static "
+             "LDS tables of %d entries; a history of up to %d tokens and the entries' %d ids may not fit", name, PEN_MAX_HISTORY, hist_max,
+             c.bias.n_ids);
+    DH_CHECK(c.stop.n_seqs == 0 || c.start || !start_needed, "%s: stop sequences need `start`, the prompt lengths", name);
+    DH_CHECK(c.top_n >= 0 && c.top_n <= MAX_TOP && c.top_n <= vocab, "%s: top_logprobs must be 0 .. min(8, vocab)", name);
+    DH_CHECK(c.top_n == 0 || (c.logprobs && c.top_ids && c.top_lp), "%s: top_logprobs needs the logprobs, top_ids and top_lp buffers", name);
+    if (int rc = check_mask_ld(name, vocab, c.mask, c.mask_ld)) return rc;
+    DH_CHECK(c.ngram >= 0 && c.ngram <= MAX_NGRAM, "%s: no_repeat_ngram=%d is not in 0 .. %d", name, c.ngram, MAX_NGRAM);
+    DH_CHECK(c.ngram == 0 || vocab <= BAN_MAX_VOCAB, "%s: no_repeat_ngram keeps a sequence's allowed-minus-banned bits in a static LDS row of "
+             "%d ids; vocab=%d does not fit", name, BAN_MAX_VOCAB, vocab);
+    DH_CHECK(c.ngram == 0 || c.start || !start_needed, "%s: no_repeat_ngram needs `start`, the prompt lengths", name);
+    return 0;
+}
+
+// An exported entry's options, as the ABI spells them, to the ctl of its launch, with the packers' checks under the entry's own name.
+// The parameters behind `logprobs` are in the order the entries gained them, and an entry passes as many as it has: the rest are off.
+// start_implied (the _rows entries): a null start is limit - max_new, which is enough for stop sequences.
+int pack_pick(const char* name, bool start_implied, int vocab, dh_pick_ctl& c, float* logprobs, int top_n = 0, int32_t* top_ids = nullptr,
+              float* top_lp = nullptr, const uint32_t* mask = nullptr, int mask_ld = 0, int ngram = 0, const int32_t* start = nullptr,
+              const dh_stop_spec* stop = nullptr, float top_p = 1.f, float min_p = 0.f, const dh_penalty_args* penalties = nullptr,
+              const dh_bias_spec* bias = nullptr) {
+    if (int rc = dh_bias_pack(name, bias, vocab, start != nullptr, c.bias)) return rc;
+    if (int rc = dh_penalty_pack(name, penalties, c.pen)) return rc;
+    if (int rc = dh_nucleus_pack(name, top_p, min_p, c.nuc)) return rc;
+    if (int rc = dh_stop_pack(name, stop, start_implied || start != nullptr, c.stop)) return rc;
+    c.logprobs = logprobs;
+    c.top_n = top_n;
+    c.top_ids = top_ids;
+    c.top_lp = top_lp;
+    c.mask = mask;
+    c.mask_ld = mask ? mask_ld : 0;
+    c.ngram = ngram;
+    c.start = start;
+    return 0;
+}
 
 }  // namespace
 
-int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
-                   int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed, int step,
-                   const int32_t* step_dev, float* logprobs, int top_n, int32_t* top_ids, float* top_lp, const uint32_t* mask,
-                   int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream, const dh_nucleus_args& nuc,
-                   const dh_penalty_args& pen, const dh_bias_args& bias) {
+int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, int n_seq,
+                   float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev,
+                   const dh_pick_ctl& c, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
-    DH_CHECK_PENALTY("dh_sample_bf16", tok_ld);
-    DH_CHECK_BIAS("dh_sample_bf16", tok_ld);
-    const bool hist = ngram > 0 || dh_penalty_on(pen) || bias.n > 0;
-    DH_CHECK(sa.n_seqs == 0 || start, "dh_sample_bf16: stop sequences need `start`, the prompt lengths");
-    DH_CHECK_TOP("dh_sample_bf16");
-    DH_CHECK_MASK("dh_sample_bf16");
-    DH_CHECK_NGRAM("dh_sample_bf16", true);
+    if (int rc = check_pick("dh_sample_bf16", vocab, tok_ld, true, c)) return rc;
     DH_CHECK(temperature > 0.f, "dh_sample_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
     // logprobs null: the kernel without the log-probability pass (the code it always was)
-    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel), dim3(n_seq), dim3(NT), dh_penalty_on(pen) || bias.n > 0 ? PEN_LDS_BYTES : 0,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel, c), dim3(n_seq), dim3(NT), dh_penalty_on(c.pen) || c.bias.n > 0 ? PEN_LDS_BYTES : 0,
                        (hipStream_t)stream,
-                       logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, logprobs, top_n,
-                       top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen, bias);
+                       logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, c.logprobs, c.top_n,
+                       c.top_ids, c.top_lp, c.mask, c.mask_ld, c.ngram, c.start, c.stop, c.nuc, c.pen, c.bias);
     DH_LAUNCH_CHECK();
     return 0;
 }
 
+// The exported ladder: each entry takes the options of the one before and its own behind them, refuses what only it can refuse, and
+// launches with the rest off.
 extern "C" int dh_sample_bf16_ex(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                  int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                  int step, void* stream, float* logprobs) {
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_ex", false, vocab, c, logprobs)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                   int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                   int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_top", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1062,8 +1083,9 @@ extern "C" int dh_sample_bf16_mask(const dh_bf16* logits, int vocab, int64_t* to
                                    int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                                    const uint32_t* mask, int mask_ld) {
     DH_CHECK(mask, "dh_sample_bf16_mask: null mask (dh_sample_bf16_top is the entry without one)");
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_mask", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld)) return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1071,18 +1093,21 @@ extern "C" int dh_sample_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* t
                                     int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                                     const uint32_t* mask, int mask_ld, int ngram, const int32_t* start) {
     DH_CHECK(ngram >= 1, "dh_sample_bf16_ngram: ngram=%d (dh_sample_bf16_mask / dh_sample_bf16_top are the entries without one)", ngram);
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_ngram", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start))
+        return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                    int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                                    int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                                    const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop) {
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_bf16_stop", stop, start != nullptr, sa)) return rc;
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_stop", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop))
+        return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1090,12 +1115,11 @@ extern "C" int dh_sample_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t*
                                       int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                                       const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
                                       float top_p, float min_p) {
-    dh_nucleus_args nuc;
-    if (int rc = dh_nucleus_pack("dh_sample_bf16_nucleus", top_p, min_p, nuc)) return rc;
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_bf16_nucleus", stop, start != nullptr, sa)) return rc;
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_nucleus", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop, top_p, min_p))
+        return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1103,14 +1127,11 @@ extern "C" int dh_sample_bf16_penalty(const dh_bf16* logits, int vocab, int64_t*
                                       int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                                       const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
                                       float top_p, float min_p, const dh_penalty_args* penalties) {
-    dh_penalty_args pen;
-    if (int rc = dh_penalty_pack("dh_sample_bf16_penalty", penalties, pen)) return rc;
-    dh_nucleus_args nuc;
-    if (int rc = dh_nucleus_pack("dh_sample_bf16_penalty", top_p, min_p, nuc)) return rc;
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_bf16_penalty", stop, start != nullptr, sa)) return rc;
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc, pen);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_penalty", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop, top_p, min_p, penalties))
+        return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1118,16 +1139,11 @@ extern "C" int dh_sample_bf16_bias(const dh_bf16* logits, int vocab, int64_t* to
                                    int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
                                    const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
                                    float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias) {
-    dh_bias_args ba;
-    if (int rc = dh_bias_pack("dh_sample_bf16_bias", bias, vocab, start != nullptr, ba)) return rc;
-    dh_penalty_args pen;
-    if (int rc = dh_penalty_pack("dh_sample_bf16_bias", penalties, pen)) return rc;
-    dh_nucleus_args nuc;
-    if (int rc = dh_nucleus_pack("dh_sample_bf16_bias", top_p, min_p, nuc)) return rc;
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_bf16_bias", stop, start != nullptr, sa)) return rc;
-    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step,
-                          nullptr, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc, pen, ba);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_bias", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop, top_p, min_p, penalties, bias))
+        return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1139,23 +1155,17 @@ extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens,
 
 int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
-                        int top_k, int64_t eos_id, uint64_t seed, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream,
-                        const dh_nucleus_args& nuc, const dh_penalty_args& pen, const dh_bias_args& bias) {
+                        int top_k, int64_t eos_id, uint64_t seed, const dh_pick_ctl& c, void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
-    DH_CHECK_PENALTY("dh_sample_rows_bf16", tok_ld);
-    DH_CHECK_BIAS("dh_sample_rows_bf16", tok_ld);
-    const bool hist = ngram > 0 || dh_penalty_on(pen) || bias.n > 0;
-    DH_CHECK_TOP("dh_sample_rows_bf16");
-    DH_CHECK_MASK("dh_sample_rows_bf16");
-    DH_CHECK_NGRAM("dh_sample_rows_bf16", false);
+    if (int rc = check_pick("dh_sample_rows_bf16", vocab, tok_ld, false, c)) return rc;
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel), dim3(n_rows), dim3(NT), dh_penalty_on(pen) || bias.n > 0 ? PEN_LDS_BYTES : 0,
-                       (hipStream_t)stream, logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_seq, max_new, temperature,
-                       top_k, eos_id, seed, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, nuc, pen, bias);
+    hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel, c), dim3(n_rows), dim3(NT),
+                       dh_penalty_on(c.pen) || c.bias.n > 0 ? PEN_LDS_BYTES : 0, (hipStream_t)stream, logits, vocab, tokens, tok_ld, length,
+                       done, limit, row_seq, n_seq, max_new, temperature, top_k, eos_id, seed, c.logprobs, c.top_n, c.top_ids, c.top_lp, c.mask,
+                       c.mask_ld, c.ngram, c.start, c.stop, c.nuc, c.pen, c.bias);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -1164,16 +1174,20 @@ extern "C" int dh_sample_rows_bf16_ex(const dh_bf16* logits, int vocab, int64_t*
                                       int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
                                       int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                       float* logprobs) {
-    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_ex", true, vocab, c, logprobs)) return rc;
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_top(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                        int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
                                        int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                        float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp) {
-    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, nullptr, 0, 0, nullptr, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_top", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp)) return rc;
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1182,8 +1196,10 @@ extern "C" int dh_sample_rows_bf16_mask(const dh_bf16* logits, int vocab, int64_
                                         float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
                                         int mask_ld) {
     DH_CHECK(mask, "dh_sample_rows_bf16_mask: null mask (dh_sample_rows_bf16_top is the entry without one)");
-    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new,
-                               temperature, top_k, eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, 0, nullptr, dh_stop_args{}, stream);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_mask", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld)) return rc;
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1193,8 +1209,11 @@ extern "C" int dh_sample_rows_bf16_ngram(const dh_bf16* logits, int vocab, int64
                                          int mask_ld, int ngram, const int32_t* start) {
     DH_CHECK(ngram >= 1, "dh_sample_rows_bf16_ngram: ngram=%d (dh_sample_rows_bf16_mask / dh_sample_rows_bf16_top are the entries without one)",
              ngram);
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_ngram", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start))
+        return rc;
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
-                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, dh_stop_args{}, stream);
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_stop(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1202,10 +1221,12 @@ extern "C" int dh_sample_rows_bf16_stop(const dh_bf16* logits, int vocab, int64_
                                         int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
                                         float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
                                         int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop) {
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_rows_bf16_stop", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_stop", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop))
+        return rc;
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
-                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream);
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_nucleus(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1214,12 +1235,12 @@ extern "C" int dh_sample_rows_bf16_nucleus(const dh_bf16* logits, int vocab, int
                                            float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
                                            int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
                                            float min_p) {
-    dh_nucleus_args nuc;
-    if (int rc = dh_nucleus_pack("dh_sample_rows_bf16_nucleus", top_p, min_p, nuc)) return rc;
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_rows_bf16_nucleus", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_nucleus", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram,
+                           start, stop, top_p, min_p))
+        return rc;
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
-                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc);
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_penalty(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1228,15 +1249,12 @@ extern "C" int dh_sample_rows_bf16_penalty(const dh_bf16* logits, int vocab, int
                                            float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
                                            int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
                                            float min_p, const dh_penalty_args* penalties) {
-    dh_penalty_args pen;
-    if (int rc = dh_penalty_pack("dh_sample_rows_bf16_penalty", penalties, pen)) return rc;
-    dh_nucleus_args nuc;
-    if (int rc = dh_nucleus_pack("dh_sample_rows_bf16_penalty", top_p, min_p, nuc)) return rc;
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_rows_bf16_penalty", stop, true, sa)) return rc;      // start null: limit - max_new_tokens
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_penalty", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram,
+                           start, stop, top_p, min_p, penalties))
+        return rc;
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
-                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc,
-                               pen);
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1245,17 +1263,12 @@ extern "C" int dh_sample_rows_bf16_bias(const dh_bf16* logits, int vocab, int64_
                                         float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
                                         int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
                                         float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias) {
-    dh_bias_args ba;
-    if (int rc = dh_bias_pack("dh_sample_rows_bf16_bias", bias, vocab, start != nullptr, ba)) return rc;
-    dh_penalty_args pen;
-    if (int rc = dh_penalty_pack("dh_sample_rows_bf16_bias", penalties, pen)) return rc;
-    dh_nucleus_args nuc;
-    if (int rc = dh_nucleus_pack("dh_sample_rows_bf16_bias", top_p, min_p, nuc)) return rc;
-    dh_stop_args sa;
-    if (int rc = dh_stop_pack("dh_sample_rows_bf16_bias", stop, true, sa)) return rc;         // start null: limit - max_new_tokens
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_bias", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop, top_p, min_p, penalties, bias))
+        return rc;
     return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
-                               eos_id, seed, logprobs, top_logprobs, top_ids, top_lp, mask, mask ? mask_ld : 0, ngram, start, sa, stream, nuc,
-                               pen, ba);
+                               eos_id, seed, c, stream);
 }
 
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
@@ -1267,20 +1280,17 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
 
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, float* logprobs, int top_n, int32_t* top_ids, float* top_lp,
-                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_args& sa, void* stream) {
-    DH_CHECK(sa.n_seqs == 0 || start, "spec_accept: stop sequences need `start`, the prompt lengths");
+                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& c, void* stream) {
+    // a verify position's history would have to include this launch's own picks, and the acceptance is an arg-max
+    DH_CHECK(!c.nuc.on() && !dh_penalty_on(c.pen) && c.bias.n == 0, "spec_accept: a verify step takes no nucleus, no penalty and no bias");
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
-    DH_CHECK_TOP("spec_accept");
-    DH_CHECK_MASK("spec_accept");
-    DH_CHECK_NGRAM("spec_accept", true);
+    if (int rc = check_pick("spec_accept", vocab, tok_ld, true, c)) return rc;
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
     if (n_seq == 0) return 0;
-    const bool hist = ngram > 0;                        // a verify step takes no penalty and no bias
-    hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel), dim3(n_seq), dim3(NT), 0,
+    hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel, c), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
-                       counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa);
+                       counters, c.logprobs, c.top_n, c.top_ids, c.top_lp, c.mask, c.mask_ld, c.ngram, c.start, c.stop);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -1312,7 +1322,7 @@ extern "C" int dh_token_top_logprobs_bf16_mask(const dh_bf16* logits, int vocab,
     DH_CHECK(mask, "dh_token_top_logprobs_bf16_mask: null mask (dh_token_top_logprobs_bf16 is the entry without one)");
     DH_CHECK(vocab > 0 && n_rows >= 0 && rows_per_mask >= 1, "dh_token_top_logprobs_bf16_mask: bad shape");
     DH_CHECK(k >= 1 && k <= MAX_TOP && k <= vocab, "dh_token_top_logprobs_bf16_mask: k must be 1 .. min(8, vocab)");
-    DH_CHECK_MASK("dh_token_top_logprobs_bf16_mask");
+    if (int rc = check_mask_ld("dh_token_top_logprobs_bf16_mask", vocab, mask, mask_ld)) return rc;
     if (n_rows == 0) return 0;
     hipLaunchKernelGGL(token_top_logprobs_kernel<true>, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, logits, vocab, k, out_ids, out_lp,
                        mask, mask_ld, rows_per_mask);

@@ -841,7 +841,6 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     bias = _check_bias(bias, speculate)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
-    nuc = top_p < 1.0 or min_p > 0.0
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     ngram = _ngram.check_ngram(no_repeat_ngram)
     if ngram:
@@ -874,41 +873,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
         if end:
             end.record()
-    if return_logprobs:
-        eng.set_logprobs(be.logprobs)   # part of the captured steps' key; without it the call runs the steps it always ran
-    if K:
-        eng.set_top_logprobs(*be.top)
-    if mask is not None:
-        eng.set_token_mask(be.mask)
-    if ngram:
-        eng.set_no_repeat_ngram(ngram, be.start)
-    if stop is not None:
-        eng.set_stop(stop, be.start)
-    if nuc:
-        eng.set_nucleus(top_p, min_p)
-    if pen:
-        eng.set_penalties(*pen, start=be.start)
-    if bias is not None:
-        eng.set_bias(bias, be.start)
-    try:
+    with _decode_settings(eng, be.logprobs, be.top, be.mask, ngram, be.start, stop, top_p, min_p, pen, bias):
         sched.run(be)
-    finally:
-        if bias is not None:
-            eng.set_bias()
-        if pen:
-            eng.set_penalties()
-        if return_logprobs:
-            eng.set_logprobs(None)      # the buffer is this call's
-        if K:
-            eng.set_top_logprobs(None)
-        if mask is not None:
-            eng.set_token_mask(None)
-        if ngram:
-            eng.set_no_repeat_ngram(0)
-        if stop is not None:
-            eng.set_stop(None)
-        if nuc:
-            eng.set_nucleus(None, None)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()

@@ -465,6 +465,38 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool =
     return out
 
 
+def _sample_tail(k: _Keep, rows: bool, logits: torch.Tensor, tokens: torch.Tensor, logprobs, top_logprobs, mask, no_repeat_ngram: int,
+                 start, stop, top_p, min_p, repetition_penalty, frequency_penalty, presence_penalty, bias):
+    """The options of sample() (rows False) and sample_rows() (True), checked: (logits on the device, the suffix of the entry to call,
+    its arguments behind `stream`).  The entries form one ladder, each taking the options of the one before and its own behind them
+    (_lib.SAMPLE_TAIL); the call goes to the narrowest one that takes every option it has on.  rows: start None is
+    limit - max_new_tokens, so neither stop sequences nor a ban need it."""
+    from .nucleus import check_nucleus
+    top_p, min_p = check_nucleus(top_p, min_p)
+    logits = _dev(logits, name="logits")
+    vocab = logits.size(1)
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous()
+    n_seq, tok_ld = tokens.shape
+    logprobs = _logprobs_buffer(logprobs, tokens)
+    top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
+    m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
+    st_ptr = _stop_arg(stop, vocab, logits.device)
+    if not rows and st_ptr is not None and stop.sequences and start is None:
+        raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
+    pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tok_ld, vocab, k)
+    b_ptr = _bias_arg(bias, pen, start, tok_ld, vocab, logits.device, k)
+    if (st_ptr is not None or pen is not None or b_ptr is not None) and not no_repeat_ngram:
+        ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
+    else:
+        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=rows)
+    tail = (_p(logprobs), top_n, _p(top_ids), _p(top_lp), m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr)
+    # (suffix, the call has what the entry adds, the arguments the entry takes), widest first
+    for suffix, on, n in (("_bias", b_ptr is not None, 13), ("_penalty", pen is not None, 12), ("_nucleus", top_p < 1.0 or min_p > 0.0, 11),
+                          ("_stop", st_ptr is not None, 9), ("_ngram", ngram, 8), ("_mask", mask is not None, 6), ("_top", True, 4)):
+        if on:
+            return logits, suffix, tail[:n]
+
+
 def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, *,
            temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: int = 0,
            step: int = 0, logprobs: Optional[torch.Tensor] = None,
@@ -491,41 +523,14 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     the same call's pick on a copy of the row in which every id an entry proposes behind tokens[u, start[u]:length[u]] holds
     bf16(y + boost), y its raw or penalised fp32 value; logits is not written, and the log-probabilities and alternatives stay the raw
     row's.  None and an empty list are off (dh_sample_bf16_bias)."""
-    from .nucleus import check_nucleus
-    top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
-    logits = _dev(logits, name="logits")
+    logits, suffix, tail = _sample_tail(k, False, logits, tokens, logprobs, top_logprobs, mask, no_repeat_ngram, start, stop, top_p, min_p,
+                                        repetition_penalty, frequency_penalty, presence_penalty, bias)
     n_seq, vocab = logits.shape
-    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.size(0) == n_seq
-    logprobs = _logprobs_buffer(logprobs, tokens)
-    top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
-    m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
-    st_ptr = _stop_arg(stop, vocab, logits.device)
-    if st_ptr is not None and stop.sequences and start is None:
-        raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
-    pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tokens.size(1), vocab, k)
-    b_ptr = _bias_arg(bias, pen, start, tokens.size(1), vocab, logits.device, k)
-    if (st_ptr is not None or pen is not None or b_ptr is not None) and not no_repeat_ngram:
-        ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
-    else:
-        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k)
-    args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
-            0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(),
-            _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if b_ptr is not None:
-        check(_lib.load().dh_sample_bf16_bias(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr))
-    elif pen is not None:
-        check(_lib.load().dh_sample_bf16_penalty(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen))
-    elif top_p < 1.0 or min_p > 0.0:
-        check(_lib.load().dh_sample_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
-    elif st_ptr is not None:
-        check(_lib.load().dh_sample_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
-    elif ngram:
-        check(_lib.load().dh_sample_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
-    elif mask is not None:
-        check(_lib.load().dh_sample_bf16_mask(*args, m_ptr, m_ld))
-    else:
-        check(_lib.load().dh_sample_bf16_top(*args))
+    assert tokens.size(0) == n_seq
+    check(getattr(_lib.load(), "dh_sample_bf16" + suffix)(
+        _p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), n_seq, float(temperature),
+        0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), int(step), _stream(), *tail))
 
 
 def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor,
@@ -542,41 +547,17 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
     (dh_sample_rows_bf16_stop).  top_p, min_p: as in sample() (dh_sample_rows_bf16_nucleus).  repetition_penalty, frequency_penalty,
     presence_penalty: as in sample(), start included (dh_sample_rows_bf16_penalty).  bias: as in sample(), start included
     (dh_sample_rows_bf16_bias)."""
-    from .nucleus import check_nucleus
-    top_p, min_p = check_nucleus(top_p, min_p)
     k = _Keep()
-    logits = _dev(logits, name="logits")
+    logits, suffix, tail = _sample_tail(k, True, logits, tokens, logprobs, top_logprobs, mask, no_repeat_ngram, start, stop, top_p, min_p,
+                                        repetition_penalty, frequency_penalty, presence_penalty, bias)
     n_rows, vocab = logits.shape
     n_seq = tokens.size(0)
-    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and row_seq.numel() == n_rows
+    assert row_seq.numel() == n_rows
     assert length.numel() == done.numel() == limit.numel() == n_seq
-    logprobs = _logprobs_buffer(logprobs, tokens)
-    top_n, top_ids, top_lp = _top_buffers(top_logprobs, logprobs, tokens, vocab)
-    m_ptr, m_ld = _mask_arg(mask, n_seq, vocab, logits.device)
-    st_ptr = _stop_arg(stop, vocab, logits.device)
-    pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tokens.size(1), vocab, k)
-    b_ptr = _bias_arg(bias, pen, start, tokens.size(1), vocab, logits.device, k)
-    if (st_ptr is not None or pen is not None or b_ptr is not None) and not no_repeat_ngram:
-        ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
-    else:
-        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=True)
-    args = (_p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
-            k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
-            -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), _p(logprobs), top_n, _p(top_ids), _p(top_lp))
-    if b_ptr is not None:
-        check(_lib.load().dh_sample_rows_bf16_bias(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr))
-    elif pen is not None:
-        check(_lib.load().dh_sample_rows_bf16_penalty(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen))
-    elif top_p < 1.0 or min_p > 0.0:
-        check(_lib.load().dh_sample_rows_bf16_nucleus(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p))
-    elif st_ptr is not None:
-        check(_lib.load().dh_sample_rows_bf16_stop(*args, m_ptr, m_ld, ngram, s_ptr, st_ptr))
-    elif ngram:
-        check(_lib.load().dh_sample_rows_bf16_ngram(*args, m_ptr, m_ld, ngram, s_ptr))
-    elif mask is not None:
-        check(_lib.load().dh_sample_rows_bf16_mask(*args, m_ptr, m_ld))
-    else:
-        check(_lib.load().dh_sample_rows_bf16_top(*args))
+    check(getattr(_lib.load(), "dh_sample_rows_bf16" + suffix)(
+        _p(logits), vocab, _p(tokens), tokens.size(1), k(length, torch.int32), k(done, torch.int32), k(limit, torch.int32),
+        k(row_seq, torch.int32), n_rows, n_seq, int(max_new_tokens), float(temperature), 0 if top_k is None else int(top_k),
+        -1 if eos_id is None else int(eos_id), int(seed) & ((1 << 64) - 1), _stream(), *tail))
 
 
 def quant_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
