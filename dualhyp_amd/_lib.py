@@ -59,6 +59,13 @@ class BiasSpec(C.Structure):
     _fields_ = [("ids", P), ("len", P), ("boost", P), ("h_ids", P), ("h_len", P), ("h_boost", P), ("n", C.c_int32)]
 
 
+class AutomatonSpec(C.Structure):
+    """dh_automaton_spec: the automaton set of one call, device arrays and their host copies (include/dualhyp_hip.h, "Automaton
+    constraints")"""
+    _fields_ = [("edge_off", P), ("edge_tok", P), ("edge_dst", P), ("init", P), ("state", P), ("h_edge_off", P), ("h_edge_tok", P),
+                ("h_edge_dst", P), ("h_init", P), ("n_states", C.c_int), ("n_edges", C.c_int), ("n_seq", C.c_int)]
+
+
 # The sampling entries: the two heads (dh_sample_bf16: ... seed, step, stream; dh_sample_rows_bf16: ... seed, stream) and the options
 # behind them, in the order the entries gained them.  Entry head + suffix takes the tail up to and including its own piece.
 SAMPLE_HEADS = {"dh_sample_bf16": [P, I, P, I, P, P, I, F, I, I64, U64, I, P],
@@ -83,9 +90,18 @@ def _sample_signatures() -> dict:
     return out
 
 
+def _automaton_signatures() -> dict:
+    """The _automaton entries: the _bias entries' arguments and the automaton set behind them.  They are registered here and not as a
+    ninth piece of SAMPLE_TAIL: tests/test_hip_sample_entries.py walks SAMPLE_TAIL with a fixed table of "off" arguments per suffix and
+    would raise on one it does not know."""
+    full = _sample_signatures()
+    return {head + "_automaton": (I, full[head + "_bias"][1] + [C.POINTER(AutomatonSpec)]) for head in SAMPLE_HEADS}
+
+
 # name -> (restype, argtypes); must list every function declared in include/dualhyp_hip.h
 SIGNATURES = {
     **_sample_signatures(),
+    **_automaton_signatures(),
     "dh_abi_version": (I, []),
     "dh_set_tuning": (I, [I, I]),
     "dh_debug_gemm_routes": (U64, [I]),
@@ -172,6 +188,7 @@ SIGNATURES = {
     "dh_engine_set_nucleus": (I, [P, F, F]),
     "dh_engine_set_penalties": (I, [P, C.POINTER(PenaltyArgs), P]),
     "dh_engine_set_bias": (I, [P, C.POINTER(BiasSpec), P]),
+    "dh_engine_set_automaton": (I, [P, C.POINTER(AutomatonSpec), P]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

@@ -91,6 +91,48 @@ int dh_bias_pack(const char* name, const dh_bias_spec* spec, int vocab, bool sta
     return 0;
 }
 
+// dh_automaton_spec -> what the kernels take by value, with the header's argument checks ("Automaton constraints"), made on the host
+// copies: nothing is launched.  Null is off.  What depends on the call (eos_id, the sequence count) is the launchers' check_pick's.
+int dh_automaton_pack(const char* name, const dh_automaton_spec* spec, int vocab, bool start_ok, dh_automaton_args& out) {
+    out = dh_automaton_args{};
+    if (!spec) return 0;
+    const int S = spec->n_states, E = spec->n_edges;
+    DH_CHECK(S >= 1 && E >= 0 && spec->n_seq >= 1, "%s: an automaton set of %d states, %d edges and %d sequences", name, S, E, spec->n_seq);
+    DH_CHECK(spec->edge_off && spec->edge_tok && spec->edge_dst && spec->init && spec->state && spec->h_edge_off && spec->h_edge_tok &&
+             spec->h_edge_dst && spec->h_init, "%s: an automaton set without its offsets, tokens, destinations, start states or state "
+             "buffer (device arrays and host copies)", name);
+    DH_CHECK(vocab <= 131072, "%s: an automaton's allowed row is an LDS row of 131072 ids; vocab=%d does not fit", name, vocab);
+    DH_CHECK(spec->h_edge_off[0] == 0 && spec->h_edge_off[S] == E, "%s: the edge offsets run from %d to %d, not from 0 to the %d edges", name,
+             spec->h_edge_off[0], spec->h_edge_off[S], E);
+    for (int q = 0; q < S; ++q)
+        DH_CHECK(spec->h_edge_off[q] <= spec->h_edge_off[q + 1] && spec->h_edge_off[q + 1] <= E, "%s: the edge offsets are not monotone at "
+                 "state %d (%d, then %d, of %d edges)", name, q, spec->h_edge_off[q], spec->h_edge_off[q + 1], E);
+    for (int q = 0; q < S; ++q) {
+        const int lo = spec->h_edge_off[q], hi = spec->h_edge_off[q + 1];
+        for (int e = lo; e < hi; ++e) {
+            const int t = spec->h_edge_tok[e], d = spec->h_edge_dst[e];
+            DH_CHECK(t >= 0 && t < vocab, "%s: state %d has an edge on token %d, outside the vocabulary of %d", name, q, t, vocab);
+            DH_CHECK(e == lo || spec->h_edge_tok[e - 1] < t, "%s: the edge tokens of state %d are not strictly ascending (%d, then %d)", name,
+                     q, spec->h_edge_tok[e > lo ? e - 1 : e], t);
+            DH_CHECK(d >= 0 && d < S, "%s: an edge of state %d leads to state %d, outside the %d states", name, q, d, S);
+        }
+    }
+    for (int u = 0; u < spec->n_seq; ++u)
+        DH_CHECK(spec->h_init[u] >= 0 && spec->h_init[u] < S, "%s: sequence %d starts in state %d, outside the %d states", name, u,
+                 spec->h_init[u], S);
+    DH_CHECK(start_ok, "%s: an automaton needs `start`, the prompt lengths: a sequence is in its start state while it has generated nothing",
+             name);
+    out.edge_off = spec->edge_off;
+    out.edge_tok = spec->edge_tok;
+    out.edge_dst = spec->edge_dst;
+    out.init = spec->init;
+    out.state = spec->state;
+    out.n_states = S;
+    out.n_edges = E;
+    out.n_seq = spec->n_seq;
+    return 0;
+}
+
 extern "C" int dh_device_info(char* h_buf, int h_buf_len, int* h_num_cu, int64_t* h_hbm_bytes) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

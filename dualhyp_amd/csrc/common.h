@@ -337,6 +337,28 @@ struct dh_bias_args {
 // the prompt lengths
 int dh_bias_pack(const char* name, const dh_bias_spec* spec, int vocab, bool start_ok, dh_bias_args& out);
 
+// Automaton constraints (include/dualhyp_hip.h): a dh_automaton_spec as the kernels take it, by value: the caller's five device arrays and
+// the counts the kernels clamp by.  n_seq is the host's, for the launchers' check of init / state against the call.  edge_off null: off.
+struct dh_automaton_args {
+    const int32_t* edge_off = nullptr;                  // [n_states + 1]
+    const int32_t* edge_tok = nullptr;                  // [n_edges], strictly ascending inside a state
+    const int32_t* edge_dst = nullptr;                  // [n_edges]
+    const int32_t* init = nullptr;                      // [n_seq]
+    int32_t* state = nullptr;                           // [n_seq], the kernels' own
+    int n_states = 0;
+    int n_edges = 0;
+    int n_seq = 0;
+    __host__ __device__ bool on() const { return edge_off != nullptr; }
+    bool operator==(const dh_automaton_args& o) const {
+        return edge_off == o.edge_off && edge_tok == o.edge_tok && edge_dst == o.edge_dst && init == o.init && state == o.state &&
+               n_states == o.n_states && n_edges == o.n_edges && n_seq == o.n_seq;
+    }
+};
+// the checks of every entry that takes a dh_automaton_spec (capi.hip), made on the spec's host copies: null is off; offsets monotone from 0
+// to n_edges, tokens in [0, vocab) and strictly ascending inside a state, edge_dst and init in [0, n_states), vocab <= 131072; start_ok: the
+// entry was given the prompt lengths
+int dh_automaton_pack(const char* name, const dh_automaton_spec* spec, int vocab, bool start_ok, dh_automaton_args& out);
+
 // The options of one pick, as the sampling launchers (sampling.hip) take them from the exported entries and from the engine's captured
 // steps, which compare them as part of a step's key.  The default is every option off: the kernels the plain entries always launched.  A
 // new sampler option is one member here, one line of operator==, and its share of the launchers' check and pack functions.
@@ -348,17 +370,18 @@ struct dh_pick_ctl {
     const uint32_t* mask = nullptr;                     // [n_seq, mask_ld] words: the sequences' allowed tokens, null = the kernels without
     int mask_ld = 0;                                    // one (dh_engine_set_token_mask)
     int ngram = 0;                                      // no-repeat n-grams, 0 = the kernels without it (dh_engine_set_no_repeat_ngram)
-    const int32_t* start = nullptr;                     // [n_seq] prompt lengths: what ngram, stop's sequences, pen and bias count from
+    const int32_t* start = nullptr;                     // [n_seq] prompt lengths: what ngram, stop's sequences, pen, bias and aut count from
     dh_stop_args stop;                                  // the stop test behind the pick (dh_engine_set_stop)
     dh_nucleus_args nuc;                                // top_p / min_p of the sampled branch (dh_engine_set_nucleus)
     dh_penalty_args pen = DH_PENALTY_OFF;               // the three penalties (dh_engine_set_penalties)
     dh_bias_args bias;                                  // the bias entries (dh_engine_set_bias)
-    // ngram, pen or bias on: the history-reading kernel family
-    bool hist() const { return ngram > 0 || dh_penalty_on(pen) || bias.n > 0; }
+    dh_automaton_args aut;                              // the sequences' automata (dh_engine_set_automaton)
+    // ngram, pen, bias or an automaton on: the history-reading kernel family
+    bool hist() const { return ngram > 0 || dh_penalty_on(pen) || bias.n > 0 || aut.on(); }
     bool operator==(const dh_pick_ctl& o) const {
         return logprobs == o.logprobs && top_n == o.top_n && top_ids == o.top_ids && top_lp == o.top_lp && mask == o.mask &&
                mask_ld == o.mask_ld && ngram == o.ngram && start == o.start && stop == o.stop && nuc == o.nuc &&
-               dh_penalty_same(pen, o.pen) && bias == o.bias;
+               dh_penalty_same(pen, o.pen) && bias == o.bias && aut == o.aut;
     }
 };
 
@@ -379,7 +402,7 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
                               dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream);
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& ctl, void* stream);   // ctl: nuc, pen and bias off
+                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& ctl, void* stream);   // ctl: nuc, pen, bias and aut off
 
 // the selection step of beam search (beam.hip, dh_beam_select_bf16), as the engine's captured step calls it
 // stop: its set ends a hypothesis as the EOS does, its sequences as well under device histories; hist (nullable, int64

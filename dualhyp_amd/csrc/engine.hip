@@ -43,7 +43,7 @@ struct dh_engine {
     // ran).  `set.start` stays null: the four setters that take the [n_seq] prompt lengths each keep their own pointer, null while their
     // option is off, and step_ctl() below gives a step the one it reads.
     dh_pick_ctl set;
-    const int32_t *ngram_start = nullptr, *stop_start = nullptr, *pen_start = nullptr, *bias_start = nullptr;
+    const int32_t *ngram_start = nullptr, *stop_start = nullptr, *pen_start = nullptr, *bias_start = nullptr, *aut_start = nullptr;
     int32_t* stop_fin_tok = nullptr;                    // dh_engine_set_stop: a beam call's [n_utt, W] ending ids
     int64_t* beam_hist = nullptr;                       // dh_engine_set_beam_history: the caller's [2][n_utt * W][max_new] history planes (null: off)
     int beam_hist_ngram = 0;                            // and the beam steps' no_repeat_ngram (0: no ban)
@@ -1017,13 +1017,14 @@ dh_pick_ctl step_ctl(const dh_engine* e, StepKind kind, int top_k) {
     c.stop = e->set.stop;
     if (kind == STEP_BEAM) return c;                    // the selection takes the mask and the stop specification, nothing else
     c = e->set;
-    if (kind == STEP_VERIFY) {                          // dh_engine_decode_spec has refused both
+    if (kind == STEP_VERIFY) {                          // dh_engine_decode_spec has refused all three
         c.pen = DH_PENALTY_OFF;
         c.bias = dh_bias_args{};
+        c.aut = dh_automaton_args{};
     }
     if (kind == STEP_VERIFY || top_k == 1) c.nuc = dh_nucleus_args{};   // the arg-max takes neither parameter: its step is the plain one
     // the prompt lengths of the step's history readers and stop sequences: the setters were given the same numbers
-    c.start = c.ngram ? e->ngram_start : dh_penalty_on(c.pen) ? e->pen_start : c.bias.n ? e->bias_start : e->stop_start;
+    c.start = c.ngram ? e->ngram_start : dh_penalty_on(c.pen) ? e->pen_start : c.bias.n ? e->bias_start : c.aut.on() ? e->aut_start : e->stop_start;
     return c;
 }
 
@@ -1035,6 +1036,15 @@ int check_pen_tables(const dh_engine* e, const char* name, int tok_ld) {
     DH_CHECK(!dh_penalty_on(c.pen) || c.bias.n == 0 || tok_ld + c.bias.n_ids <= DH_MAX_PENALTY_HISTORY, "%s: penalties and a bias are "
              "set and share static LDS tables of %d entries; tok_ld=%d and the entries' %d ids may not fit", name, DH_MAX_PENALTY_HISTORY,
              tok_ld, c.bias.n_ids);
+    return 0;
+}
+
+// the same two entries: what an automaton set needs of the call, refused here, before a step is captured or launched
+int check_automaton_call(const dh_engine* e, const char* name, int64_t eos_id, int n_seq) {
+    const dh_automaton_args& a = e->set.aut;
+    DH_CHECK(!a.on() || (eos_id >= 0 && eos_id < e->d.vocab), "%s: an automaton set is set and needs an eos_id in [0, %d), got %lld: a dead "
+             "end ends the sequence with it", name, e->d.vocab, (long long)eos_id);
+    DH_CHECK(!a.on() || a.n_seq == n_seq, "%s: the automaton set holds start states for %d sequences, the call has %d", name, a.n_seq, n_seq);
     return 0;
 }
 
@@ -1306,6 +1316,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
     if (int rc = check_pen_tables(e, "dh_engine_decode", tok_ld)) return rc;
+    if (int rc = check_automaton_call(e, "dh_engine_decode", eos_id, n_seq)) return rc;
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
@@ -1330,6 +1341,7 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(n_seq > 0 && tok_ld > 0 && max_new_tokens > 0, "dh_engine_decode_rows: bad shape");
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
     if (int rc = check_pen_tables(e, "dh_engine_decode_rows", tok_ld)) return rc;
+    if (int rc = check_automaton_call(e, "dh_engine_decode_rows", eos_id, n_seq)) return rc;
     if (n_steps <= 0) return 0;
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
@@ -1380,6 +1392,8 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
              "history would have to include this launch's own picks", (double)e->set.pen.repetition, (double)e->set.pen.frequency, (double)e->set.pen.presence);
     DH_CHECK(e->set.bias.n == 0, "dh_engine_decode_spec: a bias of %d entries is set; a verify position's tail would have to include this "
              "launch's own picks, so the step would need per-position tables", e->set.bias.n);
+    DH_CHECK(!e->set.aut.on(), "dh_engine_decode_spec: an automaton set of %d states is set; a verify position's state would depend on the "
+             "picks of this launch's earlier positions", e->set.aut.n_states);
     DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
     DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
@@ -1455,6 +1469,8 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_CHECK(e->set.bias.n == 0, "dh_engine_decode_beam: a bias of %d entries is set; %s", e->set.bias.n,
              e->beam_hist ? "a boosted logit would change what a candidate's rank and a beam's score mean, which beam search does not define"
                           : "a beam's history lives on the host, so the device cannot match it");
+    DH_CHECK(!e->set.aut.on(), "dh_engine_decode_beam: an automaton set of %d states is set; a re-parented beam would have to take over its "
+             "parent's state, which the selection does not carry", e->set.aut.n_states);
     DH_CHECK(e->set.stop.n_seqs == 0 || e->beam_hist, "dh_engine_decode_beam: %d stop sequences are set; a beam's history lives on the host, so the device "
              "cannot match a sequence against it (the stop set alone goes with beam search)", e->set.stop.n_seqs);
     DH_CHECK(!e->set.stop.on() || e->stop_fin_tok, "dh_engine_decode_beam: a stop set is set without beam_fin_tok, the ids that end the pool entries");
@@ -1564,6 +1580,15 @@ extern "C" int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const 
     if (int rc = dh_bias_pack("dh_engine_set_bias", bias, e->d.vocab, start != nullptr, ba)) return rc;
     e->set.bias = ba;
     e->bias_start = ba.n ? start : nullptr;
+    return 0;
+}
+
+extern "C" int dh_engine_set_automaton(dh_engine* e, const dh_automaton_spec* automaton, const int32_t* start) {
+    DH_CHECK(e, "dh_engine_set_automaton: null engine");
+    dh_automaton_args aa;
+    if (int rc = dh_automaton_pack("dh_engine_set_automaton", automaton, e->d.vocab, start != nullptr, aa)) return rc;
+    e->set.aut = aa;
+    e->aut_start = aa.on() ? start : nullptr;
     return 0;
 }
 

@@ -329,9 +329,17 @@ constexpr int MAX_NGRAM = 8;
 // is never taken from an empty set).  Every thread gets the LDS row, in the mask row's layout with the bits at and behind vocab clear;
 // it holds until the block's next call, which the caller separates from the pick's last read by a barrier (pick_token ends on one).
 // KEEP (the beam candidates, "Beam histories"): the fallback is taken when fewer than `keep` bits are left, not when none is.
+// ae ("Automaton constraints" of the header; launch-uniform, off: the start row it always was): the start row is the bits of the state's
+// edge tokens ae.tok[ae.lo .. ae.hi), ANDed with the mask row (MASK), or bit ae.eos alone where that leaves none — set with LDS atomicOr
+// by every thread at stride NT, so a state may hold more edges than the block has threads; the ban and its fallback then work on it.
+struct aut_edges {
+    const int32_t* tok = nullptr;                       // null: no automaton
+    int lo = 0, hi = 0;                                 // the state's edge range, inside [0, n_edges]
+    int eos = 0;                                        // the call's eos_id, in [0, vocab)
+};
 template <bool MASK, bool KEEP = false>
 __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int ngram, int vocab, const uint32_t* __restrict__ mrow,
-                                                   int keep = 1) {
+                                                   int keep = 1, const aut_edges ae = aut_edges{}) {
     __shared__ uint32_t s_row[BAN_MAX_VOCAB / 32];
     __shared__ int s_cnt[NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -342,8 +350,41 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
         if constexpr (MASK) v = mrow[w];
         return w == nw - 1 ? v & tail : v;
     };
-    for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
-    __syncthreads();
+    // the row's set bits, by the whole block (an integer sum: exact in any order); the caller keeps a barrier between two calls
+    auto count_row = [&]() -> int {
+        int cnt = 0;
+        for (int w = tid; w < nw; w += NT) cnt += __popc(s_row[w]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        if (lane == 0) s_cnt[wave] = cnt;
+        __syncthreads();
+        cnt = 0;
+        for (int w = 0; w < NT / 64; ++w) cnt += s_cnt[w];
+        return cnt;
+    };
+    // the start row, ending on a barrier
+    auto fill_start = [&]() {
+        if (ae.tok) {                                   // the same for every thread of the launch
+            for (int w = tid; w < nw; w += NT) s_row[w] = 0u;
+            __syncthreads();
+            for (int e = ae.lo + tid; e < ae.hi; e += NT) {
+                const int t = ae.tok[e];
+                if (t < 0 || t >= vocab) continue;      // the host has refused such an edge
+                uint32_t bit = 1u << (t & 31);
+                if constexpr (MASK) bit &= mrow[t >> 5];
+                if (bit) atomicOr(&s_row[t >> 5], bit);
+            }
+            __syncthreads();
+            if (count_row() == 0) {                     // a dead end, the same for every thread: the EOS alone, mask or not
+                if (tid == 0 && ae.eos >= 0 && ae.eos < vocab) s_row[ae.eos >> 5] = 1u << (ae.eos & 31);
+                __syncthreads();
+            }
+        } else {
+            for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
+            __syncthreads();
+        }
+    };
+    fill_start();
     if (ngram == 0 || m < ngram) return s_row;          // the same for every thread: no ban (a penalty alone), or no n-gram is complete yet
     int64_t suf[MAX_NGRAM - 1];                         // the (ngram - 1)-token suffix every candidate is tested against
 #pragma unroll
@@ -360,20 +401,10 @@ __device__ __forceinline__ const uint32_t* ban_row(const int64_t* g, int m, int 
     }
     __syncthreads();
     // everything banned?  popcount of the row (an integer sum: exact in any order)
-    int cnt = 0;
-    for (int w = tid; w < nw; w += NT) cnt += __popc(s_row[w]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if (lane == 0) s_cnt[wave] = cnt;
-    __syncthreads();
-    cnt = 0;
-    for (int w = 0; w < NT / 64; ++w) cnt += s_cnt[w];
+    const int cnt = count_row();
     bool refill = cnt == 0;                             // the same for every thread
     if constexpr (KEEP) refill = cnt < keep;
-    if (refill) {
-        for (int w = tid; w < nw; w += NT) s_row[w] = start_word(w);
-        __syncthreads();
-    }
+    if (refill) fill_start();
     return s_row;
 }
 
@@ -527,17 +558,46 @@ __device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int
     return ov;
 }
 
+// Automaton constraints (include/dualhyp_hip.h): the state sequence u is in at a pick behind m generated tokens, and its edge range as
+// ban_row takes it.  The host has checked the arrays' host copies; the clamps only keep a read inside the device arrays whatever they hold.
+__device__ __forceinline__ aut_edges aut_state(const dh_automaton_args& aut, int u, int m, int64_t eos_id, int& q) {
+    q = m == 0 ? aut.init[u] : aut.state[u];
+    if (q < 0 || q >= aut.n_states) q = 0;
+    int lo = aut.edge_off[q], hi = aut.edge_off[q + 1];
+    hi = hi < 0 ? 0 : hi > aut.n_edges ? aut.n_edges : hi;
+    lo = lo < 0 ? 0 : lo > hi ? hi : lo;
+    return aut_edges{aut.edge_tok, lo, hi, (int)eos_id};
+}
+// The transition behind the pick `choice`, by the whole block: state[u] = edge_dst[e] of q's edge on `choice`, or q where it has none.  An
+// edge is unique per (state, token), so at most one thread finds it; thread 0 stores the result with a plain vector store.  The read of
+// state[u] in aut_state lies behind the row build's and the pick's barriers, and no other block touches the entry.
+__device__ __forceinline__ void aut_step(const dh_automaton_args& aut, const aut_edges& ae, int q, int choice, int u) {
+    __shared__ int s_next;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_next = q;
+    __syncthreads();
+    for (int e = ae.lo + tid; e < ae.hi; e += NT) {
+        if (ae.tok[e] == choice) {
+            const int d = aut.edge_dst[e];
+            if (d >= 0 && d < aut.n_states) s_next = d;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) aut.state[u] = s_next;
+}
+
 // pick_token under no_repeat_ngram: under the row ban_row builds from the sequence's history g[0..m), through the masked paths of
 // pick_token (the 16-byte mask_byte loads included), so the pick is the unmasked pick on a copy of the row with -inf in every column that
 // the mask disallows or the history bans.  The kernels' BAN = false instantiations call pick_token<MASK> as they always did.
 // pen, bias (launch-uniform; ngram may be 0 then): the columns of the history's ids hold a_t, and those of the ids the bias proposes their
 // boosted value, as well, through pick_token's PEN paths.  Both off, the pick runs the instantiation it always ran.
+// ae (launch-uniform): ban_row's start row is the automaton state's allowed row; everything behind it is unchanged.
 template <bool MASK>
 __device__ __forceinline__ int pick_token_banned(const bf16_t* __restrict__ lg, int vocab, float temperature, int top_k, uint64_t seed,
                                              int step, int seq, const uint32_t* __restrict__ mrow, const int64_t* g, int m, int ngram,
                                              const dh_nucleus_args nuc = dh_nucleus_args{}, const dh_penalty_args pen = DH_PENALTY_OFF,
-                                             const dh_bias_args bias = dh_bias_args{}) {
-    const uint32_t* row = ban_row<MASK>(g, m, ngram, vocab, mrow);
+                                             const dh_bias_args bias = dh_bias_args{}, const aut_edges ae = aut_edges{}) {
+    const uint32_t* row = ban_row<MASK>(g, m, ngram, vocab, mrow, 1, ae);
     if (dh_penalty_on(pen) || bias.n > 0) {             // the same for every thread of the launch
         const pen_view ov = pen_build(lg, vocab, g, m, pen, bias);
         return pick_token<true, true>(lg, vocab, temperature, top_k, seed, step, seq, row, nuc, ov);
@@ -768,15 +828,19 @@ __global__ __launch_bounds__(NT) void sample_kernel(const bf16_t* __restrict__ l
                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                     const uint32_t* __restrict__ mask, int mask_ld, int ngram,
                                                     const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc,
-                                                    dh_penalty_args pen, dh_bias_args bias) {
+                                                    dh_penalty_args pen, dh_bias_args bias, dh_automaton_args aut) {
     const int seq = blockIdx.x, tid = threadIdx.x;
     if (done[seq]) return;
     const int step = step_dev ? *step_dev : step_arg;   // device counter keeps a captured graph replayable
     int choice;
     if constexpr (BAN) {                                // the history is what lies behind the prompt
-        const int p0 = start[seq];
+        const int p0 = start[seq], m = length[seq] - p0;
+        int q = 0;
+        aut_edges ae;
+        if (aut.on()) ae = aut_state(aut, seq, m, eos_id, q);          // the same for every thread of the launch
         choice = pick_token_banned<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
-                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, length[seq] - p0, ngram, nuc, pen, bias);
+                                     MASK ? mask + (size_t)seq * mask_ld : nullptr, tokens + (size_t)seq * tok_ld + p0, m, ngram, nuc, pen, bias, ae);
+        if (aut.on()) aut_step(aut, ae, q, choice, seq);
     } else {
         choice = pick_token<MASK>(logits + (size_t)seq * vocab, vocab, temperature, top_k, seed, step, seq,
                                   MASK ? mask + (size_t)seq * mask_ld : nullptr, nuc);
@@ -815,7 +879,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
                                                          const int32_t* __restrict__ start, dh_stop_args sa, dh_nucleus_args nuc,
-                                                    dh_penalty_args pen, dh_bias_args bias) {
+                                                    dh_penalty_args pen, dh_bias_args bias, dh_automaton_args aut) {
     const int u = row_seq[blockIdx.x], tid = threadIdx.x;
     if (u < 0 || u >= n_seq || done[u]) return;
     const int n = length[u], lim = min(limit[u], tok_ld);
@@ -823,8 +887,12 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
     int choice;
     if constexpr (BAN) {
         const int p0 = start ? start[u] : limit[u] - max_new;           // the prompt length, which limit[u] - max_new is
+        int q = 0;
+        aut_edges ae;
+        if (aut.on()) ae = aut_state(aut, u, n - p0, eos_id, q);       // the sequence's state, not the logits row's
         choice = pick_token_banned<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
-                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc, pen, bias);
+                                     MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc, pen, bias, ae);
+        if (aut.on()) aut_step(aut, ae, q, choice, u);
     } else {
         choice = pick_token<MASK>(logits + (size_t)blockIdx.x * vocab, vocab, temperature, top_k, seed, step, u,
                                   MASK ? mask + (size_t)u * mask_ld : nullptr, nuc);     // the sequence's mask row, not the logits row's
@@ -995,8 +1063,17 @@ int check_mask_ld(const char* name, int vocab, const uint32_t* mask, int mask_ld
 // What the three launchers check of a pick's options.  hist_max: the longest history a pick of the call can see; start_needed: the kernel
 // has no other way to the prompt lengths (the row-list kernel has limit - max_new).  A bias itself is checked where it is packed
 // (dh_bias_pack); here what depends on the call: with a penalty on, the history's ids and the entries' ids share the tables.
-int check_pick(const char* name, int vocab, int hist_max, bool start_needed, const dh_pick_ctl& c) {
-    const bool pen = dh_penalty_on(c.pen), bias = c.bias.n != 0;
+// eos_id, n_seq: the call's, for an automaton — its dead end picks the EOS, and init / state hold an entry per sequence.
+int check_pick(const char* name, int vocab, int hist_max, bool start_needed, const dh_pick_ctl& c, int64_t eos_id = -1, int n_seq = 0) {
+    const bool pen = dh_penalty_on(c.pen), bias = c.bias.n != 0, aut = c.aut.on();
+    DH_CHECK(!aut || c.start, "%s: an automaton needs `start`, the prompt lengths: a sequence is in its start state while it has generated "
+             "nothing", name);
+    DH_CHECK(!aut || vocab <= BAN_MAX_VOCAB, "%s: an automaton's allowed row is a static LDS row of %d ids; vocab=%d does not fit", name,
+             BAN_MAX_VOCAB, vocab);
+    DH_CHECK(!aut || (eos_id >= 0 && eos_id < vocab), "%s: an automaton needs an eos_id in [0, %d), got %lld: a dead end ends the sequence "
+             "with it", name, vocab, (long long)eos_id);
+    DH_CHECK(!aut || c.aut.n_seq == n_seq, "%s: the automaton set holds start states for %d sequences, the call has %d", name, c.aut.n_seq,
+             n_seq);
     DH_CHECK(!pen || c.start, "%s: penalties need `start`, the prompt lengths: the history is what lies behind the prompt", name);
     DH_CHECK(!pen || vocab <= BAN_MAX_VOCAB, "%s: penalties keep a sequence's overridden columns in a static LDS row of %d ids; vocab=%d "
              "does not fit", name, BAN_MAX_VOCAB, vocab);
@@ -1025,7 +1102,8 @@ int check_pick(const char* name, int vocab, int hist_max, bool start_needed, con
 int pack_pick(const char* name, bool start_implied, int vocab, dh_pick_ctl& c, float* logprobs, int top_n = 0, int32_t* top_ids = nullptr,
               float* top_lp = nullptr, const uint32_t* mask = nullptr, int mask_ld = 0, int ngram = 0, const int32_t* start = nullptr,
               const dh_stop_spec* stop = nullptr, float top_p = 1.f, float min_p = 0.f, const dh_penalty_args* penalties = nullptr,
-              const dh_bias_spec* bias = nullptr) {
+              const dh_bias_spec* bias = nullptr, const dh_automaton_spec* automaton = nullptr) {
+    if (int rc = dh_automaton_pack(name, automaton, vocab, start != nullptr, c.aut)) return rc;
     if (int rc = dh_bias_pack(name, bias, vocab, start != nullptr, c.bias)) return rc;
     if (int rc = dh_penalty_pack(name, penalties, c.pen)) return rc;
     if (int rc = dh_nucleus_pack(name, top_p, min_p, c.nuc)) return rc;
@@ -1047,7 +1125,7 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
                    float temperature, int top_k, int64_t eos_id, uint64_t seed, int step, const int32_t* step_dev,
                    const dh_pick_ctl& c, void* stream) {
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0, "dh_sample_bf16: bad shape");
-    if (int rc = check_pick("dh_sample_bf16", vocab, tok_ld, true, c)) return rc;
+    if (int rc = check_pick("dh_sample_bf16", vocab, tok_ld, true, c, eos_id, n_seq)) return rc;
     DH_CHECK(temperature > 0.f, "dh_sample_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_bf16: top_k must be >= 0 (0 = no crop)");
     if (n_seq == 0) return 0;
@@ -1055,7 +1133,7 @@ int dh_sample_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_kernel, c), dim3(n_seq), dim3(NT), dh_penalty_on(c.pen) || c.bias.n > 0 ? PEN_LDS_BYTES : 0,
                        (hipStream_t)stream,
                        logits, vocab, tokens, tok_ld, length, done, temperature, top_k, eos_id, seed, step, step_dev, c.logprobs, c.top_n,
-                       c.top_ids, c.top_lp, c.mask, c.mask_ld, c.ngram, c.start, c.stop, c.nuc, c.pen, c.bias);
+                       c.top_ids, c.top_lp, c.mask, c.mask_ld, c.ngram, c.start, c.stop, c.nuc, c.pen, c.bias, c.aut);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -1146,6 +1224,19 @@ extern "C" int dh_sample_bf16_bias(const dh_bf16* logits, int vocab, int64_t* to
     return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
 }
 
+extern "C" int dh_sample_bf16_automaton(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                        int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                        int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                        const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                        float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias,
+                                        const dh_automaton_spec* automaton) {
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_bf16_automaton", false, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram, start,
+                           stop, top_p, min_p, penalties, bias, automaton))
+        return rc;
+    return dh_sample_impl(logits, vocab, tokens, tok_ld, length, done, n_seq, temperature, top_k, eos_id, seed, step, nullptr, c, stream);
+}
+
 extern "C" int dh_sample_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                               int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id, uint64_t seed,
                               int step, void* stream) {
@@ -1157,7 +1248,7 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
                         const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq, int max_new, float temperature,
                         int top_k, int64_t eos_id, uint64_t seed, const dh_pick_ctl& c, void* stream) {
     DH_CHECK(logits && tokens && length && done && limit && row_seq, "dh_sample_rows_bf16: null argument");
-    if (int rc = check_pick("dh_sample_rows_bf16", vocab, tok_ld, false, c)) return rc;
+    if (int rc = check_pick("dh_sample_rows_bf16", vocab, tok_ld, false, c, eos_id, n_seq)) return rc;
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_rows >= 0 && n_seq > 0 && max_new > 0, "dh_sample_rows_bf16: bad shape");
     DH_CHECK(temperature > 0.f, "dh_sample_rows_bf16: temperature must be > 0");
     DH_CHECK(top_k >= 0, "dh_sample_rows_bf16: top_k must be >= 0 (0 = no crop)");
@@ -1165,7 +1256,7 @@ int dh_sample_rows_impl(const dh_bf16* logits, int vocab, int64_t* tokens, int t
     hipLaunchKernelGGL(DH_PICK_VARIANT(sample_rows_kernel, c), dim3(n_rows), dim3(NT),
                        dh_penalty_on(c.pen) || c.bias.n > 0 ? PEN_LDS_BYTES : 0, (hipStream_t)stream, logits, vocab, tokens, tok_ld, length,
                        done, limit, row_seq, n_seq, max_new, temperature, top_k, eos_id, seed, c.logprobs, c.top_n, c.top_ids, c.top_lp, c.mask,
-                       c.mask_ld, c.ngram, c.start, c.stop, c.nuc, c.pen, c.bias);
+                       c.mask_ld, c.ngram, c.start, c.stop, c.nuc, c.pen, c.bias, c.aut);
     DH_LAUNCH_CHECK();
     return 0;
 }
@@ -1271,6 +1362,21 @@ extern "C" int dh_sample_rows_bf16_bias(const dh_bf16* logits, int vocab, int64_
                                eos_id, seed, c, stream);
 }
 
+extern "C" int dh_sample_rows_bf16_automaton(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                             int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                             int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream,
+                                             float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp, const uint32_t* mask,
+                                             int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop, float top_p,
+                                             float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias,
+                                             const dh_automaton_spec* automaton) {
+    dh_pick_ctl c;
+    if (int rc = pack_pick("dh_sample_rows_bf16_automaton", true, vocab, c, logprobs, top_logprobs, top_ids, top_lp, mask, mask_ld, ngram,
+                           start, stop, top_p, min_p, penalties, bias, automaton))
+        return rc;
+    return dh_sample_rows_impl(logits, vocab, tokens, tok_ld, length, done, limit, row_seq, n_rows, n_seq, max_new, temperature, top_k,
+                               eos_id, seed, c, stream);
+}
+
 extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
                                    int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
                                    int max_new, float temperature, int top_k, int64_t eos_id, uint64_t seed, void* stream) {
@@ -1282,7 +1388,8 @@ int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
                         const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& c, void* stream) {
     // a verify position's history would have to include this launch's own picks, and the acceptance is an arg-max
-    DH_CHECK(!c.nuc.on() && !dh_penalty_on(c.pen) && c.bias.n == 0, "spec_accept: a verify step takes no nucleus, no penalty and no bias");
+    DH_CHECK(!c.nuc.on() && !dh_penalty_on(c.pen) && c.bias.n == 0 && !c.aut.on(),
+             "spec_accept: a verify step takes no nucleus, no penalty, no bias and no automaton");
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
     if (int rc = check_pick("spec_accept", vocab, tok_ld, true, c)) return rc;
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");

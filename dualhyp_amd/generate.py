@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence, Union
 
 import torch
 
+from . import automaton as _automaton
 from . import beam as _beam
 from . import bias as _bias
 from . import constrain as _constrain
@@ -131,8 +132,25 @@ def _compile_bias(model, bias, pen, tok_ld: int, dev):
     return spec
 
 
+def _automaton_kw(aut) -> dict:
+    """The sampling ops' keyword of a call's automaton set (none when it is off)."""
+    return dict(automaton=aut) if aut is not None else {}
+
+
+def _check_automaton(automaton, speculate: int = 0):
+    """`automaton=` looked at before the model is touched: its type, and what it does not go with.  Needs nothing but the arguments; the
+    set is checked against the call (sequences, vocabulary, eos_id) by _automaton.as_set."""
+    if automaton is None:
+        return None
+    if not isinstance(automaton, _automaton.AutomatonSet):
+        raise TypeError(f"automaton is a dualhyp_amd.automaton.AutomatonSet (from_sequences, from_prompts), not {automaton!r}")
+    if speculate:
+        raise ValueError(f"speculate={speculate} does not go with an automaton of {automaton.n_states} states: {_automaton.SPEC_REFUSAL}")
+    return automaton
+
+
 @contextlib.contextmanager
-def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float, pen=None, bias=None):
+def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float, pen=None, bias=None, aut=None):
     """What a call hands the engine for its captured decode steps, each only where the call uses it — every one is part of a captured
     step's key, so without it the call runs the steps it always ran — and takes back behind them: the buffers are the call's."""
     nuc = top_p < 1.0 or min_p > 0.0
@@ -152,9 +170,13 @@ def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p:
         eng.set_penalties(*pen, start=start)
     if bias is not None:
         eng.set_bias(bias, start)
+    if aut is not None:
+        eng.set_automaton(aut, start)
     try:
         yield
     finally:
+        if aut is not None:
+            eng.set_automaton()
         if bias is not None:
             eng.set_bias()
         if pen:
@@ -210,7 +232,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
                    stop=None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                    repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                   presence_penalty: Optional[float] = None, bias=None):
+                   presence_penalty: Optional[float] = None, bias=None, automaton=None):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -300,7 +322,19 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     own and without writing the logits; a masked or banned column stays -inf, and log-probabilities and alternatives stay the raw
     row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p, the penalties
     (then the token buffer's places plus the entries' ids may be at most 2048) and fp8; speculate is refused.  None (the default) and
-    an empty list are off: the call it always was."""
+    an empty list are off: the call it always was.
+
+    automaton (a dualhyp_amd.automaton.AutomatonSet with a start state per prompt — from_sequences, from_prompts; it needs an eos_id;
+    include/dualhyp_hip.h, "Automaton constraints"): a sequential constraint, the general form of token_mask — sequence i produces only
+    texts its automaton can follow.  At every pick the allowed ids are the tokens on the edges of the sequence's state (its start state
+    while it has generated nothing), under token_mask as well; a state that may end the text has an edge on the eos_id, and a state left
+    with nothing to pick ends the sequence with the EOS.  no_repeat_ngram, the penalties and the bias work on that row, with whatever
+    sampler the call uses.  The row is built, and the state moved along the picked edge, inside the sampling kernels — the prefill's first
+    pick and every captured decode step — with no launch or read-back of their own; log-probabilities and alternatives stay the raw
+    row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p, the penalties, bias
+    and fp8; speculate is refused.  return_state gains automaton_state, the int32 [B] states behind the last picks.  None (the default)
+    is off: the call it always was."""
+    automaton = _check_automaton(automaton, speculate)
     bias = _check_bias(bias, speculate)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
@@ -322,6 +356,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
     dev = model.transformer.wte.weight.device
     bias = _compile_bias(model, bias, pen, T_max + max_new_tokens, dev)
+    aut = None if automaton is None else _automaton.as_set(automaton, B, model.config.padded_vocab_size, dev, eos_id)
     mask = _token_mask(model, token_mask, B, 1, dev)
     stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
@@ -346,7 +381,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         length = torch.tensor(lens, dtype=torch.int32, device=dev)
         done = torch.zeros(B, dtype=torch.int32, device=dev)
     # the prompt lengths: the ban's and the penalties' history, and a stop sequence's or a bias entry's match, begin there
-    start = torch.tensor(lens, dtype=torch.int32, device=dev) if ngram or pen or bias is not None or (stop is not None and stop.sequences) else None
+    start = torch.tensor(lens, dtype=torch.int32, device=dev) \
+        if ngram or pen or bias is not None or aut is not None or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
@@ -362,11 +398,11 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
                top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p,
-               **_penalty_kw(pen), **_bias_kw(bias))
+               **_penalty_kw(pen), **_bias_kw(bias), **_automaton_kw(aut))
     if ev:
         ev[1].record()
     # each of these is part of the captured step's key; without it the call runs the steps it always ran
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias, aut):
         steps_run = 0
         if max_new_tokens > 1:
             n = max_new_tokens - 1
@@ -421,6 +457,8 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
             st["top_ids"], st["top_logprobs"] = top_buf
         if D and steps_run:             # the last verify step's drafts and the lengths they were proposed from
             st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
+        if aut is not None:
+            st["automaton_state"] = aut.state
         res += (st,)
     return res if len(res) > 1 else out
 
@@ -442,7 +480,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                  eos_id: Optional[int] = None, prefill_batch: int = 32, share_prefix: Union[bool, str] = False, token_mask=None,
                  no_repeat_ngram: int = 0, stop=None, top_logprobs: int = 0, timing: Optional[dict] = None,
                  return_state: bool = False, speculate: int = 0, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None):
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None):
     """num_samples = N (2..8) sampled candidates per prompt from ONE prefill of it (include/dualhyp_hip.h, "Sampled candidates").
 
     DEFINITION: sample j of utterance u is row u * N + j of generate_batch over [p for p in prompts for _ in range(N)] with the same
@@ -454,7 +492,9 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     decode steps are generate_batch's over B * N rows.  (A chunk of one-token prompts alone is forwarded by the single-token
     kernels, as generate_batch forwards it; the chunks here hold utterances, there rows.)
 
-    token_mask: one row, or id list, per UTTERANCE, serving its N samples.  The other arguments are generate_batch's.
+    token_mask: one row, or id list, per UTTERANCE, serving its N samples.  automaton: one start state per UTTERANCE — row u * N + j
+    starts in utterance u's — and a state per row (return_state's automaton_state, B * N entries).  The other arguments are
+    generate_batch's.
 
     Returns, per utterance, the list of its N samples in sample order, each a dict of
       tokens          1-D int64 CPU tensor, the generated ids, cut before the EOS as generate_batch cuts,
@@ -482,6 +522,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                          "ids into the source slots does not hold")
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     bias = _check_bias(bias)
+    automaton = _check_automaton(automaton)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
@@ -499,6 +540,9 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
     dev = model.transformer.wte.weight.device
     bias = _compile_bias(model, bias, pen, T_max + max_new_tokens, dev)
+    aut = None if automaton is None else _automaton.as_set(automaton, B, model.config.padded_vocab_size, dev, eos_id)
+    if aut is not None:
+        aut = aut.repeat(N)                                       # a start state and a state per decode row
     mask = _token_mask(model, token_mask, B, 1, dev)
     if mask is not None:
         mask = mask.repeat_interleave(N, dim=0).contiguous()      # a row per decode row
@@ -515,7 +559,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     length = torch.tensor(row_lens, dtype=torch.int32, device=dev)
     done = torch.zeros(R, dtype=torch.int32, device=dev)
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)      # what the fork reads
-    start = length.clone() if ngram or pen or bias is not None or (stop is not None and stop.sequences) else None
+    start = length.clone() if ngram or pen or bias is not None or aut is not None or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
     if ev:
@@ -534,11 +578,11 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         ev[4].record()
     ops.sample(last.repeat_interleave(N, dim=0), tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed,
                step=0, logprobs=lp_buf, top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p,
-               min_p=min_p, **_penalty_kw(pen), **_bias_kw(bias))
+               min_p=min_p, **_penalty_kw(pen), **_bias_kw(bias), **_automaton_kw(aut))
     if ev:
         ev[1].record()
     steps_run = 0
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias, aut):
         if max_new_tokens > 1:
             steps_run = _decode_steps(eng, tokens, length, done, max_new_tokens - 1, temperature, top_k, eos_id, seed,
                                       early=eos_id is not None or stop is not None)
@@ -575,6 +619,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         st = dict(tokens=tokens, length=length, done=done, logprobs=lp_buf)
         if K:
             st["top_ids"], st["top_logprobs"] = top_buf
+        if aut is not None:
+            st["automaton_state"] = aut.state
         return out, st
     return out
 
@@ -728,7 +774,7 @@ class _StreamBackend:
 
     def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
                  logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None,
-                 top_p: float = 1.0, min_p: float = 0.0, pen=None, bias=None) -> None:
+                 top_p: float = 1.0, min_p: float = 0.0, pen=None, bias=None, aut=None) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
@@ -753,8 +799,11 @@ class _StreamBackend:
         self.top_p, self.min_p = top_p, min_p    # generate_batch's top_p / min_p (the decode steps get them through the engine)
         self.pen = pen                       # generate_batch's penalties, checked (None: off); their history counts from the same lengths
         self.bias = bias                     # generate_batch's bias, compiled (None: off); its matches count from the same lengths
+        # generate_batch's automaton set and a valid start state for the dummy sequence, which never picks; a refilled row starts
+        # over by itself: its sequence has generated nothing, so its pick reads the start state
+        self.aut = None if aut is None else aut.padded()
         self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) \
-            if ngram or pen or bias is not None or (stop is not None and stop.sequences) else None
+            if ngram or pen or bias is not None or aut is not None or (stop is not None and stop.sequences) else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -777,7 +826,8 @@ class _StreamBackend:
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
                         self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
-                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **_penalty_kw(self.pen), **_bias_kw(self.bias), **self.kw)
+                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **_penalty_kw(self.pen), **_bias_kw(self.bias),
+                        **_automaton_kw(self.aut), **self.kw)
         if end:
             end.record()
 
@@ -804,7 +854,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
                     top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False,
                     top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None):
+                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -836,10 +886,15 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     repetition_penalty, frequency_penalty, presence_penalty: as in generate_batch — a sequence's adjusted values are formed from its own
     row of the token buffer wherever it is scheduled, so the ids do not depend on the schedule.
 
-    bias: as in generate_batch — a sequence's proposals are matched against its own row of the token buffer wherever it is scheduled."""
+    bias: as in generate_batch — a sequence's proposals are matched against its own row of the token buffer wherever it is scheduled.
+
+    automaton: as in generate_batch — a sequence's state is its own entry of the state buffer wherever it is scheduled, and a sequence
+    that is prefilled into a row another one held begins in its own start state, with no reset launch (return_state's automaton_state
+    has one entry per prompt)."""
     from .schedule import StreamScheduler
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     bias = _check_bias(bias, speculate)
+    automaton = _check_automaton(automaton, speculate)
     top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
     K = _check_top_logprobs(model, top_logprobs, return_logprobs)
     ngram = _ngram.check_ngram(no_repeat_ngram)
@@ -859,6 +914,7 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
     dev = model.transformer.wte.weight.device
     bias = _compile_bias(model, bias, pen, max(lens) + max_new_tokens, dev)
+    aut = None if automaton is None else _automaton.as_set(automaton, N, model.config.padded_vocab_size, dev, eos_id)
     mask = _token_mask(model, token_mask, N, 1, dev)
     stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
     P = _shared_prefix(model, prompts, share_prefix, dev)
@@ -867,13 +923,13 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
     be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
                         dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p, pen=pen, bias=bias)
+                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p, pen=pen, bias=bias, aut=aut)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
         if end:
             end.record()
-    with _decode_settings(eng, be.logprobs, be.top, be.mask, ngram, be.start, stop, top_p, min_p, pen, bias):
+    with _decode_settings(eng, be.logprobs, be.top, be.mask, ngram, be.start, stop, top_p, min_p, pen, bias, be.aut):
         sched.run(be)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
@@ -904,6 +960,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
             st["logprobs"] = be.logprobs[:N]
         if K:
             st["top_ids"], st["top_logprobs"] = be.top[0][:N], be.top[1][:N]
+        if be.aut is not None:
+            st["automaton_state"] = be.aut.state[:N]
         res += (st,)
     return res if len(res) > 1 else out
 
@@ -913,14 +971,15 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
              top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, top_p: Optional[float] = None,
              min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-             presence_penalty: Optional[float] = None, bias=None):
+             presence_penalty: Optional[float] = None, bias=None, automaton=None):
     """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
     generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's.  repetition_penalty, frequency_penalty,
-    presence_penalty: generate_batch's.  bias: generate_batch's."""
+    presence_penalty: generate_batch's.  bias: generate_batch's.  automaton: generate_batch's, a set with the one start state."""
     _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
     _check_bias(bias, speculate)
+    _check_automaton(automaton, speculate)
     _nucleus.check_nucleus(top_p, min_p)
     _check_top_logprobs(model, top_logprobs, return_logprobs)
     T = idx.size(0)
@@ -930,7 +989,7 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
     res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
                          speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
                          no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias)
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

@@ -616,6 +616,23 @@ class _Engine:
         _lib.check(self.lib.dh_engine_set_bias(self.handle, C.byref(bias.c_struct()), start.data_ptr()))
         self._bias = (bias, start)
 
+    def set_automaton(self, automaton=None, start: Optional[torch.Tensor] = None) -> None:
+        """The automaton set (a dualhyp_amd.automaton.AutomatonSet on the engine's device, a start state per sequence of the decode calls;
+        include/dualhyp_hip.h, "Automaton constraints") for later decode / decode_rows calls; None turns it off
+        (dh_engine_set_automaton).  start: the int32 [n_seq] prompt lengths on the engine's device, the array the other history readers
+        take; it and the set, whose state buffer the steps write, are kept alive here while set.  The set's arrays are part of a
+        captured step's key.  While set, decode_spec and decode_beam refuse, and a decode call needs an eos_id."""
+        if automaton is None:
+            _lib.check(self.lib.dh_engine_set_automaton(self.handle, None, None))
+            self._automaton = None
+            return
+        if start is None:
+            raise ValueError("an automaton needs start, the int32 prompt lengths: a sequence is in its start state while it has generated nothing")
+        if not start.is_cuda or start.dtype != torch.int32 or not start.is_contiguous() or start.dim() != 1:
+            raise TypeError("set_automaton takes start as a contiguous 1-D int32 tensor of prompt lengths on the GPU")
+        _lib.check(self.lib.dh_engine_set_automaton(self.handle, C.byref(automaton.c_struct()), start.data_ptr()))
+        self._automaton = (automaton, start)
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"

@@ -67,7 +67,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     hypotheses of dualhyp_amd.beam_search_batch, 'logprobs': bool}: the prediction is the best hypothesis, every record gains
     'beams', one {'text', 'sum_logprob', 'avg_logprob', 'finished'} per hypothesis in rank order, and with 'logprobs' the best
     one's 'sum_logprob' and 'avg_logprob' as above.  A generate_fn with a true attribute `constrained` (--constrain: it decodes under
-    per-utterance token masks) marks every record with 'constrained': true.  A generate_fn with an attribute `no_repeat_ngram` = N > 0
+    per-utterance token masks or automata) marks every record with 'constrained': true, and one with an attribute `constrain_order` = K > 0
+    (--constrain chain) gives every record 'constrain_order': K as well.  A generate_fn with an attribute `no_repeat_ngram` = N > 0
     (--no_repeat_ngram) gives every record 'no_repeat_ngram': N and 'ngram_bans': the generated positions (of the ids it returned)
     whose pick had a non-empty ban set, counted on the host from those ids (dualhyp_amd.ngram.ban_positions).  A generate_fn with a
     true attribute `stop` (--stop / --stop_file: it decodes under a stop specification) gives every record 'finish_reason', "eos",
@@ -127,6 +128,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                         "ground_truth": examples[i]["ground_truth"].strip()}
             if getattr(generate_fn, "constrained", False):
                 preds[i]["constrained"] = True
+            if getattr(generate_fn, "constrain_order", 0):
+                preds[i]["constrain_order"] = int(generate_fn.constrain_order)
             if getattr(generate_fn, "no_repeat_ngram", 0):
                 from .ngram import ban_positions
                 preds[i]["no_repeat_ngram"] = int(generate_fn.no_repeat_ngram)
@@ -381,6 +384,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     how = getattr(args, "select", None) or "avg_logprob"
     constrain = getattr(args, "constrain", "off") == "prompt"
     extra = read_token_ids(args.constrain_extra) if constrain and getattr(args, "constrain_extra", None) else ()
+    # --constrain chain: every run of K generated tokens is a run of the utterance's own prompt; the default run passes no keyword at all
+    chain = int(getattr(args, "constrain_order", 2) or 2) if getattr(args, "constrain", "off") == "chain" else 0
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
     # --beam_history device: the beams' histories on the device; the default run passes no keyword at all
     hkw = dict(history="device") if getattr(args, "beam_history", "host") == "device" else {}
@@ -406,6 +411,10 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         dev = model.transformer.wte.weight.device
         # --constrain prompt: an utterance may emit the ids of its own prompt (its hypotheses and the template), the EOS and the extras
         mask = pack_mask(allowed_from_prompts(prompts, eos, extra), model.config.padded_vocab_size, dev) if constrain else None
+        akw = {}
+        if chain:          # built from the call's prompts: an automaton per utterance
+            from .automaton import from_prompts
+            akw["automaton"] = from_prompts([p.reshape(-1).tolist() for p in prompts], order=chain, eos_id=eos)
         if beams > 1:      # --decode_batch counts decode rows: W per utterance
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
@@ -415,18 +424,18 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
             cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
                                  prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, token_mask=mask,
-                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw)
+                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw, **akw)
             return {"samples": cands, "select": how, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                    max_rows=args.decode_batch, prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)),
                                    share_prefix=share, speculate=spec, return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask,
-                                   no_repeat_ngram=ngram, **samp, **skw, **pkw)
+                                   no_repeat_ngram=ngram, **samp, **skw, **pkw, **akw)
         else:
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
                                   return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram,
-                                  **samp, **skw, **pkw)
+                                  **samp, **skw, **pkw, **akw)
         if stop is not None:
             from .stop import finish_reasons
             gen.finish_reasons = finish_reasons(outs[-1]["done"])
@@ -437,7 +446,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             return [o.cpu() for o in outs[0]], [lp.cpu() for lp in outs[1]]
         return [o.cpu() for o in outs]
 
-    gen.constrained = constrain
+    gen.constrained = constrain or bool(chain)
+    gen.constrain_order = chain
     gen.no_repeat_ngram = ngram
     gen.stop = stop is not None
     gen.sampling = sampling
@@ -540,11 +550,16 @@ def build_parser():
                    help="with --num_samples N > 1: the candidate kept — the highest avg_logprob (the default) or sum_logprob, or mbr: "
                         "the candidate with the lowest word edit distance to the other N - 1, each standing in as a reference (minimum "
                         "Bayes risk; ties go to the higher avg_logprob)")
-    p.add_argument("--constrain", choices=("off", "prompt"), default="off",
+    p.add_argument("--constrain", choices=("off", "prompt", "chain"), default="off",
                    help="prompt: constrained decoding — an utterance may emit only token ids that occur in its own prompt (its n-best "
                         "hypotheses and the template), the EOS and the ids of --constrain_extra; the mask is applied inside the sampling "
-                        "kernels, under both schedules and with --num_beams; every record gains constrained: true.  Default off: the "
-                        "path it always was")
+                        "kernels, under both schedules and with --num_beams; every record gains constrained: true.  chain: every run of "
+                        "--constrain_order K generated tokens is a run of the utterance's own prompt — a per-utterance automaton built from "
+                        "the call's prompts and walked inside the sampling kernels, under both schedules and with --num_samples; every "
+                        "record gains constrained: true and constrain_order: K; not with --constrain_extra, --speculate or --num_beams.  "
+                        "Default off: the path it always was")
+    p.add_argument("--constrain_order", type=int, default=2, metavar="K",
+                   help="with --constrain chain: the window length K, 2 .. 4 (default 2)")
     p.add_argument("--constrain_extra", type=str, default=None, metavar="FILE",
                    help="with --constrain prompt: a file of token ids, one per line, allowed for every utterance")
     p.add_argument("--no_repeat_ngram", type=int, default=0, metavar="N",
@@ -661,6 +676,19 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             p.error(f"--stop_file {args.stop_file} with --num_beams {args.num_beams}: {BEAM_REFUSAL}")
     if args.constrain_extra and args.constrain == "off":
         p.error("--constrain_extra goes with --constrain prompt")
+    if args.constrain == "chain":
+        if not 2 <= args.constrain_order <= 4:
+            p.error(f"--constrain_order {args.constrain_order}: K is 2 .. 4")
+        if args.constrain_extra:
+            p.error("--constrain_extra goes with --constrain prompt: a chain automaton has no place for ids outside its prompt")
+        if args.speculate:          # generate_batch refuses it too; here nothing has been loaded yet
+            from .automaton import SPEC_REFUSAL as AUT_SPEC_REFUSAL
+            p.error(f"--speculate {args.speculate} does not go with --constrain chain: {AUT_SPEC_REFUSAL}")
+        if args.num_beams > 1:
+            from .automaton import BEAM_REFUSAL as AUT_BEAM_REFUSAL
+            p.error(f"--num_beams {args.num_beams} does not go with --constrain chain: {AUT_BEAM_REFUSAL}")
+    elif args.constrain_order != 2:
+        p.error("--constrain_order goes with --constrain chain")
     if not 0 <= args.top_logprobs <= 8:
         p.error(f"--top_logprobs {args.top_logprobs}: K is 0 (off) or 1..8")
     if args.top_logprobs:

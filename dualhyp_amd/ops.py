@@ -359,6 +359,20 @@ def _bias_arg(bias, pen, start: Optional[torch.Tensor], tok_ld: int, vocab: int,
     return ctypes.byref(spec.c_struct())
 
 
+def _automaton_arg(automaton, start: Optional[torch.Tensor], n_seq: int, vocab: int, device, eos_id, keep):
+    """The dh_automaton_spec pointer of a sampler call ("Automaton constraints" of the header), or None when there is none.  automaton: a
+    dualhyp_amd.automaton.AutomatonSet with a start state per sequence.  On, the call needs start and an eos_id."""
+    from .automaton import as_set
+    aset = as_set(automaton, n_seq, vocab, device, eos_id)
+    if aset is None:
+        return None
+    if start is None:
+        raise ValueError("an automaton needs start, the int32 prompt lengths: a sequence is in its start state while it has generated nothing")
+    import ctypes
+    keep.append(aset)
+    return ctypes.byref(aset.c_struct())
+
+
 def token_top_logprobs(logits: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(ids int32 [rows, k], lp float32 [rows, k]): the k most probable tokens of every raw bf16 row, by value descending, then by
     index ascending, with their log-probabilities — bit-equal to token_logprobs(logits, ids[:, j]) (dh_token_top_logprobs_bf16; the
@@ -466,11 +480,11 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, *, check_ids: bool =
 
 
 def _sample_tail(k: _Keep, rows: bool, logits: torch.Tensor, tokens: torch.Tensor, logprobs, top_logprobs, mask, no_repeat_ngram: int,
-                 start, stop, top_p, min_p, repetition_penalty, frequency_penalty, presence_penalty, bias):
+                 start, stop, top_p, min_p, repetition_penalty, frequency_penalty, presence_penalty, bias, automaton=None, eos_id=None):
     """The options of sample() (rows False) and sample_rows() (True), checked: (logits on the device, the suffix of the entry to call,
     its arguments behind `stream`).  The entries form one ladder, each taking the options of the one before and its own behind them
-    (_lib.SAMPLE_TAIL); the call goes to the narrowest one that takes every option it has on.  rows: start None is
-    limit - max_new_tokens, so neither stop sequences nor a ban need it."""
+    (_lib.SAMPLE_TAIL, and the _automaton entries behind its last piece); the call goes to the narrowest one that takes every option it
+    has on.  rows: start None is limit - max_new_tokens, so neither stop sequences nor a ban need it."""
     from .nucleus import check_nucleus
     top_p, min_p = check_nucleus(top_p, min_p)
     logits = _dev(logits, name="logits")
@@ -485,13 +499,14 @@ def _sample_tail(k: _Keep, rows: bool, logits: torch.Tensor, tokens: torch.Tenso
         raise ValueError("stop sequences need start, the int32 prompt lengths: a match never reaches back into the prompt")
     pen = _penalty_arg(repetition_penalty, frequency_penalty, presence_penalty, start, tok_ld, vocab, k)
     b_ptr = _bias_arg(bias, pen, start, tok_ld, vocab, logits.device, k)
-    if (st_ptr is not None or pen is not None or b_ptr is not None) and not no_repeat_ngram:
+    a_ptr = _automaton_arg(automaton, start, n_seq, vocab, logits.device, eos_id, k)
+    if (st_ptr is not None or pen is not None or b_ptr is not None or a_ptr is not None) and not no_repeat_ngram:
         ngram, s_ptr = 0, _start_arg(start, n_seq, logits.device, k)
     else:
-        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=rows)
-    tail = (_p(logprobs), top_n, _p(top_ids), _p(top_lp), m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr)
+        ngram, s_ptr = _ngram_arg(no_repeat_ngram, start, n_seq, vocab, logits.device, k, start_optional=rows and a_ptr is None)
+    tail = (_p(logprobs), top_n, _p(top_ids), _p(top_lp), m_ptr, m_ld, ngram, s_ptr, st_ptr, top_p, min_p, pen, b_ptr, a_ptr)
     # (suffix, the call has what the entry adds, the arguments the entry takes), widest first
-    for suffix, on, n in (("_bias", b_ptr is not None, 13), ("_penalty", pen is not None, 12), ("_nucleus", top_p < 1.0 or min_p > 0.0, 11),
+    for suffix, on, n in (("_automaton", a_ptr is not None, 14), ("_bias", b_ptr is not None, 13), ("_penalty", pen is not None, 12), ("_nucleus", top_p < 1.0 or min_p > 0.0, 11),
                           ("_stop", st_ptr is not None, 9), ("_ngram", ngram, 8), ("_mask", mask is not None, 6), ("_top", True, 4)):
         if on:
             return logits, suffix, tail[:n]
@@ -503,7 +518,7 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
            top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
            no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
            min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-           presence_penalty: Optional[float] = None, bias=None) -> None:
+           presence_penalty: Optional[float] = None, bias=None, automaton=None) -> None:
     """Append one token per sequence in place (tokens/length/done); see dh_sample_bf16.  logprobs (float32, the shape of
     tokens): the appended token's log-probability goes to the same place in it (dh_sample_bf16_ex).  top_logprobs (with logprobs:
     int32 ids and float32 values, the shape of tokens + (K,)): the K alternatives of the row the token was picked from go to the
@@ -522,10 +537,15 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor, don
     bias (a dualhyp_amd.bias.BiasSpec, or a list of (ids, boost) pairs; "Contextual biasing" of the header; it needs start): the pick is
     the same call's pick on a copy of the row in which every id an entry proposes behind tokens[u, start[u]:length[u]] holds
     bf16(y + boost), y its raw or penalised fp32 value; logits is not written, and the log-probabilities and alternatives stay the raw
-    row's.  None and an empty list are off (dh_sample_bf16_bias)."""
+    row's.  None and an empty list are off (dh_sample_bf16_bias).
+    automaton (a dualhyp_amd.automaton.AutomatonSet with a start state per sequence; "Automaton constraints" of the header; it needs start
+    and an eos_id): sequence u picks among the tokens on the edges of its state — its start state while it has generated nothing, else
+    automaton.state[u], which the call before left — under the mask as well, the EOS alone where that leaves nothing; the ban, the
+    penalties and the bias work on that row, and the pick moves automaton.state[u] along its edge.  Log-probabilities and alternatives
+    stay the raw row's.  None is off (dh_sample_bf16_automaton)."""
     k = _Keep()
     logits, suffix, tail = _sample_tail(k, False, logits, tokens, logprobs, top_logprobs, mask, no_repeat_ngram, start, stop, top_p, min_p,
-                                        repetition_penalty, frequency_penalty, presence_penalty, bias)
+                                        repetition_penalty, frequency_penalty, presence_penalty, bias, automaton, eos_id)
     n_seq, vocab = logits.shape
     assert tokens.size(0) == n_seq
     check(getattr(_lib.load(), "dh_sample_bf16" + suffix)(
@@ -539,17 +559,18 @@ def sample_rows(logits: torch.Tensor, tokens: torch.Tensor, length: torch.Tensor
                 top_logprobs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, mask: Optional[torch.Tensor] = None,
                 no_repeat_ngram: int = 0, start: Optional[torch.Tensor] = None, stop=None, top_p: Optional[float] = None,
                 min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                presence_penalty: Optional[float] = None, bias=None) -> None:
+                presence_penalty: Optional[float] = None, bias=None, automaton=None) -> None:
     """Append one token to sequence row_seq[r] from logits row r, in place; see dh_sample_rows_bf16.  logprobs, top_logprobs: as
     in sample().  mask: as in sample(), one row per SEQUENCE — logits row r is picked under mask row row_seq[r]
     (dh_sample_rows_bf16_mask).  no_repeat_ngram, start: as in sample(), one entry of start per SEQUENCE; start None is
     limit - max_new_tokens (dh_sample_rows_bf16_ngram).  stop: as in sample(); start None is limit - max_new_tokens here too
     (dh_sample_rows_bf16_stop).  top_p, min_p: as in sample() (dh_sample_rows_bf16_nucleus).  repetition_penalty, frequency_penalty,
     presence_penalty: as in sample(), start included (dh_sample_rows_bf16_penalty).  bias: as in sample(), start included
-    (dh_sample_rows_bf16_bias)."""
+    (dh_sample_rows_bf16_bias).  automaton: as in sample(), one start state and one state entry per SEQUENCE, and start given
+    (dh_sample_rows_bf16_automaton)."""
     k = _Keep()
     logits, suffix, tail = _sample_tail(k, True, logits, tokens, logprobs, top_logprobs, mask, no_repeat_ngram, start, stop, top_p, min_p,
-                                        repetition_penalty, frequency_penalty, presence_penalty, bias)
+                                        repetition_penalty, frequency_penalty, presence_penalty, bias, automaton, eos_id)
     n_rows, vocab = logits.shape
     n_seq = tokens.size(0)
     assert row_seq.numel() == n_rows

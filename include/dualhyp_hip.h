@@ -35,7 +35,8 @@ typedef uint16_t dh_bf16;
  * dh_engine_set_stop (stop conditions); dh_sample_bf16_nucleus, dh_sample_rows_bf16_nucleus and dh_engine_set_nucleus (nucleus
  * and min-p sampling); dh_engine_fork_slots (sampled candidates); dh_sample_bf16_penalty, dh_sample_rows_bf16_penalty and
  * dh_engine_set_penalties (penalties); dh_sample_bf16_bias, dh_sample_rows_bf16_bias and dh_engine_set_bias (contextual biasing);
- * dh_beam_select_bf16_hist and dh_engine_set_beam_history (beam histories). */
+ * dh_beam_select_bf16_hist and dh_engine_set_beam_history (beam histories); dh_sample_bf16_automaton, dh_sample_rows_bf16_automaton and
+ * dh_engine_set_automaton (automaton constraints). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -777,6 +778,64 @@ int dh_sample_rows_bf16_bias(const dh_bf16* logits, int vocab, int64_t* tokens, 
                              const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
                              float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias);
 
+/* Automaton constraints (the general form of a token mask: the allowed set changes with every token): one deterministic finite automaton
+ * per sequence, walked on the device inside the sampling kernels.  ONE definition for every entry below.
+ * The automaton set (dh_automaton_spec) of a call has S states, numbered globally over all of the call's automata, in CSR form:
+ *   edge_off int32 [S + 1], edge_tok int32 [E], edge_dst int32 [E], init int32 [n_seq] (each sequence's start state) and state int32
+ *   [n_seq], which lives on the device, is written by the kernels and is never initialised by the caller.  Inside a state the edge tokens
+ *   are strictly ascending, so the automaton is deterministic and an edge is unique per (state, token); edge_dst lies in [0, S).  "This
+ *   state may end the text" is an ordinary edge whose token is the call's eos_id; its destination is ignored.  Null is off: the call it
+ *   always was.
+ * State at a pick: m = length[u] - start[u] is the number of tokens sequence u has generated (start: the prompt lengths the other history
+ *   readers take); q = m == 0 ? init[u] : state[u].  So the prefill's first pick and a refilled row need no reset launch.
+ * Allowed row:
+ *   1. R0 = the bits edge_tok[e], e in [edge_off[q], edge_off[q + 1]).
+ *   2. With a token mask, R0 is ANDed with the sequence's mask row.  Bits at or behind vocab are clear.
+ *   3. If R0 holds no bit, R0 = {eos_id} alone: a dead end, the sequence ends.  The mask is ignored here, so a pick is never taken from an
+ *      empty set.
+ *   4. no_repeat_ngram then bans on R0 by its own rule, its fallback included: a ban that would empty the row is ignored.
+ *   5. The pick is, bit for bit, the masked pick ("Token masks") under that row: the arg-max, the threshold / nucleus / min-p passes, the
+ *      CDF walk, and penalties and a bias through their override path.
+ *   6. Log-probabilities and alternatives stay the raw row's.
+ * Transition: for pick c, state[u] = edge_dst[e] of the edge of q with edge_tok[e] == c; without one (the dead-end EOS) state[u] = q.  A
+ *   sequence that is done is left alone.  The sequence's block builds the row with integer LDS atomics, exact in any order, and one thread
+ *   stores the new state behind the pick; the launch is the one the call made anyway.
+ * Refused before any launch, with the value in the message: eos_id < 0 or >= vocab, vocab above 131072 (the LDS row's bound, as for the
+ *   ban), a null `start`, offsets that are not monotone from 0 to E, a token outside [0, vocab) or not strictly ascending inside its state,
+ *   an edge_dst or an init outside [0, S), and n_seq other than the call's sequences.  Verify steps (a position's state would depend on
+ *   picks of the same launch) and beam steps (a re-parented beam would need its parent's state) take no automaton: dh_engine_decode_spec
+ *   and dh_engine_decode_beam refuse while one is set. */
+typedef struct dh_automaton_spec {
+    const int32_t* edge_off;    /* device, [n_states + 1] */
+    const int32_t* edge_tok;    /* device, [n_edges] */
+    const int32_t* edge_dst;    /* device, [n_edges] */
+    const int32_t* init;        /* device, [n_seq] */
+    int32_t* state;             /* device, [n_seq]: the kernels' own */
+    const int32_t* h_edge_off;  /* host copies of the first four: what the checks read */
+    const int32_t* h_edge_tok;
+    const int32_t* h_edge_dst;
+    const int32_t* h_init;
+    int n_states;
+    int n_edges;
+    int n_seq;
+} dh_automaton_spec;
+
+/* dh_sample_bf16_bias / dh_sample_rows_bf16_bias with the automaton set; everything else stays nullable / 0 / 1 / 0, and `automaton` null
+ * makes each the entry it extends.  `start` and an eos_id in [0, vocab) are needed when one is given, by both. */
+int dh_sample_bf16_automaton(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                             int32_t* done, int n_seq, float temperature, int top_k, int64_t eos_id,
+                             uint64_t seed, int step, void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                             const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                             float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias,
+                             const dh_automaton_spec* automaton);
+int dh_sample_rows_bf16_automaton(const dh_bf16* logits, int vocab, int64_t* tokens, int tok_ld, int32_t* length,
+                                  int32_t* done, const int32_t* limit, const int32_t* row_seq, int n_rows, int n_seq,
+                                  int max_new_tokens, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                                  void* stream, float* logprobs, int top_logprobs, int32_t* top_ids, float* top_lp,
+                                  const uint32_t* mask, int mask_ld, int ngram, const int32_t* start, const dh_stop_spec* stop,
+                                  float top_p, float min_p, const dh_penalty_args* penalties, const dh_bias_spec* bias,
+                                  const dh_automaton_spec* automaton);
+
 /* ------------------------------------------------------------------ fp8 serving path (csrc/fp8.hip)
  * W8A8 with OCP e4m3fn: q = fp8_rne(v * (448 / amax)), scale = amax / 448 per row (amax >= 1e-12, fp32 arithmetic);
  * weights are quantised per output channel ahead of time (dualhyp_amd.quant, after merge_lora_weights), activations
@@ -1151,6 +1210,13 @@ int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* penalties, cons
  * with penalties set as well, so does a decode call whose tok_ld plus the entries' ids pass DH_MAX_PENALTY_HISTORY.  Refused like
  * dh_sample_bf16_bias. */
 int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const int32_t* start);
+/* The automaton set (see "Automaton constraints" above; null clears it, the default) for later dh_engine_decode and dh_engine_decode_rows
+ * calls.  The spec's device arrays, `state` among them, and `start` ([n_seq] int32 on the device, the array the other history readers
+ * take) are the caller's to keep alive while set; the host copies are read here only.  The pointers, the counts and `start` are part of
+ * the captured step's key: with none set a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec and
+ * dh_engine_decode_beam refuse, and a decode call refuses an eos_id outside [0, vocab) or a sequence count other than the spec's n_seq.
+ * Refused like dh_sample_bf16_automaton. */
+int dh_engine_set_automaton(dh_engine* e, const dh_automaton_spec* automaton, const int32_t* start);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);
