@@ -153,12 +153,17 @@ SIGNATURES = {
     "dh_linear_fp8_f32": (I, [P, P, P, P, P, I, I, I, P]),
     "dh_linear_mxfp4_ex": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P]),
     "dh_linear_mxfp4_f32": (I, [P, P, P, P, P, I, I, I, P]),
+    "dh_quant_rows_mxfp6": (I, [P, P, P, I, I, P]),
+    "dh_rmsnorm_quant_mxfp6": (I, [P, P, P, P, P, I, I, F, P, P]),
+    "dh_linear_mxfp4a6_ex": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P]),
+    "dh_linear_mxfp4a6_f32": (I, [P, P, P, P, P, I, I, I, P]),
     "dh_qkv_rope_cache_kv8": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "dh_attn_decode_kv8": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "dh_kv8_expand": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "dh_engine_create": (I, [C.POINTER(ModelDesc), I, I, I, C.POINTER(P)]),
     "dh_engine_create_ex": (I, [C.POINTER(ModelDesc), I, I, I, I, C.POINTER(P)]),
     "dh_engine_create_q": (I, [C.POINTER(ModelDesc), I, I, I, I, I, C.POINTER(P)]),
+    "dh_engine_create_qa": (I, [C.POINTER(ModelDesc), I, I, I, I, I, I, C.POINTER(P)]),
     "dh_engine_destroy": (None, [P]),
     "dh_engine_device_bytes": (I64, [P]),
     "dh_im2col3_bf16": (I, [P, P, I, I, I, I, I, P]),

@@ -66,6 +66,9 @@ struct dh_engine {
     bool mx4 = false;                                   // fp8 engine whose block weights are MXFP4 (csrc/mxfp4.hip; lm_head stays e4m3)
     uint8_t* xq = nullptr;                              // fp8 mode: quantised activations [max_tokens, max(d, I)]
     float* xscale = nullptr;                            // fp8 mode: their per-token scales [max_tokens]
+    bool a6 = false;                                    // MXFP4 engine whose block activations are MXFP6 (csrc/mxfp6.hip; ln_f and lm_head stay e4m3)
+    uint8_t* xq6 = nullptr;                             // a6: e2m3 codes of max_tokens rounded up to 16 rows x max(d, I), in fragment order
+    uint8_t* xs6 = nullptr;                             // a6: their E8M0 bytes
     int32_t* h_stage = nullptr;                         // pinned staging for the metadata, carved by stage() below
     size_t cache_layer_elems = 0;
     int64_t dev_bytes = 0;
@@ -458,12 +461,25 @@ inline int fp8_kernel(bool decode, int rows) { return decode && rows <= 128 ? 2 
 int linear_fp8(dh_engine* e, const bf16_t* w, const float* ws, bf16_t* y, int M, int N, int K, int epi, const bf16_t* w2,
                const float* w2s, const bf16_t* resid, hipStream_t s, bool timed) {
     TimeScope t(e, gemm_class(e), s, timed);
+    if (e->a6)    // MXFP6 activations beside the MXFP4 block weights: the rows are in e->xq6 / e->xs6; same phase rule
+        return dh_linear_mxfp4a6_ex(e->xq6, e->xs6, reinterpret_cast<const uint8_t*>(w), reinterpret_cast<const uint8_t*>(ws), y, M, N, K,
+                                    epi, reinterpret_cast<const uint8_t*>(w2), reinterpret_cast<const uint8_t*>(w2s), nullptr, nullptr,
+                                    resid, fp8_kernel(e->phase_decode, M), s);
     if (e->mx4)   // the block linears of an MXFP4 engine: w addresses nibbles, ws E8M0 bytes; same phase rule
         return dh_linear_mxfp4_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), reinterpret_cast<const uint8_t*>(ws), y, M, N, K,
                                   epi, reinterpret_cast<const uint8_t*>(w2), reinterpret_cast<const uint8_t*>(w2s), nullptr, nullptr,
                                   resid, fp8_kernel(e->phase_decode, M), s);
     return dh_linear_fp8_ex(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(w), ws, y, M, N, K, epi,
                             reinterpret_cast<const uint8_t*>(w2), w2s, nullptr, nullptr, resid, fp8_kernel(e->phase_decode, M), s);
+}
+
+// the quantisation points of a block: e4m3 rows + token scales into e->xq / e->xscale, or MXFP6 blocks into e->xq6 / e->xs6
+int quant_act(dh_engine* e, const bf16_t* x, int rows, int K, hipStream_t s) {
+    return e->a6 ? dh_quant_rows_mxfp6(x, e->xq6, e->xs6, rows, K, s) : dh_quant_rows_fp8(x, e->xq, e->xscale, rows, K, s);
+}
+int norm_quant_act(dh_engine* e, const bf16_t* x, const bf16_t* w, int rows, int d, const uint8_t* rt, hipStream_t s) {
+    return e->a6 ? dh_rmsnorm_quant_mxfp6(x, w, nullptr, e->xq6, e->xs6, rows, d, e->d.norm_eps, rt, s)
+                 : dh_rmsnorm_quant_fp8(x, w, nullptr, e->xq, e->xscale, rows, d, e->d.norm_eps, rt, s);
 }
 
 // ---- the pieces of a layer ---------------------------------------------------------------------------------------------------
@@ -542,11 +558,11 @@ int post_attention_fp8(dh_engine* e, const dh_layer_weights& W, int rows, const 
     const dh_model_desc& D = e->d;
     const int d = D.n_embd, I = D.intermediate;
     int rc;
-    if ((rc = dh_quant_rows_fp8(att, e->xq, e->xscale, rows, d, s))) return rc;
+    if ((rc = quant_act(e, att, rows, d, s))) return rc;
     if ((rc = linear_fp8(e, W.proj_w, W.proj_ws, x, rows, d, d, DH_EPI_PLAIN, nullptr, nullptr, x, s, timed))) return rc;
-    if ((rc = dh_rmsnorm_quant_fp8(x, W.norm_2, nullptr, e->xq, e->xscale, rows, d, D.norm_eps, rt, s))) return rc;
+    if ((rc = norm_quant_act(e, x, W.norm_2, rows, d, rt, s))) return rc;
     if ((rc = linear_fp8(e, W.fc_1, W.fc_1_ws, act, rows, I, d, DH_EPI_SWIGLU, W.fc_2, W.fc_2_ws, nullptr, s, timed))) return rc;
-    if ((rc = dh_quant_rows_fp8(act, e->xq, e->xscale, rows, I, s))) return rc;
+    if ((rc = quant_act(e, act, rows, I, s))) return rc;
     return linear_fp8(e, W.mlp_proj, W.mlp_proj_ws, x, rows, d, I, DH_EPI_PLAIN, nullptr, nullptr, x, s, timed);
 }
 
@@ -615,14 +631,16 @@ int run_layers_fp8(dh_engine* e, const int64_t* ids, int n_tok, int n_seq, int m
         const dh_layer_weights& W = e->layers[l];
         bf16_t* kc = e->kc + (size_t)l * e->cache_layer_elems;
         bf16_t* vtc = e->vtc + (size_t)l * e->cache_layer_elems;
-        if ((rc = dh_rmsnorm_quant_fp8(e->x, W.norm_1, nullptr, e->xq, e->xscale, n_tok, d, D.norm_eps, rt, s))) return rc;
+        if ((rc = norm_quant_act(e, e->x, W.norm_1, n_tok, d, rt, s))) return rc;
         if (!e->kv8 && decode && n_tok <= 128) {     // every streaming-class step over a bf16 cache (fp8_kernel above): one family, no 32-row boundary
             // one launch for rope + cache append + split-KV attention + combine (decode_fused.hip): the QKV product
             // is handed over as its single fp32 "partial" (values already rounded to bf16), no LoRA (merged)
             const SeqMeta m = seq_meta(e);
             {
                 TimeScope t(e, 1, s);
-                if (e->mx4) rc = dh_linear_mxfp4_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w),
+                if (e->a6) rc = dh_linear_mxfp4a6_f32(e->xq6, e->xs6, reinterpret_cast<const uint8_t*>(W.attn_w),
+                                                      reinterpret_cast<const uint8_t*>(W.attn_ws), e->part32, n_tok, e->qkv_dim, d, s);
+                else if (e->mx4) rc = dh_linear_mxfp4_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w),
                                                      reinterpret_cast<const uint8_t*>(W.attn_ws), e->part32, n_tok, e->qkv_dim, d, s);
                 else rc = dh_linear_fp8_f32(e->xq, e->xscale, reinterpret_cast<const uint8_t*>(W.attn_w), W.attn_ws, e->part32,
                                             n_tok, e->qkv_dim, d, s);
@@ -784,7 +802,7 @@ int alloc_row_ws(dh_engine* e, int rows) {
     return 0;
 }
 
-int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype) {
+int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype, int act_dtype) {
     e->d = *desc;
     e->layers.assign(desc->h_layers, desc->h_layers + desc->n_layer);
     e->d.h_layers = nullptr;
@@ -802,6 +820,9 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
     }
     e->mx4 = weight_dtype == 1;
     DH_CHECK(!e->mx4 || e->fp8, "dh_engine_create_q: MXFP4 weights (weight_dtype 1) need the block-scale pointers (attn_ws != NULL)");
+    e->a6 = act_dtype == 1;
+    DH_CHECK(!e->a6 || e->mx4, "dh_engine_create_qa: MXFP6 activations (act_dtype 1) need MXFP4 weights (weight_dtype 1): beside an e4m3 "
+                               "weight the e2m3 activation runs the MFMA at the fp8 rate, so the pair is refused");
     e->kv8 = kv_dtype == 1;
     DH_CHECK(!e->kv8 || e->fp8, "dh_engine_create_ex: an fp8 KV cache (kv_dtype 1) needs an fp8 engine (channel scales, attn_ws != NULL)");
     e->cache_layer_elems = (size_t)max_batch * G * s_max * hs;
@@ -855,6 +876,12 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
         rc |= dmalloc(e, &e->xq, T * (size_t)(desc->intermediate > d ? desc->intermediate : d));
         rc |= dmalloc(e, &e->xscale, T);
     }
+    // whole groups of 16 rows: 3/4 byte per element and one scale byte per 32
+    const size_t a6_elems = e->a6 ? (T + 15) / 16 * 16 * (size_t)(desc->intermediate > d ? desc->intermediate : d) : 0;
+    if (e->a6) {
+        rc |= dmalloc(e, &e->xq6, a6_elems / 4 * 3);
+        rc |= dmalloc(e, &e->xs6, a6_elems / 32);
+    }
     rc |= dmalloc(e, &e->row_tail, T);
     rc |= dmalloc(e, &e->last_tail, (size_t)max_batch);
     const int64_t wb = dh_attn_decode_work_bytes(max_batch, H, hs, s_max);
@@ -868,6 +895,10 @@ int engine_init(dh_engine* e, const dh_model_desc* desc, int max_batch, int s_ma
         DH_HIP(hipMemset(e->v8, 0, e->cache_layer_elems * desc->n_layer));
         DH_HIP(hipMemset(e->ke, 0, e->exp_layer_elems * desc->n_layer));
         DH_HIP(hipMemset(e->ve, 0, e->exp_layer_elems * desc->n_layer));
+    }
+    if (e->a6) {   // the rows past a call's last one in its last group of 16 are read (never into a stored output) and never written
+        DH_HIP(hipMemset(e->xq6, 0, a6_elems / 4 * 3));
+        DH_HIP(hipMemset(e->xs6, 0, a6_elems / 32));
     }
     DH_HIP(hipMemset(e->step_dev, 0, sizeof(int32_t)));
     {
@@ -1118,7 +1149,13 @@ extern "C" int dh_engine_create_ex(const dh_model_desc* desc, int max_batch, int
 
 extern "C" int dh_engine_create_q(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype,
                                   dh_engine** out) {
+    return dh_engine_create_qa(desc, max_batch, s_max, max_tokens, kv_dtype, weight_dtype, 0, out);
+}
+
+extern "C" int dh_engine_create_qa(const dh_model_desc* desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype,
+                                   int act_dtype, dh_engine** out) {
     DH_CHECK(desc && out, "dh_engine_create: null argument");
+    DH_CHECK(act_dtype == 0 || act_dtype == 1, "dh_engine_create_qa: act_dtype %d is neither 0 (e4m3 per token) nor 1 (MXFP6)", act_dtype);
     DH_CHECK(weight_dtype == 0 || weight_dtype == 1, "dh_engine_create_q: weight_dtype %d is neither 0 (as described) nor 1 (MXFP4)", weight_dtype);
     DH_CHECK(kv_dtype == 0 || kv_dtype == 1, "dh_engine_create_ex: kv_dtype %d is neither 0 (bf16) nor 1 (fp8)", kv_dtype);
     DH_CHECK(desc->head_size == 64 || desc->head_size == 96 || desc->head_size == 128, "dh_engine_create: head_size %d unsupported", desc->head_size);
@@ -1129,7 +1166,7 @@ extern "C" int dh_engine_create_q(const dh_model_desc* desc, int max_batch, int 
     DH_CHECK(max_batch > 0 && max_tokens >= max_batch, "dh_engine_create: bad batch/token capacity");
     DH_CHECK(desc->rope_cos && desc->rope_sin && desc->wte && desc->ln_f && desc->lm_head && desc->h_layers, "dh_engine_create: null weight pointer");
     dh_engine* e = new dh_engine();
-    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens, kv_dtype, weight_dtype);
+    const int rc = engine_init(e, desc, max_batch, s_max, max_tokens, kv_dtype, weight_dtype, act_dtype);
     if (rc) { dh_engine_destroy(e); return rc; }   // one cleanup path: nothing allocated so far leaks
     {
         std::lock_guard<std::mutex> lock(g_engines_mu);
@@ -1149,7 +1186,7 @@ extern "C" void dh_engine_destroy(dh_engine* e) {
     void* ptrs[] = {e->kc, e->vtc, e->k8, e->v8, e->ke, e->ve, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
                     e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->copy_dst, e->cache_tab, e->dec_ids, e->dec_work,
                     e->beam_scratch, e->beam_cand_ids, e->beam_cand_lp,
-                    e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale};
+                    e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale, e->xq6, e->xs6};
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (e->h_stage) hipHostFree(e->h_stage);

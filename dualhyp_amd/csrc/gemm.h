@@ -76,6 +76,17 @@ enum DhGemmRoute : int {
     DH_ROUTE_MX4_T128_S2,      //   2 stages
     DH_ROUTE_COUNT
 };
+// The routes of the MXFP6-activation GEMMs, appended behind the table above (whose numbering tests/gemm_exact_reference.py mirrors entry by
+// entry): the same record, bits DH_ROUTE_COUNT and up.  Their cases are in tests/test_hip_mxfp6.py.
+enum DhGemmRouteA6 : int {
+    DH_ROUTE_MX4A6_STREAM_NG1 = DH_ROUTE_COUNT,   // mxfp6.hip: MXFP4 weights x MXFP6 activations, streaming kernel, 1 / 2 / 4 row groups
+    DH_ROUTE_MX4A6_STREAM_NG2,
+    DH_ROUTE_MX4A6_STREAM_NG4,
+    DH_ROUTE_MX4A6_T128_S4,                       //   tiled kernel, 4 stages
+    DH_ROUTE_MX4A6_T128_S2,                       //   2 stages
+    DH_ROUTE_A6_END
+};
+static_assert(DH_ROUTE_A6_END <= 64, "the route record is one 64-bit mask");
 void dh_gemm_route(int route);      // gemm.hip
 
 // M <= 32: one pass over W straight from HBM to registers (gemm_skinny.hip)

@@ -301,6 +301,11 @@ class _Engine:
             raise ValueError(f"kv_cache_dtype is 'bf16' or 'fp8', got {self.kv_cache_dtype!r}")
         if self.kv_cache_dtype == "fp8" and not fp8:
             raise _lib.DualHypHipError("an fp8 KV cache needs an fp8 model: quantize_model_fp8(model, kv_cache='fp8')")
+        self.activation_format = getattr(model, "activation_format", "fp8")    # "mxfp6": quantize_model_mxfp4(model, activations="mxfp6")
+        if self.activation_format not in ("fp8", "mxfp6"):
+            raise ValueError(f"activation_format is 'fp8' or 'mxfp6', got {self.activation_format!r}")
+        if self.activation_format == "mxfp6" and not mx4:
+            raise _lib.DualHypHipError("MXFP6 activations need an mxfp4 model: quantize_model_mxfp4(model, activations='mxfp6')")
 
         def wptr(lin) -> Optional[int]:
             """bf16 weight, or the e4m3 bytes of a quantised layer (dualhyp_amd.quant)"""
@@ -357,8 +362,8 @@ class _Engine:
         self.device = model.transformer.wte.weight.device
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(lib.dh_engine_create_q(C.byref(desc), max_batch, s_max, max_tokens, int(self.kv_cache_dtype == "fp8"),
-                                              int(mx4), C.byref(handle)))
+            _lib.check(lib.dh_engine_create_qa(C.byref(desc), max_batch, s_max, max_tokens, int(self.kv_cache_dtype == "fp8"),
+                                               int(mx4), int(self.activation_format == "mxfp6"), C.byref(handle)))
         self.handle = handle
         self.lib = lib
         self.signature = model._param_signature()
@@ -715,6 +720,7 @@ class GPT(nn.Module):
         # rounds twice in its scalar tail loop and dh_rmsnorm_bf16 can reproduce that per row.
         self.cpu_rsqrt_vec_width = 0
         self.kv_cache_dtype = "bf16"                      # "fp8": quantize_model_fp8(model, kv_cache="fp8")
+        self.activation_format = "fp8"                    # "mxfp6": quantize_model_mxfp4(model, activations="mxfp6"); read by quantised models only
         self._engine: Optional[_Engine] = None
         self._capacity = dict(max_batch=1, s_max=0, max_tokens=0)
         self._cache_len: List[int] = []                   # tokens currently valid per cache slot
@@ -795,7 +801,8 @@ class GPT(nn.Module):
                 s_need = max(cap["s_max"], need_pos, self.max_seq_length)
                 self.set_capacity(mb, s_need, max(cap["max_tokens"], need_tokens, mb * min(s_need, 1024)))
         if self._engine is not None and (self._engine.signature != self._param_signature()
-                                         or self._engine.kv_cache_dtype != getattr(self, "kv_cache_dtype", "bf16")):
+                                         or self._engine.kv_cache_dtype != getattr(self, "kv_cache_dtype", "bf16")
+                                         or self._engine.activation_format != getattr(self, "activation_format", "fp8")):
             self._drop_engine()
         if self._engine is None:
             w = self.transformer.wte.weight

@@ -140,6 +140,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["sampling"] = dict(generate_fn.sampling)
             if getattr(generate_fn, "penalties", None):
                 preds[i]["penalties"] = dict(generate_fn.penalties)
+            if getattr(generate_fn, "activations", "fp8") != "fp8":
+                preds[i]["activations"] = str(generate_fn.activations)
             if getattr(generate_fn, "bias", None):
                 from .bias import bias_hits
                 preds[i]["bias"] = dict(generate_fn.bias)
@@ -314,7 +316,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         quantize_model_fp8(model, kv_cache=getattr(args, "kv_cache", "bf16"))
     elif getattr(args, "quantize", "none") == "mxfp4":
         from .quant import quantize_model_mxfp4
-        quantize_model_mxfp4(model, kv_cache=getattr(args, "kv_cache", "bf16"))
+        quantize_model_mxfp4(model, kv_cache=getattr(args, "kv_cache", "bf16"), activations=getattr(args, "activations", "fp8"))
     fmt = args.prompts_format
     if args.dual_hypotheses and "Dual" not in fmt and fmt != "RelPrompt":
         print("Warning: dual hypotheses is enabled, but prompts format is not Dual.")
@@ -452,6 +454,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.stop = stop is not None
     gen.sampling = sampling
     gen.penalties = penalties
+    gen.activations = getattr(model, "activation_format", "fp8")
     gen.bias, gen.bias_entries = bias_rec, bias_entries
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams // n_samples), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
@@ -521,6 +524,11 @@ def build_parser():
     p.add_argument("--kv_cache", choices=("bf16", "fp8"), default="bf16",
                    help="fp8 (with --quantize fp8 or mxfp4): cached K and V vectors are stored as e4m3 bytes with one power-of-two exponent each, "
                         "half the cache bytes per token; the predictions are those of attention over the rounded cache")
+    p.add_argument("--activations", choices=("fp8", "mxfp6"), default="fp8",
+                   help="mxfp6 (with --quantize mxfp4 only): the activations of every block are quantised to OCP MXFP6 (blocks of 32 e2m3 "
+                        "elements with one power-of-two scale byte, no per-token scale) instead of e4m3 rows, the operand pair the MFMA runs at "
+                        "twice the fp8 rate; the final norm and lm_head stay e4m3; every record gains activations: \"mxfp6\".  Default fp8: "
+                        "the path it always was")
     p.add_argument("--logprobs", action="store_true",
                    help="every record of the predictions file gains sum_logprob and avg_logprob: the model's log-probability of the tokens "
                         "it generated (the EOS included; temperature 1, no top-k crop), computed inside the decode steps; the predictions "
@@ -635,6 +643,8 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     fp8_path = args.quantize in ("fp8", "mxfp4")             # mxfp4 is a weight format of the fp8 serving path: one engine, one set of refusals
     if args.kv_cache == "fp8" and not fp8_path:
         p.error("--kv_cache fp8 goes with --quantize fp8 (or mxfp4): the fp8 KV cache belongs to the fp8 serving path")
+    if args.activations != "fp8" and args.quantize != "mxfp4":
+        p.error(f"--activations {args.activations} goes with --quantize mxfp4: beside e4m3 or bf16 weights the narrow activations buy no MFMA rate")
     if args.speculate and fp8_path:                           # speculate.check_arguments refuses it too
         p.error(f"--speculate {args.speculate} does not go with --quantize {args.quantize}: an fp8 engine has no verify step")
     if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet

@@ -658,6 +658,65 @@ def linear_mxfp4(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_sc
     return y
 
 
+# ------------------------------------------------------------------------------------------ MXFP6 activations
+def _mxfp6_buffers(rows: int, K: int, device, fill: Optional[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    G = (rows + 15) // 16
+    mk = torch.empty if fill is None else (lambda *a, **kw: torch.full(*a, fill_value=fill, **kw))
+    return (mk((G, K // 128, 3, 64, 8), dtype=torch.uint8, device=device), mk((G, K // 128, 64), dtype=torch.uint8, device=device))
+
+
+def quant_rows_mxfp6(x: torch.Tensor, fill: Optional[int] = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(uint8 codes [ceil(rows / 16), K / 128, 3, 64, 8], uint8 E8M0 bytes [ceil(rows / 16), K / 128, 64]) of bf16 rows in the layout
+    of include/dualhyp_hip.h "MXFP6 activations"; dh_quant_rows_mxfp6.  fill: what the buffers hold before the call (the kernel
+    never writes the rows past `rows` of the last group); None leaves them uninitialised."""
+    x = _dev(x, name="x")
+    K = x.size(-1)
+    rows = x.numel() // K
+    q, s = _mxfp6_buffers(rows, K, x.device, fill)
+    check(_lib.load().dh_quant_rows_mxfp6(_p(x), _p(q), _p(s), rows, K, _stream()))
+    return q, s
+
+
+def rmsnorm_quant_mxfp6(x: torch.Tensor, w: torch.Tensor, eps: float, row_tail: Optional[torch.Tensor] = None, fill: Optional[int] = 0):
+    """(bf16 RMSNorm rows, their MXFP6 codes, their E8M0 bytes); dh_rmsnorm_quant_mxfp6."""
+    k = _Keep()
+    x = _dev(x, name="x")
+    d = x.size(-1)
+    rows = x.numel() // d
+    xn = torch.empty_like(x)
+    q, s = _mxfp6_buffers(rows, d, x.device, fill)
+    check(_lib.load().dh_rmsnorm_quant_mxfp6(_p(x), k(w, name="weight"), _p(xn), _p(q), _p(s), rows, d, float(eps),
+                                             k(row_tail, torch.uint8, "row_tail"), _stream()))
+    return xn, q, s
+
+
+def linear_mxfp4a6(xq: torch.Tensor, x_scale: torch.Tensor, M: int, wq: torch.Tensor, w_scale: torch.Tensor, *, epilogue: int = EPI_PLAIN,
+                   w2q: Optional[torch.Tensor] = None, w2_scale: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                   bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, kernel: int = 0,
+                   out32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_mxfp4 with MXFP6 activations: bf16 [M, N] = epilogue(dequant(x) . dequant(W)^T), xq / x_scale as quant_rows_mxfp6 or
+    dualhyp_amd.quant.pack_mxfp6 lay them out (M is passed: the buffers hold whole groups of 16 rows); dh_linear_mxfp4a6_ex, or
+    dh_linear_mxfp4a6_f32 with out32."""
+    k = _Keep()
+    K = wq.size(1) * 128
+    assert wq.dim() == 4 and wq.shape[2:] == (64, 16) and w_scale.shape == wq.shape[:3]
+    assert xq.dim() == 5 and xq.shape[1:] == (K // 128, 3, 64, 8) and x_scale.shape == xq.shape[:2] + (64,) and xq.size(0) == (M + 15) // 16
+    assert xq.dtype == torch.uint8 and x_scale.dtype == torch.uint8 and wq.dtype == torch.uint8 and w_scale.dtype == torch.uint8
+    N = wq.size(0) * 16
+    if out32:
+        assert epilogue == EPI_PLAIN and resid is None and kernel in (0, 2)
+        y = _out(out, (M, N), torch.float32, xq.device)
+        check(_lib.load().dh_linear_mxfp4a6_f32(k(xq, torch.uint8, "xq"), k(x_scale, torch.uint8, "x_scale"), k(wq, torch.uint8, "wq"),
+                                                k(w_scale, torch.uint8, "w_scale"), _p(y), M, N, K, _stream()))
+        return y
+    y = _out(out, (M, N), torch.bfloat16, xq.device)
+    check(_lib.load().dh_linear_mxfp4a6_ex(k(xq, torch.uint8, "xq"), k(x_scale, torch.uint8, "x_scale"), k(wq, torch.uint8, "wq"),
+                                           k(w_scale, torch.uint8, "w_scale"), _p(y), M, N, K, epilogue, k(w2q, torch.uint8, "w2q"),
+                                           k(w2_scale, torch.uint8, "w2_scale"), k(scale, name="scale"), k(bias, name="bias"),
+                                           k(resid, name="resid"), int(kernel), _stream()))
+    return y
+
+
 # ------------------------------------------------------------------------------------------ fp8 KV cache
 def kv8_alloc(n_slots: int, n_groups: int, s_max: int, hs: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """A zeroed fp8 KV cache: (k8 uint8 [slot, group, s_max, hs], v8 uint8 [slot, group, hs, s_max], k_exp, v_exp int8

@@ -59,7 +59,8 @@ int dh_set_tuning(int key, int value);
  * site (enum DhGemmRoute in csrc/gemm.h; tests/gemm_exact_reference.py mirrors the numbering); reset != 0 clears it after
  * the read.  Host side only: a thread-local OR next to each launch.  The quantised GEMMs are recorded as well: dh_linear_fp8*
  * (streaming with 1 / 2 / 4 row groups, the 128-tile with 4 or 2 stages, the 256-tile) and dh_linear_mxfp4* (streaming with
- * 1 / 2 / 4 row groups, tiled with 4 or 2 stages); the fp32-out entry points record the streaming routes of their bf16 forms. */
+ * 1 / 2 / 4 row groups, tiled with 4 or 2 stages) and dh_linear_mxfp4a6* (the same five, appended after them); the fp32-out entry
+ * points record the streaming routes of their bf16 forms. */
 uint64_t dh_debug_gemm_routes(int reset);
 const char* dh_last_error(void);
 /* Name of the first visible device's gcnArch ("gfx950") into buf; fails when no GPU. */
@@ -899,6 +900,50 @@ int dh_linear_mxfp4_ex(const uint8_t* xq, const float* x_scale, const uint8_t* w
 int dh_linear_mxfp4_f32(const uint8_t* xq, const float* x_scale, const uint8_t* wq, const uint8_t* w_scale, float* y32, int M,
                         int N, int K, void* stream);
 
+/* ------------------------------------------------------------------ MXFP6 activations (csrc/mxfp6.hip)
+ * An opt-in activation format beside MXFP4 weights: the activations are OCP MX v1.0 MXFP6 (e2m3) instead of e4m3 rows, and
+ * the e2m1 x e2m3 operand pair runs v_mfma_scale_f32_16x16x128_f8f6f4 at twice the rate of any pair with an e4m3 operand.
+ * Element.  e2m3: six bits, bit 5 the sign, bits 4..3 the exponent E, bits 2..0 the mantissa m.  Magnitude m / 8 for E = 0,
+ * else (1 + m / 8) * 2^(E - 1): 32 magnitudes 0 .. 7.5, strictly increasing in the low five bits.  No infinity, no NaN.
+ * Block.  32 consecutive k of one activation row share one E8M0 byte s with value 2^(s - 127).  There is no per-token scale.
+ * Quantiser (dualhyp_amd.quant.quantize_blocks_mxfp6; tests/mxfp6_reference.py is its fp64 restatement), for a bf16 row with
+ * K % 128 == 0, every step exact in fp32, the exponent from the exponent field.  amax = max |x| over the block.  amax == 0:
+ * s = 127, every code 0.  Otherwise e = floor(log2(amax)) - 2 clamped to [-126, 127], s = e + 127, a = |x| * 2^-e (bf16
+ * subnormals are the values they are).  The magnitude is the grid value nearest to a, ties to the even code; an a above 7.5
+ * saturates to 7.5 (reachable: an amax with mantissa above 1.875 would round to 8).  The sign bit is set only with a non-zero
+ * magnitude code: -0 is never produced.  Non-finite inputs are outside the contract.
+ * Product.  y[m, n] = epilogue( bf16( sum_k e2m3(xq[m, k]) * 2^(sx[m, k / 32] - 127) * e2m1(wq[n, k]) * 2^(sw[n, k / 32] - 127) ) ),
+ * fp32 accumulation, then the epilogues and bf16 rounding points of dh_linear_mxfp4_ex without the multiply by x_scale[m].
+ * The instruction applies both block scales; every product is exact in fp32; each kernel fixes one summation order per
+ * output, independent of the row count (tiled: k ascending in one accumulator; streaming: each wave's k-steps ascending,
+ * waves added in order).
+ * Physical layout of a quantised activation matrix of M rows (what xq / x_scale address): fragment order, as the weights.
+ * Rows are taken in groups of 16 and k in steps of 128; there are G = ceil(M / 16) groups, the last one complete in the
+ * buffer whatever M is.  For group g = m / 16 and k-step t = k / 128 there is one block of 1536 code bytes at byte offset
+ * (g * (K / 128) + t) * 1536 of xq and one block of 64 scale bytes at byte offset (g * (K / 128) + t) * 64 of x_scale.
+ * Inside a block, index l = 16 * q + r (r = m % 16 the row of the group, q = (k % 128) / 32 the MX block of the k-step)
+ * selects 24 code bytes and the scale byte at l.  The 24 bytes are the block's 32 codes as one little-endian 192-bit
+ * number, element i = k % 32 in bits 6 i .. 6 i + 5 (byte j holds bits 8 j .. 8 j + 7); they are stored as three planes of
+ * 512 bytes: bytes 8 p .. 8 p + 7 of the 24 are at p * 512 + l * 8 of the block, p = 0, 1, 2.  The scale byte at l is s of row
+ * m, MX block 4 t + q.  So xq has G * 16 * K * 3 / 4 bytes and x_scale G * 16 * K / 32.  The bytes of rows >= M in the last
+ * group are never written by the quantisers and never reach an output of a row < M.  dualhyp_amd.quant.pack_mxfp6 writes
+ * this layout.  (The operand map behind it, found on the hardware by tools/mxfp6_probe.hip, is in csrc/mxfp6.hip.) */
+
+/* dh_quant_rows_fp8's counterpart: bf16 rows [rows, K] -> codes q and scale bytes qscale in the layout above.  K % 128 == 0. */
+int dh_quant_rows_mxfp6(const dh_bf16* x, uint8_t* q, uint8_t* qscale, int rows, int K, void* stream);
+/* dh_rmsnorm_quant_fp8's counterpart: quantises, bit for bit, the bf16 row dh_rmsnorm_bf16 produces; xn_out (nullable)
+ * receives that row.  d % 128 == 0, d <= 8192. */
+int dh_rmsnorm_quant_mxfp6(const dh_bf16* x, const dh_bf16* w, dh_bf16* xn_out, uint8_t* q, uint8_t* qscale, int rows, int d,
+                           float eps, const uint8_t* row_tail, void* stream);
+/* dh_linear_mxfp4_ex with MXFP6 activations: xq / x_scale in the layout above, everything else (weights, K % 128 == 0,
+ * N % 16 == 0, epilogues, kernel selector, refusals) as dh_linear_mxfp4_ex. */
+int dh_linear_mxfp4a6_ex(const uint8_t* xq, const uint8_t* x_scale, const uint8_t* wq, const uint8_t* w_scale, dh_bf16* y, int M,
+                         int N, int K, int epilogue, const uint8_t* w2q, const uint8_t* w2_scale, const dh_bf16* vec_a,
+                         const dh_bf16* vec_b, const dh_bf16* resid, int kernel, void* stream);
+/* dh_linear_mxfp4_f32's counterpart: PLAIN on the streaming kernel, 1 <= M <= 128, the bf16-rounded result as fp32 [M, N]. */
+int dh_linear_mxfp4a6_f32(const uint8_t* xq, const uint8_t* x_scale, const uint8_t* wq, const uint8_t* w_scale, float* y32, int M,
+                          int N, int K, void* stream);
+
 /* ------------------------------------------------------------------ fp8 KV cache (csrc/kv8.hip, csrc/attention.hip)
  * Scheme.  Each KV group of each token has one K vector (after rope: the bf16 values dh_qkv_rope_cache_bf16 caches) and one V
  * vector of hs elements.  amax = max |x|; e = the smallest integer with amax <= 448 * 2^e (amax = m * 2^ex, m in [0.5, 1):
@@ -1003,6 +1048,16 @@ int dh_engine_create_ex(const dh_model_desc* h_desc, int max_batch, int s_max, i
  * needs n_embd and intermediate % 128 == 0 and merged LoRA. */
 int dh_engine_create_q(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype,
                        dh_engine** h_out);
+/* dh_engine_create_q with the block activations' format: act_dtype 0 = e4m3 rows with one scale per token (dh_engine_create_q
+ * itself), 1 = MXFP6 ("MXFP6 activations" above).  act_dtype 1 is accepted with weight_dtype 1 only: beside an e4m3 weight an
+ * e2m3 activation runs the MFMA at the fp8 rate, and that pair is refused with this reason.  Such an engine runs the fp8 layer
+ * sequence with its four quantisation points per block on dh_rmsnorm_quant_mxfp6 / dh_quant_rows_mxfp6 and its block linears
+ * on dh_linear_mxfp4a6_ex / _f32 (the fp32-out QKV form in front of the fused decode attention included); the final norm,
+ * lm_head and the adapter stay e4m3.  The phase-pinned kernel choice, the 128-row class boundary, kv_dtype 1 and every refusal
+ * of an fp8 engine are dh_engine_create_q's.  The code and scale buffers hold max_tokens rounded up to 16 rows and are counted
+ * in dh_engine_device_bytes. */
+int dh_engine_create_qa(const dh_model_desc* h_desc, int max_batch, int s_max, int max_tokens, int kv_dtype, int weight_dtype,
+                        int act_dtype, dh_engine** h_out);
 void dh_engine_destroy(dh_engine* e);
 int64_t dh_engine_device_bytes(const dh_engine* e);
 
