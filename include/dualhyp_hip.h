@@ -242,7 +242,20 @@ int dh_attn_verify_fused_bf16(const float* qkv32, int n_part, int pairs, int n_s
 /* LoRA-branch dropout, ger/lora.py:96,165,391 (`nn.Dropout(p=lora_dropout)` in front of lora_A; finetune/ger.py:401 trains at
  * 0.05): y = bf16(x * m), mask = m = keep ? bf16(1 / (1 - p)) : 0, keep drawn per element from Philox4x32-10 keyed by
  * (seed, call_id) and counted by (*step_dev, element): `step_dev` is a DEVICE counter the caller bumps once per micro-step, so
- * a captured hipGraph draws new masks on every replay (null = step 0).  n % 8 == 0.  ABI 5. */
+ * a captured hipGraph draws new masks on every replay (null = step 0).  n % 8 == 0.  ABI 5.
+ *
+ * The draw, completely (tests/dropout_reference.py restates it; tests/test_hip_dropout.py holds the kernel to it bit for bit):
+ *   - element i has chunk c = i / 8, half h = (i % 8) / 4 and lane e = i % 4;
+ *   - counter = {lo32(c), hi32(c) * 2 + h, lo32(step), hi32(step)}, step = *step_dev (0 when step_dev is null);
+ *   - key = {lo32(seed) ^ (call_id * 0x9E3779B9 mod 2^32), (hi32(seed) + call_id) mod 2^32};
+ *   - draw = word e of Philox4x32-10 on (counter, key): ten rounds {c0, c1, c2, c3} <- {hi(M1 * c2) ^ c1 ^ k0, lo(M1 * c2),
+ *     hi(M0 * c0) ^ c3 ^ k1, lo(M0 * c0)} with M0 = 0xD2511F53, M1 = 0xCD9E8D57, the key bumped by (0x9E3779B9, 0xBB67AE85) after
+ *     each round (Random123's philox4x32_10: its known-answer vectors hold);
+ *   - keep iff draw >= thresh, thresh = min(floor((double)(float)p * 2^32), 0xffffffff);
+ *   - m = bf16_rne(1.0f / (1.0f - p)), the subtraction and the division in fp32.  A kept element is y = bf16_rne(fp32(x) * fp32(m))
+ *     and mask = m; a dropped element is +0 in both y and mask (whatever x holds: -0, inf, NaN).
+ * So P(keep) = 1 - thresh / 2^32, and E[mask] = (1 - p) * m is 1.00195 at p = 0.05 (m = 1.0546875), not 1: m is rounded to bf16 as
+ * torch's bf16 dropout rounds it.  n % 8 != 0, p < 0, p >= 1 and a NaN p are refused and nothing is written. */
 int dh_dropout_bf16(const dh_bf16* x, dh_bf16* y, dh_bf16* mask, int64_t n, float p, uint64_t seed, uint32_t call_id,
                     const uint64_t* step_dev, void* stream);
 /* act = bf16(bf16(silu(g)) * u) from stored g, u (training forward keeps both; ger/model.py:315) */
