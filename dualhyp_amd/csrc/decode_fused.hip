@@ -833,6 +833,289 @@ size_t attn_verify_lds(int S, int ncol) {
     return 32 * HS * 2 + (size_t)(2 * S * HS + 48 * S + 32 + 2 * NW * 32 + NW * HS * ncol) * sizeof(float);
 }
 
+// --------------------------------------------------------------------------- attention (decode, shared prompt)
+// attn_decode_fused_kernel for the N rows of an utterance that share a prompt (sampled candidates, beams): rows u * N + j of qkv32,
+// j = 0 .. N-1, belong to utterance u, and every row's slot holds the same bytes in the n_sh = prompt_len[u] / 32 whole 32-key tiles
+// of the prompt (dh_engine_fork_slots, dh_engine_copy_prefix).  grid (n_utt * n_cg * n_groups), NW waves: a block serves one KV group
+// and one column group, the R <= Gs = 32 / q_per_kv consecutive rows u * N + cg * Gs + jj; query column = jj * q_per_kv + head, as in
+// attn_verify_fused_kernel.  Row jj produces the bits attn_decode_fused_kernel produces for it:
+//   - tiles t < n_sh are loaded ONCE per block, from the slot of the utterance's row 0, and serve every column; tiles t >= n_sh are
+//     private: for each row jj with t < (pos_jj + 31) / 32 the tile comes from the row's own slot and is masked to key < pos_jj for
+//     the row's columns and to nothing for every other column;
+//   - same NW, same tile -> wave deal (t % NW, shared or private, ascending t within a wave), same per-tile update and same combine
+//     order; a column's arithmetic never reads another column, and a tile in which a column sees no key leaves its running maximum,
+//     sum and accumulator as they are (attn_verify_fused_kernel's `none` rule);
+//   - each row finishes its own q / k / v from its partials, rotates at its own position kv_len - 1, appends to its own slot and
+//     merges its own key at the combine from LDS.
+// Nothing this launch writes is read back (a row's own position is masked in its own tile), so a wave's first tile is requested
+// before the LoRA / rope prologue.
+// hs 64 is held to 128 VGPRs (four waves per SIMD, 4 spilled registers): with the 75 KiB of LDS of four rows x eight heads two blocks
+// share a CU; hs 96 and 128 run one block per CU (189 / 227 VGPRs, up to 112 / 148 KiB).
+template <int HS, int PMAX, int NW>
+__global__ __launch_bounds__(NW * 64, HS == 64 ? 4 : 2) void attn_shared_fused_kernel(
+    const float* __restrict__ qkv32, int n_part, int pairs, int n_rows, int ldq, int qkv_dim,
+    const bf16_t* __restrict__ lora_b, float lora_scale, int split0, int split1,
+    const bf16_t* __restrict__ cos, const bf16_t* __restrict__ sin, const int32_t* __restrict__ seq_slot,
+    const int32_t* __restrict__ kv_len, const int32_t* __restrict__ prompt_len, bf16_t* __restrict__ k_cache,
+    bf16_t* __restrict__ vT_cache, bf16_t* __restrict__ y, int n_head, int n_groups, int s_max, int N, int Gs, int n_cg,
+    int r_max, float scale) {
+    constexpr int KS = HS / 16, DT = HS / 32, HALF = HS / 2, VC = 32, RMAX = 8;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int g = blockIdx.x % n_groups, ucg = blockIdx.x / n_groups, cg = ucg % n_cg, u = ucg / n_cg;
+    const int q_per_kv = n_head / n_groups;
+    const int R = min(Gs, N - cg * Gs), ncol = R * q_per_kv;            // this block's rows and live columns
+    const int row0 = u * N + cg * Gs;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 31, lh = lane >> 5;
+    // LDS carve (all offsets multiples of 16 B); sized by the host for r_max rows and r_max * q_per_kv columns
+    bf16_t* sQ = reinterpret_cast<bf16_t*>(smem);                       // [32][HS] rotated queries, column = jj * q_per_kv + head
+    float* sKn = reinterpret_cast<float*>(smem + VC * HS * 2);          // [r_max][HS] new keys (bf16 values)
+    float* sVn = sKn + r_max * HS;                                      // [r_max][HS] new values
+    float* sXa = sVn + r_max * HS;                                      // [r_max][48] bf16(x·A^T)
+    float* sSn = sXa + r_max * 48;                                      // [32] score of a column's own key
+    float* sPm = sSn + VC;                                              // [NW][32] running max
+    float* sPl = sPm + NW * VC;                                         // [NW][32] running sum
+    int* sPos = reinterpret_cast<int*>(sPl + NW * VC);                  // [8] position of row jj's new token
+    int* sSlot = sPos + RMAX;                                           // [8] its KV slot
+    float* sPo = reinterpret_cast<float*>(sSlot + RMAX);                // [NW][HS][ncol] partial O^T
+    constexpr int NT_ = NW * 64;
+
+    if (tid < RMAX) {
+        const int r = row0 + (tid < R ? tid : 0);
+        sPos[tid] = tid < R ? kv_len[r] - 1 : 0;
+        sSlot[tid] = seq_slot[r];
+    }
+    __syncthreads();
+    int n_sh = prompt_len[u] / 32;                                      // whole prompt tiles: the same bytes in every row's slot
+    n_sh = n_sh < 0 ? 0 : (n_sh > s_max / 32 ? s_max / 32 : n_sh);
+    int t_end = n_sh;                                                   // tiles with a key some column sees
+    for (int j = 0; j < R; ++j) t_end = max(t_end, (sPos[j] + 31) / 32);
+    const size_t blk = (size_t)s_max * HS;                              // elements of a (slot, group) block in either cache
+    const size_t sh_off = ((size_t)seq_slot[u * N] * n_groups + g) * blk;
+
+    // ---- this wave's items in walking order: tile t = wave, wave + NW, ...; a shared tile is one item, a private tile one item per
+    // row jj that has it
+    int it_t = wave, it_j = 0;
+    auto settle = [&]() {       // the first item at or behind (it_t, it_j); it_t >= t_end: none left
+        while (it_t < t_end) {
+            if (it_t < n_sh) { it_j = 0; return; }
+            while (it_j < R && it_t >= (sPos[it_j] + 31) / 32) ++it_j;
+            if (it_j < R) return;
+            it_t += NW;
+            it_j = 0;
+        }
+    };
+    auto advance = [&]() {
+        if (it_t < n_sh) { it_t += NW; it_j = 0; }
+        else ++it_j;
+        settle();
+    };
+    struct VF { bf16x8 v; };
+    struct Tile { bf16x8 kf[KS]; VF vf[DT][2]; };
+    Tile tl;
+    // the caches are in MFMA-fragment order (common.h): a tile is 8 coalesced 1-KiB loads
+    auto load_tile = [&](Tile& T, int t, int jj) {
+        const size_t off = t < n_sh ? sh_off : ((size_t)sSlot[jj] * n_groups + g) * blk;
+        const bf16_t* kbase = k_cache + off;
+        const bf16_t* vbase = vT_cache + off;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            T.kf[ks] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kbase + kfrag_blk<HS>(t, ks) + lane * 8));
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+                T.vf[dt][s2].v = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vbase + vfrag_blk<HS>(t, dt, s2) + lane * 8));
+    };
+    settle();
+    if (it_t < t_end) load_tile(tl, it_t, it_j);
+
+    const size_t pstride = (size_t)n_rows * ldq;
+    auto psum = [&](int j, int c) {
+        const float* rowp = qkv32 + (size_t)(row0 + j) * ldq;
+        float v[PMAX];
+#pragma unroll
+        for (int p = 0; p < PMAX; ++p) v[p] = p < n_part ? rowp[p * pstride + c] : 0.f;
+        // the decode family's summation order (common.h, "K-slice combine"), as in attn_decode_fused_kernel
+        float s = 0.f;
+        if (pairs) {
+#pragma unroll
+            for (int p = 0; p < PMAX; p += 2) s += v[p] + v[p + 1];
+        } else {
+#pragma unroll
+            for (int p = 0; p < PMAX; ++p) s += v[p];
+        }
+        return s;
+    };
+    if (lora_b != nullptr)
+        for (int i = tid; i < 48 * R; i += NT_) sXa[i] = rbf(psum(i / 48, qkv_dim + i % 48));
+    for (int i = tid; i < VC * HS; i += NT_) sQ[i] = 0;               // padding columns
+    __syncthreads();
+
+    // bf16 value of fused-qkv column c of row j: bf16(bf16(x·W^T) + bf16(bf16(xa·B^T)*s))
+    auto finish = [&](int j, int c) -> float {
+        float o = rbf(psum(j, c));
+        if (lora_b != nullptr) {
+            const int seg = (c >= split0) + (c >= split1);
+            const uint4* b4 = reinterpret_cast<const uint4*>(lora_b + (size_t)c * 16);
+            float l = 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint4 bv = b4[h];
+                const bf16_t* bp = reinterpret_cast<const bf16_t*>(&bv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) l = fmaf(sXa[j * 48 + seg * 16 + h * 8 + e], bf2f(bp[e]), l);
+            }
+            o = rbf(o + rbf(rbf(l) * lora_scale));
+        }
+        return o;
+    };
+    const int gbase = g * (q_per_kv + 2) * HS;
+    const int n_rope = (q_per_kv + 1) * HALF, per_row = n_rope + HS;
+    for (int it0 = tid; it0 < R * per_row; it0 += NT_) {
+        const int jr = it0 / per_row, it = it0 % per_row, pj = sPos[jr];
+        const size_t off = ((size_t)sSlot[jr] * n_groups + g) * blk;
+        bf16_t* kdst = k_cache + off;
+        bf16_t* vdst = vT_cache + off;
+        if (it < n_rope) {
+            const int j = it / HALF, i = it % HALF;
+            const float x1 = finish(jr, gbase + j * HS + i), x2 = finish(jr, gbase + j * HS + HALF + i);
+            const bf16_t* cp = cos + (size_t)pj * HS;
+            const bf16_t* sp = sin + (size_t)pj * HS;
+            const bf16_t o1 = f2bf(rbf(x1 * bf2f(cp[i])) + rbf(-x2 * bf2f(sp[i])));
+            const bf16_t o2 = f2bf(rbf(x2 * bf2f(cp[HALF + i])) + rbf(x1 * bf2f(sp[HALF + i])));
+            if (j < q_per_kv) {
+                sQ[(jr * q_per_kv + j) * HS + i] = o1;
+                sQ[(jr * q_per_kv + j) * HS + HALF + i] = o2;
+            } else {
+                sKn[jr * HS + i] = bf2f(o1);
+                sKn[jr * HS + HALF + i] = bf2f(o2);
+                kdst[kfrag_off<HS>(pj, i)] = o1;
+                kdst[kfrag_off<HS>(pj, HALF + i)] = o2;
+            }
+        } else {
+            const int e = it - n_rope;
+            const bf16_t v = f2bf(finish(jr, gbase + (q_per_kv + 1) * HS + e));
+            sVn[jr * HS + e] = bf2f(v);
+            vdst[vfrag_off<HS>(pj, e)] = v;
+        }
+    }
+    __syncthreads();
+
+    // score of each column's own key (merged at the combine, as in the single-token kernel)
+    for (int c = wave; c < ncol; c += NW) {
+        const float* kn = sKn + (c / q_per_kv) * HS;
+        float p = 0.f;
+        for (int e = lane; e < HS; e += 64) p += bf2f(sQ[c * HS + e]) * kn[e];
+        p = wave_sum(p);
+        if (lane == 0) sSn[c] = p * scale;
+    }
+
+    bf16x8 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(sQ + lr * HS + ks * 16 + lh * 8);
+    // the row of this lane's column and the keys it sees in the cache: [0, p_col); a padding column sees none
+    const int j_col = lr < ncol ? lr / q_per_kv : -1;
+    const int p_col = lr < ncol ? sPos[j_col] : 0;
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+    // jj < 0: a shared tile, every column's; else row jj's private tile
+    auto compute_tile = [&](const Tile& T, int t, int jj) {
+        const int key0 = t * 32;
+        const int lim = jj < 0 || jj == j_col ? p_col : 0;
+        f32x16 st;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.kf[ks], qf[ks], st, 0, 0, 0);
+        float m_t = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key_abs = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            float sc = st[r] * scale;
+            sc = key_abs < lim ? sc : -INFINITY;
+            st[r] = sc;
+            m_t = fmaxf(m_t, sc);
+        }
+        m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
+        const float m_new = fmaxf(m_run, m_t);
+        const bool none = m_new == -INFINITY;               // no key of this column so far: nothing changes
+        const float alpha = none ? 1.f : __expf(m_run - m_new);
+        m_run = m_new;
+        float psm = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = none ? 0.f : __expf(st[r] - m_new);
+            st[r] = p;
+            psm += p;
+        }
+        l_run = l_run * alpha + psm;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            union { bf16x8 v; uint32_t u[4]; } pf;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pf.u[j] = pack2bf(st[8 * s2 + 2 * j], st[8 * s2 + 2 * j + 1]);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                if (s2 == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+                }
+                // keys a column does not see carry p == 0 and the cache beyond the written prefix is finite
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(T.vf[dt][s2].v, pf.v, o[dt], 0, 0, 0);
+            }
+        }
+    };
+    while (it_t < t_end) {
+        const int ct = it_t, cj = it_t < n_sh ? -1 : it_j;
+        advance();
+        compute_tile(tl, ct, cj);
+        if (it_t < t_end) load_tile(tl, it_t, it_j);
+    }
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (lr < ncol) {
+        if (lh == 0) {
+            sPm[wave * VC + lr] = m_run;
+            sPl[wave * VC + lr] = l_tot;
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                sPo[(wave * HS + d) * ncol + lr] = o[dt][r];
+            }
+    }
+    __syncthreads();
+    // ---- combine the NW wave partials and each column's own key
+    for (int it = tid; it < ncol * HS; it += NT_) {
+        const int c = it / HS, d = it % HS, jr = c / q_per_kv, h = c % q_per_kv;
+        const float sn = sSn[c];
+        float M = sn;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, sPm[w * VC + c]);
+        const float pn = __expf(sn - M);
+        float L = pn, O = rbf(pn) * sVn[jr * HS + d];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = sPm[w * VC + c];
+            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            L += sPl[w * VC + c] * f;
+            O += sPo[(w * HS + d) * ncol + c] * f;
+        }
+        y[(size_t)(row0 + jr) * n_head * HS + (g * q_per_kv + h) * HS + d] = f2bf(O / L);
+    }
+}
+template <int HS>
+size_t attn_shared_lds(int r_max, int ncol) {
+    constexpr int NW = attn_fused_waves<HS>();
+    return 32 * HS * 2 + (size_t)(2 * r_max * HS + 48 * r_max + 32 + 2 * NW * 32 + 16 + NW * HS * ncol) * sizeof(float);
+}
+
 // --------------------------------------------------------------------------- finish + norm
 // grid (rows), 256 threads.  h32: [n_part][rows][ldh] fp32 partials of x·[W;A]^T (columns
 // [d, d+16) = x·A^T when lora_b != null).  Per row:
@@ -1268,6 +1551,55 @@ extern "C" int dh_attn_verify_fused_bf16(const float* qkv32, int n_part, int pai
                                          void* stream) {
     return dh_attn_verify_fused_impl(qkv32, n_part, pairs, n_seq, S, qkv_dim, n_ext, lora_b, lora_scale, split0, split1, cos, sin,
                                      seq_slot, kv_len, k_cache, vT_cache, y, n_head, n_groups, hs, s_max, p_max, stream);
+}
+
+// launches of attn_shared_fused_kernel this process has issued or captured (dh_attn_shared_launch_count, a test hook)
+static int64_t g_attn_shared_launches = 0;
+extern "C" int64_t dh_attn_shared_launch_count(void) { return g_attn_shared_launches; }
+
+// dh_attn_decode_fused_bf16 over the same rows, the whole prompt tiles of an utterance streamed once per block of its rows
+// (include/dualhyp_hip.h, "Shared-prompt attention"; the engine's step under dh_engine_set_shared_prompt launches it)
+extern "C" int dh_attn_decode_shared_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
+                                          const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
+                                          const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
+                                          dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int group_rows,
+                                          const int32_t* prompt_len, void* stream) {
+    DH_CHECK(qkv32 && cos && sin && seq_slot && kv_len && k_cache && vT_cache && y, "dh_attn_decode_shared_bf16: null argument");
+    DH_CHECK(prompt_len, "dh_attn_decode_shared_bf16: null prompt_len (a device array of n_seq / group_rows int32)");
+    DH_CHECK(group_rows >= 2 && group_rows <= 8, "dh_attn_decode_shared_bf16: group_rows = %d rows per utterance, 2 .. 8 are served", group_rows);
+    DH_CHECK(n_seq % group_rows == 0, "dh_attn_decode_shared_bf16: n_seq = %d rows are not group_rows = %d per utterance", n_seq, group_rows);
+    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DCOLS, "dh_attn_decode_shared_bf16: bad head counts");
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_shared_bf16: head_size %d unsupported", hs);
+    DH_CHECK(s_max % 64 == 0 && n_part >= 1 && n_part <= MAXP, "dh_attn_decode_shared_bf16: bad s_max / n_part");
+    DH_CHECK(qkv_dim == (n_head + 2 * n_groups) * hs, "dh_attn_decode_shared_bf16: qkv_dim mismatch");
+    DH_CHECK(lora_b == nullptr || n_ext >= 48, "dh_attn_decode_shared_bf16: LoRA needs the 48 x·A^T columns");
+    if (n_seq <= 0) return 0;
+    const float scale = 1.0f / sqrtf((float)hs);
+    hipStream_t s = (hipStream_t)stream;
+    const int q_per_kv = n_head / n_groups, N = group_rows;
+    const int Gs = 32 / q_per_kv, n_cg = (N + Gs - 1) / Gs, r_max = N < Gs ? N : Gs, ncol = r_max * q_per_kv;
+    dim3 grid((n_seq / N) * n_cg * n_groups);
+#define SHR_LAUNCH(HSV, PM)                                                                                           \
+    hipLaunchKernelGGL((attn_shared_fused_kernel<HSV, PM, attn_fused_waves<HSV>()>), grid, dim3(64 * attn_fused_waves<HSV>()), attn_shared_lds<HSV>(r_max, ncol), s, qkv32, n_part, pairs, \
+                       n_seq, qkv_dim + n_ext, qkv_dim, lora_b, lora_scale, split0, split1, cos, sin, seq_slot, kv_len, prompt_len, k_cache,  \
+                       vT_cache, y, n_head, n_groups, s_max, N, Gs, n_cg, r_max, scale)
+#define SHR_HS(HSV)                                                                                                   \
+    do {                                                                                                              \
+        DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 2, attn_fused_waves<HSV>()>), attn_shared_lds<HSV>(8, 32));    \
+        DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 8, attn_fused_waves<HSV>()>), attn_shared_lds<HSV>(8, 32));    \
+        DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 16, attn_fused_waves<HSV>()>), attn_shared_lds<HSV>(8, 32));   \
+        if (n_part <= 2) SHR_LAUNCH(HSV, 2);                                                                          \
+        else if (n_part <= 8) SHR_LAUNCH(HSV, 8);                                                                     \
+        else SHR_LAUNCH(HSV, 16);                                                                                     \
+    } while (0)
+    if (hs == 64) SHR_HS(64);
+    else if (hs == 96) SHR_HS(96);
+    else SHR_HS(128);
+#undef SHR_HS
+#undef SHR_LAUNCH
+    DH_LAUNCH_CHECK();
+    ++g_attn_shared_launches;
+    return 0;
 }
 
 // finish_norm_kernel<, true> from this many rows on.  tools/sweep_finish.py, d 2048, us per launch, loads behind | ahead of the

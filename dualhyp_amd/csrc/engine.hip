@@ -47,6 +47,10 @@ struct dh_engine {
     int32_t* stop_fin_tok = nullptr;                    // dh_engine_set_stop: a beam call's [n_utt, W] ending ids
     int64_t* beam_hist = nullptr;                       // dh_engine_set_beam_history: the caller's [2][n_utt * W][max_new] history planes (null: off)
     int beam_hist_ngram = 0;                            // and the beam steps' no_repeat_ngram (0: no ban)
+    int shared_rows = 0;                                // dh_engine_set_shared_prompt: rows per utterance (0: off) and the utterances'
+    const int32_t* shared_plen = nullptr;               // prompt lengths on the device
+    int step_shared_rows = 0;                           // the same two for the step being launched or captured (decode_step sets and
+    const int32_t* step_shared_plen = nullptr;          // clears them: a prompt forward of one token per sequence never sees them)
     int32_t* slot_list = nullptr;                       // [B]: the KV slots of a dh_engine_forward_slots call (seq_meta[0..B) stays the identity)
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
@@ -90,13 +94,15 @@ struct dh_engine {
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows; the ending ids of dh_engine_set_stop; the history planes and their ban of dh_engine_set_beam_history
         int beam_w = 0; dh_beam_state beam{}; int32_t* stop_fin_tok = nullptr; int64_t* beam_hist = nullptr; int beam_ngram = 0;
+        // dh_engine_set_shared_prompt: rows per utterance (0 in a key whose step runs the single-token attention) and the prompt lengths
+        int shared_rows = 0; const int32_t* shared_plen = nullptr;
         bool operator==(const GKey& k) const {
             return tokens == k.tokens && tok_ld == k.tok_ld && length == k.length && done == k.done && n_seq == k.n_seq &&
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
                    ctl == k.ctl && beam_w == k.beam_w && stop_fin_tok == k.stop_fin_tok && beam_hist == k.beam_hist &&
-                   beam_ngram == k.beam_ngram && memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
+                   beam_ngram == k.beam_ngram && shared_rows == k.shared_rows && shared_plen == k.shared_plen && memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
@@ -706,6 +712,10 @@ int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t
             if ((rc = dh_attn_verify_fused_impl(e->part32, np, pairs, n_seq / spec_S, spec_S, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale,
                                                 d, d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
                                                 e->s_max, p_max, s))) return rc;
+        } else if (e->step_shared_rows) {
+            if ((rc = dh_attn_decode_shared_bf16(e->part32, np, pairs, n_seq, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale, d,
+                                                 d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
+                                                 e->s_max, e->step_shared_rows, e->step_shared_plen, s))) return rc;
         } else
         if ((rc = dh_attn_decode_fused_bf16(e->part32, np, pairs, n_seq, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale, d,
                                             d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G,
@@ -1079,9 +1089,36 @@ int check_automaton_call(const dh_engine* e, const char* name, int64_t eos_id, i
     return 0;
 }
 
+// What shared-prompt attention needs of the engine (`name`: the setter) and of a call that runs under it (`name`: dh_engine_decode or
+// dh_engine_decode_beam, n_seq its rows): the streaming single-token layers over whole utterances.  group_rows == 0: nothing to check.
+int check_shared_call(const dh_engine* e, const char* name, int n_seq, int group_rows) {
+    if (group_rows == 0) return 0;
+    DH_CHECK(!e->fp8, "%s: shared-prompt attention (group_rows=%d) on an fp8 or MXFP4 engine: its step does not run the streaming "
+             "layers that launch the kernel; not supported", name, group_rows);
+    DH_CHECK(!e->kv8, "%s: shared-prompt attention (group_rows=%d) reads bf16 cache tiles; an fp8 KV cache is not supported", name, group_rows);
+    DH_CHECK(e->rsqrt_vec == 0, "%s: shared-prompt attention (group_rows=%d) with the CPU rsqrt emulation, which flags rows by their "
+             "place in a call; not supported", name, group_rows);
+    DH_CHECK(g_decode_tiled_rows == 0, "%s: shared-prompt attention (group_rows=%d) with dh_set_tuning key 10, which moves steps to the "
+             "tiled kernels by row count; not supported", name, group_rows);
+    DH_CHECK(n_seq % group_rows == 0, "%s: shared-prompt attention is set for group_rows=%d rows per utterance; %d rows are no multiple",
+             name, group_rows, n_seq);
+    DH_CHECK(n_seq <= MAX_DECODE_ROWS, "%s: shared-prompt attention (group_rows=%d): %d rows exceed the streaming step's %d", name,
+             group_rows, n_seq, MAX_DECODE_ROWS);
+    return 0;
+}
+
+int plain_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s);
 int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
-    if (k.beam_w) return beam_step(e, k, s);
     if (k.spec) return verify_step(e, k, s);
+    e->step_shared_rows = k.shared_rows;                // what run_layers_decode launches for this step's attention
+    e->step_shared_plen = k.shared_plen;
+    const int rc = k.beam_w ? beam_step(e, k, s) : plain_step(e, k, s);
+    e->step_shared_rows = 0;
+    e->step_shared_plen = nullptr;
+    return rc;
+}
+
+int plain_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     const bool rows = k.row_seq != nullptr;
     hipLaunchKernelGGL(decode_prep_kernel, dim3(cdiv(k.n_seq, 64)), dim3(64), 0, s, k.tokens, k.tok_ld, k.length, k.row_seq, k.row_slot,
                        e->dec_ids, e->tok_slot, e->tok_pos, seq_meta(e).kv, rows ? nullptr : e->step_dev, k.n_seq, k.n_all,
@@ -1354,6 +1391,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode: bad sampling parameters");
     if (int rc = check_pen_tables(e, "dh_engine_decode", tok_ld)) return rc;
     if (int rc = check_automaton_call(e, "dh_engine_decode", eos_id, n_seq)) return rc;
+    if (int rc = check_shared_call(e, "dh_engine_decode", n_seq, e->shared_rows)) return rc;
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
@@ -1367,6 +1405,7 @@ extern "C" int dh_engine_decode(dh_engine* e, int64_t* tokens, int tok_ld, int32
     key.n_seq = n_seq; key.top_k = top_k; key.temp = temperature; key.eos = eos_id; key.seed = seed;
     key.rsqrt_vec = e->rsqrt_vec; key.tiled_rows = g_decode_tiled_rows;
     key.ctl = step_ctl(e, STEP_DECODE, top_k);
+    key.shared_rows = e->shared_rows; key.shared_plen = e->shared_plen;
     return launch_steps(e, key, n_steps, s);
 }
 
@@ -1379,6 +1418,8 @@ extern "C" int dh_engine_decode_rows(dh_engine* e, int64_t* tokens, int tok_ld, 
     DH_CHECK(temperature > 0.f && top_k >= 0, "dh_engine_decode_rows: bad sampling parameters");
     if (int rc = check_pen_tables(e, "dh_engine_decode_rows", tok_ld)) return rc;
     if (int rc = check_automaton_call(e, "dh_engine_decode_rows", eos_id, n_seq)) return rc;
+    DH_CHECK(e->shared_rows == 0, "dh_engine_decode_rows: shared-prompt attention is set (group_rows=%d); a row list names any sequence "
+             "in any slot, so a step's rows are not the rows of utterances", e->shared_rows);
     if (n_steps <= 0) return 0;
     e->seq_slot = row_slot;
     // the graph reads row_seq / row_slot when it runs: their contents change between calls, their addresses are part of the key
@@ -1431,6 +1472,8 @@ extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, 
              "launch's own picks, so the step would need per-position tables", e->set.bias.n);
     DH_CHECK(!e->set.aut.on(), "dh_engine_decode_spec: an automaton set of %d states is set; a verify position's state would depend on the "
              "picks of this launch's earlier positions", e->set.aut.n_states);
+    DH_CHECK(e->shared_rows == 0, "dh_engine_decode_spec: shared-prompt attention is set (group_rows=%d); a verify step's rows are "
+             "positions of one sequence, not rows of an utterance", e->shared_rows);
     DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
     DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
     DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
@@ -1518,6 +1561,9 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     DH_CHECK(!e->kv8, "dh_engine_decode_beam: the re-parenting copies bf16 cache tiles; an fp8 KV cache is not supported");
     DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_beam: the CPU rsqrt emulation flags rows by their place in a call; not supported");
     DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_beam: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
+    DH_CHECK(e->shared_rows == 0 || e->shared_rows == W, "dh_engine_decode_beam: shared-prompt attention is set for group_rows=%d rows per "
+             "utterance, the call has W=%d beams", e->shared_rows, W);
+    if (int rc = check_shared_call(e, "dh_engine_decode_beam", (int)rows, e->shared_rows)) return rc;
     const int nt_max = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
     DH_CHECK(e->beam_cand_ids && (W == 1 || (size_t)rows * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32 <= e->beam_scratch_elems),
              "dh_engine_decode_beam: the re-parenting scratch is too small for W=%d and %d new tokens (dh_engine_reserve_beams)", W, max_new_tokens);
@@ -1530,6 +1576,7 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     key.tok_ld = max_new_tokens; key.length = st->n_steps; key.done = st->done; key.n_seq = (int)rows; key.eos = eos_id;
     key.limit = prompt_len; key.n_all = n_utt; key.max_new = max_new_tokens;
     key.ctl = step_ctl(e, STEP_BEAM, 0);
+    key.shared_rows = e->shared_rows; key.shared_plen = e->shared_plen;
     key.beam_w = W; key.beam = *st; key.stop_fin_tok = e->stop_fin_tok; key.beam_hist = e->beam_hist; key.beam_ngram = e->beam_hist_ngram;
     return launch_steps(e, key, n_steps, s);
 }
@@ -1626,6 +1673,21 @@ extern "C" int dh_engine_set_automaton(dh_engine* e, const dh_automaton_spec* au
     if (int rc = dh_automaton_pack("dh_engine_set_automaton", automaton, e->d.vocab, start != nullptr, aa)) return rc;
     e->set.aut = aa;
     e->aut_start = aa.on() ? start : nullptr;
+    return 0;
+}
+
+extern "C" int dh_engine_set_shared_prompt(dh_engine* e, int group_rows, const int32_t* d_prompt_len) {
+    DH_CHECK(e, "dh_engine_set_shared_prompt: null engine");
+    if (group_rows == 0 || d_prompt_len == nullptr) {
+        e->shared_rows = 0;
+        e->shared_plen = nullptr;
+        return 0;
+    }
+    DH_CHECK(group_rows >= 2 && group_rows <= DH_MAX_SAMPLES, "dh_engine_set_shared_prompt: group_rows=%d: 2 .. %d rows of an utterance "
+             "share a prompt (0 turns it off)", group_rows, DH_MAX_SAMPLES);
+    if (int rc = check_shared_call(e, "dh_engine_set_shared_prompt", 0, group_rows)) return rc;
+    e->shared_rows = group_rows;
+    e->shared_plen = d_prompt_len;
     return 0;
 }
 

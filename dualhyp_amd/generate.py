@@ -463,6 +463,38 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     return res if len(res) > 1 else out
 
 
+def check_shared_prompt(model, shared_prompt, rows_per_utt: int, what: str) -> bool:
+    """shared_prompt of a sample_batch / beam_search_batch call (`what`) whose utterances decode rows_per_utt rows each, or a ValueError
+    with the reason the engine's setter would give (include/dualhyp_hip.h, dh_engine_set_shared_prompt)."""
+    if not isinstance(shared_prompt, bool):
+        raise ValueError(f"shared_prompt is True or False, not {shared_prompt!r}")
+    if not shared_prompt:
+        return False
+    if not 2 <= rows_per_utt <= 8:
+        raise ValueError(f"shared_prompt=True: {what} decodes {rows_per_utt} row per utterance; 2..8 rows share a prompt")
+    if getattr(model, "fp8", False):
+        raise ValueError(f"shared_prompt=True does not go with an fp8 or MXFP4 model: its decode step does not run the streaming layers "
+                         "that launch the shared-prompt attention kernel")
+    if getattr(model, "kv_cache_dtype", "bf16") != "bf16":
+        raise ValueError("shared_prompt=True does not go with an fp8 KV cache: the kernel reads bf16 cache tiles")
+    if getattr(model, "cpu_rsqrt_vec_width", 0):
+        raise ValueError("shared_prompt=True does not go with the CPU rsqrt emulation (cpu_rsqrt_vec_width), which flags rows by their "
+                         "place in a call")
+    return True
+
+
+@contextlib.contextmanager
+def _shared_prompt(eng, on: bool, rows_per_utt: int, plen: torch.Tensor):
+    """Shared-prompt attention for the decode steps inside: part of a captured step's key, taken back behind them."""
+    if on:
+        eng.set_shared_prompt(rows_per_utt, plen)
+    try:
+        yield
+    finally:
+        if on:
+            eng.set_shared_prompt()
+
+
 MAX_SAMPLES = 8           # DH_MAX_SAMPLES: the slots dh_engine_fork_slots gives an utterance, its own included
 
 
@@ -480,7 +512,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                  eos_id: Optional[int] = None, prefill_batch: int = 32, share_prefix: Union[bool, str] = False, token_mask=None,
                  no_repeat_ngram: int = 0, stop=None, top_logprobs: int = 0, timing: Optional[dict] = None,
                  return_state: bool = False, speculate: int = 0, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None):
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None,
+                 shared_prompt: bool = False):
     """num_samples = N (2..8) sampled candidates per prompt from ONE prefill of it (include/dualhyp_hip.h, "Sampled candidates").
 
     DEFINITION: sample j of utterance u is row u * N + j of generate_batch over [p for p in prompts for _ in range(N)] with the same
@@ -505,8 +538,13 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
       top_logprobs    with top_logprobs=K: (ids [n, K] int32, values [n, K] float32) CPU tensors, generate_batch's.
     return_state: (that, the dict of the call's device state: tokens, length, done, logprobs[, top_ids, top_logprobs], B * N rows).
 
-    timing gains generate_batch's keys, with prefill_tokens counting every prompt once, and fork_ms: the fork launch between its own
-    two events, inside prefill_ms.
+    shared_prompt: the decode steps' attention reads an utterance's whole 32-key prompt tiles once per block of its N rows, from
+    slot u * N, where every row streamed its own copy (include/dualhyp_hip.h, "Shared-prompt attention") — the same bits, so the
+    same everything; it goes with every other argument.  The fork still fills the copies.  False (the default): the launches the
+    call always made.  Refused for fp8 / MXFP4 models, an fp8 KV cache and the CPU rsqrt emulation.
+
+    timing gains generate_batch's keys, with prefill_tokens counting every prompt once, fork_ms: the fork launch between its own
+    two events, inside prefill_ms, and shared_prompt.
 
     Refused with a ValueError before anything is launched: num_samples outside 2..8; top_k == 1 (the arg-max gives N equal rows);
     speculate (a verify step confirms drafts against the arg-max); RelPrompt models (their prompts carry spliced embeddings)."""
@@ -520,6 +558,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     if isinstance(model, RelGPT):
         raise ValueError(f"num_samples={N}: the RelPrompt decoder's prompts carry spliced reliability embeddings, which a prefill by "
                          "ids into the source slots does not hold")
+    shared_prompt = check_shared_prompt(model, shared_prompt, N, f"num_samples={N}")
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     bias = _check_bias(bias)
     automaton = _check_automaton(automaton)
@@ -582,7 +621,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     if ev:
         ev[1].record()
     steps_run = 0
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias, aut):
+    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias, aut), \
+            _shared_prompt(eng, shared_prompt, N, plen):
         if max_new_tokens > 1:
             steps_run = _decode_steps(eng, tokens, length, done, max_new_tokens - 1, temperature, top_k, eos_id, seed,
                                       early=eos_id is not None or stop is not None)
@@ -601,6 +641,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + R * steps_run
         timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens) - (B - 1) * P
         timing["shared_prefix"] = P
+        timing["shared_prompt"] = shared_prompt
     reasons = _stop.finish_reasons(done_h)
     out = []
     for u in range(B):
@@ -628,7 +669,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
 @torch.inference_mode()
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
                       length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
-                      token_mask=None, no_repeat_ngram: int = 0, stop=None, bias=None, history: str = "host"):
+                      token_mask=None, no_repeat_ngram: int = 0, stop=None, bias=None, history: str = "host",
+                      shared_prompt: bool = False):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
@@ -673,7 +715,12 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     2 W ids that the mask allows and the ban leaves; a row left with fewer than 2 W ignores the ban at that step), and stop
     sequences end a hypothesis whose own text completes one ("stop", the ids stay in its tokens).  The state of return_state carries
     the planes (host["history"][u][w][:n_steps[u]] is live beam w's text).  A bias and penalties stay refused: they would change
-    what a candidate's rank and a beam's score mean."""
+    what a candidate's rank and a beam's score mean.
+
+    shared_prompt (W >= 2, either `history`): the beam steps' attention reads an utterance's whole 32-key prompt tiles once per block
+    of its W rows, from slot u * W (include/dualhyp_hip.h, "Shared-prompt attention"; the re-parenting moves only the tiles behind
+    them) — the same bits, so the same tokens, parents, scores and pool.  False (the default): the launches the call always made.
+    Refused for W = 1 and, as the whole call is, for fp8 models."""
     if history not in _beam.HISTORIES:
         raise ValueError(f'history is "host" or "device", not {history!r}')
     on_device = history == "device"
@@ -692,6 +739,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
         raise ValueError(f"no_repeat_ngram={no_repeat_ngram} does not go with beam search: the beams' histories live on the host, so the "
                          "sampling kernels cannot form a beam's ban set; it runs under generate_batch and generate_stream" + _beam.HISTORY_HINT)
     W = _beam.check_arguments(model, num_beams, B)
+    shared_prompt = check_shared_prompt(model, shared_prompt, W, f"num_beams={W}")
     length_penalty = _beam.check_length_penalty(length_penalty)
     lens = [int(p.numel()) for p in prompts]
     T_max = max(lens)
@@ -729,6 +777,8 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
         eng.set_stop(stop, plen if stop.sequences else None, state.fin_tok_buffer())     # likewise
     if on_device:
         eng.set_beam_history(hist, ngram)                   # likewise
+    if shared_prompt:
+        eng.set_shared_prompt(W, plen)                      # likewise
     try:
         while step < max_new_tokens:
             c = max_new_tokens - step if eos_id is None and stop is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
@@ -743,6 +793,8 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
             eng.set_stop(None)
         if on_device:
             eng.set_beam_history(None)
+        if shared_prompt:
+            eng.set_shared_prompt()
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these hypotheses; a later cached forward must start at 0
@@ -758,6 +810,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
         moved = sum(p != w for u in range(B) for t in range(1, h["n_steps"][u]) for w, p in enumerate(h["beam_parent"][u][t]))
         timing["beam_step_rows"] = timing.get("beam_step_rows", 0) + took
         timing["beam_copied_rows"] = timing.get("beam_copied_rows", 0) + moved
+        timing["shared_prompt"] = shared_prompt
     out = []
     for u in range(B):
         hyps = _beam.hypotheses(h, u, W, length_penalty, eos_id=eos_id)

@@ -638,6 +638,20 @@ class _Engine:
         _lib.check(self.lib.dh_engine_set_automaton(self.handle, C.byref(automaton.c_struct()), start.data_ptr()))
         self._automaton = (automaton, start)
 
+    def set_shared_prompt(self, group_rows: int = 0, prompt_len: Optional[torch.Tensor] = None) -> None:
+        """Shared-prompt attention (include/dualhyp_hip.h) for later decode / decode_beam calls whose rows u * group_rows + j are the
+        candidates or beams of utterance u: prompt_len, the int32 [n_utt] prompt lengths on the engine's device (what fork_slots
+        takes), kept alive here while set; 0 / None turns it off (dh_engine_set_shared_prompt).  Part of a captured step's key.
+        While set, decode_rows and decode_spec refuse."""
+        if not group_rows or prompt_len is None:
+            _lib.check(self.lib.dh_engine_set_shared_prompt(self.handle, 0, None))
+            self._shared_prompt = None
+            return
+        if not prompt_len.is_cuda or prompt_len.dtype != torch.int32 or not prompt_len.is_contiguous() or prompt_len.dim() != 1:
+            raise TypeError("set_shared_prompt takes the prompt lengths as a contiguous 1-D int32 tensor on the GPU")
+        _lib.check(self.lib.dh_engine_set_shared_prompt(self.handle, int(group_rows), prompt_len.data_ptr()))
+        self._shared_prompt = (int(group_rows), prompt_len)
+
     def _check_logprobs(self, tokens: torch.Tensor) -> None:
         buf = getattr(self, "_logprobs", None)
         assert buf is None or tuple(buf.shape) == tuple(tokens.shape), "the logprobs buffer must have the shape of tokens"

@@ -86,6 +86,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     answers, every record gains 'samples', one {'text', 'sum_logprob', 'avg_logprob', 'finish_reason', 'key'} per candidate in sample
     order ('key' is its selection key: the score, or the mbr risk), and 'selected', the chosen index; 'logprobs', 'finish_reason' and
     the alternatives, where asked for, are the chosen candidate's.
+    A generate_fn with a true attribute `shared_prompt` (--share_prompt_kv: its decode steps read an utterance's prompt tiles once for
+    its candidates or beams) gives every record 'shared_prompt': true.
     Returns corpus metrics on every rank and predictions on
     rank 0."""
     mine = shard_indices(len(examples), rank, world)
@@ -142,6 +144,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["penalties"] = dict(generate_fn.penalties)
             if getattr(generate_fn, "activations", "fp8") != "fp8":
                 preds[i]["activations"] = str(generate_fn.activations)
+            if getattr(generate_fn, "shared_prompt", False):
+                preds[i]["shared_prompt"] = True
             if getattr(generate_fn, "bias", None):
                 from .bias import bias_hits
                 preds[i]["bias"] = dict(generate_fn.bias)
@@ -391,6 +395,9 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     ngram = int(getattr(args, "no_repeat_ngram", 0) or 0)
     # --beam_history device: the beams' histories on the device; the default run passes no keyword at all
     hkw = dict(history="device") if getattr(args, "beam_history", "host") == "device" else {}
+    # --share_prompt_kv: likewise
+    shared_kv = bool(getattr(args, "share_prompt_kv", False))
+    shkw = dict(shared_prompt=True) if shared_kv else {}
     stop = stop_from_args(args, tokenizer, model.config.padded_vocab_size, model.transformer.wte.weight.device)
     skw = dict(stop=stop, return_state=True) if stop is not None else {}       # the reasons are read from the state's done flags
     from .penalty import record as penalty_record
@@ -421,12 +428,12 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
                                      prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask,
-                                     no_repeat_ngram=ngram, stop=stop, **hkw)
+                                     no_repeat_ngram=ngram, stop=stop, **hkw, **shkw)
             return {"beams": hyps, "logprobs": want_lp}
         if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
             cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
                                  prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, token_mask=mask,
-                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw, **akw)
+                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw, **akw, **shkw)
             return {"samples": cands, "select": how, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
@@ -456,6 +463,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.penalties = penalties
     gen.activations = getattr(model, "activation_format", "fp8")
     gen.bias, gen.bias_entries = bias_rec, bias_entries
+    gen.shared_prompt = shared_kv
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams // n_samples), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -554,6 +562,11 @@ def build_parser():
                         "sum_logprob, avg_logprob, finish_reason and the selection key of every candidate) and selected, the chosen "
                         "index; --schedule batch only, not with --num_beams or --speculate.  Default 1: the path it always was (the "
                         "effect on a real corpus's WER is unmeasured)")
+    p.add_argument("--share_prompt_kv", action="store_true",
+                   help="with --num_samples N > 1 or --num_beams W > 1: the decode steps' attention reads an utterance's whole 32-key "
+                        "prompt tiles once per block of its N (or W) rows instead of once per row (shared-prompt attention; the same "
+                        "bits, so the same predictions); every record gains shared_prompt: true; not with --quantize fp8 or mxfp4.  "
+                        "Default off: the launches it always made")
     p.add_argument("--select", choices=("avg_logprob", "sum_logprob", "mbr"), default=None,
                    help="with --num_samples N > 1: the candidate kept — the highest avg_logprob (the default) or sum_logprob, or mbr: "
                         "the candidate with the lowest word edit distance to the other N - 1, each standing in as a reference (minimum "
@@ -672,6 +685,13 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                 p.error(f"--num_samples {args.num_samples} does not go with {flag}: {why}")
         if args.select is None:
             args.select = "avg_logprob"
+    if args.share_prompt_kv:
+        if args.num_samples < 2 and args.num_beams < 2:
+            p.error("--share_prompt_kv goes with --num_samples N > 1 or --num_beams W > 1: one decode row per utterance shares its "
+                    "prompt with nobody")
+        if fp8_path:
+            p.error(f"--share_prompt_kv does not go with --quantize {args.quantize}: an fp8 engine's step does not run the streaming "
+                    "layers that launch the shared-prompt attention kernel")
     if not 0 <= args.no_repeat_ngram <= 8:
         p.error(f"--no_repeat_ngram {args.no_repeat_ngram}: N is 0 (off) or 1..8")
     dev_hist = args.beam_history == "device"                # the beams' histories on the device lift the next two refusals

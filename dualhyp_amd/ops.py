@@ -967,6 +967,38 @@ def attn_verify_fused(qkv32: torch.Tensor, qkv_dim: int, lora_b: Optional[torch.
     return y
 
 
+def check_shared_rows(n_rows: int, group_rows, name: str = "attn_decode_shared") -> int:
+    """group_rows of a shared-prompt attention call over n_rows rows, or a ValueError."""
+    if isinstance(group_rows, bool) or not isinstance(group_rows, int) or not 2 <= group_rows <= 8:
+        raise ValueError(f"{name}: group_rows is the number of rows that share a prompt, an int in 2..8, not {group_rows!r}")
+    if n_rows <= 0 or n_rows % group_rows:
+        raise ValueError(f"{name}: {n_rows} rows are not group_rows = {group_rows} per utterance")
+    return group_rows
+
+
+def attn_decode_shared(qkv32: torch.Tensor, qkv_dim: int, lora_b: Optional[torch.Tensor], lora_scale: float,
+                       splits: Tuple[int, int], cos: torch.Tensor, sin: torch.Tensor, seq_slot: torch.Tensor,
+                       kv_len: torch.Tensor, k_cache: torch.Tensor, vT_cache: torch.Tensor, n_head: int, group_rows: int,
+                       prompt_len: torch.Tensor, pairs: bool = True) -> torch.Tensor:
+    """`attn_decode_fused` over rows that share prompts (include/dualhyp_hip.h, "Shared-prompt attention"): rows u * group_rows + j
+    are the candidates or beams of utterance u, prompt_len int32 [n_seq / group_rows] on the GPU; the whole prompt tiles are read
+    once per block, from the slot of the utterance's row 0.  Same bits and caches as attn_decode_fused; dh_attn_decode_shared_bf16."""
+    k = _Keep()
+    n_part, n_seq, ld = qkv32.shape
+    N = check_shared_rows(n_seq, group_rows)
+    if (not isinstance(prompt_len, torch.Tensor) or prompt_len.dtype != torch.int32 or prompt_len.dim() != 1
+            or prompt_len.numel() != n_seq // N or not prompt_len.is_contiguous()):
+        raise ValueError(f"attn_decode_shared: prompt_len is a contiguous 1-D int32 tensor of {n_seq // N} utterances")
+    n_groups, s_max, hs = k_cache.size(1), k_cache.size(2), k_cache.size(3)
+    y = torch.empty((n_seq, n_head * hs), dtype=torch.bfloat16, device=qkv32.device)
+    i32 = torch.int32
+    check(_lib.load().dh_attn_decode_shared_bf16(_p(qkv32), n_part, int(pairs), n_seq, qkv_dim, ld - qkv_dim, _p(lora_b),
+                                                 float(lora_scale), splits[0], splits[1], k(cos), k(sin),
+                                                 k(seq_slot, i32), k(kv_len, i32), _p(k_cache), _p(vT_cache),
+                                                 _p(y), n_head, n_groups, hs, s_max, N, k(prompt_len, i32), _stream()))
+    return y
+
+
 def kcache_to_plain(kc: torch.Tensor) -> torch.Tensor:
     """K cache [slot, group, s_max, hs] as stored (MFMA-fragment order, csrc/common.h kfrag_off)
     -> plain [slot, group, key, channel].  Test/debug helper."""

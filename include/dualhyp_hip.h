@@ -36,7 +36,8 @@ typedef uint16_t dh_bf16;
  * and min-p sampling); dh_engine_fork_slots (sampled candidates); dh_sample_bf16_penalty, dh_sample_rows_bf16_penalty and
  * dh_engine_set_penalties (penalties); dh_sample_bf16_bias, dh_sample_rows_bf16_bias and dh_engine_set_bias (contextual biasing);
  * dh_beam_select_bf16_hist and dh_engine_set_beam_history (beam histories); dh_sample_bf16_automaton, dh_sample_rows_bf16_automaton and
- * dh_engine_set_automaton (automaton constraints). */
+ * dh_engine_set_automaton (automaton constraints); dh_attn_decode_shared_bf16, dh_attn_shared_launch_count and
+ * dh_engine_set_shared_prompt (shared-prompt attention). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -234,6 +235,33 @@ int dh_attn_verify_fused_bf16(const float* qkv32, int n_part, int pairs, int n_s
                               const int32_t* kv_len, dh_bf16* k_cache, dh_bf16* vT_cache,
                               dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max,
                               void* stream);
+
+/* ------------------------------------------------------------------ Shared-prompt attention
+ * dh_attn_decode_fused_bf16 for rows that share a prompt: the N = group_rows (2 .. 8) rows u * N + j of utterance u — sampled
+ * candidates ("Sampled candidates" below) or beams ("Beam search") — whose KV slots hold the same bytes in the whole 32-key tiles of
+ * the prompt.  DEFINITION: y and both caches after the call are those of dh_attn_decode_fused_bf16 with the same arguments, bit
+ * for bit.  What changes is what is read: with n_sh = prompt_len[u] / 32 (prompt_len: DEVICE int32 [n_seq / N], the array
+ * dh_engine_fork_slots takes; kv_len stays per row),
+ *   - tiles t < n_sh are read once per block, from the slot of the utterance's row 0 (seq_slot[u * N]), for all of the block's rows;
+ *     the other rows' copies of those tiles are never loaded;
+ *   - tiles t >= n_sh (the partial last prompt tile and the generated keys) are read from each row's own slot and masked to
+ *     key < kv_len - 1 for that row's columns and to nothing for every other column.
+ * Column layout: a block serves one KV group and up to Gs = 32 / (n_head / n_groups) consecutive rows of one utterance, row jj's
+ * head h in query column jj * (n_head / n_groups) + h of the 32-column MFMA the single-token kernel pays for anyway (N > Gs: several
+ * blocks per utterance and group).  It holds by construction: a column's arithmetic never reads another column; tile t goes to wave
+ * t % 8, ascending within a wave, as in the single-token kernel; a tile in which a column sees no key leaves its running maximum,
+ * sum and accumulator unchanged; each row finishes, rotates and appends its own q / k / v at its own position and merges its own key
+ * at the combine.  The caller keeps prompt_len[u] <= kv_len - 1 of every row of u and the rows' tiles < n_sh equal.
+ * Refused: group_rows outside 2 .. 8, n_seq % group_rows != 0, a null prompt_len, and what dh_attn_decode_fused_bf16 refuses.
+ * Added under ABI 6. */
+int dh_attn_decode_shared_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
+                               const dh_bf16* lora_b, float lora_scale, int split0, int split1,
+                               const dh_bf16* cos, const dh_bf16* sin, const int32_t* seq_slot,
+                               const int32_t* kv_len, dh_bf16* k_cache, dh_bf16* vT_cache,
+                               dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int group_rows,
+                               const int32_t* prompt_len, void* stream);
+/* Test hook: launches of the shared-prompt attention kernel this process has issued or captured so far. */
+int64_t dh_attn_shared_launch_count(void);
 
 /* ------------------------------------------------------------------ LoRA fine-tune backward
  * finetune/ger.py:278-285 `fabric.backward(loss / accum)` for the frozen-base / LoRA-only case: the dX
@@ -1285,6 +1313,19 @@ int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const int32_t* st
  * dh_engine_decode_beam refuse, and a decode call refuses an eos_id outside [0, vocab) or a sequence count other than the spec's n_seq.
  * Refused like dh_sample_bf16_automaton. */
 int dh_engine_set_automaton(dh_engine* e, const dh_automaton_spec* automaton, const int32_t* start);
+/* Shared-prompt attention (see above; group_rows = 0 or a null d_prompt_len turns it off, the default) for later dh_engine_decode and
+ * dh_engine_decode_beam calls: their rows u * group_rows + j are the candidates or beams of utterance u, in slots that
+ * dh_engine_fork_slots or dh_engine_copy_prefix has filled from slot u * group_rows, and d_prompt_len is the DEVICE int32
+ * [n_seq / group_rows] array of the utterances' prompt lengths.  While set, the step's layers launch dh_attn_decode_shared_bf16 where
+ * they launched dh_attn_decode_fused_bf16; every other launch of the step, and every bit it produces, is unchanged.  (group_rows,
+ * d_prompt_len) is part of the captured step's key: with it unset a decode call runs the graphs it always ran.  The caller keeps
+ * d_prompt_len alive while set.
+ * Refused here, with the reason: group_rows outside 2 .. 8; an fp8 or MXFP4 engine (its step does not run the streaming layers) and an
+ * fp8 KV cache; the CPU rsqrt emulation; dh_set_tuning key 10 (steps moved to the tiled kernels by row count).  Refused by the calls
+ * while it is set, for the same reasons and: dh_engine_decode_spec (a verify step's rows are positions of one sequence),
+ * dh_engine_decode_rows (a row list names any sequence in any slot), a row count that is no multiple of group_rows or above the
+ * streaming step's 2048, and a beam call whose W is not group_rows. */
+int dh_engine_set_shared_prompt(dh_engine* e, int group_rows, const int32_t* d_prompt_len);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);

@@ -12,9 +12,16 @@ one dh_engine_copy_prefix call per utterance — five times each after a warm-up
 loop's cost is its host synchronisations; the fork's HIP-event time and the bytes it moves (every source tile read once, written
 N - 1 times) against 8 TB/s are given too.
 
+--shared_prompt: the arm for shared-prompt attention instead (include/dualhyp_hip.h; sample_batch(shared_prompt=True)).  Same shape,
+same regions, same alternation, per N in one process: sample_batch without and with the flag — equal ids (digest), decode_ms of every
+region and the median of each — and then the attention launch by itself at that shape: ops.attn_decode_fused against
+ops.attn_decode_shared on one layer's caches (rows decode rows, 8 pair-summed partials + LoRA, every row half-way through its budget),
+HIP events around 20 launches each, alternating, three times.
+
 Every GPU run is a child process of its own under a time limit; the parent never touches the GPU.
 
     python tools/bench_samples.py [--num_samples 2 4 8] [--rows 640] [--out profiles/samples.json]
+    python tools/bench_samples.py --shared_prompt --out profiles/shared_prompt.json
 """
 import argparse
 import hashlib
@@ -37,6 +44,7 @@ ap.add_argument("--prefill_batch", type=int, default=64)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--step_timeout", type=int, default=420, help="seconds each GPU run may take")
 ap.add_argument("--out", type=str, default="", help="write the lines as one JSON file")
+ap.add_argument("--shared_prompt", action="store_true", help="the shared-prompt attention arm: sample_batch without and with shared_prompt")
 ap.add_argument("--worker", type=int, default=None, help="(child) the N of this run")
 a = ap.parse_args()
 HBM_BYTES_PER_S = 8e12
@@ -135,12 +143,106 @@ def worker(N: int) -> None:
                           fork_share_of_8TBps=round(rate / HBM_BYTES_PER_S, 3))), flush=True)
 
 
+def shared_worker(N: int) -> None:
+    import torch
+    from dualhyp_amd import GPT, Config, GER_LORA, ops, sample_batch
+    from dualhyp_amd.synth import synth_state_dict, synth_prompts
+    dev = "cuda:0"
+    cfg = Config.from_name("tiny-llama-1.1b-chat", **{**GER_LORA, "dropout": 0.0})
+    m = GPT(cfg).to(device=dev, dtype=torch.bfloat16)
+    m.load_state_dict(synth_state_dict(cfg, seed=1337, device=dev, embed_scale=50.0, head_tie=1.0), strict=True)
+    m.eval()
+    B, T, new = a.rows // N, a.prompt_len, a.max_new_tokens
+    corpus = [p.to(dev) for p in synth_prompts(B, T, cfg.padded_vocab_size, seed=7)]
+    kw = dict(temperature=0.8, top_k=5, seed=1337, prefill_batch=a.prefill_batch)
+
+    def digest(rows) -> str:
+        h = hashlib.sha256()
+        for r in rows:
+            h.update(r.cpu().numpy().tobytes())
+        return h.hexdigest()[:16]
+
+    def call(shared):
+        return lambda tm: digest(s["tokens"] for ss in sample_batch(m, corpus, new, num_samples=N, timing=tm, shared_prompt=shared, **kw) for s in ss)
+
+    calls = {"unshared": call(False), "shared": call(True)}
+    ids = {name: c(None) for name, c in calls.items()}            # warm-up: allocation, graph capture of both steps
+    torch.cuda.synchronize()
+    assert ids["unshared"] == ids["shared"], "shared_prompt changed the sampled ids"
+    runs = {name: [] for name in calls}
+    for _ in range(a.repeats):
+        for name, c in calls.items():
+            tm = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c(tm)
+            torch.cuda.synchronize()
+            runs[name].append((time.perf_counter() - t0, tm))
+    line = dict(step="sample_batch_shared_prompt_vs_unshared", num_samples=N, utterances=B, rows=B * N, prompt_len=T, max_new_tokens=new,
+                ids_sha256=ids["shared"])
+    for name in calls:
+        dec = [t["decode_ms"] for _, t in runs[name]]
+        walls = [w for w, _ in runs[name]]
+        steps = runs[name][0][1]["decode_steps"]
+        line[name] = dict(decode_ms=round(statistics.median(dec), 2), decode_ms_regions=[round(x, 2) for x in dec], decode_steps=steps,
+                          step_ms=round(statistics.median(dec) / steps, 4), utt_per_s=round(B / statistics.median(walls), 1),
+                          utt_per_s_regions=[round(B / w, 1) for w in walls])
+    line["shared_over_unshared_decode_ms"] = round(line["shared"]["decode_ms"] / line["unshared"]["decode_ms"], 4)
+    print(json.dumps(line), flush=True)
+    del m
+    torch.cuda.empty_cache()
+
+    # the attention launch by itself: one layer's caches at the same shape, every row half-way through its budget
+    H, G, hs, R = cfg.n_head, cfg.n_query_groups, cfg.head_size, B * N
+    s_max = -(-(T + new) // 64) * 64
+    qkv_dim = (H + 2 * G) * hs
+    g = torch.Generator(device=dev).manual_seed(1)
+    r = lambda *sh: torch.randn(*sh, device=dev, generator=g).bfloat16()
+    kc, vt = r(R, G, s_max, hs), r(R, G, hs, s_max)
+    # the fork: every row's slot holds its utterance's whole prompt tiles (hs * 32 elements each, back to back in a (slot, group) block)
+    n_pre = (T // 32) * 32 * hs
+    for c in (kc, vt):
+        v = c.view(B, N, G, -1)
+        v[:, 1:, :, :n_pre] = v[:, :1, :, :n_pre]
+    cos, sin = r(s_max, hs), r(s_max, hs)
+    q32 = torch.randn(4, R, qkv_dim + 48, device=dev, generator=g) * 0.3       # d = 2048: 8 K-slices, handed over as 4 pair sums
+    bq = (torch.randn(qkv_dim, 16, device=dev, generator=g) * 0.05).bfloat16()
+    slot = torch.arange(R, dtype=torch.int32, device=dev)
+    kv_len = torch.full((R,), T + new // 2 + 1, dtype=torch.int32, device=dev)
+    plen = torch.full((B,), T, dtype=torch.int32, device=dev)
+    args = (q32, qkv_dim, bq, 2.0, (H * hs, (H + G) * hs), cos, sin, slot, kv_len, kc, vt, H)
+    ops_ = {"unshared": lambda: ops.attn_decode_fused(*args, pairs=False),
+            "shared": lambda: ops.attn_decode_shared(*args, N, plen, pairs=False)}
+    y = {name: fn() for name, fn in ops_.items()}
+    torch.cuda.synchronize()
+    assert torch.equal(y["unshared"], y["shared"]), "the shared launch differs from the unshared one"
+    us = {name: [] for name in ops_}
+    n_launch = 20
+    for _ in range(a.repeats):
+        for name, fn in ops_.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n_launch):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[name].append(e0.elapsed_time(e1) * 1e3 / n_launch)
+    q_per_kv = H // G
+    Gs = 32 // q_per_kv
+    line = dict(step="attention_launch_shared_vs_unshared", num_samples=N, rows=R, kv_len=int(kv_len[0]), prompt_len=T, n_head=H, n_groups=G,
+                head_size=hs, blocks_unshared=R * G, blocks_shared=B * -(-N // Gs) * G, rows_per_block=min(N, Gs),
+                unshared_us=round(statistics.median(us["unshared"]), 2), unshared_us_regions=[round(x, 2) for x in us["unshared"]],
+                shared_us=round(statistics.median(us["shared"]), 2), shared_us_regions=[round(x, 2) for x in us["shared"]])
+    line["shared_over_unshared_us"] = round(line["shared_us"] / line["unshared_us"], 4)
+    print(json.dumps(line), flush=True)
+
+
 if a.worker is not None:
-    worker(a.worker)
+    (shared_worker if a.shared_prompt else worker)(a.worker)
 else:
     lines = []
     for N in a.num_samples:
-        cmd = [sys.executable, str(Path(__file__).resolve()), "--worker", str(N)]
+        cmd = [sys.executable, str(Path(__file__).resolve()), "--worker", str(N)] + (["--shared_prompt"] if a.shared_prompt else [])
         for k in ("rows", "prompt_len", "max_new_tokens", "prefill_batch", "repeats"):
             cmd += [f"--{k}", str(getattr(a, k))]
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=a.step_timeout)      # a run that fails ends the tool
