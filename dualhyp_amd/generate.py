@@ -9,6 +9,7 @@ device state back once at the end instead of once per token (generate/base.py:79
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -52,16 +53,6 @@ def _shared_prefix(model: GPT, prompts: Sequence[torch.Tensor], share_prefix: Un
     return shared_prefix_len([p.to(dev).reshape(-1) for p in prompts])
 
 
-def _check_top_logprobs(model: GPT, top_logprobs, return_logprobs: bool) -> int:
-    """K of a call (0: off), refused before anything is launched: an int in 0 .. min(8, vocab), and K > 0 only beside return_logprobs."""
-    K = ops.check_top_logprobs(top_logprobs)
-    if K:
-        ops.check_top_logprobs(K, model.config.padded_vocab_size)
-    if K and not return_logprobs:
-        raise ValueError(f"top_logprobs={K} needs return_logprobs=True: the alternatives are returned beside the tokens' own log-probabilities")
-    return K
-
-
 def _token_mask(model: GPT, token_mask, n: int, need: int, dev) -> Optional[torch.Tensor]:
     """The call's token mask on the device, checked before anything is launched (constrain.check_mask: one read-back), or None.
     token_mask: an int32 [n, ceil(vocab / 32)] tensor on the model's device, or a list of n id lists, packed here."""
@@ -89,11 +80,6 @@ def _forward_prefix(eng, prompt: torch.Tensor, P: int, slot: int, other_slots: S
         eng.copy_prefix(slot, list(other_slots), P)
 
 
-def _penalty_kw(pen) -> dict:
-    """The sampling ops' keywords of a checked triple (none when it is off)."""
-    return dict(repetition_penalty=pen[0], frequency_penalty=pen[1], presence_penalty=pen[2]) if pen else {}
-
-
 def _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate: int = 0):
     """The checked (repetition, frequency, presence) of a call, or None when all three are off.  Needs nothing but the arguments."""
     pen = _penalty.check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
@@ -105,14 +91,9 @@ def _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, sp
     return pen
 
 
-def _bias_kw(bias) -> dict:
-    """The sampling ops' keyword of a compiled bias (none when it is off)."""
-    return dict(bias=bias) if bias is not None else {}
-
-
 def _check_bias(bias, speculate: int = 0):
     """`bias=` looked at before the model is touched: its type, and what it does not go with.  Needs nothing but the arguments; the
-    entries themselves are checked against the model's vocabulary by _compile_bias."""
+    entries themselves are checked against the model's vocabulary by bias.as_spec."""
     if bias is None or (isinstance(bias, (list, tuple)) and len(bias) == 0):
         return None
     if not isinstance(bias, (_bias.BiasSpec, list, tuple)):
@@ -120,21 +101,6 @@ def _check_bias(bias, speculate: int = 0):
     if speculate:
         raise ValueError(f"speculate={speculate} does not go with a bias of {len(bias)} entries: {_bias.SPEC_REFUSAL}")
     return bias
-
-
-def _compile_bias(model, bias, pen, tok_ld: int, dev):
-    """The call's BiasSpec on the model's device (None: off), with the limit it shares with the penalties checked."""
-    if bias is None:
-        return None
-    spec = _bias.as_spec(bias, model.config.padded_vocab_size, dev)
-    if spec is not None and pen:
-        _bias.check_tables(tok_ld, spec.n_ids)
-    return spec
-
-
-def _automaton_kw(aut) -> dict:
-    """The sampling ops' keyword of a call's automaton set (none when it is off)."""
-    return dict(automaton=aut) if aut is not None else {}
 
 
 def _check_automaton(automaton, speculate: int = 0):
@@ -150,67 +116,197 @@ def _check_automaton(automaton, speculate: int = 0):
 
 
 @contextlib.contextmanager
-def _decode_settings(eng, lp_buf, top_buf, mask, ngram: int, start, stop, top_p: float, min_p: float, pen=None, bias=None, aut=None):
-    """What a call hands the engine for its captured decode steps, each only where the call uses it — every one is part of a captured
-    step's key, so without it the call runs the steps it always ran — and takes back behind them: the buffers are the call's."""
-    nuc = top_p < 1.0 or min_p > 0.0
-    if lp_buf is not None:
-        eng.set_logprobs(lp_buf)
-    if top_buf is not None:
-        eng.set_top_logprobs(*top_buf)
-    if mask is not None:
-        eng.set_token_mask(mask)
-    if ngram:
-        eng.set_no_repeat_ngram(ngram, start)
-    if stop is not None:
-        eng.set_stop(stop, start)
-    if nuc:
-        eng.set_nucleus(top_p, min_p)
-    if pen:
-        eng.set_penalties(*pen, start=start)
-    if bias is not None:
-        eng.set_bias(bias, start)
-    if aut is not None:
-        eng.set_automaton(aut, start)
+def _engine_settings(settings, take_back=None):
+    """What a call hands the engine for its captured decode steps, and takes back behind them: the buffers are the call's.  settings:
+    (on, set, reset) triples, set in their order and reset in take_back's (None: the same), each only where the call uses it — every
+    one is part of a captured step's key, so without it the call runs the steps it always ran."""
+    for on, set_, _ in settings:
+        if on:
+            set_()
     try:
         yield
     finally:
-        if aut is not None:
-            eng.set_automaton()
-        if bias is not None:
-            eng.set_bias()
-        if pen:
-            eng.set_penalties()
-        if lp_buf is not None:
-            eng.set_logprobs(None)
-        if top_buf is not None:
-            eng.set_top_logprobs(None)
-        if mask is not None:
-            eng.set_token_mask(None)
-        if ngram:
-            eng.set_no_repeat_ngram(0)
-        if stop is not None:
-            eng.set_stop(None)
-        if nuc:
-            eng.set_nucleus(None, None)
+        for on, _, reset in settings if take_back is None else take_back:
+            if on:
+                reset()
 
 
-def _decode_steps(eng, tokens, length, done, n: int, temperature, top_k, eos_id, seed, early: bool) -> int:
-    """n single-token steps over every row of `tokens` (eng.decode); the steps issued.  early (an EOS or a stop specification can end
-    a sequence): the loop is issued EOS_CHECK_EVERY steps at a time and ends once every sequence has finished
-    (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens, inference/ger.py:71, and a correction is
-    usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps."""
-    if not early:
-        eng.decode(tokens, length, done, n, temperature, top_k, eos_id, seed, first_step=0)
-        return n
+def _shared_prompt_setting(eng, on: bool, rows_per_utt: int, plen: torch.Tensor):
+    """Shared-prompt attention for the decode steps of a call, as an entry of _engine_settings."""
+    return on, lambda: eng.set_shared_prompt(rows_per_utt, plen), lambda: eng.set_shared_prompt()
+
+
+@dataclasses.dataclass
+class _Picks:
+    """The pick options of one call, in one place for its three consumers: the first pick (kw), the captured decode steps (engine) and
+    the returned state (state).  check() builds it from the arguments alone; compile() puts the model and the call's shape to it."""
+    want_logprobs: bool
+    K: int                                  # top_logprobs
+    mask: object                            # token_mask as given; compiled: the int32 mask, a row per decode row, or None
+    ngram: int
+    stop: object                            # as given; compiled: a StopSpec on the device, or None
+    top_p: float
+    min_p: float
+    pen: Optional[tuple]                    # (repetition, frequency, presence), None: all three off
+    bias: object                            # as given; compiled: a BiasSpec on the device, or None
+    aut: object                             # as given; compiled: the AutomatonSet on the device, a start state per decode row, or None
+    lp_buf: Optional[torch.Tensor] = None   # compile(): float32 [rows, tok_ld] beside the token buffer, NaN where no token was produced
+    top_buf: Optional[tuple] = None         # compile(): _top_buffers
+    start: Optional[torch.Tensor] = None    # compile(): the rows' prompt lengths, where an option reads a row's generated text
+
+    @classmethod
+    def check(cls, *, speculate: int = 0, return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
+              stop=None, top_p=None, min_p=None, repetition_penalty=None, frequency_penalty=None, presence_penalty=None, bias=None,
+              automaton=None) -> "_Picks":
+        """Stage one: what the arguments alone decide, refused before the model is touched."""
+        pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
+        bias = _check_bias(bias, speculate)
+        automaton = _check_automaton(automaton, speculate)
+        top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
+        K = ops.check_top_logprobs(top_logprobs)
+        if K and not return_logprobs:
+            raise ValueError(f"top_logprobs={K} needs return_logprobs=True: the alternatives are returned beside the tokens' own log-probabilities")
+        return cls(bool(return_logprobs), K, token_mask, _ngram.check_ngram(no_repeat_ngram), stop, top_p, min_p, pen, bias, automaton)
+
+    def compile(self, model: GPT, lens: Sequence[int], tok_ld: int, dev, eos_id, repeat: int = 1, dummy: bool = False) -> "_Picks":
+        """Stage two: the options checked against the model and compiled for the call's len(lens) sequences, and the buffers of its
+        decode rows — `repeat` rows per sequence (sample_batch's candidates), and with `dummy` one row more, generate_stream's dummy
+        sequence of one token, which never picks."""
+        n = len(lens)
+        # only an option that is on asks the model for its vocabulary; token_mask asks in _token_mask
+        uses_vocab = self.K or self.ngram or self.pen or any(o is not None for o in (self.bias, self.aut, self.stop))
+        vocab = model.config.padded_vocab_size if uses_vocab else None
+        if self.K:
+            ops.check_top_logprobs(self.K, vocab)
+        if self.ngram:
+            _ngram.check_ngram(self.ngram, vocab)
+        if self.pen:
+            _penalty.check_history(tok_ld, vocab)
+        self.bias = _bias.as_spec(self.bias, vocab, dev)
+        if self.bias is not None and self.pen:
+            _bias.check_tables(tok_ld, self.bias.n_ids)
+        self.aut = _automaton.as_set(self.aut, n, vocab, dev, eos_id)
+        self.mask = _token_mask(model, self.mask, n, 1, dev)
+        self.stop = _stop.as_spec(self.stop, vocab, dev)
+        if self.aut is not None and (repeat > 1 or dummy):
+            # a start state and a state per decode row; the dummy's is valid, and a refilled row starts over by itself: its sequence
+            # has generated nothing, so its pick reads the start state
+            self.aut = self.aut.padded() if dummy else self.aut.repeat(repeat)
+        if self.mask is not None and repeat > 1:
+            self.mask = self.mask.repeat_interleave(repeat, dim=0).contiguous()
+        if self.mask is not None and dummy:     # an all-ones row
+            self.mask = torch.cat([self.mask, torch.full_like(self.mask[:1], -1)]).contiguous()
+        row_lens = [t for t in lens for _ in range(repeat)] + [1] * dummy
+        if self.want_logprobs:
+            self.lp_buf = torch.full((len(row_lens), tok_ld), float("nan"), dtype=torch.float32, device=dev)
+        if self.K:
+            self.top_buf = _top_buffers((len(row_lens), tok_ld), self.K, dev)
+        # the ban's and the penalties' history, and a stop sequence's, a bias entry's or the automaton's text, begin behind the prompt
+        if self.ngram or self.pen or self.bias is not None or self.aut is not None or (self.stop is not None and self.stop.sequences):
+            self.start = torch.tensor(row_lens, dtype=torch.int32, device=dev)
+        return self
+
+    def kw(self) -> dict:
+        """The keywords of the call's first picks (ops.sample, ops.sample_rows)."""
+        pen = self.pen or (None, None, None)
+        return dict(logprobs=self.lp_buf, top_logprobs=self.top_buf, mask=self.mask, no_repeat_ngram=self.ngram, start=self.start,
+                    stop=self.stop, top_p=self.top_p, min_p=self.min_p, repetition_penalty=pen[0], frequency_penalty=pen[1],
+                    presence_penalty=pen[2], bias=self.bias, automaton=self.aut)
+
+    def engine(self, eng, inner=()):
+        """The same options on the engine for the captured steps inside the `with` (_engine_settings), and `inner`, further settings
+        of the call, inside them.  The three readers of a row's generated text are taken back first, then the others in the order
+        they were set."""
+        plain = [(self.lp_buf is not None, lambda: eng.set_logprobs(self.lp_buf), lambda: eng.set_logprobs(None)),
+                 (self.top_buf is not None, lambda: eng.set_top_logprobs(*self.top_buf), lambda: eng.set_top_logprobs(None)),
+                 (self.mask is not None, lambda: eng.set_token_mask(self.mask), lambda: eng.set_token_mask(None)),
+                 (self.ngram, lambda: eng.set_no_repeat_ngram(self.ngram, self.start), lambda: eng.set_no_repeat_ngram(0)),
+                 (self.stop is not None, lambda: eng.set_stop(self.stop, self.start), lambda: eng.set_stop(None)),
+                 (self.top_p < 1.0 or self.min_p > 0.0, lambda: eng.set_nucleus(self.top_p, self.min_p), lambda: eng.set_nucleus(None, None))]
+        text = [(self.pen, lambda: eng.set_penalties(*self.pen, start=self.start), lambda: eng.set_penalties()),
+                (self.bias is not None, lambda: eng.set_bias(self.bias, self.start), lambda: eng.set_bias()),
+                (self.aut is not None, lambda: eng.set_automaton(self.aut, self.start), lambda: eng.set_automaton())]
+        inner = list(inner)
+        return _engine_settings(plain + text + inner, inner[::-1] + text[::-1] + plain)
+
+    def state(self, n: Optional[int] = None) -> dict:
+        """The entries of a return_state dict: the call's buffers, or their first n rows."""
+        rows = (lambda t: t) if n is None else (lambda t: t[:n])
+        st = {}
+        if self.lp_buf is not None:
+            st["logprobs"] = rows(self.lp_buf)
+        if self.top_buf is not None:
+            st["top_ids"], st["top_logprobs"] = rows(self.top_buf[0]), rows(self.top_buf[1])
+        if self.aut is not None:
+            st["automaton_state"] = rows(self.aut.state)
+        return st
+
+
+def _prompt_shape(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, prefill_batch: int):
+    """(lens, T_max, need_pos, chunks) of a call: the prompt lengths, the longest, the last position a sequence writes, and the
+    (first, behind-last) prompt indices of its prefills of prefill_batch prompts."""
+    lens = [int(p.numel()) for p in prompts]
+    T_max = max(lens)
+    need_pos = T_max + max_new_tokens - 1
+    if model.max_seq_length < need_pos:
+        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
+    return lens, T_max, need_pos, [(c, min(c + prefill_batch, len(lens))) for c in range(0, len(lens), prefill_batch)]
+
+
+def _prefill(eng, prompts, lens, chunks, P: int, slots: Sequence[int], dev, whole=None) -> torch.Tensor:
+    """The prompts into KV slots `slots`, a chunk at a time, behind their P shared tokens, which go through the layers once: the
+    last-position logits, bf16 [len(prompts), vocab].  whole(packed, a, b): how the call forwards a chunk of prompts that share
+    nothing (None: by forward_slots, as it forwards what follows a prefix)."""
+    last = torch.empty((len(prompts), eng.vocab), dtype=torch.bfloat16, device=dev)
+    if P:
+        _forward_prefix(eng, prompts[0], P, slots[0], slots[1:])
+    for a, b in chunks:
+        packed = torch.cat([p.to(dev).reshape(-1)[P:] for p in prompts[a:b]])
+        if P or whole is None:      # prompt_phase: a chunk of one-token remainders is still a piece of a prompt forward, not a decode step
+            last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], slots[a:b], prompt_phase=bool(P), pos0=P)
+        else:
+            last[a:b] = whole(packed, a, b)
+    return last
+
+
+def _decode(eng, picks: _Picks, step, done: torch.Tensor, n: int, early: bool, inner=()) -> int:
+    """The decode phase of a call: n steps under the call's settings, issued by step(count, first_step); the steps issued.  early (an
+    EOS or a stop specification can end a sequence, or a verify step yields several tokens): issued EOS_CHECK_EVERY at a time, until
+    every sequence has finished (generate/base.py:79-80 returns at the EOS; the harness asks for up to 150 tokens,
+    inference/ger.py:71, and a correction is usually 20-40): one 4-byte read-back per chunk instead of up to 5x the steps."""
     steps_run = 0
-    while steps_run < n:
-        c = min(EOS_CHECK_EVERY, n - steps_run)
-        eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=steps_run)
-        steps_run += c
-        if steps_run < n and bool((done != 0).all()):
-            break
+    with picks.engine(eng, inner):
+        while steps_run < n:
+            c = min(EOS_CHECK_EVERY, n - steps_run) if early else n
+            step(c, steps_run)
+            steps_run += c
+            if steps_run < n and bool((done != 0).all()):
+                break
     return steps_run
+
+
+def _add_timing(timing: dict, **amounts) -> None:
+    """The amounts of one call onto the keys of a timing dict that several calls share."""
+    for key, v in amounts.items():
+        timing[key] = timing.get(key, 0) + v
+
+
+def _row_result(r: int, n_prompt: int, length_h, done_h, max_new_tokens: int, tokens, lp_buf, top_buf, lo: int = 0):
+    """Row r of a finished call out of its buffers, as views (640 clone launches per 20-batch group otherwise): its tokens from place
+    `lo`, cut before an EOS (generate/base.py:80 returns idx[:input_pos]), and what was produced, the EOS included — the
+    log-probabilities and the alternatives, None where the call keeps none (lp_buf, top_buf None)."""
+    end = min(length_h[r], n_prompt + max_new_tokens)
+    return (tokens[r, lo:end - 1 if done_h[r] == 1 else end], None if lp_buf is None else lp_buf[r, n_prompt:end],
+            None if top_buf is None else tuple(t[r, n_prompt:end] for t in top_buf))
+
+
+def _batch_result(rows, picks: _Picks, state: Optional[dict]):
+    """generate_batch's return value from its rows' results: out, or (out[, logprobs][, top][, state])."""
+    out, logprobs, top = (list(col) for col in zip(*rows))
+    res = (out,) + ((logprobs,) if picks.lp_buf is not None else ()) + ((top,) if picks.top_buf is not None else ())
+    if state is not None:
+        res += (state,)
+    return res if len(res) > 1 else out
 
 
 def _token_buffer(prompts, lens, tok_ld: int, dev) -> torch.Tensor:
@@ -334,32 +430,18 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p, the penalties, bias
     and fp8; speculate is refused.  return_state gains automaton_state, the int32 [B] states behind the last picks.  None (the default)
     is off: the call it always was."""
-    automaton = _check_automaton(automaton, speculate)
-    bias = _check_bias(bias, speculate)
-    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
-    top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
+    picks = _Picks.check(speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
+                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
-    K = _check_top_logprobs(model, top_logprobs, return_logprobs)
-    ngram = _ngram.check_ngram(no_repeat_ngram)
-    if ngram:
-        _ngram.check_ngram(ngram, model.config.padded_vocab_size)
     D = _check_speculate(model, speculate, top_k, B)
     if drafts is not None and (D == 0 or drafts.dtype != torch.int64 or tuple(drafts.shape) != (B, max_new_tokens)):
         raise ValueError(f"drafts goes with speculate > 0 and is a [{B}, {max_new_tokens}] int64 tensor")
-    lens = [int(p.numel()) for p in prompts]
-    T_max = max(lens)
-    need_pos = T_max + max_new_tokens - 1
-    if model.max_seq_length < need_pos:
-        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
-    if pen:
-        _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
+    lens, T_max, need_pos, chunks = _prompt_shape(model, prompts, max_new_tokens, prefill_batch)
     dev = model.transformer.wte.weight.device
-    bias = _compile_bias(model, bias, pen, T_max + max_new_tokens, dev)
-    aut = None if automaton is None else _automaton.as_set(automaton, B, model.config.padded_vocab_size, dev, eos_id)
-    mask = _token_mask(model, token_mask, B, 1, dev)
-    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
-    chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
+    tok_ld = T_max + max_new_tokens
+    picks.compile(model, lens, tok_ld, dev, eos_id)
     P = _shared_prefix(model, prompts, share_prefix, dev)
     # a verify step writes K / V up to D positions behind the last token (as far as the model has positions) and runs D + 1 rows per
     # sequence through the row workspaces; the cache keeps B slots
@@ -368,10 +450,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                        exact=B > prefill_batch)
     if D:
         eng.reserve_rows(B * (D + 1))
-    tok_ld = T_max + max_new_tokens
     tokens = _token_buffer(prompts, lens, tok_ld, dev)
-    lp_buf = torch.full((B, tok_ld), float("nan"), dtype=torch.float32, device=dev) if return_logprobs else None
-    top_buf = _top_buffers((B, tok_ld), K, dev) if K else None
     if D:   # lengths, flags and the three counters side by side: one read-back
         state = torch.cat([torch.tensor(lens, dtype=torch.int32), torch.zeros(B + 3, dtype=torch.int32)]).to(dev)
         length, done, counters = state[:B], state[B:2 * B], state[2 * B:]
@@ -380,45 +459,21 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     else:
         length = torch.tensor(lens, dtype=torch.int32, device=dev)
         done = torch.zeros(B, dtype=torch.int32, device=dev)
-    # the prompt lengths: the ban's and the penalties' history, and a stop sequence's or a bias entry's match, begin there
-    start = torch.tensor(lens, dtype=torch.int32, device=dev) \
-        if ngram or pen or bias is not None or aut is not None or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # B independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
     if ev:
         ev[0].record()
-    last = torch.empty((B, eng.vocab), dtype=torch.bfloat16, device=dev)
-    if P:
-        _forward_prefix(eng, prompts[0], P, 0, range(1, B))
-    for a, b in chunks:
-        packed = torch.cat([p.to(dev).reshape(-1)[P:] for p in prompts[a:b]])
-        if P:   # prompt_phase: a chunk of one-token remainders is still a piece of a prompt forward, not a decode step
-            last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], list(range(a, b)), prompt_phase=True, pos0=P)
-        else:
-            _, last[a:b] = eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)
-    ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, logprobs=lp_buf,
-               top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p, min_p=min_p,
-               **_penalty_kw(pen), **_bias_kw(bias), **_automaton_kw(aut))
+    last = _prefill(eng, prompts, lens, chunks, P, list(range(B)), dev,
+                    whole=lambda packed, a, b: eng.forward(packed, lens[a:b], [0] * (b - a), want_all=False, want_last=True, slot_base=a)[1])
+    ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, **picks.kw())
     if ev:
         ev[1].record()
-    # each of these is part of the captured step's key; without it the call runs the steps it always ran
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias, aut):
-        steps_run = 0
-        if max_new_tokens > 1:
-            n = max_new_tokens - 1
-            if D:
-                # a step yields 1 .. D + 1 tokens per live sequence, so at most n steps are needed; EOS_CHECK_EVERY at a time, until
-                # every sequence has met its EOS or its budget (done != 0)
-                while steps_run < n:
-                    c = min(EOS_CHECK_EVERY, n - steps_run)
-                    eng.decode_spec(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature, eos_id,
-                                    first_step=steps_run)
-                    steps_run += c
-                    if steps_run < n and bool((done != 0).all()):
-                        break
-            else:
-                steps_run = _decode_steps(eng, tokens, length, done, n, temperature, top_k, eos_id, seed,
-                                          early=eos_id is not None or stop is not None)
+    if D:   # a step yields 1 .. D + 1 tokens per live sequence, so at most max_new_tokens - 1 steps are needed
+        step = lambda c, first: eng.decode_spec(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature, eos_id,
+                                                first_step=first)
+    else:
+        step = lambda c, first: eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=first)
+    steps_run = _decode(eng, picks, step, done, max_new_tokens - 1, early=bool(D) or eos_id is not None or picks.stop is not None)
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
@@ -429,38 +484,18 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
         length_h = length.tolist()          # the one host read-back
         done_h = done.tolist()
     if ev:   # the read-back above has synchronised the stream
-        timing["prefill_ms"] = timing.get("prefill_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["decode_steps"] = timing.get("decode_steps", 0) + steps_run
-        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + B * steps_run
-        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens) - (B - 1) * P
+        _add_timing(timing, prefill_ms=ev[0].elapsed_time(ev[1]), decode_ms=ev[1].elapsed_time(ev[2]), decode_steps=steps_run,
+                    decode_row_steps=B * steps_run, prefill_tokens=sum(lens) - (B - 1) * P)
         timing["shared_prefix"] = P
-    if D and timing is not None:
-        for key, v in zip(("spec_steps", "spec_drafted", "spec_accepted"), counters_h):
-            timing[key] = timing.get(key, 0) + v
-    out: List[torch.Tensor] = []
-    for i in range(B):
-        n = min(length_h[i], lens[i] + max_new_tokens)
-        if done_h[i] == 1:
-            n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
-        out.append(tokens[i, :n])       # a view of this call's own buffer (640 clone launches per 20-batch group otherwise)
-    res = (out,)
-    if return_logprobs:                 # views too: what was produced, the EOS included
-        res += ([lp_buf[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(B)],)
-    if K:
-        res += ([tuple(t[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for t in top_buf) for i in range(B)],)
+        if D:
+            _add_timing(timing, spec_steps=counters_h[0], spec_drafted=counters_h[1], spec_accepted=counters_h[2])
+    st = None
     if return_state:
-        st = dict(tokens=tokens, length=length, done=done)
-        if return_logprobs:
-            st["logprobs"] = lp_buf
-        if K:
-            st["top_ids"], st["top_logprobs"] = top_buf
+        st = dict(tokens=tokens, length=length, done=done, **picks.state())
         if D and steps_run:             # the last verify step's drafts and the lengths they were proposed from
             st["spec_drafts"], st["spec_len"] = eng.read_spec(B, D)
-        if aut is not None:
-            st["automaton_state"] = aut.state
-        res += (st,)
-    return res if len(res) > 1 else out
+    rows = [_row_result(i, lens[i], length_h, done_h, max_new_tokens, tokens, picks.lp_buf, picks.top_buf) for i in range(B)]
+    return _batch_result(rows, picks, st)
 
 
 def check_shared_prompt(model, shared_prompt, rows_per_utt: int, what: str) -> bool:
@@ -481,18 +516,6 @@ def check_shared_prompt(model, shared_prompt, rows_per_utt: int, what: str) -> b
         raise ValueError("shared_prompt=True does not go with the CPU rsqrt emulation (cpu_rsqrt_vec_width), which flags rows by their "
                          "place in a call")
     return True
-
-
-@contextlib.contextmanager
-def _shared_prompt(eng, on: bool, rows_per_utt: int, plen: torch.Tensor):
-    """Shared-prompt attention for the decode steps inside: part of a captured step's key, taken back behind them."""
-    if on:
-        eng.set_shared_prompt(rows_per_utt, plen)
-    try:
-        yield
-    finally:
-        if on:
-            eng.set_shared_prompt()
 
 
 MAX_SAMPLES = 8           # DH_MAX_SAMPLES: the slots dh_engine_fork_slots gives an utterance, its own included
@@ -559,56 +582,29 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         raise ValueError(f"num_samples={N}: the RelPrompt decoder's prompts carry spliced reliability embeddings, which a prefill by "
                          "ids into the source slots does not hold")
     shared_prompt = check_shared_prompt(model, shared_prompt, N, f"num_samples={N}")
-    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
-    bias = _check_bias(bias)
-    automaton = _check_automaton(automaton)
-    top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
+    picks = _Picks.check(return_logprobs=True, top_logprobs=top_logprobs, token_mask=token_mask, no_repeat_ngram=no_repeat_ngram, stop=stop,
+                         top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
+                         presence_penalty=presence_penalty, bias=bias, automaton=automaton)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     R = B * N
-    K = _check_top_logprobs(model, top_logprobs, True)
-    ngram = _ngram.check_ngram(no_repeat_ngram)
-    if ngram:
-        _ngram.check_ngram(ngram, model.config.padded_vocab_size)
-    lens = [int(p.numel()) for p in prompts]
-    T_max = max(lens)
-    need_pos = T_max + max_new_tokens - 1
-    if model.max_seq_length < need_pos:
-        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
-    if pen:
-        _penalty.check_history(T_max + max_new_tokens, model.config.padded_vocab_size)
+    lens, T_max, need_pos, chunks = _prompt_shape(model, prompts, max_new_tokens, prefill_batch)
     dev = model.transformer.wte.weight.device
-    bias = _compile_bias(model, bias, pen, T_max + max_new_tokens, dev)
-    aut = None if automaton is None else _automaton.as_set(automaton, B, model.config.padded_vocab_size, dev, eos_id)
-    if aut is not None:
-        aut = aut.repeat(N)                                       # a start state and a state per decode row
-    mask = _token_mask(model, token_mask, B, 1, dev)
-    if mask is not None:
-        mask = mask.repeat_interleave(N, dim=0).contiguous()      # a row per decode row
-    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
-    chunks = [(c, min(c + prefill_batch, B)) for c in range(0, B, prefill_batch)]
+    tok_ld = T_max + max_new_tokens
+    picks.compile(model, lens, tok_ld, dev, eos_id, repeat=N)       # a mask row and a start state per utterance, serving its N rows
     P = _shared_prefix(model, prompts, share_prefix, dev)
     eng = model.engine(R, min(need_pos, -(-model.config.block_size // 64) * 64),
                        max(P, R, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)), exact=R > prefill_batch)
     row_lens = [n for n in lens for _ in range(N)]
-    tok_ld = T_max + max_new_tokens
     tokens = _token_buffer([p for p in prompts for _ in range(N)], row_lens, tok_ld, dev)
-    lp_buf = torch.full((R, tok_ld), float("nan"), dtype=torch.float32, device=dev)
-    top_buf = _top_buffers((R, tok_ld), K, dev) if K else None
     length = torch.tensor(row_lens, dtype=torch.int32, device=dev)
     done = torch.zeros(R, dtype=torch.int32, device=dev)
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)      # what the fork reads
-    start = length.clone() if ngram or pen or bias is not None or aut is not None or (stop is not None and stop.sequences) else None
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
     if ev:
         ev[0].record()
-    last = torch.empty((B, eng.vocab), dtype=torch.bfloat16, device=dev)
-    if P:
-        _forward_prefix(eng, prompts[0], P, 0, [u * N for u in range(1, B)])
-    for a, b in chunks:
-        packed = torch.cat([p.to(dev).reshape(-1)[P:] for p in prompts[a:b]])
-        last[a:b] = eng.forward_slots(packed, [n - P for n in lens[a:b]], [u * N for u in range(a, b)], prompt_phase=bool(P), pos0=P)
+    last = _prefill(eng, prompts, lens, chunks, P, [u * N for u in range(B)], dev)
     if ev:
         ev[3].record()
     # positions at or behind a prompt's end in its last tile are overwritten before causality lets anything read them
@@ -616,30 +612,22 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     if ev:
         ev[4].record()
     ops.sample(last.repeat_interleave(N, dim=0), tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed,
-               step=0, logprobs=lp_buf, top_logprobs=top_buf, mask=mask, no_repeat_ngram=ngram, start=start, stop=stop, top_p=top_p,
-               min_p=min_p, **_penalty_kw(pen), **_bias_kw(bias), **_automaton_kw(aut))
+               step=0, **picks.kw())
     if ev:
         ev[1].record()
-    steps_run = 0
-    with _decode_settings(eng, lp_buf, top_buf, mask, ngram, start, stop, top_p, min_p, pen, bias, aut), \
-            _shared_prompt(eng, shared_prompt, N, plen):
-        if max_new_tokens > 1:
-            steps_run = _decode_steps(eng, tokens, length, done, max_new_tokens - 1, temperature, top_k, eos_id, seed,
-                                      early=eos_id is not None or stop is not None)
+    steps_run = _decode(eng, picks, lambda c, first: eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=first),
+                        done, max_new_tokens - 1, early=eos_id is not None or picks.stop is not None,
+                        inner=[_shared_prompt_setting(eng, shared_prompt, N, plen)])
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = length.tolist()          # the read-back: lengths, flags, tokens and log-probabilities
     done_h = done.tolist()
-    tokens_h, lp_h = tokens.cpu(), lp_buf.cpu()
-    top_h = tuple(t.cpu() for t in top_buf) if K else None
+    tokens_h, lp_h = tokens.cpu(), picks.lp_buf.cpu()
+    top_h = tuple(t.cpu() for t in picks.top_buf) if picks.K else None
     if ev:   # the read-back above has synchronised the stream
-        timing["prefill_ms"] = timing.get("prefill_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["fork_ms"] = timing.get("fork_ms", 0.0) + ev[3].elapsed_time(ev[4])
-        timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["decode_steps"] = timing.get("decode_steps", 0) + steps_run
-        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + R * steps_run
-        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens) - (B - 1) * P
+        _add_timing(timing, prefill_ms=ev[0].elapsed_time(ev[1]), fork_ms=ev[3].elapsed_time(ev[4]), decode_ms=ev[1].elapsed_time(ev[2]),
+                    decode_steps=steps_run, decode_row_steps=R * steps_run, prefill_tokens=sum(lens) - (B - 1) * P)
         timing["shared_prefix"] = P
         timing["shared_prompt"] = shared_prompt
     reasons = _stop.finish_reasons(done_h)
@@ -647,22 +635,16 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     for u in range(B):
         samples = []
         for r in range(u * N, (u + 1) * N):
-            end = min(length_h[r], lens[u] + max_new_tokens)
-            lp = lp_h[r, lens[u]:end]
+            toks, lp, top = _row_result(r, lens[u], length_h, done_h, max_new_tokens, tokens_h, lp_h, top_h, lo=lens[u])
             total = float(lp.double().sum())
-            smp = dict(tokens=tokens_h[r, lens[u]:end - 1 if done_h[r] == 1 else end], token_logprobs=lp, sum_logprob=total,
-                       avg_logprob=total / max(int(lp.numel()), 1), finish_reason=reasons[r])
-            if K:
-                smp["top_logprobs"] = tuple(t[r, lens[u]:end] for t in top_h)
+            smp = dict(tokens=toks, token_logprobs=lp, sum_logprob=total, avg_logprob=total / max(int(lp.numel()), 1),
+                       finish_reason=reasons[r])
+            if picks.K:
+                smp["top_logprobs"] = top
             samples.append(smp)
         out.append(samples)
     if return_state:
-        st = dict(tokens=tokens, length=length, done=done, logprobs=lp_buf)
-        if K:
-            st["top_ids"], st["top_logprobs"] = top_buf
-        if aut is not None:
-            st["automaton_state"] = aut.state
-        return out, st
+        return out, dict(tokens=tokens, length=length, done=done, **picks.state())
     return out
 
 
@@ -771,45 +753,27 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     if ev:
         ev[1].record()
     step = 1
-    if mask is not None:
-        eng.set_token_mask(mask)        # part of the captured step's key; without it the call runs the steps it always ran
-    if stop is not None:
-        eng.set_stop(stop, plen if stop.sequences else None, state.fin_tok_buffer())     # likewise
-    if on_device:
-        eng.set_beam_history(hist, ngram)                   # likewise
-    if shared_prompt:
-        eng.set_shared_prompt(W, plen)                      # likewise
-    try:
+    with _engine_settings([
+            (mask is not None, lambda: eng.set_token_mask(mask), lambda: eng.set_token_mask(None)),
+            (stop is not None, lambda: eng.set_stop(stop, plen if stop.sequences else None, state.fin_tok_buffer()), lambda: eng.set_stop(None)),
+            (on_device, lambda: eng.set_beam_history(hist, ngram), lambda: eng.set_beam_history(None)),
+            _shared_prompt_setting(eng, shared_prompt, W, plen)]):
         while step < max_new_tokens:
             c = max_new_tokens - step if eos_id is None and stop is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
             eng.decode_beam(state, plen, c, eos_id, first_step=step)
             step += c
             if step < max_new_tokens and bool((state.done != 0).all()):
                 break
-    finally:
-        if mask is not None:
-            eng.set_token_mask(None)
-        if stop is not None:
-            eng.set_stop(None)
-        if on_device:
-            eng.set_beam_history(None)
-        if shared_prompt:
-            eng.set_shared_prompt()
     if ev:
         ev[2].record()
     model._cache_len = []  # slots now hold these hypotheses; a later cached forward must start at 0
     h = state.host()        # the read-back: two copies
     prompts_h = torch.cat(on_dev).cpu().split(lens)
     if ev:
-        timing["prefill_ms"] = timing.get("prefill_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["decode_steps"] = timing.get("decode_steps", 0) + step - 1
-        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + rows * (step - 1)
-        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + sum(lens)
         took = sum(W * (n - 1) for n in h["n_steps"])
         moved = sum(p != w for u in range(B) for t in range(1, h["n_steps"][u]) for w, p in enumerate(h["beam_parent"][u][t]))
-        timing["beam_step_rows"] = timing.get("beam_step_rows", 0) + took
-        timing["beam_copied_rows"] = timing.get("beam_copied_rows", 0) + moved
+        _add_timing(timing, prefill_ms=ev[0].elapsed_time(ev[1]), decode_ms=ev[1].elapsed_time(ev[2]), decode_steps=step - 1,
+                    decode_row_steps=rows * (step - 1), prefill_tokens=sum(lens), beam_step_rows=took, beam_copied_rows=moved)
         timing["shared_prompt"] = shared_prompt
     out = []
     for u in range(B):
@@ -825,11 +789,10 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
 class _StreamBackend:
     """What StreamScheduler.run drives: one engine, one token buffer for every sequence of the call."""
 
-    def __init__(self, model: GPT, eng, prompts, lens, max_new_tokens, sample_kw, timing, prefix: int = 0,
-                 logprobs: bool = False, top_logprobs: int = 0, mask: Optional[torch.Tensor] = None, ngram: int = 0, stop=None,
-                 top_p: float = 1.0, min_p: float = 0.0, pen=None, bias=None, aut=None) -> None:
+    def __init__(self, eng, prompts, lens, max_new_tokens, sample_kw, picks: _Picks, timing, prefix: int = 0) -> None:
         N, dev = len(prompts), eng.device
         self.eng, self.prompts, self.lens, self.max_new, self.kw = eng, prompts, lens, max_new_tokens, sample_kw
+        self.picks = picks                   # compiled with the dummy sequence's row (_Picks.compile, dummy=True)
         self.prefix = prefix                 # every slot but the spare one holds the call's first `prefix` positions (share_prefix)
         self.prefill_tokens = 0
         tok_ld = max(lens) + max_new_tokens
@@ -841,22 +804,6 @@ class _StreamBackend:
         self.limit = torch.tensor([n + max_new_tokens for n in lens] + [1], dtype=torch.int32, device=dev)
         self.done = torch.zeros(N + 1, dtype=torch.int32, device=dev)
         self.done[N] = 2
-        # beside `tokens`: the log-probability of every sampled token (generate_batch's return_logprobs), NaN where none was
-        self.logprobs = torch.full(tuple(self.tokens.shape), float("nan"), dtype=torch.float32, device=dev) if logprobs else None
-        self.top = _top_buffers(self.tokens.shape, top_logprobs, dev) if top_logprobs else None   # generate_batch's top_logprobs
-        # the call's token mask (generate_batch's token_mask) and an all-ones row for the dummy sequence, which never picks
-        self.mask = None if mask is None else torch.cat([mask, torch.full_like(mask[:1], -1)]).contiguous()
-        # generate_batch's no_repeat_ngram and the sequences' prompt lengths (the dummy sequence's one token is all prompt)
-        self.ngram = ngram
-        self.stop = stop                     # generate_batch's stop; its sequences count from the same prompt lengths
-        self.top_p, self.min_p = top_p, min_p    # generate_batch's top_p / min_p (the decode steps get them through the engine)
-        self.pen = pen                       # generate_batch's penalties, checked (None: off); their history counts from the same lengths
-        self.bias = bias                     # generate_batch's bias, compiled (None: off); its matches count from the same lengths
-        # generate_batch's automaton set and a valid start state for the dummy sequence, which never picks; a refilled row starts
-        # over by itself: its sequence has generated nothing, so its pick reads the start state
-        self.aut = None if aut is None else aut.padded()
-        self.start = torch.tensor(lens + [1], dtype=torch.int32, device=dev) \
-            if ngram or pen or bias is not None or aut is not None or (stop is not None and stop.sequences) else None
         self.row_seq, self.row_slot = eng.row_arrays()
         self.events = {"prefill_ms": [], "decode_ms": []} if timing is not None else None
 
@@ -878,9 +825,7 @@ class _StreamBackend:
         # call is one-token prompts, where generate_batch's one packed prefill is that decode step too
         last = self.eng.forward_slots(packed, [self.lens[u] - P for u in seqs], list(slots), prompt_phase=max(self.lens) > 1, pos0=P)
         ops.sample_rows(last, self.tokens, self.length, self.done, self.limit, torch.tensor(seqs, dtype=torch.int32, device=dev),
-                        self.max_new, logprobs=self.logprobs, top_logprobs=self.top, mask=self.mask, no_repeat_ngram=self.ngram,
-                        start=self.start, stop=self.stop, top_p=self.top_p, min_p=self.min_p, **_penalty_kw(self.pen), **_bias_kw(self.bias),
-                        **_automaton_kw(self.aut), **self.kw)
+                        self.max_new, **self.picks.kw(), **self.kw)
         if end:
             end.record()
 
@@ -945,78 +890,43 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
     that is prefilled into a row another one held begins in its own start state, with no reset launch (return_state's automaton_state
     has one entry per prompt)."""
     from .schedule import StreamScheduler
-    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
-    bias = _check_bias(bias, speculate)
-    automaton = _check_automaton(automaton, speculate)
-    top_p, min_p = _nucleus.check_nucleus(top_p, min_p)
-    K = _check_top_logprobs(model, top_logprobs, return_logprobs)
-    ngram = _ngram.check_ngram(no_repeat_ngram)
-    if ngram:
-        _ngram.check_ngram(ngram, model.config.padded_vocab_size)
+    picks = _Picks.check(speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
+                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
     if speculate:
         raise ValueError(f"speculate={speculate}: continuous batching steps a row list one token at a time; speculative decoding runs "
                          "under generate_batch (--schedule batch) only")
     N = len(prompts)
     assert N > 0 and max_new_tokens > 0
-    lens = [int(p.numel()) for p in prompts]
-    need_pos = max(lens) + max_new_tokens - 1
-    if model.max_seq_length < need_pos:
-        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {need_pos}")
-    if pen:
-        _penalty.check_history(max(lens) + max_new_tokens, model.config.padded_vocab_size)
+    lens, T_max, need_pos, _ = _prompt_shape(model, prompts, max_new_tokens, prefill_batch)
     sched = StreamScheduler(N, max_new_tokens, max_rows, prefill_batch, check_every, fp8=bool(getattr(model, "fp8", False)))
     dev = model.transformer.wte.weight.device
-    bias = _compile_bias(model, bias, pen, max(lens) + max_new_tokens, dev)
-    aut = None if automaton is None else _automaton.as_set(automaton, N, model.config.padded_vocab_size, dev, eos_id)
-    mask = _token_mask(model, token_mask, N, 1, dev)
-    stop = None if stop is None else _stop.as_spec(stop, model.config.padded_vocab_size, dev)
+    picks.compile(model, lens, T_max + max_new_tokens, dev, eos_id, dummy=True)
     P = _shared_prefix(model, prompts, share_prefix, dev)
     # slots 0..max_rows-1 and the spare one; a prefill packs at most the prefill_batch longest prompts (their tokens behind the prefix)
     eng = model.engine(sched.max_rows + 1, need_pos, max(P, sum(sorted(n - P for n in lens)[-prefill_batch:])), exact=True)
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # N independent batch-1 runs
-    be = _StreamBackend(model, eng, prompts, lens, max_new_tokens,
-                        dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), timing, prefix=P, logprobs=return_logprobs,
-                        top_logprobs=K, mask=mask, ngram=ngram, stop=stop, top_p=top_p, min_p=min_p, pen=pen, bias=bias, aut=aut)
+    be = _StreamBackend(eng, prompts, lens, max_new_tokens, dict(temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed), picks,
+                        timing, prefix=P)
     if P:       # the dummy sequence's spare slot (sched.max_rows) shares nothing: it stays at position 0
         end = be._timed("prefill_ms")
         _forward_prefix(eng, prompts[0], P, 0, range(1, sched.max_rows))
         if end:
             end.record()
-    with _decode_settings(eng, be.logprobs, be.top, be.mask, ngram, be.start, stop, top_p, min_p, pen, bias, be.aut):
+    with picks.engine(eng):
         sched.run(be)
     model._cache_len = []  # slots now hold these sequences; a later cached forward must start at 0
     length_h = be.length.tolist()
     done_h = be.done.tolist()
     assert all(done_h[:N]), "generate_stream ended with an unfinished sequence"
     if timing is not None:   # the read-back above has synchronised the stream
-        for key, evs in be.events.items():
-            timing[key] = timing.get(key, 0.0) + sum(a.elapsed_time(b) for a, b in evs)
-        timing["decode_steps"] = timing.get("decode_steps", 0) + sched.decode_steps
-        timing["decode_row_steps"] = timing.get("decode_row_steps", 0) + sched.decode_row_steps
+        _add_timing(timing, **{key: sum((a.elapsed_time(b) for a, b in evs), 0.0) for key, evs in be.events.items()},
+                    decode_steps=sched.decode_steps, decode_row_steps=sched.decode_row_steps, prefill_tokens=P + be.prefill_tokens)
         timing["launch_rows"] = set(timing.get("launch_rows", ())) | sched.launch_rows
-        timing["prefill_tokens"] = timing.get("prefill_tokens", 0) + P + be.prefill_tokens
         timing["shared_prefix"] = P
-    out: List[torch.Tensor] = []
-    for i in range(N):
-        n = min(length_h[i], lens[i] + max_new_tokens)
-        if done_h[i] == 1:
-            n -= 1                      # generate/base.py:80 returns idx[:input_pos]: EOS excluded
-        out.append(be.tokens[i, :n])
-    res = (out,)
-    if return_logprobs:
-        res += ([be.logprobs[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for i in range(N)],)
-        if K:
-            res += ([tuple(t[i, lens[i]:min(length_h[i], lens[i] + max_new_tokens)] for t in be.top) for i in range(N)],)
-    if return_state:        # the dummy sequence's row stays behind
-        st = dict(tokens=be.tokens[:N], length=be.length[:N], done=be.done[:N])
-        if return_logprobs:
-            st["logprobs"] = be.logprobs[:N]
-        if K:
-            st["top_ids"], st["top_logprobs"] = be.top[0][:N], be.top[1][:N]
-        if be.aut is not None:
-            st["automaton_state"] = be.aut.state[:N]
-        res += (st,)
-    return res if len(res) > 1 else out
+    rows = [_row_result(i, lens[i], length_h, done_h, max_new_tokens, be.tokens, picks.lp_buf, picks.top_buf) for i in range(N)]
+    # the dummy sequence's row stays behind
+    return _batch_result(rows, picks, dict(tokens=be.tokens[:N], length=be.length[:N], done=be.done[:N], **picks.state(N)) if return_state else None)
 
 
 @torch.inference_mode()
@@ -1030,19 +940,15 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
     generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's.  repetition_penalty, frequency_penalty,
     presence_penalty: generate_batch's.  bias: generate_batch's.  automaton: generate_batch's, a set with the one start state."""
-    _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
-    _check_bias(bias, speculate)
-    _check_automaton(automaton, speculate)
-    _nucleus.check_nucleus(top_p, min_p)
-    _check_top_logprobs(model, top_logprobs, return_logprobs)
+    options = dict(speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
+                   no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                   frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
+    _Picks.check(**options)
     T = idx.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
-    res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                         speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
-                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
+    res = generate_batch(model, [idx], max_returned_tokens - T, temperature=temperature, top_k=top_k, eos_id=eos_id, **options)
     if top_logprobs:
         return res[0][0], res[1][0], res[2][0]
     return (res[0][0], res[1][0]) if return_logprobs else res[0]

@@ -2,12 +2,16 @@
 generate_stream against a scripted engine on the CPU, the two refusals, and the C-ABI entry (header, exports, ctypes table)."""
 import importlib
 import re
+import sys
 from pathlib import Path
 
 import pytest
 import torch
 
 from dualhyp_amd.schedule import shared_prefix_len
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from scripted_engine import ScriptedModel  # noqa: E402
 
 REPO = Path(__file__).resolve().parent.parent
 G = importlib.import_module("dualhyp_amd.generate")        # the package's `generate` attribute is the function
@@ -37,67 +41,6 @@ def test_shared_prefix_len(as_lists):
 
 
 # ---- generate_stream against a scripted engine -------------------------------------------------------------------------------
-class ScriptedEngine:
-    """What generate_stream asks of gpt._Engine, on the CPU: records every call; sequence u produces n_gen[u] tokens."""
-    vocab = 8
-
-    def __init__(self, n_gen):
-        self.device = torch.device("cpu")
-        self.n_gen, self.calls = n_gen, []
-        self.max_batch = None
-        self._rows = None
-
-    def set_rsqrt_emulation(self, vec_width, whole_call):
-        pass
-
-    def forward(self, ids_, seq_len, pos0, want_all, want_last, slot_base=0):
-        self.calls.append(("forward", ids_.tolist(), list(seq_len), list(pos0), want_all, want_last, slot_base))
-        return None, None
-
-    def copy_prefix(self, src_slot, dst_slots, n_pos):
-        self.calls.append(("copy_prefix", src_slot, list(dst_slots), n_pos))
-
-    def forward_slots(self, ids_, seq_len, slots, prompt_phase=False, pos0=0):
-        self.calls.append(("forward_slots", ids_.tolist(), list(seq_len), list(slots), prompt_phase, pos0))
-        return torch.zeros((len(seq_len), self.vocab), dtype=torch.bfloat16)
-
-    def row_arrays(self):
-        if self._rows is None:
-            self._rows = (torch.zeros(self.max_batch, dtype=torch.int32), torch.zeros(self.max_batch, dtype=torch.int32))
-        return self._rows
-
-    def _pick(self, u, tokens, length, done, made):
-        tokens[u, length[u]] = 7
-        length[u] += 1
-        if made >= self.n_gen[u]:
-            done[u] = 1
-
-    def decode_rows(self, tokens, length, done, limit, max_new, n_rows, n_steps, temperature, top_k, eos_id, seed):
-        row_seq, row_slot = (t[:n_rows].tolist() for t in self._rows)
-        self.calls.append(("decode_rows", row_seq, row_slot, n_steps))
-        for u in row_seq:
-            for _ in range(n_steps):
-                if not done[u]:
-                    self._pick(u, tokens, length, done, int(length[u]) + 1 - self.lens[u])
-
-
-class ScriptedModel:
-    """The attributes of GPT that generate_stream reads"""
-    max_seq_length = 4096
-    cpu_rsqrt_vec_width = 0
-    fp8 = False
-
-    def __init__(self, n_gen):
-        self.eng = ScriptedEngine(n_gen)
-        self.transformer = type("T", (), {"wte": type("W", (), {"weight": torch.zeros(1)})()})()
-        self.engine_args = None
-
-    def engine(self, need_batch, need_pos, need_tokens, exact=False):
-        self.engine_args = (need_batch, need_pos, need_tokens)
-        self.eng.max_batch = need_batch
-        return self.eng
-
-
 def stream(prompts, n_gen, share, monkeypatch, **kw):
     model = ScriptedModel(n_gen)
     eng = model.eng
