@@ -183,6 +183,7 @@ SIGNATURES = {
     "dh_engine_decode": (I, [P, P, I, P, P, I, I, F, I, I64, U64, I, P]),
     "dh_engine_decode_rows": (I, [P, P, I, P, P, P, I, I, P, P, I, I, F, I, I64, U64, P]),
     "dh_engine_decode_spec": (I, [P, P, I, P, P, P, I, I, I, P, P, I, F, I64, I, P]),
+    "dh_engine_decode_spec_draw": (I, [P, P, I, P, P, P, I, I, I, P, P, I, F, I, I64, U64, I, P]),
     "dh_engine_reserve_rows": (I, [P, I]),
     "dh_engine_reserve_beams": (I, [P, I, I]),
     "dh_engine_decode_beam": (I, [P, C.POINTER(BeamState), P, I, I, I, I, I64, I, P]),

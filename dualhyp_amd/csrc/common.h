@@ -400,9 +400,17 @@ int dh_attn_verify_fused_impl(const float* qkv32, int n_part, int pairs, int n_s
                               const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
                               const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
                               dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int p_max, void* stream);
+// draw ("Sampled verification" of the header, dh_engine_decode_spec_draw; null: the arg-max, ctl's nuc, pen, bias and aut off): every
+// position draws with top_k and the key (seed, n - (limit - max_new), sequence), under ctl's four as well
+struct dh_spec_draw {
+    int top_k = 0;
+    uint64_t seed = 0;
+    int max_new = 0;
+};
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& ctl, void* stream);   // ctl: nuc, pen, bias and aut off
+                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& ctl, void* stream,
+                        const dh_spec_draw* draw = nullptr);
 
 // the selection step of beam search (beam.hip, dh_beam_select_bf16), as the engine's captured step calls it
 // stop: its set ends a hypothesis as the EOS does, its sequences as well under device histories; hist (nullable, int64

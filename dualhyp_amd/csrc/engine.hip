@@ -89,6 +89,8 @@ struct dh_engine {
         const int32_t *limit = nullptr, *row_seq = nullptr, *row_slot = nullptr; int n_all = 0, max_new = 0;
         // dh_engine_decode_spec: D drafts per step (0 in every other key), the scripted drafts, the counters
         int spec = 0; const int64_t* drafts = nullptr; int32_t* counters = nullptr;
+        // dh_engine_decode_spec_draw: the step's positions draw (top_k and seed above are then the draw's, as in a plain step's key)
+        bool spec_draw = false;
         // the options the step's sampling launch takes (step_ctl): a step captured without one of them is another kernel, or other arguments
         dh_pick_ctl ctl;
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
@@ -101,6 +103,7 @@ struct dh_engine {
                    top_k == k.top_k && temp == k.temp && eos == k.eos && seed == k.seed && rsqrt_vec == k.rsqrt_vec &&
                    tiled_rows == k.tiled_rows && limit == k.limit && row_seq == k.row_seq && row_slot == k.row_slot &&
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
+                   spec_draw == k.spec_draw &&
                    ctl == k.ctl && beam_w == k.beam_w && stop_fin_tok == k.stop_fin_tok && beam_hist == k.beam_hist &&
                    beam_ngram == k.beam_ngram && shared_rows == k.shared_rows && shared_plen == k.shared_plen && memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
@@ -1004,7 +1007,7 @@ int forward_impl(dh_engine* e, const int64_t* ids, const int32_t* h_seq_len, con
 // increments.  Else (dh_engine_decode_rows) the prep and the sampling kernel index the per-sequence arrays through the row list.
 // One verify step of k.spec drafts per sequence (dh_engine_decode_spec): the prep kernel proposes and lays out the k.n_seq * S rows,
 // the streaming single-token family runs over them with the verify attention, the head gives every row's logits, the acceptance
-// kernel appends what the drafts got right plus one.
+// kernel appends what the drafts got right plus one — against the arg-max, or, k.spec_draw, against the draw of the plain sampled step.
 int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     const int S = k.spec + 1, rows = k.n_seq * S;
     const dh_model_desc& D = e->d;
@@ -1017,8 +1020,9 @@ int verify_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     int rc;
     if ((rc = run_layers_decode(e, e->dec_ids, rows, nullptr, s, S))) return rc;
     if ((rc = head(e, nullptr, rows, e->logits, nullptr, s))) return rc;
+    const dh_spec_draw draw{k.top_k, k.seed, k.max_new};
     return dh_spec_accept_impl(e->logits, D.vocab, e->dec_ids, S, k.tokens, k.tok_ld, k.length, k.done, k.limit, k.n_seq, k.temp, k.eos,
-                               e->step_dev, k.counters, k.ctl, s);
+                               e->step_dev, k.counters, k.ctl, s, k.spec_draw ? &draw : nullptr);
 }
 
 // tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends
@@ -1051,19 +1055,20 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
 // The options of a step an entry point is about to launch: what the setters have set, less what the step's kind does not take.  This is
 // what the step's sampling launch bakes in, so it is what the step's key compares.
 enum StepKind { STEP_DECODE, STEP_DECODE_ROWS, STEP_VERIFY, STEP_BEAM };
-dh_pick_ctl step_ctl(const dh_engine* e, StepKind kind, int top_k) {
+dh_pick_ctl step_ctl(const dh_engine* e, StepKind kind, int top_k, bool draw = false) {
     dh_pick_ctl c;
     c.mask = e->set.mask;
     c.mask_ld = e->set.mask_ld;
     c.stop = e->set.stop;
     if (kind == STEP_BEAM) return c;                    // the selection takes the mask and the stop specification, nothing else
     c = e->set;
-    if (kind == STEP_VERIFY) {                          // dh_engine_decode_spec has refused all three
+    const bool argmax_verify = kind == STEP_VERIFY && !draw;            // draw: dh_engine_decode_spec_draw's step keeps what a plain step keeps
+    if (argmax_verify) {                                // dh_engine_decode_spec has refused all three
         c.pen = DH_PENALTY_OFF;
         c.bias = dh_bias_args{};
         c.aut = dh_automaton_args{};
     }
-    if (kind == STEP_VERIFY || top_k == 1) c.nuc = dh_nucleus_args{};   // the arg-max takes neither parameter: its step is the plain one
+    if (argmax_verify || top_k == 1) c.nuc = dh_nucleus_args{};   // the arg-max takes neither parameter: its step is the plain one
     // the prompt lengths of the step's history readers and stop sequences: the setters were given the same numbers
     c.start = c.ngram ? e->ngram_start : dh_penalty_on(c.pen) ? e->pen_start : c.bias.n ? e->bias_start : c.aut.on() ? e->aut_start : e->stop_start;
     return c;
@@ -1453,42 +1458,65 @@ extern "C" int dh_engine_graph_count(const dh_engine* e, int n_draft) {
     return n;
 }
 
-extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, const int32_t* limit,
-                                     int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts, int32_t* counters, int n_steps,
-                                     float temperature, int64_t eos_id, int first_step, void* stream) {
-    DH_CHECK(e && tokens && length && done && limit && counters, "dh_engine_decode_spec: null argument");
-    DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "dh_engine_decode_spec: n_seq=%d exceeds max_batch=%d", n_seq, e->max_batch);
-    DH_CHECK(tok_ld > 0 && max_new_tokens > 0 && temperature > 0.f, "dh_engine_decode_spec: bad shape or temperature");
-    DH_CHECK(n_draft >= 1 && n_draft <= 7, "dh_engine_decode_spec: n_draft=%d is not in 1..7", n_draft);
+namespace {
+// dh_engine_decode_spec and dh_engine_decode_spec_draw (`name`; draw: the latter, with its top_k and seed)
+int decode_spec_call(const char* name, bool draw, dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                     const int32_t* limit, int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts, int32_t* counters, int n_steps,
+                     float temperature, int top_k, int64_t eos_id, uint64_t seed, int first_step, void* stream) {
+    DH_CHECK(e && tokens && length && done && limit && counters, "%s: null argument", name);
+    DH_CHECK(n_seq > 0 && n_seq <= e->max_batch, "%s: n_seq=%d exceeds max_batch=%d", name, n_seq, e->max_batch);
+    DH_CHECK(tok_ld > 0 && max_new_tokens > 0 && temperature > 0.f, "%s: bad shape or temperature", name);
+    DH_CHECK(top_k >= 0, "%s: top_k must be >= 0 (0 = no crop)", name);
+    DH_CHECK(n_draft >= 1 && n_draft <= 7, "%s: n_draft=%d is not in 1..7", name, n_draft);
     const int S = n_draft + 1, q_per_kv = e->d.n_head / e->d.n_groups;
-    DH_CHECK(S * q_per_kv <= 32, "dh_engine_decode_spec: %d positions x %d heads per KV group exceed the 32 query columns of the verify attention",
-             S, q_per_kv);
-    DH_CHECK(n_seq * S <= MAX_DECODE_ROWS, "dh_engine_decode_spec: %d x %d rows exceed the streaming step's %d", n_seq, S, MAX_DECODE_ROWS);
+    DH_CHECK(S * q_per_kv <= 32, "%s: %d positions x %d heads per KV group exceed the 32 query columns of the verify attention", name, S, q_per_kv);
+    DH_CHECK(n_seq * S <= MAX_DECODE_ROWS, "%s: %d x %d rows exceed the streaming step's %d", name, n_seq, S, MAX_DECODE_ROWS);
     DH_CHECK(n_seq * S <= e->row_cap && n_seq * S <= e->max_tokens,
-             "dh_engine_decode_spec: %d rows, the workspaces hold %d (dh_engine_reserve_rows) of max_tokens = %d", n_seq * S, e->row_cap, e->max_tokens);
-    DH_CHECK(!dh_penalty_on(e->set.pen), "dh_engine_decode_spec: penalties are set (repetition=%g, frequency=%g, presence=%g); a verify position's "
-             "history would have to include this launch's own picks", (double)e->set.pen.repetition, (double)e->set.pen.frequency, (double)e->set.pen.presence);
-    DH_CHECK(e->set.bias.n == 0, "dh_engine_decode_spec: a bias of %d entries is set; a verify position's tail would have to include this "
-             "launch's own picks, so the step would need per-position tables", e->set.bias.n);
-    DH_CHECK(!e->set.aut.on(), "dh_engine_decode_spec: an automaton set of %d states is set; a verify position's state would depend on the "
-             "picks of this launch's earlier positions", e->set.aut.n_states);
-    DH_CHECK(e->shared_rows == 0, "dh_engine_decode_spec: shared-prompt attention is set (group_rows=%d); a verify step's rows are "
-             "positions of one sequence, not rows of an utterance", e->shared_rows);
-    DH_CHECK(!e->fp8, "dh_engine_decode_spec: an fp8 engine's step changes its GEMM kernel with the row count; not supported");
-    DH_CHECK(e->rsqrt_vec == 0, "dh_engine_decode_spec: the CPU rsqrt emulation flags rows by their place in a call; not supported");
-    DH_CHECK(g_decode_tiled_rows == 0, "dh_engine_decode_spec: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported");
+             "%s: %d rows, the workspaces hold %d (dh_engine_reserve_rows) of max_tokens = %d", name, n_seq * S, e->row_cap, e->max_tokens);
+    if (draw) {                                         // the options a plain step takes, under the plain entries' limits
+        if (int rc = check_pen_tables(e, name, tok_ld)) return rc;
+        if (int rc = check_automaton_call(e, name, eos_id, n_seq)) return rc;
+    } else {
+        DH_CHECK(!dh_penalty_on(e->set.pen), "%s: penalties are set (repetition=%g, frequency=%g, presence=%g); a verify position's "
+                 "history would have to include this launch's own picks", name, (double)e->set.pen.repetition, (double)e->set.pen.frequency,
+                 (double)e->set.pen.presence);
+        DH_CHECK(e->set.bias.n == 0, "%s: a bias of %d entries is set; a verify position's tail would have to include this "
+                 "launch's own picks, so the step would need per-position tables", name, e->set.bias.n);
+        DH_CHECK(!e->set.aut.on(), "%s: an automaton set of %d states is set; a verify position's state would depend on the "
+                 "picks of this launch's earlier positions", name, e->set.aut.n_states);
+    }
+    DH_CHECK(e->shared_rows == 0, "%s: shared-prompt attention is set (group_rows=%d); a verify step's rows are "
+             "positions of one sequence, not rows of an utterance", name, e->shared_rows);
+    DH_CHECK(!e->fp8, "%s: an fp8 engine's step changes its GEMM kernel with the row count; not supported", name);
+    DH_CHECK(e->rsqrt_vec == 0, "%s: the CPU rsqrt emulation flags rows by their place in a call; not supported", name);
+    DH_CHECK(g_decode_tiled_rows == 0, "%s: dh_set_tuning key 10 moves steps to the tiled kernels by row count; not supported", name);
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, e->step_dev, (int32_t)first_step);
     DH_LAUNCH_CHECK();
-    dh_engine::GKey key;                                // seed, rsqrt_vec, tiled_rows: 0, the step reads none of them
+    dh_engine::GKey key;                                // rsqrt_vec, tiled_rows: 0, the step reads neither; seed: the draw's, else 0
     key.tokens = tokens; key.tok_ld = tok_ld; key.length = length; key.done = done;
-    key.n_seq = n_seq; key.top_k = 1; key.temp = temperature; key.eos = eos_id;
+    key.n_seq = n_seq; key.top_k = top_k; key.temp = temperature; key.eos = eos_id; key.seed = seed;
     key.limit = limit; key.n_all = n_seq; key.max_new = max_new_tokens;
-    key.spec = n_draft; key.drafts = drafts; key.counters = counters;
-    key.ctl = step_ctl(e, STEP_VERIFY, 1);
+    key.spec = n_draft; key.drafts = drafts; key.counters = counters; key.spec_draw = draw;
+    key.ctl = step_ctl(e, STEP_VERIFY, top_k, draw);
     return launch_steps(e, key, n_steps, s);
+}
+}  // namespace
+
+extern "C" int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, const int32_t* limit,
+                                     int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts, int32_t* counters, int n_steps,
+                                     float temperature, int64_t eos_id, int first_step, void* stream) {
+    return decode_spec_call("dh_engine_decode_spec", false, e, tokens, tok_ld, length, done, limit, n_seq, max_new_tokens, n_draft, drafts,
+                            counters, n_steps, temperature, 1, eos_id, 0, first_step, stream);
+}
+
+extern "C" int dh_engine_decode_spec_draw(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done, const int32_t* limit,
+                                          int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts, int32_t* counters, int n_steps,
+                                          float temperature, int top_k, int64_t eos_id, uint64_t seed, int first_step, void* stream) {
+    return decode_spec_call("dh_engine_decode_spec_draw", true, e, tokens, tok_ld, length, done, limit, n_seq, max_new_tokens, n_draft, drafts,
+                            counters, n_steps, temperature, top_k, eos_id, seed, first_step, stream);
 }
 
 extern "C" int dh_engine_reserve_beams(dh_engine* e, int W, int max_new_tokens) {

@@ -560,13 +560,16 @@ __device__ __forceinline__ pen_view pen_build(const bf16_t* __restrict__ lg, int
 
 // Automaton constraints (include/dualhyp_hip.h): the state sequence u is in at a pick behind m generated tokens, and its edge range as
 // ban_row takes it.  The host has checked the arrays' host copies; the clamps only keep a read inside the device arrays whatever they hold.
-__device__ __forceinline__ aut_edges aut_state(const dh_automaton_args& aut, int u, int m, int64_t eos_id, int& q) {
-    q = m == 0 ? aut.init[u] : aut.state[u];
-    if (q < 0 || q >= aut.n_states) q = 0;
+__device__ __forceinline__ aut_edges aut_range(const dh_automaton_args& aut, int q, int64_t eos_id) {     // q in [0, n_states)
     int lo = aut.edge_off[q], hi = aut.edge_off[q + 1];
     hi = hi < 0 ? 0 : hi > aut.n_edges ? aut.n_edges : hi;
     lo = lo < 0 ? 0 : lo > hi ? hi : lo;
     return aut_edges{aut.edge_tok, lo, hi, (int)eos_id};
+}
+__device__ __forceinline__ aut_edges aut_state(const dh_automaton_args& aut, int u, int m, int64_t eos_id, int& q) {
+    q = m == 0 ? aut.init[u] : aut.state[u];
+    if (q < 0 || q >= aut.n_states) q = 0;
+    return aut_range(aut, q, eos_id);
 }
 // The transition behind the pick `choice`, by the whole block: state[u] = edge_dst[e] of q's edge on `choice`, or q where it has none.  An
 // edge is unique per (state, token), so at most one thread finds it; thread 0 stores the result with a plain vector store.  The read of
@@ -584,6 +587,22 @@ __device__ __forceinline__ void aut_step(const dh_automaton_args& aut, const aut
     }
     __syncthreads();
     if (tid == 0) aut.state[u] = s_next;
+}
+// aut_step's lookup for a verify step's draw mode, which moves the state in registers: every thread gets the state behind `choice` and
+// nothing is stored.  The caller keeps a barrier between the return and the block's next call (every pick holds several).
+__device__ __forceinline__ int aut_next(const dh_automaton_args& aut, const aut_edges& ae, int q, int choice) {
+    __shared__ int s_next;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_next = q;
+    __syncthreads();
+    for (int e = ae.lo + tid; e < ae.hi; e += NT) {
+        if (ae.tok[e] == choice) {
+            const int d = aut.edge_dst[e];
+            if (d >= 0 && d < aut.n_states) s_next = d;
+        }
+    }
+    __syncthreads();
+    return s_next;
 }
 
 // pick_token under no_repeat_ngram: under the row ban_row builds from the sequence's history g[0..m), through the masked paths of
@@ -926,15 +945,25 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const bf16_t* __restric
 // block reads them back (a workgroup-scope fence: the block's waves share the CU's vector cache).
 // sa (stop conditions): an appended pick that stops ends the loop with done = 3 exactly where an EOS ends it with 1; every thread decides
 // it from its own copy of the window of the last DH_MAX_STOP_LEN generated tokens, never from thread 0's stores of this launch.
-template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
-__global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
+// DRAW ("Sampled verification" of the header, dh_engine_decode_spec_draw): pick_j is not the arg-max but the pick of the plain sampled
+// step for the token at place n — top_k and the draw keyed by (seed, n - prompt length, u), prompt length = limit[u] - max_new as in
+// sample_rows_kernel, under nuc and, with BAN, under pen, bias and aut on the history tokens[u, p0 .. n), this launch's picks included.
+// The automaton's state is read once (aut_state), lives in registers and moves along every pick's edge (aut_next); thread 0 stores the
+// state behind the last pick.  Everything behind the pick — acceptance, append order, stop window, EOS, budget, counters — is shared.
+// DRAW is a template flag and not a launch-uniform argument like nuc and pen in the samplers: a runtime top_k would put the whole
+// sampled branch, its 2 KiB of nucleus bins and the five options' arguments into the arg-max instantiations, whose code is pinned to
+// what it was (MEASUREMENTS.md, "sampled verification").  Off: draw, nuc, pen, bias and aut are not read.
+template <bool LP, bool TOP, bool MASK, bool BAN, bool DRAW>
+__device__ __forceinline__ void spec_accept_body(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
                                                          int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
                                                          int32_t* __restrict__ done, const int32_t* __restrict__ limit,
                                                          float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
                                                          int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
                                                          int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
                                                          const uint32_t* __restrict__ mask, int mask_ld, int ngram,
-                                                         const int32_t* __restrict__ start, dh_stop_args sa) {
+                                                         const int32_t* __restrict__ start, const dh_stop_args& sa,
+                                                         const dh_spec_draw& draw, const dh_nucleus_args& nuc, const dh_penalty_args& pen,
+                                                         const dh_bias_args& bias, const dh_automaton_args& aut) {
     const int u = blockIdx.x, tid = threadIdx.x;
     if (done[u]) return;
     int n = length[u];
@@ -948,13 +977,32 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
 #pragma unroll
     for (int k = 1; k < DH_MAX_STOP_LEN; ++k) w[k] = sa.n_seqs && n - k >= p0 && n - k >= 0 ? (int)tokens[(size_t)u * tok_ld + n - k] : -1;
     int appended = 0, state = 0, prev = 0;
+    int q = 0, plen = 0;                                                  // DRAW: the automaton's state, the prompt length of the draw's key
+    aut_edges ae;
+    if constexpr (DRAW) {
+        plen = limit[u] - draw.max_new;
+        if constexpr (BAN) { if (aut.on()) ae = aut_state(aut, u, n - p0, eos_id, q); }     // the same for every thread of the launch
+    }
     for (int j = 0; j < S; ++j) {
         if (j > 0) {
             if (row_ids[(size_t)u * S + j] != (int64_t)prev) break;      // the same for every thread
             __syncthreads();                                             // pick_token's shared scratch is free again
         }
         int choice;
-        if constexpr (BAN)
+        if constexpr (DRAW) {
+            if constexpr (BAN) {
+                choice = pick_token_banned<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, draw.top_k, draw.seed, n - plen, u,
+                                             MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram, nuc,
+                                             pen, bias, ae);
+                if (aut.on()) {
+                    q = aut_next(aut, ae, q, choice);
+                    ae = aut_range(aut, q, eos_id);
+                }
+            } else {
+                choice = pick_token<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, draw.top_k, draw.seed, n - plen, u,
+                                          MASK ? mask + (size_t)u * mask_ld : nullptr, nuc);
+            }
+        } else if constexpr (BAN)
             choice = pick_token_banned<MASK>(logits + ((size_t)u * S + j) * vocab, vocab, temperature, 1, 0, 0, u,
                                          MASK ? mask + (size_t)u * mask_ld : nullptr, tokens + (size_t)u * tok_ld + p0, n - p0, ngram);
         else
@@ -985,10 +1033,40 @@ __global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restric
     if (tid == 0) {
         length[u] = n;
         if (state) done[u] = state;
+        if constexpr (DRAW && BAN) { if (aut.on()) aut.state[u] = q; }   // a plain vector store, as aut_step's
         atomicMax(&counters[0], *step_dev);
         atomicAdd(&counters[1], S - 1);
         atomicAdd(&counters[2], appended > 1 ? appended - 1 : 0);
     }
+}
+
+template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
+__global__ __launch_bounds__(NT) void spec_accept_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
+                                                         int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
+                                                         int32_t* __restrict__ done, const int32_t* __restrict__ limit,
+                                                         float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
+                                                         int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
+                                                         int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
+                                                         const uint32_t* __restrict__ mask, int mask_ld, int ngram,
+                                                         const int32_t* __restrict__ start, dh_stop_args sa) {
+    spec_accept_body<LP, TOP, MASK, BAN, false>(logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
+                                                counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, dh_spec_draw{},
+                                                dh_nucleus_args{}, DH_PENALTY_OFF, dh_bias_args{}, dh_automaton_args{});
+}
+
+template <bool LP, bool TOP = false, bool MASK = false, bool BAN = false>
+__global__ __launch_bounds__(NT) void spec_accept_draw_kernel(const bf16_t* __restrict__ logits, int vocab, const int64_t* __restrict__ row_ids,
+                                                              int S, int64_t* __restrict__ tokens, int tok_ld, int32_t* __restrict__ length,
+                                                              int32_t* __restrict__ done, const int32_t* __restrict__ limit,
+                                                              float temperature, int64_t eos_id, const int32_t* __restrict__ step_dev,
+                                                              int32_t* __restrict__ counters, float* __restrict__ logprobs, int top_n,
+                                                              int32_t* __restrict__ top_ids, float* __restrict__ top_lp,
+                                                              const uint32_t* __restrict__ mask, int mask_ld, int ngram,
+                                                              const int32_t* __restrict__ start, dh_stop_args sa, dh_spec_draw draw,
+                                                              dh_nucleus_args nuc, dh_penalty_args pen, dh_bias_args bias, dh_automaton_args aut) {
+    spec_accept_body<LP, TOP, MASK, BAN, true>(logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
+                                               counters, logprobs, top_n, top_ids, top_lp, mask, mask_ld, ngram, start, sa, draw, nuc, pen, bias,
+                                               aut);
 }
 
 // out[r] = log softmax(logits[r, :])[ids[r]]; an id outside [0, vocab) reads nothing and gives NaN (the Python wrapper refuses it)
@@ -1386,15 +1464,24 @@ extern "C" int dh_sample_rows_bf16(const dh_bf16* logits, int vocab, int64_t* to
 
 int dh_spec_accept_impl(const dh_bf16* logits, int vocab, const int64_t* row_ids, int S, int64_t* tokens, int tok_ld,
                         int32_t* length, int32_t* done, const int32_t* limit, int n_seq, float temperature, int64_t eos_id,
-                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& c, void* stream) {
-    // a verify position's history would have to include this launch's own picks, and the acceptance is an arg-max
-    DH_CHECK(!c.nuc.on() && !dh_penalty_on(c.pen) && c.bias.n == 0 && !c.aut.on(),
-             "spec_accept: a verify step takes no nucleus, no penalty, no bias and no automaton");
+                        const int32_t* step_dev, int32_t* counters, const dh_pick_ctl& c, void* stream, const dh_spec_draw* draw) {
+    // the arg-max kernel reads none of the four: only the draw mode forms a position's history, this launch's own picks included
+    DH_CHECK(draw || (!c.nuc.on() && !dh_penalty_on(c.pen) && c.bias.n == 0 && !c.aut.on()),
+             "spec_accept: an arg-max verify step takes no nucleus, no penalty, no bias and no automaton");
     DH_CHECK(logits && row_ids && tokens && length && done && limit && step_dev && counters, "spec_accept: null argument");
-    if (int rc = check_pick("spec_accept", vocab, tok_ld, true, c)) return rc;
+    if (int rc = check_pick("spec_accept", vocab, tok_ld, true, c, eos_id, n_seq)) return rc;
     DH_CHECK(vocab > 0 && tok_ld > 0 && n_seq >= 0 && S >= 2, "spec_accept: bad shape");
     DH_CHECK(temperature > 0.f, "spec_accept: temperature must be > 0");
+    DH_CHECK(!draw || (draw->top_k >= 0 && draw->max_new > 0), "spec_accept: top_k must be >= 0 (0 = no crop) and max_new > 0");
     if (n_seq == 0) return 0;
+    if (draw) {                                         // the penalties' dynamic LDS as the penalised sample_kernel launch asks for it
+        hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_draw_kernel, c), dim3(n_seq), dim3(NT),
+                           dh_penalty_on(c.pen) || c.bias.n > 0 ? PEN_LDS_BYTES : 0, (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld,
+                           length, done, limit, temperature, eos_id, step_dev, counters, c.logprobs, c.top_n, c.top_ids, c.top_lp, c.mask,
+                           c.mask_ld, c.ngram, c.start, c.stop, *draw, c.nuc, c.pen, c.bias, c.aut);
+        DH_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(DH_PICK_VARIANT(spec_accept_kernel, c), dim3(n_seq), dim3(NT), 0,
                        (hipStream_t)stream, logits, vocab, row_ids, S, tokens, tok_ld, length, done, limit, temperature, eos_id, step_dev,
                        counters, c.logprobs, c.top_n, c.top_ids, c.top_lp, c.mask, c.mask_ld, c.ngram, c.start, c.stop);

@@ -25,7 +25,7 @@ from . import ops
 from . import stop as _stop
 from .gpt import GPT
 from .schedule import shared_prefix_len
-from .speculate import check_arguments as _check_speculate
+from .speculate import check_arguments as _check_speculate, check_verify as _check_verify
 
 
 EOS_CHECK_EVERY = 16     # decode steps between two "has every sequence finished" read-backs (generate_batch with an eos_id)
@@ -155,10 +155,13 @@ class _Picks:
     start: Optional[torch.Tensor] = None    # compile(): the rows' prompt lengths, where an option reads a row's generated text
 
     @classmethod
-    def check(cls, *, speculate: int = 0, return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
+    def check(cls, *, speculate: int = 0, verify: str = "argmax", return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
               stop=None, top_p=None, min_p=None, repetition_penalty=None, frequency_penalty=None, presence_penalty=None, bias=None,
               automaton=None) -> "_Picks":
-        """Stage one: what the arguments alone decide, refused before the model is touched."""
+        """Stage one: what the arguments alone decide, refused before the model is touched.  verify="draw": a verify step forms every
+        position's history itself, so the three readers of a row's generated text go with speculate."""
+        if _check_verify(verify, speculate):
+            speculate = 0
         pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty, speculate)
         bias = _check_bias(bias, speculate)
         automaton = _check_automaton(automaton, speculate)
@@ -328,7 +331,7 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
                    return_logprobs: bool = False, top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0,
                    stop=None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                    repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                   presence_penalty: Optional[float] = None, bias=None, automaton=None):
+                   presence_penalty: Optional[float] = None, bias=None, automaton=None, verify: str = "argmax"):
     """prompts: 1-D int64 tensors (any lengths).  Returns a list of 1-D tensors prompt+generated,
     cut before the EOS token when one was produced.
 
@@ -348,6 +351,15 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     drafts are right.  drafts None: drafted by prompt lookup (speculate.propose); a [B, max_new_tokens] int64 tensor: drafts[u, i]
     is proposed as the i-th generated token of sequence u (a scripted proposer for tests and tools/bench_speculate.py).
     timing gains spec_steps (verify steps until the last sequence finished), spec_drafted and spec_accepted.
+
+    verify ("argmax", the default: everything above and every refusal below; or "draw", with speculate > 0; include/dualhyp_hip.h,
+    "Sampled verification"): a verify position picks as the plain step of this call would pick the token at its place — top_k, the
+    draw keyed by (seed, tokens generated so far, sequence), top_p / min_p, and the penalties, the bias, the no-repeat ban and the
+    automaton on a history that includes the picks of the same step — and a draft is kept exactly when it equals that pick
+    (dh_engine_decode_spec_draw).  The ids, log-probabilities, alternatives, done flags and automaton states are those of the same
+    call with speculate=0, bit for bit, whatever is drafted.  It opens speculate to any top_k (top_k=1 is the arg-max verification)
+    and to top_p, min_p, the three penalties, bias and automaton, beside what speculate already goes with.  fp8 / MXFP4 and RelPrompt
+    models, the CPU rsqrt emulation and generate_stream stay refused.
 
     return_logprobs: the call returns (out, logprobs[, state]); logprobs[i] is a 1-D float32 tensor with the log-probability of every
     token the model produced for sequence i, in order, the EOS token's last when the sequence ended on one (so its length is
@@ -430,12 +442,13 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     row's.  It goes with share_prefix, return_logprobs, top_logprobs, token_mask, no_repeat_ngram, stop, top_p, min_p, the penalties, bias
     and fp8; speculate is refused.  return_state gains automaton_state, the int32 [B] states behind the last picks.  None (the default)
     is off: the call it always was."""
-    picks = _Picks.check(speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
-                         no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
+    picks = _Picks.check(speculate=speculate, verify=verify, return_logprobs=return_logprobs, top_logprobs=top_logprobs,
+                         token_mask=token_mask, no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p,
+                         repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                         bias=bias, automaton=automaton)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
-    D = _check_speculate(model, speculate, top_k, B)
+    D = _check_speculate(model, speculate, top_k, B, verify)
     if drafts is not None and (D == 0 or drafts.dtype != torch.int64 or tuple(drafts.shape) != (B, max_new_tokens)):
         raise ValueError(f"drafts goes with speculate > 0 and is a [{B}, {max_new_tokens}] int64 tensor")
     lens, T_max, need_pos, chunks = _prompt_shape(model, prompts, max_new_tokens, prefill_batch)
@@ -468,7 +481,10 @@ def generate_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: 
     ops.sample(last, tokens, length, done, temperature=temperature, top_k=top_k, eos_id=eos_id, seed=seed, step=0, **picks.kw())
     if ev:
         ev[1].record()
-    if D:   # a step yields 1 .. D + 1 tokens per live sequence, so at most max_new_tokens - 1 steps are needed
+    if D and verify == "draw":
+        step = lambda c, first: eng.decode_spec_draw(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature,
+                                                     top_k, eos_id, seed, first_step=first)
+    elif D:   # a step yields 1 .. D + 1 tokens per live sequence, so at most max_new_tokens - 1 steps are needed
         step = lambda c, first: eng.decode_spec(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature, eos_id,
                                                 first_step=first)
     else:
@@ -536,7 +552,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                  no_repeat_ngram: int = 0, stop=None, top_logprobs: int = 0, timing: Optional[dict] = None,
                  return_state: bool = False, speculate: int = 0, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None,
-                 shared_prompt: bool = False):
+                 shared_prompt: bool = False, verify: str = "argmax", drafts: Optional[torch.Tensor] = None):
     """num_samples = N (2..8) sampled candidates per prompt from ONE prefill of it (include/dualhyp_hip.h, "Sampled candidates").
 
     DEFINITION: sample j of utterance u is row u * N + j of generate_batch over [p for p in prompts for _ in range(N)] with the same
@@ -569,12 +585,20 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
     timing gains generate_batch's keys, with prefill_tokens counting every prompt once, fork_ms: the fork launch between its own
     two events, inside prefill_ms, and shared_prompt.
 
+    speculate=D with verify="draw" (generate_batch's; "Sampled verification" of the header): the decode steps are verify steps over
+    the B * N rows behind the fork, each position drawing with its row's key, so the definition above holds unchanged — every sample,
+    score and flag is the speculate=0 call's, in fewer steps where the drafts (prompt lookup on the row's own text, or `drafts`, a
+    [B * N, max_new_tokens] int64 tensor) are right.  timing gains generate_batch's spec_* counters.  shared_prompt=True is refused
+    with it: a verify step's rows are positions of one sequence, not rows of an utterance.
+
     Refused with a ValueError before anything is launched: num_samples outside 2..8; top_k == 1 (the arg-max gives N equal rows);
-    speculate (a verify step confirms drafts against the arg-max); RelPrompt models (their prompts carry spliced embeddings)."""
+    speculate without verify="draw" (a verify step confirms drafts against the arg-max); RelPrompt models (their prompts carry spliced
+    embeddings)."""
     N = check_num_samples(num_samples)
     if top_k is not None and int(top_k) == 1:
         raise ValueError(f"num_samples={N} does not go with top_k=1: the arg-max gives {N} equal rows; sample with top_k != 1")
-    if speculate:
+    draw = _check_verify(verify, speculate)
+    if speculate and not draw:
         raise ValueError(f"num_samples={N} does not go with speculate={speculate}: a verify step confirms drafts against the arg-max, "
                          "and sampled candidates are not greedy")
     from .relprompt import GPT as RelGPT
@@ -582,23 +606,36 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
         raise ValueError(f"num_samples={N}: the RelPrompt decoder's prompts carry spliced reliability embeddings, which a prefill by "
                          "ids into the source slots does not hold")
     shared_prompt = check_shared_prompt(model, shared_prompt, N, f"num_samples={N}")
-    picks = _Picks.check(return_logprobs=True, top_logprobs=top_logprobs, token_mask=token_mask, no_repeat_ngram=no_repeat_ngram, stop=stop,
+    if shared_prompt and speculate:
+        raise ValueError(f"shared_prompt=True does not go with speculate={speculate}: a verify step's rows are positions of one sequence, "
+                         "not rows of an utterance")
+    picks = _Picks.check(speculate=speculate, verify=verify, return_logprobs=True, top_logprobs=top_logprobs, token_mask=token_mask, no_repeat_ngram=no_repeat_ngram, stop=stop,
                          top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
                          presence_penalty=presence_penalty, bias=bias, automaton=automaton)
     B = len(prompts)
     assert B > 0 and max_new_tokens > 0
     R = B * N
+    D = _check_speculate(model, speculate, top_k, R, verify)
+    if drafts is not None and (D == 0 or drafts.dtype != torch.int64 or tuple(drafts.shape) != (R, max_new_tokens)):
+        raise ValueError(f"drafts goes with speculate > 0 and is a [{R}, {max_new_tokens}] int64 tensor")
     lens, T_max, need_pos, chunks = _prompt_shape(model, prompts, max_new_tokens, prefill_batch)
     dev = model.transformer.wte.weight.device
     tok_ld = T_max + max_new_tokens
     picks.compile(model, lens, tok_ld, dev, eos_id, repeat=N)       # a mask row and a start state per utterance, serving its N rows
     P = _shared_prefix(model, prompts, share_prefix, dev)
-    eng = model.engine(R, min(need_pos, -(-model.config.block_size // 64) * 64),
-                       max(P, R, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)), exact=R > prefill_batch)
+    # D: a verify step's positions and rows, as in generate_batch
+    eng = model.engine(R, min(need_pos + D, -(-model.config.block_size // 64) * 64),
+                       max(P, R * (D + 1) if D else R, max(sum(lens[a:b]) - (b - a) * P for a, b in chunks)), exact=R > prefill_batch)
+    if D:
+        eng.reserve_rows(R * (D + 1))
     row_lens = [n for n in lens for _ in range(N)]
     tokens = _token_buffer([p for p in prompts for _ in range(N)], row_lens, tok_ld, dev)
     length = torch.tensor(row_lens, dtype=torch.int32, device=dev)
     done = torch.zeros(R, dtype=torch.int32, device=dev)
+    if D:
+        counters = torch.zeros(3, dtype=torch.int32, device=dev)
+        limit = torch.tensor([n + max_new_tokens for n in row_lens], dtype=torch.int32, device=dev)
+        drafts = None if drafts is None else drafts.to(dev).contiguous()
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)      # what the fork reads
     eng.set_rsqrt_emulation(model.cpu_rsqrt_vec_width, whole_call=False)   # independent batch-1 runs
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
@@ -615,8 +652,12 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                step=0, **picks.kw())
     if ev:
         ev[1].record()
-    steps_run = _decode(eng, picks, lambda c, first: eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=first),
-                        done, max_new_tokens - 1, early=eos_id is not None or picks.stop is not None,
+    if D:
+        step = lambda c, first: eng.decode_spec_draw(tokens, length, done, limit, max_new_tokens, D, drafts, counters, c, temperature,
+                                                     top_k, eos_id, seed, first_step=first)
+    else:
+        step = lambda c, first: eng.decode(tokens, length, done, c, temperature, top_k, eos_id, seed, first_step=first)
+    steps_run = _decode(eng, picks, step, done, max_new_tokens - 1, early=bool(D) or eos_id is not None or picks.stop is not None,
                         inner=[_shared_prompt_setting(eng, shared_prompt, N, plen)])
     if ev:
         ev[2].record()
@@ -630,6 +671,8 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
                     decode_steps=steps_run, decode_row_steps=R * steps_run, prefill_tokens=sum(lens) - (B - 1) * P)
         timing["shared_prefix"] = P
         timing["shared_prompt"] = shared_prompt
+        if D:
+            _add_timing(timing, **dict(zip(("spec_steps", "spec_drafted", "spec_accepted"), counters.tolist())))
     reasons = _stop.finish_reasons(done_h)
     out = []
     for u in range(B):
@@ -852,7 +895,8 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
                     share_prefix: Union[bool, str] = False, speculate: int = 0, return_logprobs: bool = False,
                     top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, return_state: bool = False,
                     top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None):
+                    frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, bias=None, automaton=None,
+                    verify: str = "argmax"):
     """generate_batch's result for any number of prompts — the same ids, bit for bit, in prompt order — through at most
     `max_rows` decode rows that change hands: every `check_every` steps the sequences that have finished (EOS, or their own
     budget of max_new_tokens) leave their rows, the next prompts are prefilled into the KV slots they held, and the step is
@@ -888,9 +932,11 @@ def generate_stream(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens:
 
     automaton: as in generate_batch — a sequence's state is its own entry of the state buffer wherever it is scheduled, and a sequence
     that is prefilled into a row another one held begins in its own start state, with no reset launch (return_state's automaton_state
-    has one entry per prompt)."""
+    has one entry per prompt).
+
+    speculate, verify: refused unless 0 / "argmax", whatever the mode — a row list steps one token at a time."""
     from .schedule import StreamScheduler
-    picks = _Picks.check(speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
+    picks = _Picks.check(speculate=speculate, verify=verify, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
                          no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                          frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
     if speculate:
@@ -934,15 +980,15 @@ def generate(model: GPT, idx: torch.Tensor, max_returned_tokens: int, *, tempera
              top_k: Optional[int] = None, eos_id: Optional[int] = None, speculate: int = 0, return_logprobs: bool = False,
              top_logprobs: int = 0, token_mask=None, no_repeat_ngram: int = 0, stop=None, top_p: Optional[float] = None,
              min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-             presence_penalty: Optional[float] = None, bias=None, automaton=None):
-    """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate as in generate_batch.  return_logprobs: the
+             presence_penalty: Optional[float] = None, bias=None, automaton=None, verify: str = "argmax"):
+    """Drop-in for generate/base.py:generate (one prompt of shape (T,)); speculate and verify as in generate_batch.  return_logprobs: the
     result is (ids, logprobs), logprobs as generate_batch's for the one sequence; with top_logprobs=K, (ids, logprobs, (top ids,
     top values)).  token_mask: generate_batch's — a [1, words] tensor, or a list holding the one id list.  no_repeat_ngram:
     generate_batch's.  stop: generate_batch's.  top_p, min_p: generate_batch's.  repetition_penalty, frequency_penalty,
     presence_penalty: generate_batch's.  bias: generate_batch's.  automaton: generate_batch's, a set with the one start state."""
     options = dict(speculate=speculate, return_logprobs=return_logprobs, top_logprobs=top_logprobs, token_mask=token_mask,
                    no_repeat_ngram=no_repeat_ngram, stop=stop, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                   frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton)
+                   frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, bias=bias, automaton=automaton, verify=verify)
     _Picks.check(**options)
     T = idx.size(0)
     assert max_returned_tokens > T

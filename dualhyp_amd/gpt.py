@@ -489,6 +489,22 @@ class _Engine:
                 int(max_new_tokens), int(n_draft), None if drafts is None else drafts.data_ptr(), counters.data_ptr(), int(n_steps),
                 float(temperature), -1 if eos_id is None else int(eos_id), int(first_step), torch.cuda.current_stream().cuda_stream))
 
+    def decode_spec_draw(self, tokens: torch.Tensor, length: torch.Tensor, done: torch.Tensor, limit: torch.Tensor, max_new_tokens: int,
+                         n_draft: int, drafts: Optional[torch.Tensor], counters: torch.Tensor, n_steps: int, temperature: float,
+                         top_k: Optional[int], eos_id: Optional[int], seed: int, first_step: int = 0) -> None:
+        """decode_spec whose positions draw as decode's steps draw (dh_engine_decode_spec_draw, "Sampled verification" of the header): any
+        top_k, the call's seed, and the nucleus, penalties, bias and automaton that are set."""
+        B = tokens.size(0)
+        assert length.numel() == done.numel() == limit.numel() == B and counters.numel() >= 3 and counters.dtype == torch.int32
+        assert drafts is None or (drafts.dtype == torch.int64 and drafts.is_contiguous() and tuple(drafts.shape) == (B, int(max_new_tokens)))
+        self._check_logprobs(tokens)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_decode_spec_draw(
+                self.handle, tokens.data_ptr(), tokens.size(1), length.data_ptr(), done.data_ptr(), limit.data_ptr(), B,
+                int(max_new_tokens), int(n_draft), None if drafts is None else drafts.data_ptr(), counters.data_ptr(), int(n_steps),
+                float(temperature), 0 if top_k is None else int(top_k), -1 if eos_id is None else int(eos_id),
+                int(seed) & ((1 << 64) - 1), int(first_step), torch.cuda.current_stream().cuda_stream))
+
     def reserve_beams(self, num_beams: int, max_new_tokens: int) -> None:
         """Size the KV re-parenting scratch and the candidates' workspace of decode_beam (dh_engine_reserve_beams)."""
         with torch.cuda.device(self.device):

@@ -140,6 +140,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["finish_reason"] = reasons[k]
             if getattr(generate_fn, "sampling", None):
                 preds[i]["sampling"] = dict(generate_fn.sampling)
+            if getattr(generate_fn, "speculate_verify", "argmax") != "argmax":
+                preds[i]["speculate_verify"] = str(generate_fn.speculate_verify)
             if getattr(generate_fn, "penalties", None):
                 preds[i]["penalties"] = dict(generate_fn.penalties)
             if getattr(generate_fn, "activations", "fp8") != "fp8":
@@ -383,6 +385,9 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     continuous = getattr(args, "schedule", "batch") == "continuous"
     share = "auto" if getattr(args, "share_prefix", "off") == "auto" else False
     spec = int(getattr(args, "speculate", 0) or 0)
+    # --speculate_verify draw: the verify steps draw; the default run passes no keyword at all
+    draw = bool(spec) and getattr(args, "speculate_verify", "argmax") == "draw"
+    vkw = dict(verify="draw") if draw else {}
     top_n = int(getattr(args, "top_logprobs", 0) or 0)
     want_lp = bool(getattr(args, "logprobs", False)) or top_n > 0
     beams = int(getattr(args, "num_beams", 1) or 1)
@@ -433,7 +438,8 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
         if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
             cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
                                  prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, token_mask=mask,
-                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw, **akw, **shkw)
+                                 no_repeat_ngram=ngram, stop=stop, top_logprobs=top_n, **samp, **pkw, **akw, **shkw,
+                                 **(dict(speculate=spec, **vkw) if draw else {}))
             return {"samples": cands, "select": how, "logprobs": want_lp}
         if continuous:     # the rank's whole shard in one call: finished rows hand their KV slots to the next utterances
             outs = generate_stream(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
@@ -444,7 +450,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             outs = generate_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, eos_id=eos,
                                   prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), share_prefix=share, speculate=spec,
                                   return_logprobs=want_lp, top_logprobs=top_n, token_mask=mask, no_repeat_ngram=ngram,
-                                  **samp, **skw, **pkw, **akw)
+                                  **samp, **skw, **pkw, **akw, **vkw)
         if stop is not None:
             from .stop import finish_reasons
             gen.finish_reasons = finish_reasons(outs[-1]["done"])
@@ -460,6 +466,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.no_repeat_ngram = ngram
     gen.stop = stop is not None
     gen.sampling = sampling
+    gen.speculate_verify = "draw" if draw else "argmax"
     gen.penalties = penalties
     gen.activations = getattr(model, "activation_format", "fp8")
     gen.bias, gen.bias_entries = bias_rec, bias_entries
@@ -523,6 +530,12 @@ def build_parser():
                    help="D in 1..7: a decode step verifies D tokens drafted by prompt lookup (the correction mostly copies spans of its "
                         "prompt) next to each sequence's last one and keeps those the greedy arg-max confirms; --schedule batch only; "
                         "the predictions do not depend on it.  Default 0: off (acceptance on real corpora is unmeasured)")
+    p.add_argument("--speculate_verify", choices=("argmax", "draw"), default="argmax",
+                   help="with --speculate D: how a verify step confirms a draft.  argmax (the default): against the greedy arg-max, so "
+                        "--top_k 1 only.  draw: against the seeded draw the plain step would have made at that place, so --speculate goes "
+                        "with any --top_k, --top_p, --min_p, the penalties, --bias_file, --constrain chain and --num_samples (not with "
+                        "--share_prompt_kv); the predictions are those of the run without --speculate; every record gains "
+                        "speculate_verify: draw")
     p.add_argument("--quantize", choices=("none", "fp8", "mxfp4"), default="none",
                    help="fp8: after the checkpoint is loaded, LoRA is merged and every dense weight becomes e4m3 rows with channel scales "
                         "(quantize_model_fp8); activations are quantised per token and every product runs on the fp8 MFMA.  mxfp4: the "
@@ -662,6 +675,9 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error(f"--speculate {args.speculate} does not go with --quantize {args.quantize}: an fp8 engine has no verify step")
     if args.speculate and args.schedule == "continuous":      # generate_stream refuses it too; here nothing has been loaded yet
         p.error(f"--speculate {args.speculate} goes with --schedule batch: continuous batching steps a row list one token at a time")
+    draw = args.speculate_verify == "draw"                    # lifts the refusals of --speculate with the sampled path below
+    if draw and not args.speculate:
+        p.error("--speculate_verify draw goes with --speculate D: it says how a verify step confirms its drafts")
     if not 1 <= args.num_beams <= 4:
         p.error(f"--num_beams {args.num_beams}: W is 1 (greedy) or 2..4")
     if args.num_beams > 1:
@@ -678,7 +694,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error(f"--select {args.select} goes with --num_samples N > 1: one answer leaves nothing to select among")
     if args.num_samples > 1:
         for on, flag, why in ((args.num_beams > 1, f"--num_beams {args.num_beams}", "beam search ranks hypotheses by score and draws nothing"),
-                              (bool(args.speculate), f"--speculate {args.speculate}", "a verify step confirms drafts against the greedy arg-max"),
+                              (bool(args.speculate) and not draw, f"--speculate {args.speculate}", "a verify step confirms drafts against the greedy arg-max"),
                               (args.schedule == "continuous", "--schedule continuous", "an utterance's N decode slots are forked and stepped together"),
                               (args.top_k == 1, "--top_k 1", f"the arg-max gives {args.num_samples} equal candidates; sample with --top_k 0 or K > 1")):
             if on:
@@ -686,6 +702,9 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         if args.select is None:
             args.select = "avg_logprob"
     if args.share_prompt_kv:
+        if args.speculate and args.num_samples > 1:         # sample_batch refuses it too
+            p.error(f"--share_prompt_kv does not go with --speculate {args.speculate}: a verify step's rows are positions of one "
+                    "sequence, not rows of an utterance")
         if args.num_samples < 2 and args.num_beams < 2:
             p.error("--share_prompt_kv goes with --num_samples N > 1 or --num_beams W > 1: one decode row per utterance shares its "
                     "prompt with nobody")
@@ -711,7 +730,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             p.error(f"--constrain_order {args.constrain_order}: K is 2 .. 4")
         if args.constrain_extra:
             p.error("--constrain_extra goes with --constrain prompt: a chain automaton has no place for ids outside its prompt")
-        if args.speculate:          # generate_batch refuses it too; here nothing has been loaded yet
+        if args.speculate and not draw:     # generate_batch refuses it too; here nothing has been loaded yet
             from .automaton import SPEC_REFUSAL as AUT_SPEC_REFUSAL
             p.error(f"--speculate {args.speculate} does not go with --constrain chain: {AUT_SPEC_REFUSAL}")
         if args.num_beams > 1:
@@ -738,7 +757,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         p.error(f"--repetition_penalty / --frequency_penalty / --presence_penalty: {e}")
     if penalties_on(*pen):
         flags = f"--repetition_penalty {pen[0]} --frequency_penalty {pen[1]} --presence_penalty {pen[2]}"
-        if args.speculate:          # generate_batch refuses it too; here nothing has been loaded yet
+        if args.speculate and not draw:     # generate_batch refuses it too; here nothing has been loaded yet
             p.error(f"--speculate {args.speculate} does not go with {flags}: a verify position's history would have to include the picks "
                     "of its own step")
         if args.num_beams > 1:
@@ -749,7 +768,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     if not math.isfinite(args.bias_boost):
         p.error(f"--bias_boost {args.bias_boost}: the boost is finite")
     if args.bias_file:
-        if args.speculate:          # generate_batch refuses it too; here nothing has been loaded yet
+        if args.speculate and not draw:     # generate_batch refuses it too; here nothing has been loaded yet
             from .bias import SPEC_REFUSAL
             p.error(f"--speculate {args.speculate} does not go with --bias_file {args.bias_file}: {SPEC_REFUSAL}")
         if args.num_beams > 1:
@@ -761,7 +780,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     if args.top_k < 0:
         p.error(f"--top_k {args.top_k}: K is 0 (no crop), 1 (greedy) or more")
     if args.top_k != 1:
-        if args.speculate:          # speculate.check_arguments refuses it too; here nothing has been loaded yet
+        if args.speculate and not draw:     # speculate.check_arguments refuses it too; here nothing has been loaded yet
             p.error(f"--speculate {args.speculate} does not go with --top_k {args.top_k}: a verify step confirms drafts against the greedy "
                     "arg-max, so it runs with --top_k 1 only")
         if args.num_beams > 1:

@@ -1,10 +1,15 @@
-"""Speculative greedy decoding (generate_batch(..., speculate=D)): the proposer's rule, the argument checks, and a host replay of
-the acceptance rule.
+"""Speculative decoding (generate_batch(..., speculate=D)): the proposer's rule, the argument checks, and a host replay of the
+acceptance rule.
 
 A verify step feeds a sequence's last token and D drafted tokens through the decode kernels at once and keeps the drafts the model's
 own arg-max confirms (dh_engine_decode_spec).  The ids never depend on the drafts; the drafts only decide how many tokens a step
 yields.  The correction of an ASR hypothesis is mostly a copy of spans of its prompt, so the default proposer looks the continuation
 up in the sequence itself.
+
+verify="draw" (the default is "argmax", everything above): a verify position draws as the plain sampled step would — the draw is a
+function of (seed, tokens generated so far, sequence) and the row — and a draft is kept exactly when it equals the draw
+(dh_engine_decode_spec_draw; include/dualhyp_hip.h, "Sampled verification"), so a sampled call, with any of the sampler's options, gets
+the ids of its speculate=0 run in fewer steps.  replay() is the rule of both modes: it only compares drafts with the known ids.
 """
 from __future__ import annotations
 
@@ -12,6 +17,7 @@ from typing import List, Optional, Sequence
 
 MAX_DRAFTS = 7            # S = D + 1 positions of a sequence share the 32 query columns of the verify attention's MFMA
 VERIFY_COLUMNS = 32
+VERIFY_MODES = ("argmax", "draw")
 MAX_VERIFY_ROWS = 2048    # the streaming single-token step's row limit (engine.hip MAX_DECODE_ROWS)
 
 
@@ -33,14 +39,24 @@ def propose(tokens: Sequence[int], D: int, ngram_max: int = 3) -> List[int]:
     return [tokens[-1]] * D
 
 
-def check_arguments(model, speculate: int, top_k: Optional[int], n_seq: int) -> int:
-    """D of a generate_batch call, or a ValueError that says why this call cannot speculate.  Nothing here touches the GPU."""
+def check_verify(verify, speculate) -> bool:
+    """verify of a call: True for "draw", False for "argmax" (the default), or a ValueError.  Needs nothing but the arguments."""
+    if not isinstance(verify, str) or verify not in VERIFY_MODES:
+        raise ValueError(f'verify is "argmax" (a draft is kept when it is the arg-max) or "draw" (when it is the seeded draw), not {verify!r}')
+    if verify == "draw" and not speculate:
+        raise ValueError('verify="draw" goes with speculate > 0: it says how a verify step confirms its drafts, and this call has none')
+    return verify == "draw"
+
+
+def check_arguments(model, speculate: int, top_k: Optional[int], n_seq: int, verify: str = "argmax") -> int:
+    """D of a generate_batch call, or a ValueError that says why this call cannot speculate.  Nothing here touches the GPU.
+    verify="draw": any top_k speculates; the other refusals stand."""
     if isinstance(speculate, bool) or not isinstance(speculate, int) or not 0 <= speculate <= MAX_DRAFTS:
         raise ValueError(f"speculate is the number of drafts per step, 0..{MAX_DRAFTS}, not {speculate!r}")
     D = speculate
     if D == 0:
         return 0
-    if top_k != 1:
+    if top_k != 1 and not check_verify(verify, D):
         raise ValueError(f"speculate={D} needs top_k=1 (greedy): a draft is accepted when it IS the arg-max; top_k={top_k!r} samples")
     cfg = model.config
     q_per_kv = cfg.n_head // cfg.n_query_groups

@@ -1222,6 +1222,32 @@ int dh_engine_decode_spec(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* le
                           const int32_t* limit, int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts,
                           int32_t* counters, int n_steps, float temperature, int64_t eos_id, int first_step,
                           void* stream);
+/* Sampled verification: dh_engine_decode_spec whose positions DRAW where its positions take the arg-max, so that a sampled call
+ * (any top_k, with top_p / min_p, the penalties, a bias and an automaton where they are set) can speculate.
+ *   The key.  Position j of sequence u picks from logits row u * S + j exactly as the plain step picks a sequence's next token:
+ *   temperature, top_k, the mask row u, and the draw keyed by (seed, step, seq) with step = n - prompt length, n the sequence's
+ *   length at that position counting the picks this launch appended before it, prompt length = limit[u] - max_new_tokens, and
+ *   seq = u.  That is the key dh_engine_decode uses for the token at place n (its step counter is the number of tokens generated so
+ *   far, its row index the sequence), and dh_sample_rows_bf16's.
+ *   The history.  The no-repeat ban, the penalties' counts and the bias' proposals of position j are formed from
+ *   tokens[u, start[u] .. n), this launch's own picks included (thread 0's stores, read back behind a barrier); the automaton's
+ *   state is read once, carried across the positions and moved along every appended pick's edge, and state[u] behind the launch is
+ *   the state behind the last appended pick.
+ *   The equality.  A verify step's logits rows are, position by position, the bits of single-token steps as long as every earlier
+ *   draft was right, and the pick is a function of (row bytes, options, key, history) alone.  With draft_j accepted exactly when
+ *   draft_j == pick_{j-1}, the appended ids, log-probabilities, alternatives, done flags and automaton states are therefore those of
+ *   dh_engine_decode with the same top_k, seed and options, bit for bit, whatever is drafted; the drafts only decide how many tokens
+ *   a step yields.  top_k = 1 is dh_engine_decode_spec's arg-max (the draw is not consulted).
+ * Arguments, counters, the acceptance rule, the append order, EOS / stop / budget handling and the refusals (fp8 / MXFP4 engines, the
+ * CPU rsqrt emulation, dh_set_tuning key 10, shared-prompt attention, the shape limits) are dh_engine_decode_spec's; top_k >= 0 and
+ * seed are dh_engine_decode's.  The options dh_engine_set_nucleus, dh_engine_set_penalties, dh_engine_set_bias and
+ * dh_engine_set_automaton have set are applied (under the table limits of dh_engine_decode: tok_ld, plus the bias' ids, at most
+ * DH_MAX_PENALTY_HISTORY with penalties on; an automaton needs its eos_id and n_seq).  top_k, seed and every option are part of the
+ * captured step's key, and a step of this entry never replays one of dh_engine_decode_spec, or the reverse. */
+int dh_engine_decode_spec_draw(dh_engine* e, int64_t* tokens, int tok_ld, int32_t* length, int32_t* done,
+                               const int32_t* limit, int n_seq, int max_new_tokens, int n_draft, const int64_t* drafts,
+                               int32_t* counters, int n_steps, float temperature, int top_k, int64_t eos_id, uint64_t seed,
+                               int first_step, void* stream);
 /* Size the per-row workspaces of the single-token steps (logits, fp32 partial sums, ids) for `rows` rows
  * (<= 2048 and <= max_tokens) where dh_engine_create sized them for max_batch: a verify step has
  * n_seq * (n_draft + 1) rows and the KV cache stays at max_batch slots.  Growing drops the captured steps.
@@ -1288,28 +1314,28 @@ int dh_engine_set_stop(dh_engine* e, const dh_stop_spec* stop, const int32_t* st
  * 0 .. 8, vocab above 131072 with ngram > 0, null tokens with ngram > 0.  The caller keeps the planes alive while set. */
 int dh_engine_set_beam_history(dh_engine* e, int64_t* tokens, int ngram);
 /* top_p and min_p (see "Nucleus and min-p" above; 1 and 0 = off, the default) for later dh_engine_decode and dh_engine_decode_rows
- * calls with top_k != 1.  Both values are part of the captured step's key, beside the mask, (ngram, start) and the stop specification:
- * with them unset, or with top_k == 1, a decode call runs the graphs it always ran.  Verify and beam steps take neither.  Refused like
+ * calls with top_k != 1, and for dh_engine_decode_spec_draw's.  Both values are part of the captured step's key, beside the mask, (ngram, start) and the stop specification:
+ * with them unset, or with top_k == 1, a decode call runs the graphs it always ran.  Arg-max verify steps and beam steps take neither.  Refused like
  * dh_sample_bf16_nucleus. */
 int dh_engine_set_nucleus(dh_engine* e, float top_p, float min_p);
 /* The penalties (see "Penalties" above; null or all off clears them, the default) for later dh_engine_decode and dh_engine_decode_rows
  * calls, with any top_k.  `start` ([n_seq] int32 on the device, needed when a penalty is on) is the array dh_engine_set_no_repeat_ngram
  * and dh_engine_set_stop take and holds the same numbers; the caller keeps it alive while set.  The values and `start` are part of the
- * captured step's key: with them unset a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec and
+ * captured step's key: with them unset a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec (not dh_engine_decode_spec_draw, which applies it) and
  * dh_engine_decode_beam refuse, and a decode call with tok_ld above DH_MAX_PENALTY_HISTORY is refused before anything is launched.
  * Refused like dh_sample_bf16_penalty. */
 int dh_engine_set_penalties(dh_engine* e, const dh_penalty_args* penalties, const int32_t* start);
 /* The bias (see "Contextual biasing" above; null or no entry clears it, the default) for later dh_engine_decode and dh_engine_decode_rows
  * calls.  The spec's device arrays and `start` ([n_seq] int32 on the device, the array the other history readers take) are the caller's to
  * keep alive while set; the host copies are read here only.  The pointers, the counts and `start` are part of the captured step's key:
- * with none set a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec and dh_engine_decode_beam refuse, and,
+ * with none set a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec (not dh_engine_decode_spec_draw, which applies it) and dh_engine_decode_beam refuse, and,
  * with penalties set as well, so does a decode call whose tok_ld plus the entries' ids pass DH_MAX_PENALTY_HISTORY.  Refused like
  * dh_sample_bf16_bias. */
 int dh_engine_set_bias(dh_engine* e, const dh_bias_spec* bias, const int32_t* start);
 /* The automaton set (see "Automaton constraints" above; null clears it, the default) for later dh_engine_decode and dh_engine_decode_rows
  * calls.  The spec's device arrays, `state` among them, and `start` ([n_seq] int32 on the device, the array the other history readers
  * take) are the caller's to keep alive while set; the host copies are read here only.  The pointers, the counts and `start` are part of
- * the captured step's key: with none set a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec and
+ * the captured step's key: with none set a decode call runs the graphs it always ran.  While set, dh_engine_decode_spec (not dh_engine_decode_spec_draw, which applies it) and
  * dh_engine_decode_beam refuse, and a decode call refuses an eos_id outside [0, vocab) or a sequence count other than the spec's n_seq.
  * Refused like dh_sample_bf16_automaton. */
 int dh_engine_set_automaton(dh_engine* e, const dh_automaton_spec* automaton, const int32_t* start);

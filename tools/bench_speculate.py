@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Speculative greedy decoding (generate_batch(..., speculate=D)) against speculate=0, one GPU: TinyLlama shape, hash weights + LoRA
-r16, --rows prompts of 512 tokens, 64 new tokens, greedy, no EOS.
+"""Speculative decoding (generate_batch(..., speculate=D)) against speculate=0, one GPU: TinyLlama shape, hash weights + LoRA
+r16, --rows prompts of 512 tokens, 64 new tokens, no EOS; greedy, or with --verify draw the sampled call of --top_k / --temperature
+(/ --top_p / the three penalties), whose verify steps confirm drafts against the seeded draw.
 
 Per row count (default 32 and 640), in ONE process on one box: the plain call (warm-up, then --repeats timed calls), then for
 D = 1, 2, 3 and the target acceptance rates 0, 0.5 and 1.0 a scripted proposer — `drafts` = the plain run's own continuation with
@@ -8,6 +9,11 @@ every token replaced independently with the probability that makes the expected 
 --repeats timed calls each.  Figures are the call's own HIP-event decode time (median call): ms per issued step, decode tokens per second,
 the measured acceptance, and per D the break-even acceptance (ms per verify step / ms per plain step - 1) / D.  The ids of every
 speculative call must equal the plain call's (digest).  A combination the engine refuses (rows x (D + 1) > 2048) is recorded as such.
+
+--verify draw adds, per D, `argmax_verify`: the arg-max verify step (top_k = 1, the same D, every draft wrong) timed in the same process,
+and the draw step's time over it.  --lookup adds, per D, a call drafted by prompt lookup (drafts=None) and its accepted share.
+
+    python tools/bench_speculate.py --rows 32 --verify draw --top_k 40 --temperature 0.8 [--top_p 0.9 --repetition_penalty 1.3] [--lookup]
 
 Every row count is a child process of its own under a time limit; the parent never touches the GPU and prints ONE JSON line.
 
@@ -40,8 +46,20 @@ ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--step_timeout", type=int, default=420, help="seconds each child may take")
 ap.add_argument("--out", type=str, default="", help="write the line as a JSON file too")
 ap.add_argument("--worker", type=int, default=None, help="(child) the row count of this run")
+ap.add_argument("--verify", choices=("argmax", "draw"), default="argmax", help="draw: the sampled call, verified against the seeded draw")
+ap.add_argument("--top_k", type=int, default=1, help="with --verify draw: 0 (no crop) or K")
+ap.add_argument("--temperature", type=float, default=0.2)
+ap.add_argument("--top_p", type=float, default=None)
+ap.add_argument("--repetition_penalty", type=float, default=None)
+ap.add_argument("--frequency_penalty", type=float, default=None)
+ap.add_argument("--presence_penalty", type=float, default=None)
+ap.add_argument("--seed", type=int, default=1337)
+ap.add_argument("--lookup", action="store_true", help="per D, a call drafted by prompt lookup as well")
 ap.add_argument("--trace", choices=("plain", "spec"), default=None, help="two calls of one kind in this process, for a kernel trace")
 a = ap.parse_args()
+if a.verify == "argmax" and (a.top_k != 1 or any(v is not None for v in (a.top_p, a.repetition_penalty, a.frequency_penalty, a.presence_penalty))):
+    ap.error("--top_k other than 1, --top_p and the penalties go with --verify draw: the arg-max verifies a greedy call")
+SAMPLER = {k: getattr(a, k) for k in ("top_p", "repetition_penalty", "frequency_penalty", "presence_penalty") if getattr(a, k) is not None}
 
 
 def digest(outs) -> str:
@@ -77,7 +95,10 @@ def setup(rows: int):
     m.load_state_dict(synth_state_dict(cfg, seed=1337, device=dev, embed_scale=50.0, head_tie=1.0), strict=True)
     m.eval()
     corpus = [p.to(dev) for p in synth_prompts(rows, a.prompt_len, cfg.padded_vocab_size, seed=7)]
-    return m, corpus, cfg.padded_vocab_size, dict(temperature=0.2, top_k=1, prefill_batch=a.prefill_batch)
+    kw = dict(temperature=a.temperature, top_k=a.top_k or None, prefill_batch=a.prefill_batch)
+    if a.verify == "draw":
+        kw.update(seed=a.seed, **SAMPLER)
+    return m, corpus, cfg.padded_vocab_size, kw
 
 
 def trace(kind: str) -> None:
@@ -120,7 +141,8 @@ def worker(rows: int) -> None:
     truth = torch.stack([o[T:T + new] for o in outs]).contiguous()
     steps = new - 1
     plain_ms = tm["decode_ms"] / steps
-    res = dict(rows=rows, ids_sha256=ident,
+    vkw = dict(verify="draw") if a.verify == "draw" else {}
+    res = dict(rows=rows, ids_sha256=ident, verify=a.verify, sampler=dict(temperature=a.temperature, top_k=a.top_k, **SAMPLER),
                plain=dict(decode_ms=round(tm["decode_ms"], 3), decode_ms_regions=regions, steps=steps, ms_per_step=round(plain_ms, 4),
                           tokens_per_s=round(rows * steps / tm["decode_ms"] * 1e3, 1)), speculate={})
     g = torch.Generator().manual_seed(11)
@@ -131,7 +153,7 @@ def worker(rows: int) -> None:
             wrong = (torch.rand((rows, new), generator=g) < p).to(dev)
             drafts = torch.where(wrong, (truth + 1) % V, truth).contiguous()
             try:
-                o2, id2, t2, reg2 = timed(speculate=D, drafts=drafts)
+                o2, id2, t2, reg2 = timed(speculate=D, drafts=drafts, **vkw)
             except ValueError as e:
                 cell[str(rate)] = dict(refused=str(e))
                 continue
@@ -147,6 +169,25 @@ def worker(rows: int) -> None:
         if done:   # tokens per step = 1 + share * D: equal tokens/s where share = (verify / plain - 1) / D
             ratio = statistics.median(c["ms_per_step_over_plain"] for c in done)
             cell["break_even_accepted_share"] = round((ratio - 1) / D, 4)
+        if done and a.lookup:       # prompt lookup on the rows' own text: what share of its drafts this call's picks confirm
+            o3, id3, t3, _ = timed(speculate=D, **vkw)
+            assert id3 == ident, f"rows {rows} D {D} lookup: the ids differ from the plain run's"
+            cell["lookup"] = dict(accepted_share=round(t3["spec_accepted"] / max(t3["spec_drafted"], 1), 4), steps=t3["spec_steps"],
+                                  decode_ms=round(t3["decode_ms"], 3), tokens_per_s_over_plain=round(tm["decode_ms"] / t3["decode_ms"], 4))
+        if done and a.verify == "draw":     # the arg-max verify step of the same D in the same process (greedy call, every draft wrong)
+            greedy = dict(kw, temperature=0.2, top_k=1)
+            for k in ("seed", *SAMPLER):
+                greedy.pop(k, None)
+            wrong = torch.randint(0, V, (rows, new), generator=g).to(dev)
+            tms = []
+            for i in range(a.repeats + 1):      # the first call is the warm-up
+                t4 = {}
+                generate_batch(m, corpus, new, timing=t4, speculate=D, drafts=wrong, **greedy)
+                tms.append(t4["decode_ms"] / t4["decode_steps"])
+            am = statistics.median(tms[1:])
+            dm = statistics.median(c["ms_per_step"] for c in done)
+            cell["argmax_verify"] = dict(ms_per_step=round(am, 4), draw_ms_per_step=round(dm, 4), draw_over_argmax=round(dm / am, 4),
+                                         draw_minus_argmax_us=round((dm - am) * 1e3, 1))
         res["speculate"][str(D)] = cell
     print(json.dumps(res), flush=True)
 
@@ -156,11 +197,14 @@ if a.trace is not None:
 elif a.worker is not None:
     worker(a.worker)
 else:
-    line = dict(tool="bench_speculate", prompt_len=a.prompt_len, max_new_tokens=a.max_new_tokens, repeats=a.repeats, runs=[])
+    line = dict(tool="bench_speculate", verify=a.verify, prompt_len=a.prompt_len, max_new_tokens=a.max_new_tokens, repeats=a.repeats, runs=[])
     for rows in a.rows:
         cmd = [sys.executable, str(Path(__file__).resolve()), "--worker", str(rows), "--drafts", *map(str, a.drafts), "--rates", *map(str, a.rates)]
-        for k in ("prompt_len", "max_new_tokens", "prefill_batch", "repeats"):
+        for k in ("prompt_len", "max_new_tokens", "prefill_batch", "repeats", "verify", "top_k", "temperature", "seed"):
             cmd += [f"--{k}", str(getattr(a, k))]
+        for k, v in SAMPLER.items():
+            cmd += [f"--{k}", str(v)]
+        cmd += ["--lookup"] * a.lookup
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=a.step_timeout)      # a run that fails ends the tool
         if r.returncode != 0:
             sys.exit(f"run --rows {rows} failed with {r.returncode}:\n{r.stdout[-1000:]}{r.stderr[-3000:]}")
