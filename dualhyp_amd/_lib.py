@@ -122,6 +122,8 @@ SIGNATURES = {
     "dh_attn_verify_fused_bf16": (I, [P, I, I, I, I, I, I, P, F, I, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "dh_attn_decode_shared_bf16": (I, [P, I, I, I, I, I, P, F, I, I, P, P, P, P, P, P, P, I, I, I, I, I, P, P]),
     "dh_attn_shared_launch_count": (I64, []),
+    "dh_attn_decode_shared_tab_bf16": (I, [P, I, I, I, I, I, P, F, I, I, P, P, P, P, P, P, P, I, I, I, I, I, P, P, I, P, P]),
+    "dh_beam_retile": (I, [P, P, P, P, I, P, P, P, I, I, I, I, P, I, I, I, P]),
     "dh_attn_prefill_bf16": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "dh_dropout_bf16": (I, [P, P, P, I64, F, C.c_uint64, C.c_uint32, P, P]),
     "dh_swiglu_fwd_bf16": (I, [P, P, P, I64, P]),
@@ -198,6 +200,8 @@ SIGNATURES = {
     "dh_engine_set_bias": (I, [P, C.POINTER(BiasSpec), P]),
     "dh_engine_set_automaton": (I, [P, C.POINTER(AutomatonSpec), P]),
     "dh_engine_set_shared_prompt": (I, [P, I, P]),
+    "dh_engine_set_beam_tiles": (I, [P, P, I]),
+    "dh_engine_reserve_beam_tiles": (I, [P, I, I]),
     "dh_engine_graph_count": (I, [P, I]),
     "dh_engine_read": (I, [P, I, I, P, I64, P]),
     "dh_engine_set_timing": (I, [P, I]),

@@ -16,6 +16,9 @@ import torch
 MAX_BEAMS = 4             # DH_MAX_BEAMS: a row offers 2 W <= DH_MAX_TOP_LOGPROBS candidates
 MAX_BEAM_ROWS = 2048      # the streaming single-token step's row limit (engine.hip MAX_DECODE_ROWS)
 
+MAX_BEAM_TILES = 64       # DH_MAX_BEAM_TILES: tiles per row of a tile table
+KV_MODES = ("copy", "table")        # beam_search_batch(kv=), --beam_kv
+
 HISTORIES = ("host", "device")      # beam_search_batch(history=), --beam_history
 # the closing clause of the two refusals that device histories lift (no_repeat_ngram, stop sequences)
 HISTORY_HINT = '; history="device" (--beam_history device) keeps the beams\' histories on the device and lifts this'
@@ -42,6 +45,38 @@ def check_arguments(model, num_beams, n_utt: int) -> int:
     if model.cpu_rsqrt_vec_width != 0:
         raise ValueError(f"num_beams={W}: cpu_rsqrt_vec_width != 0 flags rows by their index within a call; a beam step has other rows")
     return W
+
+
+def beam_tiles(max_new: int, s_max: int) -> int:
+    """NT of a tile table: the 32-key tiles that the keys of max_new generated tokens can span, wherever in a tile the prompt ends,
+    held to the tiles of a cache of s_max positions (the engine's beam_tiles)."""
+    return min((int(max_new) + 30) // 32 + 1, int(s_max) // 32)
+
+
+def check_kv(kv, W: int, shared_prompt: bool, flag: str = 'kv="table"', needs: str = "shared_prompt=True") -> str:
+    """kv of a beam_search_batch call ("copy" or "table"), or a ValueError that says why "table" cannot run."""
+    if kv not in KV_MODES:
+        raise ValueError(f'kv is "copy" or "table", not {kv!r}')
+    if kv == "table":
+        if W < 2:
+            raise ValueError(f"{flag} names, per tile, the sibling beam whose KV slot holds it; num_beams={W} has no sibling (it needs "
+                             "num_beams >= 2)")
+        if not shared_prompt:
+            raise ValueError(f"{flag} reads the beams' private tiles inside the shared-prompt attention kernel; it needs {needs}")
+    return kv
+
+
+def resolve_slot(plane, row: int, pos: int, prompt_len: int, W: int) -> int:
+    """The KV slot that holds position `pos` of row `row`'s hypothesis under a tile table plane ("Beam KV tile table" of the header):
+    plane is [rows][NT] (nested lists or a CPU tensor).  A position in a whole prompt tile is read from slot u * W; a tile at or beyond
+    NT, like an entry outside 0 .. W-1 once clamped, from what the attention kernel reads."""
+    u, tile0, tile = row // W, prompt_len >> 5, pos >> 5
+    if tile < tile0:
+        return u * W
+    j = tile - tile0
+    if j >= len(plane[row]):
+        return row
+    return u * W + min(max(int(plane[row][j]), 0), W - 1)
 
 
 def check_length_penalty(length_penalty) -> float:
@@ -71,6 +106,7 @@ class BeamState:
         self._c = None
         self.fin_tok = None         # int32 [n_utt, W] beside fin_step, under a stop set only: the id that ended pool entry k
         self.history = None         # int64 [2, n_utt, W, max_new], under device histories only (history_buffer)
+        self.tiles = None           # int32 [2, n_utt, W, NT], under a tile table only (tile_table)
 
     def fin_tok_buffer(self) -> torch.Tensor:
         """fin_tok, made at its first use (-1: no entry): what dh_beam_select_bf16_stop and dh_engine_set_stop write."""
@@ -84,6 +120,17 @@ class BeamState:
         if self.history is None:
             self.history = torch.zeros((2, self.n_utt, self.W, self.max_new), dtype=torch.int64, device=self.device)
         return self.history
+
+    def tile_table(self, n_tiles: int) -> torch.Tensor:
+        """The tile table, made at its first use: int32 [2, n_utt, W, n_tiles], both planes the identity ([.., w, j] = w); plane
+        t & 1 names, behind step t, the sibling whose slot holds each tile of a row's hypothesis ("Beam KV tile table" of the header):
+        what dh_engine_set_beam_tiles takes."""
+        if self.tiles is None:
+            assert 1 <= n_tiles <= MAX_BEAM_TILES
+            w = torch.arange(self.W, dtype=torch.int32, device=self.device)
+            self.tiles = w.view(1, 1, self.W, 1).expand(2, self.n_utt, self.W, n_tiles).contiguous()
+        assert self.tiles.size(3) == n_tiles
+        return self.tiles
 
     def c_struct(self):
         from . import _lib
@@ -104,6 +151,9 @@ class BeamState:
         if self.history is not None:                          # device histories: per utterance the plane its last step wrote,
             planes = self.history.cpu()                       # [W][max_new], the first n_steps ids of a row are the beam's tokens
             out["history"] = [planes[(int(n) - 1) & 1, u].tolist() for u, n in enumerate(out["n_steps"])]
+        if self.tiles is not None:                            # a tile table: per utterance the plane its last step wrote, [W][NT]
+            planes = self.tiles.cpu()
+            out["tiles"] = [planes[(int(n) - 1) & 1, u].tolist() for u, n in enumerate(out["n_steps"])]
         return out
 
 

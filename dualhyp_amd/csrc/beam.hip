@@ -115,7 +115,93 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const int32_t* __restric
     }
 }
 
+// The KV step of a beam call under a tile table (include/dualhyp_hip.h, "Beam KV tile table"), in place of the re-parenting: behind the
+// selection of step t the rows' table rows move from plane (t - 1) & 1 to plane t & 1, and the one OPEN tile, tile0 + cur, of a row
+// that continues another beam is copied from the parent's slot — every closed tile stays where it was written.  Two launches through
+// the scratch, as the re-parenting: to_scratch, the parents' tile into the row's own scratch block and the table rows (they are read
+// from one plane and written to the other); then the block into the row's own slot.  So no launch reads what it writes and any parent
+// map is right.  grid (pieces of 256 units of ONE tile, tables x groups, rows): fixed, what there is to do is read from the device.
+// cache_tab: the engine's [2 L] table of cache pointers; null: the pair (c0, c1) of dh_beam_retile.  A row that continues itself, a
+// tile that just closed, an utterance that did not take step t and a parent outside 0 .. W-1 (taken as the row itself) copy nothing.
+__global__ __launch_bounds__(256) void beam_retile_kernel(bf16_t* const* __restrict__ cache_tab, bf16_t* c0, bf16_t* c1,
+                                                          bf16_t* __restrict__ scratch, int32_t* tab, int nt,
+                                                          const int32_t* __restrict__ beam_parent, const int32_t* __restrict__ n_steps,
+                                                          const int32_t* __restrict__ plen, const int32_t* __restrict__ step_dev, int step_arg,
+                                                          int W, int max_new, int n_groups, size_t block_elems, int tile_units,
+                                                          int cache_tiles, int to_scratch) {
+    const int row = blockIdx.z, u = row / W, w = row % W;
+    const int step = step_dev ? *step_dev : step_arg;
+    if (step < 1) return;                                            // step 0 is the caller's: both planes are its identity
+    const int P = plen[u];
+    const bool took = step < max_new && n_steps[u] == step + 1 && P >= 1;
+    int parent = w, tile0 = 0, cur = 0, nxt = 0;
+    if (took) {
+        parent = beam_parent[((size_t)u * max_new + step) * W + w];
+        parent = parent < 0 || parent >= W ? w : parent;
+        tile0 = P >> 5;
+        cur = ((P + step - 1) >> 5) - tile0;
+        nxt = ((P + step) >> 5) - tile0;
+    }
+    if (to_scratch && blockIdx.x == 0 && blockIdx.y == 0) {
+        const size_t plane = (size_t)gridDim.z * nt;
+        const int32_t* old = tab + (size_t)((step - 1) & 1) * plane;
+        int32_t* now = tab + (size_t)(step & 1) * plane;
+        for (int j = threadIdx.x; j < nt; j += 256) {
+            int v = w;                                               // j > cur: a tile no key has reached
+            if (!took) v = old[(size_t)row * nt + j];                // frozen rows read the same entries at either parity
+            else if (j < cur) v = old[((size_t)u * W + parent) * nt + j];
+            else if (j == cur) v = nxt == cur ? w : parent;          // still open: the row's own, copied below; just closed: where it is
+            now[(size_t)row * nt + j] = v;
+        }
+    }
+    if (!took || parent == w || nxt != cur) return;
+    if (tile0 + cur >= cache_tiles) return;                          // never past the (slot, group) block
+    const int unit = blockIdx.x * 256 + threadIdx.x;
+    if (unit >= tile_units) return;
+    const int g = blockIdx.y % n_groups;
+    typedef __attribute__((address_space(1))) bf16_t gbf16_t;
+    typedef __attribute__((address_space(1))) i32x4 gi32x4;
+    bf16_t* base = cache_tab ? cache_tab[blockIdx.y / n_groups] : (blockIdx.y / n_groups ? c1 : c0);
+    gbf16_t* cache = (gbf16_t*)base + (size_t)g * block_elems + ((size_t)(tile0 + cur) * tile_units + unit) * 8;
+    const size_t slot_elems = (size_t)n_groups * block_elems;
+    gbf16_t* sc = (gbf16_t*)scratch + (((size_t)row * gridDim.y + blockIdx.y) * tile_units + unit) * 8;
+    if (to_scratch) *(gi32x4*)sc = *(const gi32x4*)(cache + (size_t)(u * W + parent) * slot_elems);
+    else *(gi32x4*)(cache + (size_t)row * slot_elems) = *(const gi32x4*)sc;
+}
+
 }  // namespace
+
+int dh_beam_retile_impl(dh_bf16* const* cache_tab, dh_bf16* c0, dh_bf16* c1, int n_tabs, dh_bf16* scratch, int32_t* tab, int nt,
+                        const int32_t* beam_parent, const int32_t* n_steps, const int32_t* plen, const int32_t* step_dev, int step, int rows,
+                        int W, int max_new, int n_groups, int hs, int s_max, void* stream) {
+    const int tile_units = hs * 4;                                   // 16-byte units of a 32-key tile
+    const dim3 grid((tile_units + 255) / 256, n_tabs * n_groups, rows);
+    for (int to_scratch = 1; to_scratch >= 0; --to_scratch) {
+        hipLaunchKernelGGL(beam_retile_kernel, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t* const*)cache_tab, (bf16_t*)c0, (bf16_t*)c1,
+                           (bf16_t*)scratch, tab, nt, beam_parent, n_steps, plen, step_dev, step, W, max_new, n_groups, (size_t)s_max * hs,
+                           tile_units, s_max / 32, to_scratch);
+        DH_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int dh_beam_retile(dh_bf16* k_cache, dh_bf16* vT_cache, dh_bf16* scratch, int32_t* tile_tab, int n_tiles,
+                              const int32_t* beam_parent, const int32_t* n_steps, const int32_t* prompt_len, int n_utt, int W,
+                              int max_new_tokens, int step, const int32_t* step_dev, int n_groups, int hs, int s_max, void* stream) {
+    DH_CHECK(k_cache && vT_cache && scratch && tile_tab && beam_parent && n_steps && prompt_len, "dh_beam_retile: null argument");
+    DH_CHECK(W >= 2 && W <= MAX_W, "dh_beam_retile: W=%d beams, 2 .. %d are supported (a single beam continues itself)", W, MAX_W);
+    DH_CHECK(n_tiles >= 1 && n_tiles <= DH_MAX_BEAM_TILES, "dh_beam_retile: n_tiles=%d tiles per row, 1 .. %d are supported", n_tiles,
+             DH_MAX_BEAM_TILES);
+    DH_CHECK(n_utt >= 0 && max_new_tokens > 0 && n_groups > 0, "dh_beam_retile: bad shape");
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_beam_retile: head_size %d unsupported", hs);
+    DH_CHECK(s_max > 0 && s_max % 32 == 0, "dh_beam_retile: s_max=%d is no multiple of the 32 keys of a tile", s_max);
+    DH_CHECK(step_dev || (step >= 1 && step < max_new_tokens), "dh_beam_retile: step %d is outside the steps 1 .. %d that re-parent", step,
+             max_new_tokens - 1);
+    DH_CHECK((int64_t)n_utt * W <= 65535, "dh_beam_retile: %d x %d rows exceed a grid's 65535", n_utt, W);
+    if (n_utt == 0) return 0;
+    return dh_beam_retile_impl(nullptr, k_cache, vT_cache, 2, scratch, tile_tab, n_tiles, beam_parent, n_steps, prompt_len, step_dev, step,
+                               n_utt * W, W, max_new_tokens, n_groups, hs, s_max, stream);
+}
 
 int dh_beam_select_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_per_utt, int W, int max_new, int64_t eos_id, int step,
                         const int32_t* step_dev, const dh_beam_state& st, int32_t* cand_ids, float* cand_lp, const uint32_t* mask,

@@ -424,6 +424,12 @@ int dh_beam_top_hist_impl(const dh_bf16* logits, int vocab, int n_utt, int rows_
                           float* out_lp, const uint32_t* mask, int mask_ld, const int64_t* hist, int ngram, const int32_t* n_steps,
                           const int32_t* done, void* stream);
 
+// the table update and one-tile copy of a beam step under a tile table (beam.hip, beam_retile_kernel; "Beam KV tile table" of the
+// header): cache_tab, the engine's device table of n_tabs cache pointers, or null and the pair (c0, c1) with n_tabs = 2
+int dh_beam_retile_impl(dh_bf16* const* cache_tab, dh_bf16* c0, dh_bf16* c1, int n_tabs, dh_bf16* scratch, int32_t* tab, int nt,
+                        const int32_t* beam_parent, const int32_t* n_steps, const int32_t* plen, const int32_t* step_dev, int step, int rows,
+                        int W, int max_new, int n_groups, int hs, int s_max, void* stream);
+
 // hipFuncSetAttribute applies to the CURRENT device, and the launchers are entered from several host threads
 // (one engine per thread, dualhyp_amd/pipeline.py): remember per device that the attribute is set.  Two threads
 // racing on the first launch both set it, which is harmless.  `kernel` must be parenthesised if it contains commas.

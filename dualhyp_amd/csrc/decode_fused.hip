@@ -851,14 +851,27 @@ size_t attn_verify_lds(int S, int ncol) {
 // before the LoRA / rope prologue.
 // hs 64 is held to 128 VGPRs (four waves per SIMD, 4 spilled registers): with the 75 KiB of LDS of four rows x eight heads two blocks
 // share a CU; hs 96 and 128 run one block per CU (189 / 227 VGPRs, up to 112 / 148 KiB).
-template <int HS, int PMAX, int NW>
+// TAB ("Beam KV tile table" of the header; dh_attn_decode_shared_tab_bf16): row jj's private tile t is read from the slot of the sibling
+// that the table names, entry [plane][row][t - n_sh], plane (*step - 1) & 1 (null step: 0).  The block's r_max x nt entries go to LDS
+// in the prologue as SLOTS — the entry clamped to 0 .. N-1, then seq_slot of that sibling's row — and load_tile does one LDS lookup per
+// private tile; a tile at or behind nt is the row's own.  The append, the tile -> wave deal, the per-tile update and the combine are
+// the code of TAB = false, whose instantiations take an empty argument and compile to what they were.
+template <bool TAB>
+struct attn_tab_args {};
+template <>
+struct attn_tab_args<true> {
+    const int32_t* tab;       // [2][n_rows][ld]
+    const int32_t* step;      // device step counter, or null
+    int ld;                   // row stride = tiles per row
+};
+template <int HS, int PMAX, int NW, bool TAB = false>
 __global__ __launch_bounds__(NW * 64, HS == 64 ? 4 : 2) void attn_shared_fused_kernel(
     const float* __restrict__ qkv32, int n_part, int pairs, int n_rows, int ldq, int qkv_dim,
     const bf16_t* __restrict__ lora_b, float lora_scale, int split0, int split1,
     const bf16_t* __restrict__ cos, const bf16_t* __restrict__ sin, const int32_t* __restrict__ seq_slot,
     const int32_t* __restrict__ kv_len, const int32_t* __restrict__ prompt_len, bf16_t* __restrict__ k_cache,
     bf16_t* __restrict__ vT_cache, bf16_t* __restrict__ y, int n_head, int n_groups, int s_max, int N, int Gs, int n_cg,
-    int r_max, float scale) {
+    int r_max, float scale, attn_tab_args<TAB> ta) {
     constexpr int KS = HS / 16, DT = HS / 32, HALF = HS / 2, VC = 32, RMAX = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int g = blockIdx.x % n_groups, ucg = blockIdx.x / n_groups, cg = ucg % n_cg, u = ucg / n_cg;
@@ -879,11 +892,23 @@ __global__ __launch_bounds__(NW * 64, HS == 64 ? 4 : 2) void attn_shared_fused_k
     int* sSlot = sPos + RMAX;                                           // [8] its KV slot
     float* sPo = reinterpret_cast<float*>(sSlot + RMAX);                // [NW][HS][ncol] partial O^T
     constexpr int NT_ = NW * 64;
+    int* sTab = reinterpret_cast<int*>(sPo + NW * HS * (r_max * q_per_kv));   // TAB: [r_max][nt] slots of the rows' private tiles
+    int nt_tab = 0;
 
     if (tid < RMAX) {
         const int r = row0 + (tid < R ? tid : 0);
         sPos[tid] = tid < R ? kv_len[r] - 1 : 0;
         sSlot[tid] = seq_slot[r];
+    }
+    if constexpr (TAB) {
+        nt_tab = ta.ld;
+        const int plane = ta.step ? (*ta.step - 1) & 1 : 0;
+        const int32_t* tp = ta.tab + ((size_t)plane * n_rows + row0) * nt_tab;
+        for (int i = tid; i < R * nt_tab; i += NT_) {
+            int b = tp[i];
+            b = b < 0 ? 0 : (b >= N ? N - 1 : b);                       // nothing is trusted to index
+            sTab[i] = seq_slot[u * N + b];
+        }
     }
     __syncthreads();
     int n_sh = prompt_len[u] / 32;                                      // whole prompt tiles: the same bytes in every row's slot
@@ -915,7 +940,13 @@ __global__ __launch_bounds__(NW * 64, HS == 64 ? 4 : 2) void attn_shared_fused_k
     Tile tl;
     // the caches are in MFMA-fragment order (common.h): a tile is 8 coalesced 1-KiB loads
     auto load_tile = [&](Tile& T, int t, int jj) {
-        const size_t off = t < n_sh ? sh_off : ((size_t)sSlot[jj] * n_groups + g) * blk;
+        size_t off;
+        if constexpr (TAB) {
+            const int j = t - n_sh;
+            off = t < n_sh ? sh_off : ((size_t)(j < nt_tab ? sTab[jj * nt_tab + j] : sSlot[jj]) * n_groups + g) * blk;
+        } else {
+            off = t < n_sh ? sh_off : ((size_t)sSlot[jj] * n_groups + g) * blk;
+        }
         const bf16_t* kbase = k_cache + off;
         const bf16_t* vbase = vT_cache + off;
 #pragma unroll
@@ -1114,6 +1145,11 @@ template <int HS>
 size_t attn_shared_lds(int r_max, int ncol) {
     constexpr int NW = attn_fused_waves<HS>();
     return 32 * HS * 2 + (size_t)(2 * r_max * HS + 48 * r_max + 32 + 2 * NW * 32 + 16 + NW * HS * ncol) * sizeof(float);
+}
+// the table variant's: the r_max x nt slots behind the partial outputs
+template <int HS>
+size_t attn_shared_tab_lds(int r_max, int ncol, int nt) {
+    return attn_shared_lds<HS>(r_max, ncol) + (size_t)r_max * nt * sizeof(int);
 }
 
 // --------------------------------------------------------------------------- finish + norm
@@ -1558,33 +1594,50 @@ static int64_t g_attn_shared_launches = 0;
 extern "C" int64_t dh_attn_shared_launch_count(void) { return g_attn_shared_launches; }
 
 // dh_attn_decode_fused_bf16 over the same rows, the whole prompt tiles of an utterance streamed once per block of its rows
-// (include/dualhyp_hip.h, "Shared-prompt attention"; the engine's step under dh_engine_set_shared_prompt launches it)
-extern "C" int dh_attn_decode_shared_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
-                                          const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
-                                          const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
-                                          dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int group_rows,
-                                          const int32_t* prompt_len, void* stream) {
-    DH_CHECK(qkv32 && cos && sin && seq_slot && kv_len && k_cache && vT_cache && y, "dh_attn_decode_shared_bf16: null argument");
-    DH_CHECK(prompt_len, "dh_attn_decode_shared_bf16: null prompt_len (a device array of n_seq / group_rows int32)");
-    DH_CHECK(group_rows >= 2 && group_rows <= 8, "dh_attn_decode_shared_bf16: group_rows = %d rows per utterance, 2 .. 8 are served", group_rows);
-    DH_CHECK(n_seq % group_rows == 0, "dh_attn_decode_shared_bf16: n_seq = %d rows are not group_rows = %d per utterance", n_seq, group_rows);
-    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DCOLS, "dh_attn_decode_shared_bf16: bad head counts");
-    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "dh_attn_decode_shared_bf16: head_size %d unsupported", hs);
-    DH_CHECK(s_max % 64 == 0 && n_part >= 1 && n_part <= MAXP, "dh_attn_decode_shared_bf16: bad s_max / n_part");
-    DH_CHECK(qkv_dim == (n_head + 2 * n_groups) * hs, "dh_attn_decode_shared_bf16: qkv_dim mismatch");
-    DH_CHECK(lora_b == nullptr || n_ext >= 48, "dh_attn_decode_shared_bf16: LoRA needs the 48 x·A^T columns");
+// (include/dualhyp_hip.h, "Shared-prompt attention"; the engine's step under dh_engine_set_shared_prompt launches it).  tab != null:
+// the table variant ("Beam KV tile table"), `name` the entry that refuses.
+static int attn_shared_call(const char* name, const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
+                            const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos, const dh_bf16* sin,
+                            const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache, dh_bf16* vT_cache, dh_bf16* y, int n_head,
+                            int n_groups, int hs, int s_max, int group_rows, const int32_t* prompt_len, const int32_t* tab, int tab_ld,
+                            const int32_t* step_dev, void* stream) {
+    DH_CHECK(qkv32 && cos && sin && seq_slot && kv_len && k_cache && vT_cache && y, "%s: null argument", name);
+    DH_CHECK(prompt_len, "%s: null prompt_len (a device array of n_seq / group_rows int32)", name);
+    DH_CHECK(group_rows >= 2 && group_rows <= 8, "%s: group_rows = %d rows per utterance, 2 .. 8 are served", name, group_rows);
+    DH_CHECK(n_seq % group_rows == 0, "%s: n_seq = %d rows are not group_rows = %d per utterance", name, n_seq, group_rows);
+    DH_CHECK(n_groups > 0 && n_head % n_groups == 0 && n_head / n_groups <= DCOLS, "%s: bad head counts", name);
+    DH_CHECK(hs == 64 || hs == 96 || hs == 128, "%s: head_size %d unsupported", name, hs);
+    DH_CHECK(s_max % 64 == 0 && n_part >= 1 && n_part <= MAXP, "%s: bad s_max / n_part", name);
+    DH_CHECK(qkv_dim == (n_head + 2 * n_groups) * hs, "%s: qkv_dim mismatch", name);
+    DH_CHECK(lora_b == nullptr || n_ext >= 48, "%s: LoRA needs the 48 x·A^T columns", name);
+    DH_CHECK(!tab || (tab_ld >= 1 && tab_ld <= DH_MAX_BEAM_TILES), "%s: a tile table of %d tiles per row, 1 .. %d are served", name, tab_ld,
+             DH_MAX_BEAM_TILES);
     if (n_seq <= 0) return 0;
     const float scale = 1.0f / sqrtf((float)hs);
     hipStream_t s = (hipStream_t)stream;
     const int q_per_kv = n_head / n_groups, N = group_rows;
     const int Gs = 32 / q_per_kv, n_cg = (N + Gs - 1) / Gs, r_max = N < Gs ? N : Gs, ncol = r_max * q_per_kv;
     dim3 grid((n_seq / N) * n_cg * n_groups);
+    const attn_tab_args<true> ta{tab, step_dev, tab_ld};
 #define SHR_LAUNCH(HSV, PM)                                                                                           \
     hipLaunchKernelGGL((attn_shared_fused_kernel<HSV, PM, attn_fused_waves<HSV>()>), grid, dim3(64 * attn_fused_waves<HSV>()), attn_shared_lds<HSV>(r_max, ncol), s, qkv32, n_part, pairs, \
                        n_seq, qkv_dim + n_ext, qkv_dim, lora_b, lora_scale, split0, split1, cos, sin, seq_slot, kv_len, prompt_len, k_cache,  \
-                       vT_cache, y, n_head, n_groups, s_max, N, Gs, n_cg, r_max, scale)
+                       vT_cache, y, n_head, n_groups, s_max, N, Gs, n_cg, r_max, scale, attn_tab_args<false>{})
+#define SHR_TAB_LAUNCH(HSV, PM)                                                                                       \
+    hipLaunchKernelGGL((attn_shared_fused_kernel<HSV, PM, attn_fused_waves<HSV>(), true>), grid, dim3(64 * attn_fused_waves<HSV>()), attn_shared_tab_lds<HSV>(r_max, ncol, tab_ld), s, qkv32, n_part, pairs, \
+                       n_seq, qkv_dim + n_ext, qkv_dim, lora_b, lora_scale, split0, split1, cos, sin, seq_slot, kv_len, prompt_len, k_cache,  \
+                       vT_cache, y, n_head, n_groups, s_max, N, Gs, n_cg, r_max, scale, ta)
 #define SHR_HS(HSV)                                                                                                   \
     do {                                                                                                              \
+        if (tab) {                                                                                                    \
+            DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 2, attn_fused_waves<HSV>(), true>), attn_shared_tab_lds<HSV>(8, 32, DH_MAX_BEAM_TILES));  \
+            DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 8, attn_fused_waves<HSV>(), true>), attn_shared_tab_lds<HSV>(8, 32, DH_MAX_BEAM_TILES));  \
+            DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 16, attn_fused_waves<HSV>(), true>), attn_shared_tab_lds<HSV>(8, 32, DH_MAX_BEAM_TILES)); \
+            if (n_part <= 2) SHR_TAB_LAUNCH(HSV, 2);                                                                  \
+            else if (n_part <= 8) SHR_TAB_LAUNCH(HSV, 8);                                                             \
+            else SHR_TAB_LAUNCH(HSV, 16);                                                                             \
+            break;                                                                                                    \
+        }                                                                                                             \
         DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 2, attn_fused_waves<HSV>()>), attn_shared_lds<HSV>(8, 32));    \
         DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 8, attn_fused_waves<HSV>()>), attn_shared_lds<HSV>(8, 32));    \
         DH_MAX_LDS_ONCE((attn_shared_fused_kernel<HSV, 16, attn_fused_waves<HSV>()>), attn_shared_lds<HSV>(8, 32));   \
@@ -1596,10 +1649,34 @@ extern "C" int dh_attn_decode_shared_bf16(const float* qkv32, int n_part, int pa
     else if (hs == 96) SHR_HS(96);
     else SHR_HS(128);
 #undef SHR_HS
+#undef SHR_TAB_LAUNCH
 #undef SHR_LAUNCH
     DH_LAUNCH_CHECK();
     ++g_attn_shared_launches;
     return 0;
+}
+
+extern "C" int dh_attn_decode_shared_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
+                                          const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
+                                          const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
+                                          dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int group_rows,
+                                          const int32_t* prompt_len, void* stream) {
+    return attn_shared_call("dh_attn_decode_shared_bf16", qkv32, n_part, pairs, n_seq, qkv_dim, n_ext, lora_b, lora_scale, split0, split1,
+                            cos, sin, seq_slot, kv_len, k_cache, vT_cache, y, n_head, n_groups, hs, s_max, group_rows, prompt_len, nullptr, 0,
+                            nullptr, stream);
+}
+
+// the same call with the rows' private tiles read through a tile table ("Beam KV tile table" of the header)
+extern "C" int dh_attn_decode_shared_tab_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
+                                              const dh_bf16* lora_b, float lora_scale, int split0, int split1, const dh_bf16* cos,
+                                              const dh_bf16* sin, const int32_t* seq_slot, const int32_t* kv_len, dh_bf16* k_cache,
+                                              dh_bf16* vT_cache, dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int group_rows,
+                                              const int32_t* prompt_len, const int32_t* tile_tab, int tab_ld, const int32_t* step_dev,
+                                              void* stream) {
+    DH_CHECK(tile_tab, "dh_attn_decode_shared_tab_bf16: null tile table (dh_attn_decode_shared_bf16 is the entry without one)");
+    return attn_shared_call("dh_attn_decode_shared_tab_bf16", qkv32, n_part, pairs, n_seq, qkv_dim, n_ext, lora_b, lora_scale, split0,
+                            split1, cos, sin, seq_slot, kv_len, k_cache, vT_cache, y, n_head, n_groups, hs, s_max, group_rows, prompt_len,
+                            tile_tab, tab_ld, step_dev, stream);
 }
 
 // finish_norm_kernel<, true> from this many rows on.  tools/sweep_finish.py, d 2048, us per launch, loads behind | ahead of the

@@ -55,6 +55,12 @@ struct dh_engine {
     int32_t* copy_dst = nullptr;                        // [B]: the destination slots of a dh_engine_copy_prefix call
     bf16_t* beam_scratch = nullptr;                     // dh_engine_reserve_beams: [row][2 L x G][tiles][hs * 32], the re-parenting's way station
     size_t beam_scratch_elems = 0;
+    int32_t* beam_tab = nullptr;                        // dh_engine_set_beam_tiles: the caller's [2][n_utt * W][beam_tab_nt] tile table (null: off)
+    int beam_tab_nt = 0;
+    int32_t* step_beam_tab = nullptr;                   // the same two for the step being launched or captured, as step_shared_rows
+    int step_beam_tab_nt = 0;
+    bf16_t* beam_tile_scratch = nullptr;                // dh_engine_reserve_beam_tiles: [row][2 L x G][hs * 32], the open tile's way station
+    size_t beam_tile_scratch_elems = 0;
     int32_t* beam_cand_ids = nullptr;                   // [B, 2 W_max] candidates of a beam step's rows (dh_beam_select_bf16's workspace)
     float* beam_cand_lp = nullptr;
     bf16_t** cache_tab = nullptr;                       // [2 L] device table, written once: K cache of layer l at 2l, V^T cache at 2l + 1
@@ -96,6 +102,8 @@ struct dh_engine {
         // dh_engine_decode_beam: W beams (0 in every other key) and the call's state arrays; length = n_steps, limit = prompt_len,
         // n_seq = n_utt * W rows; the ending ids of dh_engine_set_stop; the history planes and their ban of dh_engine_set_beam_history
         int beam_w = 0; dh_beam_state beam{}; int32_t* stop_fin_tok = nullptr; int64_t* beam_hist = nullptr; int beam_ngram = 0;
+        // the tile table of dh_engine_set_beam_tiles and its tiles per row (null / 0: the re-parenting copy)
+        int32_t* beam_tab = nullptr; int beam_tab_nt = 0;
         // dh_engine_set_shared_prompt: rows per utterance (0 in a key whose step runs the single-token attention) and the prompt lengths
         int shared_rows = 0; const int32_t* shared_plen = nullptr;
         bool operator==(const GKey& k) const {
@@ -105,7 +113,7 @@ struct dh_engine {
                    n_all == k.n_all && max_new == k.max_new && spec == k.spec && drafts == k.drafts && counters == k.counters &&
                    spec_draw == k.spec_draw &&
                    ctl == k.ctl && beam_w == k.beam_w && stop_fin_tok == k.stop_fin_tok && beam_hist == k.beam_hist &&
-                   beam_ngram == k.beam_ngram && shared_rows == k.shared_rows && shared_plen == k.shared_plen && memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
+                   beam_ngram == k.beam_ngram && beam_tab == k.beam_tab && beam_tab_nt == k.beam_tab_nt && shared_rows == k.shared_rows && shared_plen == k.shared_plen && memcmp(&beam, &k.beam, sizeof(beam)) == 0;         // a struct of pointers: no padding
         }
     };
     struct GEntry { GKey key; hipGraphExec_t exec; uint64_t used; };
@@ -715,6 +723,11 @@ int run_layers_decode(dh_engine* e, const int64_t* ids, int n_seq, const uint8_t
             if ((rc = dh_attn_verify_fused_impl(e->part32, np, pairs, n_seq / spec_S, spec_S, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale,
                                                 d, d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
                                                 e->s_max, p_max, s))) return rc;
+        } else if (e->step_shared_rows && e->step_beam_tab) {
+            if ((rc = dh_attn_decode_shared_tab_bf16(e->part32, np, pairs, n_seq, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale, d,
+                                                     d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
+                                                     e->s_max, e->step_shared_rows, e->step_shared_plen, e->step_beam_tab,
+                                                     e->step_beam_tab_nt, e->step_dev, s))) return rc;
         } else if (e->step_shared_rows) {
             if ((rc = dh_attn_decode_shared_bf16(e->part32, np, pairs, n_seq, e->qkv_dim, ext1, W.attn_lora_b, D.lora_scale, d,
                                                  d + e->kv_dim, D.rope_cos, D.rope_sin, m.seq_slot, m.kv, kc, vtc, e->att, H, G, hs,
@@ -1041,6 +1054,10 @@ int beam_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if ((rc = dh_beam_select_impl(e->logits, D.vocab, rows / W, W, W, k.max_new, k.eos, 0, e->step_dev, k.beam, e->beam_cand_ids,
                                   e->beam_cand_lp, k.ctl.mask, k.ctl.mask_ld, k.ctl.stop, k.stop_fin_tok, s, k.beam_hist, k.beam_ngram))) return rc;
     if (W == 1) return 0;                                   // a single beam continues itself
+    if (k.beam_tab)                                         // "Beam KV tile table": the table rows and the one open tile
+        return dh_beam_retile_impl(e->cache_tab, nullptr, nullptr, 2 * D.n_layer, e->beam_tile_scratch, k.beam_tab, k.beam_tab_nt,
+                                   k.beam.beam_parent, k.length, k.limit, e->step_dev, 0, rows, W, k.max_new, D.n_groups, D.head_size,
+                                   e->s_max, s);
     const int tile_units = D.head_size * 4, nt_max = std::min(beam_tiles(k.max_new), e->s_max / 32);
     const dim3 grid(cdiv(nt_max * tile_units, 256), 2 * D.n_layer * D.n_groups, rows);
     for (int to_scratch = 1; to_scratch >= 0; --to_scratch) {
@@ -1117,9 +1134,13 @@ int decode_step(dh_engine* e, const dh_engine::GKey& k, hipStream_t s) {
     if (k.spec) return verify_step(e, k, s);
     e->step_shared_rows = k.shared_rows;                // what run_layers_decode launches for this step's attention
     e->step_shared_plen = k.shared_plen;
+    e->step_beam_tab = k.beam_tab;
+    e->step_beam_tab_nt = k.beam_tab_nt;
     const int rc = k.beam_w ? beam_step(e, k, s) : plain_step(e, k, s);
     e->step_shared_rows = 0;
     e->step_shared_plen = nullptr;
+    e->step_beam_tab = nullptr;
+    e->step_beam_tab_nt = 0;
     return rc;
 }
 
@@ -1227,7 +1248,7 @@ extern "C" void dh_engine_destroy(dh_engine* e) {
     for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
     void* ptrs[] = {e->kc, e->vtc, e->k8, e->v8, e->ke, e->ve, e->x, e->xn, e->qkv, e->qrot, e->att, e->xa, e->act, e->xlast, e->logits,
                     e->tok_slot, e->tok_pos, e->seq_meta, e->last_row, e->last_meta, e->att_last, e->xn_last, e->act_last, e->step_dev, e->slot_list, e->copy_dst, e->cache_tab, e->dec_ids, e->dec_work,
-                    e->beam_scratch, e->beam_cand_ids, e->beam_cand_lp,
+                    e->beam_scratch, e->beam_tile_scratch, e->beam_cand_ids, e->beam_cand_lp,
                     e->row_tail, e->last_tail, e->ones, e->part32, e->xq, e->xscale, e->xq6, e->xs6};
     for (void* p : ptrs)
         if (p) hipFree(p);
@@ -1519,14 +1540,10 @@ extern "C" int dh_engine_decode_spec_draw(dh_engine* e, int64_t* tokens, int tok
                             counters, n_steps, temperature, top_k, eos_id, seed, first_step, stream);
 }
 
-extern "C" int dh_engine_reserve_beams(dh_engine* e, int W, int max_new_tokens) {
-    DH_CHECK(e, "dh_engine_reserve_beams: null engine");
-    DH_CHECK(W >= 1 && W <= DH_MAX_BEAMS && max_new_tokens > 0, "dh_engine_reserve_beams: W=%d (1 .. %d) beams, %d new tokens", W,
-             DH_MAX_BEAMS, max_new_tokens);
-    DH_CHECK(!e->kv8 && !e->fp8, "dh_engine_reserve_beams: an fp8 engine has no beam step");
-    const int nt_max = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
-    const size_t need = W == 1 ? 0 : (size_t)e->max_batch * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32;
-    if (e->beam_cand_ids && need <= e->beam_scratch_elems) return 0;
+// dh_engine_reserve_beams and dh_engine_reserve_beam_tiles (`name`): the candidates' workspace, and `need` elements in the scratch
+// *scratch of *have elements (`what` it is, for the refusal)
+static int reserve_beam_ws(dh_engine* e, const char* name, const char* what, size_t need, bf16_t** scratch, size_t* have) {
+    if (e->beam_cand_ids && need <= *have) return 0;
     // the captured steps hold the old addresses
     DH_HIP(hipDeviceSynchronize());
     for (auto& g : e->graphs) hipGraphExecDestroy(g.exec);
@@ -1534,22 +1551,55 @@ extern "C" int dh_engine_reserve_beams(dh_engine* e, int W, int max_new_tokens) 
     if (!e->beam_cand_ids) {
         const size_t n = (size_t)e->max_batch * 2 * DH_MAX_BEAMS;
         if (dmalloc(e, &e->beam_cand_ids, n) || dmalloc(e, &e->beam_cand_lp, n)) {
-            dh_set_error("dh_engine_reserve_beams: device allocation failed (%s)", dh_last_error());
+            dh_set_error("%s: device allocation failed (%s)", name, dh_last_error());
             return 2;
         }
     }
-    if (need > e->beam_scratch_elems) {      // on failure the engine keeps the scratch it had
+    if (need > *have) {      // on failure the engine keeps the scratch it had
         bf16_t* p = nullptr;
         if (hipMalloc((void**)&p, need * sizeof(bf16_t)) != hipSuccess) {
             (void)hipGetLastError();
-            dh_set_error("dh_engine_reserve_beams: %.2f GiB of re-parenting scratch could not be allocated", need * 2 / 1073741824.0);
+            dh_set_error("%s: %.2f GiB of %s scratch could not be allocated", name, need * 2 / 1073741824.0, what);
             return 2;
         }
-        hipFree(e->beam_scratch);
-        e->dev_bytes += (int64_t)((need - e->beam_scratch_elems) * sizeof(bf16_t));
-        e->beam_scratch = p;
-        e->beam_scratch_elems = need;
+        hipFree(*scratch);
+        e->dev_bytes += (int64_t)((need - *have) * sizeof(bf16_t));
+        *scratch = p;
+        *have = need;
     }
+    return 0;
+}
+
+extern "C" int dh_engine_reserve_beams(dh_engine* e, int W, int max_new_tokens) {
+    DH_CHECK(e, "dh_engine_reserve_beams: null engine");
+    DH_CHECK(W >= 1 && W <= DH_MAX_BEAMS && max_new_tokens > 0, "dh_engine_reserve_beams: W=%d (1 .. %d) beams, %d new tokens", W,
+             DH_MAX_BEAMS, max_new_tokens);
+    DH_CHECK(!e->kv8 && !e->fp8, "dh_engine_reserve_beams: an fp8 engine has no beam step");
+    const int nt_max = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
+    const size_t need = W == 1 ? 0 : (size_t)e->max_batch * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32;
+    return reserve_beam_ws(e, "dh_engine_reserve_beams", "re-parenting", need, &e->beam_scratch, &e->beam_scratch_elems);
+}
+
+extern "C" int dh_engine_reserve_beam_tiles(dh_engine* e, int W, int max_new_tokens) {
+    DH_CHECK(e, "dh_engine_reserve_beam_tiles: null engine");
+    DH_CHECK(W >= 1 && W <= DH_MAX_BEAMS && max_new_tokens > 0, "dh_engine_reserve_beam_tiles: W=%d (1 .. %d) beams, %d new tokens", W,
+             DH_MAX_BEAMS, max_new_tokens);
+    DH_CHECK(!e->kv8 && !e->fp8, "dh_engine_reserve_beam_tiles: an fp8 engine has no beam step");
+    const int nt = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
+    DH_CHECK(nt <= DH_MAX_BEAM_TILES, "dh_engine_reserve_beam_tiles: %d new tokens span %d tiles, a tile table holds %d per row",
+             max_new_tokens, nt, DH_MAX_BEAM_TILES);
+    const size_t need = W == 1 ? 0 : (size_t)e->max_batch * 2 * e->d.n_layer * e->d.n_groups * e->d.head_size * 32;
+    return reserve_beam_ws(e, "dh_engine_reserve_beam_tiles", "one-tile", need, &e->beam_tile_scratch, &e->beam_tile_scratch_elems);
+}
+
+extern "C" int dh_engine_set_beam_tiles(dh_engine* e, int32_t* tab, int n_tiles) {
+    DH_CHECK(e, "dh_engine_set_beam_tiles: null engine");
+    DH_CHECK(!tab || (n_tiles >= 1 && n_tiles <= DH_MAX_BEAM_TILES), "dh_engine_set_beam_tiles: n_tiles=%d tiles per row, 1 .. %d are supported",
+             n_tiles, DH_MAX_BEAM_TILES);
+    DH_CHECK(!tab || !e->fp8, "dh_engine_set_beam_tiles: an fp8 or MXFP4 engine has no beam step; not supported");
+    DH_CHECK(!tab || !e->kv8, "dh_engine_set_beam_tiles: the table names bf16 cache tiles; an fp8 KV cache is not supported");
+    e->beam_tab = tab;
+    e->beam_tab_nt = tab ? n_tiles : 0;
     return 0;
 }
 
@@ -1593,8 +1643,18 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
              "utterance, the call has W=%d beams", e->shared_rows, W);
     if (int rc = check_shared_call(e, "dh_engine_decode_beam", (int)rows, e->shared_rows)) return rc;
     const int nt_max = std::min(beam_tiles(max_new_tokens), e->s_max / 32);
-    DH_CHECK(e->beam_cand_ids && (W == 1 || (size_t)rows * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32 <= e->beam_scratch_elems),
-             "dh_engine_decode_beam: the re-parenting scratch is too small for W=%d and %d new tokens (dh_engine_reserve_beams)", W, max_new_tokens);
+    if (e->beam_tab) {                                  // "Beam KV tile table"
+        DH_CHECK(W >= 2, "dh_engine_decode_beam: a tile table is set and W=1; a single beam continues itself and has no sibling slot");
+        DH_CHECK(e->shared_rows == W, "dh_engine_decode_beam: a tile table is set; its attention is the shared-prompt kernel's variant, which "
+                 "needs dh_engine_set_shared_prompt with group_rows = W = %d (it is %d)", W, e->shared_rows);
+        DH_CHECK(e->beam_tab_nt == nt_max, "dh_engine_decode_beam: the tile table holds %d tiles per row, %d new tokens in a cache of %d "
+                 "positions span %d", e->beam_tab_nt, max_new_tokens, e->s_max, nt_max);
+        DH_CHECK(e->beam_cand_ids && (size_t)rows * 2 * e->d.n_layer * e->d.n_groups * e->d.head_size * 32 <= e->beam_tile_scratch_elems,
+                 "dh_engine_decode_beam: a tile table is set without its one-tile scratch for W=%d (dh_engine_reserve_beam_tiles)", W);
+    } else {
+        DH_CHECK(e->beam_cand_ids && (W == 1 || (size_t)rows * 2 * e->d.n_layer * e->d.n_groups * nt_max * e->d.head_size * 32 <= e->beam_scratch_elems),
+                 "dh_engine_decode_beam: the re-parenting scratch is too small for W=%d and %d new tokens (dh_engine_reserve_beams)", W, max_new_tokens);
+    }
     if (n_steps <= 0) return 0;
     e->seq_slot = e->seq_meta;
     hipStream_t s = (hipStream_t)stream;
@@ -1606,6 +1666,7 @@ extern "C" int dh_engine_decode_beam(dh_engine* e, const dh_beam_state* st, cons
     key.ctl = step_ctl(e, STEP_BEAM, 0);
     key.shared_rows = e->shared_rows; key.shared_plen = e->shared_plen;
     key.beam_w = W; key.beam = *st; key.stop_fin_tok = e->stop_fin_tok; key.beam_hist = e->beam_hist; key.beam_ngram = e->beam_hist_ngram;
+    key.beam_tab = e->beam_tab; key.beam_tab_nt = e->beam_tab_nt;
     return launch_steps(e, key, n_steps, s);
 }
 

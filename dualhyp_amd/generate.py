@@ -120,10 +120,10 @@ def _engine_settings(settings, take_back=None):
     """What a call hands the engine for its captured decode steps, and takes back behind them: the buffers are the call's.  settings:
     (on, set, reset) triples, set in their order and reset in take_back's (None: the same), each only where the call uses it — every
     one is part of a captured step's key, so without it the call runs the steps it always ran."""
-    for on, set_, _ in settings:
-        if on:
-            set_()
     try:
+        for on, set_, _ in settings:      # a setter that refuses leaves nothing set: the ones before it are taken back below
+            if on:
+                set_()
         yield
     finally:
         for on, _, reset in settings if take_back is None else take_back:
@@ -695,7 +695,7 @@ def sample_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: in
 def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_tokens: int, *, num_beams: int, eos_id: Optional[int] = None,
                       length_penalty: float = 1.0, prefill_batch: int = 32, timing: Optional[dict] = None, return_state: bool = False,
                       token_mask=None, no_repeat_ngram: int = 0, stop=None, bias=None, history: str = "host",
-                      shared_prompt: bool = False):
+                      shared_prompt: bool = False, kv: str = "copy"):
     """Beam search over num_beams = W (1..4) hypotheses per prompt, exact by definition (include/dualhyp_hip.h, "Beam search";
     tests/beam_reference.py is the host model): result[i] is the ranked list of at most W hypotheses of prompt i, each a dict of
       tokens          1-D int64 CPU tensor, prompt + generated, cut before the EOS,
@@ -745,7 +745,15 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     shared_prompt (W >= 2, either `history`): the beam steps' attention reads an utterance's whole 32-key prompt tiles once per block
     of its W rows, from slot u * W (include/dualhyp_hip.h, "Shared-prompt attention"; the re-parenting moves only the tiles behind
     them) — the same bits, so the same tokens, parents, scores and pool.  False (the default): the launches the call always made.
-    Refused for W = 1 and, as the whole call is, for fp8 models."""
+    Refused for W = 1 and, as the whole call is, for fp8 models.
+
+    kv: "copy" (the default: the re-parenting above, the launches the call always made) or "table" (include/dualhyp_hip.h, "Beam KV
+    tile table"; needs shared_prompt=True and W >= 2, a ValueError otherwise): two int32 planes name, per row and tile, the sibling
+    slot that holds the tile; a beam step's attention reads every closed tile where it was written and the re-parenting copies only
+    the open tile of the rows that continue another beam — the same keys, so the same tokens, parents, scores and pool.  timing gains
+    beam_kv and beam_copied_tiles (the (row, tile) pairs the re-parenting copied, each through every layer, both caches and every
+    group); the state of return_state carries the planes (host["tiles"][u][w] is live beam w's row of the plane the last step
+    wrote; beam.resolve_slot reads a position's slot off it)."""
     if history not in _beam.HISTORIES:
         raise ValueError(f'history is "host" or "device", not {history!r}')
     on_device = history == "device"
@@ -765,6 +773,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
                          "sampling kernels cannot form a beam's ban set; it runs under generate_batch and generate_stream" + _beam.HISTORY_HINT)
     W = _beam.check_arguments(model, num_beams, B)
     shared_prompt = check_shared_prompt(model, shared_prompt, W, f"num_beams={W}")
+    kv = _beam.check_kv(kv, W, shared_prompt)
     length_penalty = _beam.check_length_penalty(length_penalty)
     lens = [int(p.numel()) for p in prompts]
     T_max = max(lens)
@@ -778,8 +787,16 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
     rows = B * W
     eng = model.engine(rows, need_pos, max(rows, max(sum(lens[a:b]) for a, b in chunks)), exact=rows > prefill_batch)
     eng.set_rsqrt_emulation(0, whole_call=False)
-    eng.reserve_beams(W, max_new_tokens)
     state = _beam.BeamState(B, W, max_new_tokens, dev)
+    tiles = None
+    if kv == "table":
+        n_tiles = _beam.beam_tiles(max_new_tokens, eng.s_max)
+        if n_tiles > _beam.MAX_BEAM_TILES:
+            raise ValueError(f'kv="table": {max_new_tokens} new tokens span {n_tiles} tiles, a tile table holds {_beam.MAX_BEAM_TILES} per row')
+        eng.reserve_beam_tiles(W, max_new_tokens)
+        tiles = state.tile_table(n_tiles)
+    else:
+        eng.reserve_beams(W, max_new_tokens)
     hist = state.history_buffer() if on_device else None
     plen = torch.tensor(lens, dtype=torch.int32, device=dev)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
@@ -800,6 +817,7 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
             (mask is not None, lambda: eng.set_token_mask(mask), lambda: eng.set_token_mask(None)),
             (stop is not None, lambda: eng.set_stop(stop, plen if stop.sequences else None, state.fin_tok_buffer()), lambda: eng.set_stop(None)),
             (on_device, lambda: eng.set_beam_history(hist, ngram), lambda: eng.set_beam_history(None)),
+            (tiles is not None, lambda: eng.set_beam_tiles(tiles), lambda: eng.set_beam_tiles(None)),
             _shared_prompt_setting(eng, shared_prompt, W, plen)]):
         while step < max_new_tokens:
             c = max_new_tokens - step if eos_id is None and stop is None else min(EOS_CHECK_EVERY, max_new_tokens - step)
@@ -818,6 +836,12 @@ def beam_search_batch(model: GPT, prompts: Sequence[torch.Tensor], max_new_token
         _add_timing(timing, prefill_ms=ev[0].elapsed_time(ev[1]), decode_ms=ev[1].elapsed_time(ev[2]), decode_steps=step - 1,
                     decode_row_steps=rows * (step - 1), prefill_tokens=sum(lens), beam_step_rows=took, beam_copied_rows=moved)
         timing["shared_prompt"] = shared_prompt
+        timing["beam_kv"] = kv
+        # the (row, tile) pairs copied: under the table the open tile of a row that continues another beam, unless the step closed it;
+        # under the copy every tile that holds a generated key
+        timing["beam_copied_tiles"] = sum(
+            (1 if (lens[u] + t) >> 5 == (lens[u] + t - 1) >> 5 else 0) if kv == "table" else ((lens[u] + t - 1) >> 5) - (lens[u] >> 5) + 1
+            for u in range(B) for t in range(1, h["n_steps"][u]) for w, p in enumerate(h["beam_parent"][u][t]) if p != w)
     out = []
     for u in range(B):
         hyps = _beam.hypotheses(h, u, W, length_penalty, eos_id=eos_id)

@@ -510,6 +510,24 @@ class _Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_reserve_beams(self.handle, int(num_beams), int(max_new_tokens)))
 
+    def reserve_beam_tiles(self, num_beams: int, max_new_tokens: int) -> None:
+        """reserve_beams for decode_beam calls under a tile table (set_beam_tiles): the candidates' workspace and a scratch of one
+        tile per (row, layer's K and V^T, group), whatever max_new_tokens is (dh_engine_reserve_beam_tiles)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dh_engine_reserve_beam_tiles(self.handle, int(num_beams), int(max_new_tokens)))
+
+    def set_beam_tiles(self, table: Optional[torch.Tensor]) -> None:
+        """The tile table of later decode_beam calls (dh_engine_set_beam_tiles; include/dualhyp_hip.h, "Beam KV tile table"): the int32
+        [2, n_utt, W, NT] planes of a dualhyp_amd.beam.BeamState (tile_table()); None turns it off.  While set, a beam step's attention
+        reads every closed tile from the sibling slot that holds it and its re-parenting copies the one open tile; it needs
+        set_shared_prompt(W, ...) and reserve_beam_tiles.  Part of a beam step's key.  The caller keeps the planes alive while set."""
+        if table is not None and (table.dtype != torch.int32 or not table.is_cuda or not table.is_contiguous() or table.dim() != 4
+                                  or table.size(0) != 2):
+            raise TypeError("set_beam_tiles takes a contiguous int32 [2, n_utt, W, NT] tensor on the GPU, or None")
+        _lib.check(self.lib.dh_engine_set_beam_tiles(self.handle, None if table is None else table.data_ptr(),
+                                                     0 if table is None else table.size(3)))
+        self._beam_tiles = table
+
     def decode_beam(self, state, prompt_len: torch.Tensor, n_steps: int, eos_id: Optional[int], first_step: int) -> None:
         """n_steps beam steps of state.n_utt utterances x state.W beams, the first one step number first_step >= 1
         (dh_engine_decode_beam; `state` is a dualhyp_amd.beam.BeamState, prompt_len int32 [n_utt] on the GPU)."""
@@ -518,6 +536,8 @@ class _Engine:
         assert mask is None or mask.size(0) == state.n_utt, "the token mask has one row per utterance"
         hist = getattr(self, "_beam_history", None)
         assert hist is None or tuple(hist.shape) == (2, state.n_utt, state.W, state.max_new), "the history planes are another state's"
+        tiles = getattr(self, "_beam_tiles", None)
+        assert tiles is None or tuple(tiles.shape[:3]) == (2, state.n_utt, state.W), "the tile table is another state's"
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dh_engine_decode_beam(
                 self.handle, C.byref(state.c_struct()), prompt_len.data_ptr(), state.n_utt, state.W, state.max_new, int(n_steps),

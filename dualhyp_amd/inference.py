@@ -87,7 +87,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
     order ('key' is its selection key: the score, or the mbr risk), and 'selected', the chosen index; 'logprobs', 'finish_reason' and
     the alternatives, where asked for, are the chosen candidate's.
     A generate_fn with a true attribute `shared_prompt` (--share_prompt_kv: its decode steps read an utterance's prompt tiles once for
-    its candidates or beams) gives every record 'shared_prompt': true.
+    its candidates or beams) gives every record 'shared_prompt': true; one with an attribute `beam_kv` of "table" (--beam_kv table:
+    the beams' closed KV tiles are read where they were written) gives every record 'beam_kv': "table".
     Returns corpus metrics on every rank and predictions on
     rank 0."""
     mine = shard_indices(len(examples), rank, world)
@@ -148,6 +149,8 @@ def run_inference(generate_fn: Callable[[List[torch.Tensor]], List[torch.Tensor]
                 preds[i]["activations"] = str(generate_fn.activations)
             if getattr(generate_fn, "shared_prompt", False):
                 preds[i]["shared_prompt"] = True
+            if getattr(generate_fn, "beam_kv", "copy") == "table":
+                preds[i]["beam_kv"] = "table"
             if getattr(generate_fn, "bias", None):
                 from .bias import bias_hits
                 preds[i]["bias"] = dict(generate_fn.bias)
@@ -403,6 +406,9 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     # --share_prompt_kv: likewise
     shared_kv = bool(getattr(args, "share_prompt_kv", False))
     shkw = dict(shared_prompt=True) if shared_kv else {}
+    # --beam_kv table: likewise
+    beam_kv = getattr(args, "beam_kv", "copy") or "copy"
+    bkw = dict(kv="table") if beam_kv == "table" else {}
     stop = stop_from_args(args, tokenizer, model.config.padded_vocab_size, model.transformer.wte.weight.device)
     skw = dict(stop=stop, return_state=True) if stop is not None else {}       # the reasons are read from the state's done flags
     from .penalty import record as penalty_record
@@ -433,7 +439,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
             hyps = beam_search_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_beams=beams, eos_id=eos,
                                      length_penalty=float(getattr(args, "length_penalty", 1.0)),
                                      prefill_batch=max(1, min(args.prefill_batch, args.decode_batch)), token_mask=mask,
-                                     no_repeat_ngram=ngram, stop=stop, **hkw, **shkw)
+                                     no_repeat_ngram=ngram, stop=stop, **hkw, **shkw, **bkw)
             return {"beams": hyps, "logprobs": want_lp}
         if n_samples > 1:  # --decode_batch counts decode rows: N per utterance
             cands = sample_batch(model, [p.to(dev) for p in prompts], args.max_new_tokens, num_samples=n_samples, eos_id=eos,
@@ -471,6 +477,7 @@ def result(adapter_path: str, model, tokenizer, args, rank: int = 0, world: int 
     gen.activations = getattr(model, "activation_format", "fp8")
     gen.bias, gen.bias_entries = bias_rec, bias_entries
     gen.shared_prompt = shared_kv
+    gen.beam_kv = beam_kv
     out = run_inference(gen, examples, tokenizer.decode, batch_size=max(len(examples), 1) if continuous else max(1, args.decode_batch // beams // n_samples), rank=rank, world=world, eos_id=eos,
                         device="cpu" if os.environ.get("DUALHYP_DP_REHEARSAL") == "1" or world == 1 else model.transformer.wte.weight.device)
     out["adapter_path"] = adapter_path
@@ -568,6 +575,11 @@ def build_parser():
                         "no_repeat_ngram and ngram_bans of the best hypothesis) and the stop sequences of --stop_file run under beam "
                         "search; penalties and --bias_file stay refused there: they would change what a candidate's rank means.  Default "
                         "host: the steps, and the refusals, it always had")
+    p.add_argument("--beam_kv", choices=("copy", "table"), default="copy",
+                   help="with --num_beams W > 1 and --share_prompt_kv: table keeps, per beam and 32-key tile, the sibling KV slot that "
+                        "holds the tile; a beam step's attention reads every closed tile where it was written and the re-parenting copies "
+                        "one open tile instead of every tile with a generated key (the same keys, so the same predictions); every "
+                        "record gains beam_kv: table.  Default copy: the launches it always made")
     p.add_argument("--num_samples", type=int, default=1, metavar="N",
                    help="N in 2..8 (with --top_k other than 1): N sampled candidates per utterance from one prefill of its prompt "
                         "(sample_batch: the prompt's KV cache is forked into N decode slots by one launch), --decode_batch // N "
@@ -711,6 +723,12 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         if fp8_path:
             p.error(f"--share_prompt_kv does not go with --quantize {args.quantize}: an fp8 engine's step does not run the streaming "
                     "layers that launch the shared-prompt attention kernel")
+    if args.beam_kv == "table":                             # beam_search_batch refuses both too; here nothing has been loaded yet
+        if args.num_beams < 2:
+            p.error("--beam_kv table goes with --num_beams W > 1: the table names, per tile, the sibling beam whose KV slot holds it")
+        if not args.share_prompt_kv:
+            p.error("--beam_kv table goes with --share_prompt_kv: the beams' private tiles are read through the table inside the "
+                    "shared-prompt attention kernel")
     if not 0 <= args.no_repeat_ngram <= 8:
         p.error(f"--no_repeat_ngram {args.no_repeat_ngram}: N is 0 (off) or 1..8")
     dev_hist = args.beam_history == "device"                # the beams' histories on the device lift the next two refusals

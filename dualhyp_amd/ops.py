@@ -979,10 +979,15 @@ def check_shared_rows(n_rows: int, group_rows, name: str = "attn_decode_shared")
 def attn_decode_shared(qkv32: torch.Tensor, qkv_dim: int, lora_b: Optional[torch.Tensor], lora_scale: float,
                        splits: Tuple[int, int], cos: torch.Tensor, sin: torch.Tensor, seq_slot: torch.Tensor,
                        kv_len: torch.Tensor, k_cache: torch.Tensor, vT_cache: torch.Tensor, n_head: int, group_rows: int,
-                       prompt_len: torch.Tensor, pairs: bool = True) -> torch.Tensor:
+                       prompt_len: torch.Tensor, pairs: bool = True, tile_tab: Optional[torch.Tensor] = None,
+                       step_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`attn_decode_fused` over rows that share prompts (include/dualhyp_hip.h, "Shared-prompt attention"): rows u * group_rows + j
     are the candidates or beams of utterance u, prompt_len int32 [n_seq / group_rows] on the GPU; the whole prompt tiles are read
-    once per block, from the slot of the utterance's row 0.  Same bits and caches as attn_decode_fused; dh_attn_decode_shared_bf16."""
+    once per block, from the slot of the utterance's row 0.  Same bits and caches as attn_decode_fused; dh_attn_decode_shared_bf16.
+    tile_tab (None: the call above, unchanged): the rows' tile table, contiguous int32 [2, n_seq, NT] on the GPU ("Beam KV tile table"
+    of the header) — private tile prompt_len[u] // 32 + j of row r is read from the slot of the sibling that entry [plane, r, j] names;
+    step_dev (a one-element int32 tensor, the device step counter t) selects plane (t - 1) & 1, None plane 0;
+    dh_attn_decode_shared_tab_bf16."""
     k = _Keep()
     n_part, n_seq, ld = qkv32.shape
     N = check_shared_rows(n_seq, group_rows)
@@ -992,11 +997,62 @@ def attn_decode_shared(qkv32: torch.Tensor, qkv_dim: int, lora_b: Optional[torch
     n_groups, s_max, hs = k_cache.size(1), k_cache.size(2), k_cache.size(3)
     y = torch.empty((n_seq, n_head * hs), dtype=torch.bfloat16, device=qkv32.device)
     i32 = torch.int32
+    if tile_tab is not None:
+        if (not isinstance(tile_tab, torch.Tensor) or tile_tab.dtype != i32 or tile_tab.dim() != 3 or tile_tab.size(0) != 2
+                or tile_tab.size(1) != n_seq or not tile_tab.is_contiguous() or tile_tab.device != qkv32.device):
+            raise ValueError(f"attn_decode_shared: tile_tab is a contiguous int32 tensor [2, {n_seq}, NT] on {qkv32.device}")
+        if step_dev is not None and (step_dev.dtype != i32 or step_dev.numel() != 1 or step_dev.device != qkv32.device):
+            raise ValueError("attn_decode_shared: step_dev is a one-element int32 tensor on the GPU")
+        check(_lib.load().dh_attn_decode_shared_tab_bf16(_p(qkv32), n_part, int(pairs), n_seq, qkv_dim, ld - qkv_dim, _p(lora_b),
+                                                         float(lora_scale), splits[0], splits[1], k(cos), k(sin),
+                                                         k(seq_slot, i32), k(kv_len, i32), _p(k_cache), _p(vT_cache),
+                                                         _p(y), n_head, n_groups, hs, s_max, N, k(prompt_len, i32), _p(tile_tab),
+                                                         tile_tab.size(2), _p(step_dev), _stream()))
+        return y
+    if step_dev is not None:
+        raise ValueError("attn_decode_shared: step_dev selects a plane of tile_tab, which is None")
     check(_lib.load().dh_attn_decode_shared_bf16(_p(qkv32), n_part, int(pairs), n_seq, qkv_dim, ld - qkv_dim, _p(lora_b),
                                                  float(lora_scale), splits[0], splits[1], k(cos), k(sin),
                                                  k(seq_slot, i32), k(kv_len, i32), _p(k_cache), _p(vT_cache),
                                                  _p(y), n_head, n_groups, hs, s_max, N, k(prompt_len, i32), _stream()))
     return y
+
+
+def beam_retile(k_cache: torch.Tensor, vT_cache: torch.Tensor, tile_tab: torch.Tensor, beam_parent: torch.Tensor,
+                n_steps: torch.Tensor, prompt_len: torch.Tensor, step: int, scratch: Optional[torch.Tensor] = None) -> None:
+    """The KV step of a beam call under a tile table, alone and in place ("Beam KV tile table" of the header; dh_beam_retile): behind
+    the selection of `step` (1 .. max_new - 1), plane step & 1 of tile_tab (int32 [2, n_utt * W, NT]) receives the rows' entries and
+    the open tile of every row that continues another beam is copied from its parent's slot.  k_cache [n_utt * W, G, s_max, hs] and
+    vT_cache [n_utt * W, G, hs, s_max] are one layer's pair as stored; beam_parent int32 [n_utt, max_new, W], n_steps and prompt_len
+    int32 [n_utt], all on the GPU.  scratch: bf16, at least rows * 2 * G * hs * 32 elements (made here when None)."""
+    i32 = torch.int32
+    dev = k_cache.device
+    if beam_parent.dim() != 3 or beam_parent.dtype != i32 or not beam_parent.is_contiguous():
+        raise ValueError("beam_retile: beam_parent is a contiguous int32 tensor [n_utt, max_new, W]")
+    n_utt, max_new, W = beam_parent.shape
+    rows = n_utt * W
+    if (k_cache.dim() != 4 or k_cache.dtype != torch.bfloat16 or k_cache.size(0) != rows or not k_cache.is_contiguous()
+            or vT_cache.dtype != torch.bfloat16 or not vT_cache.is_contiguous()):
+        raise ValueError(f"beam_retile: k_cache is a contiguous bf16 [{rows}, G, s_max, hs] and vT_cache its [{rows}, G, hs, s_max]")
+    G, s_max, hs = k_cache.size(1), k_cache.size(2), k_cache.size(3)
+    if tuple(vT_cache.shape) != (rows, G, hs, s_max):
+        raise ValueError(f"beam_retile: vT_cache must be {(rows, G, hs, s_max)}, got {tuple(vT_cache.shape)}")
+    if (tile_tab.dtype != i32 or tile_tab.dim() != 3 or tile_tab.size(0) != 2 or tile_tab.size(1) != rows
+            or not tile_tab.is_contiguous()):
+        raise ValueError(f"beam_retile: tile_tab is a contiguous int32 tensor [2, {rows}, NT]")
+    for name, t in (("n_steps", n_steps), ("prompt_len", prompt_len)):
+        if t.dtype != i32 or t.dim() != 1 or t.numel() != n_utt or not t.is_contiguous():
+            raise ValueError(f"beam_retile: {name} is a contiguous int32 tensor of {n_utt} utterances")
+    for t in (vT_cache, tile_tab, beam_parent, n_steps, prompt_len):
+        if t.device != dev:
+            raise ValueError("beam_retile: every tensor lives on the caches' device")
+    need = rows * 2 * G * hs * 32
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.bfloat16, device=dev)
+    elif scratch.dtype != torch.bfloat16 or scratch.numel() < need or not scratch.is_contiguous() or scratch.device != dev:
+        raise ValueError(f"beam_retile: scratch holds at least {need} contiguous bf16 elements on {dev}")
+    check(_lib.load().dh_beam_retile(_p(k_cache), _p(vT_cache), _p(scratch), _p(tile_tab), tile_tab.size(2), _p(beam_parent), _p(n_steps),
+                                     _p(prompt_len), n_utt, W, max_new, int(step), None, G, hs, s_max, _stream()))
 
 
 def kcache_to_plain(kc: torch.Tensor) -> torch.Tensor:

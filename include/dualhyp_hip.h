@@ -37,7 +37,8 @@ typedef uint16_t dh_bf16;
  * dh_engine_set_penalties (penalties); dh_sample_bf16_bias, dh_sample_rows_bf16_bias and dh_engine_set_bias (contextual biasing);
  * dh_beam_select_bf16_hist and dh_engine_set_beam_history (beam histories); dh_sample_bf16_automaton, dh_sample_rows_bf16_automaton and
  * dh_engine_set_automaton (automaton constraints); dh_attn_decode_shared_bf16, dh_attn_shared_launch_count and
- * dh_engine_set_shared_prompt (shared-prompt attention). */
+ * dh_engine_set_shared_prompt (shared-prompt attention); dh_attn_decode_shared_tab_bf16, dh_beam_retile, dh_engine_set_beam_tiles and
+ * dh_engine_reserve_beam_tiles (beam KV tile table). */
 #define DH_ABI_VERSION 6
 
 int dh_abi_version(void);
@@ -262,6 +263,50 @@ int dh_attn_decode_shared_bf16(const float* qkv32, int n_part, int pairs, int n_
                                const int32_t* prompt_len, void* stream);
 /* Test hook: launches of the shared-prompt attention kernel this process has issued or captured so far. */
 int64_t dh_attn_shared_launch_count(void);
+
+/* ------------------------------------------------------------------ Beam KV tile table
+ * An opt-in second way to keep the beams' KV cache ("Beam search" below; dh_engine_set_beam_tiles).  The W beams of an utterance
+ * advance in lockstep, so 32-key tile j of every one of its W slots is written during the same steps, and once the position has left
+ * a tile no slot's copy of it is written again: a CLOSED tile is immutable.  A hypothesis therefore does not need its closed tiles in
+ * its own slot, only to know which sibling's slot holds each; the one OPEN tile, the tile its next key goes into, is private.
+ *   Layout.  Utterance u has the W rows r = u * W + w in slots r; P = prompt_len[u], tile0 = P >> 5 (the first tile that is not a
+ *     whole prompt tile), NT = min((max_new_tokens + 30) / 32 + 1, s_max / 32) <= DH_MAX_BEAM_TILES tiles that generated keys can
+ *     span.  The table is two int32 planes [2][n_utt * W][NT], the caller's, as the history planes are.  Entry [plane][r][j] is a
+ *     beam index 0 .. W-1: the sibling whose slot holds tile tile0 + j of row r's hypothesis.  Entries are clamped to 0 .. W-1 before
+ *     use.  Both planes start as the identity, [r][j] = w.
+ *   Attention of step t (the device step counter reads t): private tile tt >= tile0 of row r is loaded from slot
+ *     u * W + tab[(t - 1) & 1][r][tt - tile0]; a tile index at or beyond NT reads the row's own slot.  The shared tiles and the append
+ *     into the row's own slot are those of dh_attn_decode_shared_bf16.
+ *   Update behind the selection of step t, for the utterances that took it (n_steps[u] == t + 1): cur = ((P + t - 1) >> 5) - tile0,
+ *     nxt = ((P + t) >> 5) - tile0, parent = beam_parent[u, t, w], new = plane t & 1, old = plane (t - 1) & 1:
+ *       new[r][j] = old[u * W + parent][j]           for j < cur,
+ *       new[r][cur] = w if nxt == cur (the tile is still open), else parent (it just closed),
+ *       new[r][j] = w                                for j > cur;
+ *     when nxt == cur and parent != w, tile tile0 + cur of the parent's slot is copied into the row's slot — every layer, K and V^T,
+ *     every group — through a scratch in two launches, so no launch reads what it writes and any parent map is right.  When the tile
+ *     just closed nothing is copied.  An utterance that did not take the step copies its old rows to new, so its frozen rows read the
+ *     same entries at either parity.  So does an utterance whose prompt_len is below 1 (outside the definition: the re-parenting
+ *     copy skips it too), and a parent outside 0 .. W-1 is taken as the row itself.  Invariant: at every step the open tile's entry
+ *     is the row itself.
+ *   DEFINITION: the keys and values a row's attention sees are those its own slot would hold under the re-parenting copy, so a beam
+ *     call under a table records the tokens, parents, log-probabilities, scores and pool of the call without one, bit for bit.
+ * dh_attn_decode_shared_tab_bf16: dh_attn_decode_shared_bf16 with the rows' private tiles read through tile_tab (device int32
+ * [2][n_seq][tab_ld], tab_ld = NT, 1 .. DH_MAX_BEAM_TILES), plane (*step_dev - 1) & 1; a null step_dev means plane 0.  group_rows is
+ * W.  Refused: a null table, tab_ld outside 1 .. DH_MAX_BEAM_TILES, and what dh_attn_decode_shared_bf16 refuses.
+ * dh_beam_retile: the update alone, over one K / V^T cache pair ([n_utt * W slots][n_groups][s_max * hs] each, the engine's layout of
+ * one layer): step (1 .. max_new_tokens - 1), or step_dev non-null: read from the device; scratch: n_utt * W x 2 x n_groups x hs * 32
+ * elements.  Two launches.  Added under ABI 6. */
+#define DH_MAX_BEAM_TILES 64
+int dh_attn_decode_shared_tab_bf16(const float* qkv32, int n_part, int pairs, int n_seq, int qkv_dim, int n_ext,
+                                   const dh_bf16* lora_b, float lora_scale, int split0, int split1,
+                                   const dh_bf16* cos, const dh_bf16* sin, const int32_t* seq_slot,
+                                   const int32_t* kv_len, dh_bf16* k_cache, dh_bf16* vT_cache,
+                                   dh_bf16* y, int n_head, int n_groups, int hs, int s_max, int group_rows,
+                                   const int32_t* prompt_len, const int32_t* tile_tab, int tab_ld, const int32_t* step_dev,
+                                   void* stream);
+int dh_beam_retile(dh_bf16* k_cache, dh_bf16* vT_cache, dh_bf16* scratch, int32_t* tile_tab, int n_tiles,
+                   const int32_t* beam_parent, const int32_t* n_steps, const int32_t* prompt_len, int n_utt, int W,
+                   int max_new_tokens, int step, const int32_t* step_dev, int n_groups, int hs, int s_max, void* stream);
 
 /* ------------------------------------------------------------------ LoRA fine-tune backward
  * finetune/ger.py:278-285 `fabric.backward(loss / accum)` for the frozen-base / LoRA-only case: the dX
@@ -1352,6 +1397,18 @@ int dh_engine_set_automaton(dh_engine* e, const dh_automaton_spec* automaton, co
  * dh_engine_decode_rows (a row list names any sequence in any slot), a row count that is no multiple of group_rows or above the
  * streaming step's 2048, and a beam call whose W is not group_rows. */
 int dh_engine_set_shared_prompt(dh_engine* e, int group_rows, const int32_t* d_prompt_len);
+/* The tile table ("Beam KV tile table" above; null = off, the default) for later dh_engine_decode_beam calls: tab, device int32
+ * [2][n_utt * W][n_tiles], both planes the identity, n_tiles = min((max_new_tokens + 30) / 32 + 1, s_max / 32) of the calls.  While
+ * set, a beam step's attention is dh_attn_decode_shared_tab_bf16 and its re-parenting is the table update with the one-tile copy;
+ * every other launch of the step is unchanged.  The pointer and n_tiles are part of a beam step's key, as the history planes are: with
+ * it unset a beam call runs the graphs it always ran.  While set, dh_engine_decode_beam needs dh_engine_set_shared_prompt with
+ * group_rows = W and dh_engine_reserve_beam_tiles, and refuses otherwise with the reason.  Refused here: n_tiles outside
+ * 1 .. DH_MAX_BEAM_TILES with a table; an fp8 or MXFP4 engine and an fp8 KV cache.  The caller keeps the planes alive while set. */
+int dh_engine_set_beam_tiles(dh_engine* e, int32_t* tab, int n_tiles);
+/* dh_engine_reserve_beams for calls under a tile table: the candidates' workspace and a scratch of ONE tile per (row, layer's K and
+ * V^T, group) — max_batch x 2 L x G x hs * 32 elements, whatever max_new_tokens is (it is checked: its tiles must not exceed
+ * DH_MAX_BEAM_TILES).  W = 1 needs no scratch.  Growing drops the captured steps; on failure the engine keeps what it had. */
+int dh_engine_reserve_beam_tiles(dh_engine* e, int W, int max_new_tokens);
 /* Test hook, like dh_engine_read: the number of captured steps kept for n_draft drafts (0: dh_engine_decode /
  * dh_engine_decode_rows; -1: all).  Nothing on the serving path calls it. */
 int dh_engine_graph_count(const dh_engine* e, int n_draft);

@@ -16,9 +16,18 @@ that with two stop sequences), each timed in alternation with the plain call, an
 histories (history_arms below says which figures are subtraction remainders).  Without the flag the tool runs what it always ran, so
 the same command line times the plain beam step on another build of the library (DUALHYP_HIP_LIB) or another checkout.
 
+--kv table runs the tile-table arms INSTEAD (beam_search_batch(shared_prompt=True, kv="table"); include/dualhyp_hip.h, "Beam KV tile
+table"): per W, utterance count and --max_new_tokens, three arms in alternation — "table"; "copy", this build's
+beam_search_batch(shared_prompt=True); and, with --parent_lib, "parent", the same call on a second model whose engine is bound to
+another build of the library (a build of the parent commit) — and, apart, this build's default call beside the parent's.  Reported:
+ms per step of every arm (median and min .. max of --repeats), the (row, tile) pairs either scheme copied, the two scratches' bytes,
+and the event time of the table's two copy launches alone (ops.beam_retile over one K / V^T pair with n_groups = layers x groups, the
+engine's grid and bytes, at the call's middle step and its recorded parents).
+
 The parent never touches the GPU and prints ONE JSON line.
 
     python tools/bench_beam.py [--beams 1 2 4] [--history] [--out profiles/beam_search.json]
+    python tools/bench_beam.py --kv table --beams 2 4 --max_new_tokens 64 [--parent_lib OTHER.so] [--out profiles/beam_kv_table.json]
 """
 import argparse
 import json
@@ -43,6 +52,8 @@ ap.add_argument("--out", type=str, default="", help="write the line as a JSON fi
 ap.add_argument("--history", action="store_true",
                 help="also time the device-history arms (beam_search_batch(history='device')): histories alone, no_repeat_ngram = 3, and "
                      "that with two stop sequences, each beside the plain call; and the selection's two kernels with and without histories")
+ap.add_argument("--kv", choices=("copy", "table"), default="copy", help="table: the tile-table arms instead of the greedy comparison")
+ap.add_argument("--parent_lib", type=str, default="", help="--kv table: another build of libdualhyp_hip.so for the baseline arm")
 ap.add_argument("--worker", type=int, nargs=2, default=None, metavar=("W", "N"), help="(child) beams and utterances of this run")
 a = ap.parse_args()
 
@@ -127,6 +138,79 @@ def worker(W: int, n: int) -> None:
                           reserve_beams_bytes=int(scratch), engine_bytes=int(bytes_with), **hist_fields)), flush=True)
 
 
+def kv_worker(W: int, n: int) -> None:
+    """--kv table: the arms of one (W, utterances, max_new_tokens) in alternation"""
+    import ctypes as C
+    import torch
+    from dualhyp_amd import GPT, Config, GER_LORA, _lib, beam_search_batch, ops
+    from dualhyp_amd.beam import beam_tiles
+    from dualhyp_amd.synth import synth_state_dict, synth_prompts
+    dev = "cuda:0"
+    cfg = Config.from_name("tiny-llama-1.1b-chat", **{**GER_LORA, "dropout": 0.0})
+    sd = synth_state_dict(cfg, seed=1337, device=dev, embed_scale=50.0, head_tie=1.0)
+
+    def model():
+        m = GPT(cfg).to(device=dev, dtype=torch.bfloat16)
+        m.load_state_dict(sd, strict=True)
+        m.eval()
+        return m
+
+    rows, new, V = n * W, a.max_new_tokens, cfg.padded_vocab_size
+    corpus = [p.to(dev) for p in synth_prompts(n, a.prompt_len, V, seed=7)]
+    need = (rows, a.prompt_len + new, max(rows, a.prefill_batch * a.prompt_len))
+    m = model()
+    call = lambda mm, tm, **kw: beam_search_batch(mm, corpus, new, num_beams=W, prefill_batch=a.prefill_batch, timing=tm, **kw)
+    arms = dict(table=lambda tm=None: call(m, tm, shared_prompt=True, kv="table"), copy=lambda tm=None: call(m, tm, shared_prompt=True),
+                default=lambda tm=None: call(m, tm))
+    if a.parent_lib:      # a second model whose engine is created, and so bound, while the other build stands in for this one's
+        other = C.CDLL(a.parent_lib)
+        for name, sig in _lib.SIGNATURES.items():
+            if hasattr(other, name):
+                getattr(other, name).restype, getattr(other, name).argtypes = sig
+        m0 = model()
+        _lib.load()
+        mine, _lib._lib = _lib._lib, other
+        try:
+            m0.engine(*need, exact=rows > a.prefill_batch)
+        finally:
+            _lib._lib = mine
+        assert m0._engine.lib is other
+        arms["parent"] = lambda tm=None: call(m0, tm, shared_prompt=True)
+        arms["parent_default"] = lambda tm=None: call(m0, tm)
+    for f in arms.values():
+        f()                                                   # allocation, graph capture
+    steps = new - 1
+    times = {k: [] for k in arms}
+    last = {}
+    for _ in range(a.repeats):
+        for k, f in arms.items():
+            tm = {}
+            f(tm)
+            times[k].append(tm["decode_ms"] / steps)
+            last[k] = tm
+    stat = lambda xs: dict(median=round(statistics.median(xs), 4), min=round(min(xs), 4), max=round(max(xs), 4))
+    eng = m._engine
+    L, G, hs = cfg.n_layer, cfg.n_query_groups, cfg.head_size
+    NT = beam_tiles(new, eng.s_max)
+    # the table's two copy launches alone: one K / V^T pair with n_groups = L * G is the engine's grid and the engine's bytes
+    _, st = beam_search_batch(m, corpus, new, num_beams=W, prefill_batch=a.prefill_batch, shared_prompt=True, kv="table", return_state=True)
+    S = -(-(a.prompt_len + new + 1) // 32) * 32
+    kc = torch.zeros((rows, L * G, S, hs), dtype=torch.bfloat16, device=dev)
+    vt = torch.zeros((rows, L * G, hs, S), dtype=torch.bfloat16, device=dev)
+    scratch = torch.empty(rows * 2 * L * G * hs * 32, dtype=torch.bfloat16, device=dev)
+    tab = st["beam"].tile_table(NT).view(2, rows, NT).clone()
+    t_mid = next(t for t in range(new // 2, new) if (a.prompt_len + t) >> 5 == (a.prompt_len + t - 1) >> 5)      # a step whose tile stays open
+    n_steps = torch.full((n,), t_mid + 1, dtype=torch.int32, device=dev)
+    retile_us = event_us(lambda: ops.beam_retile(kc, vt, tab, st["beam"].beam_parent, n_steps, st["prompt_len"], t_mid, scratch=scratch))
+    moved_mid = sum(p != w for u in range(n) for w, p in enumerate(st["host"]["beam_parent"][u][t_mid]))
+    print(json.dumps(dict(W=W, utterances=n, rows=rows, steps=steps, max_new_tokens=new, n_tiles=NT,
+                          ms_per_step={k: stat(v) for k, v in times.items()},
+                          copied_rows=last["table"]["beam_copied_rows"], step_rows=last["table"]["beam_step_rows"],
+                          copied_tiles_table=last["table"]["beam_copied_tiles"], copied_tiles_copy=last["copy"]["beam_copied_tiles"],
+                          retile_two_launches_us=round(retile_us, 1), retile_step=t_mid, retile_rows_moved=moved_mid,
+                          scratch_bytes_table=rows * 2 * L * G * hs * 32 * 2, scratch_bytes_copy=rows * 2 * L * G * hs * 32 * 2 * NT)), flush=True)
+
+
 def history_arms(m, prompts, W, n, new, V, logits, plain):
     """--history: the whole step under device histories (the plain call repeated beside each arm, alternating), and the selection's
     kernels alone on the step's rows at step new // 2.  merge_us is beam_select minus token_top_logprobs at K = 2 W, and
@@ -189,15 +273,19 @@ def history_arms(m, prompts, W, n, new, V, logits, plain):
 
 
 if a.worker is not None:
-    worker(*a.worker)
+    (kv_worker if a.kv == "table" else worker)(*a.worker)
 else:
     line = dict(tool="bench_beam", prompt_len=a.prompt_len, max_new_tokens=a.max_new_tokens, repeats=a.repeats, runs=[])
+    if a.kv != "copy":
+        line.update(kv=a.kv, parent_lib=bool(a.parent_lib))
     for W in a.beams:
         for n in sorted({a.utterances, max(1, a.rows // W)}):
             cmd = [sys.executable, str(Path(__file__).resolve()), "--worker", str(W), str(n)]
             for k in ("prompt_len", "max_new_tokens", "prefill_batch", "repeats"):
                 cmd += [f"--{k}", str(getattr(a, k))]
             cmd += ["--history"] if a.history else []
+            cmd += ["--kv", a.kv] if a.kv != "copy" else []
+            cmd += ["--parent_lib", str(Path(a.parent_lib).resolve())] if a.parent_lib else []
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=a.step_timeout)      # a run that fails ends the tool
             if r.returncode != 0:
                 sys.exit(f"run W={W} utterances={n} failed with {r.returncode}:\n{r.stdout[-1000:]}{r.stderr[-3000:]}")
